@@ -10,10 +10,14 @@ a camera that moves every step along a fixed orbit, with the splats already resi
            --master-port P bench.py --gpus N --steps K --warmup W
 
 Rank 0 prints ONE JSON line.  The per-stage device times come from hipEvents that the library
-records on its own stream inside the timed region (GS_FLAG_TIMING).  After the timed region (N = 1) the
-last camera is rendered again in the other blend mode and with the reference's binning (self_check), and
-the CPU oracle renders ONE whole frame of the same scene and camera on the host cores: that is both the
-cpu_baseline (a reported baseline, not a target) and the check of the frame the bench timed.
+records on its own stream inside the timed region (GS_FLAG_TIMING).  A plain run sets up, warms up, times
+--steps frames and prints the line; --dump-outputs DIR also writes the last timed frame there.
+
+With --full, after the timed region (N = 1) the same steps are repeated one frame at a time (where `stages`
+and `roofline` come from when frames overlap in the timed region), the last camera is rendered again in the
+other blend mode and with the reference's binning (self_check), and the CPU oracle renders ONE whole frame
+of the same scene and camera on the host cores: that is both the cpu_baseline (a reported baseline, not a
+target) and the check of the frame the bench timed.  N > 1: the assembled frame is checked likewise.
 """
 import argparse
 import json
@@ -261,6 +265,25 @@ def copy_probe(dev, nbytes=512 << 20, iters=10):
             "nominal_peak_GBps": HBM_PEAK_GBS}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, frame):
+    """--dump-outputs: the frame of the last timed step, as float32.  A frame whose float32 copy exceeds DUMP_LIMIT_BYTES (4K and
+    above) is cut to a fixed sample of its pixels (seed 0, the same for every run of the same size); frame_pixel_index.npy holds
+    their row-major indices."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    px = frame.reshape(-1, frame.shape[-1]).astype(np.float32)
+    if px.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(out_dir, "frame_rgba8.npy"), px.reshape(frame.shape))
+        return
+    k = DUMP_LIMIT_BYTES // 32  # pixels: 16 bytes of values + 8 of index each, within the budget
+    idx = np.sort(np.random.default_rng(0).choice(px.shape[0], k, replace=False))
+    np.save(os.path.join(out_dir, "frame_rgba8.npy"), px[idx])
+    np.save(os.path.join(out_dir, "frame_pixel_index.npy"), idx.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -304,7 +327,14 @@ def main():
                     help="render this 3DGS .ply (native loader) instead of the synthetic scene; also taken from $GS_PLY (SURVEY.md 8d)")
     ap.add_argument("--proj-chunks", type=int, default=0, help="GS_OPT_PROJ_CHUNKS (tuning): cull chunks per workgroup of the tight projection")
     ap.add_argument("--lib", default="", help="A/B only: another build of libgsplat_hip.so (sets $GSPLAT_LIB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: per-stage times one frame at a time (stages, roofline), "
+                         "the frame checks, the other blend mode, the reference-binning leg, the CPU baseline and the copy probe")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the frame of the last timed step to DIR/frame_rgba8.npy (float32 [H, W, 4], 0..255)")
     args = ap.parse_args()
+    if not args.full:  # a plain run measures the headline figure only
+        args.no_cpu = args.no_verify = True
     if args.lib:
         os.environ["GSPLAT_LIB"] = os.path.abspath(args.lib)
 
@@ -475,9 +505,11 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     st = r.stats()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, xch.image.cpu().numpy() if multi else r.read_rgba8())
 
     slab_strict = None
-    if multi and rank == 0 and not args.no_timing:
+    if multi and rank == 0 and not args.no_timing and args.full:
         # outside the timed region: rank 0's slab strictly one frame after the other on a context with per-stage hipEvents (no
         # exchange): where `stages` and `roofline` of an N > 1 line come from
         rt = make_slab_renderer(None, owner, flags)
@@ -565,14 +597,17 @@ def main():
             # region, strictly one frame after the other: its per-stage times (and the frames/s of that discipline) are what
             # `stages` and `roofline` are computed from; the overlapped brackets are kept as `stages_overlapped_us`.
             line["stages_overlapped_us"] = {k_: round(v, 2) for k_, v in st["stage_us_mean"].items()}
-            line["one_frame_in_flight"], stq = flight_pass(r, _abi, uniforms, args, 1)
-            r.set_option(_abi.GS_OPT_FRAMES_IN_FLIGHT, st["frames_in_flight"])
-            stage_source = "the same steps strictly one frame after the other (one_frame_in_flight), outside the timed region"
+            if args.full:
+                line["one_frame_in_flight"], stq = flight_pass(r, _abi, uniforms, args, 1)
+                r.set_option(_abi.GS_OPT_FRAMES_IN_FLIGHT, st["frames_in_flight"])
+                stage_source = "the same steps strictly one frame after the other (one_frame_in_flight), outside the timed region"
+            else:
+                stq = None  # kernel durations need that pass of their own: --full
         if slab_strict is not None:
             line["one_frame_in_flight"], stq = slab_strict
             line["one_frame_in_flight"]["note"] = "rank 0's slab alone, no exchange"
             stage_source = "rank 0's slab strictly one frame after the other, outside the timed region"
-        if not args.no_timing and stq["frames_timed"]:
+        if not args.no_timing and stq is not None and stq["frames_timed"]:
             st_main, st = st, stq
             ab = algorithmic_bytes(st, W, H, T)
             stages = {}

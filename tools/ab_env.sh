@@ -5,7 +5,7 @@ OUT=gpurun_out/$TAG; mkdir -p $OUT
 i=0
 for e in "$@"; do
   i=$((i+1))
-  env $e timeout -k 10 300 python bench.py --no-cpu --no-verify --steps 100 --warmup 10 $ARGS > $OUT/e$i.json 2> $OUT/e$i.err || echo "variant $i failed"
+  env $e timeout -k 10 300 python bench.py --full --no-cpu --no-verify --steps 100 --warmup 10 $ARGS > $OUT/e$i.json 2> $OUT/e$i.err || echo "variant $i failed"
   python - <<PY
 import json
 try:

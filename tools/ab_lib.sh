@@ -6,7 +6,7 @@ i=0
 for lib in "$@"; do
   i=$((i+1))
   if [ -n "$lib" ]; then export GSPLAT_LIB=$PWD/gaussian-splatting-wgpu_amd/lib/variants/$lib.so; else unset GSPLAT_LIB; fi
-  timeout -k 10 300 python bench.py --no-cpu --no-verify --steps 100 --warmup 10 $ARGS > $OUT/l$i.json 2> $OUT/l$i.err || echo "variant $i failed"
+  timeout -k 10 300 python bench.py --full --no-cpu --no-verify --steps 100 --warmup 10 $ARGS > $OUT/l$i.json 2> $OUT/l$i.err || echo "variant $i failed"
   python - <<PY
 import json
 try:

@@ -1,12 +1,12 @@
 #!/bin/bash
-# GPU box: the -m gpu suite (with durations) and a default bench line.  Usage: tools/gpu_suite.sh <tag>
+# GPU box: the -m gpu suite (with durations) and a `bench.py --full` line.  Usage: tools/gpu_suite.sh <tag>
 TAG=${1:-run}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 timeout -k 10 900 python -m pytest tests -m gpu -x -q -s --durations=25 > $OUT/pytest.log 2>&1
 echo "pytest rc=$?" | tee -a $OUT/pytest.log
 tail -45 $OUT/pytest.log
-timeout -k 10 500 python bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 500 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 echo "bench rc=$?"
 tail -3 $OUT/bench.err
 python - <<PY

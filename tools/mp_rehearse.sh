@@ -3,7 +3,7 @@
 TAG=$1; N=$2; shift; shift
 OUT=gpurun_out/$TAG; mkdir -p $OUT
 timeout -k 10 420 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29600 + N)) \
-  bench.py --gpus $N --steps 60 --warmup 6 --backend gloo --single-device "$@" > $OUT/n$N.json 2> $OUT/n$N.err
+  bench.py --full --gpus $N --steps 60 --warmup 6 --backend gloo --single-device "$@" > $OUT/n$N.json 2> $OUT/n$N.err
 echo "N=$N rc=$?"
 tail -3 $OUT/n$N.err
 python - <<PY

@@ -4,12 +4,13 @@
 PROF=$(dirname "$0")/../gaussian-splatting-wgpu_amd/lib/libgsplat_hip_prof.so
 [ -f "$PROF" ] && export GSPLAT_LIB=$(cd "$(dirname "$PROF")" && pwd)/libgsplat_hip_prof.so
 ARGS=$1; shift
-mkdir -p gpurun_out
+J=$(mktemp)
 for v in "$@"; do
-  timeout -k 10 200 python bench.py --steps 60 --warmup 10 --no-cpu $ARGS --blend-ablation $v > gpurun_out/sweep.json 2>/dev/null || exit 1
-  python - "$v" <<'PY'
+  timeout -k 10 200 python bench.py --full --steps 60 --warmup 10 --no-cpu $ARGS --blend-ablation $v > "$J" 2>/dev/null || exit 1
+  python - "$v" "$J" <<'PY'
 import json, sys
-d = json.load(open("gpurun_out/sweep.json"))
+d = json.load(open(sys.argv[2]))
 print(sys.argv[1], round(d["value"], 1), {k: v["us"] for k, v in d["stages"].items()})
 PY
 done
+rm -f "$J"
