@@ -196,8 +196,9 @@ __global__ __launch_bounds__(TS* TS) void gs_blend_kernel(const uint4* __restric
                     const bool pd = (p1.x > 0.0f) && (p1.z > 0.0f) && (p1.x * p1.z - p1.y * p1.y > 0.0f);
                     float mag;
                     const float q = block_qmin(p1.x, p1.y, p1.z, dxlo, dxhi, dylo, dyhi, mag);
-                    rel = !pd || !(q > p0.z + 1.0e-5f * mag); // NaNs compare false -> relevant
-                    if (rel && pd && blend_tmax_cull(p1.x, p1.y, p1.z, sP2[buf][e0 + lane].w, dxlo, dxhi, dylo, dyhi, Tmax)) rel = false;
+                    const bool nocull = (dbg & 4u) != 0u; // GS_OPT_BLEND_ABLATION bit 2: both culls off, as in gs_blend_quad_kernel
+                    rel = nocull || !pd || !(q > p0.z + 1.0e-5f * mag); // NaNs compare false -> relevant
+                    if (rel && pd && !nocull && blend_tmax_cull(p1.x, p1.y, p1.z, sP2[buf][e0 + lane].w, dxlo, dxhi, dylo, dyhi, Tmax)) rel = false;
 #ifdef GS_PROFILING
                     if (dbg & 1u) rel = false; // staging + cull cost without the pixel loop
 #endif

@@ -54,7 +54,7 @@ def check_image(r, ref, exact_image, max_ill=0.005, report=None):
                        "rgba8_max_lsb": int(d8.max(initial=0))})
     assert err[~ill].max(initial=0.0) <= 1e-4, "fused blend deviates by %g" % err[~ill].max()
     assert ill.mean() <= max_ill, "too many ill-conditioned pixels: %g" % ill.mean()
-    assert err.max(initial=0.0) <= 0.05
+    assert err.max(initial=0.0) <= 4e-3, "fused blend deviates by %g on a flagged pixel" % err.max()  # the full-size frames' bound
     assert d8[~ill].max(initial=0) <= 1
 
 

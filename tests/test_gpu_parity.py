@@ -675,29 +675,35 @@ def test_blend_culls_change_no_bit():
     bounding box of the pixels that are not final yet, and Tmax (1 - alpha_lo) over that box must reach 1e-4.  Both tests are
     conservative, a final pixel ignores every entry and a live one skips what fails `T (1 - alpha) >= 1e-4` anyway: the frame with the
     culls (default) and without them (GS_OPT_BLEND_ABLATION 4) is the same frame, bit for bit, in BOTH blend modes -- on a scene deep
-    enough that most blocks saturate (hundreds of splats per pixel), with opaque and faint splats, at tiles 16 and 32."""
+    enough that most blocks saturate (hundreds of splats per pixel), with opaque and faint splats, in every blend kernel: the quad
+    kernel at tiles 16 and 32, the workgroup-per-tile kernel (ablation bit 3) at 16 and 32 and gs_blend_kernel<8>; with tight
+    binning (the quad kernel's MASKED walkers) and with the reference's binning (GS_OPT_TILE_CULL 0: MASKED=false).  The scenes aimed
+    at the culls' margins are in test_blend_culls.py."""
     from gsplat import _abi
     n, W, H = 400000, 256, 144
     s = scene(n).copy()
     rng = np.random.default_rng(11)
     idx = rng.integers(0, n, n // 5)
     s[idx, 12] = rng.choice([6.0, 2.0, -4.0, -5.4], idx.size).astype(np.float32)  # opacity logits: opaque ... just above 1/255
-    for ts in (16, 32):
+    for ts, abl in ((16, 0), (32, 0), (16, 8), (32, 8), (8, 0)):
         for flags in (0, _abi.GS_FLAG_EXACT_BLEND):
             r = _mk(s, W, H, ts, flags=flags)
-            for step in (2, 33):
-                u = _uniforms(W, H, step=step)
-                r.set_option(_abi.GS_OPT_BLEND_ABLATION, 0)
-                r.render_uniforms(u); r.wait()
-                ev_cull = r.stats()["num_evaluated"]
-                img = r.read_rgba8()
-                f32 = r.read_buffer(_abi.GS_BUF_RGB_F32, np.float32).copy()
-                r.set_option(_abi.GS_OPT_BLEND_ABLATION, 4)
-                r.render_uniforms(u); r.wait()
-                ev_all = r.stats()["num_evaluated"]
-                np.testing.assert_array_equal(r.read_buffer(_abi.GS_BUF_RGB_F32, np.float32).view(np.uint32), f32.view(np.uint32))
-                np.testing.assert_array_equal(r.read_rgba8(), img)
-                assert ev_cull < ev_all, (ts, flags, ev_cull, ev_all)  # the culls do remove work (10 % here; 75 % at config B, where most blocks saturate)
+            for tight in (1, 0):
+                r.set_option(_abi.GS_OPT_TILE_CULL, tight)
+                for step in (2, 33):
+                    u = _uniforms(W, H, step=step)
+                    r.set_option(_abi.GS_OPT_BLEND_ABLATION, abl)
+                    r.render_uniforms(u); r.wait()
+                    ev_cull = r.stats()["num_evaluated"]
+                    assert r.stats()["tight_binning"] == tight
+                    img = r.read_rgba8()
+                    f32 = r.read_buffer(_abi.GS_BUF_RGB_F32, np.float32).copy()
+                    r.set_option(_abi.GS_OPT_BLEND_ABLATION, abl | 4)
+                    r.render_uniforms(u); r.wait()
+                    ev_all = r.stats()["num_evaluated"]
+                    np.testing.assert_array_equal(r.read_buffer(_abi.GS_BUF_RGB_F32, np.float32).view(np.uint32), f32.view(np.uint32))
+                    np.testing.assert_array_equal(r.read_rgba8(), img)
+                    assert ev_cull < ev_all, (ts, abl, flags, tight, ev_cull, ev_all)  # the culls do remove work (10 % here; 75 % at config B, where most blocks saturate)
             r.destroy()
 
 
