@@ -151,6 +151,8 @@ struct gs_ctx {
     uint32_t* ranges = nullptr;
     uint32_t* rgba8 = nullptr;
     float* rgbf = nullptr;
+    float* alpha = nullptr;    // GS_FLAG_AUX_OUTPUTS: f32[H][slab_w] alpha and accumulated-depth planes, allocated in gs_create (a shadow
+    float* depth = nullptr;    // inherits the flag and owns its own), never moved afterwards
     uint32_t* d_pxb = nullptr; // assemble: pixel boundaries (device copy of pxb_host)
     uint32_t pxb_host[65] = {};
     uint32_t pxb_n = 0;
@@ -166,6 +168,7 @@ struct gs_ctx {
     GsPreprocessLaunch pre{};
     bool gkey_index = false, gkey_tight = false;
     void* gkey_ext = nullptr;
+    float *gkey_alpha = nullptr, *gkey_depth = nullptr; // the aux planes the capture writes (they never move: recorded so that a change cannot go unnoticed)
     uint64_t graph_frames = 0;
     // frame state
     bool have_frame = false, pending = false, last_debug = false;
@@ -289,6 +292,12 @@ GS_EXPORT int32_t gs_create(const gs_config* cfg, gs_ctx** out) {
     HIP_TRY(hipMalloc((void**)&c->rgba8, px * 4));
     HIP_TRY(hipMemset(c->rgba8, 0, px * 4));
     if (cfg->flags & GS_FLAG_F32_TAP) HIP_TRY(hipMalloc((void**)&c->rgbf, px * 12));
+    if (cfg->flags & GS_FLAG_AUX_OUTPUTS) { // eagerly, with the context: every blend of this context writes them
+        HIP_TRY(hipMalloc((void**)&c->alpha, px * 4));
+        HIP_TRY(hipMalloc((void**)&c->depth, px * 4));
+        HIP_TRY(hipMemset(c->alpha, 0, px * 4));
+        HIP_TRY(hipMemset(c->depth, 0, px * 4));
+    }
     HIP_TRY(hipHostMalloc((void**)&c->h_ctl, sizeof(GsControl), hipHostMallocDefault));
     memset(c->h_ctl, 0, sizeof(GsControl));
     HIP_TRY(hipMalloc((void**)&c->d_pxb, 65 * 4));
@@ -321,7 +330,7 @@ GS_EXPORT int32_t gs_destroy(gs_ctx* c) {
     if (!c->scene_borrowed) hipFree(c->scene_mem);
     hipFree(c->counts); hipFree(c->offsets); hipFree(c->gdata);
     hipFree(c->grec); hipFree(c->rowptr); hipFree(c->gsort_scratch);
-    hipFree(c->ranges); hipFree(c->rgba8); hipFree(c->rgbf); hipFree(c->d_pxb); hipFree(c->sticky); hipFree(c->blend_prof);
+    hipFree(c->ranges); hipFree(c->rgba8); hipFree(c->rgbf); hipFree(c->alpha); hipFree(c->depth); hipFree(c->d_pxb); hipFree(c->sticky); hipFree(c->blend_prof);
     hipFree(c->tileoff); hipFree(c->rowtot);
     if (c->h_ctl) hipHostFree(c->h_ctl);
     if (c->h_rep) hipHostFree(c->h_rep);
@@ -529,8 +538,11 @@ static int32_t record_frame(gs_ctx* c, const GsUniforms& u, bool debug, void* ex
     mark(c, 5);
     uint32_t* target = ext_rgba8 ? (uint32_t*)ext_rgba8 : c->rgba8;
     if ((c->blend_ablation & 0x10000u) && !c->blend_prof) HIP_TRY(hipMalloc((void**)&c->blend_prof, (size_t)(1u << 20) * 16));
-    const int walkers = gs_launch_blend(c->gdata, c->valsS, c->ranges, f, target, c->rgbf, c->ctl, c->tile_depth, (c->cfg.flags & GS_FLAG_EXACT_BLEND) != 0,
-                                        c->blend_ablation & 0xFFFFu, tight, st, (c->blend_ablation & 0x10000u) ? c->blend_prof : nullptr, &c->blend_prof_blocks);
+    const bool aux = (c->cfg.flags & GS_FLAG_AUX_OUTPUTS) != 0; // the planes go to the context's own buffers, also under gs_render_to
+    const int walkers = gs_launch_blend(c->gdata, c->valsS, c->ranges, f, target, c->rgbf, aux, c->alpha, c->depth, c->ctl, c->tile_depth,
+                                        (c->cfg.flags & GS_FLAG_EXACT_BLEND) != 0, c->blend_ablation & 0xFFFFu, tight, st,
+                                        (c->blend_ablation & 0x10000u) ? c->blend_prof : nullptr, &c->blend_prof_blocks);
+    if (walkers == -2) return fail(GS_ERR_INVALID_ARGUMENT, "blend: GS_FLAG_AUX_OUTPUTS without its alpha / depth planes");
     if (walkers < 0) return fail(GS_ERR_INVALID_ARGUMENT, "unsupported tile size %u", f.tile_size);
     c->blend_walkers = (uint32_t)walkers;
     mark(c, 6);
@@ -565,7 +577,8 @@ static int32_t enqueue_frame(gs_ctx* c, const GsUniforms& u, bool debug, void* e
     // of its identity.
     const bool graphable = c->use_graph && !debug && !c->have_events && !(c->blend_ablation & 0x10000u) && c->n;
     if (graphable) {
-        if (!c->gexec || !c->graph_valid || c->gkey_index != c->index_order || c->gkey_tight != tight || c->gkey_ext != ext_rgba8) {
+        if (!c->gexec || !c->graph_valid || c->gkey_index != c->index_order || c->gkey_tight != tight || c->gkey_ext != ext_rgba8 ||
+            c->gkey_alpha != c->alpha || c->gkey_depth != c->depth) {
             if (c->gexec) HIP_TRY(hipStreamSynchronize(st)); // a replay of the old capture may still be running: not destroyed under it
             drop_graph(c);
             HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
@@ -592,6 +605,7 @@ static int32_t enqueue_frame(gs_ctx* c, const GsUniforms& u, bool debug, void* e
                 c->pre_node = nullptr;
             }
             c->gkey_index = c->index_order; c->gkey_tight = tight; c->gkey_ext = ext_rgba8;
+            c->gkey_alpha = c->alpha; c->gkey_depth = c->depth;
             c->gnotes = {c->keysS, c->valsS, c->last_passes, c->blend_walkers, c->last_by_index, c->last_keys16, c->last_tight};
             c->graph_valid = true;
         } else {
@@ -846,6 +860,11 @@ static int32_t tap(gs_ctx* c, int32_t which, void** ptr, uint64_t* bytes) {
     case GS_BUF_RGB_F32:
         if (!c->rgbf) return fail(GS_ERR_INVALID_ARGUMENT, "GS_BUF_RGB_F32 needs GS_FLAG_F32_TAP");
         *ptr = c->rgbf; *bytes = px * 12; return GS_OK;
+    case GS_BUF_ALPHA_F32:
+    case GS_BUF_DEPTH_F32:
+        if (!c->alpha || !c->depth)
+            return fail(GS_ERR_INVALID_ARGUMENT, "%s needs GS_FLAG_AUX_OUTPUTS", which == GS_BUF_ALPHA_F32 ? "GS_BUF_ALPHA_F32" : "GS_BUF_DEPTH_F32");
+        *ptr = which == GS_BUF_ALPHA_F32 ? c->alpha : c->depth; *bytes = px * 4; return GS_OK;
     default: return fail(GS_ERR_INVALID_ARGUMENT, "unknown buffer id %d", which);
     }
 }

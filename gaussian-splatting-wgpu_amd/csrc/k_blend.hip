@@ -66,6 +66,14 @@ __device__ __forceinline__ bool blend_tmax_cull(float cx, float cy, float cz, fl
     return Tmax * (1.0f - alo) < 0.0000999f; // (NaN anywhere: false, the entry stays)
 }
 
+// GS_FLAG_AUX_OUTPUTS: the per-pixel alpha plane (1 - T) and accumulated-depth plane (sum of cond z alpha T, z = GaussianData.depth,
+// the same weights and association as the colour).  The planes ride in a kernel-argument pack that is EMPTY when AUX is false:
+// those instantiations keep the argument layout of the kernels without the feature, and with it their code (gs_blend_kernel reads
+// gridDim from the hidden arguments that follow the explicit ones, so one more explicit argument would move that load).
+struct GsAuxPlanes { float* alpha; float* depth; }; // f32[H][slab_w] each, indexed like the rgba8 slab
+__device__ __forceinline__ GsAuxPlanes gs_aux_planes() { return GsAuxPlanes{nullptr, nullptr}; }
+__device__ __forceinline__ GsAuxPlanes gs_aux_planes(GsAuxPlanes p) { return p; }
+
 // One workgroup per tile, TS*TS threads, one pixel per thread; wave w owns the 8x8 pixel block
 // (w % (TS/8), w / (TS/8)) of the tile.  The tile's sorted list is consumed in batches of TS*TS
 // entries through a DOUBLE-BUFFERED LDS stage: while a batch is being blended, the next batch's
@@ -76,11 +84,12 @@ __device__ __forceinline__ bool blend_tmax_cull(float cx, float cy, float cz, fl
 // rounding, so no output bit changes), then walks only the set bits with a branch-free body.
 // A finished pixel needs no flag inside the loop: by the exit criterion no later entry can pass
 // `T*(1-alpha) >= 1e-4` for it, so `done` is only evaluated between batches to skip whole waves/tiles.
-template <int TS, bool EXACT>
+template <int TS, bool EXACT, bool AUX = false, typename... Aux>
 __global__ __launch_bounds__(TS* TS) void gs_blend_kernel(const uint4* __restrict__ gdata, const uint32_t* __restrict__ values,
                                                            const uint32_t* __restrict__ ranges, GsFrame f,
                                                            uint32_t* __restrict__ rgba8, float* __restrict__ rgbf, GsControl* ctl,
-                                                           uint32_t dbg, uint32_t id_mask) {
+                                                           uint32_t dbg, uint32_t id_mask, Aux... aux) {
+    static_assert(sizeof...(Aux) == (AUX ? 1u : 0u), "AUX kernels take one GsAuxPlanes, the others none");
     constexpr int NT = TS * TS;
     constexpr int ROUNDS = NT / 64; // 64-entry groups per batch
     constexpr int WPR = TS / 8;     // waves per tile row
@@ -101,6 +110,7 @@ __global__ __launch_bounds__(TS* TS) void gs_blend_kernel(const uint4* __restric
     const float pxf = (float)gx, pyf = (float)gy;
     const float bx0f = (float)bx0, by0f = (float)by0;
     float T = 1.0f, cr = 0.0f, cg = 0.0f, cb = 0.0f;
+    float cd = 0.0f; // AUX: accumulated depth
     const bool outside = !(gx < f.width && gy < f.height);
     bool done = outside;
     const float c255 = (float)(1.0 / 255.0);
@@ -221,6 +231,7 @@ __global__ __launch_bounds__(TS* TS) void gs_blend_kernel(const uint4* __restric
                         cr += cond * p2v.x * alpha * T;
                         cg += cond * p2v.y * alpha * T;
                         cb += cond * p2v.z * alpha * T;
+                        if constexpr (AUX) cd += cond * p1.w * alpha * T; // sP1.w: the depth, staged in both modes
                         T = cond * test + (1.0f - cond) * T;
                     } else {
                         const float u = __builtin_fmaf(p1.x, dx, p1.y * dy);
@@ -234,6 +245,7 @@ __global__ __launch_bounds__(TS* TS) void gs_blend_kernel(const uint4* __restric
                         cr = __builtin_fmaf(p2v.x, wgt, cr);
                         cg = __builtin_fmaf(p2v.y, wgt, cg);
                         cb = __builtin_fmaf(p2v.z, wgt, cb);
+                        if constexpr (AUX) cd = __builtin_fmaf(p1.w, wgt, cd);
                         T = keep ? test : T;
                     }
                 }
@@ -267,6 +279,11 @@ __global__ __launch_bounds__(TS* TS) void gs_blend_kernel(const uint4* __restric
             rgbf[o * 3 + 1] = cg;
             rgbf[o * 3 + 2] = cb;
         }
+        if constexpr (AUX) {
+            const GsAuxPlanes ap = gs_aux_planes(aux...);
+            ap.alpha[o] = 1.0f - T;
+            ap.depth[o] = cd;
+        }
     }
 }
 
@@ -299,14 +316,17 @@ extern "C" __attribute__((visibility("default"))) int gs_prof_blend_footprint(un
     return 0;
 }
 #endif
+constexpr bool gs_lds_disjoint(int a, int na, int b, int nb) { return a + na <= b || b + nb <= a; } // byte ranges [a, a+na), [b, b+nb)
 typedef uint32_t gs_u32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t gs_u32x3 __attribute__((ext_vector_type(3)));
 typedef uint32_t gs_u32x4 __attribute__((ext_vector_type(4)));
-template <bool EXACT, int TS = 16, bool MASKED = false>
+template <bool EXACT, int TS = 16, bool MASKED = false, bool AUX = false, typename... Aux>
 __global__ __launch_bounds__(64) void gs_blend_quad_kernel(const uint4* __restrict__ gdata, const uint32_t* __restrict__ values,
                                                             const uint32_t* __restrict__ ranges, GsFrame f,
                                                             uint32_t* __restrict__ rgba8, float* __restrict__ rgbf, GsControl* ctl,
-                                                            uint32_t* __restrict__ tile_depth, uint32_t dbg, uint32_t* __restrict__ prof) {
+                                                            uint32_t* __restrict__ tile_depth, uint32_t dbg, uint32_t* __restrict__ prof,
+                                                            Aux... aux) {
+    static_assert(sizeof...(Aux) == (AUX ? 1u : 0u), "AUX kernels take one GsAuxPlanes, the others none");
     constexpr uint32_t BPR = TS / 8, NB = BPR * BPR;
 #ifdef GS_PROFILING // (build.py --profiling; GS_OPT_BLEND_ABLATION bit 16): start / end stamp (100 MHz), evaluated and staged entries per walker
     const uint32_t t_start = prof ? (uint32_t)__builtin_amdgcn_s_memrealtime() : 0u;
@@ -318,6 +338,8 @@ __global__ __launch_bounds__(64) void gs_blend_quad_kernel(const uint4* __restri
     // tabulated by the lane that parks the entry (4 instructions per row).  The loop evaluates it with two fmas and no
     // subtraction; round 3's first table (conic.y' dy, conic.z' dy^2 + log2 op per row) still needed dx = gx - px and a third
     // read per entry.  Rows are 65 slots apart: the 8 rows of a slot then sit in 8 different bank pairs (ds_read_b64).
+    // AUX (GS_FLAG_AUX_OUTPUTS): EXACT stages the depth in sP1.w; fused adds sZ (0.99 z per slot: the loop's weight is T alpha / 0.99)
+    // AFTER the last region, so the regions of the kernels without the planes stay where they are.
 #ifndef GS_L_OFF_T
 #define GS_L_OFF_T 0
 #define GS_L_OFF_Q 4160
@@ -325,14 +347,26 @@ __global__ __launch_bounds__(64) void gs_blend_quad_kernel(const uint4* __restri
 #define GS_L_OFF_L 6208
 #define GS_L_TOTAL 6464
 #endif
+#define GS_L_OFF_Z GS_L_TOTAL
+#define GS_L_TOTAL_AUX (GS_L_TOTAL + 256)
+    static_assert(gs_lds_disjoint(GS_L_OFF_T, 8 * 65 * 8, GS_L_OFF_Q, 256 * 4) && gs_lds_disjoint(GS_L_OFF_T, 8 * 65 * 8, GS_L_OFF_P, 64 * 16) &&
+                  gs_lds_disjoint(GS_L_OFF_T, 8 * 65 * 8, GS_L_OFF_L, 64 * 4) && gs_lds_disjoint(GS_L_OFF_T, 8 * 65 * 8, GS_L_OFF_Z, 64 * 4) &&
+                  gs_lds_disjoint(GS_L_OFF_Q, 256 * 4, GS_L_OFF_P, 64 * 16) && gs_lds_disjoint(GS_L_OFF_Q, 256 * 4, GS_L_OFF_L, 64 * 4) &&
+                  gs_lds_disjoint(GS_L_OFF_Q, 256 * 4, GS_L_OFF_Z, 64 * 4) && gs_lds_disjoint(GS_L_OFF_P, 64 * 16, GS_L_OFF_L, 64 * 4) &&
+                  gs_lds_disjoint(GS_L_OFF_P, 64 * 16, GS_L_OFF_Z, 64 * 4) && gs_lds_disjoint(GS_L_OFF_L, 64 * 4, GS_L_OFF_Z, 64 * 4),
+                  "fused LDS regions overlap");
+    static_assert(GS_L_OFF_T + 8 * 65 * 8 <= GS_L_TOTAL && GS_L_OFF_Q + 256 * 4 <= GS_L_TOTAL && GS_L_OFF_P + 64 * 16 <= GS_L_TOTAL &&
+                  GS_L_OFF_L + 64 * 4 <= GS_L_TOTAL && GS_L_OFF_Z + 64 * 4 <= GS_L_TOTAL_AUX && GS_L_OFF_P % 16 == 0 && GS_L_OFF_T % 8 == 0,
+                  "a fused LDS region ends outside its array");
     __shared__ __attribute__((aligned(16))) unsigned char lds_x[EXACT ? 4096 : 16];         // EXACT: sP0 | sP1 | sP2 | sQ
-    __shared__ __attribute__((aligned(16))) unsigned char lds_f[EXACT ? 16 : GS_L_TOTAL];   // fused: placed by hand (the offsets matter: see gs_launch_blend)
+    __shared__ __attribute__((aligned(16))) unsigned char lds_f[EXACT ? 16 : (AUX ? GS_L_TOTAL_AUX : GS_L_TOTAL)]; // fused: placed by hand (the offsets matter: see gs_launch_blend)
     float4* const sP0 = reinterpret_cast<float4*>(EXACT ? lds_x : lds_f + GS_L_OFF_P);
     float4* const sP1 = reinterpret_cast<float4*>(lds_x + (EXACT ? 1024 : 0));
     float4* const sP2 = reinterpret_cast<float4*>(lds_x + (EXACT ? 2048 : 0));
     uint32_t* const sQ = reinterpret_cast<uint32_t*>(EXACT ? lds_x + 3072 : lds_f + GS_L_OFF_Q);
     float* const sL = reinterpret_cast<float*>(lds_f + (EXACT ? 0 : GS_L_OFF_L));
     float2* const sT = reinterpret_cast<float2*>(lds_f + (EXACT ? 0 : GS_L_OFF_T));
+    float* const sZ = reinterpret_cast<float*>(lds_f + ((EXACT || !AUX) ? 0 : GS_L_OFF_Z)); // fused AUX only
     const uint32_t lane = threadIdx.x;
     const uint32_t slab_tx = f.col1 - f.col0;
     // Workgroups are dealt round-robin to the 8 XCDs (b % 8), each with its own L2.  XCD x owns the column strips
@@ -364,15 +398,18 @@ __global__ __launch_bounds__(64) void gs_blend_quad_kernel(const uint4* __restri
     const bool outside = !(gx < f.width && gy < f.height);
     bool done = outside;
     float T = 1.0f, cr = 0.0f, cg = 0.0f, cb = 0.0f;
+    float cd = 0.0f; // AUX: accumulated depth
     uint32_t staged = 0, evaluated = 0;
 #ifdef GS_PROFILING
     uint32_t fp_lanes = 0, fp_quads = 0, fp_none = 0, fp_live = 0, fp_kept = 0, fp_dead = 0, fp_q1 = 0, fp_tailn = 0, fp_tailbits = 0, fp_nokeep = 0;
 #endif
 
     // the three pieces of a record a lane fetches (uv | conic | colour, opacity), as native vectors: each is ONE register tuple
-    // from the load to the asm pin below, so nothing has to be copied (and waited for) in between
+    // from the load to the asm pin below, so nothing has to be copied (and waited for) in between.  AUX: the conic piece is read
+    // with the depth behind it (record + 16: still one aligned 16-byte load)
+    using R1 = std::conditional_t<AUX, gs_u32x4, gs_u32x3>;
     gs_u32x2 r0 = {0u, 0u};
-    gs_u32x3 r1 = {0u, 0u, 0u};
+    R1 r1 = {0u, 0u, 0u};
     gs_u32x4 r2 = {0u, 0u, 0u, 0u};
     // this walker's bit of the mask: its 8x8 block at tile 16, the 16x16 quadrant holding it at tile 32
     const uint32_t mybit = GS_ID_BITS + (TS == 32 ? ((q / BPR) / 2u) * 2u + ((q % BPR) / 2u) : q);
@@ -431,7 +468,7 @@ __global__ __launch_bounds__(64) void gs_blend_quad_kernel(const uint4* __restri
         g = lane < cnt ? g : 0u;
         const uint32_t* rec = reinterpret_cast<const uint32_t*>(gdata + (uint64_t)g * 4);
         r0 = *reinterpret_cast<const gs_u32x2*>(rec);
-        r1 = *reinterpret_cast<const gs_u32x3*>(rec + 4);
+        r1 = *reinterpret_cast<const R1*>(rec + 4);
         r2 = *reinterpret_cast<const gs_u32x4*>(rec + 8);
     };
     uint32_t cnt = 0, vnext = 0;
@@ -450,6 +487,8 @@ __global__ __launch_bounds__(64) void gs_blend_quad_kernel(const uint4* __restri
         const float gxp = __uint_as_float(r0.x) * Wf, gyp = __uint_as_float(r0.y) * Hf; // compute_tiles.wgsl:52
         const float cx = __uint_as_float(r1.x), cy = __uint_as_float(r1.y), cz = __uint_as_float(r1.z);
         const float op = __uint_as_float(r2.w);
+        float z = 0.0f; // AUX: GaussianData.depth (byte 28)
+        if constexpr (AUX) z = __uint_as_float(r1.w);
         // THE LIVE BOX.  Whatever decided that an entry can touch this block (the binning's mask bit at tile 16, nothing in a
         // reference-binning frame) decided it for the block's 64 pixels -- but most of them are FINAL long before the block is:
         // at an average evaluation 8 of the 64 pixels were still live, and a third of the evaluations touched final pixels only
@@ -535,7 +574,7 @@ __global__ __launch_bounds__(64) void gs_blend_quad_kernel(const uint4* __restri
             // The opacity rides in the exponent: alpha = exp2(power*log2(e) + log2(op)).
             if (EXACT) {
                 sP0[slot] = make_float4(gxp, gyp, 0.0f, 0.0f);
-                sP1[slot] = make_float4(cx, cy, cz, 0.0f);
+                sP1[slot] = make_float4(cx, cy, cz, z);
                 sP2[slot] = make_float4(__uint_as_float(r2.x), __uint_as_float(r2.y), __uint_as_float(r2.z), op);
             } else {
                 // with d = gx - bx0 (block-relative centre), dy = gy - (by0 + r):
@@ -548,6 +587,7 @@ __global__ __launch_bounds__(64) void gs_blend_quad_kernel(const uint4* __restri
                 const float b0 = (-2.0f * hx) * d, a1 = hy * d, a0 = __builtin_fmaf(hx * d, d, lop);
                 sP0[slot] = make_float4(hx, 0.99f * __uint_as_float(r2.x), 0.99f * __uint_as_float(r2.y), 0.99f * __uint_as_float(r2.z));
                 sL[slot] = lop;
+                if constexpr (AUX) sZ[slot] = 0.99f * z;
 #pragma unroll
                 for (int r = 0; r < 8; ++r) {
                     const float dy = gyp - (by0f + (float)r);
@@ -573,7 +613,7 @@ __global__ __launch_bounds__(64) void gs_blend_quad_kernel(const uint4* __restri
         const float xlf = (float)(lane & 7u);
         auto walk = [&](auto checked_tag) {
             constexpr bool CHECKED = decltype(checked_tag)::value;
-            auto one = [&](uint32_t e, const float4 p0, const float2 tt) { // p0 / tt: the entry's sP0 word / (fused) its row-table pair
+            auto one = [&](uint32_t e, const float4 p0, const float2 tt, const float zz) { // p0 / tt / zz: the entry's sP0 word / (fused) its row-table pair / (fused AUX) 0.99 z
                 if (EXACT) {
                     const float dx = p0.x - pxf;
                     const float4 p1 = sP1[e];
@@ -587,6 +627,7 @@ __global__ __launch_bounds__(64) void gs_blend_quad_kernel(const uint4* __restri
                     cr += cond * p2v.x * alpha * T;
                     cg += cond * p2v.y * alpha * T;
                     cb += cond * p2v.z * alpha * T;
+                    if constexpr (AUX) cd += cond * p1.w * alpha * T;
                     T = cond * test + (1.0f - cond) * T;
                 } else {
                     const float pw = __builtin_fmaf(xlf, __builtin_fmaf(xlf, p0.x, tt.x), tt.y); // log2(alpha / 0.99) before the clamp
@@ -619,6 +660,7 @@ __global__ __launch_bounds__(64) void gs_blend_quad_kernel(const uint4* __restri
                         cr = __builtin_fmaf(p0.y, wk, cr);
                         cg = __builtin_fmaf(p0.z, wk, cg);
                         cb = __builtin_fmaf(p0.w, wk, cb);
+                        if constexpr (AUX) cd = __builtin_fmaf(zz, wk, cd);
                         T = keep ? test : T;
                     } else {
                         // The keep/skip decision as an exec mask instead of two selects: the two compares narrow exec, the three
@@ -627,6 +669,25 @@ __global__ __launch_bounds__(64) void gs_blend_quad_kernel(const uint4* __restri
                         // vector instructions are issued here.  Same operations on the kept lanes, nothing on the others.
                         float wgt, test;
                         unsigned long long save;
+                        if constexpr (AUX) // the same block, plus the depth's fmac under the same exec mask
+                            asm(
+                                "v_mul_f32_e32 %[wgt], %[T], %[ea]\n\t"
+                                "v_fma_f32 %[test], %[wgt], %[m99], %[T]\n\t"
+                                "s_mov_b64 %[save], exec\n\t"
+                                "v_cmpx_le_f32_e32 vcc, %[k1], %[ea]\n\t"
+                                "v_cmpx_le_f32_e32 vcc, %[thr], %[test]\n\t"
+                                "v_mov_b32_e32 %[T], %[test]\n\t"
+                                "v_fmac_f32_e32 %[cr], %[c0], %[wgt]\n\t"
+                                "v_fmac_f32_e32 %[cg], %[c1], %[wgt]\n\t"
+                                "v_fmac_f32_e32 %[cb], %[c2], %[wgt]\n\t"
+                                "v_fmac_f32_e32 %[cd], %[z], %[wgt]\n\t"
+                                "s_mov_b64 exec, %[save]"
+                                : [save] "=&s"(save), [wgt] "=&v"(wgt), [test] "=&v"(test), [T] "+v"(T), [cr] "+v"(cr), [cg] "+v"(cg), [cb] "+v"(cb),
+                                  [cd] "+v"(cd)
+                                : [k1] "s"(k1), [thr] "s"(0.0001f), [m99] "s"(-0.99f), [ea] "v"(ea), [c0] "v"(p0.y), [c1] "v"(p0.z), [c2] "v"(p0.w),
+                                  [z] "v"(zz)
+                                : "vcc");
+                        else
                         asm(
                             "v_mul_f32_e32 %[wgt], %[T], %[ea]\n\t"
                             "v_fma_f32 %[test], %[wgt], %[m99], %[T]\n\t"
@@ -652,14 +713,17 @@ __global__ __launch_bounds__(64) void gs_blend_quad_kernel(const uint4* __restri
                 constexpr int G = decltype(n_tag)::value;
                 float4 p[G];
                 float2 t[G];
+                float zz[G];
 #pragma unroll
                 for (int k = 0; k < G; ++k) {
                     p[k] = sP0[e + k];
                     t[k] = EXACT ? make_float2(0.0f, 0.0f) : sT[trow + e + k]; // this pixel row's (B_r, A_r)
+                    zz[k] = 0.0f;
+                    if constexpr (AUX && !EXACT) zz[k] = sZ[e + k];
                 }
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int k = 0; k < G; ++k) one(e + k, p[k], t[k]);
+                for (int k = 0; k < G; ++k) one(e + k, p[k], t[k], zz[k]);
                 __builtin_amdgcn_sched_barrier(0);
             };
             uint32_t e = 0;
@@ -712,6 +776,11 @@ __global__ __launch_bounds__(64) void gs_blend_quad_kernel(const uint4* __restri
             rgbf[o * 3 + 0] = cr;
             rgbf[o * 3 + 1] = cg;
             rgbf[o * 3 + 2] = cb;
+        }
+        if constexpr (AUX) {
+            const GsAuxPlanes ap = gs_aux_planes(aux...);
+            ap.alpha[o] = 1.0f - T;
+            ap.depth[o] = cd;
         }
     }
 }
@@ -768,35 +837,50 @@ void gs_launch_debug_view(const uint32_t* ranges, const GsFrame& f, uint32_t vie
 }
 
 // ---- host launchers --------------------------------------------------------------------------------
+// aux: GS_FLAG_AUX_OUTPUTS -- the AUX instantiations, which take the planes `ap` (non-null: gs_launch_blend checks)
 template <int TS>
-static void launch_blend_t(bool exact, dim3 grid, hipStream_t st, const uint4* gdata, const uint32_t* values, const uint32_t* ranges,
-                           const GsFrame& f, uint32_t* rgba8, float* rgbf, GsControl* ctl, uint32_t dbg, uint32_t id_mask) {
-    if (exact)
-        hipLaunchKernelGGL((gs_blend_kernel<TS, true>), grid, dim3(TS * TS), 0, st, gdata, values, ranges, f, rgba8, rgbf, ctl, dbg, id_mask);
-    else
-        hipLaunchKernelGGL((gs_blend_kernel<TS, false>), grid, dim3(TS * TS), 0, st, gdata, values, ranges, f, rgba8, rgbf, ctl, dbg, id_mask);
+static void launch_blend_t(bool exact, bool aux, GsAuxPlanes ap, dim3 grid, hipStream_t st, const uint4* gdata, const uint32_t* values,
+                           const uint32_t* ranges, const GsFrame& f, uint32_t* rgba8, float* rgbf, GsControl* ctl, uint32_t dbg, uint32_t id_mask) {
+#define GS_WG(E) hipLaunchKernelGGL((gs_blend_kernel<TS, E>), grid, dim3(TS * TS), 0, st, gdata, values, ranges, f, rgba8, rgbf, ctl, dbg, id_mask)
+#define GS_WG_AUX(E) hipLaunchKernelGGL((gs_blend_kernel<TS, E, true, GsAuxPlanes>), grid, dim3(TS * TS), 0, st, gdata, values, ranges, f, rgba8, \
+                                        rgbf, ctl, dbg, id_mask, ap)
+    if (aux) { if (exact) GS_WG_AUX(true); else GS_WG_AUX(false); }
+    else { if (exact) GS_WG(true); else GS_WG(false); }
+#undef GS_WG
+#undef GS_WG_AUX
 }
 template <int TS>
-static void launch_quad_t(bool exact, bool masked, uint32_t nblk, uint32_t pad, hipStream_t st, const uint4* g, const uint32_t* values,
-                          const uint32_t* ranges, const GsFrame& f, uint32_t* rgba8, float* rgbf, GsControl* ctl, uint32_t* tile_depth,
-                          uint32_t dbg, uint32_t* prof) {
+static void launch_quad_t(bool exact, bool masked, bool aux, GsAuxPlanes ap, uint32_t nblk, uint32_t pad, hipStream_t st, const uint4* g,
+                          const uint32_t* values, const uint32_t* ranges, const GsFrame& f, uint32_t* rgba8, float* rgbf, GsControl* ctl,
+                          uint32_t* tile_depth, uint32_t dbg, uint32_t* prof) {
 #define GS_QUAD(E, M) hipLaunchKernelGGL((gs_blend_quad_kernel<E, TS, M>), dim3(nblk), dim3(64), pad, st, g, values, ranges, f, rgba8, rgbf, ctl, tile_depth, dbg, prof)
-    if (exact) { if (masked) GS_QUAD(true, true); else GS_QUAD(true, false); }
-    else { if (masked) GS_QUAD(false, true); else GS_QUAD(false, false); }
+#define GS_QUAD_AUX(E, M) hipLaunchKernelGGL((gs_blend_quad_kernel<E, TS, M, true, GsAuxPlanes>), dim3(nblk), dim3(64), pad, st, g, values, ranges, f, \
+                                             rgba8, rgbf, ctl, tile_depth, dbg, prof, ap)
+    if (aux) {
+        if (exact) { if (masked) GS_QUAD_AUX(true, true); else GS_QUAD_AUX(true, false); }
+        else { if (masked) GS_QUAD_AUX(false, true); else GS_QUAD_AUX(false, false); }
+    } else {
+        if (exact) { if (masked) GS_QUAD(true, true); else GS_QUAD(true, false); }
+        else { if (masked) GS_QUAD(false, true); else GS_QUAD(false, false); }
+    }
 #undef GS_QUAD
+#undef GS_QUAD_AUX
 }
-// Returns -1 for an unsupported tile size, 4 when the quadrant kernel ran (gs_stats.num_processed is then the sum of
-// tile_depth[], the per-tile maximum over its four independent walkers), 1 otherwise (ctl->num_processed).
+// Returns -1 for an unsupported tile size, -2 for aux planes requested without both of them (nothing is launched), 4 when the
+// quadrant kernel ran (gs_stats.num_processed is then the sum of tile_depth[], the per-tile maximum over its four independent
+// walkers), 1 otherwise (ctl->num_processed).  aux: run the AUX instantiation, which writes alpha / depth (f32[H][slab_w] each).
 int gs_launch_blend(const void* gdata, const uint32_t* values, const uint32_t* ranges, const GsFrame& f, uint32_t* rgba8, float* rgbf,
-                    GsControl* ctl, uint32_t* tile_depth, bool exact, uint32_t ablation, bool masked, hipStream_t st, uint32_t* prof,
-                    uint32_t* prof_blocks) {
+                    bool aux, float* alpha, float* depth, GsControl* ctl, uint32_t* tile_depth, bool exact, uint32_t ablation, bool masked,
+                    hipStream_t st, uint32_t* prof, uint32_t* prof_blocks) {
+    if (aux && (!alpha || !depth)) return -2; // an AUX kernel only ever sees both planes
+    const GsAuxPlanes ap{alpha, depth};
     uint32_t dbg = ablation; // GS_OPT_BLEND_ABLATION: 0 = product path
     const uint32_t id_mask = masked ? GS_ID_MASK : 0xFFFFFFFFu; // kernels without mask support only strip the bits
     const dim3 grid(f.col1 - f.col0, f.nty);
     if (grid.x == 0 || grid.y == 0) return 1;
     const uint4* g = (const uint4*)gdata;
     switch (f.tile_size) {
-    case 8: launch_blend_t<8>(exact, grid, st, g, values, ranges, f, rgba8, rgbf, ctl, dbg, id_mask); return 1;
+    case 8: launch_blend_t<8>(exact, aux, ap, grid, st, g, values, ranges, f, rgba8, rgbf, ctl, dbg, id_mask); return 1;
     case 16:
     case 32: {
         // default: one single-wave workgroup per 8x8 pixel block; GS_OPT_BLEND_ABLATION bit 3 picks the workgroup-per-tile kernel
@@ -833,12 +917,12 @@ int gs_launch_blend(const void* gdata, const uint32_t* values, const uint32_t* r
             const uint32_t pad = 0u;
 #endif
             if (prof_blocks) *prof_blocks = nblk;
-            if (t32) { launch_quad_t<32>(exact, masked, nblk, pad, st, g, values, ranges, f, rgba8, rgbf, ctl, tile_depth, dbg, prof); return 16; }
-            launch_quad_t<16>(exact, masked, nblk, pad, st, g, values, ranges, f, rgba8, rgbf, ctl, tile_depth, dbg, prof);
+            if (t32) { launch_quad_t<32>(exact, masked, aux, ap, nblk, pad, st, g, values, ranges, f, rgba8, rgbf, ctl, tile_depth, dbg, prof); return 16; }
+            launch_quad_t<16>(exact, masked, aux, ap, nblk, pad, st, g, values, ranges, f, rgba8, rgbf, ctl, tile_depth, dbg, prof);
             return 4;
         }
-        if (t32) { launch_blend_t<32>(exact, grid, st, g, values, ranges, f, rgba8, rgbf, ctl, dbg, id_mask); return 1; } // ablation bit 3: 1024-thread workgroup per tile
-        launch_blend_t<16>(exact, grid, st, g, values, ranges, f, rgba8, rgbf, ctl, dbg, id_mask);
+        if (t32) { launch_blend_t<32>(exact, aux, ap, grid, st, g, values, ranges, f, rgba8, rgbf, ctl, dbg, id_mask); return 1; } // ablation bit 3: 1024-thread workgroup per tile
+        launch_blend_t<16>(exact, aux, ap, grid, st, g, values, ranges, f, rgba8, rgbf, ctl, dbg, id_mask);
         return 1;
     }
     default: return -1;

@@ -575,6 +575,9 @@ static napi_value init(napi_env env, napi_value exports) {
     set_num(env, exports, "FLAG_EXACT_BLEND", GS_FLAG_EXACT_BLEND);
     set_num(env, exports, "FLAG_F32_TAP", GS_FLAG_F32_TAP);
     set_num(env, exports, "FLAG_TIMING", GS_FLAG_TIMING);
+    set_num(env, exports, "FLAG_AUX_OUTPUTS", GS_FLAG_AUX_OUTPUTS);
+    set_num(env, exports, "BUF_ALPHA_F32", GS_BUF_ALPHA_F32);
+    set_num(env, exports, "BUF_DEPTH_F32", GS_BUF_DEPTH_F32);
     return exports;
 }
 

@@ -14,11 +14,14 @@ LIB_PATH = os.environ.get("GSPLAT_LIB") or os.path.abspath(os.path.join(_HERE, "
 GS_FLAG_EXACT_BLEND = 0x1
 GS_FLAG_F32_TAP = 0x2
 GS_FLAG_TIMING = 0x4
+GS_FLAG_AUX_OUTPUTS = 0x8
 
 GS_STAGE_NAMES = ("preprocess", "scan", "emit", "sort", "ranges", "blend")
 
 (GS_BUF_TILE_COUNTS, GS_BUF_TILE_OFFSETS, GS_BUF_GAUSSIAN_DATA, GS_BUF_KEYS_UNSORTED, GS_BUF_VALUES_UNSORTED, GS_BUF_KEYS,
  GS_BUF_VALUES, GS_BUF_RANGES, GS_BUF_RGBA8, GS_BUF_RGB_F32, GS_BUF_BLOCK_MASKS) = range(11)
+GS_BUF_ALPHA_F32 = 13  # GS_FLAG_AUX_OUTPUTS (11 and 12 are the library's profiling and test taps)
+GS_BUF_DEPTH_F32 = 14
 
 GS_OPT_BLEND_ABLATION = 1
 GS_OPT_PERSISTENT_GRID = 2

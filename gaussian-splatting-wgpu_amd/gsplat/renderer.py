@@ -139,6 +139,22 @@ class Renderer:
             check(self._L.gs_read_buffer(self._ctx, which, out.ctypes.data, out.nbytes, None))
         return out
 
+    def read_alpha(self):
+        """GS_FLAG_AUX_OUTPUTS: the last frame's accumulated opacity A = 1 - T, f32[H, slab_width] (0 where no splat reaches).  The
+        colour is premultiplied: composite over a background B as C + (1 - A) B."""
+        return self.read_buffer(_abi.GS_BUF_ALPHA_F32, np.float32).reshape(self.canvas.height, self.slab_width)
+
+    def read_depth(self, normalized=False):
+        """GS_FLAG_AUX_OUTPUTS: the last frame's accumulated depth D = sum of z alpha T (the colour's weights), f32[H, slab_width];
+        normalized=True: the expected depth D / A where A > 0, else 0."""
+        d = self.read_buffer(_abi.GS_BUF_DEPTH_F32, np.float32).reshape(self.canvas.height, self.slab_width)
+        if not normalized:
+            return d
+        a = self.read_alpha()
+        out = np.zeros_like(d)
+        np.divide(d, a, out=out, where=a > 0)
+        return out
+
     def device_ptr(self, which):
         p = ctypes.c_void_p()
         check(self._L.gs_device_ptr(self._ctx, which, ctypes.byref(p)))
@@ -218,6 +234,14 @@ class PipelinedRenderer:
     def read_rgba8(self, slot):
         self.wait(slot)
         return self.renderers[slot].read_rgba8()
+
+    def read_alpha(self, slot):
+        self.wait(slot)
+        return self.renderers[slot].read_alpha()
+
+    def read_depth(self, slot, normalized=False):
+        self.wait(slot)
+        return self.renderers[slot].read_depth(normalized)
 
     def set_option(self, key, value):
         for r in self.renderers:

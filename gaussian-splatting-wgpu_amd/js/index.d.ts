@@ -31,6 +31,10 @@ export class Renderer {
   constructor(canvas: CanvasLike, interactiveCamera: InteractiveCamera, device: number | { ordinal: number; flags?: number; shareWith?: Renderer }, gaussians: PackedGaussians, tileSize: number);
   animate(): Promise<void>; destroy(): Promise<void>;
   renderUniforms(uniforms: Float32Array, debug?: boolean): void; readPixels(): Uint8Array; readBuffer(which: number): ArrayBuffer;
+  /** FLAG.AUX_OUTPUTS: the last frame's accumulated opacity, f32[height][slabWidth]. */
+  readAlpha(): Float32Array;
+  /** FLAG.AUX_OUTPUTS: the last frame's accumulated depth D, or D / alpha where alpha > 0 (else 0) with normalized = true. */
+  readDepth(normalized?: boolean): Float32Array;
   stats(): { numGaussians: number; numVisible: number; numIntersections: number; numProcessed: number; numTiles: number; sortPasses: number; frames: number; frameUs: number; stageUs: number[]; numEvaluated: number; depthOrdered: number; tightBinning: number; graphFrames: number; capacity: number; maxIntersectionsSeen: number; truncatedFrames: number };
 }
 export function loadFileAsArrayBuffer(path: string): Promise<ArrayBuffer>;
@@ -39,3 +43,6 @@ export function loadCameraFile(path: string, canvas?: CanvasLike): { name: strin
 export function getProjectionMatrix(znear: number, zfar: number, fovX: number, fovY: number): Mat4;
 export function focal2fov(focal: number, pixels: number): number;
 export function writePPM(file: string, rgba: Uint8Array, width: number, height: number): void;
+export const BUF: { TILE_COUNTS: 0; TILE_OFFSETS: 1; GAUSSIAN_DATA: 2; KEYS_UNSORTED: 3; VALUES_UNSORTED: 4; KEYS: 5; VALUES: 6; RANGES: 7; RGBA8: 8; RGB_F32: 9;
+                    ALPHA_F32: 13; DEPTH_F32: 14 };
+export const FLAG: { EXACT_BLEND: 0x1; F32_TAP: 0x2; TIMING: 0x4; AUX_OUTPUTS: 0x8 };

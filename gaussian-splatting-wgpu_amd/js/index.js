@@ -18,5 +18,7 @@ function writePPM(file, rgba, width, height) {
 module.exports = {
   Renderer, Camera, InteractiveCamera, PackedGaussians, loadFileAsArrayBuffer, cameraFromJSON, loadCameraFile,
   getProjectionMatrix, focal2fov, mat4, mat3, vec3, writePPM, loadNative,
-  BUF: { TILE_COUNTS: 0, TILE_OFFSETS: 1, GAUSSIAN_DATA: 2, KEYS_UNSORTED: 3, VALUES_UNSORTED: 4, KEYS: 5, VALUES: 6, RANGES: 7, RGBA8: 8, RGB_F32: 9 },
+  BUF: { TILE_COUNTS: 0, TILE_OFFSETS: 1, GAUSSIAN_DATA: 2, KEYS_UNSORTED: 3, VALUES_UNSORTED: 4, KEYS: 5, VALUES: 6, RANGES: 7, RGBA8: 8, RGB_F32: 9,
+         ALPHA_F32: 13, DEPTH_F32: 14 },
+  FLAG: { EXACT_BLEND: 0x1, F32_TAP: 0x2, TIMING: 0x4, AUX_OUTPUTS: 0x8 },
 };

@@ -133,6 +133,18 @@ class Renderer {
   renderUniforms(uniforms, debug) { loadNative().renderSync(this.handle, uniforms, !!debug); this.numFrames++; }
   readPixels() { return new Uint8Array(loadNative().readRgba8(this.handle)); }
   readBuffer(which) { return loadNative().readBuffer(this.handle, which); }
+  // GS_FLAG_AUX_OUTPUTS ({ordinal, flags} at construction): the last frame's f32[height][slabWidth] planes.  readAlpha(): accumulated
+  // opacity A (the colour is premultiplied: C + (1 - A) * background); readDepth(): accumulated depth D, or with normalized = true
+  // the expected depth D / A where A > 0 (0 elsewhere)
+  readAlpha() { const n = loadNative(); return new Float32Array(n.readBuffer(this.handle, n.BUF_ALPHA_F32)); }
+  readDepth(normalized) {
+    const n = loadNative();
+    const d = new Float32Array(n.readBuffer(this.handle, n.BUF_DEPTH_F32));
+    if (!normalized) return d;
+    const a = this.readAlpha();
+    for (let i = 0; i < d.length; ++i) d[i] = a[i] > 0 ? d[i] / a[i] : 0;
+    return d;
+  }
   stats() { return loadNative().stats(this.handle); }
 }
 

@@ -65,6 +65,8 @@ extern "C" {
                                     the CPU oracle; default is fused f32 + hardware exp2 (<=1e-4 per channel)  */
 #define GS_FLAG_F32_TAP 0x2u     /* also keep the un-quantised f32 RGB accumulators (GS_BUF_RGB_F32)            */
 #define GS_FLAG_TIMING 0x4u      /* bracket every stage with hipEvents; gs_get_stats returns stage microseconds */
+#define GS_FLAG_AUX_OUTPUTS 0x8u /* also keep the per-pixel alpha and accumulated-depth planes (GS_BUF_ALPHA_F32, GS_BUF_DEPTH_F32),
+                                    computed from the colour's own entries and weights; the rgba8 image is unchanged (alpha byte 255) */
 
 typedef struct gs_config {
     uint32_t struct_size;       /* = sizeof(gs_config); lets the struct grow                                     */
@@ -132,8 +134,14 @@ enum {
     GS_BUF_RANGES = 7,        /* u32[T]     rangesBuffer                                       */
     GS_BUF_RGBA8 = 8,         /* u8[H][Wslab][4] renderTarget (rgba8unorm), this ctx's slab    */
     GS_BUF_RGB_F32 = 9,       /* f32[H][Wslab][3] (GS_FLAG_F32_TAP)                            */
-    GS_BUF_BLOCK_MASKS = 10   /* u32[I]     per sorted instance: one bit per 8x8 pixel block of its tile (row-major, tile_size/8
+    GS_BUF_BLOCK_MASKS = 10,  /* u32[I]     per sorted instance: one bit per 8x8 pixel block of its tile (row-major, tile_size/8
                                  per row) the blend evaluates it for; all blocks when the frame did not use tight binning  */
+    /* 11 and 12 are the library's profiling and test taps */
+    GS_BUF_ALPHA_F32 = 13,    /* f32[H][Wslab] (GS_FLAG_AUX_OUTPUTS) accumulated opacity A = 1 - T_final; 0 where no entry reaches.
+                                 The colour is premultiplied: over a background B, C + (1 - A) B                              */
+    GS_BUF_DEPTH_F32 = 14     /* f32[H][Wslab] (GS_FLAG_AUX_OUTPUTS) accumulated depth D = sum of z alpha T over the kept entries,
+                                 z = GaussianData.depth, in list order with the colour's association; expected depth = D / A
+                                 where A > 0 (the division is left to the host)                                                */
 };
 
 typedef struct gs_ctx gs_ctx;
