@@ -54,3 +54,7 @@ void gs_launch_rows(const uint32_t* arena, const void* grec, const uint32_t* chu
                     uint32_t* sticky, GsReport* rep, hipStream_t st, void (*mark)(void*, int), void* mark_arg);
 void gs_launch_rows_rebuild_keys(const uint32_t* ranges, uint32_t T, const uint32_t* vals, const uint32_t* counts, uint32_t count, uint32_t n,
                                  uint32_t* keys, hipStream_t st);
+// k_pick.hip: gs_pick, one wave per query over the last frame's lists (queries: {x, y} pairs; results: 12 words per query;
+// contrib: max_contrib {id, weight} pairs per query, or null)
+void gs_launch_pick(const void* gdata, const uint32_t* values, const uint32_t* ranges, const GsFrame& f, uint32_t id_mask, const void* d_queries,
+                    uint32_t n, void* d_results, uint32_t max_contrib, void* d_contrib, hipStream_t st);

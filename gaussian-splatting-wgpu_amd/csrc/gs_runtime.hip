@@ -156,6 +156,9 @@ struct gs_ctx {
     uint32_t* d_pxb = nullptr; // assemble: pixel boundaries (device copy of pxb_host)
     uint32_t pxb_host[65] = {};
     uint32_t pxb_n = 0;
+    // gs_pick (root ctx): device copies of the queries, the results and the contributor records; allocated on first use
+    void *pick_q = nullptr, *pick_r = nullptr, *pick_c = nullptr;
+    uint64_t pick_c_bytes = 0;
     hipEvent_t ev[GS_EV_RING][GS_STAGE_COUNT + 1] = {}; // ring of per-frame stage brackets (GS_FLAG_TIMING)
     bool have_events = false;
     uint64_t timed_from = 0; // first frame index included in the stage means
@@ -332,6 +335,7 @@ GS_EXPORT int32_t gs_destroy(gs_ctx* c) {
     hipFree(c->grec); hipFree(c->rowptr); hipFree(c->gsort_scratch);
     hipFree(c->ranges); hipFree(c->rgba8); hipFree(c->rgbf); hipFree(c->alpha); hipFree(c->depth); hipFree(c->d_pxb); hipFree(c->sticky); hipFree(c->blend_prof);
     hipFree(c->tileoff); hipFree(c->rowtot);
+    hipFree(c->pick_q); hipFree(c->pick_r); hipFree(c->pick_c);
     if (c->h_ctl) hipHostFree(c->h_ctl);
     if (c->h_rep) hipHostFree(c->h_rep);
     if (c->have_events)
@@ -626,6 +630,7 @@ static int32_t enqueue_frame(gs_ctx* c, const GsUniforms& u, bool debug, void* e
         if (rc != GS_OK) return rc;
     }
     c->keysG_valid = false;
+    c->h_ctl_valid = false; // (a replayed frame too: record_frame, which also clears it, only runs for the capture)
     HIP_TRY(hipGetLastError());
     c->pending = true;
     c->have_frame = true;
@@ -1019,6 +1024,45 @@ GS_EXPORT int32_t gs_get_stats(gs_ctx* root, gs_stats* out) {
             }
         }
     }
+    return GS_OK;
+}
+
+// Per-pixel splat queries on the last frame (k_pick.hip).  Not a frame: nothing of the frame state, the statistics or a
+// captured graph is touched; the kernel is one more launch on the stream of the ring member that rendered the last frame.
+GS_EXPORT int32_t gs_pick(gs_ctx* root, const gs_pick_query* queries, uint32_t n, gs_pick_result* results, uint32_t max_contrib,
+                          gs_pick_contrib* contrib) {
+    static_assert(sizeof(gs_pick_query) == 8 && sizeof(gs_pick_result) == 48 && sizeof(gs_pick_contrib) == 8, "gs_pick record layouts");
+    if (!root || !queries || !results) return fail(GS_ERR_INVALID_ARGUMENT, "gs_pick: null argument");
+    if (n == 0 || n > GS_PICK_MAX_QUERIES) return fail(GS_ERR_INVALID_ARGUMENT, "gs_pick: n must be 1..%u (got %u)", GS_PICK_MAX_QUERIES, n);
+    if (max_contrib > GS_PICK_MAX_CONTRIB) return fail(GS_ERR_INVALID_ARGUMENT, "gs_pick: max_contrib must be at most %u (got %u)", GS_PICK_MAX_CONTRIB, max_contrib);
+    if ((contrib != nullptr) != (max_contrib != 0))
+        return fail(GS_ERR_INVALID_ARGUMENT, "gs_pick: contrib and max_contrib must be given together (contrib %s, max_contrib %u)",
+                    contrib ? "set" : "null", max_contrib);
+    for (uint32_t i = 0; i < n; ++i)
+        if (queries[i].x >= root->frame.width || queries[i].y >= root->frame.height)
+            return fail(GS_ERR_INVALID_ARGUMENT, "gs_pick: query %u: pixel (%u, %u) is outside the %u x %u canvas", i, queries[i].x, queries[i].y,
+                        root->frame.width, root->frame.height);
+    gs_ctx* c = last_of(root);
+    if (!c->have_frame) return fail(GS_ERR_NO_FRAME, "gs_pick: no frame rendered");
+    if (c->pending) { int32_t rc = wait_one(c); if (rc != GS_OK) return rc; } // (an overflowed frame has been re-rendered from full lists)
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    if (!root->pick_q) HIP_TRY(hipMalloc(&root->pick_q, (size_t)GS_PICK_MAX_QUERIES * sizeof(gs_pick_query)));
+    if (!root->pick_r) HIP_TRY(hipMalloc(&root->pick_r, (size_t)GS_PICK_MAX_QUERIES * sizeof(gs_pick_result)));
+    const uint64_t cbytes = (uint64_t)n * max_contrib * sizeof(gs_pick_contrib);
+    if (cbytes > root->pick_c_bytes) {
+        hipFree(root->pick_c);
+        root->pick_c = nullptr;
+        root->pick_c_bytes = 0;
+        HIP_TRY(hipMalloc(&root->pick_c, (size_t)cbytes));
+        root->pick_c_bytes = cbytes;
+    }
+    HIP_TRY(hipMemcpyAsync(root->pick_q, queries, (size_t)n * sizeof(gs_pick_query), hipMemcpyHostToDevice, c->stream));
+    gs_launch_pick(c->gdata, c->valsS, c->ranges, c->frame, c->last_tight ? GS_ID_MASK : 0xFFFFFFFFu, root->pick_q, n, root->pick_r, max_contrib,
+                   max_contrib ? root->pick_c : nullptr, c->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(results, root->pick_r, (size_t)n * sizeof(gs_pick_result), hipMemcpyDeviceToHost, c->stream));
+    if (max_contrib) HIP_TRY(hipMemcpyAsync(contrib, root->pick_c, (size_t)cbytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return GS_OK;
 }
 

@@ -333,6 +333,39 @@ static napi_value js_read_buffer(napi_env env, napi_callback_info info) {
     return rc == GS_OK ? ab : throw_gs(env, rc);
 }
 
+/* pick(handle, queries ( Uint32Array x,y pairs ), maxContrib) -> {results: ArrayBuffer (48 bytes per query), contrib: ArrayBuffer | null} */
+static napi_value js_pick(napi_env env, napi_callback_info info) {
+    size_t argc = 3;
+    napi_value argv[3];
+    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    gs_ctx* ctx = argc >= 2 ? unwrap(env, argv[0]) : NULL;
+    if (!ctx) return NULL;
+    void* q = NULL;
+    size_t qlen = 0;
+    if (!get_bytes(env, argv[1], &q, &qlen) || qlen % sizeof(gs_pick_query) != 0) {
+        napi_throw_type_error(env, NULL, "gsplat: pick expects a Uint32Array of x,y pairs");
+        return NULL;
+    }
+    uint32_t max_contrib = 0;
+    if (argc >= 3) NAPI_CALL(env, napi_get_value_uint32(env, argv[2], &max_contrib));
+    const size_t n = qlen / sizeof(gs_pick_query);
+    if (n == 0 || n > GS_PICK_MAX_QUERIES || max_contrib > GS_PICK_MAX_CONTRIB) { /* (they size the buffers below) */
+        napi_throw_range_error(env, NULL, "gsplat: pick takes 1..65536 queries and maxContrib 0..256");
+        return NULL;
+    }
+    void *res = NULL, *con = NULL;
+    napi_value res_ab, con_ab, out;
+    NAPI_CALL(env, napi_create_arraybuffer(env, n * sizeof(gs_pick_result), &res, &res_ab));
+    if (max_contrib) NAPI_CALL(env, napi_create_arraybuffer(env, n * max_contrib * sizeof(gs_pick_contrib), &con, &con_ab));
+    else NAPI_CALL(env, napi_get_null(env, &con_ab));
+    int32_t rc = gs_pick(ctx, (const gs_pick_query*)q, (uint32_t)n, (gs_pick_result*)res, max_contrib, (gs_pick_contrib*)con);
+    if (rc != GS_OK) return throw_gs(env, rc);
+    NAPI_CALL(env, napi_create_object(env, &out));
+    NAPI_CALL(env, napi_set_named_property(env, out, "results", res_ab));
+    NAPI_CALL(env, napi_set_named_property(env, out, "contrib", con_ab));
+    return out;
+}
+
 static void set_num(napi_env env, napi_value obj, const char* k, double v) {
     napi_value n;
     napi_create_double(env, v, &n);
@@ -564,7 +597,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"renderSync", js_render_sync}, {"renderAsync", js_render_async}, {"readRgba8", js_read_rgba8},
         {"readBuffer", js_read_buffer}, {"stats", js_stats},             {"slab", js_slab},
         {"loadPly", js_load_ply},    {"shareSplats", js_share},       {"uploadPly", js_upload_ply},
-        {"hostAlloc", js_host_alloc}, {"renderToSink", js_render_to_sink},
+        {"hostAlloc", js_host_alloc}, {"renderToSink", js_render_to_sink}, {"pick", js_pick},
     };
     for (size_t i = 0; i < sizeof(fns) / sizeof(fns[0]); ++i) {
         napi_value f;
@@ -578,6 +611,11 @@ static napi_value init(napi_env env, napi_value exports) {
     set_num(env, exports, "FLAG_AUX_OUTPUTS", GS_FLAG_AUX_OUTPUTS);
     set_num(env, exports, "BUF_ALPHA_F32", GS_BUF_ALPHA_F32);
     set_num(env, exports, "BUF_DEPTH_F32", GS_BUF_DEPTH_F32);
+    set_num(env, exports, "PICK_OK", GS_PICK_OK);
+    set_num(env, exports, "PICK_OUTSIDE_SLAB", GS_PICK_OUTSIDE_SLAB);
+    set_num(env, exports, "PICK_NONE", GS_PICK_NONE);
+    set_num(env, exports, "PICK_MAX_QUERIES", GS_PICK_MAX_QUERIES);
+    set_num(env, exports, "PICK_MAX_CONTRIB", GS_PICK_MAX_CONTRIB);
     return exports;
 }
 

@@ -34,12 +34,22 @@ GS_OPT_FRAMES_IN_FLIGHT = 8
 GS_OPT_FRAME_GRAPH = 9
 GS_OPT_PROJ_CHUNKS = 10
 
+GS_ERR_INVALID_ARGUMENT = -1
+GS_ERR_NO_FRAME = -6
+
+# gs_pick
+GS_PICK_OK = 0
+GS_PICK_OUTSIDE_SLAB = 1
+GS_PICK_NONE = 0xFFFFFFFF
+GS_PICK_MAX_QUERIES = 65536
+GS_PICK_MAX_CONTRIB = 256
+
 # every symbol include/gsplat/gs_abi.h declares
 ABI_SYMBOLS = ("gs_last_error", "gs_abi_version", "gs_create", "gs_destroy", "gs_upload_splats", "gs_upload_splats_device",
                "gs_share_splats",
                "gs_ply_load", "gs_ply_free", "gs_upload_ply",
                "gs_render", "gs_render_debug", "gs_render_to", "gs_wait", "gs_render_host", "gs_wait_ticket", "gs_host_alloc", "gs_host_free", "gs_read_rgba8", "gs_read_buffer", "gs_device_ptr",
-               "gs_get_stats", "gs_set_option", "gs_slab_width", "gs_assemble_slabs", "gs_sort_pairs_u32",
+               "gs_get_stats", "gs_pick", "gs_set_option", "gs_slab_width", "gs_assemble_slabs", "gs_sort_pairs_u32",
                "gs_exclusive_scan_u32")
 
 
@@ -58,6 +68,26 @@ class GsStats(ctypes.Structure):
                 ("capacity", ctypes.c_uint64), ("max_intersections_seen", ctypes.c_uint64), ("truncated_frames", ctypes.c_uint64),
                 ("tight_binning", ctypes.c_uint32), ("frames_in_flight", ctypes.c_uint32), ("graph_frames", ctypes.c_uint64),
                 ("num_row_items", ctypes.c_uint64), ("num_row_slots", ctypes.c_uint64), ("row_capacity", ctypes.c_uint64)]
+
+
+class GsPickQuery(ctypes.Structure):
+    _fields_ = [("x", ctypes.c_uint32), ("y", ctypes.c_uint32)]
+
+
+class GsPickResult(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_uint32), ("list_length", ctypes.c_uint32), ("hit_count", ctypes.c_uint32),
+                ("first_id", ctypes.c_uint32), ("first_depth", ctypes.c_float), ("max_id", ctypes.c_uint32),
+                ("max_weight", ctypes.c_float), ("median_id", ctypes.c_uint32), ("median_depth", ctypes.c_float),
+                ("alpha", ctypes.c_float), ("depth_acc", ctypes.c_float), ("reserved", ctypes.c_uint32)]
+
+
+class GsPickContrib(ctypes.Structure):
+    _fields_ = [("id", ctypes.c_uint32), ("weight", ctypes.c_float)]
+
+
+# numpy views of the same records (what Renderer.pick returns)
+PICK_RESULT_DTYPE = np.dtype([(n, np.float32 if t is ctypes.c_float else np.uint32) for n, t in GsPickResult._fields_])
+PICK_CONTRIB_DTYPE = np.dtype([("id", np.uint32), ("weight", np.float32)])
 
 
 class GsError(RuntimeError):
@@ -101,6 +131,7 @@ def load():
     L.gs_read_buffer.argtypes = [vp, i32, vp, u64, ctypes.POINTER(u64)]
     L.gs_device_ptr.argtypes = [vp, i32, ctypes.POINTER(vp)]
     L.gs_get_stats.argtypes = [vp, ctypes.POINTER(GsStats)]
+    L.gs_pick.argtypes = [vp, vp, u32, vp, u32, vp]
     L.gs_set_option.argtypes = [vp, i32, ctypes.c_int64]
     L.gs_slab_width.argtypes = [vp, ctypes.POINTER(u32), ctypes.POINTER(u32)]
     L.gs_assemble_slabs.argtypes = [vp, vp, ctypes.POINTER(u32), u32, u64, vp]

@@ -54,6 +54,28 @@ def slab_pixels(bounds, width, tile_size):
     return [(b0 * tile_size, min(width, b1 * tile_size)) for b0, b1 in zip(bounds[:-1], bounds[1:])]
 
 
+def merge_picks(per_rank_results):
+    """Merges the answers of all ranks to ONE query list (Renderer.pick on every rank's slab context, the same `xy`): a pixel
+    lies in exactly one slab, so for every query exactly one rank answers GS_PICK_OK and the others GS_PICK_OUTSIDE_SLAB; the
+    merged record is that rank's.  `per_rank_results`: a sequence of structured arrays (or one (world, n) array).  Raises
+    ValueError when the slabs overlap or leave a query unanswered."""
+    from . import _abi
+    parts = [np.asarray(r) for r in per_rank_results]
+    if not parts:
+        raise ValueError("merge_picks: no results")
+    if any(p.dtype != parts[0].dtype or p.shape != parts[0].shape or p.ndim != 1 for p in parts):
+        raise ValueError("merge_picks: the ranks answered different query lists")
+    allr = np.stack(parts)
+    ok = allr["status"] == _abi.GS_PICK_OK
+    if not np.all(ok | (allr["status"] == _abi.GS_PICK_OUTSIDE_SLAB)):
+        raise ValueError("merge_picks: unknown status")
+    cnt = ok.sum(axis=0)
+    if np.any(cnt != 1):
+        q = int(np.flatnonzero(cnt != 1)[0])
+        raise ValueError("merge_picks: query %d was answered by %d ranks (the slabs must tile the canvas)" % (q, int(cnt[q])))
+    return allr[np.argmax(ok, axis=0), np.arange(allr.shape[1])]
+
+
 class SlabExchange:
     """Gathers per-rank slab images and assembles the frame.  Works on any torch.distributed backend
     (tested with gloo on CPU); on GPUs the assembly runs in the library (gs_assemble_slabs)."""
@@ -110,6 +132,13 @@ class SlabExchange:
                 dist.all_gather(list(gathered.view(self.world, self.stride).unbind(0)), send)
         else:
             dist.all_gather_into_tensor(gathered, send)
+
+    def gather_picks(self, results):
+        """Every rank's Renderer.pick answer to the same query list -> the merged answer (merge_picks), on every rank."""
+        import torch.distributed as dist
+        parts = [None] * self.world
+        dist.all_gather_object(parts, np.asarray(results))  # 48-byte records; a few per second, not per frame
+        return merge_picks(parts)
 
     def assemble(self, gathered=None):
         """Column slabs -> row-major frame (self.image)."""

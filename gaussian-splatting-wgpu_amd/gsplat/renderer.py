@@ -155,6 +155,47 @@ class Renderer:
         np.divide(d, a, out=out, where=a > 0)
         return out
 
+    def pick(self, xy, max_contrib=0):
+        """gs_pick: which splats lie under the canvas pixels `xy` (an (n, 2) integer array of x, y) in the last frame.  Returns a
+        structured array (_abi.PICK_RESULT_DTYPE: status, list_length, hit_count, first_id / first_depth, max_id / max_weight,
+        median_id / median_depth, alpha, depth_acc), one record per query; with max_contrib > 0 also an (n, max_contrib) array of
+        the first accepted entries {id, weight} in list order (unused slots {GS_PICK_NONE, 0}).  The answer is the canonical
+        (EXACT) blend's, whatever blend the frame used.  At most 65536 queries per call (pick_rect chunks)."""
+        q = np.asarray(xy)
+        if q.ndim != 2 or q.shape[1] != 2 or q.dtype.kind not in "iu":
+            raise ValueError("pick: xy must be an (n, 2) integer array")
+        if q.size and q.min() < 0:
+            raise ValueError("pick: negative pixel coordinate")
+        if q.size and q.max() > 0xFFFFFFFF:
+            raise ValueError("pick: pixel coordinate does not fit 32 bits")
+        q = np.ascontiguousarray(q, dtype=np.uint32)
+        n, mc = q.shape[0], int(max_contrib)
+        res = np.zeros(n, dtype=_abi.PICK_RESULT_DTYPE)
+        con = np.zeros((n, mc), dtype=_abi.PICK_CONTRIB_DTYPE) if mc else None
+        check(self._L.gs_pick(self._ctx, q.ctypes.data if n else None, n, res.ctypes.data if n else None, mc,
+                              con.ctypes.data if mc and n else None))
+        return (res, con) if mc else res
+
+    def pick_rect(self, x0, y0, x1, y1, which="first"):
+        """The rectangle-select of an editor: the sorted unique ids of one field ("first", "max" or "median") over the canvas
+        pixels [x0, x1) x [y0, y1), pixels without such a splat (and, on a slab, outside it) left out."""
+        if which not in ("first", "max", "median"):
+            raise ValueError("pick_rect: which must be first, max or median")
+        x0, y0, x1, y1 = int(x0), int(y0), int(x1), int(y1)
+        if not (0 <= x0 < x1 and 0 <= y0 < y1):
+            raise ValueError("pick_rect: empty rectangle")
+        w = x1 - x0
+        rows = max(1, _abi.GS_PICK_MAX_QUERIES // w)
+        ids = [np.zeros(0, np.uint32)]
+        for ya in range(y0, y1, rows):
+            for xa in range(x0, x1, _abi.GS_PICK_MAX_QUERIES):  # (a row wider than one call is cut too)
+                xb, yb = min(x1, xa + _abi.GS_PICK_MAX_QUERIES), min(y1, ya + rows)
+                yy, xx = np.meshgrid(np.arange(ya, yb, dtype=np.uint32), np.arange(xa, xb, dtype=np.uint32), indexing="ij")
+                r = self.pick(np.stack([xx.ravel(), yy.ravel()], axis=1))
+                f = r[which + "_id"][r["status"] == _abi.GS_PICK_OK]
+                ids.append(np.unique(f[f != _abi.GS_PICK_NONE]))
+        return np.unique(np.concatenate(ids))
+
     def device_ptr(self, which):
         p = ctypes.c_void_p()
         check(self._L.gs_device_ptr(self._ctx, which, ctypes.byref(p)))
@@ -242,6 +283,10 @@ class PipelinedRenderer:
     def read_depth(self, slot, normalized=False):
         self.wait(slot)
         return self.renderers[slot].read_depth(normalized)
+
+    def pick(self, slot, xy, max_contrib=0):
+        self.wait(slot)
+        return self.renderers[slot].pick(xy, max_contrib)
 
     def set_option(self, key, value):
         for r in self.renderers:

@@ -35,8 +35,25 @@ export class Renderer {
   readAlpha(): Float32Array;
   /** FLAG.AUX_OUTPUTS: the last frame's accumulated depth D, or D / alpha where alpha > 0 (else 0) with normalized = true. */
   readDepth(normalized?: boolean): Float32Array;
+  /** gs_pick on the last frame: queries = x,y pairs of canvas pixels (at most 65536 pairs); the canonical (EXACT) blend's answer. */
+  pick(queries: Uint32Array, maxContrib?: number): PickResult;
   stats(): { numGaussians: number; numVisible: number; numIntersections: number; numProcessed: number; numTiles: number; sortPasses: number; frames: number; frameUs: number; stageUs: number[]; numEvaluated: number; depthOrdered: number; tightBinning: number; graphFrames: number; capacity: number; maxIntersectionsSeen: number; truncatedFrames: number };
 }
+export interface PickRecord {
+  status: number; listLength: number; hitCount: number; firstId: number; firstDepth: number; maxId: number; maxWeight: number;
+  medianId: number; medianDepth: number; alpha: number; depthAcc: number; reserved: number; contrib?: { id: number; weight: number }[];
+}
+export class PickResult {
+  readonly count: number; readonly maxContrib: number;
+  /** count records of 48 bytes (gs_pick_result); u32 / f32 view the same bytes, word 12 q + PICK_FIELD.x. */
+  readonly bytes: ArrayBuffer; readonly u32: Uint32Array; readonly f32: Float32Array;
+  /** count * maxContrib records {id, weight}: contribId[2 i], contribWeight[2 i + 1]; null when maxContrib = 0. */
+  readonly contribBytes: ArrayBuffer | null; readonly contribId: Uint32Array | null; readonly contribWeight: Float32Array | null;
+  get(q: number): PickRecord;
+}
+export const PICK: { OK: 0; OUTSIDE_SLAB: 1; NONE: 0xFFFFFFFF; MAX_QUERIES: 65536; MAX_CONTRIB: 256 };
+export const PICK_FIELD: { status: 0; listLength: 1; hitCount: 2; firstId: 3; firstDepth: 4; maxId: 5; maxWeight: 6; medianId: 7; medianDepth: 8;
+                           alpha: 9; depthAcc: 10; reserved: 11 };
 export function loadFileAsArrayBuffer(path: string): Promise<ArrayBuffer>;
 export function cameraFromJSON(raw: CameraRaw, canvasW: number, canvasH: number): Camera;
 export function loadCameraFile(path: string, canvas?: CanvasLike): { name: string; camera: Camera }[];

@@ -145,7 +145,48 @@ class Renderer {
     for (let i = 0; i < d.length; ++i) d[i] = a[i] > 0 ? d[i] / a[i] : 0;
     return d;
   }
+  // gs_pick: which splats lie under canvas pixels of the last frame.  queries: Uint32Array of x,y pairs (at most 65536 pairs per call);
+  // maxContrib > 0 also returns the first accepted entries of every pixel.  The result holds typed-array views over the native
+  // 48-byte records (u32 and f32 share the bytes: word 12 q + k, see FIELD) and get(q), which decodes one record.
+  pick(queries, maxContrib = 0) {
+    if (!(queries instanceof Uint32Array) || queries.length % 2 !== 0) throw new TypeError('gsplat: pick expects a Uint32Array of x,y pairs');
+    const n = loadNative();
+    const raw = n.pick(this.handle, queries, maxContrib >>> 0);
+    return new PickResult(raw.results, raw.contrib, queries.length / 2, maxContrib >>> 0);
+  }
   stats() { return loadNative().stats(this.handle); }
 }
 
-module.exports = { Renderer, loadNative };
+const PICK = { OK: 0, OUTSIDE_SLAB: 1, NONE: 0xFFFFFFFF, MAX_QUERIES: 65536, MAX_CONTRIB: 256 };
+// word index of every field of a 48-byte gs_pick_result
+const PICK_FIELD = { status: 0, listLength: 1, hitCount: 2, firstId: 3, firstDepth: 4, maxId: 5, maxWeight: 6, medianId: 7, medianDepth: 8,
+                     alpha: 9, depthAcc: 10, reserved: 11 };
+const PICK_F32 = new Set(['firstDepth', 'maxWeight', 'medianDepth', 'alpha', 'depthAcc']);
+class PickResult {
+  constructor(results, contrib, count, maxContrib) {
+    this.count = count;
+    this.maxContrib = maxContrib;
+    this.bytes = results;                  // ArrayBuffer: count records of 48 bytes (gs_pick_result)
+    this.u32 = new Uint32Array(results);   // word 12 q + PICK_FIELD.x for the integer fields
+    this.f32 = new Float32Array(results);  // ... and for the float fields
+    this.contribBytes = contrib;           // ArrayBuffer | null: count * maxContrib records {id u32, weight f32}
+    this.contribId = contrib ? new Uint32Array(contrib) : null;      // word 2 (q maxContrib + k)
+    this.contribWeight = contrib ? new Float32Array(contrib) : null; // word 2 (q maxContrib + k) + 1
+  }
+  get(q) {
+    if (!(q >= 0 && q < this.count)) throw new RangeError('gsplat: pick result index out of range');
+    const o = {};
+    for (const [k, w] of Object.entries(PICK_FIELD)) o[k] = PICK_F32.has(k) ? this.f32[12 * q + w] : this.u32[12 * q + w];
+    if (this.contribId) {
+      o.contrib = [];
+      for (let k = 0; k < this.maxContrib; ++k) {
+        const i = 2 * (q * this.maxContrib + k);
+        if (this.contribId[i] === PICK.NONE) break;
+        o.contrib.push({ id: this.contribId[i], weight: this.contribWeight[i + 1] });
+      }
+    }
+    return o;
+  }
+}
+
+module.exports = { Renderer, loadNative, PickResult, PICK, PICK_FIELD };

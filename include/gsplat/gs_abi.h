@@ -212,6 +212,55 @@ int32_t gs_read_buffer(gs_ctx* ctx, int32_t which, void* dst, uint64_t size, uin
 /* Device address of a tap (valid until the next gs_render / gs_destroy), for zero-copy consumers. */
 int32_t gs_device_ptr(gs_ctx* ctx, int32_t which, void** d_ptr);
 int32_t gs_get_stats(gs_ctx* ctx, gs_stats* out);
+/* ---- picking: which splat is under a pixel of the LAST frame ------------------------------------
+ * The planes of GS_FLAG_AUX_OUTPUTS tell how opaque a pixel is and how far its colour lies on average; they cannot tell WHICH
+ * splat the user clicked.  gs_pick answers that for up to 65536 pixels per call by walking, for each of them, its tile's list of
+ * the last frame (GS_BUF_VALUES / GS_BUF_RANGES / GS_BUF_GAUSSIAN_DATA, still resident) with the blend's own arithmetic,
+ * compute_tiles.wgsl:44-66 restated: per entry  d = uv * (W, H) - pixel,  power = -0.5 (cx dx dx + cz dy dy) - cy dx dy,
+ * alpha = min(0.99, opacity exp(power)),  test = T (1 - alpha),  cond = power <= 0 && alpha >= 1/255 && test >= 1e-4
+ * (:60-63),  T = cond test + (1 - cond) T (:65).  An entry with cond = 1 is ACCEPTED; its weight is w = alpha T with T taken
+ * before the entry.  The reference has no early termination: an entry rejected by test < 1e-4 may be followed by an accepted one.
+ * The results are DEFINED by the canonical (GS_FLAG_EXACT_BLEND) arithmetic -- one f32 rounding per written operation, the
+ * oracle's exp -- whatever blend the frame itself used: on a default (fused) frame they are the canonical answer, which differs
+ * from what the fused kernel accumulated by its documented <= 1e-4 envelope; on an EXACT frame `alpha` and `depth_acc` equal
+ * GS_BUF_ALPHA_F32 / GS_BUF_DEPTH_F32 bit for bit.  Every field is the same for tight and reference binning (a tight list drops
+ * only entries no pixel of the tile accepts), gs_render and gs_render_debug, and every GS_OPT_EMIT_ORDER -- except list_length,
+ * which describes the lists actually rendered.  The reference has no picking (a viewer, not an editor). */
+#define GS_PICK_OK 0u
+#define GS_PICK_OUTSIDE_SLAB 1u
+#define GS_PICK_NONE 0xFFFFFFFFu
+#define GS_PICK_MAX_QUERIES 65536u
+#define GS_PICK_MAX_CONTRIB 256u
+typedef struct gs_pick_query { uint32_t x, y; } gs_pick_query; /* CANVAS pixel coordinates */
+typedef struct gs_pick_result { /* 48 bytes */
+    uint32_t status;       /* GS_PICK_OK; GS_PICK_OUTSIDE_SLAB: x is on the canvas but not in this ctx's slab (every other field
+                              0 / GS_PICK_NONE), so a multi-GPU host can send one query list to every rank                   */
+    uint32_t list_length;  /* entries of the pixel's tile list in the frame that was rendered                               */
+    uint32_t hit_count;    /* entries the blend accepts at this pixel (cond = 1, compute_tiles.wgsl:60-63)                   */
+    uint32_t first_id;     /* gaussian index of the first accepted entry; GS_PICK_NONE if hit_count = 0                      */
+    float first_depth;     /* its GaussianData.depth; 0 if none                                                             */
+    uint32_t max_id;       /* accepted entry with the largest weight w (one f32 product alpha * T); the EARLIEST on ties;
+                              GS_PICK_NONE if none                                                                          */
+    float max_weight;      /* that w; 0 if none                                                                             */
+    uint32_t median_id;    /* first accepted entry after which T <= 0.5; GS_PICK_NONE if T never gets there.  Unlike the mean
+                              depth_acc / alpha, the median always lies on a surface: the orbit pivot / "focus here" depth     */
+    float median_depth;    /* its GaussianData.depth; 0 if none                                                             */
+    float alpha;           /* 1 - T_final: what GS_BUF_ALPHA_F32 holds for an EXACT frame                                    */
+    float depth_acc;       /* sum of cond z alpha T in list order: what GS_BUF_DEPTH_F32 holds for an EXACT frame            */
+    uint32_t reserved;     /* 0                                                                                             */
+} gs_pick_result;
+typedef struct gs_pick_contrib { uint32_t id; float weight; } gs_pick_contrib;
+/* Answers `n` (1..GS_PICK_MAX_QUERIES) queries about the LAST frame enqueued (its ring member, like gs_read_buffer), waiting for
+ * it first if it is still pending.  HOST pointers in and out (there is no device-pointer variant yet); `results` has n records.
+ * `contrib` may be NULL (then max_contrib must be 0); otherwise max_contrib is 1..GS_PICK_MAX_CONTRIB and `contrib` has
+ * n * max_contrib records: for query q, at contrib[q * max_contrib], the first min(hit_count, max_contrib) accepted entries in
+ * list order with their weights, the remaining slots {GS_PICK_NONE, 0}.  One wave per query on the frame's own stream; the call
+ * returns with the results on the host.  It is not a frame: no statistic, tap or option changes and a captured frame graph
+ * stays valid.  GS_ERR_INVALID_ARGUMENT (the message names the query) for a pixel outside the canvas, GS_ERR_NO_FRAME when no
+ * frame has been rendered since gs_create / the last upload. */
+int32_t gs_pick(gs_ctx* ctx, const gs_pick_query* queries, uint32_t n, gs_pick_result* results, uint32_t max_contrib,
+                gs_pick_contrib* contrib);
+
 /* Tuning / profiling knobs. */
 #define GS_OPT_BLEND_ABLATION 1  /* bit 3 (8): the workgroup-per-tile blend kernel at tiles 16 and 32 (identical results; default = one
                                     wave per 8x8 pixel block); bit 2 (4): every blend kernel without its two parking culls (live box,
