@@ -45,7 +45,7 @@ void gs_launch_assemble(const void* slabs, void* image, uint32_t width, uint32_t
 uint32_t gs_gsort_tiles(uint32_t n);
 uint64_t gs_gsort_scratch_bytes(uint32_t n);
 void gs_launch_gsort(const uint32_t* words, const uint32_t* aux_in, uint32_t n, void* scratch, void* grec, uint32_t* chunk_table, uint32_t chunk_cap,
-                     uint32_t* tot_visible, uint32_t* tot_quantity, hipStream_t st);
+                     uint32_t* tot_visible, uint32_t* tot_quantity, uint32_t grid, hipStream_t st);
 // k_rows.hip: the tight row pipeline (row sort, per-chunk counts, scan, expansion into the final per-tile lists + ranges)
 uint32_t gs_rows_sort_tiles(uint64_t row_cap);
 uint32_t gs_rows_chunks(uint64_t row_cap);

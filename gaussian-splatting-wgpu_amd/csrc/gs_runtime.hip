@@ -126,7 +126,7 @@ struct gs_ctx {
     uint32_t* rows_status = nullptr;            // row sort (tight row pipeline)
     void* grec = nullptr;                       // visible gaussians in (depth bucket, index) order: {id, count word, prefix, arena address} (k_gsort.hip)
     uint32_t tight_nb = 0;                      // GS_OPT_PROJ_CHUNKS: cull chunks per workgroup of the tight projection (0 = automatic)
-    void* gsort_scratch = nullptr;              // (bucket, chunk) table of the gaussian-level counting sort
+    void* gsort_scratch = nullptr;              // (bucket, run) table of the gaussian-level counting sort
     // tight row pipeline (k_rows.hip): row items in projection order / sorted by tile row, slot addresses in depth order
     uint64_t row_cap = 0;
     uint32_t *arena = nullptr, *rows_sorted = nullptr, *rowptr = nullptr;
@@ -490,7 +490,7 @@ static int32_t record_frame(gs_ctx* c, const GsUniforms& u, bool debug, void* ex
         // row sort (the row items take write_tile_ids' place), "sort" = count + scan + expansion into the final lists,
         // "ranges" = nothing (they fall out of the scan).
         gs_launch_gsort(c->counts, c->rowptr, c->n, c->gsort_scratch, c->grec, c->chunk_table, (uint32_t)gs_emit_chunks(std::max(c->capacity, c->row_cap)),
-                        &c->ctl->num_visible, &c->ctl->num_slots, st);
+                        &c->ctl->num_visible, &c->ctl->num_slots, c->grid_persist, st);
         mark(c, 2);
         gs_launch_rows(c->arena, c->grec, c->chunk_table, c->rows_sorted, c->ctl, c->rows_status, (uint32_t)c->row_cap, c->M3, c->tileoff, c->rowtot, f, c->valsA,
                        c->ranges, c->grid_persist / 4u, c->sticky, c->h_rep, st, mark_cb, c);
@@ -508,7 +508,7 @@ static int32_t record_frame(gs_ctx* c, const GsUniforms& u, bool debug, void* ex
         // than instances: k_gsort.hip) and emitting their instances in that order leaves only the tile id for the stable
         // instance sort: 2 digits of key/1000 instead of 3 of the key.  The sorted (key,value) arrays are identical.
         gs_launch_gsort(c->counts, nullptr, c->n, c->gsort_scratch, c->grec, c->chunk_table, (uint32_t)gs_emit_chunks(std::max(c->capacity, c->row_cap)),
-                        &c->ctl->num_visible, &c->ctl->num_intersections, st);
+                        &c->ctl->num_visible, &c->ctl->num_intersections, c->grid_persist, st);
         mark(c, 2);
         gs_launch_emit_balanced(c->gdata, c->grec, c->chunk_table, f, c->keysA, c->valsA, c->ctl, c->grid_persist * 2,
                                 c->tile_bits, c->tile_passes, c->tile16, st);

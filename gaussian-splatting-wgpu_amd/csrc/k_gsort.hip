@@ -7,17 +7,33 @@
 // leaves only the tile id for the stable instance binning.
 //
 // Round 2 fed this stage from a chained look-back scan that compacted the visible gaussians (31 us for 24 MB, bound by the
-// chain) and counted buckets over tiles of the COMPACTED list (4 launches, 85 us).  Here the tiles are chunks of 2048
-// consecutive gaussian INDICES, so nothing has to be compacted or scanned beforehand and no workgroup waits for another:
-//   hist     every chunk counts the buckets of its visible gaussians      -> M[bucket][chunk] = (gaussians, quantity)
-//   rowscan  every bucket's row of M is scanned over the chunks (exclusive) -> row totals
-//   scatter  every chunk compacts its visible gaussians (index order), ranks them by bucket (wave ballots, stable), reorders
-//            them through LDS, scans their quantity in that order and writes one record {id, word, prefix, aux} per gaussian
-//            at  base[bucket] + M[bucket][chunk] + rank;  plus the chunk table (first gaussian of every 1024 units of the
-//            quantity) that the reference-binning emission and the row sort of the tight pipeline (k_rows.hip) start from.
-// Position in (bucket, index) order = bucket base + gaussians of that bucket in earlier chunks + rank inside the chunk: the
-// chunks are index ranges, so the order inside a bucket is the index order the reference's stable sort keeps.
-// All three are HBM-trivial (24-50 MB); what they cost is their launches.
+// chain) and counted buckets over tiles of the COMPACTED list (4 launches, 85 us).  Here the unit of work is a chunk of 2048
+// consecutive gaussian INDICES, so nothing has to be compacted or scanned beforehand and no workgroup waits for another.  The
+// NT chunks are cut into G contiguous RUNS of ceil(NT / G) chunks (G = the context's persistent grid, about one workgroup
+// per residency slot of the scatter); one workgroup owns a run in hist and in scatter, and the (bucket, run) table M has one
+// column per RUN: a (chunk, bucket) cell holds 0.8 gaussians on average at 6.1 M, so a per-chunk table was bigger than the
+// data it indexed.  When NT <= G a run is one chunk.
+//   hist     every run counts the buckets of its visible gaussians, chunk after chunk into ONE LDS histogram
+//                                                                          -> M[bucket][run] = (gaussians, quantity)
+//   rowscan  every bucket's row of M is scanned over the runs (exclusive)  -> row totals
+//   scatter  every run builds its bucket bases once (scan of the row totals + its column of M), then walks its chunks in
+//            ascending order: rank the chunk's visible gaussians by bucket where they are (wave ballots; a wave's items are
+//            in index order, so the rank is stable), reorder them through LDS, scan their quantity in that order and write
+//            one record {id, word, prefix, aux} per gaussian at  base[bucket] + rank;  then base[bucket] advances by the
+//            chunk's own (count, quantity) of the bucket.  Plus the chunk table (first gaussian of every 1024 units of the quantity) that the reference-binning
+//            emission and the row sort of the tight pipeline (k_rows.hip) start from.
+// Position in (bucket, index) order = bucket base + gaussians of the bucket in earlier runs (the table) + gaussians of the
+// bucket in earlier chunks of this run (carried in the base) + stable rank inside the chunk: runs and chunks are ascending
+// index ranges, so the order inside a bucket is the gaussian index order, which is what write_tile_ids.wgsl:31 plus a stable
+// sort gives.  The table is written by one kernel and read by the next: launch boundaries are the only ordering needed.
+//
+// Saturation.  Quantities are summed in 64 bits and stored as sat32(sum).  For non-negative terms
+// sat32(sat32(a) + b) == sat32(a + b), so the carried base stays 32 bits wide in LDS (a 64-bit base would cost 4 KB and the
+// fourth workgroup of a CU) and still equals sat32(true 64-bit base) at every chunk: `off`, the chunk table and the totals
+// saturate exactly where a per-chunk table made them saturate.  The one step that needs care is the chunk's own quantity of a
+// bucket, read from the saturated in-chunk prefix P: if P at the bucket's END is saturated the new base is saturated as well,
+// because the base of a bucket already counts every earlier bucket of this chunk (base >= P at the bucket's START), so
+// base + (end - start) >= P(end) >= 2^32 - 1; otherwise both P values are exact.
 #include "gs_device.h"
 
 #define GC_ITEMS 8
@@ -25,35 +41,55 @@
 #define GC (GC_THREADS * GC_ITEMS) // gaussian indices per chunk
 #define GBINS 1024                 // bucket = u32(min(50 depth, 999)) < 1000 (write_tile_ids.wgsl:31)
 #define GS_EMIT_CHUNK_SHIFT 10     // = EMIT_CHUNK_SHIFT of k_binning.hip
-// The (bucket, chunk) table is stored [bucket / 8][chunk][bucket % 8]: the 1024 entries a chunk's workgroup writes (hist) or
+#ifndef GS_GSORT_RUNS_Q
+#define GS_GSORT_RUNS_Q 4          // runs = persistent grid * Q / 4 (swept 2 / 3 / 4 / 8: profiles/README.md)
+#endif
+// The (bucket, run) table is stored [bucket / 8][run][bucket % 8]: the 1024 entries a run's workgroup writes (hist) or
 // reads (scatter) are 128 whole 64-byte sectors instead of 1024 partial ones, and a bucket's row is still a strided stream.
-__device__ __forceinline__ uint64_t m_index(uint32_t b, uint32_t chunk, uint32_t NT) { return ((uint64_t)(b >> 3) * NT + chunk) * 8u + (b & 7u); }
+__device__ __forceinline__ uint64_t m_index(uint32_t b, uint32_t col, uint32_t ncol) { return ((uint64_t)(b >> 3) * ncol + col) * 8u + (b & 7u); }
 
 __device__ __forceinline__ uint32_t sat32(unsigned long long v) { return v > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)v; }
 
-__global__ __launch_bounds__(GC_THREADS) void gs_gsort_hist_kernel(const uint32_t* __restrict__ words, uint32_t n, uint2* __restrict__ M, uint32_t NT) {
+// One workgroup per run: chunks [run * cpr, min((run + 1) * cpr, NT)); the loads of chunk k + 1 are issued before the LDS
+// atomics of chunk k.
+__global__ __launch_bounds__(GC_THREADS) void gs_gsort_hist_kernel(const uint32_t* __restrict__ words, uint32_t n, uint2* __restrict__ M, uint32_t ncol,
+                                                                   uint32_t cpr, uint32_t NT) {
     __shared__ uint32_t s_cnt[GBINS];
-    __shared__ unsigned long long s_sum[GBINS]; // a chunk's quantity can exceed 32 bits (4096 x 2^22 tiles): saturated on store
-    const uint32_t chunk = blockIdx.x, tid = threadIdx.x;
+    __shared__ unsigned long long s_sum[GBINS]; // a run's quantity can exceed 32 bits (2048 x 2^22 tiles a chunk): saturated on store
+    const uint32_t run = blockIdx.x, tid = threadIdx.x;
+    const uint32_t c0 = run * cpr, c1 = c0 + cpr < NT ? c0 + cpr : NT;
     for (uint32_t b = tid; b < GBINS; b += GC_THREADS) { s_cnt[b] = 0u; s_sum[b] = 0ull; }
-    __syncthreads();
+    uint32_t wv[GC_ITEMS];
 #pragma unroll
     for (int j = 0; j < GC_ITEMS; ++j) {
-        const uint32_t k = chunk * GC + j * GC_THREADS + tid;
-        if (k < n) {
-            const uint32_t w = words[k];
+        const uint32_t k = c0 * GC + j * GC_THREADS + tid;
+        wv[j] = (k < n) ? words[k] : 0u;
+    }
+    __syncthreads();
+    for (uint32_t c = c0; c < c1; ++c) {
+        uint32_t nx[GC_ITEMS];
+#pragma unroll
+        for (int j = 0; j < GC_ITEMS; ++j) {
+            const uint32_t k = (c + 1u) * GC + j * GC_THREADS + tid;
+            nx[j] = (c + 1u < c1 && k < n) ? words[k] : 0u;
+        }
+#pragma unroll
+        for (int j = 0; j < GC_ITEMS; ++j) {
+            const uint32_t w = wv[j];
             if (w & GS_COUNT_MASK) {
                 const uint32_t b = w >> GS_COUNT_BITS;
                 atomicAdd(&s_cnt[b], 1u);
                 atomicAdd(&s_sum[b], (unsigned long long)(w & GS_COUNT_MASK));
             }
         }
+#pragma unroll
+        for (int j = 0; j < GC_ITEMS; ++j) wv[j] = nx[j];
     }
     __syncthreads();
 #pragma unroll
     for (uint32_t i = 0; i < GBINS / GC_THREADS; ++i) { // thread t: buckets 4t .. 4t+3 (32 contiguous bytes)
         const uint32_t b = tid * (GBINS / GC_THREADS) + i;
-        M[m_index(b, chunk, NT)] = make_uint2(s_cnt[b], sat32(s_sum[b]));
+        M[m_index(b, run, ncol)] = make_uint2(s_cnt[b], sat32(s_sum[b]));
     }
 }
 
@@ -87,8 +123,28 @@ __device__ __forceinline__ GsPair block_excl2(GsPair v, uint32_t tid, GsPair* s_
     return r;
 }
 
-// One workgroup of 1024 threads per 8 buckets (one 64-byte sector per chunk): thread (cl = t / 8, sub = t % 8) owns the chunks
-// [cl * per, (cl + 1) * per) of bucket 8 * blockIdx + sub -- a dozen at 6.1 M gaussians, two batches of independent loads; the
+// The scans inside a chunk need 32 bits inside a wave (DPP adds, no LDS shuffles): bucket counts sum to <= 2048, a thread's
+// eight quantities to < 2^25 and 64 of those to < 2^31; only the sum over the four waves can need more (A = 64 bits there).
+template <typename A>
+__device__ __forceinline__ A block_excl_u32(uint32_t v, uint32_t tid, uint32_t* s_w /*[GC_THREADS / 64]*/, A& total) {
+    const uint32_t lane = tid & 63, w = tid >> 6;
+    const uint32_t iv = wave_incl_scan(v, lane);
+    if (lane == 63) s_w[w] = iv;
+    __syncthreads();
+    A base = 0;
+    total = 0;
+#pragma unroll
+    for (int k = 0; k < GC_THREADS / 64; ++k) {
+        const uint32_t t = s_w[k];
+        if (k < (int)w) base += t;
+        total += t;
+    }
+    __syncthreads();
+    return base + (iv - v);
+}
+
+// One workgroup of 1024 threads per 8 buckets (one 64-byte sector per run): thread (cl = t / 8, sub = t % 8) owns the runs
+// [cl * per, (cl + 1) * per) of bucket 8 * blockIdx + sub -- eight at 1024 runs, one batch of independent loads; the
 // 128 partial sums of a bucket are scanned by lane shifts of 8 inside a wave and through LDS across the 16 waves.
 #define GR_THREADS 1024
 __device__ __forceinline__ void scan_stride8(uint32_t& x, unsigned long long& y, uint32_t lane) { // inclusive over lanes l, l-8, l-16, ...
@@ -98,13 +154,13 @@ __device__ __forceinline__ void scan_stride8(uint32_t& x, unsigned long long& y,
         if ((int)lane >= d) { x += ox; y += ((unsigned long long)hi << 32) | lo; }
     }
 }
-__global__ __launch_bounds__(GR_THREADS) void gs_gsort_rowscan_kernel(uint2* __restrict__ M, uint32_t NT, uint32_t n, uint2* __restrict__ rowtot) {
+__global__ __launch_bounds__(GR_THREADS) void gs_gsort_rowscan_kernel(uint2* __restrict__ M, uint32_t ncol, uint2* __restrict__ rowtot) {
     __shared__ uint32_t s_x[GR_THREADS / 64][8];
     __shared__ unsigned long long s_y[GR_THREADS / 64][8];
-    const uint32_t nt = (n + GC - 1) / GC, tid = threadIdx.x, lane = tid & 63, w = tid >> 6, cl = tid >> 3, sub = tid & 7u;
+    const uint32_t nt = ncol, tid = threadIdx.x, lane = tid & 63, w = tid >> 6, cl = tid >> 3, sub = tid & 7u;
     const uint32_t per = (nt + GR_THREADS / 8 - 1u) / (GR_THREADS / 8);
     const uint32_t c0 = cl * per < nt ? cl * per : nt, c1 = (cl + 1u) * per < nt ? (cl + 1u) * per : nt;
-    uint2* row = M + (uint64_t)blockIdx.x * NT * 8u + sub;
+    uint2* row = M + (uint64_t)blockIdx.x * ncol * 8u + sub;
     uint32_t ax = 0;
     unsigned long long ay = 0;
     for (uint32_t c = c0; c < c1; c += 8u) {
@@ -141,52 +197,70 @@ __global__ __launch_bounds__(GR_THREADS) void gs_gsort_rowscan_kernel(uint2* __r
     if (tid < 8u) rowtot[blockIdx.x * 8u + sub] = make_uint2(tx, sat32(ty));
 }
 
-struct GsortShared {
-    uint2 base[GBINS];                 // first sorted position / first quantity offset of (bucket, this chunk)
+struct alignas(16) GsortShared {
+    uint2 base[GBINS];                 // next sorted position / next quantity offset (saturated) of the bucket in this run
     unsigned short binstart[GBINS];    // first slot of the bucket in the chunk's sorted order
     union {
         unsigned short whist[GC_THREADS / 64][GBINS]; // per-wave running counts while ranking ([wave][bucket]) ...
         uint32_t P[GC];                               // ... then the prefix of the sorted quantities
+        uint4 zero[GC / 4];                           // (the counters again, for clearing them 16 bytes at a time)
     } u;
     unsigned short id[GC];             // index inside the chunk
     uint32_t word[GC], aux[GC];
     GsPair w2[GC_THREADS / 64];
-    uint32_t wcnt[GC_THREADS / 64];
+    uint32_t w1[GC_THREADS / 64];
+    uint32_t ptot;                     // P one past the last slot: the chunk's whole quantity (saturated)
 };
 static_assert(sizeof(unsigned short) * (GC_THREADS / 64) * GBINS == sizeof(uint32_t) * GC, "the ranking counters and the prefix share their storage");
+static_assert(sizeof(GsortShared) <= 40 * 1024, "four workgroups per CU");
 
 // Output: ONE 16-byte record per visible gaussian in (bucket, index) order -- {gaussian id, count word, exclusive prefix of the
 // quantity, aux} -- because a (chunk, bucket) run is about two gaussians long: four separate arrays were four scattered 4-byte
 // stores each (round 2), a record is one 16-byte store.  aux_in (optional, tight row pipeline): a second per-gaussian word
 // (the arena address of its row-item slots).  chunk_table[c] = the gaussian whose quantity interval holds c * 1024 (the
 // reference-binning emission and the row sort start there).  tot_*: visible gaussians, total quantity (saturated).
-// 38 KB of LDS: four workgroups per CU; every global load of the workgroup is issued before the first barrier.
+// One workgroup per run, 38 KB of LDS: four workgroups per CU.  The row totals, the run's table column and the first chunk
+// are loaded before the first barrier; inside the loop the next chunk's words (+ aux) are loaded into registers before the
+// current one is ranked, so only the first chunk's load latency is exposed.  Every barrier of a trip is reached by all 256
+// threads: the trip count and `nc` are uniform over the workgroup.
 __global__ __launch_bounds__(GC_THREADS) void gs_gsort_scatter_kernel(const uint32_t* __restrict__ words, const uint32_t* __restrict__ aux_in, uint32_t n,
-                                                                      const uint2* __restrict__ M, uint32_t NT, const uint2* __restrict__ rowtot,
-                                                                      uint4* __restrict__ grec, uint32_t* __restrict__ chunk_table,
-                                                                      uint32_t chunk_cap, uint32_t* __restrict__ tot_visible,
-                                                                      uint32_t* __restrict__ tot_quantity) {
+                                                                      const uint2* __restrict__ M, uint32_t ncol, uint32_t cpr, uint32_t NT,
+                                                                      const uint2* __restrict__ rowtot, uint4* __restrict__ grec,
+                                                                      uint32_t* __restrict__ chunk_table, uint32_t chunk_cap,
+                                                                      uint32_t* __restrict__ tot_visible, uint32_t* __restrict__ tot_quantity) {
     __shared__ GsortShared S;
-    const uint32_t chunk = blockIdx.x;
+    const uint32_t run_id = blockIdx.x;
+    const uint32_t chunk0 = run_id * cpr, chunk1 = chunk0 + cpr < NT ? chunk0 + cpr : NT;
     const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
     constexpr uint32_t BPT = GBINS / GC_THREADS; // buckets per thread (4 consecutive)
 
-    // ---- every global load up front: the chunk's count words (+ aux), the row totals, this chunk's entries of the table ----
-    uint32_t wv[GC_ITEMS], av[GC_ITEMS];
-    const uint32_t e0 = chunk * GC + w * (64 * GC_ITEMS) + lane; // wave w reads indices w * 512 + j * 64 + lane
+    // ---- every global load of the prologue up front: the first chunk's count words (+ aux), the row totals, the run's column ----
+    uint32_t nwv[GC_ITEMS], nav[GC_ITEMS]; // the NEXT trip's words: wave w reads indices w * 512 + j * 64 + lane of its chunk
+    const uint32_t whole = n / GC;         // chunks below this one need no bounds checks
+    auto load_chunk = [&](uint32_t c) {
+        const uint32_t k0 = c * GC + w * (64 * GC_ITEMS) + lane;
+        if (c < whole) { // (uniform)
 #pragma unroll
-    for (int j = 0; j < GC_ITEMS; ++j) {
-        const uint32_t k = e0 + j * 64;
-        wv[j] = (k < n) ? words[k] : 0u;
-        av[j] = (aux_in && k < n) ? aux_in[k] : 0u;
-    }
-    uint2 t[BPT], mm[BPT];
+            for (int j = 0; j < GC_ITEMS; ++j) nwv[j] = words[k0 + j * 64];
 #pragma unroll
-    for (uint32_t i = 0; i < BPT; ++i) { t[i] = rowtot[tid * BPT + i]; mm[i] = M[m_index(tid * BPT + i, chunk, NT)]; }
-
-    // ---- bucket bases: exclusive scan of the row totals, plus this chunk's entry of the scanned table ----
+            for (int j = 0; j < GC_ITEMS; ++j) nav[j] = aux_in ? aux_in[k0 + j * 64] : 0u;
+        } else {
+#pragma unroll
+            for (int j = 0; j < GC_ITEMS; ++j) {
+                const uint32_t k = k0 + j * 64;
+                nwv[j] = (k < n) ? words[k] : 0u;
+                nav[j] = (aux_in && k < n) ? aux_in[k] : 0u;
+            }
+        }
+    };
+    load_chunk(chunk0);
     {
+        uint2 t[BPT], mm[BPT];
+#pragma unroll
+        for (uint32_t i = 0; i < BPT; ++i) { t[i] = rowtot[tid * BPT + i]; mm[i] = M[m_index(tid * BPT + i, run_id, ncol)]; }
+
+        // ---- bucket bases: exclusive scan of the row totals, plus this run's entry of the scanned table ----
         GsPair acc; acc.x = 0u; acc.y = 0ull;
 #pragma unroll
         for (uint32_t i = 0; i < BPT; ++i) { acc.x += t[i].x; acc.y += t[i].y; }
@@ -197,170 +271,163 @@ __global__ __launch_bounds__(GC_THREADS) void gs_gsort_scatter_kernel(const uint
             S.base[tid * BPT + i] = make_uint2(run.x + mm[i].x, sat32(run.y + mm[i].y));
             run.x += t[i].x; run.y += t[i].y;
         }
-        if (chunk == 0 && tid == 0) { *tot_visible = total.x; *tot_quantity = sat32(total.y); }
+        if (run_id == 0 && tid == 0) { *tot_visible = total.x; *tot_quantity = sat32(total.y); }
     }
-    for (uint32_t k = lane; k < GBINS; k += 64) S.u.whist[w][k] = 0;
 
-    // ---- the chunk's visible gaussians, compacted in index order ----
-    uint32_t wave_vis = 0;
+    for (uint32_t chunk = chunk0; chunk < chunk1; ++chunk) {
+        // (the barrier that ends a trip, or block_excl2's above, separates the last reads of P / word / id / aux from here)
+        uint32_t wv[GC_ITEMS], av[GC_ITEMS];
 #pragma unroll
-    for (int j = 0; j < GC_ITEMS; ++j) {
-        if (!(wv[j] & GS_COUNT_MASK)) wv[j] = 0u;
-        wave_vis += (uint32_t)__popcll(__ballot(wv[j] != 0u));
-    }
-    if (lane == 0) S.wcnt[w] = wave_vis;
-    __syncthreads();
-    uint32_t cbase = 0, nc = 0;
-#pragma unroll
-    for (int k = 0; k < GC_THREADS / 64; ++k) { if (k < (int)w) cbase += S.wcnt[k]; nc += S.wcnt[k]; }
-#pragma unroll
-    for (int j = 0; j < GC_ITEMS; ++j) {
-        const unsigned long long bal = __ballot(wv[j] != 0u);
-        if (wv[j]) {
-            const uint32_t p = cbase + (uint32_t)__popcll(bal & lt_mask);
-            S.id[p] = (unsigned short)(w * (64 * GC_ITEMS) + j * 64 + lane);
-            S.word[p] = wv[j];
-            S.aux[p] = av[j];
+        for (int j = 0; j < GC_ITEMS; ++j) { wv[j] = nwv[j]; av[j] = nav[j]; }
+        if (chunk + 1u < chunk1) load_chunk(chunk + 1u); // (uniform) prefetch: consumed at the top of the next trip
+        {   // zero this wave's ranking counters (2 KB: 32 bytes a lane)
+            S.u.zero[w * (GBINS / 8) + lane] = make_uint4(0u, 0u, 0u, 0u);
+            S.u.zero[w * (GBINS / 8) + 64 + lane] = make_uint4(0u, 0u, 0u, 0u);
         }
-        cbase += (uint32_t)__popcll(bal);
-    }
-    for (uint32_t p = nc + tid; p < GC; p += GC_THREADS) S.word[p] = 0xFFFFFFFFu; // absent: bucket 1023, sorts behind every real one, never stored
-    __syncthreads();
-    if (nc == 0) return; // (uniform)
-
-    // ---- rank by bucket: wave w owns the compacted positions [w*Q, w*Q + Q), item j of lane l = w*Q + j*64 + l ----
-    const uint32_t T = (nc + GC_THREADS - 1) / GC_THREADS; // items per thread (uniform over the workgroup)
-    const uint32_t Q = T * 64;
-    uint32_t gid[GC_ITEMS], wd[GC_ITEMS], ax[GC_ITEMS];
-    uint32_t rank2[GC_ITEMS / 2];
+        // ---- rank the visible gaussians by bucket where they are: (item, lane) of wave w IS the index order ----
+        // peers = visible lanes holding the same bucket (10 ballots); rank = the wave's running count + peers below: stable
+        uint32_t rank2[GC_ITEMS / 2];
 #pragma unroll
-    for (int j = 0; j < GC_ITEMS; ++j) {
-        const uint32_t p = w * Q + j * 64 + lane;
-        const bool in = (uint32_t)j < T; // (p < GC then: T * 256 <= GC)
-        gid[j] = in ? (uint32_t)S.id[p] : 0u;
-        wd[j] = in ? S.word[p] : 0xFFFFFFFFu;
-        ax[j] = in ? S.aux[p] : 0u;
-    }
-    // peers = lanes holding the same bucket (10 ballots), order = (item, lane): stable
+        for (int j = 0; j < GC_ITEMS; ++j) {
+            if (!(wv[j] & GS_COUNT_MASK)) wv[j] = 0u;
+            const unsigned long long vis = __ballot(wv[j] != 0u);
+            uint32_t r = 0;
+            if (vis) { // (uniform over the wave)
+                const uint32_t d = wv[j] >> GS_COUNT_BITS;
+                uint32_t plo = (uint32_t)vis, phi = (uint32_t)(vis >> 32);
 #pragma unroll
-    for (int j = 0; j < GC_ITEMS; ++j) {
-        if ((uint32_t)j < T) {
-            const uint32_t d = wd[j] >> GS_COUNT_BITS;
-            uint32_t plo = 0xFFFFFFFFu, phi = 0xFFFFFFFFu;
-#pragma unroll
-            for (int b = 0; b < 10; ++b) {
-                const uint32_t bit = (d >> b) & 1u;
-                const unsigned long long bal = __ballot(bit != 0u);
-                const uint32_t inv = bit - 1u;
-                plo &= (uint32_t)bal ^ inv;
-                phi &= (uint32_t)(bal >> 32) ^ inv;
+                for (int b = 0; b < 10; ++b) {
+                    const uint32_t bit = (d >> b) & 1u;
+                    const unsigned long long bal = __ballot(bit != 0u);
+                    const uint32_t inv = bit - 1u;
+                    plo &= (uint32_t)bal ^ inv;
+                    phi &= (uint32_t)(bal >> 32) ^ inv;
+                }
+                const uint32_t below = __popc(plo & (uint32_t)lt_mask) + __popc(phi & (uint32_t)(lt_mask >> 32));
+                const uint32_t cnt = __popc(plo) + __popc(phi);
+                const uint32_t pre = S.u.whist[w][d];
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); // every peer has read `pre` before the leader's store (one wave, in-order LDS)
+                if (wv[j] && below == 0) S.u.whist[w][d] = (unsigned short)(pre + cnt);
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                r = pre + below; // < 2048
             }
-            const uint32_t below = __popc(plo & (uint32_t)lt_mask) + __popc(phi & (uint32_t)(lt_mask >> 32));
-            const uint32_t cnt = __popc(plo) + __popc(phi);
-            const uint32_t pre = S.u.whist[w][d];
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); // every peer has read `pre` before the leader's store (one wave, in-order LDS)
-            if (below == 0) S.u.whist[w][d] = (unsigned short)(pre + cnt);
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            const uint32_t r = pre + below; // < 2048
             if (j & 1) rank2[j >> 1] |= r << 16;
             else rank2[j >> 1] = r;
         }
-    }
-    __syncthreads();
-    // ---- per-wave counts -> exclusive across waves; bucket starts inside the chunk ----
-    {
-        uint32_t tot[BPT], acc = 0;
+        __syncthreads();
+        // ---- per-wave counts -> exclusive across waves; bucket starts inside the chunk; the chunk's visible gaussians ----
+        uint32_t nc;
+        {
+            uint32_t tot[BPT], acc = 0;
 #pragma unroll
-        for (uint32_t i = 0; i < BPT; ++i) {
-            const uint32_t b = tid * BPT + i;
-            uint32_t run = 0;
+            for (uint32_t i = 0; i < BPT; ++i) {
+                const uint32_t b = tid * BPT + i;
+                uint32_t run = 0;
 #pragma unroll
-            for (int k = 0; k < GC_THREADS / 64; ++k) { const uint32_t c = S.u.whist[k][b]; S.u.whist[k][b] = (unsigned short)run; run += c; }
-            tot[i] = run;
-            acc += run;
+                for (int k = 0; k < GC_THREADS / 64; ++k) { const uint32_t c = S.u.whist[k][b]; S.u.whist[k][b] = (unsigned short)run; run += c; }
+                tot[i] = run;
+                acc += run;
+            }
+            uint32_t run = block_excl_u32<uint32_t>(acc, tid, S.w1, nc);
+#pragma unroll
+            for (uint32_t i = 0; i < BPT; ++i) { S.binstart[tid * BPT + i] = (unsigned short)run; run += tot[i]; }
         }
-        GsPair total, in;
-        in.x = acc; in.y = 0ull;
-        const GsPair ex = block_excl2(in, tid, S.w2, total);
-        uint32_t run = ex.x;
-#pragma unroll
-        for (uint32_t i = 0; i < BPT; ++i) { S.binstart[tid * BPT + i] = (unsigned short)run; run += tot[i]; }
-    }
-    __syncthreads();
-    // ---- reorder through LDS (every thread holds its items in registers: the arrays can be overwritten) ----
-    uint32_t mypos[GC_ITEMS];
-#pragma unroll
-    for (int j = 0; j < GC_ITEMS; ++j) {
-        mypos[j] = 0xFFFFFFFFu;
-        if ((uint32_t)j < T) {
-            const uint32_t d = wd[j] >> GS_COUNT_BITS;
-            const uint32_t r = (j & 1) ? (rank2[j >> 1] >> 16) : (rank2[j >> 1] & 0xFFFFu);
-            mypos[j] = (uint32_t)S.binstart[d] + (uint32_t)S.u.whist[w][d] + r;
-        }
-    }
-    __syncthreads(); // every wave has read the ranking counters: the prefix below overwrites them
-#pragma unroll
-    for (int j = 0; j < GC_ITEMS; ++j) {
-        if ((uint32_t)j < T) {
-            S.id[mypos[j]] = (unsigned short)gid[j];
-            S.word[mypos[j]] = wd[j];
-            S.aux[mypos[j]] = ax[j];
-        }
-    }
-    __syncthreads();
-    // ---- exclusive scan of the quantities in sorted order (thread t: slots 8t .. 8t+7) ----
-    {
-        uint32_t c[GC_ITEMS];
-        unsigned long long acc = 0;
+        // (uniform) nothing visible: the bases do not move.  Every read of the ranking counters lies before block_excl_u32's
+        // barriers and nothing written since is read again, so the next trip may start at once.
+        if (nc == 0) continue;
+        __syncthreads();
+        // ---- reorder through LDS: the sorted arrays were last read before the barrier that ended the previous trip ----
 #pragma unroll
         for (int j = 0; j < GC_ITEMS; ++j) {
-            const uint32_t p = tid * GC_ITEMS + j;
-            const uint32_t x = (p < T * GC_THREADS) ? S.word[p] : 0xFFFFFFFFu;
-            c[j] = x == 0xFFFFFFFFu ? 0u : (x & GS_COUNT_MASK);
-            acc += c[j];
+            if (wv[j]) {
+                const uint32_t d = wv[j] >> GS_COUNT_BITS;
+                const uint32_t r = (j & 1) ? (rank2[j >> 1] >> 16) : (rank2[j >> 1] & 0xFFFFu);
+                const uint32_t pos = (uint32_t)S.binstart[d] + (uint32_t)S.u.whist[w][d] + r;
+                S.id[pos] = (unsigned short)(w * (64 * GC_ITEMS) + j * 64 + lane);
+                S.word[pos] = wv[j];
+                S.aux[pos] = av[j];
+            }
         }
-        GsPair total, in;
-        in.x = 0u; in.y = acc;
-        const GsPair ex = block_excl2(in, tid, S.w2, total);
-        unsigned long long run = ex.y;
+        __syncthreads(); // (every wave has read the ranking counters as well: the prefix below overwrites them)
+        // ---- exclusive scan of the quantities in sorted order (thread t: slots 8t .. 8t+7) ----
+        {
+            uint32_t c[GC_ITEMS], acc = 0; // (8 x 2^22 at most)
 #pragma unroll
-        for (int j = 0; j < GC_ITEMS; ++j) { S.u.P[tid * GC_ITEMS + j] = sat32(run); run += c[j]; }
-    }
-    __syncthreads();
-    // ---- store: coalesced over the sorted slots ----
+            for (int j = 0; j < GC_ITEMS; ++j) {
+                const uint32_t p = tid * GC_ITEMS + j;
+                c[j] = (p < nc) ? (S.word[p] & GS_COUNT_MASK) : 0u;
+                acc += c[j];
+            }
+            unsigned long long total;
+            unsigned long long run = block_excl_u32<unsigned long long>(acc, tid, S.w1, total);
 #pragma unroll
-    for (int j = 0; j < GC_ITEMS; ++j) {
-        const uint32_t pos = j * GC_THREADS + tid;
-        if (pos >= nc) continue;
-        const uint32_t x = S.word[pos];
-        const uint32_t b = x >> GS_COUNT_BITS, first = S.binstart[b];
-        const uint2 base = S.base[b];
-        const uint32_t g = base.x + (pos - first);
-        const unsigned long long off64 = (unsigned long long)base.y + (S.u.P[pos] - S.u.P[first]);
-        const uint32_t off = sat32(off64);
-        grec[g] = make_uint4(chunk * GC + (uint32_t)S.id[pos], x, off, S.aux[pos]);
-        const uint32_t cnt = x & GS_COUNT_MASK; // > 0: only visible gaussians are here
-        if (off != 0xFFFFFFFFu) {
-            const unsigned long long lastq = (off64 + cnt - 1ull) >> GS_EMIT_CHUNK_SHIFT;
-            const uint32_t last = lastq > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)lastq;
-            for (uint32_t c = (uint32_t)((off64 + (1u << GS_EMIT_CHUNK_SHIFT) - 1ull) >> GS_EMIT_CHUNK_SHIFT); c <= last && c < chunk_cap; ++c) chunk_table[c] = g;
+            for (int j = 0; j < GC_ITEMS; ++j) { S.u.P[tid * GC_ITEMS + j] = sat32(run); run += c[j]; }
+            if (tid == 0) S.ptot = sat32(total);
+        }
+        __syncthreads();
+        // ---- store: coalesced over the sorted slots ----
+#pragma unroll
+        for (int j = 0; j < GC_ITEMS; ++j) {
+            const uint32_t pos = j * GC_THREADS + tid;
+            if (pos >= nc) continue;
+            const uint32_t x = S.word[pos];
+            const uint32_t b = x >> GS_COUNT_BITS, first = S.binstart[b];
+            const uint2 base = S.base[b];
+            const uint32_t g = base.x + (pos - first);
+            const unsigned long long off64 = (unsigned long long)base.y + (S.u.P[pos] - S.u.P[first]);
+            const uint32_t off = sat32(off64);
+            grec[g] = make_uint4(chunk * GC + (uint32_t)S.id[pos], x, off, S.aux[pos]);
+            const uint32_t cnt = x & GS_COUNT_MASK; // > 0: only visible gaussians are here
+            if (off != 0xFFFFFFFFu) {
+                const unsigned long long lastq = (off64 + cnt - 1ull) >> GS_EMIT_CHUNK_SHIFT;
+                const uint32_t last = lastq > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)lastq;
+                for (uint32_t c = (uint32_t)((off64 + (1u << GS_EMIT_CHUNK_SHIFT) - 1ull) >> GS_EMIT_CHUNK_SHIFT); c <= last && c < chunk_cap; ++c) chunk_table[c] = g;
+            }
+        }
+        // ---- the bases advance by the chunk's own (count, quantity) of every bucket (see "Saturation" in the header) ----
+        if (chunk + 1u < chunk1) { // (uniform)
+            uint32_t dx[BPT], py[BPT + 1];
+            uint32_t s = S.binstart[tid * BPT];
+            py[0] = s < GC ? S.u.P[s] : S.ptot;
+#pragma unroll
+            for (uint32_t i = 0; i < BPT; ++i) {
+                const uint32_t b = tid * BPT + i;
+                const uint32_t e = (b + 1u < GBINS) ? (uint32_t)S.binstart[b + 1u] : nc;
+                dx[i] = e - s;
+                py[i + 1] = e < GC ? S.u.P[e] : S.ptot;
+                s = e;
+            }
+            __syncthreads(); // every thread has read the bases, P and the bucket starts of this trip
+#pragma unroll
+            for (uint32_t i = 0; i < BPT; ++i) {
+                uint2 v = S.base[tid * BPT + i];
+                v.x += dx[i];
+                v.y = py[i + 1] == 0xFFFFFFFFu ? 0xFFFFFFFFu : sat32((unsigned long long)v.y + (py[i + 1] - py[i]));
+                S.base[tid * BPT + i] = v;
+            }
         }
     }
 }
 
 // ---- host launchers --------------------------------------------------------------------------------
 uint32_t gs_gsort_tiles(uint32_t n) { return (n + GC - 1) / GC; }
+// An upper bound for every n and every number of runs: the table has min(NT, runs) <= NT columns.
 uint64_t gs_gsort_scratch_bytes(uint32_t n) { return ((uint64_t)GBINS * gs_gsort_tiles(n ? n : 1) + GBINS) * sizeof(uint2); }
 // words: one word per gaussian INDEX (quantity in the low 22 bits, depth bucket in the high 10; 0 = not visible); scratch:
-// gs_gsort_scratch_bytes(n) bytes.  Output records in (bucket, index) order; tot_visible / tot_quantity: device words.
+// gs_gsort_scratch_bytes(n) bytes; grid: the context's persistent grid, from which the number of runs follows.  Output
+// records in (bucket, index) order; tot_visible / tot_quantity: device words.
 void gs_launch_gsort(const uint32_t* words, const uint32_t* aux_in, uint32_t n, void* scratch, void* grec, uint32_t* chunk_table, uint32_t chunk_cap,
-                     uint32_t* tot_visible, uint32_t* tot_quantity, hipStream_t st) {
+                     uint32_t* tot_visible, uint32_t* tot_quantity, uint32_t grid, hipStream_t st) {
     if (!n) return;
     const uint32_t NT = gs_gsort_tiles(n);
+    uint64_t want = (uint64_t)grid * GS_GSORT_RUNS_Q / 4u;
+    if (!want) want = 1;
+    const uint32_t cpr = (uint32_t)((NT + want - 1) / want); // chunks per run
+    const uint32_t G = (NT + cpr - 1) / cpr;                 // runs that hold a chunk: min(NT, want) at most
     uint2* M = (uint2*)scratch;
-    uint2* rowtot = M + (uint64_t)GBINS * NT;
-    hipLaunchKernelGGL(gs_gsort_hist_kernel, dim3(NT), dim3(GC_THREADS), 0, st, words, n, M, NT);
-    hipLaunchKernelGGL(gs_gsort_rowscan_kernel, dim3(GBINS / 8), dim3(GR_THREADS), 0, st, M, NT, n, rowtot);
-    hipLaunchKernelGGL(gs_gsort_scatter_kernel, dim3(NT), dim3(GC_THREADS), 0, st, words, aux_in, n, (const uint2*)M, NT, (const uint2*)rowtot,
+    uint2* rowtot = M + (uint64_t)GBINS * G;
+    hipLaunchKernelGGL(gs_gsort_hist_kernel, dim3(G), dim3(GC_THREADS), 0, st, words, n, M, G, cpr, NT);
+    hipLaunchKernelGGL(gs_gsort_rowscan_kernel, dim3(GBINS / 8), dim3(GR_THREADS), 0, st, M, G, rowtot);
+    hipLaunchKernelGGL(gs_gsort_scatter_kernel, dim3(G), dim3(GC_THREADS), 0, st, words, aux_in, n, (const uint2*)M, G, cpr, NT, (const uint2*)rowtot,
                        (uint4*)grec, chunk_table, chunk_cap, tot_visible, tot_quantity);
 }
