@@ -18,7 +18,8 @@ ARCH = "gfx950"
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC", "-fvisibility=hidden",
          "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result"]
 FILE_FLAGS = {}  # per-file flags (none at present)
-SOURCES = ["k_preprocess.hip", "k_binning.hip", "k_gsort.hip", "k_rows.hip", "k_sort.hip", "k_blend.hip", "k_pick.hip", "gs_runtime.hip"]
+SOURCES = ["k_preprocess.hip", "k_binning.hip", "k_gsort.hip", "k_rows.hip", "k_sort.hip", "k_blend.hip", "k_pick.hip",
+           "gs_context.hip", "gs_frame.hip", "gs_readback.hip", "gs_ply.hip", "gs_stages.hip"]
 
 
 def _stale(target, deps):
@@ -34,7 +35,7 @@ def build(force=False, verbose=False, profiling=False):
     os.makedirs(OUT, exist_ok=True)
     objdir = os.path.join(OUT, "obj_prof" if profiling else "obj")
     os.makedirs(objdir, exist_ok=True)
-    headers = [os.path.join(HERE, h) for h in ("gs_device.h", "gs_kernels.h", "gs_tight.h")] + [
+    headers = [os.path.join(HERE, h) for h in ("gs_device.h", "gs_kernels.h", "gs_tight.h", "gs_runtime.h")] + [
         os.path.join(HERE, "..", "..", "include", "gsplat", "gs_abi.h")]
 
     def compile_one(src):
@@ -47,7 +48,7 @@ def build(force=False, verbose=False, profiling=False):
             subprocess.check_call(cmd)
         return obj
 
-    with ThreadPoolExecutor(max_workers=6) as ex:
+    with ThreadPoolExecutor(max_workers=12) as ex:
         objs = list(ex.map(compile_one, SOURCES))
     so = os.path.join(OUT, "libgsplat_hip_prof.so" if profiling else "libgsplat_hip.so")
     if force or _stale(so, objs):

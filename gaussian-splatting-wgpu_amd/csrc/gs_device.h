@@ -157,6 +157,18 @@ __device__ __forceinline__ float gs_exp(float x) {
     return (y * sa) * sb;
 }
 
+// Columns of a rect that fall in the slab; column ntx aliases to column 0 of the next tile row
+// (write_tile_ids.wgsl:26-31).  Returns main-run [xa,xb) and whether the alias column is owned.
+// Used by the projection's tile count (k_preprocess.hip) and by the emission (k_binning.hip).
+__device__ __forceinline__ void slab_cols(uint32_t rx0, uint32_t rx1, const GsFrame& f, uint32_t& xa, uint32_t& wmain,
+                                          uint32_t& alias) {
+    const uint32_t hi = rx1 < f.ntx ? rx1 : f.ntx; // real columns end at ntx
+    xa = rx0 > f.col0 ? rx0 : f.col0;
+    const uint32_t xb = hi < f.col1 ? hi : f.col1;
+    wmain = xb > xa ? xb - xa : 0u;
+    alias = (rx1 == f.ntx + 1u && f.col0 == 0u) ? 1u : 0u;
+}
+
 // ---- wave64 helpers -------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 
@@ -171,6 +183,14 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, uint32_t) {
     v += GS_DPP(v, 0x118, 0xf);
     v += GS_DPP(v, 0x142, 0xa);
     v += GS_DPP(v, 0x143, 0xc);
+    return v;
+}
+__device__ __forceinline__ unsigned long long wave_incl_scan64(unsigned long long v, uint32_t lane) { // k_gsort.hip, k_rows.hip
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t lo = __shfl_up((uint32_t)v, d, 64), hi = __shfl_up((uint32_t)(v >> 32), d, 64);
+        if ((int)lane >= d) v += ((unsigned long long)hi << 32) | lo;
+    }
     return v;
 }
 __device__ __forceinline__ uint32_t wave_incl_max(uint32_t v) { // unsigned: the identity is 0

@@ -1,0 +1,187 @@
+// gs_runtime.h -- private to the runtime sources (gs_context / gs_frame / gs_readback / gs_ply / gs_stages .hip): the error
+// channel, the owners of HIP resources, and the context.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <mutex>
+#include <vector>
+
+#include "../../include/gsplat/gs_abi.h"
+#include "gs_kernels.h"
+
+#define GS_EXPORT extern "C" __attribute__((visibility("default")))
+
+// ---- errors: one message per thread (gs_last_error), one macro ---------------------------------------------
+extern thread_local char g_err[512];
+int32_t fail(int32_t code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+#define HIP_TRY(expr)                                                                                       \
+    do {                                                                                                    \
+        hipError_t e_ = (expr);                                                                             \
+        if (e_ != hipSuccess)                                                                               \
+            return fail(e_ == hipErrorOutOfMemory ? GS_ERR_OUT_OF_MEMORY : GS_ERR_HIP, "%s: %s", #expr,      \
+                        hipGetErrorString(e_));                                                             \
+    } while (0)
+
+// ---- owners: move-only, released by the destructor and by reset(), read like the raw pointer they hold -------
+template <class P, auto Destroy>
+struct Owned {
+    P p = nullptr;
+    Owned() = default;
+    explicit Owned(P q) : p(q) {}
+    Owned(const Owned&) = delete;
+    Owned& operator=(const Owned&) = delete;
+    Owned(Owned&& o) noexcept : p(o.p) { o.p = nullptr; }
+    Owned& operator=(Owned&& o) noexcept { if (this != &o) { reset(); p = o.p; o.p = nullptr; } return *this; }
+    ~Owned() { reset(); }
+    void reset() { if (p) { (void)Destroy(p); p = nullptr; } }
+    P* out() { reset(); return &p; } // for the creating call's out-parameter: whatever was held goes first
+    P get() const { return p; }
+    operator P() const { return p; }
+    P operator->() const { return p; }
+};
+template <class T = void> using DevBuf = Owned<T*, hipFree>;        // hipMalloc
+template <class T = void> using PinnedBuf = Owned<T*, hipHostFree>; // hipHostMalloc
+using Event = Owned<hipEvent_t, hipEventDestroy>;
+using Stream = Owned<hipStream_t, hipStreamDestroy>;
+using File = Owned<FILE*, fclose>;
+
+// What record_frame notes about the frame it records (where the sorted result lives, which pipeline ran).  A REPLAY of the
+// captured frame restores the capture's notes -- a frame recorded in between (gs_render_debug) would otherwise leave its own.
+struct FrameNotes {
+    uint32_t *keysS = nullptr, *valsS = nullptr; // views: the sorted result is in keysA/valsA or keysB/valsB (tight frames: no keys)
+    uint32_t last_passes = 0;
+    uint32_t blend_walkers = 1; // workgroups that walk each tile's list independently in the blend
+    bool last_by_index = true;
+    bool last_keys16 = false;   // the sorted keys are u16 tile ids (GS_BUF_KEYS is rebuilt on demand into keysG)
+    bool last_tight = false;    // the frame used the tight (opacity-aware) binning
+};
+
+// What a captured frame depends on beside the buffers: the emission order, the binning, and the addresses it writes.
+struct GraphKey {
+    bool index = false, tight = false;
+    void* ext = nullptr;
+    float *alpha = nullptr, *depth = nullptr; // the aux planes (they never move: recorded so that a change cannot go unnoticed)
+    bool operator==(const GraphKey& o) const { return index == o.index && tight == o.tight && ext == o.ext && alpha == o.alpha && depth == o.depth; }
+};
+
+#define GS_EV_RING 256
+struct gs_ctx {
+    ~gs_ctx();
+    gs_config cfg{};
+    Stream own_stream;            // declared before every buffer: destroyed after them
+    hipStream_t stream = nullptr; // view: own_stream, or the caller's cfg.stream
+    GsFrame frame{};
+    uint32_t T = 0, passes = 0, key_bits = 0; // passes: 8-bit digits of the full key (reference-order pipeline)
+    uint32_t tile_passes = 0, tile_bits = 0;  // digits of key/1000 (depth-ordered pipeline)
+    bool tile16 = false;                      // every tile id fits 16 bits: the depth-ordered instance sort moves u16 sort words
+    bool tight_ok = false;                    // the canvas has at most 255 tile rows and columns (8-bit digits of the row pipeline)
+    uint32_t grid_persist = 0;                // workgroups of the persistent (ticket-loop) kernels
+    // options
+    int emit_order = 2;                       // GS_OPT_EMIT_ORDER: 0 depth-bucket order, 1 gaussian-index order (reference), 2 auto
+    bool index_order = true;                  // what the frame being enqueued uses
+    uint32_t debug_view = 0;                  // GS_OPT_DEBUG_VIEW
+    bool tile_cull = true;                    // GS_OPT_TILE_CULL: tight (opacity-aware) binning in gs_render / gs_render_to
+    uint32_t tight_nb = 0;                    // GS_OPT_PROJ_CHUNKS: cull chunks per workgroup of the tight projection (0 = automatic)
+    uint32_t blend_ablation = 0;              // profiling only (GS_OPT_BLEND_ABLATION)
+    DevBuf<uint32_t> blend_prof;              // profiling only (ablation bit 16): 4 words per blend walker
+    uint32_t blend_prof_blocks = 0;
+    // Frames in flight (GS_OPT_FRAMES_IN_FLIGHT): when gs_render is called while this context's previous frame is still on the
+    // device, the frame goes to a SHADOW context (own stream and per-frame arrays, this context's resident splats), created on
+    // first need; gs_render then alternates between them, so one frame's blend (instruction-issue bound) overlaps the next
+    // frame's projection / binning / sort (memory and latency bound).  gs_wait waits for all of them; read-backs, taps and
+    // statistics refer to the context that rendered the LAST frame.
+    uint32_t fif = 1;                         // allowed frames in flight (1 = none of the above)
+    std::vector<gs_ctx*> shadows;             // owned: gs_destroy'ed before this context's scene goes
+    bool is_shadow = false;
+    gs_ctx* last = nullptr;                   // who rendered the last frame (this or a shadow); nullptr = this
+    uint32_t rr = 0;                          // next slot of the ring {this, shadows...}
+    uint64_t cap_hint = 0, row_hint = 0;      // largest capacities any member of the ring has grown to
+    // gs_render_host / gs_wait_ticket (root ctx): the event of the last frame + copy of every ring member, who rendered which ticket
+    Event ev_done;
+    uint64_t next_ticket = 1;
+    struct { uint64_t ticket; gs_ctx* member; } tickets[64] = {};
+    std::mutex ticket_mu;
+    // scene planes
+    DevBuf<> scene_own;         // the resident scene, when this context uploaded it
+    void* scene_mem = nullptr;  // view: scene_own, or after gs_share_splats the owner's scene_own (the owner must outlive this context)
+    size_t scene_bytes = 0;
+    GsScene scene{};            // views into scene_mem
+    uint32_t n = 0;
+    // per-gaussian frame buffers (alloc_per_gaussian)
+    DevBuf<uint32_t> counts, offsets, rowptr;
+    DevBuf<> gdata;
+    DevBuf<> grec;              // visible gaussians in (depth bucket, index) order: {id, count word, prefix, arena address} (k_gsort.hip)
+    DevBuf<> gsort_scratch;     // (bucket, run) table of the gaussian-level counting sort
+    // (key,value) arrays and what grows with them (alloc_kv)
+    uint64_t capacity = 0;
+    DevBuf<uint32_t> keysA, valsA, keysB, valsB;
+    DevBuf<uint32_t> keysU, valsU;  // debug copies of the unsorted arrays, allocated by the first gs_render_debug
+    DevBuf<uint32_t> keysG;         // full keys rebuilt on demand from a frame that holds u16 tile ids or none (GS_BUF_KEYS)
+    bool keysG_valid = false;
+    DevBuf<uint32_t> chunk_table;   // balanced emission: first gaussian of every EMIT_CHUNK output slots
+    // tight row pipeline (k_rows.hip): row items in projection order / sorted by tile row, slot addresses in depth order
+    uint64_t row_cap = 0;
+    DevBuf<uint32_t> arena, rows_sorted, M3;
+    DevBuf<uint32_t> tileoff, rowtot; // (fixed size: gs_create)
+    // control block + look-back status words (one allocation, one memset per frame)
+    DevBuf<> ctl_mem;
+    size_t ctl_bytes = 0;
+    size_t ctl_bytes_tight = 0;               // the part of the control block a tight frame polls: what its memset has to zero
+    GsControl* ctl = nullptr;                 // views into ctl_mem, in its order:
+    uint32_t* tile_depth = nullptr;           //   blend statistic: deepest staged entry per tile (quadrant kernel)
+    uint32_t* rows_status = nullptr;          //   row sort (tight row pipeline)
+    unsigned long long* scan_status = nullptr; //  [2][scan blocks]
+    uint32_t* sort_status = nullptr;          //   instance sort (reference binning)
+    // reports
+    PinnedBuf<GsControl> h_ctl; // pinned copy of the control block's counters, fetched on demand (gs_get_stats)
+    bool h_ctl_valid = false;
+    PinnedBuf<GsReport> h_rep;  // host-mapped: the frame's last binning kernel writes its report here (gs_device.h); no per-frame copy
+    DevBuf<uint32_t> sticky;    // device: [0] frames that overflowed, [1] fault, [2] largest I, [3] largest arena demand -- NOT in the
+                                // per-frame memset (gs_frame_report)
+    uint64_t max_I_seen = 0;       // largest instance count since GS_OPT_RESET_TIMING
+    uint64_t truncated_frames = 0; // frames that overflowed the capacity and were NOT the frame gs_wait could re-render
+    // outputs
+    DevBuf<uint32_t> ranges, rgba8;
+    DevBuf<float> rgbf;
+    DevBuf<float> alpha, depth; // GS_FLAG_AUX_OUTPUTS: f32[H][slab_w] alpha and accumulated-depth planes, allocated in gs_create (a shadow
+                                // inherits the flag and owns its own), never moved afterwards
+    DevBuf<uint32_t> d_pxb;     // assemble: pixel boundaries (device copy of pxb_host)
+    uint32_t pxb_host[65] = {};
+    uint32_t pxb_n = 0;
+    // gs_pick (root ctx): device copies of the queries, the results and the contributor records; allocated on first use
+    struct { DevBuf<> q, r, c; uint64_t c_bytes = 0; } pick;
+    Event ev[GS_EV_RING][GS_STAGE_COUNT + 1]; // ring of per-frame stage brackets (GS_FLAG_TIMING)
+    bool have_events = false;
+    uint64_t timed_from = 0; // first frame index included in the stage means
+    // frame graph (GS_OPT_FRAME_GRAPH): the frame's launches captured once, replayed with hipGraphLaunch; only the projection's
+    // uniforms change from frame to frame (kernel-node parameter update)
+    struct {
+        bool use = false, valid = false;
+        hipGraph_t graph = nullptr; // destroyed by drop_graph, before the buffers the capture points into
+        hipGraphExec_t exec = nullptr;
+        hipGraphNode_t pre_node = nullptr;
+        GraphKey key;
+        FrameNotes notes; // of the captured frame
+        uint64_t frames = 0;
+    } gr;
+    GsPreprocessLaunch pre{};
+    // frame state
+    FrameNotes notes; // of the last frame enqueued
+    bool have_frame = false, pending = false, last_debug = false;
+    void* last_ext = nullptr;
+    GsUniforms last_u{};
+    uint64_t frames = 0;
+};
+
+// gs_context.hip
+int32_t alloc_kv(gs_ctx* c, uint64_t capacity, uint64_t row_cap); // the caller has drained the stream
+int32_t scene_alloc(gs_ctx* c, uint64_t n);
+void drop_shadows(gs_ctx* c);
+// gs_frame.hip
+void drop_graph(gs_ctx* c);
+int32_t wait_one(gs_ctx* c);
+inline gs_ctx* last_of(gs_ctx* c) { return (c && c->last) ? c->last : c; }

@@ -167,15 +167,6 @@ __global__ __launch_bounds__(SCAN_THREADS) void gs_scan_kernel(const uint32_t* _
 // instance order y outer / x inner, gaussians in index order -- so a stable sort reproduces the
 // reference's tie order bit for bit.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void slab_cols_emit(uint32_t rx0, uint32_t rx1, const GsFrame& f, uint32_t& xa, uint32_t& wmain,
-                                               uint32_t& alias) {
-    const uint32_t hi = rx1 < f.ntx ? rx1 : f.ntx;
-    xa = rx0 > f.col0 ? rx0 : f.col0;
-    const uint32_t xb = hi < f.col1 ? hi : f.col1;
-    wmain = xb > xa ? xb - xa : 0u;
-    alias = (rx1 == f.ntx + 1u && f.col0 == 0u) ? 1u : 0u;
-}
-
 // perm/n_dev: optional order of emission (element k of the launch is gaussian perm[k], k < *n_dev): the
 // depth-ordered pipeline emits gaussians sorted by depth bucket so that the instance sort only has to order by tile.
 __global__ __launch_bounds__(256) void gs_emit_kernel(const uint4* __restrict__ gdata, const uint32_t* __restrict__ counts,
@@ -207,7 +198,7 @@ __global__ __launch_bounds__(256) void gs_emit_kernel(const uint4* __restrict__ 
         const uint4 rect = gdata[(uint64_t)i * 4 + 3];
         const uint32_t bucket = packed >> GS_COUNT_BITS; // u32(min(50*depth, 999)), computed by the preprocess
         uint32_t xa, wmain, alias;
-        slab_cols_emit(rect.x, rect.z, f, xa, wmain, alias);
+        slab_cols(rect.x, rect.z, f, xa, wmain, alias);
         row = xa | (wmain << 16) | (alias << 31);
         yb = rect.y | (bucket << 16);
     }
@@ -287,7 +278,7 @@ __global__ __launch_bounds__(256) void gs_emit_balanced_kernel(const uint4* __re
                 off = gr.z;
                 const uint4 rect = gdata[(uint64_t)gid * 4 + 3];
                 uint32_t xa, wmain, alias;
-                slab_cols_emit(rect.x, rect.z, f, xa, wmain, alias);
+                slab_cols(rect.x, rect.z, f, xa, wmain, alias);
                 row = xa | (wmain << 16) | (alias << 31);
                 yb = rect.y | ((packed >> GS_COUNT_BITS) << 16);
             }

@@ -96,14 +96,6 @@ __global__ __launch_bounds__(GC_THREADS) void gs_gsort_hist_kernel(const uint32_
 // exclusive scan of (count, quantity) over a workgroup: each thread holds the sum of its consecutive elements in v; the
 // quantity channel is 64 bits wide inside the scan and saturates where it is stored
 struct GsPair { uint32_t x; unsigned long long y; };
-__device__ __forceinline__ unsigned long long wave_incl_scan64(unsigned long long v, uint32_t lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t lo = __shfl_up((uint32_t)v, d, 64), hi = __shfl_up((uint32_t)(v >> 32), d, 64);
-        if ((int)lane >= d) v += ((unsigned long long)hi << 32) | lo;
-    }
-    return v;
-}
 __device__ __forceinline__ GsPair block_excl2(GsPair v, uint32_t tid, GsPair* s_w /*[GC_THREADS / 64]*/, GsPair& total) {
     const uint32_t lane = tid & 63, w = tid >> 6;
     const uint32_t ix = wave_incl_scan(v.x, lane);

@@ -113,17 +113,6 @@ __device__ __forceinline__ void m4_mulv(const float* m, float x, float y, float 
     for (int r = 0; r < 4; ++r) o[r] = ((m[0 + r] * x + m[4 + r] * y) + m[8 + r] * z) + m[12 + r] * 1.0f;
 }
 
-// Columns of a rect that fall in the slab; column ntx aliases to column 0 of the next tile row
-// (write_tile_ids.wgsl:26-31).  Returns main-run [xa,xb) and whether the alias column is owned.
-__device__ __forceinline__ void slab_cols(uint32_t rx0, uint32_t rx1, const GsFrame& f, uint32_t& xa, uint32_t& wmain,
-                                          uint32_t& alias) {
-    const uint32_t hi = rx1 < f.ntx ? rx1 : f.ntx; // real columns end at ntx
-    xa = rx0 > f.col0 ? rx0 : f.col0;
-    const uint32_t xb = hi < f.col1 ? hi : f.col1;
-    wmain = xb > xa ? xb - xa : 0u;
-    alias = (rx1 == f.ntx + 1u && f.col0 == 0u) ? 1u : 0u;
-}
-
 // sigmoid (:282-294): both branches evaluated, blended by a 0/1 float
 __device__ __forceinline__ float sigmoid_ref(float o) {
     const float ez = gs_exp(o);
@@ -562,7 +551,7 @@ void gs_launch_repack(const void* d_aos, uint32_t n, const GsScene& s, hipStream
                        (float*)s.pz, (float*)s.smax, (float*)s.geo, (float*)s.sh);
 }
 // The projection's launch as data: the one kernel of a frame whose arguments change from frame to frame (the uniforms, by
-// value), so a captured frame graph (gs_runtime.hip) re-launches it with updated parameters.
+// value), so a captured frame graph (gs_frame.hip) re-launches it with updated parameters.
 void gs_preprocess_prepare(GsPreprocessLaunch& L, const GsScene& s, const GsUniforms& u, const GsFrame& f, void* gdata, uint32_t* counts,
                            bool tight, uint32_t* arena, uint32_t* rowptr, GsControl* ctl, uint32_t tight_nb) {
     // cull chunks per workgroup (see NB).  Reference binning: 8 for a slab narrower than 30 % of the canvas, 4 up to 75 %, else 1.

@@ -261,14 +261,6 @@ __global__ __launch_bounds__(RA_THREADS) void gs_rows_sort_kernel(const uint32_t
 // Chunk geometry shared by the count / scan / expand kernels: tile row r holds items [ibase[r], ibase[r] + cnt[r]) of the
 // row-sorted array and chunks [cbase[r], cbase[r + 1]) of RB_CH items each (the last one shorter).
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned long long wave_incl_scan64(unsigned long long v, uint32_t lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t lo = __shfl_up((uint32_t)v, d, 64), hi = __shfl_up((uint32_t)(v >> 32), d, 64);
-        if ((int)lane >= d) v += ((unsigned long long)hi << 32) | lo;
-    }
-    return v;
-}
 struct RowTables {
     uint32_t ibase[257]; // exclusive scan of GsControl::rowhist, clamped to the arrays' capacity
     uint32_t cbase[257]; // exclusive scan of ceil(items / RB_CH)

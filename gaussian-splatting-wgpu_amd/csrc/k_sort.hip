@@ -27,7 +27,7 @@
 #define RS_VALUE (~RS_FLAGS)
 
 // Digit of pass `pass`: `bits` bits of the sort word, which is the key itself (mode 0) or the key's tile id
-// key/1000 (mode 1: the depth-ordered pipeline sorts instances by tile only, see gs_runtime.hip).
+// key/1000 (mode 1: the depth-ordered pipeline sorts instances by tile only, see gs_frame.hip).
 struct SortDigits {
     uint32_t bits;    // bits per pass (<= 8)
     uint32_t by_tile; // 0: word = key, 1: word = key / 1000 (u16 tile-id keys are their own word: mode 0)

@@ -3,7 +3,7 @@
 flight, frame graph, projection chunks, workgroup-per-tile blend), bursts of frames without a wait (a debug frame among them), frames presented through
 gs_render_host with tickets waited for in any order (every sink checked), reads in between -- the last frame
 of every burst against the oracle (EXACT, bit for bit).  Hunts life-cycle bugs (stale captures, ring members with old arrays,
-capacities).  Usage: tools/fuzz_sequence.py [sequences=30] [seed0=0]"""
+capacities).  Stops at the first failing sequence (exit status 1).  Usage: tools/fuzz_sequence.py [sequences=30] [seed0=0]"""
 import ctypes, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "gaussian-splatting-wgpu_amd")); sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -18,7 +18,6 @@ import gpu_checks as gc
 o.build()
 seqs = int(sys.argv[1]) if len(sys.argv) > 1 else 30
 seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 0
-bad = 0
 L = _abi.load()
 for q in range(seed0, seed0 + seqs):
     rng = np.random.default_rng(31337 + q)
@@ -97,9 +96,8 @@ for q in range(seed0, seed0 + seqs):
         r.destroy()
         print("sequence %d (%dx%d ts %d): ok  %s" % (q, W, H, ts, " | ".join(log)), flush=True)
     except Exception as e:
-        bad += 1
+        # the first failure ends the run: nothing more is started on a GPU that has just shown trouble, the context included
         print("sequence %d (%dx%d ts %d): FAILED %s  after: %s" % (q, W, H, ts, repr(e)[:300], " | ".join(log)), flush=True)
-        try: r.destroy()
-        except Exception: pass
-print("%d sequences, %d failed" % (seqs, bad))
-sys.exit(1 if bad else 0)
+        print("stopped at the first failing sequence (%d of %d run)" % (q - seed0 + 1, seqs))
+        sys.exit(1)
+print("%d sequences, 0 failed" % seqs)
