@@ -197,7 +197,10 @@ int32_t scene_alloc(gs_ctx* c, uint64_t n) {
     int32_t rc = alloc_per_gaussian(c, n);
     if (rc != GS_OK) return rc;
     const size_t np = ((size_t)n + 63) & ~(size_t)63; // plane stride keeps every plane and both record arrays 256-byte aligned
-    const size_t bytes = np * 4 * 4 + np * 32 + (size_t)n * 192;
+    // (GS_FLAG_SPLAT_STATE: the state plane follows the SH records, on the next 256-byte boundary; np bytes, so that whole words
+    // and 16-byte groups of it are the context's own)
+    const size_t sh_end = np * 4 * 4 + np * 32 + (size_t)n * 192, state_at = (sh_end + 255) & ~(size_t)255;
+    const size_t bytes = has_state(c) ? state_at + np : sh_end;
     HIP_TRY(hipMalloc(c->scene_own.out(), std::max<size_t>(bytes, 256)));
     c->scene_mem = c->scene_own;
     c->scene_bytes = bytes;
@@ -207,6 +210,11 @@ int32_t scene_alloc(gs_ctx* c, uint64_t n) {
     s.smax = (float*)p; p += np * 4;
     s.geo = (float4*)p; p += np * 32;
     s.sh = (float4*)p;
+    s.state = nullptr;
+    if (has_state(c)) { // zeroed by every upload
+        s.state = (const uint8_t*)c->scene_mem + state_at;
+        HIP_TRY(hipMemsetAsync((char*)c->scene_mem + state_at, 0, std::max<size_t>(np, 4), c->stream));
+    }
     return GS_OK;
 }
 
@@ -234,6 +242,8 @@ GS_EXPORT int32_t gs_share_splats(gs_ctx* c, gs_ctx* owner) {
     if (c->cfg.device != owner->cfg.device) return fail(GS_ERR_INVALID_ARGUMENT, "gs_share_splats: contexts are on different devices");
     if (!c->is_shadow) drop_shadows(c);
     if (!owner->scene_mem) return fail(GS_ERR_NO_SCENE, "gs_share_splats: the owner holds no splats");
+    if (has_state(c) && !has_state(owner))
+        return fail(GS_ERR_INVALID_ARGUMENT, "gs_share_splats: this context has GS_FLAG_SPLAT_STATE, the owner keeps no state plane");
     HIP_TRY(hipSetDevice(c->cfg.device));
     if (c->pending) { int32_t rc = wait_one(c); if (rc != GS_OK) return rc; }
     // start from the capacity the owner has already grown to: a borrower exists to keep several frames in flight, and a
@@ -297,6 +307,11 @@ static int32_t set_option_one(gs_ctx* c, int32_t key, int64_t value) {
     case GS_OPT_DEBUG_VIEW: if (value < 0 || value > 4) break; c->debug_view = (uint32_t)value; return GS_OK;
     case GS_OPT_TILE_CULL: c->tile_cull = (value != 0); return GS_OK;
     case GS_OPT_PROJ_CHUNKS: if (value != 0 && value != 2 && value != 4 && value != 8) break; c->tight_nb = (uint32_t)value; return GS_OK;
+    case GS_OPT_SELECT_TINT: // (the captured frame is dropped above: its projection node holds the tint by value)
+        if (!has_state(c)) return fail(GS_ERR_INVALID_ARGUMENT, "gs_set_option: GS_OPT_SELECT_TINT needs GS_FLAG_SPLAT_STATE");
+        if (value < 0 || value > 0xFFFFFFFFll) break;
+        c->select_tint = (uint32_t)value;
+        return GS_OK;
     default: break;
     }
     return fail(GS_ERR_INVALID_ARGUMENT, "gs_set_option: bad key/value %d/%lld", key, (long long)value);

@@ -96,7 +96,13 @@ struct GsScene {
                        // Two arrays, not one 256-byte record: the covariance phase reads 32 bytes, the colour phase -- long
                        // after it, behind the tight row counting -- 192; in one record the first 128-byte line was fetched by
                        // both (round 2: 1.19 GB of traffic for 0.78 GB of algorithmic bytes, profiles/README.md)
+    const uint8_t* state; // u8[N] state plane (GS_FLAG_SPLAT_STATE; null otherwise): read by the STATE projection with the positions
 };
+
+// state byte (gs_abi.h GS_SPLAT_*) and the selection tint as the projection applies it: col + k (t - col), k = a / 255, t = channel / 255
+#define GS_ST_HIDDEN 1u
+#define GS_ST_SELECTED 2u
+struct GsTint { float t[3]; float k; };
 
 struct GsPlyTable { // where the 11 + 48 values of a packed record live in a raw .ply vertex (gs_upload_ply)
     uint32_t stride, nsrc, all_float;

@@ -53,7 +53,8 @@ static int32_t record_frame(gs_ctx* c, const GsUniforms& u, bool debug, void* ex
     c->h_ctl_valid = false;
     if (debug) HIP_TRY(hipMemsetAsync(c->gdata, 0, std::max<size_t>((size_t)c->n * 64, 256), st));
     mark(c, 0);
-    gs_preprocess_prepare(c->pre, c->scene, u, f, c->gdata, c->counts, tight, c->arena, c->rowptr, c->ctl, c->tight_nb);
+    gs_preprocess_prepare(c->pre, c->scene, u, f, c->gdata, c->counts, tight, c->arena, c->rowptr, c->ctl, c->tight_nb, has_state(c),
+                          tint_of(c->select_tint));
     gs_launch_preprocess(c->pre, st);
     mark(c, 1);
     const bool by_index = !tight && (debug || c->index_order);
@@ -186,7 +187,8 @@ static int32_t enqueue_frame(gs_ctx* c, const GsUniforms& u, bool debug, void* e
         } else {
             c->notes = c->gr.notes;
             // (the launch descriptor too: the frame in between prepared it for ITS projection -- other kernel, grid and outputs)
-            gs_preprocess_prepare(c->pre, c->scene, u, c->frame, c->gdata, c->counts, tight, c->arena, c->rowptr, c->ctl, c->tight_nb);
+            gs_preprocess_prepare(c->pre, c->scene, u, c->frame, c->gdata, c->counts, tight, c->arena, c->rowptr, c->ctl, c->tight_nb, has_state(c),
+                                  tint_of(c->select_tint));
             hipKernelNodeParams kp{};
             kp.func = const_cast<void*>(c->pre.func);
             kp.gridDim = dim3(c->pre.blocks); kp.blockDim = dim3(256); kp.sharedMemBytes = 0;
@@ -301,6 +303,7 @@ static int32_t add_shadow(gs_ctx* c) {
     if (rc != GS_OK) { gs_destroy(s); return rc; }
     s->emit_order = c->emit_order; s->tile_cull = c->tile_cull; s->debug_view = c->debug_view;
     s->blend_ablation = c->blend_ablation; s->grid_persist = c->grid_persist; s->timed_from = 0; s->tight_nb = c->tight_nb;
+    s->select_tint = c->select_tint;
     s->gr.use = c->gr.use;
     c->shadows.push_back(s);
     return GS_OK;

@@ -8,11 +8,13 @@ struct GsPreprocessLaunch { // the projection's launch as data (its uniforms are
     const void* func;
     uint32_t blocks;
     GsScene s; GsUniforms u; GsFrame f;
-    void* gdata; uint32_t* counts; GsTightOut to;
-    void* args[6];
+    void* gdata; uint32_t* counts; GsTightOut to; GsTint tint;
+    void* args[7];
 };
+// state: the STATE instantiation (honours s.state and the tint); false launches exactly the kernels a context without the plane has
 void gs_preprocess_prepare(GsPreprocessLaunch& L, const GsScene& s, const GsUniforms& u, const GsFrame& f, void* gdata, uint32_t* counts,
-                           bool tight, uint32_t* arena, uint32_t* rowptr, GsControl* ctl, uint32_t tight_nb = 0);
+                           bool tight, uint32_t* arena, uint32_t* rowptr, GsControl* ctl, uint32_t tight_nb = 0, bool state = false,
+                           GsTint tint = GsTint{});
 void gs_launch_preprocess(GsPreprocessLaunch& L, hipStream_t st);
 void gs_launch_zero(void* p, uint64_t bytes, hipStream_t st); // bytes: a multiple of 16
 uint32_t gs_scan_blocks(uint32_t n);
@@ -54,6 +56,25 @@ void gs_launch_rows(const uint32_t* arena, const void* grec, const uint32_t* chu
                     uint32_t* sticky, GsReport* rep, hipStream_t st, void (*mark)(void*, int), void* mark_arg);
 void gs_launch_rows_rebuild_keys(const uint32_t* ranges, uint32_t T, const uint32_t* vals, const uint32_t* counts, uint32_t count, uint32_t n,
                                  uint32_t* keys, hipStream_t st);
+// k_state.hip: the state plane's streaming kernels (gs_state.hip).  The plane is 256-byte aligned with np >= n bytes behind it.
+struct GsRegionDev { // a gs_region as the kernel reads it
+    float a[3], b[3];       // SPHERE: centre, radius in b[0].  BOX: min, max
+    float x0, y0, x1, y1;   // SCREEN_RECT bounds as f32
+    float W, H;             // canvas size as f32
+    uint32_t wi, hi;        // ... and as integers (mask stride and bound)
+    float proj[16];         // the camera's proj (= P * V), column-major
+    float viewz[4];         // row 2 of its view matrix: m[2], m[6], m[10], m[14]
+    const uint8_t* mask;    // SCREEN_MASK: device u8[hi][wi]
+};
+// `matched` / `count` are GS_STATE_SLOTS partial sums, GS_STATE_SLOT_STRIDE words (256 bytes) apart, zeroed by the caller and added up
+// on the host: a workgroup adds to slot (workgroup % GS_STATE_SLOTS).  One word would take every workgroup's atomic in turn: 5 958
+// of them at 6.1 M splats were 76 us of a kernel that moves its 79 MB in 20 (profiles/state_ops.txt).
+#define GS_STATE_SLOTS 32
+#define GS_STATE_SLOT_STRIDE 32
+void gs_launch_state_region(uint32_t kind, uint8_t* state, const GsScene& s, uint32_t n, const GsRegionDev& r, uint32_t op, uint32_t bits,
+                            uint32_t where_mask, uint32_t where_value, unsigned long long* matched, hipStream_t st);
+void gs_launch_state_ids(uint8_t* state, const uint32_t* ids, uint64_t n, uint32_t op, uint32_t bits, hipStream_t st);
+void gs_launch_state_count(const uint8_t* state, uint32_t n, uint32_t mask, uint32_t value, unsigned long long* count, hipStream_t st);
 // k_pick.hip: gs_pick, one wave per query over the last frame's lists (queries: {x, y} pairs; results: 12 words per query;
 // contrib: max_contrib {id, weight} pairs per query, or null)
 void gs_launch_pick(const void* gdata, const uint32_t* values, const uint32_t* ranges, const GsFrame& f, uint32_t id_mask, const void* d_queries,

@@ -54,8 +54,29 @@ static int32_t tap(gs_ctx* c, int32_t which, void** ptr, uint64_t* bytes) {
     }
 }
 
+// GS_BUF_SPLAT_STATE: the plane as it is now -- of the scene, not of a frame (every ring member views the same one).
+static int32_t state_tap(gs_ctx* c, void** ptr, uint64_t* bytes) {
+    if (!has_state(c)) return fail(GS_ERR_INVALID_ARGUMENT, "GS_BUF_SPLAT_STATE needs GS_FLAG_SPLAT_STATE");
+    if (!c->scene_mem || !c->scene.state) return fail(GS_ERR_NO_SCENE, "GS_BUF_SPLAT_STATE: no splats uploaded");
+    *ptr = const_cast<uint8_t*>(c->scene.state);
+    *bytes = c->n;
+    return GS_OK;
+}
+
 GS_EXPORT int32_t gs_read_buffer(gs_ctx* c, int32_t which, void* dst, uint64_t size, uint64_t* written) {
     if (!c) return fail(GS_ERR_INVALID_ARGUMENT, "gs_read_buffer: null ctx");
+    if (which == GS_BUF_SPLAT_STATE) { // (state calls return when done: the plane is at rest; frames in flight only read it)
+        void* p = nullptr;
+        uint64_t bytes = 0;
+        const int32_t rc = state_tap(c, &p, &bytes);
+        if (rc != GS_OK) return rc;
+        if (written) *written = bytes;
+        if (!dst) return GS_OK;
+        if (size < bytes) return fail(GS_ERR_INVALID_ARGUMENT, "gs_read_buffer: need %llu bytes, got %llu", (unsigned long long)bytes, (unsigned long long)size);
+        HIP_TRY(hipSetDevice(c->cfg.device));
+        if (bytes) HIP_TRY(hipMemcpy(dst, p, bytes, hipMemcpyDeviceToHost));
+        return GS_OK;
+    }
     c = last_of(c);
     if (!c->have_frame) return fail(GS_ERR_NO_FRAME, "gs_read_buffer: no frame rendered");
     if (c->pending) { int32_t rc = wait_one(c); if (rc != GS_OK) return rc; }
@@ -118,8 +139,9 @@ GS_EXPORT int32_t gs_read_rgba8(gs_ctx* c, void* dst, uint64_t size) {
 
 GS_EXPORT int32_t gs_device_ptr(gs_ctx* c, int32_t which, void** d_ptr) {
     if (!c || !d_ptr) return fail(GS_ERR_INVALID_ARGUMENT, "gs_device_ptr: null argument");
-    c = last_of(c);
     uint64_t bytes = 0;
+    if (which == GS_BUF_SPLAT_STATE) return state_tap(c, d_ptr, &bytes);
+    c = last_of(c);
     if (which == GS_BUF_RGBA8) { *d_ptr = c->rgba8; return GS_OK; }
     if (!c->have_frame) return fail(GS_ERR_NO_FRAME, "gs_device_ptr: no frame rendered");
     return tap(c, which, d_ptr, &bytes);

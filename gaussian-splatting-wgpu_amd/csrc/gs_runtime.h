@@ -1,4 +1,4 @@
-// gs_runtime.h -- private to the runtime sources (gs_context / gs_frame / gs_readback / gs_ply / gs_stages .hip): the error
+// gs_runtime.h -- private to the runtime sources (gs_context / gs_frame / gs_readback / gs_state / gs_ply / gs_stages .hip): the error
 // channel, the owners of HIP resources, and the context.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -87,6 +87,7 @@ struct gs_ctx {
     bool tile_cull = true;                    // GS_OPT_TILE_CULL: tight (opacity-aware) binning in gs_render / gs_render_to
     uint32_t tight_nb = 0;                    // GS_OPT_PROJ_CHUNKS: cull chunks per workgroup of the tight projection (0 = automatic)
     uint32_t blend_ablation = 0;              // profiling only (GS_OPT_BLEND_ABLATION)
+    uint32_t select_tint = 0x80FFFF00u;       // GS_OPT_SELECT_TINT (GS_FLAG_SPLAT_STATE): a<<24 | r<<16 | g<<8 | b
     DevBuf<uint32_t> blend_prof;              // profiling only (ablation bit 16): 4 words per blend walker
     uint32_t blend_prof_blocks = 0;
     // Frames in flight (GS_OPT_FRAMES_IN_FLIGHT): when gs_render is called while this context's previous frame is still on the
@@ -154,6 +155,8 @@ struct gs_ctx {
     uint32_t pxb_n = 0;
     // gs_pick (root ctx): device copies of the queries, the results and the contributor records; allocated on first use
     struct { DevBuf<> q, r, c; uint64_t c_bytes = 0; } pick;
+    // gs_state_* (gs_state.hip): the matched / count word, device copies of an id list and of a screen mask; grown on demand
+    struct { DevBuf<unsigned long long> counter; DevBuf<uint32_t> ids; DevBuf<uint8_t> mask; uint64_t ids_cap = 0, mask_cap = 0; } st;
     Event ev[GS_EV_RING][GS_STAGE_COUNT + 1]; // ring of per-frame stage brackets (GS_FLAG_TIMING)
     bool have_events = false;
     uint64_t timed_from = 0; // first frame index included in the stage means
@@ -185,3 +188,8 @@ void drop_shadows(gs_ctx* c);
 void drop_graph(gs_ctx* c);
 int32_t wait_one(gs_ctx* c);
 inline gs_ctx* last_of(gs_ctx* c) { return (c && c->last) ? c->last : c; }
+inline bool has_state(const gs_ctx* c) { return (c->cfg.flags & GS_FLAG_SPLAT_STATE) != 0; }
+inline GsTint tint_of(uint32_t argb) { // a<<24 | r<<16 | g<<8 | b -> what the projection applies (each quotient one f32 division)
+    return GsTint{{(float)((argb >> 16) & 255u) / 255.0f, (float)((argb >> 8) & 255u) / 255.0f, (float)(argb & 255u) / 255.0f},
+                  (float)(argb >> 24) / 255.0f};
+}

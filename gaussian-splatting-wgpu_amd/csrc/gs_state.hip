@@ -1,0 +1,146 @@
+// gs_state.hip -- the state plane's entry points: region and id selections, counting, restore.  Part of the C ABI
+// (include/gsplat/gs_abi.h "splat state"); the kernels are in k_state.hip, the projection that honours the plane in
+// k_preprocess.hip (STATE).
+//
+// The reference has no counterpart: it is a viewer.  An editor on it would edit its own 320-byte records and upload them again
+// (renderer.ts:130-137); here a selection is one streaming pass over 13 bytes per splat.
+//
+// Every call drains the context's ring first (gs_wait), runs on the context's stream and returns when done: a frame never sees
+// a half-applied call, and the host never has to order a state call against its own frames.  None of them is a frame: nothing
+// of the frame state, the statistics or a captured graph is touched (the graph's projection reads the plane when it is replayed).
+#include "gs_runtime.h"
+
+// What every entry point checks first; drains the ring.  An error of the wait is the call's error: nothing is applied.
+static int32_t state_begin(gs_ctx* c, const char* who) {
+    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, "%s: null ctx", who);
+    if (!has_state(c)) return fail(GS_ERR_INVALID_ARGUMENT, "%s: the context was created without GS_FLAG_SPLAT_STATE", who);
+    if (!c->scene_mem || !c->scene.state) return fail(GS_ERR_NO_SCENE, "%s: no splats uploaded", who);
+    return GS_OK;
+}
+static constexpr size_t kCounterBytes = (size_t)GS_STATE_SLOTS * GS_STATE_SLOT_STRIDE * sizeof(unsigned long long);
+static int32_t state_drain(gs_ctx* c) {
+    const int32_t rc = gs_wait(c);
+    if (rc != GS_OK) return rc;
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    if (!c->st.counter) HIP_TRY(hipMalloc(c->st.counter.out(), kCounterBytes));
+    return GS_OK;
+}
+// The kernels' partial sums (gs_kernels.h GS_STATE_SLOTS): zeroed before the launch, added up after it; returns when the stream is done.
+static int32_t counter_zero(gs_ctx* c) {
+    HIP_TRY(hipMemsetAsync(c->st.counter, 0, kCounterBytes, c->stream));
+    return GS_OK;
+}
+static int32_t counter_sum(gs_ctx* c, unsigned long long* total) {
+    unsigned long long h[GS_STATE_SLOTS * GS_STATE_SLOT_STRIDE];
+    HIP_TRY(hipMemcpyAsync(h, c->st.counter, kCounterBytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    *total = 0;
+    for (int k = 0; k < GS_STATE_SLOTS; ++k) *total += h[k * GS_STATE_SLOT_STRIDE];
+    return GS_OK;
+}
+static int32_t check_op(const char* who, uint32_t op, uint32_t bits) {
+    if (op < GS_STATE_SET || op > GS_STATE_ASSIGN) return fail(GS_ERR_INVALID_ARGUMENT, "%s: unknown op %u (GS_STATE_SET .. GS_STATE_ASSIGN)", who, op);
+    if (bits > 0xFFu) return fail(GS_ERR_INVALID_ARGUMENT, "%s: bits 0x%x do not fit the state byte", who, bits);
+    return GS_OK;
+}
+static uint8_t* plane(gs_ctx* c) { return const_cast<uint8_t*>(c->scene.state); }
+
+GS_EXPORT int32_t gs_state_region(gs_ctx* c, const gs_region* rg, uint32_t op, uint32_t bits, uint64_t* matched) {
+    int32_t rc = state_begin(c, "gs_state_region");
+    if (rc != GS_OK) return rc;
+    if (!rg) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_region: null region");
+    if (rg->struct_size != sizeof(gs_region)) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_region: struct_size %u != %zu", rg->struct_size, sizeof(gs_region));
+    if (rg->kind > GS_REGION_SCREEN_MASK) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_region: unknown region kind %u", rg->kind);
+    rc = check_op("gs_state_region", op, bits);
+    if (rc != GS_OK) return rc;
+    if (rg->where_mask > 0xFFu) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_region: where_mask 0x%x does not fit the state byte", rg->where_mask);
+    const bool screen = rg->kind == GS_REGION_SCREEN_RECT || rg->kind == GS_REGION_SCREEN_MASK;
+    if (screen && !rg->uniforms160) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_region: a screen region needs uniforms160 (the camera)");
+    if (rg->kind == GS_REGION_SCREEN_MASK && !rg->mask) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_region: GS_REGION_SCREEN_MASK needs a mask");
+    rc = state_drain(c);
+    if (rc != GS_OK) return rc;
+
+    GsRegionDev r{};
+    for (int k = 0; k < 3; ++k) { r.a[k] = rg->a[k]; r.b[k] = rg->b[k]; }
+    r.x0 = (float)rg->x0; r.y0 = (float)rg->y0; r.x1 = (float)rg->x1; r.y1 = (float)rg->y1;
+    r.wi = c->frame.width; r.hi = c->frame.height; // the CANVAS, also on a slab context
+    r.W = (float)r.wi; r.H = (float)r.hi;
+    if (screen) {
+        GsUniforms u;
+        memcpy(&u, rg->uniforms160, sizeof(u));
+        memcpy(r.proj, u.proj, sizeof(r.proj));
+        for (int k = 0; k < 4; ++k) r.viewz[k] = u.view[4 * k + 2];
+    }
+    if (rg->kind == GS_REGION_SCREEN_MASK) {
+        const uint64_t mb = (uint64_t)r.wi * r.hi;
+        if (mb > c->st.mask_cap) {
+            c->st.mask_cap = 0;
+            HIP_TRY(hipMalloc(c->st.mask.out(), (size_t)mb));
+            c->st.mask_cap = mb;
+        }
+        HIP_TRY(hipMemcpyAsync(c->st.mask, rg->mask, (size_t)mb, hipMemcpyHostToDevice, c->stream));
+        r.mask = c->st.mask;
+    }
+    rc = counter_zero(c);
+    if (rc != GS_OK) return rc;
+    gs_launch_state_region(rg->kind, plane(c), c->scene, c->n, r, op, bits, rg->where_mask, rg->where_value, c->st.counter, c->stream);
+    HIP_TRY(hipGetLastError());
+    unsigned long long m = 0;
+    rc = counter_sum(c, &m);
+    if (rc != GS_OK) return rc;
+    if (matched) *matched = m;
+    return GS_OK;
+}
+
+GS_EXPORT int32_t gs_state_ids(gs_ctx* c, const uint32_t* ids, uint64_t n, uint32_t op, uint32_t bits) {
+    int32_t rc = state_begin(c, "gs_state_ids");
+    if (rc != GS_OK) return rc;
+    if (!ids && n) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_ids: null ids");
+    rc = check_op("gs_state_ids", op, bits);
+    if (rc != GS_OK) return rc;
+    for (uint64_t i = 0; i < n; ++i) // before anything is changed
+        if (ids[i] >= c->n)
+            return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_ids: ids[%llu] = %u is not a splat (N = %u)", (unsigned long long)i, ids[i], c->n);
+    rc = state_drain(c);
+    if (rc != GS_OK) return rc;
+    if (!n) return GS_OK;
+    if (n > c->st.ids_cap) {
+        c->st.ids_cap = 0;
+        HIP_TRY(hipMalloc(c->st.ids.out(), (size_t)n * 4));
+        c->st.ids_cap = n;
+    }
+    HIP_TRY(hipMemcpyAsync(c->st.ids, ids, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    gs_launch_state_ids(plane(c), c->st.ids, n, op, bits, c->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream)); // (also: the caller's ids have been copied)
+    return GS_OK;
+}
+
+GS_EXPORT int32_t gs_state_count(gs_ctx* c, uint32_t mask, uint32_t value, uint64_t* count) {
+    int32_t rc = state_begin(c, "gs_state_count");
+    if (rc != GS_OK) return rc;
+    if (!count) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_count: null count");
+    rc = state_drain(c);
+    if (rc != GS_OK) return rc;
+    rc = counter_zero(c);
+    if (rc != GS_OK) return rc;
+    gs_launch_state_count(c->scene.state, c->n, mask, value, c->st.counter, c->stream);
+    HIP_TRY(hipGetLastError());
+    unsigned long long m = 0;
+    rc = counter_sum(c, &m);
+    if (rc != GS_OK) return rc;
+    *count = m;
+    return GS_OK;
+}
+
+GS_EXPORT int32_t gs_state_write(gs_ctx* c, const uint8_t* src, uint64_t n) {
+    int32_t rc = state_begin(c, "gs_state_write");
+    if (rc != GS_OK) return rc;
+    if (n != c->n) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_write: n = %llu, the plane holds %u splats (whole plane only)", (unsigned long long)n, c->n);
+    if (!src && n) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_write: null source");
+    rc = state_drain(c);
+    if (rc != GS_OK) return rc;
+    if (n) HIP_TRY(hipMemcpyAsync(plane(c), src, (size_t)n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return GS_OK;
+}

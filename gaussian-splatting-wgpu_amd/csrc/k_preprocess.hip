@@ -231,9 +231,14 @@ typedef uint32_t gs_row_u32x3 __attribute__((ext_vector_type(3), aligned(4)));
 //                workgroup its dense phases would run on a few dozen lanes each (131-145 us per rank at 8 slabs).  The tight
 //                path always uses 8: 1 490 workgroups at 6.1 M gaussians keep the bump cursors and the row histogram cold
 //                (one atomic per workgroup and trip / per touched tile row instead of eight times as many).
-template <bool TIGHT, int NB>
+// STATE        : the context keeps a state byte per splat (GS_FLAG_SPLAT_STATE, s.state).  The byte is loaded in phase 1 WITH the
+//                position loads (one more unconditional load of the group: 1 B on the 12 B every gaussian costs); a HIDDEN splat
+//                fails the cull like one outside the frustum; a survivor's byte rides in the free high half of its s_ids word
+//                (the low half is an offset < 4096) into phase 3, where a SELECTED splat's colour is drawn towards the tint.
+//                STATE = false is the code a context without the plane has always launched: nothing of this is in it.
+template <bool TIGHT, int NB, bool STATE>
 __global__ __launch_bounds__(256, PRE_WAVES) void gs_preprocess_kernel(GsScene s, GsUniforms u, GsFrame f, uint4* __restrict__ gdata,
-                                                             uint32_t* __restrict__ tile_counts, GsTightOut to) {
+                                                             uint32_t* __restrict__ tile_counts, GsTightOut to, GsTint tint) {
     __shared__ uint32_t s_ids[PRE_G * NB];
     constexpr bool KEEP_POS = NB == 2; // (whole canvas; at NB = 8 the 48 KB would halve the slab workgroups per CU: 65-100 -> 128-184 us per rank)
     __shared__ float s_pos[3][KEEP_POS ? PRE_G * NB : 1];
@@ -264,6 +269,7 @@ __global__ __launch_bounds__(256, PRE_WAVES) void gs_preprocess_kernel(GsScene s
 #pragma unroll 1
         for (int h = 0; h < 2 * NB / GRP; ++h) {
             float X[GRP], Y[GRP], Z[GRP], S[GRP];
+            uint32_t B[GRP];
             // every position load of the group is issued before the first test: the loads are UNCONDITIONAL (index clamped; a
             // conditional load is waited for right behind its issue) and a scheduling barrier keeps the tests behind them --
             // the compiler had made four load / wait / test rounds of this
@@ -273,6 +279,7 @@ __global__ __launch_bounds__(256, PRE_WAVES) void gs_preprocess_kernel(GsScene s
                 const uint32_t ic = i < f.n ? i : f.n - 1u;
                 X[k] = s.px[ic]; Y[k] = s.py[ic]; Z[k] = s.pz[ic];
                 S[k] = 0.0f;
+                B[k] = STATE ? (uint32_t)s.state[ic] : 0u; // (unconditional like the positions: one of the group's loads)
             }
             if (!f.full) { // (one branch around the group's four loads, not one per load with its wait behind it)
 #pragma unroll
@@ -289,6 +296,7 @@ __global__ __launch_bounds__(256, PRE_WAVES) void gs_preprocess_kernel(GsScene s
                 bool v = false;
                 if (i < f.n) {
                     v = in_frustum_slab(u, f, X[k], Y[k], Z[k], S[k]);
+                    if (STATE && (B[k] & GS_ST_HIDDEN)) v = false; // a hidden splat: exactly a culled one
                     if (!v) tile_counts[i] = 0u;
                 }
                 const unsigned long long b = __ballot(v);
@@ -298,7 +306,7 @@ __global__ __launch_bounds__(256, PRE_WAVES) void gs_preprocess_kernel(GsScene s
                     at = (uint32_t)__builtin_amdgcn_readlane((int)at, __builtin_ctzll(b));
                     if (v) {
                         const uint32_t slot = at + (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
-                        s_ids[slot] = off;
+                        s_ids[slot] = STATE ? (off | (B[k] << 16)) : off;
                         if (KEEP_POS) { s_pos[0][slot] = X[k]; s_pos[1][slot] = Y[k]; s_pos[2][slot] = Z[k]; } // the survivor's position rides along
                     }
                 }
@@ -308,6 +316,7 @@ __global__ __launch_bounds__(256, PRE_WAVES) void gs_preprocess_kernel(GsScene s
         nvis = s_misc[1];
     } else {
         bool vis[2];
+        uint32_t sb[2] = {0u, 0u};
         unsigned long long bal[2];
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
@@ -315,6 +324,10 @@ __global__ __launch_bounds__(256, PRE_WAVES) void gs_preprocess_kernel(GsScene s
             vis[k] = false;
             if (i < f.n) {
                 vis[k] = in_frustum_slab(u, f, s.px[i], s.py[i], s.pz[i], f.full ? 0.0f : s.smax[i]);
+                if (STATE) {
+                    sb[k] = (uint32_t)s.state[i];
+                    if (sb[k] & GS_ST_HIDDEN) vis[k] = false;
+                }
                 if (!vis[k]) tile_counts[i] = 0u;
             }
             bal[k] = __ballot(vis[k]);
@@ -331,7 +344,7 @@ __global__ __launch_bounds__(256, PRE_WAVES) void gs_preprocess_kernel(GsScene s
                 nvis += c;
             }
             if (k == 1) before += s_cnt[0][0] + s_cnt[0][1] + s_cnt[0][2] + s_cnt[0][3];
-            if (vis[k]) s_ids[before + (uint32_t)__popcll(bal[k] & ((1ull << lane) - 1ull))] = k * 256 + tid;
+            if (vis[k]) s_ids[before + (uint32_t)__popcll(bal[k] & ((1ull << lane) - 1ull))] = (k * 256 + tid) | (STATE ? sb[k] << 16 : 0u);
         }
         __syncthreads();
     }
@@ -346,7 +359,8 @@ __global__ __launch_bounds__(256, PRE_WAVES) void gs_preprocess_kernel(GsScene s
         // TIGHT: every thread takes every trip (workgroup barriers inside); a thread without a survivor recomputes the
         // last one and writes nothing
         const bool active = v < nvis;
-        const uint32_t i = base + s_ids[active ? v : nvis - 1u];
+        const uint32_t sid = s_ids[active ? v : nvis - 1u];
+        const uint32_t i = base + (STATE ? (sid & 0xFFFFu) : sid);
         const float4* geo = s.geo + (uint64_t)i * 2;
         // (NB = 2: the position the cull loaded rides through LDS: three gathers per survivor less in a kernel bound by its memory pipeline)
         const float x = KEEP_POS ? s_pos[0][v < nvis ? v : nvis - 1u] : s.px[i], y = KEEP_POS ? s_pos[1][v < nvis ? v : nvis - 1u] : s.py[i],
@@ -519,6 +533,10 @@ __global__ __launch_bounds__(256, PRE_WAVES) void gs_preprocess_kernel(GsScene s
         // ---- phase 3: colour (:240-280) and opacity (:282-294) ----
         float col[3];
         sh_colour(s.sh + (uint64_t)i * 12, x, y, z, u, col);
+        if (STATE && ((sid >> 16) & GS_ST_SELECTED) && tint.k != 0.0f) { // a = 0: the colour is left as it is, not multiplied by 0
+#pragma unroll
+            for (int c = 0; c < 3; ++c) col[c] = col[c] + tint.k * (tint.t[c] - col[c]);
+        }
         if (!TIGHT) opacity = sigmoid_ref(so.w);
         // GaussianData record (:97-104), 64 B as four 16-byte stores
         uint4* o4 = gdata + (uint64_t)i * 4;
@@ -553,7 +571,7 @@ void gs_launch_repack(const void* d_aos, uint32_t n, const GsScene& s, hipStream
 // The projection's launch as data: the one kernel of a frame whose arguments change from frame to frame (the uniforms, by
 // value), so a captured frame graph (gs_frame.hip) re-launches it with updated parameters.
 void gs_preprocess_prepare(GsPreprocessLaunch& L, const GsScene& s, const GsUniforms& u, const GsFrame& f, void* gdata, uint32_t* counts,
-                           bool tight, uint32_t* arena, uint32_t* rowptr, GsControl* ctl, uint32_t tight_nb) {
+                           bool tight, uint32_t* arena, uint32_t* rowptr, GsControl* ctl, uint32_t tight_nb, bool state, GsTint tint) {
     // cull chunks per workgroup (see NB).  Reference binning: 8 for a slab narrower than 30 % of the canvas, 4 up to 75 %, else 1.
     // Tight: 2 on the whole canvas (5 958 workgroups at 6.1 M gaussians: with 8 the 1 490 workgroups were 1.45 residency rounds,
     // the second one half empty), 8 / 4 for slabs as above.
@@ -561,13 +579,20 @@ void gs_preprocess_prepare(GsPreprocessLaunch& L, const GsScene& s, const GsUnif
     uint32_t nb = f.full || wcols * 4u > f.ntx * 3u ? 1u : (wcols * 10u > f.ntx * 3u ? 4u : 8u);
     if (tight) nb = tight_nb ? tight_nb : (nb == 1u ? 2u : nb);
     L.blocks = (f.n + PRE_G * nb - 1) / (PRE_G * nb);
-    if (tight) L.func = nb == 8u ? (const void*)&gs_preprocess_kernel<true, 8> : nb == 4u ? (const void*)&gs_preprocess_kernel<true, 4>
-                                                                                       : (const void*)&gs_preprocess_kernel<true, 2>;
-    else L.func = nb == 8u ? (const void*)&gs_preprocess_kernel<false, 8> : nb == 4u ? (const void*)&gs_preprocess_kernel<false, 4>
-                                                                                        : (const void*)&gs_preprocess_kernel<false, 1>;
-    L.s = s; L.u = u; L.f = f; L.gdata = gdata; L.counts = counts;
+    if (state) {
+        if (tight) L.func = nb == 8u ? (const void*)&gs_preprocess_kernel<true, 8, true> : nb == 4u ? (const void*)&gs_preprocess_kernel<true, 4, true>
+                                                                                                     : (const void*)&gs_preprocess_kernel<true, 2, true>;
+        else L.func = nb == 8u ? (const void*)&gs_preprocess_kernel<false, 8, true> : nb == 4u ? (const void*)&gs_preprocess_kernel<false, 4, true>
+                                                                                                  : (const void*)&gs_preprocess_kernel<false, 1, true>;
+    } else {
+        if (tight) L.func = nb == 8u ? (const void*)&gs_preprocess_kernel<true, 8, false> : nb == 4u ? (const void*)&gs_preprocess_kernel<true, 4, false>
+                                                                                                      : (const void*)&gs_preprocess_kernel<true, 2, false>;
+        else L.func = nb == 8u ? (const void*)&gs_preprocess_kernel<false, 8, false> : nb == 4u ? (const void*)&gs_preprocess_kernel<false, 4, false>
+                                                                                                   : (const void*)&gs_preprocess_kernel<false, 1, false>;
+    }
+    L.s = s; L.u = u; L.f = f; L.gdata = gdata; L.counts = counts; L.tint = tint;
     L.to.arena = arena; L.to.rowptr = rowptr; L.to.ctl = ctl;
-    L.args[0] = &L.s; L.args[1] = &L.u; L.args[2] = &L.f; L.args[3] = &L.gdata; L.args[4] = &L.counts; L.args[5] = &L.to;
+    L.args[0] = &L.s; L.args[1] = &L.u; L.args[2] = &L.f; L.args[3] = &L.gdata; L.args[4] = &L.counts; L.args[5] = &L.to; L.args[6] = &L.tint;
 }
 void gs_launch_preprocess(GsPreprocessLaunch& L, hipStream_t st) {
     if (!L.f.n) return;

@@ -366,6 +366,159 @@ static napi_value js_pick(napi_env env, napi_callback_info info) {
     return out;
 }
 
+/* ---- splat state (GS_FLAG_SPLAT_STATE): 1:1 wrappers of gs_state_* --------------------------------------------------------- */
+static int get_f32x3_prop(napi_env env, napi_value obj, const char* name, float* out) {
+    napi_value v, e;
+    bool has = false;
+    if (napi_has_named_property(env, obj, name, &has) != napi_ok || !has) return 0;
+    if (napi_get_named_property(env, obj, name, &v) != napi_ok) return 0;
+    for (uint32_t k = 0; k < 3; ++k) {
+        double d;
+        if (napi_get_element(env, v, k, &e) != napi_ok || napi_get_value_double(env, e, &d) != napi_ok) return 0;
+        out[k] = (float)d;
+    }
+    return 1;
+}
+
+/* stateRegion(handle, {kind, a, b, x0, y0, x1, y1, uniforms, mask, whereMask, whereValue}, op, bits) -> matched */
+static napi_value js_state_region(napi_env env, napi_callback_info info) {
+    size_t argc = 4;
+    napi_value argv[4];
+    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    gs_ctx* ctx = argc >= 4 ? unwrap(env, argv[0]) : NULL;
+    if (!ctx) return NULL;
+    gs_region rg;
+    memset(&rg, 0, sizeof(rg));
+    rg.struct_size = sizeof(rg);
+    if (!get_u32_prop(env, argv[1], "kind", &rg.kind)) {
+        napi_throw_type_error(env, NULL, "gsplat.stateRegion: {kind} required");
+        return NULL;
+    }
+    get_f32x3_prop(env, argv[1], "a", rg.a);
+    get_f32x3_prop(env, argv[1], "b", rg.b);
+    get_u32_prop(env, argv[1], "x0", &rg.x0);
+    get_u32_prop(env, argv[1], "y0", &rg.y0);
+    get_u32_prop(env, argv[1], "x1", &rg.x1);
+    get_u32_prop(env, argv[1], "y1", &rg.y1);
+    get_u32_prop(env, argv[1], "whereMask", &rg.where_mask);
+    get_u32_prop(env, argv[1], "whereValue", &rg.where_value);
+    napi_value v;
+    bool has = false;
+    void* data = NULL;
+    size_t len = 0;
+    if (napi_has_named_property(env, argv[1], "uniforms", &has) == napi_ok && has &&
+        napi_get_named_property(env, argv[1], "uniforms", &v) == napi_ok && get_bytes(env, v, &data, &len)) {
+        if (len < GS_UNIFORM_BYTES) { napi_throw_type_error(env, NULL, "gsplat.stateRegion: uniforms must be the 160-byte block"); return NULL; }
+        rg.uniforms160 = data;
+    }
+    has = false;
+    if (napi_has_named_property(env, argv[1], "mask", &has) == napi_ok && has &&
+        napi_get_named_property(env, argv[1], "mask", &v) == napi_ok && get_bytes(env, v, &data, &len)) {
+        uint32_t cw = 0, ch = 0; /* the mask covers the CANVAS (the JS Renderer passes its canvas size): checked against the bytes given */
+        if (!get_u32_prop(env, argv[1], "maskWidth", &cw) || !get_u32_prop(env, argv[1], "maskHeight", &ch) || (double)len < (double)cw * (double)ch) {
+            napi_throw_type_error(env, NULL, "gsplat.stateRegion: mask needs maskWidth, maskHeight and width * height bytes");
+            return NULL;
+        }
+        rg.mask = (const uint8_t*)data;
+    }
+    uint32_t op = 0, bits = 0;
+    NAPI_CALL(env, napi_get_value_uint32(env, argv[2], &op));
+    NAPI_CALL(env, napi_get_value_uint32(env, argv[3], &bits));
+    uint64_t matched = 0;
+    int32_t rc = gs_state_region(ctx, &rg, op, bits, &matched);
+    if (rc != GS_OK) return throw_gs(env, rc);
+    napi_value out;
+    NAPI_CALL(env, napi_create_double(env, (double)matched, &out));
+    return out;
+}
+
+/* stateIds(handle, ids (Uint32Array), op, bits) */
+static napi_value js_state_ids(napi_env env, napi_callback_info info) {
+    size_t argc = 4;
+    napi_value argv[4];
+    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    gs_ctx* ctx = argc >= 4 ? unwrap(env, argv[0]) : NULL;
+    if (!ctx) return NULL;
+    void* data = NULL;
+    size_t len = 0;
+    if (!get_bytes(env, argv[1], &data, &len) || len % 4 != 0) {
+        napi_throw_type_error(env, NULL, "gsplat.stateIds: expects a Uint32Array of splat indices");
+        return NULL;
+    }
+    uint32_t op = 0, bits = 0;
+    NAPI_CALL(env, napi_get_value_uint32(env, argv[2], &op));
+    NAPI_CALL(env, napi_get_value_uint32(env, argv[3], &bits));
+    int32_t rc = gs_state_ids(ctx, (const uint32_t*)data, (uint64_t)(len / 4), op, bits);
+    return rc == GS_OK ? NULL : throw_gs(env, rc);
+}
+
+/* stateCount(handle, mask, value) -> count */
+static napi_value js_state_count(napi_env env, napi_callback_info info) {
+    size_t argc = 3;
+    napi_value argv[3];
+    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    gs_ctx* ctx = argc >= 3 ? unwrap(env, argv[0]) : NULL;
+    if (!ctx) return NULL;
+    uint32_t mask = 0, value = 0;
+    NAPI_CALL(env, napi_get_value_uint32(env, argv[1], &mask));
+    NAPI_CALL(env, napi_get_value_uint32(env, argv[2], &value));
+    uint64_t count = 0;
+    int32_t rc = gs_state_count(ctx, mask, value, &count);
+    if (rc != GS_OK) return throw_gs(env, rc);
+    napi_value out;
+    NAPI_CALL(env, napi_create_double(env, (double)count, &out));
+    return out;
+}
+
+/* readState(handle) -> ArrayBuffer (N bytes): the plane as it is now */
+static napi_value js_read_state(napi_env env, napi_callback_info info) {
+    size_t argc = 1;
+    napi_value argv[1];
+    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    gs_ctx* ctx = argc >= 1 ? unwrap(env, argv[0]) : NULL;
+    if (!ctx) return NULL;
+    uint64_t bytes = 0;
+    int32_t rc = gs_read_buffer(ctx, GS_BUF_SPLAT_STATE, NULL, 0, &bytes);
+    if (rc != GS_OK) return throw_gs(env, rc);
+    void* dst = NULL;
+    napi_value ab;
+    NAPI_CALL(env, napi_create_arraybuffer(env, (size_t)bytes, &dst, &ab));
+    if (bytes) rc = gs_read_buffer(ctx, GS_BUF_SPLAT_STATE, dst, bytes, NULL);
+    return rc == GS_OK ? ab : throw_gs(env, rc);
+}
+
+/* writeState(handle, bytes (Uint8Array of N)) */
+static napi_value js_write_state(napi_env env, napi_callback_info info) {
+    size_t argc = 2;
+    napi_value argv[2];
+    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    gs_ctx* ctx = argc >= 2 ? unwrap(env, argv[0]) : NULL;
+    if (!ctx) return NULL;
+    void* data = NULL;
+    size_t len = 0;
+    if (!get_bytes(env, argv[1], &data, &len)) {
+        napi_throw_type_error(env, NULL, "gsplat.writeState: expects a Uint8Array of N state bytes");
+        return NULL;
+    }
+    int32_t rc = gs_state_write(ctx, (const uint8_t*)data, (uint64_t)len);
+    return rc == GS_OK ? NULL : throw_gs(env, rc);
+}
+
+/* setOption(handle, key, value) */
+static napi_value js_set_option(napi_env env, napi_callback_info info) {
+    size_t argc = 3;
+    napi_value argv[3];
+    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    gs_ctx* ctx = argc >= 3 ? unwrap(env, argv[0]) : NULL;
+    if (!ctx) return NULL;
+    int32_t key = 0;
+    double value = 0;
+    NAPI_CALL(env, napi_get_value_int32(env, argv[1], &key));
+    NAPI_CALL(env, napi_get_value_double(env, argv[2], &value));
+    int32_t rc = gs_set_option(ctx, key, (int64_t)value);
+    return rc == GS_OK ? NULL : throw_gs(env, rc);
+}
+
 static void set_num(napi_env env, napi_value obj, const char* k, double v) {
     napi_value n;
     napi_create_double(env, v, &n);
@@ -598,6 +751,8 @@ static napi_value init(napi_env env, napi_value exports) {
         {"readBuffer", js_read_buffer}, {"stats", js_stats},             {"slab", js_slab},
         {"loadPly", js_load_ply},    {"shareSplats", js_share},       {"uploadPly", js_upload_ply},
         {"hostAlloc", js_host_alloc}, {"renderToSink", js_render_to_sink}, {"pick", js_pick},
+        {"stateRegion", js_state_region}, {"stateIds", js_state_ids},  {"stateCount", js_state_count},
+        {"readState", js_read_state}, {"writeState", js_write_state},  {"setOption", js_set_option},
     };
     for (size_t i = 0; i < sizeof(fns) / sizeof(fns[0]); ++i) {
         napi_value f;
@@ -609,6 +764,9 @@ static napi_value init(napi_env env, napi_value exports) {
     set_num(env, exports, "FLAG_F32_TAP", GS_FLAG_F32_TAP);
     set_num(env, exports, "FLAG_TIMING", GS_FLAG_TIMING);
     set_num(env, exports, "FLAG_AUX_OUTPUTS", GS_FLAG_AUX_OUTPUTS);
+    set_num(env, exports, "FLAG_SPLAT_STATE", GS_FLAG_SPLAT_STATE);
+    set_num(env, exports, "BUF_SPLAT_STATE", GS_BUF_SPLAT_STATE);
+    set_num(env, exports, "OPT_SELECT_TINT", GS_OPT_SELECT_TINT);
     set_num(env, exports, "BUF_ALPHA_F32", GS_BUF_ALPHA_F32);
     set_num(env, exports, "BUF_DEPTH_F32", GS_BUF_DEPTH_F32);
     set_num(env, exports, "PICK_OK", GS_PICK_OK);

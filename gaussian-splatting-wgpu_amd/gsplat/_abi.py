@@ -15,6 +15,7 @@ GS_FLAG_EXACT_BLEND = 0x1
 GS_FLAG_F32_TAP = 0x2
 GS_FLAG_TIMING = 0x4
 GS_FLAG_AUX_OUTPUTS = 0x8
+GS_FLAG_SPLAT_STATE = 0x10
 
 GS_STAGE_NAMES = ("preprocess", "scan", "emit", "sort", "ranges", "blend")
 
@@ -22,6 +23,7 @@ GS_STAGE_NAMES = ("preprocess", "scan", "emit", "sort", "ranges", "blend")
  GS_BUF_VALUES, GS_BUF_RANGES, GS_BUF_RGBA8, GS_BUF_RGB_F32, GS_BUF_BLOCK_MASKS) = range(11)
 GS_BUF_ALPHA_F32 = 13  # GS_FLAG_AUX_OUTPUTS (11 and 12 are the library's profiling and test taps)
 GS_BUF_DEPTH_F32 = 14
+GS_BUF_SPLAT_STATE = 15  # GS_FLAG_SPLAT_STATE
 
 GS_OPT_BLEND_ABLATION = 1
 GS_OPT_PERSISTENT_GRID = 2
@@ -33,6 +35,7 @@ GS_OPT_TILE_CULL = 7
 GS_OPT_FRAMES_IN_FLIGHT = 8
 GS_OPT_FRAME_GRAPH = 9
 GS_OPT_PROJ_CHUNKS = 10
+GS_OPT_SELECT_TINT = 11
 
 GS_ERR_INVALID_ARGUMENT = -1
 GS_ERR_NO_FRAME = -6
@@ -44,12 +47,19 @@ GS_PICK_NONE = 0xFFFFFFFF
 GS_PICK_MAX_QUERIES = 65536
 GS_PICK_MAX_CONTRIB = 256
 
+# splat state (GS_FLAG_SPLAT_STATE)
+GS_SPLAT_HIDDEN = 0x1
+GS_SPLAT_SELECTED = 0x2
+GS_STATE_SET, GS_STATE_CLEAR, GS_STATE_TOGGLE, GS_STATE_ASSIGN = 1, 2, 3, 4
+GS_REGION_ALL, GS_REGION_SPHERE, GS_REGION_BOX, GS_REGION_SCREEN_RECT, GS_REGION_SCREEN_MASK = range(5)
+GS_SELECT_TINT_DEFAULT = 0x80FFFF00
+
 # every symbol include/gsplat/gs_abi.h declares
 ABI_SYMBOLS = ("gs_last_error", "gs_abi_version", "gs_create", "gs_destroy", "gs_upload_splats", "gs_upload_splats_device",
                "gs_share_splats",
                "gs_ply_load", "gs_ply_free", "gs_upload_ply",
                "gs_render", "gs_render_debug", "gs_render_to", "gs_wait", "gs_render_host", "gs_wait_ticket", "gs_host_alloc", "gs_host_free", "gs_read_rgba8", "gs_read_buffer", "gs_device_ptr",
-               "gs_get_stats", "gs_pick", "gs_set_option", "gs_slab_width", "gs_assemble_slabs", "gs_sort_pairs_u32",
+               "gs_get_stats", "gs_pick", "gs_state_region", "gs_state_ids", "gs_state_count", "gs_state_write", "gs_set_option", "gs_slab_width", "gs_assemble_slabs", "gs_sort_pairs_u32",
                "gs_exclusive_scan_u32")
 
 
@@ -83,6 +93,13 @@ class GsPickResult(ctypes.Structure):
 
 class GsPickContrib(ctypes.Structure):
     _fields_ = [("id", ctypes.c_uint32), ("weight", ctypes.c_float)]
+
+
+class GsRegion(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("kind", ctypes.c_uint32), ("a", ctypes.c_float * 3), ("b", ctypes.c_float * 3),
+                ("x0", ctypes.c_uint32), ("y0", ctypes.c_uint32), ("x1", ctypes.c_uint32), ("y1", ctypes.c_uint32),
+                ("uniforms160", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("where_mask", ctypes.c_uint32),
+                ("where_value", ctypes.c_uint32)]
 
 
 # numpy views of the same records (what Renderer.pick returns)
@@ -132,6 +149,10 @@ def load():
     L.gs_device_ptr.argtypes = [vp, i32, ctypes.POINTER(vp)]
     L.gs_get_stats.argtypes = [vp, ctypes.POINTER(GsStats)]
     L.gs_pick.argtypes = [vp, vp, u32, vp, u32, vp]
+    L.gs_state_region.argtypes = [vp, ctypes.POINTER(GsRegion), u32, u32, ctypes.POINTER(u64)]
+    L.gs_state_ids.argtypes = [vp, vp, u64, u32, u32]
+    L.gs_state_count.argtypes = [vp, u32, u32, ctypes.POINTER(u64)]
+    L.gs_state_write.argtypes = [vp, vp, u64]
     L.gs_set_option.argtypes = [vp, i32, ctypes.c_int64]
     L.gs_slab_width.argtypes = [vp, ctypes.POINTER(u32), ctypes.POINTER(u32)]
     L.gs_assemble_slabs.argtypes = [vp, vp, ctypes.POINTER(u32), u32, u64, vp]

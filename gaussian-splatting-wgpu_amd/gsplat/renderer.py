@@ -196,6 +196,83 @@ class Renderer:
                 ids.append(np.unique(f[f != _abi.GS_PICK_NONE]))
         return np.unique(np.concatenate(ids))
 
+    # -- splat state (GS_FLAG_SPLAT_STATE) ------------------------------------------------------------
+    def state_region(self, kind, op, bits, where=(0, 0), *, a=(0, 0, 0), b=(0, 0, 0), rect=(0, 0, 0, 0), uniforms=None, mask=None):
+        """gs_state_region: applies `op` (GS_STATE_*) with `bits` to every resident splat whose CENTRE lies in the region and
+        whose byte passes (s & where[0]) == where[1]; returns how many those are.  kind GS_REGION_SPHERE: a centre, b[0] radius;
+        BOX: a min, b max (inclusive); SCREEN_RECT: rect = canvas pixels (x0, y0, x1, y1), half open, under the camera
+        `uniforms`; SCREEN_MASK: mask = u8[height, width] of the canvas (nonzero = inside) under `uniforms`; ALL: everything.
+        Completes every frame in flight first; the next frame sees the new state."""
+        r = _abi.GsRegion()
+        r.struct_size, r.kind = ctypes.sizeof(_abi.GsRegion), int(kind)
+        r.a[:] = [float(v) for v in a]
+        r.b[:] = [float(v) for v in b]
+        r.x0, r.y0, r.x1, r.y1 = (int(v) for v in rect)
+        u = m = None  # (kept alive until the call returns)
+        if uniforms is not None:
+            u = np.ascontiguousarray(uniforms, dtype=np.float32).reshape(40)
+            r.uniforms160 = u.ctypes.data
+        if mask is not None:
+            m = np.ascontiguousarray(mask, dtype=np.uint8)
+            if m.shape != (self.canvas.height, self.canvas.width):
+                raise ValueError("state_region: the mask must be u8[canvas.height, canvas.width]")
+            r.mask = m.ctypes.data
+        r.where_mask, r.where_value = int(where[0]), int(where[1])
+        matched = ctypes.c_uint64()
+        check(self._L.gs_state_region(self._ctx, ctypes.byref(r), int(op), int(bits), ctypes.byref(matched)))
+        return int(matched.value)
+
+    def state_ids(self, ids, op, bits):
+        """gs_state_ids: the same for a list of splat indices (what pick / pick_rect return); duplicates behave as the sequential
+        application would."""
+        i = np.asarray(ids)
+        if i.size and (i.dtype.kind not in "iu" or i.min() < 0 or i.max() > 0xFFFFFFFF):
+            raise ValueError("state_ids: ids must be non-negative 32-bit integers")
+        i = np.ascontiguousarray(i, dtype=np.uint32).ravel()
+        check(self._L.gs_state_ids(self._ctx, i.ctypes.data if i.size else None, i.size, int(op), int(bits)))
+
+    def state_count(self, mask, value):
+        """gs_state_count: splats with (s & mask) == value."""
+        n = ctypes.c_uint64()
+        check(self._L.gs_state_count(self._ctx, int(mask), int(value), ctypes.byref(n)))
+        return int(n.value)
+
+    def read_state(self):
+        """The state plane as it is now, u8[N] (GS_BUF_SPLAT_STATE): a snapshot for undo, or a filter over the host's own records."""
+        n = ctypes.c_uint64()
+        check(self._L.gs_read_buffer(self._ctx, _abi.GS_BUF_SPLAT_STATE, None, 0, ctypes.byref(n)))
+        out = np.empty(n.value, dtype=np.uint8)
+        if n.value:
+            check(self._L.gs_read_buffer(self._ctx, _abi.GS_BUF_SPLAT_STATE, out.ctypes.data, out.nbytes, None))
+        return out
+
+    def write_state(self, arr):
+        """gs_state_write: replaces the whole plane (u8[N]): undo / restore."""
+        a = np.ascontiguousarray(arr, dtype=np.uint8).ravel()
+        check(self._L.gs_state_write(self._ctx, a.ctypes.data if a.size else None, a.size))
+
+    def select_rect(self, x0, y0, x1, y1, uniforms, op=_abi.GS_STATE_SET):
+        return self.state_region(_abi.GS_REGION_SCREEN_RECT, op, _abi.GS_SPLAT_SELECTED, rect=(x0, y0, x1, y1), uniforms=uniforms)
+
+    def select_mask(self, mask, uniforms, op=_abi.GS_STATE_SET):
+        return self.state_region(_abi.GS_REGION_SCREEN_MASK, op, _abi.GS_SPLAT_SELECTED, mask=mask, uniforms=uniforms)
+
+    def select_sphere(self, centre, radius, op=_abi.GS_STATE_SET):
+        return self.state_region(_abi.GS_REGION_SPHERE, op, _abi.GS_SPLAT_SELECTED, a=centre, b=(radius, 0, 0))
+
+    def select_box(self, lo, hi, op=_abi.GS_STATE_SET):
+        return self.state_region(_abi.GS_REGION_BOX, op, _abi.GS_SPLAT_SELECTED, a=lo, b=hi)
+
+    def clear_selection(self):
+        return self.state_region(_abi.GS_REGION_ALL, _abi.GS_STATE_CLEAR, _abi.GS_SPLAT_SELECTED)
+
+    def hide_selected(self):
+        return self.state_region(_abi.GS_REGION_ALL, _abi.GS_STATE_SET, _abi.GS_SPLAT_HIDDEN,
+                                 where=(_abi.GS_SPLAT_SELECTED, _abi.GS_SPLAT_SELECTED))
+
+    def unhide_all(self):
+        return self.state_region(_abi.GS_REGION_ALL, _abi.GS_STATE_CLEAR, _abi.GS_SPLAT_HIDDEN)
+
     def device_ptr(self, which):
         p = ctypes.c_void_p()
         check(self._L.gs_device_ptr(self._ctx, which, ctypes.byref(p)))
@@ -291,6 +368,48 @@ class PipelinedRenderer:
     def set_option(self, key, value):
         for r in self.renderers:
             r.set_option(key, value)
+
+    # splat state: the plane lives with the owner's splats, the borrowers render it.  Their frames are the host's to drain
+    # (gs_abi.h): every slot is drained here, then the owner is asked
+    def _state_owner(self):
+        self.wait()
+        return self.renderers[0]
+
+    def state_region(self, *a, **kw):
+        return self._state_owner().state_region(*a, **kw)
+
+    def state_ids(self, ids, op, bits):
+        return self._state_owner().state_ids(ids, op, bits)
+
+    def state_count(self, mask, value):
+        return self._state_owner().state_count(mask, value)
+
+    def read_state(self):
+        return self._state_owner().read_state()
+
+    def write_state(self, arr):
+        return self._state_owner().write_state(arr)
+
+    def select_rect(self, *a, **kw):
+        return self._state_owner().select_rect(*a, **kw)
+
+    def select_mask(self, *a, **kw):
+        return self._state_owner().select_mask(*a, **kw)
+
+    def select_sphere(self, *a, **kw):
+        return self._state_owner().select_sphere(*a, **kw)
+
+    def select_box(self, *a, **kw):
+        return self._state_owner().select_box(*a, **kw)
+
+    def clear_selection(self):
+        return self._state_owner().clear_selection()
+
+    def hide_selected(self):
+        return self._state_owner().hide_selected()
+
+    def unhide_all(self):
+        return self._state_owner().unhide_all()
 
     def destroy(self):
         for r in reversed(self.renderers):  # borrowers first

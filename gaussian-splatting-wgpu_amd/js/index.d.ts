@@ -37,8 +37,23 @@ export class Renderer {
   readDepth(normalized?: boolean): Float32Array;
   /** gs_pick on the last frame: queries = x,y pairs of canvas pixels (at most 65536 pairs); the canonical (EXACT) blend's answer. */
   pick(queries: Uint32Array, maxContrib?: number): PickResult;
+  setOption(key: number, value: number): void;
+  /** FLAG.SPLAT_STATE: applies op (STATE.SET / CLEAR / TOGGLE / ASSIGN) with bits to every splat whose centre lies in the region and whose byte passes the where filter; returns how many those are. */
+  stateRegion(region: StateRegion, op: number, bits: number): number;
+  stateIds(ids: Uint32Array, op: number, bits: number): void;
+  stateCount(mask: number, value: number): number;
+  /** The state plane as it is now, one byte per resident splat. */
+  readState(): Uint8Array;
+  writeState(bytes: Uint8Array): void;
   stats(): { numGaussians: number; numVisible: number; numIntersections: number; numProcessed: number; numTiles: number; sortPasses: number; frames: number; frameUs: number; stageUs: number[]; numEvaluated: number; depthOrdered: number; tightBinning: number; graphFrames: number; capacity: number; maxIntersectionsSeen: number; truncatedFrames: number };
 }
+export interface StateRegion {
+  kind: number; a?: number[]; b?: number[]; x0?: number; y0?: number; x1?: number; y1?: number;
+  uniforms?: Float32Array; mask?: Uint8Array; whereMask?: number; whereValue?: number;
+}
+export const STATE: { HIDDEN: 0x1; SELECTED: 0x2; SET: 1; CLEAR: 2; TOGGLE: 3; ASSIGN: 4 };
+export const REGION: { ALL: 0; SPHERE: 1; BOX: 2; SCREEN_RECT: 3; SCREEN_MASK: 4 };
+export const OPT: { SELECT_TINT: 11 };
 export interface PickRecord {
   status: number; listLength: number; hitCount: number; firstId: number; firstDepth: number; maxId: number; maxWeight: number;
   medianId: number; medianDepth: number; alpha: number; depthAcc: number; reserved: number; contrib?: { id: number; weight: number }[];
@@ -61,5 +76,5 @@ export function getProjectionMatrix(znear: number, zfar: number, fovX: number, f
 export function focal2fov(focal: number, pixels: number): number;
 export function writePPM(file: string, rgba: Uint8Array, width: number, height: number): void;
 export const BUF: { TILE_COUNTS: 0; TILE_OFFSETS: 1; GAUSSIAN_DATA: 2; KEYS_UNSORTED: 3; VALUES_UNSORTED: 4; KEYS: 5; VALUES: 6; RANGES: 7; RGBA8: 8; RGB_F32: 9;
-                    ALPHA_F32: 13; DEPTH_F32: 14 };
-export const FLAG: { EXACT_BLEND: 0x1; F32_TAP: 0x2; TIMING: 0x4; AUX_OUTPUTS: 0x8 };
+                    ALPHA_F32: 13; DEPTH_F32: 14; SPLAT_STATE: 15 };
+export const FLAG: { EXACT_BLEND: 0x1; F32_TAP: 0x2; TIMING: 0x4; AUX_OUTPUTS: 0x8; SPLAT_STATE: 0x10 };

@@ -155,7 +155,34 @@ class Renderer {
     return new PickResult(raw.results, raw.contrib, queries.length / 2, maxContrib >>> 0);
   }
   stats() { return loadNative().stats(this.handle); }
+  setOption(key, value) { loadNative().setOption(this.handle, key, value); }
+  // Splat state (FLAG.SPLAT_STATE at construction): one byte per resident splat -- STATE.HIDDEN splats are not rendered, STATE.SELECTED
+  // ones are drawn tinted (setOption(OPT.SELECT_TINT, a<<24 | r<<16 | g<<8 | b)), bits 2-7 are the host's.  Every call completes the
+  // frames in flight first; the next frame sees the new state.
+  // stateRegion({kind: REGION.*, a, b, x0, y0, x1, y1, uniforms, mask, whereMask, whereValue}, op, bits) -> splats matched: `op`
+  // (STATE.SET / CLEAR / TOGGLE / ASSIGN) is applied to every splat whose CENTRE lies in the region and whose byte passes
+  // (s & whereMask) == whereValue.  SPHERE: a centre, b[0] radius; BOX: a min, b max; SCREEN_RECT: canvas pixels [x0,x1) x [y0,y1)
+  // under the camera `uniforms`; SCREEN_MASK: mask = Uint8Array[height * width] of the canvas, nonzero = inside.
+  stateRegion(region, op, bits) {
+    const r = Object.assign({}, region);
+    if (r.mask) { r.maskWidth = this.canvas.width; r.maskHeight = this.canvas.height; }
+    return loadNative().stateRegion(this.handle, r, op >>> 0, bits >>> 0);
+  }
+  // the same for a Uint32Array of splat indices (what pick returns); duplicates behave as the sequential application would
+  stateIds(ids, op, bits) {
+    if (!(ids instanceof Uint32Array)) throw new TypeError('gsplat: stateIds expects a Uint32Array of splat indices');
+    loadNative().stateIds(this.handle, ids, op >>> 0, bits >>> 0);
+  }
+  stateCount(mask, value) { return loadNative().stateCount(this.handle, mask >>> 0, value >>> 0); }
+  readState() { return new Uint8Array(loadNative().readState(this.handle)); } // the plane as it is now: undo snapshot, export filter
+  writeState(bytes) {
+    if (!(bytes instanceof Uint8Array)) throw new TypeError('gsplat: writeState expects a Uint8Array of N state bytes');
+    loadNative().writeState(this.handle, bytes);
+  }
 }
+
+const STATE = { HIDDEN: 0x1, SELECTED: 0x2, SET: 1, CLEAR: 2, TOGGLE: 3, ASSIGN: 4 };
+const REGION = { ALL: 0, SPHERE: 1, BOX: 2, SCREEN_RECT: 3, SCREEN_MASK: 4 };
 
 const PICK = { OK: 0, OUTSIDE_SLAB: 1, NONE: 0xFFFFFFFF, MAX_QUERIES: 65536, MAX_CONTRIB: 256 };
 // word index of every field of a 48-byte gs_pick_result
@@ -189,4 +216,4 @@ class PickResult {
   }
 }
 
-module.exports = { Renderer, loadNative, PickResult, PICK, PICK_FIELD };
+module.exports = { Renderer, loadNative, PickResult, PICK, PICK_FIELD, STATE, REGION };

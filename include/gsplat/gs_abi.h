@@ -67,6 +67,8 @@ extern "C" {
 #define GS_FLAG_TIMING 0x4u      /* bracket every stage with hipEvents; gs_get_stats returns stage microseconds */
 #define GS_FLAG_AUX_OUTPUTS 0x8u /* also keep the per-pixel alpha and accumulated-depth planes (GS_BUF_ALPHA_F32, GS_BUF_DEPTH_F32),
                                     computed from the colour's own entries and weights; the rgba8 image is unchanged (alpha byte 255) */
+#define GS_FLAG_SPLAT_STATE 0x10u /* keep one state byte per resident splat (GS_BUF_SPLAT_STATE, gs_state_*): hidden splats are not
+                                    rendered, selected ones are drawn tinted.  Without the flag no frame changes by a bit          */
 
 typedef struct gs_config {
     uint32_t struct_size;       /* = sizeof(gs_config); lets the struct grow                                     */
@@ -139,9 +141,11 @@ enum {
     /* 11 and 12 are the library's profiling and test taps */
     GS_BUF_ALPHA_F32 = 13,    /* f32[H][Wslab] (GS_FLAG_AUX_OUTPUTS) accumulated opacity A = 1 - T_final; 0 where no entry reaches.
                                  The colour is premultiplied: over a background B, C + (1 - A) B                              */
-    GS_BUF_DEPTH_F32 = 14     /* f32[H][Wslab] (GS_FLAG_AUX_OUTPUTS) accumulated depth D = sum of z alpha T over the kept entries,
+    GS_BUF_DEPTH_F32 = 14,    /* f32[H][Wslab] (GS_FLAG_AUX_OUTPUTS) accumulated depth D = sum of z alpha T over the kept entries,
                                  z = GaussianData.depth, in list order with the colour's association; expected depth = D / A
                                  where A > 0 (the division is left to the host)                                                */
+    GS_BUF_SPLAT_STATE = 15   /* u8[N] (GS_FLAG_SPLAT_STATE) the state plane as it is NOW (not of the last frame); readable as soon as
+                                 splats are resident, before any frame                                                          */
 };
 
 typedef struct gs_ctx gs_ctx;
@@ -261,6 +265,60 @@ typedef struct gs_pick_contrib { uint32_t id; float weight; } gs_pick_contrib;
 int32_t gs_pick(gs_ctx* ctx, const gs_pick_query* queries, uint32_t n, gs_pick_result* results, uint32_t max_contrib,
                 gs_pick_contrib* contrib);
 
+/* ---- splat state: hide, select and tint resident splats without re-upload ------------------------
+ * A ctx created with GS_FLAG_SPLAT_STATE keeps a u8[N] plane inside its scene allocation, one byte per resident splat, zeroed by
+ * every gs_upload_*.  GS_SPLAT_HIDDEN: the projection treats the splat exactly like one that fails in_frustum
+ * (process_gaussians.wgsl:108-125): tile count 0, no GaussianData record, no instance.  GS_SPLAT_SELECTED: the splat's colour,
+ * after compute_color_from_sh (:240-280), becomes col + k (tint - col) per channel (GS_OPT_SELECT_TINT; one f32 rounding per
+ * operation).  Hidden wins over selected.  Bits 2-7 belong to the host (lock flags, layers): carried and filtered on, never
+ * interpreted.  gs_share_splats carries the plane to a borrower (a flagged ctx cannot borrow from an unflagged owner); the shadows
+ * of the frames-in-flight ring inherit it.  The reference has no counterpart (a viewer, not an editor): this is what an editor
+ * does with the answer of gs_pick -- select / delete / inspect -- where a host would otherwise edit its own 320-byte records and
+ * upload them again.
+ * Membership of a region is a test of the splat's CENTRE (x, y, z of its record), fixed to the operation so that a host can
+ * restate it bit for bit (one f32 rounding per operation, no contraction):
+ *     ph = proj * (x, y, z, 1), pv = view * (x, y, z, 1), each row ((m[r] x + m[4+r] y) + m[8+r] z) + m[12+r]
+ *     pw = 1 / (ph.w + 1e-7);  px = ((ph.x pw) 0.5 + 0.5) W;  py = ((ph.y pw) 0.5 + 0.5) H      (W, H: the CANVAS, also on a slab ctx)
+ *     SCREEN_RECT  !(pv.z <= 0.2) && px >= x0 && px < x1 && py >= y0 && py < y1                 (x0.. converted to f32)
+ *     SCREEN_MASK  !(pv.z <= 0.2) && px >= 0 && px < W && py >= 0 && py < H && mask[(int)py][(int)px] != 0
+ *     SPHERE       (dx dx + dy dy) + dz dz <= r r,  d = position - a, r = b[0]
+ *     BOX          a <= position <= b on every axis, both ends inclusive
+ *     ALL          every splat
+ * A NaN fails every test.  These select THROUGH surfaces; surface-only selection is Renderer.pick_rect / gs_pick followed by
+ * gs_state_ids.
+ * Ordering: every gs_state_* call first completes all frames enqueued on the ctx's ring, as gs_wait does (an error of that wait is
+ * returned and nothing is applied), then runs on the ctx's stream and returns when done.  A state call is not a frame: taps,
+ * statistics and gs_pick still describe what was rendered, a captured frame graph stays valid (it reads the plane when it is
+ * replayed), and the NEXT frame sees the new state.  Contexts that the host drives itself through gs_share_splats are the
+ * host's to drain before a state call, as they are before an upload.  On a ctx without GS_FLAG_SPLAT_STATE every call below, the
+ * tap and GS_OPT_SELECT_TINT return GS_ERR_INVALID_ARGUMENT.  Multi-GPU: every rank holds its own copy of the scene; the host
+ * applies the same call on every rank (the result is deterministic). */
+#define GS_SPLAT_HIDDEN 0x1u
+#define GS_SPLAT_SELECTED 0x2u
+#define GS_STATE_SET 1u      /* s |= bits */
+#define GS_STATE_CLEAR 2u    /* s &= ~bits */
+#define GS_STATE_TOGGLE 3u   /* s ^= bits */
+#define GS_STATE_ASSIGN 4u   /* s = bits */
+enum { GS_REGION_ALL = 0, GS_REGION_SPHERE = 1, GS_REGION_BOX = 2, GS_REGION_SCREEN_RECT = 3, GS_REGION_SCREEN_MASK = 4 };
+typedef struct gs_region {
+    uint32_t struct_size, kind; /* = sizeof(gs_region), GS_REGION_*                                                    */
+    float a[3], b[3];          /* SPHERE: a centre, b[0] radius.  BOX: a min, b max, both inclusive                     */
+    uint32_t x0, y0, x1, y1;   /* SCREEN_RECT: canvas pixels [x0,x1) x [y0,y1)                                          */
+    const void* uniforms160;   /* SCREEN_*: the camera (host pointer, copied)                                           */
+    const uint8_t* mask;       /* SCREEN_MASK: host u8[height][width] of the CANVAS, nonzero = inside (copied)          */
+    uint32_t where_mask, where_value; /* only splats with (s & where_mask) == where_value are touched                  */
+} gs_region;
+/* Applies `op` with `bits` (<= 0xFF) to the state byte of every splat in the region that passes the `where` filter.  *matched
+ * (may be NULL) receives their number, whether or not their byte changed.  One streaming pass: 13 bytes read per splat. */
+int32_t gs_state_region(gs_ctx* ctx, const gs_region* region, uint32_t op, uint32_t bits, uint64_t* matched);
+/* The same for n splat indices (HOST pointer).  An id >= N: GS_ERR_INVALID_ARGUMENT, the message names the index, nothing is
+ * changed.  Duplicates behave as the sequential application would (TOGGLE twice is a no-op). */
+int32_t gs_state_ids(gs_ctx* ctx, const uint32_t* ids, uint64_t n, uint32_t op, uint32_t bits);
+/* Number of splats with (s & mask) == value. */
+int32_t gs_state_count(gs_ctx* ctx, uint32_t mask, uint32_t value, uint64_t* count);
+/* Replaces the whole plane (n must be N) from host memory: undo / restore of what GS_BUF_SPLAT_STATE returned. */
+int32_t gs_state_write(gs_ctx* ctx, const uint8_t* src, uint64_t n);
+
 /* Tuning / profiling knobs. */
 #define GS_OPT_BLEND_ABLATION 1  /* bit 3 (8): the workgroup-per-tile blend kernel at tiles 16 and 32 (identical results; default = one
                                     wave per 8x8 pixel block); bit 2 (4): every blend kernel without its two parking culls (live box,
@@ -304,6 +362,9 @@ int32_t gs_pick(gs_ctx* ctx, const gs_pick_query* queries, uint32_t n, gs_pick_r
                                     the capture is redone when a buffer moves (capacity growth), an option or the emission order
                                     changes.  Renderer.animate re-encodes every pass every frame (renderer.ts:394-587).  Default 0. */
 #define GS_OPT_PROJ_CHUNKS 10     /* tuning: 512-gaussian cull chunks per workgroup of the tight projection (2, 4 or 8; 0 = automatic)  */
+#define GS_OPT_SELECT_TINT 11      /* (GS_FLAG_SPLAT_STATE) a<<24 | r<<16 | g<<8 | b: colour GS_SPLAT_SELECTED splats are drawn towards and how
+                                    far (k = a / 255, tint = channel / 255); default 0x80FFFF00; a = 0: selection not drawn (the
+                                    colour is left untouched, not multiplied by 0)                                              */
 int32_t gs_set_option(gs_ctx* ctx, int32_t key, int64_t value);
 /* Width in pixels of this ctx's slab (= width when the ctx owns the whole screen). */
 int32_t gs_slab_width(gs_ctx* ctx, uint32_t* px_begin, uint32_t* px_width);
