@@ -193,8 +193,8 @@ static int32_t alloc_per_gaussian(gs_ctx* c, uint64_t n, uint64_t min_capacity =
 }
 
 // Drops the previous scene, allocates the per-gaussian work arrays and the resident scene arrays for n gaussians.
-int32_t scene_alloc(gs_ctx* c, uint64_t n) {
-    int32_t rc = alloc_per_gaussian(c, n);
+int32_t scene_alloc(gs_ctx* c, uint64_t n, uint64_t min_capacity, uint64_t min_rows) {
+    int32_t rc = alloc_per_gaussian(c, n, min_capacity, min_rows);
     if (rc != GS_OK) return rc;
     const size_t np = ((size_t)n + 63) & ~(size_t)63; // plane stride keeps every plane and both record arrays 256-byte aligned
     // (GS_FLAG_SPLAT_STATE: the state plane follows the SH records, on the next 256-byte boundary; np bytes, so that whole words

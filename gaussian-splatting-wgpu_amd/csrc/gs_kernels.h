@@ -75,6 +75,16 @@ void gs_launch_state_region(uint32_t kind, uint8_t* state, const GsScene& s, uin
                             uint32_t where_mask, uint32_t where_value, unsigned long long* matched, hipStream_t st);
 void gs_launch_state_ids(uint8_t* state, const uint32_t* ids, uint64_t n, uint32_t op, uint32_t bits, hipStream_t st);
 void gs_launch_state_count(const uint8_t* state, uint32_t n, uint32_t mask, uint32_t value, unsigned long long* count, hipStream_t st);
+// k_export.hip: the splat edits (gs_export.hip).  Selection = splats with (s & mask) == value in ascending order: `counts` holds
+// gs_select_blocks(n) + 1 words (one per 1024 splats; after the launch their exclusive prefix, the total last), `ids` the total.
+uint32_t gs_select_blocks(uint32_t n);
+void gs_launch_select_count(const uint8_t* state, uint32_t n, uint32_t mask, uint32_t value, uint32_t* counts, hipStream_t st); // count + scan
+void gs_launch_select_scatter(const uint8_t* state, uint32_t n, uint32_t mask, uint32_t value, const uint32_t* offsets, uint32_t* ids, uint32_t cap,
+                              hipStream_t st);
+// records [first, first + m) of the selection (ids null: of the scene) as 320-byte records; out_ids (may be null): their indices
+void gs_launch_unpack(const GsScene& s, uint32_t n, const uint32_t* ids, uint32_t first, uint32_t m, void* d_aos, uint32_t* out_ids, hipStream_t st);
+// new splat g of `d` = splat ids[g] of `o` (every plane, the state byte included when both keep one)
+void gs_launch_compact_planes(const GsScene& o, uint32_t n_old, const uint32_t* ids, uint32_t m, const GsScene& d, hipStream_t st);
 // k_pick.hip: gs_pick, one wave per query over the last frame's lists (queries: {x, y} pairs; results: 12 words per query;
 // contrib: max_contrib {id, weight} pairs per query, or null)
 void gs_launch_pick(const void* gdata, const uint32_t* values, const uint32_t* ranges, const GsFrame& f, uint32_t id_mask, const void* d_queries,

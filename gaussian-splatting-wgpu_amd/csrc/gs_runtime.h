@@ -1,4 +1,4 @@
-// gs_runtime.h -- private to the runtime sources (gs_context / gs_frame / gs_readback / gs_state / gs_ply / gs_stages .hip): the error
+// gs_runtime.h -- private to the runtime sources (gs_context / gs_frame / gs_readback / gs_state / gs_export / gs_ply / gs_stages .hip): the error
 // channel, the owners of HIP resources, and the context.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -157,6 +157,8 @@ struct gs_ctx {
     struct { DevBuf<> q, r, c; uint64_t c_bytes = 0; } pick;
     // gs_state_* (gs_state.hip): the matched / count word, device copies of an id list and of a screen mask; grown on demand
     struct { DevBuf<unsigned long long> counter; DevBuf<uint32_t> ids; DevBuf<uint8_t> mask; uint64_t ids_cap = 0, mask_cap = 0; } st;
+    // splat edits (gs_export.hip): the selection's per-workgroup counts and its id list; grown on demand
+    struct { DevBuf<uint32_t> counts, ids; uint64_t counts_cap = 0, ids_cap = 0; } ex;
     Event ev[GS_EV_RING][GS_STAGE_COUNT + 1]; // ring of per-frame stage brackets (GS_FLAG_TIMING)
     bool have_events = false;
     uint64_t timed_from = 0; // first frame index included in the stage means
@@ -182,7 +184,7 @@ struct gs_ctx {
 
 // gs_context.hip
 int32_t alloc_kv(gs_ctx* c, uint64_t capacity, uint64_t row_cap); // the caller has drained the stream
-int32_t scene_alloc(gs_ctx* c, uint64_t n);
+int32_t scene_alloc(gs_ctx* c, uint64_t n, uint64_t min_capacity = 0, uint64_t min_rows = 0); // min_*: capacities a compaction keeps
 void drop_shadows(gs_ctx* c);
 // gs_frame.hip
 void drop_graph(gs_ctx* c);

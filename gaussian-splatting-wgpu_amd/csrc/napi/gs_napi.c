@@ -504,6 +504,143 @@ static napi_value js_write_state(napi_env env, napi_callback_info info) {
     return rc == GS_OK ? NULL : throw_gs(env, rc);
 }
 
+static void set_num(napi_env env, napi_value obj, const char* k, double v);
+
+/* ---- splat edits (gs_abi.h "splat edits") ---- */
+static int get_filter(napi_env env, napi_value m, napi_value v, uint32_t* mask, uint32_t* value) {
+    return napi_get_value_uint32(env, m, mask) == napi_ok && napi_get_value_uint32(env, v, value) == napi_ok;
+}
+
+/* listState(handle, mask, value) -> ArrayBuffer of u32 indices, ascending */
+static napi_value js_list_state(napi_env env, napi_callback_info info) {
+    size_t argc = 3;
+    napi_value argv[3];
+    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    gs_ctx* ctx = argc >= 3 ? unwrap(env, argv[0]) : NULL;
+    if (!ctx) return NULL;
+    uint32_t mask = 0, value = 0;
+    if (!get_filter(env, argv[1], argv[2], &mask, &value)) {
+        napi_throw_type_error(env, NULL, "gsplat.listState: mask and value must be numbers");
+        return NULL;
+    }
+    uint64_t n = 0;
+    int32_t rc = gs_state_list(ctx, mask, value, NULL, 0, &n);
+    if (rc != GS_OK) return throw_gs(env, rc);
+    void* dst = NULL;
+    napi_value ab;
+    NAPI_CALL(env, napi_create_arraybuffer(env, (size_t)n * 4, &dst, &ab));
+    if (n) rc = gs_state_list(ctx, mask, value, (uint32_t*)dst, n, &n);
+    return rc == GS_OK ? ab : throw_gs(env, rc);
+}
+
+/* exportSplats(handle, mask, value) -> {n, records: ArrayBuffer (n x 320 B), ids: ArrayBuffer (n x u32)} */
+static napi_value js_export_splats(napi_env env, napi_callback_info info) {
+    size_t argc = 3;
+    napi_value argv[3];
+    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    gs_ctx* ctx = argc >= 3 ? unwrap(env, argv[0]) : NULL;
+    if (!ctx) return NULL;
+    uint32_t mask = 0, value = 0;
+    if (!get_filter(env, argv[1], argv[2], &mask, &value)) {
+        napi_throw_type_error(env, NULL, "gsplat.exportSplats: mask and value must be numbers");
+        return NULL;
+    }
+    uint64_t n = 0;
+    int32_t rc = gs_export_splats(ctx, mask, value, NULL, 0, &n, NULL);
+    if (rc != GS_OK) return throw_gs(env, rc);
+    void *rec = NULL, *ids = NULL;
+    napi_value rab, iab, o;
+    NAPI_CALL(env, napi_create_arraybuffer(env, (size_t)n * GS_SPLAT_RECORD_BYTES, &rec, &rab));
+    NAPI_CALL(env, napi_create_arraybuffer(env, (size_t)n * 4, &ids, &iab));
+    if (n) rc = gs_export_splats(ctx, mask, value, rec, n, &n, (uint32_t*)ids);
+    if (rc != GS_OK) return throw_gs(env, rc);
+    NAPI_CALL(env, napi_create_object(env, &o));
+    set_num(env, o, "n", (double)n);
+    napi_set_named_property(env, o, "records", rab);
+    napi_set_named_property(env, o, "ids", iab);
+    return o;
+}
+
+/* compact(handle, mask, value) -> ArrayBuffer of u32: ids[new index] = old index */
+static napi_value js_compact(napi_env env, napi_callback_info info) {
+    size_t argc = 3;
+    napi_value argv[3];
+    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    gs_ctx* ctx = argc >= 3 ? unwrap(env, argv[0]) : NULL;
+    if (!ctx) return NULL;
+    uint32_t mask = 0, value = 0;
+    if (!get_filter(env, argv[1], argv[2], &mask, &value)) {
+        napi_throw_type_error(env, NULL, "gsplat.compact: mask and value must be numbers");
+        return NULL;
+    }
+    uint64_t kept = 0;
+    gs_stats st;
+    int32_t rc = gs_get_stats(ctx, &st);
+    if (rc != GS_OK) return throw_gs(env, rc);
+    uint32_t* ids = (uint32_t*)malloc(((size_t)st.num_gaussians + 1) * 4); /* gs_compact's capacity: N before the call */
+    if (!ids) {
+        napi_throw_error(env, NULL, "gsplat.compact: allocation failed");
+        return NULL;
+    }
+    rc = gs_compact(ctx, mask, value, &kept, ids);
+    if (rc != GS_OK) {
+        free(ids);
+        return throw_gs(env, rc);
+    }
+    void* dst = NULL;
+    napi_value ab;
+    if (napi_create_arraybuffer(env, (size_t)kept * 4, &dst, &ab) != napi_ok) {
+        free(ids);
+        napi_throw_error(env, NULL, "gsplat.compact: allocation failed");
+        return NULL;
+    }
+    memcpy(dst, ids, (size_t)kept * 4);
+    free(ids);
+    return ab;
+}
+
+/* exportPly(handle, path, mask, value, shDegree) -> n written (gs_export_ply: streamed, no whole-scene host buffer) */
+static napi_value js_export_ply(napi_env env, napi_callback_info info) {
+    size_t argc = 5;
+    napi_value argv[5];
+    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    gs_ctx* ctx = argc >= 5 ? unwrap(env, argv[0]) : NULL;
+    if (!ctx) return NULL;
+    char path[4096];
+    size_t len = 0;
+    uint32_t mask = 0, value = 0;
+    int32_t degree = 3;
+    if (napi_get_value_string_utf8(env, argv[1], path, sizeof(path), &len) != napi_ok || !get_filter(env, argv[2], argv[3], &mask, &value) ||
+        napi_get_value_int32(env, argv[4], &degree) != napi_ok) {
+        napi_throw_type_error(env, NULL, "gsplat.exportPly: expects (handle, path, mask, value, shDegree)");
+        return NULL;
+    }
+    uint64_t n = 0;
+    int32_t rc = gs_export_ply(ctx, path, mask, value, degree, &n);
+    if (rc != GS_OK) return throw_gs(env, rc);
+    napi_value v;
+    NAPI_CALL(env, napi_create_double(env, (double)n, &v));
+    return v;
+}
+
+/* savePly(path, records (ArrayBuffer / typed array of n x 320 B), shDegree): gs_ply_save, no context */
+static napi_value js_save_ply(napi_env env, napi_callback_info info) {
+    size_t argc = 3;
+    napi_value argv[3];
+    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    char path[4096];
+    size_t len = 0, bytes = 0;
+    void* data = NULL;
+    int32_t degree = 3;
+    if (argc < 3 || napi_get_value_string_utf8(env, argv[0], path, sizeof(path), &len) != napi_ok || !get_bytes(env, argv[1], &data, &bytes) ||
+        bytes % GS_SPLAT_RECORD_BYTES != 0 || napi_get_value_int32(env, argv[2], &degree) != napi_ok) {
+        napi_throw_type_error(env, NULL, "gsplat.savePly: expects (path, records of n x 320 bytes, shDegree)");
+        return NULL;
+    }
+    int32_t rc = gs_ply_save(path, data, (uint64_t)(bytes / GS_SPLAT_RECORD_BYTES), degree);
+    return rc == GS_OK ? NULL : throw_gs(env, rc);
+}
+
 /* setOption(handle, key, value) */
 static napi_value js_set_option(napi_env env, napi_callback_info info) {
     size_t argc = 3;
@@ -753,6 +890,8 @@ static napi_value init(napi_env env, napi_value exports) {
         {"hostAlloc", js_host_alloc}, {"renderToSink", js_render_to_sink}, {"pick", js_pick},
         {"stateRegion", js_state_region}, {"stateIds", js_state_ids},  {"stateCount", js_state_count},
         {"readState", js_read_state}, {"writeState", js_write_state},  {"setOption", js_set_option},
+        {"listState", js_list_state}, {"exportSplats", js_export_splats}, {"compact", js_compact},
+        {"exportPly", js_export_ply}, {"savePly", js_save_ply},
     };
     for (size_t i = 0; i < sizeof(fns) / sizeof(fns[0]); ++i) {
         napi_value f;

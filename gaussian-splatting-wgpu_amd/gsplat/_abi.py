@@ -38,6 +38,7 @@ GS_OPT_PROJ_CHUNKS = 10
 GS_OPT_SELECT_TINT = 11
 
 GS_ERR_INVALID_ARGUMENT = -1
+GS_ERR_NO_SCENE = -5
 GS_ERR_NO_FRAME = -6
 
 # gs_pick
@@ -59,7 +60,8 @@ ABI_SYMBOLS = ("gs_last_error", "gs_abi_version", "gs_create", "gs_destroy", "gs
                "gs_share_splats",
                "gs_ply_load", "gs_ply_free", "gs_upload_ply",
                "gs_render", "gs_render_debug", "gs_render_to", "gs_wait", "gs_render_host", "gs_wait_ticket", "gs_host_alloc", "gs_host_free", "gs_read_rgba8", "gs_read_buffer", "gs_device_ptr",
-               "gs_get_stats", "gs_pick", "gs_state_region", "gs_state_ids", "gs_state_count", "gs_state_write", "gs_set_option", "gs_slab_width", "gs_assemble_slabs", "gs_sort_pairs_u32",
+               "gs_get_stats", "gs_pick", "gs_state_region", "gs_state_ids", "gs_state_count", "gs_state_write",
+               "gs_state_list", "gs_export_splats", "gs_export_splats_device", "gs_compact", "gs_ply_save", "gs_export_ply", "gs_set_option", "gs_slab_width", "gs_assemble_slabs", "gs_sort_pairs_u32",
                "gs_exclusive_scan_u32")
 
 
@@ -153,6 +155,12 @@ def load():
     L.gs_state_ids.argtypes = [vp, vp, u64, u32, u32]
     L.gs_state_count.argtypes = [vp, u32, u32, ctypes.POINTER(u64)]
     L.gs_state_write.argtypes = [vp, vp, u64]
+    L.gs_state_list.argtypes = [vp, u32, u32, vp, u64, ctypes.POINTER(u64)]
+    L.gs_export_splats.argtypes = [vp, u32, u32, vp, u64, ctypes.POINTER(u64), vp]
+    L.gs_export_splats_device.argtypes = [vp, u32, u32, vp, u64, ctypes.POINTER(u64), vp]
+    L.gs_compact.argtypes = [vp, u32, u32, ctypes.POINTER(u64), vp]
+    L.gs_ply_save.argtypes = [ctypes.c_char_p, vp, u64, i32]
+    L.gs_export_ply.argtypes = [vp, ctypes.c_char_p, u32, u32, i32, ctypes.POINTER(u64)]
     L.gs_set_option.argtypes = [vp, i32, ctypes.c_int64]
     L.gs_slab_width.argtypes = [vp, ctypes.POINTER(u32), ctypes.POINTER(u32)]
     L.gs_assemble_slabs.argtypes = [vp, vp, ctypes.POINTER(u32), u32, u64, vp]
@@ -198,3 +206,10 @@ def load_ply(path):
         return arr.reshape(n.value, 80).copy(), deg.value
     finally:
         L.gs_ply_free(rec)
+
+
+def save_ply(path, records, sh_degree=3):
+    """gs_ply_save, the inverse of load_ply: float32 [n,80] records -> a binary little-endian 3DGS .ply (coefficients above
+    sh_degree are not written)."""
+    rec = np.ascontiguousarray(records, dtype=np.float32).reshape(-1, 80)
+    check(load().gs_ply_save(str(path).encode(), rec.ctypes.data if rec.shape[0] else None, rec.shape[0], int(sh_degree)))

@@ -273,6 +273,66 @@ class Renderer:
     def unhide_all(self):
         return self.state_region(_abi.GS_REGION_ALL, _abi.GS_STATE_CLEAR, _abi.GS_SPLAT_HIDDEN)
 
+    # -- splat edits: list, export, compact and save resident splats by state ------------------------------
+    def list_state(self, mask, value):
+        """gs_state_list: the indices of the splats with (s & mask) == value, ascending, uint32[n]."""
+        n = ctypes.c_uint64()
+        check(self._L.gs_state_list(self._ctx, int(mask), int(value), None, 0, ctypes.byref(n)))
+        ids = np.empty(n.value, dtype=np.uint32)
+        if n.value:
+            check(self._L.gs_state_list(self._ctx, int(mask), int(value), ids.ctypes.data, ids.size, ctypes.byref(n)))
+        return ids
+
+    def export_splats(self, mask=0, value=0, with_ids=False, device=False):
+        """gs_export_splats: the resident splats with (s & mask) == value as float32[n, 80] records (what PackedGaussians and the
+        uploads take; the 21 padding floats come back 0), in ascending index order.  (0, 0): every splat, also without
+        GS_FLAG_SPLAT_STATE.  with_ids: returns (records, uint32[n] old indices).  device=True: torch tensors on this device
+        (gs_export_splats_device), never a host copy."""
+        mask, value = int(mask), int(value)
+        n = ctypes.c_uint64()
+        check(self._L.gs_export_splats(self._ctx, mask, value, None, 0, ctypes.byref(n), None))
+        m = n.value
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            rec = torch.empty((m, 80), dtype=torch.float32, device=dev)
+            ids = torch.empty((m,), dtype=torch.int32, device=dev) if with_ids else None
+            torch.cuda.current_stream(dev).synchronize()  # the allocator may hand out memory another stream still uses
+            if m:
+                check(self._L.gs_export_splats_device(self._ctx, mask, value, rec.data_ptr(), m, ctypes.byref(n),
+                                                      ids.data_ptr() if with_ids else None))
+            return (rec, ids) if with_ids else rec
+        rec = np.empty((m, 80), dtype=np.float32)
+        ids = np.empty(m, dtype=np.uint32) if with_ids else None
+        if m:
+            check(self._L.gs_export_splats(self._ctx, mask, value, rec.ctypes.data, m, ctypes.byref(n),
+                                           ids.ctypes.data if with_ids else None))
+        return (rec, ids) if with_ids else rec
+
+    def compact(self, mask, value):
+        """gs_compact: keeps the splats with (s & mask) == value, drops the rest for good and renumbers.  Returns the id map
+        uint32[kept]: ids[new index] = old index (how a host renumbers its own per-splat metadata).  State bytes are carried;
+        the next frame renders what the scene with the dropped splats hidden rendered.  Like an upload, taps and pick need a
+        new frame afterwards."""
+        st = GsStats()
+        check(self._L.gs_get_stats(self._ctx, ctypes.byref(st)))  # N before the call: the capacity gs_compact expects of ids
+        ids = np.empty(max(int(st.num_gaussians), 1), dtype=np.uint32)
+        kept = ctypes.c_uint64()
+        check(self._L.gs_compact(self._ctx, int(mask), int(value), ctypes.byref(kept), ids.ctypes.data))
+        self.numGaussians = int(kept.value)
+        return ids[:self.numGaussians].copy()
+
+    def delete_hidden(self):
+        """Removes every hidden splat for good (compact(GS_SPLAT_HIDDEN, 0)); returns the id map."""
+        return self.compact(_abi.GS_SPLAT_HIDDEN, 0)
+
+    def save_ply(self, path, mask=0, value=0, sh_degree=3):
+        """gs_export_ply: streams the splats with (s & mask) == value into a binary 3DGS .ply (no whole-scene host buffer);
+        returns how many were written."""
+        n = ctypes.c_uint64()
+        check(self._L.gs_export_ply(self._ctx, str(path).encode(), int(mask), int(value), int(sh_degree), ctypes.byref(n)))
+        return int(n.value)
+
     def device_ptr(self, which):
         p = ctypes.c_void_p()
         check(self._L.gs_device_ptr(self._ctx, which, ctypes.byref(p)))
@@ -410,6 +470,27 @@ class PipelinedRenderer:
 
     def unhide_all(self):
         return self._state_owner().unhide_all()
+
+    # splat edits go to the owner too; after a compaction the other members borrow the new scene, as the constructor made them
+    def list_state(self, mask, value):
+        return self._state_owner().list_state(mask, value)
+
+    def export_splats(self, *a, **kw):
+        return self._state_owner().export_splats(*a, **kw)
+
+    def save_ply(self, *a, **kw):
+        return self._state_owner().save_ply(*a, **kw)
+
+    def compact(self, mask, value):
+        first = self._state_owner()
+        ids = first.compact(mask, value)
+        for r in self.renderers[1:]:
+            check(r._L.gs_share_splats(r._ctx, first._ctx))
+            r.numGaussians = first.numGaussians
+        return ids
+
+    def delete_hidden(self):
+        return self.compact(_abi.GS_SPLAT_HIDDEN, 0)
 
     def destroy(self):
         for r in reversed(self.renderers):  # borrowers first

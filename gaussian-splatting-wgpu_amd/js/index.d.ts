@@ -45,6 +45,16 @@ export class Renderer {
   /** The state plane as it is now, one byte per resident splat. */
   readState(): Uint8Array;
   writeState(bytes: Uint8Array): void;
+  /** Indices of the splats with (s & mask) == value, ascending. */
+  listState(mask: number, value: number): Uint32Array;
+  /** The matching splats as 320-byte records (accepted by PackedGaussians.fromRecords, as an uploaded buffer is) and their indices; default every splat. */
+  exportSplats(filter?: { mask?: number; value?: number }): { buffer: ArrayBuffer; ids: Uint32Array };
+  /** Keeps the matching splats, drops the rest for good, renumbers; returns ids[new index] = old index and updates numGaussians. */
+  compact(mask: number, value: number): Uint32Array;
+  /** compact(STATE.HIDDEN, 0). */
+  deleteHidden(): Uint32Array;
+  /** Streams the matching splats into a binary 3DGS .ply; returns how many were written. */
+  savePly(file: string, options?: { mask?: number; value?: number; shDegree?: number }): number;
   stats(): { numGaussians: number; numVisible: number; numIntersections: number; numProcessed: number; numTiles: number; sortPasses: number; frames: number; frameUs: number; stageUs: number[]; numEvaluated: number; depthOrdered: number; tightBinning: number; graphFrames: number; capacity: number; maxIntersectionsSeen: number; truncatedFrames: number };
 }
 export interface StateRegion {
@@ -74,6 +84,8 @@ export function cameraFromJSON(raw: CameraRaw, canvasW: number, canvasH: number)
 export function loadCameraFile(path: string, canvas?: CanvasLike): { name: string; camera: Camera }[];
 export function getProjectionMatrix(znear: number, zfar: number, fovX: number, fovY: number): Mat4;
 export function focal2fov(focal: number, pixels: number): number;
+/** The inverse of PackedGaussians.fromFile: writes the records as a binary 3DGS .ply of that SH degree. */
+export function savePly(file: string, gaussians: PackedGaussians, shDegree?: number): void;
 export function writePPM(file: string, rgba: Uint8Array, width: number, height: number): void;
 export const BUF: { TILE_COUNTS: 0; TILE_OFFSETS: 1; GAUSSIAN_DATA: 2; KEYS_UNSORTED: 3; VALUES_UNSORTED: 4; KEYS: 5; VALUES: 6; RANGES: 7; RGBA8: 8; RGB_F32: 9;
                     ALPHA_F32: 13; DEPTH_F32: 14; SPLAT_STATE: 15 };

@@ -179,6 +179,33 @@ class Renderer {
     if (!(bytes instanceof Uint8Array)) throw new TypeError('gsplat: writeState expects a Uint8Array of N state bytes');
     loadNative().writeState(this.handle, bytes);
   }
+  // Splat edits: bring splats back out of the library and make an edit permanent.  A splat matches when (s & mask) == value;
+  // matching splats always come in ascending index order; (0, 0) is every splat and needs no FLAG.SPLAT_STATE.
+  listState(mask, value) { return new Uint32Array(loadNative().listState(this.handle, mask >>> 0, value >>> 0)); }
+  // -> {buffer: ArrayBuffer of 320-byte records (what PackedGaussians.fromRecords and an upload take), ids: their indices}
+  exportSplats({ mask = 0, value = 0 } = {}) {
+    const e = loadNative().exportSplats(this.handle, mask >>> 0, value >>> 0);
+    return { buffer: e.records, ids: new Uint32Array(e.ids) };
+  }
+  // keeps the matching splats, drops the rest for good and renumbers; returns ids[new index] = old index (how a host renumbers
+  // its own per-splat metadata).  State bytes are carried.  Like an upload: readPixels / readBuffer / pick need a new frame.
+  compact(mask, value) {
+    const ids = new Uint32Array(loadNative().compact(this.handle, mask >>> 0, value >>> 0));
+    this.numGaussians = ids.length;
+    return ids;
+  }
+  deleteHidden() { return this.compact(STATE.HIDDEN, 0); }
+  // streams the matching splats into a binary 3DGS .ply (no whole-scene host buffer); returns how many were written
+  savePly(file, { mask = 0, value = 0, shDegree = 3 } = {}) {
+    return loadNative().exportPly(this.handle, String(file), mask >>> 0, value >>> 0, shDegree | 0);
+  }
+}
+
+// savePly(file, packedGaussians, shDegree): the inverse of PackedGaussians.fromFile (gs_ply_save; no context, no GPU)
+function savePly(file, gaussians, shDegree = 3) {
+  const buf = gaussians.gaussiansBuffer;
+  const bytes = gaussians.numGaussians * 320;
+  loadNative().savePly(String(file), bytes === buf.byteLength ? buf : buf.slice(0, bytes), shDegree | 0);
 }
 
 const STATE = { HIDDEN: 0x1, SELECTED: 0x2, SET: 1, CLEAR: 2, TOGGLE: 3, ASSIGN: 4 };
@@ -216,4 +243,4 @@ class PickResult {
   }
 }
 
-module.exports = { Renderer, loadNative, PickResult, PICK, PICK_FIELD, STATE, REGION };
+module.exports = { Renderer, loadNative, savePly, PickResult, PICK, PICK_FIELD, STATE, REGION };

@@ -176,7 +176,8 @@ int32_t gs_upload_splats_device(gs_ctx* ctx, const void* d_aos320, uint64_t n);
 /* `ctx` renders `owner`'s resident splats (same device; read-only during a frame) with its own stream and per-frame
  * buffers: several contexts rendered round-robin keep several frames in flight, so one frame's blend (instruction-issue
  * bound) overlaps the next frame's binning and sort (memory/latency bound).  The reference has one frame in flight
- * (Renderer.animate awaits every stage, renderer.ts:394-587).  `owner` must outlive `ctx` and must not re-upload meanwhile. */
+ * (Renderer.animate awaits every stage, renderer.ts:394-587).  `owner` must outlive `ctx` and must not re-upload
+ * meanwhile; a gs_compact of the owner counts as a re-upload (share again afterwards). */
 int32_t gs_share_splats(gs_ctx* ctx, gs_ctx* owner);
 
 /* Replaces one Renderer.animate() frame (renderer.ts:349-593): enqueues the whole frame for the
@@ -318,6 +319,55 @@ int32_t gs_state_ids(gs_ctx* ctx, const uint32_t* ids, uint64_t n, uint32_t op, 
 int32_t gs_state_count(gs_ctx* ctx, uint32_t mask, uint32_t value, uint64_t* count);
 /* Replaces the whole plane (n must be N) from host memory: undo / restore of what GS_BUF_SPLAT_STATE returned. */
 int32_t gs_state_write(gs_ctx* ctx, const uint8_t* src, uint64_t n);
+
+/* ---- splat edits: list, export, compact and save resident splats by state ------------------------
+ * The state calls above stop at the byte; these bring splats back OUT of the library and make an edit permanent.  The reference
+ * has no counterpart: its host keeps the PackedGaussians buffer it uploaded (renderer.ts:130-137) and would filter and upload
+ * that again; gs_upload_ply streams a file into the device planes precisely so that no such host copy exists.
+ * Filter: every call takes (mask, value); a splat matches when (s & mask) == value, exactly gs_state_count's filter.  mask or
+ * value above 0xFF: GS_ERR_INVALID_ARGUMENT.  (0, 0) matches every splat and is accepted on a ctx WITHOUT GS_FLAG_SPLAT_STATE
+ * (export and save what is resident); any other filter on such a ctx is refused like the state calls.
+ * Ordering: matching splats are always delivered in ASCENDING index order -- the reference's tie-break order inside a depth
+ * bucket, so a compacted scene renders what the scene with the same splats hidden rendered.  Every call first completes all
+ * frames enqueued on the ctx's ring, as gs_state_* do (an error of that wait is the call's error and nothing is done), then runs
+ * on the ctx's stream and returns when done.  GS_ERR_NO_SCENE before any upload.
+ * Ownership: output buffers are caller-allocated; the selection scratch (one count per 1024 splats, the id list) belongs to the
+ * ctx, grows on demand and goes with it.  A record is the 320-byte layout gs_upload_splats takes; the device scene carries 59 of
+ * its 80 floats, so the 21 padding floats (float 3, 7, 13, 14, 15 and 19 + 4k, k = 0..15) come back as +0.0f and every other
+ * float as the uploaded bit pattern (NaN payloads, -0 and infinities included).
+ * Multi-GPU: every rank holds its own copy of the scene; the host applies the same call on every rank (the result is
+ * deterministic). */
+/* Indices of the matching splats, ascending.  ids == NULL: only *n is written (query).  cap < *n: GS_ERR_INVALID_ARGUMENT, the
+ * message names the count needed, nothing is written to ids. */
+int32_t gs_state_list(gs_ctx* ctx, uint32_t mask, uint32_t value, uint32_t* ids, uint64_t cap, uint64_t* n);
+/* The matching splats as 320-byte records in HOST memory.  ids (may be NULL, else cap_records entries): the old index of every
+ * record.  aos320 == NULL: query (only *n).  cap_records too small: as above.  One pass: 244 B read, 320 B written per splat. */
+int32_t gs_export_splats(gs_ctx* ctx, uint32_t mask, uint32_t value, void* aos320, uint64_t cap_records, uint64_t* n, uint32_t* ids);
+/* Same, DEVICE pointers (d_aos320 and d_ids); written on the ctx stream, complete on return. */
+int32_t gs_export_splats_device(gs_ctx* ctx, uint32_t mask, uint32_t value, void* d_aos320, uint64_t cap_records, uint64_t* n,
+                                uint32_t* d_ids);
+/* Keeps the matching splats, drops the rest, renumbers: the ctx then holds *kept splats and is in the state of a ctx that was
+ * given gs_upload_splats(the kept records, in order) followed by gs_state_write(their state bytes) -- the bytes are carried
+ * unchanged, so a selection survives a delete and host bits 2-7 survive.  ids (HOST, may be NULL, capacity = N before the call):
+ * ids[new index] = old index, how a host renumbers its own per-splat metadata.  Like an upload: the frames-in-flight shadows are
+ * dropped, a captured frame graph is invalidated, taps, gs_read_rgba8 and gs_pick return GS_ERR_NO_FRAME until the next frame;
+ * statistics windows are untouched; the per-gaussian work arrays are re-sized for the new N while the (key,value) and row
+ * capacities stay at least as large as they were.  kept == 0 leaves the ctx as gs_upload_splats(ctx, NULL, 0) leaves it; kept == N
+ * takes the same path.  Old and new scene are both resident during the call: 245 B x (N + kept).  A ctx that borrows its scene
+ * (gs_share_splats) is refused with GS_ERR_INVALID_ARGUMENT: compact the owner.  For the owner's borrowers a compaction counts as
+ * a re-upload: the owner must not compact while they render, and they must gs_share_splats again afterwards. */
+int32_t gs_compact(gs_ctx* ctx, uint32_t mask, uint32_t value, uint64_t* kept, uint32_t* ids);
+/* Inverse of gs_ply_load: n packed records -> binary little-endian 3DGS .ply as ply.ts:162-228 reads it.  Header `ply`, `format
+ * binary_little_endian 1.0`, `element vertex n`, then `property float` x y z nx ny nz f_dc_0..2 f_rest_0..3K-1 opacity
+ * scale_0..2 rot_0..3 with K = (sh_degree + 1)^2 - 1, `end_header`.  Normals are +0.0f; f_dc_c is record float 16 + c,
+ * f_rest_{cK+i} record float 16 + 4(i+1) + c (ply.ts:178-187 inverted); coefficients above the degree are not written.  No ctx,
+ * no GPU.  sh_degree outside 0..3, a null path or records, a file that cannot be created or fully written:
+ * GS_ERR_INVALID_ARGUMENT naming the path and the errno text; a partial file is removed. */
+int32_t gs_ply_save(const char* path, const void* records, uint64_t n, int32_t sh_degree);
+/* gs_export_splats + gs_ply_save without a whole-scene host buffer: chunks of at most 64 Ki records are unpacked into a device
+ * staging buffer, copied to one of two pinned host buffers and written while the next chunk is on its way -- gs_upload_ply's
+ * mirror image.  Host memory does not grow with N.  *n (may be NULL): records written. */
+int32_t gs_export_ply(gs_ctx* ctx, const char* path, uint32_t mask, uint32_t value, int32_t sh_degree, uint64_t* n);
 
 /* Tuning / profiling knobs. */
 #define GS_OPT_BLEND_ABLATION 1  /* bit 3 (8): the workgroup-per-tile blend kernel at tiles 16 and 32 (identical results; default = one

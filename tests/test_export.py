@@ -1,0 +1,639 @@
+"""Splat edits: list, export, compact and save resident splats by state (include/gsplat/gs_abi.h "splat edits").
+
+The reference every answer is held to is tests/export_restate.py: keep = (state & mask) == value, ascending ids, records with
+their 21 padding floats zeroed, the property order of a saved .ply.  Every float comparison is on the uint32 view; the only
+tolerance is gpu_checks.check_image for fused frames, used as it stands.  A compaction is held to the definition the header
+gives it: the context must be indistinguishable from a fresh one given gs_upload_splats(kept records) + gs_state_write(their
+bytes) -- every tap and the image, bit for bit.
+"""
+import ctypes
+import json
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import scene
+import export_restate as er
+import state_restate as sr
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+F = np.float32
+NODE = shutil.which("node")
+HID, SEL = er.HIDDEN, er.SELECTED
+SYMBOLS = ("gs_state_list", "gs_export_splats", "gs_export_splats_device", "gs_compact", "gs_ply_save", "gs_export_ply")
+FILTERS = [(0, 0), (HID, 0), (SEL, SEL), (0xFF, 0x83), (0, 1), (HID | SEL, SEL)]
+_CACHE = {}
+
+
+def _special(rec):
+    """A copy with a handful of floats overwritten by a NaN, a payload NaN, -0.0, +-inf and a denormal (carried floats), and the
+    padding floats of two records filled with junk that must NOT come back."""
+    out = np.array(rec, dtype=F, copy=True).reshape(-1, 80)
+    w = out.view(np.uint32)
+    n = out.shape[0]
+    vals = [0x7FC00000, 0x7FA12345, 0x80000000, 0x7F800000, 0xFF800000, 0x00000001, 0xFFC0BEEF]
+    slots = [0, 5, 9, 12, 16, 18, 17 + 4 * 15, 4, 2, 22]
+    for k, v in enumerate(vals * 2):
+        w[(k * 7) % n, slots[k % len(slots)]] = v
+    w[0, er.PADDING] = 0xA5A5A5A5
+    w[n - 1, er.PADDING] = 0x3F800000
+    return out
+
+
+def _records(n):
+    """n records of synth.bicycle_like (the ragged fixture's own scene for 3001) with the special floats."""
+    if ("rec", n) not in _CACHE:
+        from gsplat import synth
+        base = synth.bicycle_like(3001) if n == 3001 else scene(10000)[:n]
+        _CACHE[("rec", n)] = _special(base)
+    return _CACHE[("rec", n)]
+
+
+# ---- CPU --------------------------------------------------------------------------------------------------------------------------
+def test_export_abi():
+    """The six symbols are exported without a GPU and listed; the ABI version stays 3; a null context (for gs_ply_save: a null
+    path) is refused with a message; the Node host's names exist."""
+    from gsplat import _abi
+    L = _abi.load()
+    for name in SYMBOLS:
+        assert hasattr(L, name) and name in _abi.ABI_SYMBOLS
+    assert L.gs_abi_version() == 3
+    n = ctypes.c_uint64(77)
+    for call, who in ((lambda: L.gs_state_list(None, 0, 0, None, 0, ctypes.byref(n)), b"gs_state_list"),
+                      (lambda: L.gs_export_splats(None, 0, 0, None, 0, ctypes.byref(n), None), b"gs_export_splats"),
+                      (lambda: L.gs_export_splats_device(None, 0, 0, None, 0, ctypes.byref(n), None), b"gs_export_splats_device"),
+                      (lambda: L.gs_compact(None, 0, 0, ctypes.byref(n), None), b"gs_compact"),
+                      (lambda: L.gs_export_ply(None, b"x.ply", 0, 0, 3, ctypes.byref(n)), b"gs_export_ply"),
+                      (lambda: L.gs_ply_save(None, None, 0, 3), b"gs_ply_save")):
+        assert call() == _abi.GS_ERR_INVALID_ARGUMENT
+        assert who in L.gs_last_error() and b"null" in L.gs_last_error()
+    assert n.value == 77
+    hdr = open(os.path.join(ROOT, "include", "gsplat", "gs_abi.h")).read()
+    for name in SYMBOLS:
+        assert "int32_t %s(" % name in hdr
+    assert "splat edits" in hdr and "#define GS_ABI_VERSION 3\n" in hdr
+    js = os.path.join(ROOT, "gaussian-splatting-wgpu_amd", "js")
+    dts, rjs, idx = (open(os.path.join(js, f)).read() for f in ("index.d.ts", "renderer.js", "index.js"))
+    for m in ("listState(", "exportSplats(", "compact(", "deleteHidden(", "savePly("):
+        assert m in dts and m in rjs
+    assert "savePly" in idx and "export function savePly(" in dts
+    napi = open(os.path.join(ROOT, "gaussian-splatting-wgpu_amd", "csrc", "napi", "gs_napi.c")).read()
+    for name in ("listState", "exportSplats", "compact", "exportPly", "savePly"):
+        assert '{"%s", js_' % name in napi
+
+
+def test_restatement_sanity():
+    """The padding list has 21 entries, is disjoint from the 59 floats the upload reads, and together they are the record."""
+    assert len(er.PADDING) == 21 and len(set(er.PADDING)) == 21
+    assert len(er.CARRIED) == 59 and len(set(er.CARRIED)) == 59
+    assert not set(er.PADDING) & set(er.CARRIED)
+    assert sorted(er.PADDING + er.CARRIED) == list(range(80))
+    assert er.PADDING == [3, 7, 13, 14, 15] + [19 + 4 * k for k in range(16)]
+    st = np.array([0, 1, 2, 3, 0x83, 0x80], np.uint8)
+    assert er.ids_of(st, HID, 0).tolist() == [0, 2, 5] and er.ids_of(st, 0, 0).tolist() == [0, 1, 2, 3, 4, 5]
+    assert er.ids_of(st, 0, 1).size == 0 and er.ids_of(st, 0xFF, 0x83).tolist() == [4]
+    names, cols = er.ply_columns(_records(5), 1)
+    assert names[9:18] == ["f_rest_%d" % k for k in range(9)] and cols.shape == (5, 26)
+    # f_rest_{cK+i} is coefficient i + 1, channel c
+    np.testing.assert_array_equal(cols[:, 9 + 1 * 3 + 2], er.bits(_records(5))[:, 16 + 4 * 3 + 1])
+
+
+@pytest.mark.parametrize("n", [0, 1, 5, 3001])
+@pytest.mark.parametrize("degree", [0, 1, 2, 3])
+def test_ply_save_round_trip(tmp_path, degree, n):
+    """gs_ply_save -> gs_ply_load: the records come back with the padding zeroed and the coefficients above the degree zeroed, bit
+    for bit, special floats included; the header is the property list of the restatement and the data has the stated size."""
+    from gsplat import _abi
+    rec = _special(_records(3001)[:n]) if n else np.zeros((0, 80), F)  # (the special floats land inside the first n records)
+    path = str(tmp_path / "out.ply")
+    _abi.save_ply(path, rec, degree)
+    back, deg = _abi.load_ply(path)
+    assert deg == degree and back.shape == (n, 80)
+    np.testing.assert_array_equal(er.bits(back), er.bits(er.truncate_degree(er.zero_padding(rec), degree)))
+    raw = open(path, "rb").read()
+    count, names, off = er.parse_ply_header(raw)
+    want_names, want_cols = er.ply_columns(rec, degree)
+    K = er.sh_rest_count(degree)
+    assert count == n and names == want_names and len(names) == 17 + 3 * K
+    assert len(raw) - off == n * 4 * (17 + 3 * K)
+    np.testing.assert_array_equal(np.frombuffer(raw[off:], dtype="<u4").reshape(n, 17 + 3 * K), want_cols)
+    if n:
+        assert not np.isfinite(back).all() and (n < 5 or (np.isnan(back).any() and np.isinf(back).any()))
+
+
+def test_ply_save_errors(tmp_path):
+    from gsplat import _abi
+    L = _abi.load()
+    rec = _records(5)
+    good = str(tmp_path / "good.ply").encode()
+    for degree in (4, -1):
+        assert L.gs_ply_save(good, rec.ctypes.data, 5, degree) == _abi.GS_ERR_INVALID_ARGUMENT
+        assert b"sh_degree" in L.gs_last_error()
+    assert L.gs_ply_save(None, rec.ctypes.data, 5, 3) == _abi.GS_ERR_INVALID_ARGUMENT
+    assert L.gs_ply_save(good, None, 5, 3) == _abi.GS_ERR_INVALID_ARGUMENT
+    assert not os.path.exists(good.decode())
+    missing = str(tmp_path / "no_such_dir" / "out.ply")
+    assert L.gs_ply_save(missing.encode(), rec.ctypes.data, 5, 3) == _abi.GS_ERR_INVALID_ARGUMENT
+    msg = L.gs_last_error().decode()
+    assert missing in msg and os.strerror(2) in msg
+    assert not os.path.exists(missing) and not os.path.exists(os.path.dirname(missing))
+    assert L.gs_ply_save(good, None, 0, 3) == 0  # no records: a header alone
+    assert er.parse_ply_header(open(good.decode(), "rb").read())[0] == 0
+
+
+# ---- GPU --------------------------------------------------------------------------------------------------------------------------
+def _mk(s, W, H, ts, exact=True, state=True, cols=None, flags=0, **kw):
+    from gpu_checks import make_renderer
+    from gsplat import _abi
+    fl = flags | (_abi.GS_FLAG_EXACT_BLEND if exact else 0) | (_abi.GS_FLAG_SPLAT_STATE if state else 0)
+    return make_renderer(s, W, H, ts, flags=fl, cols=cols, **kw)
+
+
+def _code(fn):
+    from gsplat import _abi
+    with pytest.raises(_abi.GsError) as e:
+        fn()
+    return e.value.code, str(e.value)
+
+
+def _planes(n):
+    rng = np.random.default_rng(1234 + n)
+    first, last = np.full(n, 0xFF, np.uint8), np.full(n, 0xFF, np.uint8)
+    first[0] = 0
+    last[n - 1] = 0
+    return {"zero": np.zeros(n, np.uint8), "all_0x83": np.full(n, 0x83, np.uint8),
+            "every_third": np.where(np.arange(n) % 3 == 1, HID, 0).astype(np.uint8),
+            "random": rng.integers(0, 256, n, dtype=np.uint8),
+            # exactly one splat matches the filter (HID, 0): the first, or the last (and every splat but that one (SEL, SEL))
+            "only_first": first, "only_last": last}
+
+
+def _guarded(shape, dtype):
+    a = np.empty(shape, dtype)
+    a.view(np.uint8).fill(0xA5)
+    return a
+
+
+def _is_fill(a):
+    return bool((np.ascontiguousarray(a).view(np.uint8) == 0xA5).all())
+
+
+def _raw_export(r, mask, value, with_ids, device=False):
+    """gs_export_splats[_device] into buffers one record and one id longer than needed, pre-filled with 0xA5; returns (records,
+    ids or None) after checking the guards."""
+    from gsplat import _abi
+    L = _abi.load()
+    n = ctypes.c_uint64()
+    _abi.check(L.gs_export_splats(r._ctx, mask, value, None, 0, ctypes.byref(n), None))
+    m = n.value
+    if device:
+        import torch
+        rec_t = torch.full((m + 1, 80), 0, dtype=torch.float32, device="cuda")
+        rec_t.view(torch.uint8).fill_(0xA5)
+        ids_t = torch.zeros(m + 1, dtype=torch.int32, device="cuda")
+        ids_t.view(torch.uint8).fill_(0xA5)
+        torch.cuda.synchronize()
+        n2 = ctypes.c_uint64()
+        _abi.check(L.gs_export_splats_device(r._ctx, mask, value, rec_t.data_ptr(), m + 1, ctypes.byref(n2), ids_t.data_ptr() if with_ids else None))
+        rec, ids = rec_t.cpu().numpy(), ids_t.cpu().numpy().view(np.uint32)
+    else:
+        rec, ids = _guarded((m + 1, 80), F), _guarded(m + 1, np.uint32)
+        n2 = ctypes.c_uint64()
+        _abi.check(L.gs_export_splats(r._ctx, mask, value, rec.ctypes.data, m + 1, ctypes.byref(n2), ids.ctypes.data if with_ids else None))
+    assert n2.value == m
+    assert _is_fill(rec[m:]) and _is_fill(ids[m:])
+    if not with_ids:
+        assert _is_fill(ids)
+    return rec[:m], (ids[:m] if with_ids else None)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [1, 3, 4, 5, 1023, 1024, 1025, 3001, 10000])
+def test_list_and_export_kernels(n):
+    """Every plane x every filter: gs_state_list, gs_export_splats (with and without ids) and gs_export_splats_device equal the
+    restatement; the guards behind the outputs are intact; the query form and gs_state_count return the same n.  n = 1, 3, 4, 5:
+    the word tail; 1023, 1024, 1025: one workgroup less one splat, exactly one, one plus one splat; 3001: the ragged fixture."""
+    from gsplat import _abi
+    L = _abi.load()
+    rec = _records(n)
+    r = _mk(rec, 64, 64, 8)
+    seen = 0
+    for pname, plane in _planes(n).items():
+        r.write_state(plane)
+        for mask, value in FILTERS:
+            want_ids = er.ids_of(plane, mask, value)
+            want_rec = er.records(rec, plane, mask, value)
+            m = want_ids.size
+            seen += int(0 < m < n)
+            cnt = ctypes.c_uint64()
+            _abi.check(L.gs_state_list(r._ctx, mask, value, None, 0, ctypes.byref(cnt)))
+            assert cnt.value == m == r.state_count(mask, value), (pname, mask, value)
+            ids = _guarded(m + 1, np.uint32)
+            _abi.check(L.gs_state_list(r._ctx, mask, value, ids.ctypes.data, m + 1, ctypes.byref(cnt)))
+            assert cnt.value == m and _is_fill(ids[m:])
+            np.testing.assert_array_equal(ids[:m], want_ids, err_msg="%s (%#x, %#x)" % (pname, mask, value))
+            np.testing.assert_array_equal(r.list_state(mask, value), want_ids)
+            for with_ids in (False, True):
+                for device in (False, True):
+                    got, gids = _raw_export(r, mask, value, with_ids, device)
+                    np.testing.assert_array_equal(er.bits(got), er.bits(want_rec), err_msg="%s (%#x, %#x) device=%s" % (pname, mask, value, device))
+                    if with_ids:
+                        np.testing.assert_array_equal(gids, want_ids)
+            if pname == "random":
+                a, b = r.export_splats(mask, value, with_ids=True)
+                np.testing.assert_array_equal(er.bits(a), er.bits(want_rec))
+                np.testing.assert_array_equal(b, want_ids)
+                d = r.export_splats(mask, value, device=True)
+                np.testing.assert_array_equal(er.bits(d.cpu().numpy()), er.bits(want_rec))
+    assert seen >= (4 if n >= 3 else 0)  # proper subsets were selected
+    r.destroy()
+
+
+@pytest.mark.gpu
+def test_large_list():
+    """1 050 001 splats = 1 026 workgroup counts: more than the 256 threads of the one scan workgroup, so its loop runs five trips
+    and the carry crosses them.  All-zero records (nothing is rendered), a seeded random plane, gs_state_list only."""
+    n = 1050001
+    r = _mk(np.zeros((n, 80), F), 64, 64, 8)
+    plane = np.random.default_rng(7).integers(0, 256, n, dtype=np.uint8)
+    r.write_state(plane)
+    for mask, value in ((HID, 0), (0xFF, 0x83), (HID | SEL, SEL), (0, 0)):
+        np.testing.assert_array_equal(r.list_state(mask, value), er.ids_of(plane, mask, value))
+    r.destroy()
+
+
+@pytest.mark.gpu
+def test_unflagged_context(tmp_path):
+    """Without GS_FLAG_SPLAT_STATE (0, 0) exports, lists and saves what is resident; any other filter is refused."""
+    from gsplat import _abi
+    rec = _records(3001)
+    r = _mk(rec, 64, 64, 8, state=False)
+    got, ids = _raw_export(r, 0, 0, True)
+    np.testing.assert_array_equal(er.bits(got), er.bits(er.zero_padding(rec)))
+    np.testing.assert_array_equal(ids, np.arange(3001, dtype=np.uint32))
+    got, ids = _raw_export(r, 0, 0, True, device=True)
+    np.testing.assert_array_equal(er.bits(got), er.bits(er.zero_padding(rec)))
+    np.testing.assert_array_equal(ids, np.arange(3001, dtype=np.uint32))
+    np.testing.assert_array_equal(r.list_state(0, 0), np.arange(3001, dtype=np.uint32))
+    path = str(tmp_path / "all.ply")
+    assert r.save_ply(path) == 3001
+    np.testing.assert_array_equal(er.bits(_abi.load_ply(path)[0]), er.bits(er.zero_padding(rec)))
+    for fn in (lambda: r.list_state(HID, 0), lambda: r.export_splats(HID, 0), lambda: r.export_splats(0, 1, device=True),
+               lambda: r.compact(HID, 0), lambda: r.save_ply(path, SEL, SEL)):
+        c, msg = _code(fn)
+        assert c == _abi.GS_ERR_INVALID_ARGUMENT and "GS_FLAG_SPLAT_STATE" in msg
+    np.testing.assert_array_equal(r.compact(0, 0), np.arange(3001, dtype=np.uint32))  # everything kept: the same path
+    np.testing.assert_array_equal(er.bits(r.export_splats()), er.bits(er.zero_padding(rec)))
+    r.destroy()
+
+
+@pytest.mark.gpu
+def test_export_errors():
+    from gpu_checks import orbit_uniforms
+    from gsplat import _abi
+    L = _abi.load()
+    rec = scene(10000)
+    W = H = 256
+    u = orbit_uniforms(W, H)
+    n = rec.shape[0]
+    plane = np.where(np.arange(n) % 3 == 1, HID, 0).astype(np.uint8)
+    m = int((plane == 0).sum())
+    r = _mk(rec, W, H, 16)
+    r.write_state(plane)
+    cnt = ctypes.c_uint64()
+    ids = _guarded(m, np.uint32)
+    out = _guarded((m, 80), F)
+    assert L.gs_state_list(r._ctx, HID, 0, ids.ctypes.data, m - 1, ctypes.byref(cnt)) == _abi.GS_ERR_INVALID_ARGUMENT
+    assert str(m).encode() in L.gs_last_error() and _is_fill(ids)
+    assert L.gs_export_splats(r._ctx, HID, 0, out.ctypes.data, m - 1, ctypes.byref(cnt), ids.ctypes.data) == _abi.GS_ERR_INVALID_ARGUMENT
+    assert str(m).encode() in L.gs_last_error() and _is_fill(ids) and _is_fill(out)
+    import torch
+    d = torch.zeros((m, 80), dtype=torch.float32, device="cuda")
+    d.view(torch.uint8).fill_(0xA5)
+    torch.cuda.synchronize()
+    assert L.gs_export_splats_device(r._ctx, HID, 0, d.data_ptr(), m - 1, ctypes.byref(cnt), None) == _abi.GS_ERR_INVALID_ARGUMENT
+    assert str(m).encode() in L.gs_last_error() and _is_fill(d.cpu().numpy())
+    for fn in (lambda: r.list_state(0x100, 0), lambda: r.export_splats(0, 0x100), lambda: r.compact(0x100, 0),
+               lambda: r.save_ply("/nonexistent/x.ply", 0x1FF, 0)):
+        assert _code(fn)[0] == _abi.GS_ERR_INVALID_ARGUMENT
+    assert _code(lambda: r.save_ply("/nonexistent_dir_of_the_test/x.ply", HID, 0))[0] == _abi.GS_ERR_INVALID_ARGUMENT
+    assert _code(lambda: r.save_ply("x.ply", HID, 0, sh_degree=4))[0] == _abi.GS_ERR_INVALID_ARGUMENT
+    np.testing.assert_array_equal(r.read_state(), plane)
+    # before any upload
+    cfg = _abi.GsConfig()
+    cfg.struct_size, cfg.width, cfg.height, cfg.tile_size, cfg.flags = ctypes.sizeof(cfg), 64, 64, 8, _abi.GS_FLAG_SPLAT_STATE
+    ctx = ctypes.c_void_p()
+    _abi.check(L.gs_create(ctypes.byref(cfg), ctypes.byref(ctx)))
+    assert L.gs_state_list(ctx, 0, 0, None, 0, ctypes.byref(cnt)) == _abi.GS_ERR_NO_SCENE
+    assert L.gs_export_splats(ctx, 0, 0, None, 0, ctypes.byref(cnt), None) == _abi.GS_ERR_NO_SCENE
+    assert L.gs_compact(ctx, 0, 0, ctypes.byref(cnt), None) == _abi.GS_ERR_NO_SCENE
+    assert L.gs_export_ply(ctx, b"x.ply", 0, 0, 3, None) == _abi.GS_ERR_NO_SCENE
+    _abi.check(L.gs_destroy(ctx))
+    # a borrower is refused; the owner's and the borrower's frames are what they were
+    b = _mk(rec, W, H, 16, share_with=r)
+    before = []
+    for x in (r, b):
+        x.render_uniforms(u)
+        x.wait()
+        before.append(x.read_rgba8())
+    c, msg = _code(lambda: b.compact(HID, 0))
+    assert c == _abi.GS_ERR_INVALID_ARGUMENT and "owner" in msg
+    np.testing.assert_array_equal(b.list_state(HID, 0), er.ids_of(plane, HID, 0))  # listing and exporting a borrowed scene is fine
+    for x, img in zip((r, b), before):
+        x.render_uniforms(u)
+        x.wait()
+        np.testing.assert_array_equal(x.read_rgba8(), img)
+    assert before[0][..., :3].any()
+    b.destroy()
+    r.destroy()
+
+
+# ---- compaction is a filtered upload -----------------------------------------------------------------------------------------------
+def _compaction_plane(name, which):
+    import test_splat_state as tss
+    s = tss._scene(name)[0]
+    n = s.shape[0]
+    host = (np.random.default_rng(99).integers(0, 64, n, dtype=np.uint8) << 2).astype(np.uint8)  # bits 2-7 belong to the host
+    if which == "every_third":
+        return tss._hidden_plane(name, "every_third") | host
+    if which == "rect_sphere":
+        return (tss._hidden_plane(name, "centre_half_rect") | np.where(tss._inside(name, "sphere_r1"), SEL, 0).astype(np.uint8)) | host
+    return host  # nothing hidden: kept == N takes the same path
+
+
+COMPACTIONS = [("every_third", (HID, 0)), ("rect_sphere", (HID, 0)), ("rect_sphere", (SEL, SEL)), ("host_bits", (HID, 0))]
+TAPS = ("TILE_COUNTS", "GAUSSIAN_DATA", "KEYS", "VALUES", "RANGES")
+
+
+def _frame(r, u, debug):
+    from gsplat import _abi
+    r.render_uniforms(u, debug=debug)
+    r.wait()
+    out = {t: r.read_buffer(getattr(_abi, "GS_BUF_" + t)) for t in TAPS}
+    out["rgba8"] = r.read_rgba8()
+    out["rgbf"] = r.read_buffer(_abi.GS_BUF_RGB_F32)
+    return out
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("exact", [True, False], ids=["exact", "fused"])
+@pytest.mark.parametrize("which,filt", COMPACTIONS, ids=["%s-%x-%x" % (w, f[0], f[1]) for w, f in COMPACTIONS])
+@pytest.mark.parametrize("case", [("cfgA", 8), ("cfgA", 16), ("cfgA", 32), ("ragged", 8)], ids=lambda c: "%s-t%d" % c)
+def test_compaction_is_a_filtered_upload(oracle, case, which, filt, exact):
+    import test_splat_state as tss
+    from gpu_checks import check_image
+    from gsplat import _abi
+    assert list(tss.FRAME_CASES) == [("cfgA", 8), ("cfgA", 16), ("cfgA", 32), ("ragged", 8)]
+    name, ts = case
+    s, u, W, H = tss._scene(name)
+    plane = _compaction_plane(name, which)
+    want_ids = er.ids_of(plane, *filt)
+    hidden_filter = filt == (HID, 0)
+    if which != "host_bits":
+        assert 0 < want_ids.size < s.shape[0]
+    r = _mk(s, W, H, ts, exact=exact)
+    r.write_state(plane)
+    old = _frame(r, u, False) if hidden_filter else None
+    ids = r.compact(*filt)
+    np.testing.assert_array_equal(ids, want_ids)
+    assert r.numGaussians == want_ids.size
+    np.testing.assert_array_equal(r.read_state(), plane[want_ids])
+    np.testing.assert_array_equal(er.bits(r.export_splats()), er.bits(er.zero_padding(s[want_ids])))
+    fresh = _mk(np.ascontiguousarray(s[want_ids]), W, H, ts, exact=exact)
+    fresh.write_state(plane[want_ids])
+    for debug in (False, True):
+        a, b = _frame(r, u, debug), _frame(fresh, u, debug)
+        assert r.stats()["num_gaussians"] == want_ids.size
+        for t in TAPS:
+            np.testing.assert_array_equal(a[t], b[t], err_msg="%s debug=%s" % (t, debug))
+        if exact:
+            np.testing.assert_array_equal(a["rgba8"], b["rgba8"])
+            np.testing.assert_array_equal(a["rgbf"], b["rgbf"])
+        else:
+            k = ("ref", name, ts, which, filt)
+            if k not in _CACHE:
+                _CACHE[k] = sr.state_frame(oracle, np.ascontiguousarray(s[want_ids]), u, W, H, ts, plane[want_ids], want_illcond=True)
+            check_image(r, _CACHE[k], False)
+        if hidden_filter and not debug:
+            # what the hidden scene rendered: the same lists under the old numbering, and in EXACT mode the same image
+            np.testing.assert_array_equal(ids[a["VALUES"]], old["VALUES"])
+            np.testing.assert_array_equal(a["RANGES"], old["RANGES"])
+            if exact:
+                np.testing.assert_array_equal(a["rgba8"], old["rgba8"])
+                np.testing.assert_array_equal(a["rgbf"], old["rgbf"])
+    if hidden_filter:  # (the selected splats of cfgA all lie in the hidden rectangle: that compaction renders black, as it must)
+        assert a["rgba8"][..., :3].any()
+    fresh.destroy()
+    r.destroy()
+
+
+@pytest.mark.gpu
+def test_compaction_on_frame_paths(oracle):
+    """Frames in flight, a captured frame graph, a slab, PipelinedRenderer and kept == 0."""
+    import gsplat
+    import test_splat_state as tss
+    from gpu_checks import check_image
+    from gsplat import _abi
+    name, ts = "cfgA", 16
+    s, u, W, H = tss._scene(name)
+    n = s.shape[0]
+    plane = tss._hidden_plane(name, "every_third")
+    ids = er.ids_of(plane, HID, 0)
+    ref = tss._ref(oracle, name, ts, "every_third", plane)  # hidden in place: the image a compacted scene must render too
+    # three frames enqueued and not waited for: the call drains them
+    r = _mk(s, W, H, ts)
+    r.write_state(plane)
+    for _ in range(3):
+        r.render_uniforms(u)
+    np.testing.assert_array_equal(r.delete_hidden(), ids)
+    for _ in range(3):
+        r.render_uniforms(u)
+    check_image(r, ref, True)
+    st = r.stats()
+    assert st["num_gaussians"] == ids.size and st["frames_in_flight"] == 3
+    # capacities are kept at least as large as they were
+    cap = st["capacity"], st["row_capacity"]
+    r.write_state(np.where(np.arange(ids.size) < 10, 0, HID).astype(np.uint8))
+    assert r.delete_hidden().size == 10
+    r.render_uniforms(u)
+    r.wait()
+    st = r.stats()
+    assert st["num_gaussians"] == 10 and st["capacity"] >= cap[0] and st["row_capacity"] >= cap[1]
+    # kept == 0: the context an empty upload leaves
+    r.write_state(np.full(10, HID, np.uint8))
+    assert r.delete_hidden().size == 0 and r.numGaussians == 0
+    r.render_uniforms(u)
+    r.wait()
+    assert r.stats()["num_gaussians"] == 0 and r.stats()["num_intersections"] == 0
+    assert not r.read_rgba8()[..., :3].any() and r.list_state(0, 0).size == 0 and r.export_splats().shape == (0, 80)
+    r.destroy()
+    # a captured graph: the frame after the compaction is right and graph_frames goes on counting
+    g = _mk(s, W, H, ts)
+    g.set_option(_abi.GS_OPT_FRAMES_IN_FLIGHT, 1)
+    g.set_option(_abi.GS_OPT_FRAME_GRAPH, 1)
+    g.write_state(plane)
+    for k in range(2):
+        g.render_uniforms(u)
+        g.wait()
+    assert g.stats()["graph_frames"] == 2
+    check_image(g, ref, True)
+    np.testing.assert_array_equal(g.delete_hidden(), ids)
+    for k in range(2):
+        g.render_uniforms(u)
+        g.wait()
+        check_image(g, ref, True)
+    assert g.stats()["graph_frames"] == 4 and g.stats()["num_gaussians"] == ids.size
+    g.destroy()
+    # a slab context: the slab image after the compaction is the slab image with the splats hidden
+    sl = _mk(s, W, H, ts, cols=(3, 16))
+    sl.write_state(plane)
+    sl.render_uniforms(u)
+    sl.wait()
+    img, f32 = sl.read_rgba8(), sl.read_buffer(_abi.GS_BUF_RGB_F32)
+    np.testing.assert_array_equal(sl.delete_hidden(), ids)
+    sl.render_uniforms(u)
+    sl.wait()
+    np.testing.assert_array_equal(sl.read_rgba8(), img)
+    np.testing.assert_array_equal(sl.read_buffer(_abi.GS_BUF_RGB_F32), f32)
+    assert img[..., :3].any()
+    sl.destroy()
+    # PipelinedRenderer: the owner compacts, the other members are shared again; every slot renders the compacted scene
+    p = gsplat.PipelinedRenderer(gsplat.Canvas(W, H), None, 0, gsplat.PackedGaussians(s), ts, frames_in_flight=3,
+                                 flags=_abi.GS_FLAG_EXACT_BLEND | _abi.GS_FLAG_F32_TAP | _abi.GS_FLAG_SPLAT_STATE)
+    p.render_uniforms(u)  # in flight when the calls come
+    p.write_state(plane)
+    p.render_uniforms(u)
+    np.testing.assert_array_equal(p.delete_hidden(), ids)
+    np.testing.assert_array_equal(p.list_state(0, 0), np.arange(ids.size, dtype=np.uint32))
+    slots = [p.render_uniforms(u) for _ in range(3)]
+    assert sorted(slots) == [0, 1, 2]
+    for slot in slots:
+        p.wait(slot)
+        check_image(p.renderers[slot], ref, True)
+        assert p.renderers[slot].stats()["num_gaussians"] == ids.size
+    p.destroy()
+
+
+@pytest.mark.gpu
+def test_pick_after_compaction(oracle):
+    """gs_pick needs a new frame after a compaction; its ids are then those of the compacted scene."""
+    import test_splat_state as tss
+    from gsplat import _abi
+    from pick_restate import restate_ref
+    name, ts = "cfgA", 16
+    s, u, W, H = tss._scene(name)
+    plane = tss._hidden_plane(name, "centre_half_rect")
+    ids = er.ids_of(plane, HID, 0)
+    xy = np.array([(x, y) for y in range(3, H, 17) for x in range(5, W, 13)], np.uint32)
+    r = _mk(s, W, H, ts)
+    r.write_state(plane)
+    r.render_uniforms(u)
+    r.wait()
+    r.pick(xy)
+    np.testing.assert_array_equal(r.delete_hidden(), ids)
+    assert _code(lambda: r.pick(xy))[0] == _abi.GS_ERR_NO_FRAME
+    assert _code(lambda: r.read_rgba8())[0] == _abi.GS_ERR_NO_FRAME
+    assert _code(lambda: r.read_buffer(_abi.GS_BUF_VALUES))[0] == _abi.GS_ERR_NO_FRAME
+    r.render_uniforms(u)
+    r.wait()
+    ref = oracle.render(np.ascontiguousarray(s[ids]), u, W, H, ts)
+    want = restate_ref(ref, W, H, ts, xy)[0]
+    got = r.pick(xy)
+    for f in ("first_id", "max_id", "median_id", "hit_count"):
+        np.testing.assert_array_equal(got[f], want[f], err_msg=f)
+    assert (got["hit_count"] > 0).any() and (got["first_id"][got["hit_count"] > 0] < ids.size).all()
+    r.destroy()
+
+
+@pytest.mark.gpu
+def test_export_ply(tmp_path):
+    import test_splat_state as tss
+    from gsplat import _abi
+    name, ts = "cfgA", 16
+    s, u, W, H = tss._scene(name)
+    plane = tss._hidden_plane(name, "every_third")
+    ids = er.ids_of(plane, HID, 0)
+    r = _mk(s, W, H, ts)
+    r.write_state(plane)
+    p3, p1 = str(tmp_path / "d3.ply"), str(tmp_path / "d1.ply")
+    assert r.save_ply(p3, HID, 0) == ids.size
+    exported = r.export_splats(HID, 0)
+    np.testing.assert_array_equal(er.bits(exported), er.bits(er.zero_padding(s[ids])))
+    back, deg = _abi.load_ply(p3)
+    assert deg == 3
+    np.testing.assert_array_equal(er.bits(back), er.bits(exported))
+    assert r.save_ply(p1, HID, 0, sh_degree=1) == ids.size
+    back1, deg1 = _abi.load_ply(p1)
+    assert deg1 == 1 and not er.bits(back1)[:, 16 + 16:].any() and er.bits(exported)[:, 16 + 16:].any()
+    np.testing.assert_array_equal(er.bits(back1)[:, :32], er.bits(exported)[:, :32])
+    # the file, uploaded into a fresh context, renders the compacted context's image
+    r.delete_hidden()
+    r.render_uniforms(u)
+    r.wait()
+    fresh = _mk(np.zeros((1, 80), F), W, H, ts)
+    cnt = ctypes.c_uint64()
+    _abi.check(_abi.load().gs_upload_ply(fresh._ctx, p3.encode(), ctypes.byref(cnt)))
+    assert cnt.value == ids.size
+    fresh.render_uniforms(u)
+    fresh.wait()
+    np.testing.assert_array_equal(fresh.read_rgba8(), r.read_rgba8())
+    np.testing.assert_array_equal(fresh.read_buffer(_abi.GS_BUF_RGB_F32), r.read_buffer(_abi.GS_BUF_RGB_F32))
+    assert r.read_rgba8()[..., :3].any()
+    fresh.destroy()
+    r.destroy()
+    # 70 001 records exported whole: a second chunk and a ragged last one
+    n = 70001
+    big = np.tile(_records(10000), (8, 1))[:n].copy()
+    big[:, 0] += np.arange(n, dtype=F)  # every record distinct
+    b = _mk(big, 64, 64, 8, state=False)
+    pb = str(tmp_path / "big.ply")
+    assert b.save_ply(pb) == n
+    np.testing.assert_array_equal(er.bits(_abi.load_ply(pb)[0]), er.bits(er.zero_padding(big)))
+    b.destroy()
+
+
+@pytest.mark.gpu
+@pytest.mark.skipif(NODE is None, reason="node is not installed")
+def test_node_host_export_matches_python(tmp_path):
+    """tests/js/export_check.js hides, deletes, renders, exports and saves through the Node host: the ids, the image, the exported
+    records and the file equal what the Python host makes of the same sequence, byte for byte."""
+    import test_splat_state as tss
+    s, u, W, H = tss._scene("cfgA")
+    n, ts = s.shape[0], 16
+    plane = tss._hidden_plane("cfgA", "every_third")
+    hide = np.flatnonzero(plane).astype(np.uint32)
+    rec, ub, hb, out, ply, ply2 = (str(tmp_path / f) for f in ("rec.bin", "u.bin", "hide.bin", "out.bin", "node.ply", "node2.ply"))
+    s.tofile(rec)
+    np.ascontiguousarray(u, F).tofile(ub)
+    hide.tofile(hb)
+    res = subprocess.run([NODE, os.path.join(ROOT, "tests", "js", "export_check.js")] + [str(a) for a in (rec, n, W, H, ts, ub, hb, out, ply, ply2)],
+                         capture_output=True, text=True, timeout=300)
+    assert res.returncode == 0, res.stderr
+    info = json.loads(res.stdout.strip().splitlines()[-1])
+    r = _mk(s, W, H, ts, exact=False)
+    r.state_ids(hide, sr.SET, HID)
+    listed = r.list_state(HID, 0)
+    ids = r.delete_hidden()
+    r.render_uniforms(u)
+    r.wait()
+    img = r.read_rgba8()
+    exported, eids = r.export_splats(with_ids=True)
+    mine = str(tmp_path / "py.ply")
+    assert r.save_ply(mine) == ids.size
+    r.destroy()
+    k = ids.size
+    assert info["kept"] == k and info["listed"] == k and info["numGaussians"] == k and info["saved"] == k
+    raw = np.fromfile(out, dtype=np.uint8)
+    assert raw.size == 4 * k + 4 * k + W * H * 4 + k * 320 + 4 * k
+    o = 0
+    for want in (listed, ids, img, exported, eids):
+        nb = want.nbytes
+        np.testing.assert_array_equal(raw[o:o + nb], np.ascontiguousarray(want).view(np.uint8).ravel())
+        o += nb
+    assert open(ply, "rb").read() == open(mine, "rb").read()   # renderer.savePly
+    assert open(ply2, "rb").read() == open(mine, "rb").read()  # module-level savePly of the exported buffer
+    assert info["errors"] == {"unflagged": "-1", "badMask": "-1"}
