@@ -163,6 +163,46 @@ __device__ __forceinline__ float gs_exp(float x) {
     return (y * sa) * sb;
 }
 
+// ---- the canonical (EXACT) blend of one list entry on one pixel: the expression tree of compute_tiles.wgsl:52-66, one rounding
+// per written operation.  Shared by both blend kernels (k_blend.hip) and, up to alpha, by the pick (k_pick.hip).
+// conic = (x, y, z) of the entry's conic, d = entry centre - pixel centre, in pixels
+__device__ __forceinline__ float gs_blend_power(float cx, float cy, float cz, float dx, float dy) {
+    const float t1 = cx * dx * dx, t2 = cz * dy * dy, t3 = cy * dx * dy;
+    return -0.5f * (t1 + t2) - t3;
+}
+__device__ __forceinline__ float gs_blend_alpha(float op, float power) { return wg_min(0.99f, op * gs_exp(power)); }
+struct GsPixel { float T, cr, cg, cb, cd; }; // a pixel's transmittance, colour and (AUX) accumulated depth
+// (in and out by value: with five references the workgroup kernel's EXACT code came out with other registers)
+// p1 = conic.xyz, depth; p2 = r, g, b, opacity.  A skipped entry (cond = 0) changes nothing: alpha is in [0, 0.99], so test is finite
+template <bool AUX>
+__device__ __forceinline__ GsPixel gs_blend_exact(GsPixel p, float4 p1, float4 p2, float dx, float dy) {
+    const float power = gs_blend_power(p1.x, p1.y, p1.z, dx, dy);
+    const float alpha = gs_blend_alpha(p2.w, power);
+    const float test = p.T * (1.0f - alpha);
+    const float cond = (power <= 0.0f && alpha >= (float)(1.0 / 255.0) && test >= 0.0001f) ? 1.0f : 0.0f;
+    p.cr += cond * p2.x * alpha * p.T;
+    p.cg += cond * p2.y * alpha * p.T;
+    p.cb += cond * p2.z * alpha * p.T;
+    if constexpr (AUX) p.cd += cond * p1.w * alpha * p.T;
+    p.T = cond * test + (1.0f - cond) * p.T;
+    return p;
+}
+// The exit criterion: a later entry is only kept with alpha >= c = f32(1/255) and T (1 - alpha) >= 1e-4, and
+// fl(T fl(1 - alpha)) <= fl(T fl(1 - c)) for every such alpha, so once that is below 1e-4 the pixel is final.  (fused: its own rounding of it)
+template <bool EXACT>
+__device__ __forceinline__ bool gs_pixel_final(float T) {
+    const float c255 = (float)(1.0 / 255.0);
+    return (EXACT ? T * (1.0f - c255) : __builtin_fmaf(-T, c255, T)) < 0.0001f;
+}
+
+// A tile's run [x, y) of the sorted list (ranges[] holds the inclusive scan of the tile counts), clamped to what the arrays hold
+__device__ __forceinline__ uint2 gs_tile_range(const uint32_t* __restrict__ ranges, uint32_t tile, uint32_t capacity) {
+    const uint32_t start = tile > 0 ? ranges[tile - 1] : 0u;
+    uint32_t end = ranges[tile];
+    if (end > capacity) end = capacity;
+    return make_uint2(start, end);
+}
+
 // Columns of a rect that fall in the slab; column ntx aliases to column 0 of the next tile row
 // (write_tile_ids.wgsl:26-31).  Returns main-run [xa,xb) and whether the alias column is owned.
 // Used by the projection's tile count (k_preprocess.hip) and by the emission (k_binning.hip).

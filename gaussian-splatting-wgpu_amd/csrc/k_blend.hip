@@ -62,8 +62,21 @@ __device__ __forceinline__ bool blend_tmax_cull(float cx, float cy, float cz, fl
     const float qmax = __builtin_fmaxf(__builtin_fmaxf(ax0 + by0 + c00, ax0 + by1 + c01), __builtin_fmaxf(ax1 + by0 + c10, ax1 + by1 + c11));
     const float qmag = __builtin_fmaxf(ax0, ax1) + __builtin_fmaxf(by0, by1) +
                        __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(c00), __builtin_fabsf(c01)), __builtin_fmaxf(__builtin_fabsf(c10), __builtin_fabsf(c11)));
+    // alpha >= min(0.99, op exp(-qmax)) on every live pixel; 1 % off for the roundings of q, exp and the loop's own alpha
     const float alo = 0.99f * __builtin_fminf(0.99f, op * __builtin_amdgcn_exp2f(-1.44269502162933349609375f * (qmax + 1.0e-5f * qmag)));
     return Tmax * (1.0f - alo) < 0.0000999f; // (NaN anywhere: false, the entry stays)
+}
+
+// The bounding box of a block's LIVE pixels (lane = 8 row + column) from their ballot: first / last column and row, as floats.
+// EMPTY_OK: lv may be 0 (the scans are guarded; the box is then meaningless and the caller must not use it)
+struct GsLiveBox { float c0, c1, r0, r1; };
+template <bool EMPTY_OK>
+__device__ __forceinline__ GsLiveBox gs_live_box(unsigned long long lv) {
+    uint32_t lcm = (uint32_t)lv | (uint32_t)(lv >> 32);
+    lcm |= lcm >> 16; lcm |= lcm >> 8; lcm &= 0xFFu; // columns of the block that hold a live pixel
+    const unsigned long long lo = EMPTY_OK ? lv | (1ull << 63) : lv, hi = EMPTY_OK ? lv | 1ull : lv;
+    return GsLiveBox{(float)__builtin_ctz(lcm | 0x100u), (float)(31 - __builtin_clz(lcm | 1u)), (float)(__builtin_ctzll(lo) >> 3),
+                     (float)((63 - __builtin_clzll(hi)) >> 3)};
 }
 
 // GS_FLAG_AUX_OUTPUTS: the per-pixel alpha plane (1 - T) and accumulated-depth plane (sum of cond z alpha T, z = GaussianData.depth,
@@ -73,6 +86,39 @@ __device__ __forceinline__ bool blend_tmax_cull(float cx, float cy, float cz, fl
 struct GsAuxPlanes { float* alpha; float* depth; }; // f32[H][slab_w] each, indexed like the rgba8 slab
 __device__ __forceinline__ GsAuxPlanes gs_aux_planes() { return GsAuxPlanes{nullptr, nullptr}; }
 __device__ __forceinline__ GsAuxPlanes gs_aux_planes(GsAuxPlanes p) { return p; }
+
+// vec4(C, 1) as rgba8unorm (textureStore, compute_tiles.wgsl:71): clamp, *255, round; a NaN channel stores 0
+__device__ __forceinline__ uint32_t gs_pack_rgba8(float cr, float cg, float cb) {
+    const float c[3] = {cr, cg, cb};
+    uint32_t q = 0xFF000000u;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        float v = c[ch];
+        v = (v != v) ? 0.0f : wg_min(wg_max(v, 0.0f), 1.0f);
+        q |= (uint32_t)__builtin_floorf(v * 255.0f + 0.5f) << (8 * ch);
+    }
+    return q;
+}
+// A finished pixel's stores, shared by the blend kernels: rgba8, the optional f32 tap, the AUX planes.  The frame by value, the
+// plane pack by reference and the pack before the offset: each of the other forms changed the register assignment of a blend
+// kernel far from its stores (tools/kernel_resources.py --isa)
+template <bool AUX, typename... Aux>
+__device__ __forceinline__ void gs_store_pixel(const GsFrame f, uint32_t gx, uint32_t gy, float T, float cr, float cg, float cb, float cd,
+                                               uint32_t* rgba8, float* rgbf, const Aux&... aux) {
+    const uint32_t q = gs_pack_rgba8(cr, cg, cb);
+    const uint64_t o = (uint64_t)gy * f.slab_w + (gx - f.px0);
+    rgba8[o] = q;
+    if (rgbf) {
+        rgbf[o * 3 + 0] = cr;
+        rgbf[o * 3 + 1] = cg;
+        rgbf[o * 3 + 2] = cb;
+    }
+    if constexpr (AUX) {
+        const GsAuxPlanes ap = gs_aux_planes(aux...);
+        ap.alpha[o] = 1.0f - T;
+        ap.depth[o] = cd;
+    }
+}
 
 // One workgroup per tile, TS*TS threads, one pixel per thread; wave w owns the 8x8 pixel block
 // (w % (TS/8), w / (TS/8)) of the tile.  The tile's sorted list is consumed in batches of TS*TS
@@ -101,9 +147,8 @@ __global__ __launch_bounds__(TS* TS) void gs_blend_kernel(const uint4* __restric
     const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const uint32_t tx = f.col0 + blockIdx.x, ty = blockIdx.y;
     const uint32_t tile = tx + ty * f.ntx;
-    const uint32_t start = tile > 0 ? ranges[tile - 1] : 0u;
-    uint32_t end = ranges[tile];
-    if (end > f.capacity) end = f.capacity;
+    const uint2 run = gs_tile_range(ranges, tile, f.capacity);
+    const uint32_t start = run.x, end = run.y;
 
     const uint32_t bx0 = tx * TS + (w % WPR) * 8, by0 = ty * TS + (w / WPR) * 8;
     const uint32_t gx = bx0 + (lane & 7), gy = by0 + (lane >> 3);
@@ -182,10 +227,7 @@ __global__ __launch_bounds__(TS* TS) void gs_blend_kernel(const uint4* __restric
         const unsigned long long lv = __ballot(!done);
         if (lv != 0ull) { // otherwise this wave's 8x8 block is final (uniform per wave)
             // the live box and the transmittance left in it (as in gs_blend_quad_kernel: an entry that cannot change a live pixel is skipped)
-            uint32_t lcm = (uint32_t)lv | (uint32_t)(lv >> 32);
-            lcm |= lcm >> 16; lcm |= lcm >> 8; lcm &= 0xFFu;
-            const float lc0 = (float)__builtin_ctz(lcm | 0x100u), lc1 = (float)(31 - __builtin_clz(lcm | 1u));
-            const float lr0 = (float)(__builtin_ctzll(lv) >> 3), lr1 = (float)((63 - __builtin_clzll(lv)) >> 3);
+            const GsLiveBox lb = gs_live_box<false>(lv);
             const float Tmax = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)wave_incl_max(done ? 0u : __float_as_uint(T)), 63));
 #pragma unroll 1
             for (int r = 0; r < ROUNDS; ++r) {
@@ -202,7 +244,7 @@ __global__ __launch_bounds__(TS* TS) void gs_blend_kernel(const uint4* __restric
                         p1.z *= -2.0f * iL;
                     }
                     const float dxh = p0.x - bx0f, dyh = p0.y - by0f;
-                    const float dxlo = dxh - lc1, dxhi = dxh - lc0, dylo = dyh - lr1, dyhi = dyh - lr0; // the LIVE pixels' box
+                    const float dxlo = dxh - lb.c1, dxhi = dxh - lb.c0, dylo = dyh - lb.r1, dyhi = dyh - lb.r0; // the LIVE pixels' box
                     const bool pd = (p1.x > 0.0f) && (p1.z > 0.0f) && (p1.x * p1.z - p1.y * p1.y > 0.0f);
                     float mag;
                     const float q = block_qmin(p1.x, p1.y, p1.z, dxlo, dxhi, dylo, dyhi, mag);
@@ -223,16 +265,8 @@ __global__ __launch_bounds__(TS* TS) void gs_blend_kernel(const uint4* __restric
                     const float4 p2v = sP2[buf][e];
                     const float dx = p0.x - pxf, dy = p0.y - pyf;
                     if (EXACT) {
-                        const float t1 = p1.x * dx * dx, t2 = p1.z * dy * dy, t3 = p1.y * dx * dy;
-                        const float power = -0.5f * (t1 + t2) - t3;
-                        const float alpha = wg_min(0.99f, p2v.w * gs_exp(power));
-                        const float test = T * (1.0f - alpha);
-                        const float cond = (power <= 0.0f && alpha >= c255 && test >= 0.0001f) ? 1.0f : 0.0f;
-                        cr += cond * p2v.x * alpha * T;
-                        cg += cond * p2v.y * alpha * T;
-                        cb += cond * p2v.z * alpha * T;
-                        if constexpr (AUX) cd += cond * p1.w * alpha * T; // sP1.w: the depth, staged in both modes
-                        T = cond * test + (1.0f - cond) * T;
+                        const GsPixel n = gs_blend_exact<AUX>({T, cr, cg, cb, cd}, p1, p2v, dx, dy); // (p1.w: the depth, staged in both modes)
+                        T = n.T; cr = n.cr; cg = n.cg; cb = n.cb; cd = n.cd;
                     } else {
                         const float u = __builtin_fmaf(p1.x, dx, p1.y * dy);
                         const float v = (p1.z * dy) * dy;
@@ -250,9 +284,7 @@ __global__ __launch_bounds__(TS* TS) void gs_blend_kernel(const uint4* __restric
                     }
                 }
             }
-            // exit criterion: no later entry can be kept once fl(T*fl(1-c255)) < 1e-4
-            if (EXACT) done = outside || (T * (1.0f - c255) < 0.0001f);
-            else done = outside || (__builtin_fmaf(-T, c255, T) < 0.0001f);
+            done = outside || gs_pixel_final<EXACT>(T);
         }
         if (nb < end) stage(nb, buf ^ 1); // every wave finished reading buf^1 before the previous barrier
         // one barrier per batch: publishes the next stage; stop when every pixel of the tile is final
@@ -262,29 +294,7 @@ __global__ __launch_bounds__(TS* TS) void gs_blend_kernel(const uint4* __restric
     if (tid == 0 && staged) atomicAdd(&ctl->num_processed[(blockIdx.x + blockIdx.y * gridDim.x) & 63u], (unsigned long long)staged);
     if (lane == 0 && evaluated) atomicAdd(&ctl->num_evaluated[(blockIdx.x + blockIdx.y * gridDim.x + w) & 63u], (unsigned long long)evaluated);
 
-    // textureStore(render_target, xy, vec4(C, 1)) to rgba8unorm (compute_tiles.wgsl:71): clamp, *255, round
-    if (!outside) {
-        const float c[3] = {cr, cg, cb};
-        uint32_t q = 0xFF000000u;
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) {
-            float v = c[ch];
-            v = (v != v) ? 0.0f : wg_min(wg_max(v, 0.0f), 1.0f);
-            q |= (uint32_t)__builtin_floorf(v * 255.0f + 0.5f) << (8 * ch);
-        }
-        const uint64_t o = (uint64_t)gy * f.slab_w + (gx - f.px0);
-        rgba8[o] = q;
-        if (rgbf) {
-            rgbf[o * 3 + 0] = cr;
-            rgbf[o * 3 + 1] = cg;
-            rgbf[o * 3 + 2] = cb;
-        }
-        if constexpr (AUX) {
-            const GsAuxPlanes ap = gs_aux_planes(aux...);
-            ap.alpha[o] = 1.0f - T;
-            ap.depth[o] = cd;
-        }
-    }
+    if (!outside) gs_store_pixel<AUX>(f, gx, gy, T, cr, cg, cb, cd, rgba8, rgbf, aux...);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -316,7 +326,35 @@ extern "C" __attribute__((visibility("default"))) int gs_prof_blend_footprint(un
     return 0;
 }
 #endif
-constexpr bool gs_lds_disjoint(int a, int na, int b, int nb) { return a + na <= b || b + nb <= a; } // byte ranges [a, a+na), [b, b+nb)
+// The fused quad kernel's LDS regions, byte offsets into ONE array placed by hand: T the row tables (8 rows x 65 slots of float2),
+// Q the id ring, P sP0, L sL, Z sZ (what they hold: the kernel's head).  Z (AUX only) comes AFTER the last region, so the regions
+// of the kernels without the planes stay where they are.
+namespace gs_lds {
+struct Region { int off, size, align; };
+constexpr int T = 0, Q = 4160, P = 5184, L = 6208, TOTAL = 6464, Z = TOTAL, TOTAL_AUX = TOTAL + 256;
+constexpr Region regions[] = {{T, 8 * 65 * 8, 8}, {Q, 256 * 4, 4}, {P, 64 * 16, 16}, {L, 64 * 4, 4}, {Z, 64 * 4, 4}};
+constexpr bool fits(const Region* r, int n, int total) { // the first n regions: aligned, inside [0, total), pairwise disjoint
+    for (int i = 0; i < n; ++i) {
+        if (r[i].off % r[i].align || r[i].off < 0 || r[i].off + r[i].size > total) return false;
+        for (int j = 0; j < i; ++j)
+            if (r[i].off < r[j].off + r[j].size && r[j].off < r[i].off + r[i].size) return false;
+    }
+    return true;
+}
+static_assert(fits(regions, 4, TOTAL) && fits(regions, 5, TOTAL_AUX), "a fused LDS region overlaps another or ends outside its array");
+} // namespace gs_lds
+// the keep/skip block of the fused evaluation (see its use); EXTRA: further instructions under the same exec mask
+#define GS_KEEP_BLOCK(EXTRA)                          \
+    "v_mul_f32_e32 %[wgt], %[T], %[ea]\n\t"           \
+    "v_fma_f32 %[test], %[wgt], %[m99], %[T]\n\t"     \
+    "s_mov_b64 %[save], exec\n\t"                     \
+    "v_cmpx_le_f32_e32 vcc, %[k1], %[ea]\n\t"         \
+    "v_cmpx_le_f32_e32 vcc, %[thr], %[test]\n\t"      \
+    "v_mov_b32_e32 %[T], %[test]\n\t"                 \
+    "v_fmac_f32_e32 %[cr], %[c0], %[wgt]\n\t"         \
+    "v_fmac_f32_e32 %[cg], %[c1], %[wgt]\n\t"         \
+    "v_fmac_f32_e32 %[cb], %[c2], %[wgt]\n\t" EXTRA   \
+    "s_mov_b64 exec, %[save]"
 typedef uint32_t gs_u32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t gs_u32x3 __attribute__((ext_vector_type(3)));
 typedef uint32_t gs_u32x4 __attribute__((ext_vector_type(4)));
@@ -338,35 +376,16 @@ __global__ __launch_bounds__(64) void gs_blend_quad_kernel(const uint4* __restri
     // tabulated by the lane that parks the entry (4 instructions per row).  The loop evaluates it with two fmas and no
     // subtraction; round 3's first table (conic.y' dy, conic.z' dy^2 + log2 op per row) still needed dx = gx - px and a third
     // read per entry.  Rows are 65 slots apart: the 8 rows of a slot then sit in 8 different bank pairs (ds_read_b64).
-    // AUX (GS_FLAG_AUX_OUTPUTS): EXACT stages the depth in sP1.w; fused adds sZ (0.99 z per slot: the loop's weight is T alpha / 0.99)
-    // AFTER the last region, so the regions of the kernels without the planes stay where they are.
-#ifndef GS_L_OFF_T
-#define GS_L_OFF_T 0
-#define GS_L_OFF_Q 4160
-#define GS_L_OFF_P 5184
-#define GS_L_OFF_L 6208
-#define GS_L_TOTAL 6464
-#endif
-#define GS_L_OFF_Z GS_L_TOTAL
-#define GS_L_TOTAL_AUX (GS_L_TOTAL + 256)
-    static_assert(gs_lds_disjoint(GS_L_OFF_T, 8 * 65 * 8, GS_L_OFF_Q, 256 * 4) && gs_lds_disjoint(GS_L_OFF_T, 8 * 65 * 8, GS_L_OFF_P, 64 * 16) &&
-                  gs_lds_disjoint(GS_L_OFF_T, 8 * 65 * 8, GS_L_OFF_L, 64 * 4) && gs_lds_disjoint(GS_L_OFF_T, 8 * 65 * 8, GS_L_OFF_Z, 64 * 4) &&
-                  gs_lds_disjoint(GS_L_OFF_Q, 256 * 4, GS_L_OFF_P, 64 * 16) && gs_lds_disjoint(GS_L_OFF_Q, 256 * 4, GS_L_OFF_L, 64 * 4) &&
-                  gs_lds_disjoint(GS_L_OFF_Q, 256 * 4, GS_L_OFF_Z, 64 * 4) && gs_lds_disjoint(GS_L_OFF_P, 64 * 16, GS_L_OFF_L, 64 * 4) &&
-                  gs_lds_disjoint(GS_L_OFF_P, 64 * 16, GS_L_OFF_Z, 64 * 4) && gs_lds_disjoint(GS_L_OFF_L, 64 * 4, GS_L_OFF_Z, 64 * 4),
-                  "fused LDS regions overlap");
-    static_assert(GS_L_OFF_T + 8 * 65 * 8 <= GS_L_TOTAL && GS_L_OFF_Q + 256 * 4 <= GS_L_TOTAL && GS_L_OFF_P + 64 * 16 <= GS_L_TOTAL &&
-                  GS_L_OFF_L + 64 * 4 <= GS_L_TOTAL && GS_L_OFF_Z + 64 * 4 <= GS_L_TOTAL_AUX && GS_L_OFF_P % 16 == 0 && GS_L_OFF_T % 8 == 0,
-                  "a fused LDS region ends outside its array");
+    // AUX (GS_FLAG_AUX_OUTPUTS): EXACT stages the depth in sP1.w; fused adds sZ (0.99 z per slot: the loop's weight is T alpha / 0.99).
     __shared__ __attribute__((aligned(16))) unsigned char lds_x[EXACT ? 4096 : 16];         // EXACT: sP0 | sP1 | sP2 | sQ
-    __shared__ __attribute__((aligned(16))) unsigned char lds_f[EXACT ? 16 : (AUX ? GS_L_TOTAL_AUX : GS_L_TOTAL)]; // fused: placed by hand (the offsets matter: see gs_launch_blend)
-    float4* const sP0 = reinterpret_cast<float4*>(EXACT ? lds_x : lds_f + GS_L_OFF_P);
+    __shared__ __attribute__((aligned(16))) unsigned char lds_f[EXACT ? 16 : (AUX ? gs_lds::TOTAL_AUX : gs_lds::TOTAL)]; // fused: gs_lds
+    float4* const sP0 = reinterpret_cast<float4*>(EXACT ? lds_x : lds_f + gs_lds::P);
     float4* const sP1 = reinterpret_cast<float4*>(lds_x + (EXACT ? 1024 : 0));
     float4* const sP2 = reinterpret_cast<float4*>(lds_x + (EXACT ? 2048 : 0));
-    uint32_t* const sQ = reinterpret_cast<uint32_t*>(EXACT ? lds_x + 3072 : lds_f + GS_L_OFF_Q);
-    float* const sL = reinterpret_cast<float*>(lds_f + (EXACT ? 0 : GS_L_OFF_L));
-    float2* const sT = reinterpret_cast<float2*>(lds_f + (EXACT ? 0 : GS_L_OFF_T));
-    float* const sZ = reinterpret_cast<float*>(lds_f + ((EXACT || !AUX) ? 0 : GS_L_OFF_Z)); // fused AUX only
+    uint32_t* const sQ = reinterpret_cast<uint32_t*>(EXACT ? lds_x + 3072 : lds_f + gs_lds::Q);
+    float* const sL = reinterpret_cast<float*>(lds_f + (EXACT ? 0 : gs_lds::L));
+    float2* const sT = reinterpret_cast<float2*>(lds_f + (EXACT ? 0 : gs_lds::T));
+    float* const sZ = reinterpret_cast<float*>(lds_f + ((EXACT || !AUX) ? 0 : gs_lds::Z)); // fused AUX only
     const uint32_t lane = threadIdx.x;
     const uint32_t slab_tx = f.col1 - f.col0;
     // Workgroups are dealt round-robin to the 8 XCDs (b % 8), each with its own L2.  XCD x owns the column strips
@@ -387,10 +406,8 @@ __global__ __launch_bounds__(64) void gs_blend_quad_kernel(const uint4* __restri
     const uint32_t tx = f.col0 + (x + 8u * (cc / SW)) * SW + cc % SW;
     const uint32_t lin = ty * slab_tx + (tx - f.col0);
     const uint32_t tile = tx + ty * f.ntx;
-    const uint32_t start = tile > 0 ? ranges[tile - 1] : 0u;
-    uint32_t end = ranges[tile];
-    if (end > f.capacity) end = f.capacity;
-    const float c255 = (float)(1.0 / 255.0);
+    const uint2 run = gs_tile_range(ranges, tile, f.capacity);
+    const uint32_t start = run.x, end = run.y;
     const float Wf = (float)f.width, Hf = (float)f.height;
     const uint32_t bx0 = tx * TS + (q % BPR) * 8u, by0 = ty * TS + (q / BPR) * 8u;
     const uint32_t gx = bx0 + (lane & 7), gy = by0 + (lane >> 3);
@@ -401,6 +418,7 @@ __global__ __launch_bounds__(64) void gs_blend_quad_kernel(const uint4* __restri
     float cd = 0.0f; // AUX: accumulated depth
     uint32_t staged = 0, evaluated = 0;
 #ifdef GS_PROFILING
+    // gs_blend_foot's words [1..10] (loose locals: as members of one struct they changed the code of the MASKED profiling kernels)
     uint32_t fp_lanes = 0, fp_quads = 0, fp_none = 0, fp_live = 0, fp_kept = 0, fp_dead = 0, fp_q1 = 0, fp_tailn = 0, fp_tailbits = 0, fp_nokeep = 0;
 #endif
 
@@ -497,10 +515,7 @@ __global__ __launch_bounds__(64) void gs_blend_quad_kernel(const uint4* __restri
         // ARE STILL LIVE (conservative closed form, block_qmin): no output bit changes, 27 % fewer evaluations at config B
         // (blend 495 -> 418 us).  The box is taken by the whole wave, outside the branch of the lanes that hold an entry.
         const unsigned long long lv = __ballot(!done);
-        uint32_t lcm = (uint32_t)lv | (uint32_t)(lv >> 32);
-        lcm |= lcm >> 16; lcm |= lcm >> 8; lcm &= 0xFFu; // columns of the block that hold a live pixel
-        const float lc0 = (float)__builtin_ctz(lcm | 0x100u), lc1 = (float)(31 - __builtin_clz(lcm | 1u));
-        const float lr0 = (float)(__builtin_ctzll(lv | (1ull << 63)) >> 3), lr1 = (float)((63 - __builtin_clzll(lv | 1ull)) >> 3);
+        const GsLiveBox lb = gs_live_box<true>(lv);
         // ... AND THE TRANSMITTANCE THAT IS LEFT.  A live pixel whose T is just above the final threshold (1.0039e-4) accepts only
         // entries with alpha <= 1 - 1e-4 / T -- a few per cent -- and stays live, keeping its block alive, until one comes: 84 % of
         // the evaluations that the live box leaves keep NO lane (tools/blend_footprint.py).  With Tmax = the largest T among the live
@@ -514,40 +529,10 @@ __global__ __launch_bounds__(64) void gs_blend_quad_kernel(const uint4* __restri
             {   // (at tile 16 the binning's mask bit has already said "this block": the box is what is left to test)
                 const float dxh = gxp - bx0f, dyh = gyp - by0f;
                 float mag;
-                const float qm = block_qmin(cx, cy, cz, dxh - lc1, dxh - lc0, dyh - lr1, dyh - lr0, mag);
+                const float qm = block_qmin(cx, cy, cz, dxh - lb.c1, dxh - lb.c0, dyh - lb.r1, dyh - lb.r0, mag);
                 const bool nocull = (dbg & 4u) != 0u; // GS_OPT_BLEND_ABLATION bit 2: both culls off (tests: they must not change a bit)
                 rel = lv != 0ull && (nocull || !pd || !(qm > lim + 1.0e-5f * mag)); // (no live pixel: a block outside the canvas)
-#ifndef GS_NO_TMAX // (A/B: tools/build_variant.py notmax -DGS_NO_TMAX)
-                if (rel && pd && !nocull) {
-                    const float x0 = dxh - lc1, x1 = dxh - lc0, y0 = dyh - lr1, y1 = dyh - lr0;
-                    const float ax0 = (0.5f * cx) * x0 * x0, ax1 = (0.5f * cx) * x1 * x1, by0 = (0.5f * cz) * y0 * y0, by1 = (0.5f * cz) * y1 * y1;
-                    const float c00 = cy * x0 * y0, c01 = cy * x0 * y1, c10 = cy * x1 * y0, c11 = cy * x1 * y1;
-                    const float qmax = __builtin_fmaxf(__builtin_fmaxf(ax0 + by0 + c00, ax0 + by1 + c01), __builtin_fmaxf(ax1 + by0 + c10, ax1 + by1 + c11));
-                    const float qmag = __builtin_fmaxf(ax0, ax1) + __builtin_fmaxf(by0, by1) +
-                                       __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(c00), __builtin_fabsf(c01)), __builtin_fmaxf(__builtin_fabsf(c10), __builtin_fabsf(c11)));
-                    // alpha >= min(0.99, op exp(-qmax)) on every live pixel; 1 % off for the roundings of q, exp and the loop's own alpha
-                    const float alo = 0.99f * __builtin_fminf(0.99f, op * __builtin_amdgcn_exp2f(-1.44269502162933349609375f * (qmax + 1.0e-5f * qmag)));
-                    if (Tmax * (1.0f - alo) < 0.0000999f) rel = false; // (NaN anywhere: the comparison is false, the entry stays)
-                }
-#endif
-#ifdef GS_BLEND_PIXTEST
-                // few live pixels: the same two tests per PIXEL instead of per box (alpha within its rounding bounds at the pixel, against
-                // 1/255 and against what the pixel's own T still accepts)
-                if (rel && pd && !nocull && (uint32_t)__popcll(lv) <= GS_BLEND_PIXTEST) {
-                    bool any = false;
-                    for (unsigned long long mm = lv; mm; mm &= mm - 1ull) {
-                        const int pl = __builtin_ctzll(mm);
-                        const float Tp = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(T), pl));
-                        const float dx = dxh - (float)(pl & 7), dy = dyh - (float)(pl >> 3);
-                        const float a = (0.5f * cx) * dx * dx, b = (0.5f * cz) * dy * dy, c = cy * dx * dy;
-                        const float q = a + b + c, mg = 1.0e-5f * (a + b + __builtin_fabsf(c));
-                        const float ahi = 1.01f * (op * __builtin_amdgcn_exp2f(-1.44269502162933349609375f * (q - mg)));
-                        const float alo = 0.99f * __builtin_fminf(0.99f, op * __builtin_amdgcn_exp2f(-1.44269502162933349609375f * (q + mg)));
-                        any = any || !(ahi < c255 || Tp * (1.0f - alo) < 0.0000999f); // (NaN: kept)
-                    }
-                    rel = any;
-                }
-#endif
+                if (rel && pd && !nocull && blend_tmax_cull(cx, cy, cz, op, dxh - lb.c1, dxh - lb.c0, dyh - lb.r1, dyh - lb.r0, Tmax)) rel = false;
             }
 #ifdef GS_PROFILING
             if (dbg & 1u) rel = false; // staging cost without the pixel loop
@@ -619,16 +604,8 @@ __global__ __launch_bounds__(64) void gs_blend_quad_kernel(const uint4* __restri
                     const float4 p1 = sP1[e];
                     const float dy = p0.y - pyf;
                     const float4 p2v = sP2[e];
-                    const float t1 = p1.x * dx * dx, t2 = p1.z * dy * dy, t3 = p1.y * dx * dy;
-                    const float power = -0.5f * (t1 + t2) - t3;
-                    const float alpha = wg_min(0.99f, p2v.w * gs_exp(power));
-                    const float test = T * (1.0f - alpha);
-                    const float cond = (power <= 0.0f && alpha >= c255 && test >= 0.0001f) ? 1.0f : 0.0f;
-                    cr += cond * p2v.x * alpha * T;
-                    cg += cond * p2v.y * alpha * T;
-                    cb += cond * p2v.z * alpha * T;
-                    if constexpr (AUX) cd += cond * p1.w * alpha * T;
-                    T = cond * test + (1.0f - cond) * T;
+                    const GsPixel n = gs_blend_exact<AUX>({T, cr, cg, cb, cd}, p1, p2v, dx, dy); // (the reads above: in the order the schedule was found with)
+                    T = n.T; cr = n.cr; cg = n.cg; cb = n.cb; cd = n.cd;
                 } else {
                     const float pw = __builtin_fmaf(xlf, __builtin_fmaf(xlf, p0.x, tt.x), tt.y); // log2(alpha / 0.99) before the clamp
                     float ea; // min(1, alpha / 0.99): v_exp_f32 with the clamp modifier (one instruction; a v_min on alpha was a second)
@@ -642,7 +619,7 @@ __global__ __launch_bounds__(64) void gs_blend_quad_kernel(const uint4* __restri
                         fp_quads += (uint32_t)((km & q0) != 0) + (uint32_t)((km & (q0 << 4)) != 0) + (uint32_t)((km & (q0 << 32)) != 0) + (uint32_t)((km & (q0 << 36)) != 0);
                         fp_none += (uint32_t)(km == 0);
                         // lanes whose pixel is still live (an entry can still pass its transmittance test) and what the entry does to them
-                        const unsigned long long lv = __ballot(__builtin_fmaf(-T, c255, T) >= 0.0001f);
+                        const unsigned long long lv = __ballot(__builtin_fmaf(-T, (float)(1.0 / 255.0), T) >= 0.0001f);
                         const unsigned long long kp = __ballot(ea >= k1 && __builtin_fmaf(T * ea, -0.99f, T) >= 0.0001f);
                         fp_live += (uint32_t)__popcll(lv);
                         fp_kept += (uint32_t)__popcll(kp);
@@ -670,38 +647,17 @@ __global__ __launch_bounds__(64) void gs_blend_quad_kernel(const uint4* __restri
                         float wgt, test;
                         unsigned long long save;
                         if constexpr (AUX) // the same block, plus the depth's fmac under the same exec mask
-                            asm(
-                                "v_mul_f32_e32 %[wgt], %[T], %[ea]\n\t"
-                                "v_fma_f32 %[test], %[wgt], %[m99], %[T]\n\t"
-                                "s_mov_b64 %[save], exec\n\t"
-                                "v_cmpx_le_f32_e32 vcc, %[k1], %[ea]\n\t"
-                                "v_cmpx_le_f32_e32 vcc, %[thr], %[test]\n\t"
-                                "v_mov_b32_e32 %[T], %[test]\n\t"
-                                "v_fmac_f32_e32 %[cr], %[c0], %[wgt]\n\t"
-                                "v_fmac_f32_e32 %[cg], %[c1], %[wgt]\n\t"
-                                "v_fmac_f32_e32 %[cb], %[c2], %[wgt]\n\t"
-                                "v_fmac_f32_e32 %[cd], %[z], %[wgt]\n\t"
-                                "s_mov_b64 exec, %[save]"
+                            asm(GS_KEEP_BLOCK("v_fmac_f32_e32 %[cd], %[z], %[wgt]\n\t")
                                 : [save] "=&s"(save), [wgt] "=&v"(wgt), [test] "=&v"(test), [T] "+v"(T), [cr] "+v"(cr), [cg] "+v"(cg), [cb] "+v"(cb),
                                   [cd] "+v"(cd)
                                 : [k1] "s"(k1), [thr] "s"(0.0001f), [m99] "s"(-0.99f), [ea] "v"(ea), [c0] "v"(p0.y), [c1] "v"(p0.z), [c2] "v"(p0.w),
                                   [z] "v"(zz)
                                 : "vcc");
                         else
-                        asm(
-                            "v_mul_f32_e32 %[wgt], %[T], %[ea]\n\t"
-                            "v_fma_f32 %[test], %[wgt], %[m99], %[T]\n\t"
-                            "s_mov_b64 %[save], exec\n\t"
-                            "v_cmpx_le_f32_e32 vcc, %[k1], %[ea]\n\t"
-                            "v_cmpx_le_f32_e32 vcc, %[thr], %[test]\n\t"
-                            "v_mov_b32_e32 %[T], %[test]\n\t"
-                            "v_fmac_f32_e32 %[cr], %[c0], %[wgt]\n\t"
-                            "v_fmac_f32_e32 %[cg], %[c1], %[wgt]\n\t"
-                            "v_fmac_f32_e32 %[cb], %[c2], %[wgt]\n\t"
-                            "s_mov_b64 exec, %[save]"
-                            : [save] "=&s"(save), [wgt] "=&v"(wgt), [test] "=&v"(test), [T] "+v"(T), [cr] "+v"(cr), [cg] "+v"(cg), [cb] "+v"(cb)
-                            : [k1] "s"(k1), [thr] "s"(0.0001f), [m99] "s"(-0.99f), [ea] "v"(ea), [c0] "v"(p0.y), [c1] "v"(p0.z), [c2] "v"(p0.w)
-                            : "vcc");
+                            asm(GS_KEEP_BLOCK("")
+                                : [save] "=&s"(save), [wgt] "=&v"(wgt), [test] "=&v"(test), [T] "+v"(T), [cr] "+v"(cr), [cg] "+v"(cg), [cb] "+v"(cb)
+                                : [k1] "s"(k1), [thr] "s"(0.0001f), [m99] "s"(-0.99f), [ea] "v"(ea), [c0] "v"(p0.y), [c1] "v"(p0.z), [c2] "v"(p0.w)
+                                : "vcc");
                     }
                 }
             };
@@ -734,8 +690,7 @@ __global__ __launch_bounds__(64) void gs_blend_quad_kernel(const uint4* __restri
         };
         if (EXACT || __ballot(npd) != 0ull) walk(std::true_type{});
         else walk(std::false_type{});
-        if (EXACT) done = outside || (T * (1.0f - c255) < 0.0001f);
-        else done = outside || (__builtin_fmaf(-T, c255, T) < 0.0001f);
+        done = outside || gs_pixel_final<EXACT>(T);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         if (__ballot(!done) == 0ull) break; // this block's 64 pixels are final (exact criterion)
@@ -747,12 +702,9 @@ __global__ __launch_bounds__(64) void gs_blend_quad_kernel(const uint4* __restri
     if (lane == 0 && evaluated) atomicAdd(&ctl->num_evaluated[(b + 1u) & 63u], (unsigned long long)evaluated);
 #ifdef GS_PROFILING
     if ((dbg & 32u) && lane == 0) {
-        unsigned long long* fp = gs_blend_foot[b & 255u];
-        atomicAdd(&fp[0], (unsigned long long)evaluated); atomicAdd(&fp[1], (unsigned long long)fp_lanes);
-        atomicAdd(&fp[2], (unsigned long long)fp_quads); atomicAdd(&fp[3], (unsigned long long)fp_none);
-        atomicAdd(&fp[4], (unsigned long long)fp_live); atomicAdd(&fp[5], (unsigned long long)fp_kept);
-        atomicAdd(&fp[6], (unsigned long long)fp_dead); atomicAdd(&fp[7], (unsigned long long)fp_q1);
-        atomicAdd(&fp[8], (unsigned long long)fp_tailn); atomicAdd(&fp[9], (unsigned long long)fp_tailbits); atomicAdd(&fp[10], (unsigned long long)fp_nokeep);
+        const uint32_t w[11] = {evaluated, fp_lanes, fp_quads, fp_none, fp_live, fp_kept, fp_dead, fp_q1, fp_tailn, fp_tailbits, fp_nokeep};
+#pragma unroll
+        for (int k = 0; k < 11; ++k) atomicAdd(&gs_blend_foot[b & 255u][k], (unsigned long long)w[k]);
     }
     if (prof && lane == 0) {
         prof[b * 4u + 0u] = t_start;
@@ -761,28 +713,7 @@ __global__ __launch_bounds__(64) void gs_blend_quad_kernel(const uint4* __restri
         prof[b * 4u + 3u] = staged;
     }
 #endif
-    if (!outside) {
-        const float c[3] = {cr, cg, cb};
-        uint32_t px = 0xFF000000u;
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) {
-            float v = c[ch];
-            v = (v != v) ? 0.0f : wg_min(wg_max(v, 0.0f), 1.0f);
-            px |= (uint32_t)__builtin_floorf(v * 255.0f + 0.5f) << (8 * ch);
-        }
-        const uint64_t o = (uint64_t)gy * f.slab_w + (gx - f.px0);
-        rgba8[o] = px;
-        if (rgbf) {
-            rgbf[o * 3 + 0] = cr;
-            rgbf[o * 3 + 1] = cg;
-            rgbf[o * 3 + 2] = cb;
-        }
-        if constexpr (AUX) {
-            const GsAuxPlanes ap = gs_aux_planes(aux...);
-            ap.alpha[o] = 1.0f - T;
-            ap.depth[o] = cd;
-        }
-    }
+    if (!outside) gs_store_pixel<AUX>(f, gx, gy, T, cr, cg, cb, cd, rgba8, rgbf, aux...);
 }
 
 // ---- multi-GPU presentation: slabs (rank-major, each u32[H][w_g]) -> one row-major u32[H][W] image ---
@@ -822,7 +753,7 @@ __global__ __launch_bounds__(256) void gs_debug_view_kernel(const uint32_t* __re
     } else {
         c[0] = c[1] = len / 100.0f; c[2] = 0.0f;
     }
-    uint32_t px = 0xFF000000u;
+    uint32_t px = 0xFF000000u; // (gs_pack_rgba8 without its NaN test: sharing it changed this kernel's code)
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
         const float v = wg_min(wg_max(c[ch], 0.0f), 1.0f);
@@ -838,33 +769,36 @@ void gs_launch_debug_view(const uint32_t* ranges, const GsFrame& f, uint32_t vie
 
 // ---- host launchers --------------------------------------------------------------------------------
 // aux: GS_FLAG_AUX_OUTPUTS -- the AUX instantiations, which take the planes `ap` (non-null: gs_launch_blend checks)
+// calls f with one std::bool_constant per runtime bool: every combination is instantiated, the matching one runs
+template <class F>
+static void gs_dispatch(F&& f) { f(); }
+template <class F, class... Bs>
+static void gs_dispatch(F&& f, bool b, Bs... rest) {
+    if (b) gs_dispatch([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+    else gs_dispatch([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
 template <int TS>
 static void launch_blend_t(bool exact, bool aux, GsAuxPlanes ap, dim3 grid, hipStream_t st, const uint4* gdata, const uint32_t* values,
                            const uint32_t* ranges, const GsFrame& f, uint32_t* rgba8, float* rgbf, GsControl* ctl, uint32_t dbg, uint32_t id_mask) {
-#define GS_WG(E) hipLaunchKernelGGL((gs_blend_kernel<TS, E>), grid, dim3(TS * TS), 0, st, gdata, values, ranges, f, rgba8, rgbf, ctl, dbg, id_mask)
-#define GS_WG_AUX(E) hipLaunchKernelGGL((gs_blend_kernel<TS, E, true, GsAuxPlanes>), grid, dim3(TS * TS), 0, st, gdata, values, ranges, f, rgba8, \
-                                        rgbf, ctl, dbg, id_mask, ap)
-    if (aux) { if (exact) GS_WG_AUX(true); else GS_WG_AUX(false); }
-    else { if (exact) GS_WG(true); else GS_WG(false); }
-#undef GS_WG
-#undef GS_WG_AUX
+    gs_dispatch([&](auto E, auto A) {
+        auto go = [&](auto kernel, auto... planes) {
+            hipLaunchKernelGGL(kernel, grid, dim3(TS * TS), 0, st, gdata, values, ranges, f, rgba8, rgbf, ctl, dbg, id_mask, planes...);
+        };
+        if constexpr (A.value) go(gs_blend_kernel<TS, E.value, true, GsAuxPlanes>, ap);
+        else go(gs_blend_kernel<TS, E.value>);
+    }, exact, aux);
 }
 template <int TS>
 static void launch_quad_t(bool exact, bool masked, bool aux, GsAuxPlanes ap, uint32_t nblk, uint32_t pad, hipStream_t st, const uint4* g,
                           const uint32_t* values, const uint32_t* ranges, const GsFrame& f, uint32_t* rgba8, float* rgbf, GsControl* ctl,
                           uint32_t* tile_depth, uint32_t dbg, uint32_t* prof) {
-#define GS_QUAD(E, M) hipLaunchKernelGGL((gs_blend_quad_kernel<E, TS, M>), dim3(nblk), dim3(64), pad, st, g, values, ranges, f, rgba8, rgbf, ctl, tile_depth, dbg, prof)
-#define GS_QUAD_AUX(E, M) hipLaunchKernelGGL((gs_blend_quad_kernel<E, TS, M, true, GsAuxPlanes>), dim3(nblk), dim3(64), pad, st, g, values, ranges, f, \
-                                             rgba8, rgbf, ctl, tile_depth, dbg, prof, ap)
-    if (aux) {
-        if (exact) { if (masked) GS_QUAD_AUX(true, true); else GS_QUAD_AUX(true, false); }
-        else { if (masked) GS_QUAD_AUX(false, true); else GS_QUAD_AUX(false, false); }
-    } else {
-        if (exact) { if (masked) GS_QUAD(true, true); else GS_QUAD(true, false); }
-        else { if (masked) GS_QUAD(false, true); else GS_QUAD(false, false); }
-    }
-#undef GS_QUAD
-#undef GS_QUAD_AUX
+    gs_dispatch([&](auto E, auto M, auto A) {
+        auto go = [&](auto kernel, auto... planes) {
+            hipLaunchKernelGGL(kernel, dim3(nblk), dim3(64), pad, st, g, values, ranges, f, rgba8, rgbf, ctl, tile_depth, dbg, prof, planes...);
+        };
+        if constexpr (A.value) go(gs_blend_quad_kernel<E.value, TS, M.value, true, GsAuxPlanes>, ap);
+        else go(gs_blend_quad_kernel<E.value, TS, M.value>);
+    }, exact, masked, aux);
 }
 // Returns -1 for an unsupported tile size, -2 for aux planes requested without both of them (nothing is launched), 4 when the
 // quadrant kernel ran (gs_stats.num_processed is then the sum of tile_depth[], the per-tile maximum over its four independent

@@ -62,10 +62,8 @@ __global__ __launch_bounds__(64) void gs_pick_kernel(const uint4* __restrict__ g
     // the slab's pixels, as the blend owns them (the host has rejected pixels outside the canvas)
     if (xy.x >= f.px0 && xy.x - f.px0 < f.slab_w && xy.y < f.height) {
         const uint32_t tile = xy.x / f.tile_size + (xy.y / f.tile_size) * f.ntx; // canvas tile index, as every blend kernel forms it
-        const uint32_t start = tile > 0 ? ranges[tile - 1] : 0u;
-        uint32_t end = ranges[tile];
-        if (end > f.capacity) end = f.capacity;
-        if (end < start) end = start;
+        const uint2 run = gs_tile_range(ranges, tile, f.capacity);
+        const uint32_t start = run.x, end = run.y < start ? start : run.y;
         list_length = end - start;
         const float pxf = (float)xy.x, pyf = (float)xy.y;
         const float Wf = (float)f.width, Hf = (float)f.height;
@@ -74,11 +72,9 @@ __global__ __launch_bounds__(64) void gs_pick_kernel(const uint4* __restrict__ g
         bool settled = false;
         for (uint32_t b = start; b < end && !settled; b += 64u) {
             const GsPickRec nxt = gs_pick_fetch(gdata, values, b + 64u + lane, end, id_mask, f.n); // in flight while this chunk is resolved
-            // compute_tiles.wgsl:52-59, the expression tree of gs_blend_kernel<EXACT>
-            const float dx = cur.ux * Wf - pxf, dy = cur.uy * Hf - pyf;
-            const float t1 = cur.cx * dx * dx, t2 = cur.cz * dy * dy, t3 = cur.cy * dx * dy;
-            const float power = -0.5f * (t1 + t2) - t3;
-            const float alpha = wg_min(0.99f, cur.op * gs_exp(power));
+            // compute_tiles.wgsl:52-59, the head of gs_blend_exact
+            const float power = gs_blend_power(cur.cx, cur.cy, cur.cz, cur.ux * Wf - pxf, cur.uy * Hf - pyf);
+            const float alpha = gs_blend_alpha(cur.op, power);
             unsigned long long m = __ballot(cur.live && power <= 0.0f && alpha >= c255);
             while (m) {
                 const int l = __builtin_ctzll(m);
@@ -99,7 +95,7 @@ __global__ __launch_bounds__(64) void gs_pick_kernel(const uint4* __restrict__ g
                 // The blend kernels' exit.  Every later candidate has alpha >= c255, so fl(1 - alpha) <= fl(1 - c255) and
                 // fl(T fl(1 - alpha)) <= fl(T fl(1 - c255)) (rounding is monotonic, T > 0): once the right-hand side is below 1e-4
                 // no later entry can be accepted, T never changes again, and no field of the result depends on a rejected entry.
-                if (T * (1.0f - c255) < 0.0001f) { settled = true; break; }
+                if (gs_pixel_final<true>(T)) { settled = true; break; }
             }
             cur = nxt;
         }
