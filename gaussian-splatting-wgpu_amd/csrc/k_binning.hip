@@ -11,14 +11,14 @@
 // kernel that writes every tile exactly once (no per-frame memset of `ranges`).
 // All three are HBM-bound integer kernels: scan 8 B/gaussian, emit 24 B/visible + 8 B/entry,
 // ranges 4 B/entry + 4 B/tile.
-#include "gs_device.h"
+#include "gs_binning.h"
 
 // ------------------------------------------------------------------------------------------------
 // Exclusive scan, 4096 counts per workgroup, status granule = {flag:2, visible:30, sum:32} in one 8-byte
 // word: the count of visible gaussians rides along the same look-back (a separate atomic counter on one
 // hot word serialises at ~88 atomics/us on this chip).
 // ------------------------------------------------------------------------------------------------
-#define EMIT_CHUNK_SHIFT 10
+#define EMIT_CHUNK_SHIFT GS_EMIT_CHUNK_SHIFT // (the chunk table of k_gsort.hip is cut in the same chunks)
 #define EMIT_CHUNK (1u << EMIT_CHUNK_SHIFT) // output slots one wave emits at a time in the balanced emission
 #define SCAN_ITEMS 24 // 24 576 counts per workgroup: 6.1 M gaussians are 249 workgroups, one residency round of the 256 CUs
 #define SCAN_THREADS 1024 // 16 waves: the look-back chain advances 64 workgroups per step, so fewer, larger workgroups finish sooner

@@ -34,21 +34,18 @@
 // bucket, read from the saturated in-chunk prefix P: if P at the bucket's END is saturated the new base is saturated as well,
 // because the base of a bucket already counts every earlier bucket of this chunk (base >= P at the bucket's START), so
 // base + (end - start) >= P(end) >= 2^32 - 1; otherwise both P values are exact.
-#include "gs_device.h"
+#include "gs_binning.h"
 
 #define GC_ITEMS 8
 #define GC_THREADS 256
 #define GC (GC_THREADS * GC_ITEMS) // gaussian indices per chunk
 #define GBINS 1024                 // bucket = u32(min(50 depth, 999)) < 1000 (write_tile_ids.wgsl:31)
-#define GS_EMIT_CHUNK_SHIFT 10     // = EMIT_CHUNK_SHIFT of k_binning.hip
 #ifndef GS_GSORT_RUNS_Q
 #define GS_GSORT_RUNS_Q 4          // runs = persistent grid * Q / 4 (swept 2 / 3 / 4 / 8: profiles/README.md)
 #endif
 // The (bucket, run) table is stored [bucket / 8][run][bucket % 8]: the 1024 entries a run's workgroup writes (hist) or
 // reads (scatter) are 128 whole 64-byte sectors instead of 1024 partial ones, and a bucket's row is still a strided stream.
 __device__ __forceinline__ uint64_t m_index(uint32_t b, uint32_t col, uint32_t ncol) { return ((uint64_t)(b >> 3) * ncol + col) * 8u + (b & 7u); }
-
-__device__ __forceinline__ uint32_t sat32(unsigned long long v) { return v > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)v; }
 
 // One workgroup per run: chunks [run * cpr, min((run + 1) * cpr, NT)); the loads of chunk k + 1 are issued before the LDS
 // atomics of chunk k.
@@ -91,48 +88,6 @@ __global__ __launch_bounds__(GC_THREADS) void gs_gsort_hist_kernel(const uint32_
         const uint32_t b = tid * (GBINS / GC_THREADS) + i;
         M[m_index(b, run, ncol)] = make_uint2(s_cnt[b], sat32(s_sum[b]));
     }
-}
-
-// exclusive scan of (count, quantity) over a workgroup: each thread holds the sum of its consecutive elements in v; the
-// quantity channel is 64 bits wide inside the scan and saturates where it is stored
-struct GsPair { uint32_t x; unsigned long long y; };
-__device__ __forceinline__ GsPair block_excl2(GsPair v, uint32_t tid, GsPair* s_w /*[GC_THREADS / 64]*/, GsPair& total) {
-    const uint32_t lane = tid & 63, w = tid >> 6;
-    const uint32_t ix = wave_incl_scan(v.x, lane);
-    const unsigned long long iy = wave_incl_scan64(v.y, lane);
-    if (lane == 63) { s_w[w].x = ix; s_w[w].y = iy; }
-    __syncthreads();
-    GsPair base; base.x = 0u; base.y = 0ull;
-    total.x = 0u; total.y = 0ull;
-#pragma unroll
-    for (int k = 0; k < GC_THREADS / 64; ++k) {
-        const GsPair t = s_w[k];
-        if (k < (int)w) { base.x += t.x; base.y += t.y; }
-        total.x += t.x; total.y += t.y;
-    }
-    __syncthreads();
-    GsPair r; r.x = base.x + ix - v.x; r.y = base.y + iy - v.y;
-    return r;
-}
-
-// The scans inside a chunk need 32 bits inside a wave (DPP adds, no LDS shuffles): bucket counts sum to <= 2048, a thread's
-// eight quantities to < 2^25 and 64 of those to < 2^31; only the sum over the four waves can need more (A = 64 bits there).
-template <typename A>
-__device__ __forceinline__ A block_excl_u32(uint32_t v, uint32_t tid, uint32_t* s_w /*[GC_THREADS / 64]*/, A& total) {
-    const uint32_t lane = tid & 63, w = tid >> 6;
-    const uint32_t iv = wave_incl_scan(v, lane);
-    if (lane == 63) s_w[w] = iv;
-    __syncthreads();
-    A base = 0;
-    total = 0;
-#pragma unroll
-    for (int k = 0; k < GC_THREADS / 64; ++k) {
-        const uint32_t t = s_w[k];
-        if (k < (int)w) base += t;
-        total += t;
-    }
-    __syncthreads();
-    return base + (iv - v);
 }
 
 // One workgroup of 1024 threads per 8 buckets (one 64-byte sector per run): thread (cl = t / 8, sub = t % 8) owns the runs
@@ -257,7 +212,7 @@ __global__ __launch_bounds__(GC_THREADS) void gs_gsort_scatter_kernel(const uint
 #pragma unroll
         for (uint32_t i = 0; i < BPT; ++i) { acc.x += t[i].x; acc.y += t[i].y; }
         GsPair total;
-        GsPair run = block_excl2(acc, tid, S.w2, total);
+        GsPair run = block_excl2<GC_THREADS / 64>(acc, tid, S.w2, total);
 #pragma unroll
         for (uint32_t i = 0; i < BPT; ++i) {
             S.base[tid * BPT + i] = make_uint2(run.x + mm[i].x, sat32(run.y + mm[i].y));
@@ -277,7 +232,7 @@ __global__ __launch_bounds__(GC_THREADS) void gs_gsort_scatter_kernel(const uint
             S.u.zero[w * (GBINS / 8) + 64 + lane] = make_uint4(0u, 0u, 0u, 0u);
         }
         // ---- rank the visible gaussians by bucket where they are: (item, lane) of wave w IS the index order ----
-        // peers = visible lanes holding the same bucket (10 ballots); rank = the wave's running count + peers below: stable
+        // peers = visible lanes holding the same bucket (10 ballots)
         uint32_t rank2[GC_ITEMS / 2];
 #pragma unroll
         for (int j = 0; j < GC_ITEMS; ++j) {
@@ -286,7 +241,7 @@ __global__ __launch_bounds__(GC_THREADS) void gs_gsort_scatter_kernel(const uint
             uint32_t r = 0;
             if (vis) { // (uniform over the wave)
                 const uint32_t d = wv[j] >> GS_COUNT_BITS;
-                uint32_t plo = (uint32_t)vis, phi = (uint32_t)(vis >> 32);
+                uint32_t plo = (uint32_t)vis, phi = (uint32_t)(vis >> 32); // (the ballots of wave_rank in place: 128 instructions more as a call)
 #pragma unroll
                 for (int b = 0; b < 10; ++b) {
                     const uint32_t bit = (d >> b) & 1u;
@@ -295,16 +250,9 @@ __global__ __launch_bounds__(GC_THREADS) void gs_gsort_scatter_kernel(const uint
                     plo &= (uint32_t)bal ^ inv;
                     phi &= (uint32_t)(bal >> 32) ^ inv;
                 }
-                const uint32_t below = __popc(plo & (uint32_t)lt_mask) + __popc(phi & (uint32_t)(lt_mask >> 32));
-                const uint32_t cnt = __popc(plo) + __popc(phi);
-                const uint32_t pre = S.u.whist[w][d];
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); // every peer has read `pre` before the leader's store (one wave, in-order LDS)
-                if (wv[j] && below == 0) S.u.whist[w][d] = (unsigned short)(pre + cnt);
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                r = pre + below; // < 2048
+                r = wave_rank_peers(S.u.whist[w], d, plo, phi, wv[j] != 0u, lt_mask); // < 2048
             }
-            if (j & 1) rank2[j >> 1] |= r << 16;
-            else rank2[j >> 1] = r;
+            rank2_put(rank2, j, r);
         }
         __syncthreads();
         // ---- per-wave counts -> exclusive across waves; bucket starts inside the chunk; the chunk's visible gaussians ----
@@ -320,7 +268,7 @@ __global__ __launch_bounds__(GC_THREADS) void gs_gsort_scatter_kernel(const uint
                 tot[i] = run;
                 acc += run;
             }
-            uint32_t run = block_excl_u32<uint32_t>(acc, tid, S.w1, nc);
+            uint32_t run = block_excl_u32<GC_THREADS / 64, uint32_t>(acc, tid, S.w1, nc);
 #pragma unroll
             for (uint32_t i = 0; i < BPT; ++i) { S.binstart[tid * BPT + i] = (unsigned short)run; run += tot[i]; }
         }
@@ -333,7 +281,7 @@ __global__ __launch_bounds__(GC_THREADS) void gs_gsort_scatter_kernel(const uint
         for (int j = 0; j < GC_ITEMS; ++j) {
             if (wv[j]) {
                 const uint32_t d = wv[j] >> GS_COUNT_BITS;
-                const uint32_t r = (j & 1) ? (rank2[j >> 1] >> 16) : (rank2[j >> 1] & 0xFFFFu);
+                const uint32_t r = rank2_get(rank2, j);
                 const uint32_t pos = (uint32_t)S.binstart[d] + (uint32_t)S.u.whist[w][d] + r;
                 S.id[pos] = (unsigned short)(w * (64 * GC_ITEMS) + j * 64 + lane);
                 S.word[pos] = wv[j];
@@ -351,7 +299,7 @@ __global__ __launch_bounds__(GC_THREADS) void gs_gsort_scatter_kernel(const uint
                 acc += c[j];
             }
             unsigned long long total;
-            unsigned long long run = block_excl_u32<unsigned long long>(acc, tid, S.w1, total);
+            unsigned long long run = block_excl_u32<GC_THREADS / 64, unsigned long long>(acc, tid, S.w1, total);
 #pragma unroll
             for (int j = 0; j < GC_ITEMS; ++j) { S.u.P[tid * GC_ITEMS + j] = sat32(run); run += c[j]; }
             if (tid == 0) S.ptot = sat32(total);

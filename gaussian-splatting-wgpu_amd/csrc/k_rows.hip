@@ -24,7 +24,7 @@
 // Order inside a tile = item order inside the tile row = depth order of the gaussians = (bucket, index): the reference's.
 // Every kernel is integer work on 12-byte items and 4-byte values; algorithmic bytes per frame (R items, I instances):
 // 12 R read + 12 R written by the row sort, 12 R read twice by count / expand, 4 I written.
-#include "gs_device.h"
+#include "gs_binning.h"
 #include "gs_tight.h"
 
 typedef uint32_t gs_item3 __attribute__((ext_vector_type(3), aligned(4)));
@@ -37,10 +37,6 @@ typedef uint32_t gs_item3 __attribute__((ext_vector_type(3), aligned(4)));
 #endif
 #define RA_THREADS (RA_WAVES * 64)
 #define RA_TILE (RA_THREADS * RA_ITEMS) // 4096 slots per tile (8 waves x 8 items per lane): 48 KB of LDS for the reorder, three workgroups (24 waves) per CU
-#define RA_AGG (1u << 30)
-#define RA_PREFIX (2u << 30)
-#define RA_FLAGS (3u << 30)
-#define RA_VALUE (~RA_FLAGS)
 
 #ifndef RB_CH
 #define RB_CH 512u   // items per chunk
@@ -79,10 +75,9 @@ struct RowSortShared {
 __global__ __launch_bounds__(RA_THREADS) void gs_rows_sort_kernel(const uint32_t* __restrict__ arena, const uint4* __restrict__ grec,
                                                                   const uint32_t* __restrict__ chunk_table, uint32_t* __restrict__ rows_out,
                                                                   GsControl* ctl, uint32_t* __restrict__ status, uint32_t row_cap, uint32_t ndig) {
-    // ndig: tile rows of the canvas = digits that exist; holes take digit `hole` (127 when the rows fit 7 bits: one ballot less)
+    // ndig: tile rows of the canvas = digits that exist
     __shared__ RowSortShared sh;
-    const uint32_t hole = ndig < 128u ? 127u : 255u;
-    const int nbits = ndig < 128u ? 7 : 8;
+    const GsDigits dg = gs_digits(ndig);
     const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
     uint32_t n = ctl->num_slots;
@@ -91,11 +86,9 @@ __global__ __launch_bounds__(RA_THREADS) void gs_rows_sort_kernel(const uint32_t
     const uint32_t nvis = ctl->num_visible;
     {   // first slot of every tile row's run: exclusive scan of the digit histogram (every workgroup for itself)
         const uint32_t c = tid < 256u ? gs_rowhist(ctl, tid) : 0u;
-        const uint32_t incl = wave_incl_scan(c, lane);
-        if (lane == 63) sh.wsum[w] = incl;
+        const uint32_t incl = wave_scan_publish(c, lane, w, sh.wsum);
         __syncthreads();
-        uint32_t b = 0;
-        for (uint32_t k = 0; k < w; ++k) b += sh.wsum[k];
+        const uint32_t b = waves_before<uint32_t>(sh.wsum, w);
         if (tid < 256u) sh.dbase[tid] = b + incl - c;
         __syncthreads();
     }
@@ -142,9 +135,7 @@ __global__ __launch_bounds__(RA_THREADS) void gs_rows_sort_kernel(const uint32_t
 #pragma unroll
         for (int j = 0; j < RA_ITEMS; ++j) {
             const uint32_t sp = w * (64 * RA_ITEMS) + j * 64 + lane, slot = s0 + sp;
-            uint32_t m = wave_incl_max((uint32_t)sh.u.g.mark[sp]);
-            m = m > carry ? m : carry;
-            carry = (uint32_t)__builtin_amdgcn_readlane((int)m, 63);
+            const uint32_t m = owner_walk((uint32_t)sh.u.g.mark[sp], carry);
             ix[j] = GS_ROW_HOLE; iy[j] = 0u; iz[j] = 0u;
             if (slot < n) {
                 const uint32_t k = m - 1u;
@@ -160,18 +151,16 @@ __global__ __launch_bounds__(RA_THREADS) void gs_rows_sort_kernel(const uint32_t
         __syncthreads();
         // holes (and the slots past the end) take a digit no tile row has: they rank last and are not stored
 #pragma unroll
-        for (int j = 0; j < RA_ITEMS; ++j) atomicAdd(&sh.tot[ix[j] == GS_ROW_HOLE ? hole : (iy[j] & 0xFFu)], 1u);
+        for (int j = 0; j < RA_ITEMS; ++j) atomicAdd(&sh.tot[ix[j] == GS_ROW_HOLE ? dg.hole : (iy[j] & 0xFFu)], 1u);
         __syncthreads();
-        // the tile's digit counts are published BEFORE the ranking: successors rarely meet an unpublished word
-        if (tid < ndig) st_agent(status + (uint64_t)tile * 256 + tid, (tile == 0 ? RA_PREFIX : RA_AGG) | sh.tot[tid]);
-        // rank inside the wave: peers = lanes holding the same digit (8 ballots), order = (item, lane)
+        if (tid < ndig) st_agent(status + (uint64_t)tile * 256 + tid, (tile == 0 ? GS_LB_PREFIX : GS_LB_AGG) | sh.tot[tid]); // early aggregate
 #pragma unroll
         for (int j = 0; j < RA_ITEMS; ++j) {
-            const uint32_t d = ix[j] == GS_ROW_HOLE ? hole : (iy[j] & 0xFFu);
-            uint32_t plo = 0xFFFFFFFFu, phi = 0xFFFFFFFFu;
+            const uint32_t d = ix[j] == GS_ROW_HOLE ? dg.hole : (iy[j] & 0xFFu);
+            uint32_t plo = 0xFFFFFFFFu, phi = 0xFFFFFFFFu; // (the ballots of wave_rank in place: their number is a run-time 7 or 8)
 #pragma unroll
             for (int b = 0; b < 8; ++b) {
-                if (b < nbits) {
+                if (b < dg.nbits) {
                     const uint32_t bit = (d >> b) & 1u;
                     const unsigned long long bal = __ballot(bit != 0u);
                     const uint32_t inv = bit - 1u;
@@ -182,12 +171,11 @@ __global__ __launch_bounds__(RA_THREADS) void gs_rows_sort_kernel(const uint32_t
             const uint32_t below = __popc(plo & (uint32_t)lt_mask) + __popc(phi & (uint32_t)(lt_mask >> 32));
             const uint32_t cnt = __popc(plo) + __popc(phi);
             const uint32_t pre = sh.hist[w][d];
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); // every peer has read `pre` before the leader's store (one wave, in-order LDS)
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); // (wave_rank_peers in place: as a call the kernel's code differs)
             if (below == 0) sh.hist[w][d] = pre + cnt;
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             const uint32_t r = pre + below;
-            if (j & 1) rank2[j >> 1] |= r << 16;
-            else rank2[j >> 1] = r;
+            rank2_put(rank2, j, r);
         }
         __syncthreads();
         // thread d < 256: counts of digit d per wave -> exclusive offsets across waves, tile total; look-back over the predecessors
@@ -195,47 +183,44 @@ __global__ __launch_bounds__(RA_THREADS) void gs_rows_sort_kernel(const uint32_t
         uint32_t cw[RA_WAVES], total = 0, excl = 0, incl = 0;
         if (tid < 256u) {
 #pragma unroll
-            for (int k = 0; k < RA_WAVES; ++k) { cw[k] = sh.hist[k][tid]; total += cw[k]; }
-            incl = wave_incl_scan(total, lane);
-            if (lane == 63) sh.wsum[w] = incl;
-            if (tile > 0 && tid < ndig) {
+            for (int k = 0; k < RA_WAVES; ++k) { cw[k] = sh.hist[k][tid]; total += cw[k]; } // (wave_counts in place: as a call the schedule differs)
+            incl = wave_scan_publish(total, lane, w, sh.wsum);
+            if (tile > 0 && tid < ndig) { // the look-back of gs_binning.h (the same walk as in k_sort.hip)
                 constexpr int LB = 8;
                 bool found = false;
                 for (int t = (int)tile - 1; t >= 0 && !found; t -= LB) {
                     uint32_t sv[LB];
 #pragma unroll
-                    for (int k = 0; k < LB; ++k) sv[k] = (t - k >= 0) ? ld_agent(status + (uint64_t)(t - k) * 256 + tid) : RA_PREFIX;
+                    for (int k = 0; k < LB; ++k) sv[k] = (t - k >= 0) ? ld_agent(status + (uint64_t)(t - k) * 256 + tid) : GS_LB_PREFIX;
 #pragma unroll
                     for (int k = 0; k < LB; ++k) {
                         if (found) break;
                         uint32_t v = sv[k], spins = 0;
-                        while ((v & RA_FLAGS) == 0 && ++spins < GS_SPIN_LIMIT) { // not published yet: poll this one word
+                        while ((v & GS_LB_FLAGS) == 0 && ++spins < GS_SPIN_LIMIT) {
                             __builtin_amdgcn_s_sleep(1);
                             v = ld_agent(status + (uint64_t)(t - k) * 256 + tid);
                         }
-                        if ((v & RA_FLAGS) == 0) { ctl->fault = 1u; found = true; break; }
-                        excl += v & RA_VALUE;
-                        if ((v & RA_FLAGS) == RA_PREFIX) found = true;
+                        if ((v & GS_LB_FLAGS) == 0) { ctl->fault = 1u; found = true; break; }
+                        excl += v & GS_LB_VALUE;
+                        if ((v & GS_LB_FLAGS) == GS_LB_PREFIX) found = true;
                     }
                 }
-                st_agent(status + (uint64_t)tile * 256 + tid, RA_PREFIX | ((excl + total) & RA_VALUE));
+                st_agent(status + (uint64_t)tile * 256 + tid, GS_LB_PREFIX | ((excl + total) & GS_LB_VALUE));
             }
         }
         __syncthreads();
         if (tid < 256u) {
-            uint32_t wv = 0;
-            for (uint32_t k = 0; k < w; ++k) wv += sh.wsum[k];
-            uint32_t run = wv + incl - total; // first position of digit `tid` in the tile's sorted order
-            if (tid == hole) sh.nvalid = run; // the holes start here (no digit above `hole` occurs)
+            uint32_t run = waves_before<uint32_t>(sh.wsum, w) + incl - total; // first position of digit `tid` in the tile's sorted order
+            if (tid == dg.hole) sh.nvalid = run; // the holes start here (no digit above `hole` occurs)
             sh.gbase[tid] = sh.dbase[tid] + excl - run;
 #pragma unroll
-            for (int k = 0; k < RA_WAVES; ++k) { sh.hist[k][tid] = run; run += cw[k]; }
+            for (int k = 0; k < RA_WAVES; ++k) { sh.hist[k][tid] = run; run += cw[k]; } // (wave_starts in place: as above)
         }
         __syncthreads();
 #pragma unroll
         for (int j = 0; j < RA_ITEMS; ++j) {
-            const uint32_t d = ix[j] == GS_ROW_HOLE ? hole : (iy[j] & 0xFFu);
-            const uint32_t r = (j & 1) ? (rank2[j >> 1] >> 16) : (rank2[j >> 1] & 0xFFFFu);
+            const uint32_t d = ix[j] == GS_ROW_HOLE ? dg.hole : (iy[j] & 0xFFu);
+            const uint32_t r = rank2_get(rank2, j);
             const uint32_t pos = sh.hist[w][d] + r;
             sh.u.it[pos * 3 + 0] = ix[j];
             sh.u.it[pos * 3 + 1] = iy[j];
@@ -276,12 +261,11 @@ __device__ __forceinline__ void row_tables(RowTables& T, const GsControl* ctl, u
     const bool on = tid < 256u;
     const uint32_t c = on ? gs_rowhist(ctl, tid) : 0u;
     const unsigned long long ic = wave_incl_scan64(c, lane); // (64 bits: the sum of the histogram can pass 2^32 before the clamp)
-    if (on && lane == 63) { T.w4[w] = (uint32_t)(ic > 0xFFFFFFFFull ? 0xFFFFFFFFull : ic); }
+    if (on && lane == 63) T.w4[w] = sat32(ic);
     __syncthreads();
     uint32_t i0 = 0, cc = 0;
     if (on) {
-        unsigned long long b = ic - c;
-        for (uint32_t k = 0; k < w; ++k) b += T.w4[k];
+        const unsigned long long b = waves_before<unsigned long long>(T.w4, w, ic - c);
         const unsigned long long e = b + c;
         i0 = b > row_cap ? row_cap : (uint32_t)b;
         const uint32_t i1 = e > row_cap ? row_cap : (uint32_t)e;
@@ -294,8 +278,7 @@ __device__ __forceinline__ void row_tables(RowTables& T, const GsControl* ctl, u
     if (on && lane == 63) T.w4[4 + w] = ih;
     __syncthreads();
     if (on) {
-        uint32_t bh = 0;
-        for (uint32_t k = 0; k < w; ++k) bh += T.w4[4 + k];
+        const uint32_t bh = waves_before<uint32_t>(T.w4 + 4, w);
         T.cbase[tid] = bh + ih - ch;
         if (tid == 255u) T.cbase[256] = bh + ih;
     }
@@ -314,6 +297,10 @@ __device__ __forceinline__ uint32_t row_of_chunk(const RowTables& T, uint32_t c)
     for (int k = 0; k < 4; ++k) r += (uint32_t)__popcll(__ballot(v[k] <= c && (lane + 64u * k) != 0u));
     return r;
 }
+__device__ __forceinline__ uint2 chunk_items(const RowTables& T, uint32_t r, uint32_t c) { // items [x, y) of chunk c of tile row r
+    const uint32_t i0 = T.ibase[r] + (c - T.cbase[r]) * RB_CH;
+    return make_uint2(i0, (i0 + RB_CH < T.ibase[r + 1]) ? i0 + RB_CH : T.ibase[r + 1]);
+}
 
 __global__ __launch_bounds__(256) void gs_rows_count_kernel(const uint32_t* __restrict__ rows, const GsControl* ctl, uint32_t* __restrict__ M3,
                                                             uint32_t chunk_cap, uint32_t row_cap) {
@@ -325,9 +312,8 @@ __global__ __launch_bounds__(256) void gs_rows_count_kernel(const uint32_t* __re
     uint32_t nch = T.cbase[256];
     if (nch > chunk_cap) nch = chunk_cap;
     for (uint32_t c = blockIdx.x; c < nch; c += gridDim.x) {
-        const uint32_t r = row_of_chunk(T, c);
-        const uint32_t i0 = T.ibase[r] + (c - T.cbase[r]) * RB_CH;
-        const uint32_t i1 = (i0 + RB_CH < T.ibase[r + 1]) ? i0 + RB_CH : T.ibase[r + 1];
+        const uint2 ext = chunk_items(T, row_of_chunk(T, c), c);
+        const uint32_t i0 = ext.x, i1 = ext.y;
         s_diff[tid] = 0;
         if (tid == 0) s_diff[256] = 0;
         __syncthreads();
@@ -344,12 +330,10 @@ __global__ __launch_bounds__(256) void gs_rows_count_kernel(const uint32_t* __re
         __syncthreads();
         // instances of column `tid` = inclusive prefix of the difference array
         const uint32_t v = (uint32_t)s_diff[tid];
-        const uint32_t incl = wave_incl_scan(v, lane);
+        const uint32_t incl = wave_incl_scan(v, lane); // (wave_scan_publish, written out: one instruction more as a call)
         if (lane == 63) s_w[w] = incl;
         __syncthreads();
-        uint32_t b = 0;
-        for (uint32_t k = 0; k < w; ++k) b += s_w[k];
-        M3[(uint64_t)c * 256u + tid] = b + incl;
+        M3[(uint64_t)c * 256u + tid] = waves_before<uint32_t>(s_w, w) + incl;
         __syncthreads();
     }
 }
@@ -388,31 +372,26 @@ __global__ __launch_bounds__(1024) void gs_rows_scan_kernel(const GsControl* ctl
         for (int k = 0; k < 8; ++k) v[k] = (j + k < j1) ? M3[(uint64_t)(j + k) * 256u + c] : 0u;
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-            if (j + k < j1) M3[(uint64_t)(j + k) * 256u + c] = run > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)run;
+            if (j + k < j1) M3[(uint64_t)(j + k) * 256u + c] = sat32(run);
             run += v[k];
         }
     }
     // exclusive scan of the tile totals over the row's columns (threads of part 0)
     if (p == 0) {
         const uint32_t lane = tid & 63, w = tid >> 6;
-        unsigned long long incl = tot;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t lo = __shfl_up((uint32_t)incl, d, 64), hi = __shfl_up((uint32_t)(incl >> 32), d, 64);
-            if ((int)lane >= d) incl += ((unsigned long long)hi << 32) | lo;
-        }
+        const unsigned long long incl = wave_incl_scan64(tot, lane);
         if (lane == 63) s_w[w] = incl;
         s_ex[c] = incl - tot; // in-wave exclusive
     }
     __syncthreads();
     if (p == 0) {
         const uint32_t w = tid >> 6;
-        unsigned long long b = 0, all = 0;
+        unsigned long long b = 0, all = 0; // (waves_before_total in place: as a call the schedule differs)
 #pragma unroll
         for (int k = 0; k < 4; ++k) { if (k < (int)w) b += s_w[k]; all += s_w[k]; }
         const unsigned long long ex = b + s_ex[c];
-        tileoff[r * 256u + c] = ex > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)ex;
-        if (c == 0) rowtot[r] = all > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)all;
+        tileoff[r * 256u + c] = sat32(ex);
+        if (c == 0) rowtot[r] = sat32(all);
     }
 }
 
@@ -443,25 +422,17 @@ __global__ __launch_bounds__(256) void gs_rows_expand_kernel(const uint32_t* __r
     const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
     const uint32_t ns = f.tile_size >= 16u ? 2u : 1u;
-    const uint32_t hole = f.ntx < 128u ? 127u : 255u; // the digit of the slots past a sub-batch's end: no tile column has it
-    const int nbits = f.ntx < 128u ? 7 : 8;
+    const GsDigits dg = gs_digits(f.ntx); // dg.hole: the digit of the slots past a sub-batch's end
     row_tables(S.T, ctl, row_cap, tid);
     {   // first instance of every tile row
         const uint32_t v = tid < f.nty ? rowtot[tid] : 0u;
-        unsigned long long incl = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t lo = __shfl_up((uint32_t)incl, d, 64), hi = __shfl_up((uint32_t)(incl >> 32), d, 64);
-            if ((int)lane >= d) incl += ((unsigned long long)hi << 32) | lo;
-        }
+        const unsigned long long incl = wave_incl_scan64(v, lane);
         __shared__ unsigned long long s_r[4];
         if (lane == 63) s_r[w] = incl;
         __syncthreads();
-        unsigned long long b = 0;
-        for (uint32_t k = 0; k < w; ++k) b += s_r[k];
-        const unsigned long long ex = b + incl - v;
-        S.rbase[tid] = ex > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)ex;
-        if (tid == 255u) S.rbase[256] = (b + incl) > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)(b + incl);
+        const unsigned long long b = waves_before<unsigned long long>(s_r, w);
+        S.rbase[tid] = sat32(b + incl - v);
+        if (tid == 255u) S.rbase[256] = sat32(b + incl);
         __syncthreads();
     }
     if (blockIdx.x == 0 && tid == 0) { // the frame's instance count; its flags and sizes go to the sticky words and the host's report
@@ -476,7 +447,7 @@ __global__ __launch_bounds__(256) void gs_rows_expand_kernel(const uint32_t* __r
         if (tid < f.ntx) {
             const uint32_t endoff = (tid + 1u < 256u) ? tileoff[r * 256u + tid + 1u] : rowtot[r];
             const unsigned long long e = (unsigned long long)S.rbase[r] + endoff;
-            ranges[r * f.ntx + tid] = e > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)e;
+            ranges[r * f.ntx + tid] = sat32(e);
         }
     }
     uint32_t nch = S.T.cbase[256];
@@ -487,9 +458,9 @@ __global__ __launch_bounds__(256) void gs_rows_expand_kernel(const uint32_t* __r
     uint32_t n_r = 0, n_ni = 0, n_tstart = 0, n_done = 0;
     auto prefetch = [&](uint32_t c) {
         n_r = row_of_chunk(S.T, c);
-        const uint32_t i0 = S.T.ibase[n_r] + (c - S.T.cbase[n_r]) * RB_CH;
-        const uint32_t i1 = (i0 + RB_CH < S.T.ibase[n_r + 1]) ? i0 + RB_CH : S.T.ibase[n_r + 1];
-        n_ni = i1 - i0;
+        const uint2 ext = chunk_items(S.T, n_r, c);
+        const uint32_t i0 = ext.x;
+        n_ni = ext.y - i0;
 #pragma unroll
         for (int k = 0; k < (int)RB_IT; ++k) {
             const uint32_t e = tid * RB_IT + k;
@@ -517,8 +488,8 @@ __global__ __launch_bounds__(256) void gs_rows_expand_kernel(const uint32_t* __r
         uint32_t done = n_done;           // ... + what the row's earlier chunks put there
         if (c + gridDim.x < nch) prefetch(c + gridDim.x);
         {
-            const uint32_t incl = wave_incl_scan(lsum, lane);
-            if (lane == 63) S.wsum[w] = incl;
+            const uint32_t incl = wave_incl_scan(lsum, lane); // (wave_scan_publish / waves_before_total in place, here and twice below:
+            if (lane == 63) S.wsum[w] = incl;                 // as calls they change the kernel's schedule or add 1 to 3 instructions)
             __syncthreads();
             uint32_t b = 0, all = 0;
 #pragma unroll
@@ -589,10 +560,8 @@ __global__ __launch_bounds__(256) void gs_rows_expand_kernel(const uint32_t* __r
             for (int j = 0; j < (int)RB_PER; ++j) {
                 if ((uint32_t)j >= jn) break;
                 const uint32_t sp = w * RB_WSL + j * 64u + lane, x = s0 + sp;
-                uint32_t m = wave_incl_max((uint32_t)S.x.e.mark[sp]);
-                m = m > carry ? m : carry;
-                carry = (uint32_t)__builtin_amdgcn_readlane((int)m, 63);
-                uint32_t d = hole;
+                const uint32_t m = owner_walk((uint32_t)S.x.e.mark[sp], carry);
+                uint32_t d = dg.hole;
                 val[j] = 0u;
                 if (x < ninst) {
                     const uint32_t e = m - 1u;
@@ -607,10 +576,10 @@ __global__ __launch_bounds__(256) void gs_rows_expand_kernel(const uint32_t* __r
             for (int j = 0; j < (int)RB_PER; ++j) {
                 if ((uint32_t)j >= jn) break;
                 const uint32_t d = (col4[j >> 2] >> (8 * (j & 3))) & 0xFFu;
-                uint32_t plo = 0xFFFFFFFFu, phi = 0xFFFFFFFFu;
+                uint32_t plo = 0xFFFFFFFFu, phi = 0xFFFFFFFFu; // (the ballots of wave_rank in place: their number is a run-time 7 or 8)
 #pragma unroll
                 for (int b = 0; b < 8; ++b) {
-                    if (b < nbits) {
+                    if (b < dg.nbits) {
                         const uint32_t bit = (d >> b) & 1u;
                         const unsigned long long bal = __ballot(bit != 0u);
                         const uint32_t inv = bit - 1u;
@@ -621,19 +590,18 @@ __global__ __launch_bounds__(256) void gs_rows_expand_kernel(const uint32_t* __r
                 const uint32_t below = __popc(plo & (uint32_t)lt_mask) + __popc(phi & (uint32_t)(lt_mask >> 32));
                 const uint32_t cnt = __popc(plo) + __popc(phi);
                 const uint32_t pre = S.hist[w][d];
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); // (wave_rank_peers in place: one instruction more as a call)
                 if (below == 0) S.hist[w][d] = pre + cnt;
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
                 const uint32_t rr = pre + below;
-                if (j & 1) rank2[j >> 1] |= rr << 16;
-                else rank2[j >> 1] = rr;
+                rank2_put(rank2, j, rr);
             }
             __syncthreads(); // (also: every wave is done with P / mark, which the sorted values overwrite below)
             // ---- thread = column: exclusive offsets across waves, start of the column's run in the sub-batch's sorted order ----
             {
                 uint32_t cw[4], total = 0;
 #pragma unroll
-                for (int k = 0; k < 4; ++k) { cw[k] = S.hist[k][tid]; total += cw[k]; }
+                for (int k = 0; k < 4; ++k) { cw[k] = S.hist[k][tid]; total += cw[k]; } // (wave_counts / wave_starts in place: as calls the schedule differs)
                 const uint32_t incl = wave_incl_scan(total, lane);
                 if (lane == 63) S.wsum[4 + w] = incl;
                 __syncthreads();
@@ -641,7 +609,7 @@ __global__ __launch_bounds__(256) void gs_rows_expand_kernel(const uint32_t* __r
 #pragma unroll
                 for (int k = 0; k < 4; ++k) if (k < (int)w) b += S.wsum[4 + k];
                 uint32_t run = b + incl - total;
-                if (tid == hole) S.nvalid = run;
+                if (tid == dg.hole) S.nvalid = run;
                 S.gbase[tid] = tstart + done - run; // (wraps are harmless: only gbase + position is used, and it is bounds-checked)
                 done += total;
 #pragma unroll
@@ -652,7 +620,7 @@ __global__ __launch_bounds__(256) void gs_rows_expand_kernel(const uint32_t* __r
             for (int j = 0; j < (int)RB_PER; ++j) {
                 if ((uint32_t)j >= jn) break;
                 const uint32_t d = (col4[j >> 2] >> (8 * (j & 3))) & 0xFFu;
-                const uint32_t rr = (j & 1) ? (rank2[j >> 1] >> 16) : (rank2[j >> 1] & 0xFFFFu);
+                const uint32_t rr = rank2_get(rank2, j);
                 const uint32_t pos = S.hist[w][d] + rr;
                 S.x.vals[pos] = val[j];
                 S.cols[pos] = (unsigned char)d;

@@ -15,16 +15,12 @@
 //   * keys are re-ordered through LDS before the global scatter so each digit's run leaves the
 //     workgroup as contiguous stores.
 // HBM-bound: histogram 4 B/key once, each sweep 8 B/key read + 8 B/key written.
-#include "gs_device.h"
+#include "gs_binning.h"
 
 #define RS_ITEMS 16
 #define RS_WAVES 8 // waves per workgroup: a tile is RS_WAVES * 64 * RS_ITEMS keys
 #define RS_THREADS (RS_WAVES * 64)
 #define RS_TILE (RS_THREADS * RS_ITEMS)
-#define RS_AGG (1u << 30)
-#define RS_PREFIX (2u << 30)
-#define RS_FLAGS (3u << 30)
-#define RS_VALUE (~RS_FLAGS)
 
 // Digit of pass `pass`: `bits` bits of the sort word, which is the key itself (mode 0) or the key's tile id
 // key/1000 (mode 1: the depth-ordered pipeline sorts instances by tile only, see gs_frame.hip).
@@ -103,9 +99,7 @@ __device__ __forceinline__ void sweep_tile(SweepShared& sh, const KT* __restrict
         else key[j] = (wbase + j * 64 < valid) ? kp[j * 64] : 0xFFFFFFFFu; // pads sort last and are never stored
     }
     for (uint32_t k = lane; k < 256; k += 64) sh.hist[w][k] = 0;
-    // Early aggregate: the tile's digit counts are cheap (16 LDS atomics per thread) next to the ranking below, and they
-    // are all a successor needs from this tile.  Publishing them BEFORE the ranking puts the ranking time between "my
-    // aggregate is visible" and "I look at my predecessors'", so the look-back rarely finds an unpublished word.
+    // early aggregate (gs_binning.h): the tile's digit counts are cheap (16 LDS atomics per thread) next to the ranking below
     if (tid < 256u) sh.tot[tid] = 0u;
     __syncthreads();
 #pragma unroll
@@ -113,83 +107,54 @@ __device__ __forceinline__ void sweep_tile(SweepShared& sh, const KT* __restrict
     __syncthreads();
     if (tid < 256u) {
         const uint32_t c = sh.tot[tid]; // (pads only exist in the last tile, whose counts no tile reads)
-        st_agent(status + (uint64_t)tile * 256 + tid, (tile == 0 ? RS_PREFIX : RS_AGG) | c);
+        st_agent(status + (uint64_t)tile * 256 + tid, (tile == 0 ? GS_LB_PREFIX : GS_LB_AGG) | c);
     }
-
-    // rank inside the wave: peers = lanes holding the same digit (8 ballots), order = (item, lane)
+    // rank inside the wave: 8 ballots per key
 #pragma unroll
     for (int j = 0; j < RS_ITEMS; ++j) {
         const uint32_t d = sort_digit(key[j], pass, sd);
-        uint32_t plo = 0xFFFFFFFFu, phi = 0xFFFFFFFFu;
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            const uint32_t bit = (d >> b) & 1u;
-            const unsigned long long bal = __ballot(bit != 0u);
-            const uint32_t inv = bit - 1u; // 0 when the bit is set, ~0 when clear: peers &= bit ? bal : ~bal
-            plo &= (uint32_t)bal ^ inv;
-            phi &= (uint32_t)(bal >> 32) ^ inv;
-        }
-        const uint32_t below = __popc(plo & (uint32_t)lt_mask) + __popc(phi & (uint32_t)(lt_mask >> 32));
-        const uint32_t cnt = __popc(plo) + __popc(phi);
-        const uint32_t pre = sh.hist[w][d];
-        // every peer has read `pre` before the leader's store is issued: one wave, in-order LDS
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        if (below == 0) sh.hist[w][d] = pre + cnt;
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const uint32_t r = pre + below; // < 1024
-        if (j & 1) rank2[j >> 1] |= r << 16;
-        else rank2[j >> 1] = r;
+        rank2_put(rank2, j, wave_rank<8>(sh.hist[w], d, 0xFFFFFFFFu, 0xFFFFFFFFu, true, lt_mask)); // < 1024
     }
     __syncthreads();
-
     // thread d (d < 256): counts of digit d per wave -> exclusive offsets across waves, tile total
     uint32_t cw[RS_WAVES], total = 0, incl = 0, excl = 0;
     const bool owner = tid < 256u;
     if (owner) {
-#pragma unroll
-        for (int k = 0; k < RS_WAVES; ++k) { cw[k] = sh.hist[k][tid]; total += cw[k]; }
-        incl = wave_incl_scan(total, lane);
-        if (lane == 63) sh.wsum[w] = incl;
-
-        // publish this tile's digit count, then walk back over the predecessors' words
+        total = wave_counts(sh.hist, tid, cw);
+        incl = wave_scan_publish(total, lane, w, sh.wsum);
         uint32_t* my = status + (uint64_t)tile * 256 + tid;
-        if (tile > 0) { // (the aggregate, or tile 0's prefix, was published before the ranking)
-            // Walk back over the predecessors' words LB at a time: the loads of one round are independent and in
-            // flight together, so a walk of k tiles costs ~k/LB L2 round trips instead of k (all resident
-            // workgroups start together, so the first tiles of a launch walk back hundreds of tiles).
+        if (tile > 0) { // the look-back of gs_binning.h (the same walk as in k_rows.hip)
             constexpr int LB = 8;
             bool found = false;
             for (int t = (int)tile - 1; t >= 0 && !found; t -= LB) {
                 uint32_t sv[LB];
 #pragma unroll
-                for (int k = 0; k < LB; ++k) sv[k] = (t - k >= 0) ? ld_agent(status + (uint64_t)(t - k) * 256 + tid) : RS_PREFIX;
+                for (int k = 0; k < LB; ++k) sv[k] = (t - k >= 0) ? ld_agent(status + (uint64_t)(t - k) * 256 + tid) : GS_LB_PREFIX;
 #pragma unroll
                 for (int k = 0; k < LB; ++k) {
                     if (found) break;
                     uint32_t v = sv[k], spins = 0;
-                    while ((v & RS_FLAGS) == 0 && ++spins < GS_SPIN_LIMIT) { // not published yet: poll this one word
+                    while ((v & GS_LB_FLAGS) == 0 && ++spins < GS_SPIN_LIMIT) {
                         __builtin_amdgcn_s_sleep(1);
                         v = ld_agent(status + (uint64_t)(t - k) * 256 + tid);
                     }
-                    if ((v & RS_FLAGS) == 0) { ctl->fault = 1u; found = true; break; }
-                    excl += v & RS_VALUE;
-                    if ((v & RS_FLAGS) == RS_PREFIX) found = true;
+                    if ((v & GS_LB_FLAGS) == 0) { ctl->fault = 1u; found = true; break; }
+                    excl += v & GS_LB_VALUE;
+                    if ((v & GS_LB_FLAGS) == GS_LB_PREFIX) found = true;
                 }
             }
-            st_agent(my, RS_PREFIX | ((excl + total) & RS_VALUE));
+            st_agent(my, GS_LB_PREFIX | ((excl + total) & GS_LB_VALUE));
         }
     }
     __syncthreads();
     if (owner) {
-        uint32_t wv = 0;
+        uint32_t wv = 0; // (waves_before, written out: as a call the sum for gbase below is associated differently)
         for (uint32_t k = 0; k < w; ++k) wv += sh.wsum[k];
         uint32_t run = wv + incl - total; // first slot of digit `tid` in the tile's sorted order
         sh.gbase[tid] = hist[tid] + excl - run;
-#pragma unroll
-        for (int k = 0; k < RS_WAVES; ++k) { sh.hist[k][tid] = run; run += cw[k]; }
+        wave_starts(sh.hist, tid, run, cw);
     }
     __syncthreads();
-
     // reorder through LDS, then store each digit's run contiguously (payloads are only loaded now:
     // holding them across the ranking phase costs 16 VGPRs and a wave of occupancy)
 #pragma unroll
@@ -198,7 +163,7 @@ __device__ __forceinline__ void sweep_tile(SweepShared& sh, const KT* __restrict
         if (FULL) v = vp[j * 64];
         else v = (wbase + j * 64 < valid) ? vp[j * 64] : 0u;
         const uint32_t d = sort_digit(key[j], pass, sd);
-        const uint32_t r = (j & 1) ? (rank2[j >> 1] >> 16) : (rank2[j >> 1] & 0xFFFFu);
+        const uint32_t r = rank2_get(rank2, j);
         const uint32_t pos = sh.hist[w][d] + r;
         sh.keys[pos] = key[j];
         sh.vals[pos] = v;
@@ -235,15 +200,10 @@ __global__ __launch_bounds__(RS_THREADS, 4) void gs_sort_sweep_kernel(const KT* 
         uint32_t c = 0, incl = 0;
         if (tid < 256u) {
             c = hist[tid];
-            incl = wave_incl_scan(c, lane);
-            if (lane == 63) sh.wsum[w] = incl;
+            incl = wave_scan_publish(c, lane, w, sh.wsum);
         }
         __syncthreads();
-        if (tid < 256u) {
-            uint32_t b = 0;
-            for (uint32_t k = 0; k < w; ++k) b += sh.wsum[k];
-            s_dbase[tid] = b + incl - c;
-        }
+        if (tid < 256u) s_dbase[tid] = waves_before<uint32_t>(sh.wsum, w) + incl - c;
         __syncthreads();
     }
     for (;;) {
