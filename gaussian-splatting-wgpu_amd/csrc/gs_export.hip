@@ -14,7 +14,7 @@
 #include "gs_runtime.h"
 
 // What every entry point checks first; drains the ring.  An error of the wait is the call's error: nothing is done.
-static int32_t edit_begin(gs_ctx* c, const char* who, uint32_t mask, uint32_t value) {
+int32_t edit_begin(gs_ctx* c, const char* who, uint32_t mask, uint32_t value) {
     if (!c) return fail(GS_ERR_INVALID_ARGUMENT, "%s: null ctx", who);
     if (mask > 0xFFu || value > 0xFFu) return fail(GS_ERR_INVALID_ARGUMENT, "%s: filter (0x%x, 0x%x) does not fit the state byte", who, mask, value);
     if ((mask | value) && !has_state(c)) // (0, 0) matches every splat: what is resident can be exported without a plane
@@ -28,7 +28,7 @@ static int32_t edit_begin(gs_ctx* c, const char* who, uint32_t mask, uint32_t va
 
 // Counts the matching splats (count + scan launches, the total read back like the state calls' counter); with want_ids also
 // writes their indices, ascending, to c->ex.ids.
-static int32_t select(gs_ctx* c, uint32_t mask, uint32_t value, bool want_ids, uint64_t* total) {
+int32_t edit_select(gs_ctx* c, uint32_t mask, uint32_t value, bool want_ids, uint64_t* total) {
     const uint32_t nb = gs_select_blocks(c->n);
     if ((uint64_t)nb + 1 > c->ex.counts_cap) {
         c->ex.counts_cap = 0;
@@ -57,7 +57,7 @@ GS_EXPORT int32_t gs_state_list(gs_ctx* c, uint32_t mask, uint32_t value, uint32
     if (rc != GS_OK) return rc;
     if (!n) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_list: null n");
     uint64_t total = 0;
-    rc = select(c, mask, value, ids != nullptr, &total); // (the list is built in the context's scratch: a refusal writes nothing to ids)
+    rc = edit_select(c, mask, value, ids != nullptr, &total); // (the list is built in the context's scratch: a refusal writes nothing to ids)
     if (rc != GS_OK) return rc;
     *n = total;
     if (!ids) return GS_OK;
@@ -78,7 +78,7 @@ static int32_t export_common(gs_ctx* c, const char* who, uint32_t mask, uint32_t
     const bool all = !(mask | value); // every splat, in place: no selection runs and the unpack reads splat g for record g
     uint64_t total = c->n;
     if (!all) {
-        rc = select(c, mask, value, out != nullptr, &total);
+        rc = edit_select(c, mask, value, out != nullptr, &total);
         if (rc != GS_OK) return rc;
     }
     *n = total;
@@ -121,7 +121,7 @@ GS_EXPORT int32_t gs_compact(gs_ctx* c, uint32_t mask, uint32_t value, uint64_t*
     if (c->scene_mem != c->scene_own.get())
         return fail(GS_ERR_INVALID_ARGUMENT, "gs_compact: this context borrows its splats (gs_share_splats): compact the owner");
     uint64_t total = 0;
-    rc = select(c, mask, value, true, &total); // (0, 0) and kept == N take this path too: no special case
+    rc = edit_select(c, mask, value, true, &total); // (0, 0) and kept == N take this path too: no special case
     if (rc != GS_OK) return rc;
     if (ids && total) HIP_TRY(hipMemcpyAsync(ids, c->ex.ids, (size_t)total * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -229,7 +229,7 @@ GS_EXPORT int32_t gs_export_ply(gs_ctx* c, const char* path, uint32_t mask, uint
     const bool all = !(mask | value);
     uint64_t total = c->n;
     if (!all) {
-        rc = select(c, mask, value, true, &total);
+        rc = edit_select(c, mask, value, true, &total);
         if (rc != GS_OK) return rc;
     }
     const uint32_t* sel = all ? nullptr : c->ex.ids.get();

@@ -85,6 +85,10 @@ void gs_launch_select_scatter(const uint8_t* state, uint32_t n, uint32_t mask, u
 void gs_launch_unpack(const GsScene& s, uint32_t n, const uint32_t* ids, uint32_t first, uint32_t m, void* d_aos, uint32_t* out_ids, hipStream_t st);
 // new splat g of `d` = splat ids[g] of `o` (every plane, the state byte included when both keep one)
 void gs_launch_compact_planes(const GsScene& o, uint32_t n_old, const uint32_t* ids, uint32_t m, const GsScene& d, hipStream_t st);
+// k_xform.hip: gs_transform_splats.  Entry g (0 .. m) is splat ids[g], or splat g when ids is null (then m = n); the parts named in
+// x.flags are transformed in place.
+struct gs_xform;
+void gs_launch_xform(const GsScene& s, uint32_t n, const uint32_t* ids, uint32_t m, const gs_xform& x, hipStream_t st);
 // k_pick.hip: gs_pick, one wave per query over the last frame's lists (queries: {x, y} pairs; results: 12 words per query;
 // contrib: max_contrib {id, weight} pairs per query, or null)
 void gs_launch_pick(const void* gdata, const uint32_t* values, const uint32_t* ranges, const GsFrame& f, uint32_t id_mask, const void* d_queries,

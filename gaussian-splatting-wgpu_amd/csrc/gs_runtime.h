@@ -1,4 +1,4 @@
-// gs_runtime.h -- private to the runtime sources (gs_context / gs_frame / gs_readback / gs_state / gs_export / gs_ply / gs_stages .hip): the error
+// gs_runtime.h -- private to the runtime sources (gs_context / gs_frame / gs_readback / gs_state / gs_export / gs_xform / gs_ply / gs_stages .hip): the error
 // channel, the owners of HIP resources, and the context.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -189,6 +189,10 @@ void drop_shadows(gs_ctx* c);
 // gs_frame.hip
 void drop_graph(gs_ctx* c);
 int32_t wait_one(gs_ctx* c);
+// gs_export.hip: what the splat edits and gs_transform_splats check first (drains the ring), and their selection: counts the splats
+// with (s & mask) == value and, with want_ids, leaves their indices, ascending, in c->ex.ids
+int32_t edit_begin(gs_ctx* c, const char* who, uint32_t mask, uint32_t value);
+int32_t edit_select(gs_ctx* c, uint32_t mask, uint32_t value, bool want_ids, uint64_t* total);
 inline gs_ctx* last_of(gs_ctx* c) { return (c && c->last) ? c->last : c; }
 inline bool has_state(const gs_ctx* c) { return (c->cfg.flags & GS_FLAG_SPLAT_STATE) != 0; }
 inline GsTint tint_of(uint32_t argb) { // a<<24 | r<<16 | g<<8 | b -> what the projection applies (each quotient one f32 division)

@@ -641,6 +641,73 @@ static napi_value js_save_ply(napi_env env, napi_callback_info info) {
     return rc == GS_OK ? NULL : throw_gs(env, rc);
 }
 
+/* ---- splat transforms (gs_abi.h "splat transforms") ---- */
+/* composeTransform(rot (4 numbers) | null, translate (3) | null, scale, pivot (3) | null) -> ArrayBuffer holding a gs_xform */
+static int get_floats(napi_env env, napi_value v, float* out, uint32_t n) {
+    bool is = false;
+    if (napi_is_array(env, v, &is) != napi_ok) return 0;
+    if (!is && (napi_is_typedarray(env, v, &is) != napi_ok || !is)) return 0;
+    for (uint32_t k = 0; k < n; ++k) {
+        napi_value e;
+        double d;
+        if (napi_get_element(env, v, k, &e) != napi_ok || napi_get_value_double(env, e, &d) != napi_ok) return 0;
+        out[k] = (float)d;
+    }
+    return 1;
+}
+static int is_nullish(napi_env env, napi_value v) {
+    napi_valuetype t;
+    return napi_typeof(env, v, &t) == napi_ok && (t == napi_undefined || t == napi_null);
+}
+static napi_value js_compose_transform(napi_env env, napi_callback_info info) {
+    size_t argc = 4;
+    napi_value argv[4];
+    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    float rot[4] = {1.0f, 0.0f, 0.0f, 0.0f}, tr[3] = {0.0f, 0.0f, 0.0f}, pv[3];
+    double scale = 1.0;
+    int have_pivot = 0, ok = argc >= 4;
+    if (ok && !is_nullish(env, argv[0])) ok = get_floats(env, argv[0], rot, 4);
+    if (ok && !is_nullish(env, argv[1])) ok = get_floats(env, argv[1], tr, 3);
+    if (ok && !is_nullish(env, argv[2])) ok = napi_get_value_double(env, argv[2], &scale) == napi_ok;
+    if (ok && !is_nullish(env, argv[3])) ok = have_pivot = get_floats(env, argv[3], pv, 3);
+    if (!ok) {
+        napi_throw_type_error(env, NULL, "gsplat.composeTransform: expects (rotation[4] | null, translation[3] | null, scale | null, pivot[3] | null)");
+        return NULL;
+    }
+    gs_xform x;
+    int32_t rc = gs_xform_compose(rot, tr, (float)scale, have_pivot ? pv : NULL, &x);
+    if (rc != GS_OK) return throw_gs(env, rc);
+    void* dst = NULL;
+    napi_value ab;
+    NAPI_CALL(env, napi_create_arraybuffer(env, sizeof(x), &dst, &ab));
+    memcpy(dst, &x, sizeof(x));
+    return ab;
+}
+
+/* transformSplats(handle, xform (ArrayBuffer / typed array holding a gs_xform), mask, value) -> matched */
+static napi_value js_transform_splats(napi_env env, napi_callback_info info) {
+    size_t argc = 4;
+    napi_value argv[4];
+    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    gs_ctx* ctx = argc >= 4 ? unwrap(env, argv[0]) : NULL;
+    if (!ctx) return NULL;
+    void* data = NULL;
+    size_t len = 0;
+    uint32_t mask = 0, value = 0;
+    if (!get_bytes(env, argv[1], &data, &len) || len != sizeof(gs_xform) || !get_filter(env, argv[2], argv[3], &mask, &value)) {
+        napi_throw_type_error(env, NULL, "gsplat.transformSplats: expects (handle, the buffer composeTransform returned, mask, value)");
+        return NULL;
+    }
+    gs_xform x;
+    memcpy(&x, data, sizeof(x)); /* (a view may be unaligned) */
+    uint64_t matched = 0;
+    int32_t rc = gs_transform_splats(ctx, mask, value, &x, &matched);
+    if (rc != GS_OK) return throw_gs(env, rc);
+    napi_value v;
+    NAPI_CALL(env, napi_create_double(env, (double)matched, &v));
+    return v;
+}
+
 /* setOption(handle, key, value) */
 static napi_value js_set_option(napi_env env, napi_callback_info info) {
     size_t argc = 3;
@@ -892,6 +959,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"readState", js_read_state}, {"writeState", js_write_state},  {"setOption", js_set_option},
         {"listState", js_list_state}, {"exportSplats", js_export_splats}, {"compact", js_compact},
         {"exportPly", js_export_ply}, {"savePly", js_save_ply},
+        {"composeTransform", js_compose_transform}, {"transformSplats", js_transform_splats},
     };
     for (size_t i = 0; i < sizeof(fns) / sizeof(fns[0]); ++i) {
         napi_value f;

@@ -55,13 +55,17 @@ GS_STATE_SET, GS_STATE_CLEAR, GS_STATE_TOGGLE, GS_STATE_ASSIGN = 1, 2, 3, 4
 GS_REGION_ALL, GS_REGION_SPHERE, GS_REGION_BOX, GS_REGION_SCREEN_RECT, GS_REGION_SCREEN_MASK = range(5)
 GS_SELECT_TINT_DEFAULT = 0x80FFFF00
 
+# splat transforms
+GS_XFORM_POSITION, GS_XFORM_ORIENT, GS_XFORM_SIZE = 0x1, 0x2, 0x4
+
 # every symbol include/gsplat/gs_abi.h declares
 ABI_SYMBOLS = ("gs_last_error", "gs_abi_version", "gs_create", "gs_destroy", "gs_upload_splats", "gs_upload_splats_device",
                "gs_share_splats",
                "gs_ply_load", "gs_ply_free", "gs_upload_ply",
                "gs_render", "gs_render_debug", "gs_render_to", "gs_wait", "gs_render_host", "gs_wait_ticket", "gs_host_alloc", "gs_host_free", "gs_read_rgba8", "gs_read_buffer", "gs_device_ptr",
                "gs_get_stats", "gs_pick", "gs_state_region", "gs_state_ids", "gs_state_count", "gs_state_write",
-               "gs_state_list", "gs_export_splats", "gs_export_splats_device", "gs_compact", "gs_ply_save", "gs_export_ply", "gs_set_option", "gs_slab_width", "gs_assemble_slabs", "gs_sort_pairs_u32",
+               "gs_state_list", "gs_export_splats", "gs_export_splats_device", "gs_compact", "gs_ply_save", "gs_export_ply",
+               "gs_xform_compose", "gs_transform_splats", "gs_set_option", "gs_slab_width", "gs_assemble_slabs", "gs_sort_pairs_u32",
                "gs_exclusive_scan_u32")
 
 
@@ -102,6 +106,11 @@ class GsRegion(ctypes.Structure):
                 ("x0", ctypes.c_uint32), ("y0", ctypes.c_uint32), ("x1", ctypes.c_uint32), ("y1", ctypes.c_uint32),
                 ("uniforms160", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("where_mask", ctypes.c_uint32),
                 ("where_value", ctypes.c_uint32)]
+
+
+class GsXform(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("m", ctypes.c_float * 12), ("q", ctypes.c_float * 4),
+                ("log_scale", ctypes.c_float), ("sh1", ctypes.c_float * 9), ("sh2", ctypes.c_float * 25), ("sh3", ctypes.c_float * 49)]
 
 
 # numpy views of the same records (what Renderer.pick returns)
@@ -161,6 +170,9 @@ def load():
     L.gs_compact.argtypes = [vp, u32, u32, ctypes.POINTER(u64), vp]
     L.gs_ply_save.argtypes = [ctypes.c_char_p, vp, u64, i32]
     L.gs_export_ply.argtypes = [vp, ctypes.c_char_p, u32, u32, i32, ctypes.POINTER(u64)]
+    L.gs_xform_compose.argtypes = [ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.c_float,
+                                   ctypes.POINTER(ctypes.c_float), ctypes.POINTER(GsXform)]
+    L.gs_transform_splats.argtypes = [vp, u32, u32, ctypes.POINTER(GsXform), ctypes.POINTER(u64)]
     L.gs_set_option.argtypes = [vp, i32, ctypes.c_int64]
     L.gs_slab_width.argtypes = [vp, ctypes.POINTER(u32), ctypes.POINTER(u32)]
     L.gs_assemble_slabs.argtypes = [vp, vp, ctypes.POINTER(u32), u32, u64, vp]
@@ -213,3 +225,14 @@ def save_ply(path, records, sh_degree=3):
     sh_degree are not written)."""
     rec = np.ascontiguousarray(records, dtype=np.float32).reshape(-1, 80)
     check(load().gs_ply_save(str(path).encode(), rec.ctypes.data if rec.shape[0] else None, rec.shape[0], int(sh_degree)))
+
+
+def compose_xform(rot=(1, 0, 0, 0), translate=(0, 0, 0), scale=1.0, pivot=None):
+    """gs_xform_compose: the GsXform of p' = scale R (p - pivot) + pivot + translate, R the rotation of the quaternion `rot`
+    (r, x, y, z; any non-zero length).  Host mathematics in double, no GPU: the 3x4 matrix, the normalised quaternion, log(scale)
+    and the SH band matrices of R."""
+    f3, f4 = ctypes.c_float * 3, ctypes.c_float * 4
+    x = GsXform()
+    check(load().gs_xform_compose(f4(*[float(v) for v in rot]), f3(*[float(v) for v in translate]), float(scale),
+                                  None if pivot is None else f3(*[float(v) for v in pivot]), ctypes.byref(x)))
+    return x

@@ -333,6 +333,26 @@ class Renderer:
         check(self._L.gs_export_ply(self._ctx, str(path).encode(), int(mask), int(value), int(sh_degree), ctypes.byref(n)))
         return int(n.value)
 
+    # -- splat transforms: move, rotate and scale resident splats in place ----------------------------------
+    def transform(self, xform, mask=_abi.GS_SPLAT_SELECTED, value=_abi.GS_SPLAT_SELECTED):
+        """gs_transform_splats: applies a GsXform (_abi.compose_xform) in place to the resident splats with (s & mask) == value
+        (default: the selection; (0, 0): every splat, also without GS_FLAG_SPLAT_STATE); returns how many those are.  Completes
+        every frame in flight first; not a frame and not an upload: the next frame sees the moved splats.  The inverse transform
+        is not a bit-exact undo: export the selection first if one is needed."""
+        matched = ctypes.c_uint64()
+        check(self._L.gs_transform_splats(self._ctx, int(mask), int(value), ctypes.byref(xform), ctypes.byref(matched)))
+        return int(matched.value)
+
+    def translate_selected(self, t):
+        return self.transform(_abi.compose_xform(translate=t))
+
+    def rotate_selected(self, rot, pivot=None):
+        """rot: quaternion (r, x, y, z) of any non-zero length; pivot: the point that stays where it is (default: the origin)."""
+        return self.transform(_abi.compose_xform(rot=rot, pivot=pivot))
+
+    def scale_selected(self, s, pivot=None):
+        return self.transform(_abi.compose_xform(scale=s, pivot=pivot))
+
     def device_ptr(self, which):
         p = ctypes.c_void_p()
         check(self._L.gs_device_ptr(self._ctx, which, ctypes.byref(p)))
@@ -480,6 +500,18 @@ class PipelinedRenderer:
 
     def save_ply(self, *a, **kw):
         return self._state_owner().save_ply(*a, **kw)
+
+    def transform(self, *a, **kw):
+        return self._state_owner().transform(*a, **kw)
+
+    def translate_selected(self, t):
+        return self._state_owner().translate_selected(t)
+
+    def rotate_selected(self, rot, pivot=None):
+        return self._state_owner().rotate_selected(rot, pivot)
+
+    def scale_selected(self, s, pivot=None):
+        return self._state_owner().scale_selected(s, pivot)
 
     def compact(self, mask, value):
         first = self._state_owner()

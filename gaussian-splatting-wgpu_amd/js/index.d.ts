@@ -55,6 +55,8 @@ export class Renderer {
   deleteHidden(): Uint32Array;
   /** Streams the matching splats into a binary 3DGS .ply; returns how many were written. */
   savePly(file: string, options?: { mask?: number; value?: number; shDegree?: number }): number;
+  /** Applies what composeTransform returned, in place, to the resident splats with (s & mask) == value (default: the selection; (0, 0): every splat); returns how many those are. The next frame sees the moved splats; the inverse transform is not a bit-exact undo. */
+  transformSplats(xform: ArrayBuffer | Float32Array, mask?: number, value?: number): number;
   stats(): { numGaussians: number; numVisible: number; numIntersections: number; numProcessed: number; numTiles: number; sortPasses: number; frames: number; frameUs: number; stageUs: number[]; numEvaluated: number; depthOrdered: number; tightBinning: number; graphFrames: number; capacity: number; maxIntersectionsSeen: number; truncatedFrames: number };
 }
 export interface StateRegion {
@@ -86,6 +88,8 @@ export function getProjectionMatrix(znear: number, zfar: number, fovX: number, f
 export function focal2fov(focal: number, pixels: number): number;
 /** The inverse of PackedGaussians.fromFile: writes the records as a binary 3DGS .ply of that SH degree. */
 export function savePly(file: string, gaussians: PackedGaussians, shDegree?: number): void;
+/** The opaque gs_xform of p' = scale R (p - pivot) + pivot + translation, R the rotation of the quaternion (r, x, y, z; any non-zero length); uniform scale > 0 only. No context, no GPU. */
+export function composeTransform(transform?: { rotation?: number[]; translation?: number[]; scale?: number; pivot?: number[] }): ArrayBuffer;
 export function writePPM(file: string, rgba: Uint8Array, width: number, height: number): void;
 export const BUF: { TILE_COUNTS: 0; TILE_OFFSETS: 1; GAUSSIAN_DATA: 2; KEYS_UNSORTED: 3; VALUES_UNSORTED: 4; KEYS: 5; VALUES: 6; RANGES: 7; RGBA8: 8; RGB_F32: 9;
                     ALPHA_F32: 13; DEPTH_F32: 14; SPLAT_STATE: 15 };

@@ -1,7 +1,7 @@
 'use strict';
 // gsplat (Node host): the reference's class surface -- Renderer, Camera, InteractiveCamera,
 // PackedGaussians, loadFileAsArrayBuffer -- backed by the MI355X-native C ABI through N-API.
-const { Renderer, loadNative, savePly, PickResult, PICK, PICK_FIELD, STATE, REGION } = require('./renderer');
+const { Renderer, loadNative, savePly, composeTransform, PickResult, PICK, PICK_FIELD, STATE, REGION } = require('./renderer');
 const { Camera, InteractiveCamera, cameraFromJSON, loadCameraFile, getProjectionMatrix, focal2fov } = require('./camera');
 const { PackedGaussians, loadFileAsArrayBuffer } = require('./ply');
 const { mat4, mat3, vec3 } = require('./mat4');
@@ -17,7 +17,7 @@ function writePPM(file, rgba, width, height) {
 
 module.exports = {
   Renderer, Camera, InteractiveCamera, PackedGaussians, loadFileAsArrayBuffer, cameraFromJSON, loadCameraFile,
-  getProjectionMatrix, focal2fov, mat4, mat3, vec3, writePPM, loadNative, savePly,
+  getProjectionMatrix, focal2fov, mat4, mat3, vec3, writePPM, loadNative, savePly, composeTransform,
   BUF: { TILE_COUNTS: 0, TILE_OFFSETS: 1, GAUSSIAN_DATA: 2, KEYS_UNSORTED: 3, VALUES_UNSORTED: 4, KEYS: 5, VALUES: 6, RANGES: 7, RGBA8: 8, RGB_F32: 9,
          ALPHA_F32: 13, DEPTH_F32: 14, SPLAT_STATE: 15 },
   FLAG: { EXACT_BLEND: 0x1, F32_TAP: 0x2, TIMING: 0x4, AUX_OUTPUTS: 0x8, SPLAT_STATE: 0x10 },

@@ -199,6 +199,19 @@ class Renderer {
   savePly(file, { mask = 0, value = 0, shDegree = 3 } = {}) {
     return loadNative().exportPly(this.handle, String(file), mask >>> 0, value >>> 0, shDegree | 0);
   }
+  // Splat transforms: applies what composeTransform returned, in place, to the resident splats with (s & mask) == value (default:
+  // the selection; (0, 0): every splat); returns how many those are.  Not a frame and not an upload: the next frame sees the
+  // moved splats.  The inverse transform is not a bit-exact undo: exportSplats first if one is needed.
+  transformSplats(xform, mask = STATE.SELECTED, value = STATE.SELECTED) {
+    return loadNative().transformSplats(this.handle, xform, mask >>> 0, value >>> 0);
+  }
+}
+
+// composeTransform({rotation, translation, scale, pivot}) -> ArrayBuffer holding the gs_xform of p' = scale R (p - pivot) + pivot +
+// translation, R the rotation of the quaternion `rotation` (r, x, y, z; any non-zero length).  Host mathematics (gs_xform_compose):
+// no context, no GPU.  The buffer is opaque: hand it to renderer.transformSplats.
+function composeTransform({ rotation = null, translation = null, scale = 1, pivot = null } = {}) {
+  return loadNative().composeTransform(rotation, translation, scale, pivot);
 }
 
 // savePly(file, packedGaussians, shDegree): the inverse of PackedGaussians.fromFile (gs_ply_save; no context, no GPU)
@@ -243,4 +256,4 @@ class PickResult {
   }
 }
 
-module.exports = { Renderer, loadNative, savePly, PickResult, PICK, PICK_FIELD, STATE, REGION };
+module.exports = { Renderer, loadNative, savePly, composeTransform, PickResult, PICK, PICK_FIELD, STATE, REGION };

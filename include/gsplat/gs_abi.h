@@ -369,6 +369,69 @@ int32_t gs_ply_save(const char* path, const void* records, uint64_t n, int32_t s
  * mirror image.  Host memory does not grow with N.  *n (may be NULL): records written. */
 int32_t gs_export_ply(gs_ctx* ctx, const char* path, uint32_t mask, uint32_t value, int32_t sh_degree, uint64_t* n);
 
+/* ---- splat transforms: move, rotate and scale resident splats in place -----------------------------
+ * The verb the edits above lack: a similarity p' = s R (p - pivot) + pivot + t, uniform s > 0, applied to the resident splats that
+ * pass a state filter, in ONE streaming pass over the affected planes -- no export / edit / re-upload round trip, no reallocation,
+ * no frame kernel touched.  The reference has no counterpart (a viewer); the conventions a transform must respect are its own:
+ * compute_cov3d (process_gaussians.wgsl:127-163) normalises rot every frame and builds the covariance from exp(log-scale);
+ * compute_color_from_sh (:221-280) fixes the SH basis order, constants and signs, evaluated at dir = normalize(position - camera).
+ * A NON-UNIFORM scale or a shear does not keep a splat an axis-aligned-scales-plus-rotation gaussian: out of scope, there is no
+ * field for it.
+ * Two layers.  gs_transform_splats applies exactly the f32 numbers of a gs_xform, with arithmetic a host can restate bit for bit
+ * (one f32 rounding per written operation, no contraction, left to right -- the rule of gs_state_region).  Everything that needs
+ * trigonometry or the SH rotation lives in gs_xform_compose: plain host code, no ctx, no GPU, computed in double, every output
+ * rounded once.  A host may also fill the struct itself.
+ * Per matching splat; only the parts named in `flags` are read or written, the others keep their bit patterns (NaN payloads
+ * included); opacity, SH band 0 and the state byte are never written:
+ *   POSITION  p'_r = ((m[4r] x + m[4r+1] y) + m[4r+2] z) + m[4r+3],  r = 0, 1, 2
+ *   ORIENT    rot' = q * rot (Hamilton product, both (r,x,y,z), a = q, b = rot):
+ *               r' = ((a.r b.r - a.x b.x) - a.y b.y) - a.z b.z        x' = ((a.r b.x + a.x b.r) + a.y b.z) - a.z b.y
+ *               y' = ((a.r b.y - a.x b.z) + a.y b.r) + a.z b.x        z' = ((a.r b.z + a.x b.y) - a.y b.x) + a.z b.r
+ *             not renormalised (compute_cov3d normalises per frame: any non-zero rot stays correct); and for every channel c and
+ *             band l = 1, 2, 3 (coefficients k0 .. k0 + 2l, k0 = 1, 4, 9, record float 16 + 4k + c):
+ *               out_i = sum_j D_l[i][j] in_j  evaluated as  acc = D[i][0] in_0;  acc = acc + D[i][j] in_j  for j ascending,
+ *             every output of a band from the OLD values of the band (D_1 = sh1, D_2 = sh2, D_3 = sh3, row-major)
+ *   SIZE      log-scale_k' = log-scale_k + log_scale, k = 0, 1, 2; the derived largest log-scale the slab cull reads is recomputed
+ *             as fmaxf(l0', fmaxf(l1', l2')), the upload's own expression: a transformed ctx and a freshly uploaded one agree
+ * Traffic per matched splat: POSITION 12 B read, 12 B written; ORIENT 16 + 180 B each way; SIZE 12 B read, 16 B written; plus
+ * 1 B of state per RESIDENT splat when a filter other than (0, 0) is given (the selection of the splat edits, which reads the
+ * plane once to count and once more to scatter, and moves 4 B of index per match each way).
+ * Filter, refusals and ordering are those of the splat edits: (mask, value) as gs_state_count, above 0xFF refused, (0, 0) matches
+ * every splat and is accepted on a ctx without GS_FLAG_SPLAT_STATE, any other filter on such a ctx is refused.  The call first
+ * completes all frames enqueued on the ctx's ring (an error of that wait is the call's error, nothing is applied), runs on the
+ * ctx's stream and returns when done.  It is NOT a frame and NOT an upload: taps, statistics and gs_pick keep describing the frame
+ * that was rendered, the frames-in-flight shadows, the capacities and a captured frame graph stay (the graph reads the planes when
+ * it is replayed); the NEXT frame sees the moved splats.  A ctx that borrows its scene (gs_share_splats) is refused: transform the
+ * owner -- its borrowers then render the new scene, and as for a state call the host drains them first.  GS_ERR_NO_SCENE before
+ * any upload; N == 0: *matched = 0, GS_OK.  Multi-GPU: the same call on every rank (the result is deterministic).
+ * The inverse transform is NOT a bit-exact undo (every step rounds): a host that wants one exports the selection first.
+ * "Bit for bit" has one exception a restating host must know: a NaN that an operation above PRODUCES or propagates (a NaN or an
+ * infinite input in a flagged part: inf * 0, inf - inf) is a NaN on every machine, but IEEE 754 leaves its sign and payload open
+ * and the device's choice differs from that of other processors (x86 produces 0xFFC00000 for inf * 0): compare such floats as
+ * "NaN on both sides".  Floats of parts that are not flagged, and of splats that do not match, are never computed: their NaN
+ * payloads survive untouched. */
+#define GS_XFORM_POSITION 0x1u  /* positions                                   */
+#define GS_XFORM_ORIENT   0x2u  /* rot quaternion and SH bands 1..3            */
+#define GS_XFORM_SIZE     0x4u  /* the three log-scales (and the derived smax) */
+typedef struct gs_xform {
+    uint32_t struct_size, flags; /* = sizeof(gs_xform), GS_XFORM_*                                                   */
+    float m[12];      /* row-major 3x4: p'_r = ((m[4r] x + m[4r+1] y) + m[4r+2] z) + m[4r+3]                         */
+    float q[4];       /* (r,x,y,z), composed on the LEFT of the splat's rot                                          */
+    float log_scale;  /* added to each of the three log-scales                                                       */
+    float sh1[9], sh2[25], sh3[49]; /* row-major band matrices D_l; band 0 is never touched                          */
+} gs_xform;
+/* Fills *out for p' = scale R (p - pivot) + pivot + translate, R the rotation of rot_rxyz (any non-zero length; pivot NULL = the
+ * origin): q = rot_rxyz normalised; m = [sR | t + pivot - sR pivot]; log_scale = (float)log(scale); D_l such that, with B_l(d) the
+ * vector of compute_color_from_sh's band-l terms (constants and signs included), B_l(R^T d) = D_l^T B_l(d) for every unit d -- the
+ * rotated splat seen from d shows what the original showed from R^T d.  flags = POSITION, plus ORIENT unless the normalised q is
+ * +-(1,0,0,0), plus SIZE unless scale == 1.  A null pointer other than pivot, a zero or non-finite quaternion, scale <= 0 or
+ * non-finite, a non-finite translate or pivot: GS_ERR_INVALID_ARGUMENT and a message. */
+int32_t gs_xform_compose(const float rot_rxyz[4], const float translate[3], float scale, const float pivot[3], gs_xform* out);
+/* Applies *x to every resident splat with (s & mask) == value; *matched (may be NULL) receives their number.  A wrong struct_size,
+ * unknown flag bits or a non-finite member of a flagged part: GS_ERR_INVALID_ARGUMENT, nothing is applied.  flags == 0 is a valid
+ * no-op that still reports *matched. */
+int32_t gs_transform_splats(gs_ctx* ctx, uint32_t mask, uint32_t value, const gs_xform* x, uint64_t* matched);
+
 /* Tuning / profiling knobs. */
 #define GS_OPT_BLEND_ABLATION 1  /* bit 3 (8): the workgroup-per-tile blend kernel at tiles 16 and 32 (identical results; default = one
                                     wave per 8x8 pixel block); bit 2 (4): every blend kernel without its two parking culls (live box,

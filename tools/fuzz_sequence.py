@@ -1,9 +1,12 @@
 #!/usr/bin/env python3
 """GPU box: random SEQUENCES of calls on one context -- new scenes of other sizes, option changes (binning, emission order, frames in
-flight, frame graph, projection chunks, workgroup-per-tile blend), bursts of frames without a wait (a debug frame among them), frames presented through
+flight, frame graph, projection chunks, workgroup-per-tile blend), similarity transforms of the resident scene (gs_transform_splats, with
+frames still in flight: the call drains them; the oracle then renders the restated records), bursts of frames without a wait (a debug frame among them), frames presented through
 gs_render_host with tickets waited for in any order (every sink checked), reads in between -- the last frame
 of every burst against the oracle (EXACT, bit for bit).  Hunts life-cycle bugs (stale captures, ring members with old arrays,
-capacities).  Stops at the first failing sequence (exit status 1).  Usage: tools/fuzz_sequence.py [sequences=30] [seed0=0]"""
+capacities).  The transform step takes the last tenth of the step draw (c >= 0.90, formerly bursts): uploads, options and
+presentations fall where they fell, but a sequence that draws it differs from there on, so seeds recorded before the step existed
+reproduce only up to their first such draw.  Stops at the first failing sequence (exit status 1).  Usage: tools/fuzz_sequence.py [sequences=30] [seed0=0]"""
 import ctypes, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "gaussian-splatting-wgpu_amd")); sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -14,6 +17,7 @@ import gsplat
 from gsplat import _abi, synth
 from oracle import gs_oracle as o
 import gpu_checks as gc
+import xform_restate as xr
 
 o.build()
 seqs = int(sys.argv[1]) if len(sys.argv) > 1 else 30
@@ -43,6 +47,15 @@ for q in range(seed0, seed0 + seqs):
                 r.wait()
                 r.set_option(key, val)
                 log.append("opt %d=%d" % (key, val))
+            elif c >= 0.90:
+                # the whole scene moved in place, frames of the old scene possibly still in flight; the host's copy follows by restatement
+                ang = float(rng.uniform(-1.0, 1.0))
+                x = _abi.compose_xform(xr.axis_angle(rng.normal(size=3) + 1e-3, ang), rng.uniform(-0.3, 0.3, size=3),
+                                       float(rng.choice([1.0, 0.8, 1.25])), rng.uniform(-1.0, 1.0, size=3) if rng.random() < 0.5 else None)
+                if rng.random() < 0.5: r.render_uniforms(synth.orbit_camera(int(rng.integers(0, 64)), W, H).uniforms(W, H))
+                assert r.transform(x, 0, 0) == n
+                s = xr.apply(s, xr.Xform.from_struct(x))
+                log.append("xform %d" % x.flags)
             elif c < 0.60:
                 # pipelined presentation: k frames through gs_render_host into sinks of their own (plain and debug frames of other
                 # cameras enqueued in between), tickets waited for in random order, EVERY sink against the oracle
