@@ -103,6 +103,10 @@ struct GsScene {
 #define GS_ST_HIDDEN 1u
 #define GS_ST_SELECTED 2u
 struct GsTint { float t[3]; float k; };
+// the four operations of gs_abi.h GS_STATE_* on one byte (k_state.hip, k_coverage.hip)
+__device__ __forceinline__ uint32_t gs_state_apply(uint32_t s, uint32_t op, uint32_t bits) {
+    return op == 1u ? (s | bits) : op == 2u ? (s & ~bits) : op == 3u ? (s ^ bits) : bits;
+}
 
 struct GsPlyTable { // where the 11 + 48 values of a packed record live in a raw .ply vertex (gs_upload_ply)
     uint32_t stride, nsrc, all_float;
@@ -193,6 +197,60 @@ template <bool EXACT>
 __device__ __forceinline__ bool gs_pixel_final(float T) {
     const float c255 = (float)(1.0 / 255.0);
     return (EXACT ? T * (1.0f - c255) : __builtin_fmaf(-T, c255, T)) < 0.0001f;
+}
+
+// ---- the two parking culls of the 8x8-block walkers (k_blend.hip; k_coverage.hip walks the same lists with the same culls) ------------
+// Minimum over the pixel block [dxlo,dxhi] x [dylo,dyhi] (offsets g - p) of the quadratic
+// q(d) = 0.5*(cx*dx^2 + cz*dy^2) + cy*dx*dy (power = -q).  For a positive-definite conic whose centre
+// is outside the block the minimiser lies on an edge facing the centre: at most two 1-D problems.
+// (v_rcp_f32 instead of an IEEE division: q is evaluated AT the clamped point, so a 1-ulp error in the
+// minimiser only moves q by a second-order amount, far inside the caller's margin.)
+__device__ __forceinline__ float block_qmin(float cx, float cy, float cz, float dxlo, float dxhi, float dylo, float dyhi,
+                                            float& mag) {
+    const float X = __builtin_fminf(__builtin_fmaxf(0.0f, dxlo), dxhi); // clamp(0, lo, hi)
+    const float Y = __builtin_fminf(__builtin_fmaxf(0.0f, dylo), dyhi);
+    float q = 3.0e38f;
+    mag = 0.0f;
+    if (X == 0.0f && Y == 0.0f) return 0.0f; // centre inside the block
+    if (X != 0.0f) {
+        const float dy = __builtin_fminf(__builtin_fmaxf(-cy * X * __builtin_amdgcn_rcpf(cz), dylo), dyhi);
+        const float a = 0.5f * cx * X * X, b = 0.5f * cz * dy * dy, c = cy * X * dy;
+        q = a + b + c;
+        mag = __builtin_fabsf(a) + __builtin_fabsf(b) + __builtin_fabsf(c);
+    }
+    if (Y != 0.0f) {
+        const float dx = __builtin_fminf(__builtin_fmaxf(-cy * Y * __builtin_amdgcn_rcpf(cx), dxlo), dxhi);
+        const float a = 0.5f * cx * dx * dx, b = 0.5f * cz * Y * Y, c = cy * dx * Y;
+        const float q2 = a + b + c;
+        if (q2 < q) { q = q2; mag = __builtin_fabsf(a) + __builtin_fabsf(b) + __builtin_fabsf(c); }
+    }
+    return q;
+}
+
+// The transmittance cull of the blend walkers (see gs_blend_quad_kernel, "... and the transmittance that is left"): true if
+// Tmax (1 - alpha_lo) < 1e-4 with margins, alpha_lo a lower bound of the entry's alpha over the box [dxlo,dxhi] x [dylo,dyhi]
+// (offsets centre - pixel; the quadratic's maximum over a rectangle is at a corner).  Positive-definite conics only.
+__device__ __forceinline__ bool blend_tmax_cull(float cx, float cy, float cz, float op, float dxlo, float dxhi, float dylo, float dyhi, float Tmax) {
+    const float ax0 = (0.5f * cx) * dxlo * dxlo, ax1 = (0.5f * cx) * dxhi * dxhi, by0 = (0.5f * cz) * dylo * dylo, by1 = (0.5f * cz) * dyhi * dyhi;
+    const float c00 = cy * dxlo * dylo, c01 = cy * dxlo * dyhi, c10 = cy * dxhi * dylo, c11 = cy * dxhi * dyhi;
+    const float qmax = __builtin_fmaxf(__builtin_fmaxf(ax0 + by0 + c00, ax0 + by1 + c01), __builtin_fmaxf(ax1 + by0 + c10, ax1 + by1 + c11));
+    const float qmag = __builtin_fmaxf(ax0, ax1) + __builtin_fmaxf(by0, by1) +
+                       __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(c00), __builtin_fabsf(c01)), __builtin_fmaxf(__builtin_fabsf(c10), __builtin_fabsf(c11)));
+    // alpha >= min(0.99, op exp(-qmax)) on every live pixel; 1 % off for the roundings of q, exp and the loop's own alpha
+    const float alo = 0.99f * __builtin_fminf(0.99f, op * __builtin_amdgcn_exp2f(-1.44269502162933349609375f * (qmax + 1.0e-5f * qmag)));
+    return Tmax * (1.0f - alo) < 0.0000999f; // (NaN anywhere: false, the entry stays)
+}
+
+// The bounding box of a block's LIVE pixels (lane = 8 row + column) from their ballot: first / last column and row, as floats.
+// EMPTY_OK: lv may be 0 (the scans are guarded; the box is then meaningless and the caller must not use it)
+struct GsLiveBox { float c0, c1, r0, r1; };
+template <bool EMPTY_OK>
+__device__ __forceinline__ GsLiveBox gs_live_box(unsigned long long lv) {
+    uint32_t lcm = (uint32_t)lv | (uint32_t)(lv >> 32);
+    lcm |= lcm >> 16; lcm |= lcm >> 8; lcm &= 0xFFu; // columns of the block that hold a live pixel
+    const unsigned long long lo = EMPTY_OK ? lv | (1ull << 63) : lv, hi = EMPTY_OK ? lv | 1ull : lv;
+    return GsLiveBox{(float)__builtin_ctz(lcm | 0x100u), (float)(31 - __builtin_clz(lcm | 1u)), (float)(__builtin_ctzll(lo) >> 3),
+                     (float)((63 - __builtin_clzll(hi)) >> 3)};
 }
 
 // A tile's run [x, y) of the sorted list (ranges[] holds the inclusive scan of the tile counts), clamped to what the arrays hold

@@ -1,4 +1,4 @@
-// gs_runtime.h -- private to the runtime sources (gs_context / gs_frame / gs_readback / gs_state / gs_export / gs_xform / gs_ply / gs_stages .hip): the error
+// gs_runtime.h -- private to the runtime sources (gs_context / gs_frame / gs_readback / gs_state / gs_export / gs_xform / gs_coverage / gs_ply / gs_stages .hip): the error
 // channel, the owners of HIP resources, and the context.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -159,6 +159,8 @@ struct gs_ctx {
     struct { DevBuf<unsigned long long> counter; DevBuf<uint32_t> ids; DevBuf<uint8_t> mask; uint64_t ids_cap = 0, mask_cap = 0; } st;
     // splat edits (gs_export.hip): the selection's per-workgroup counts and its id list; grown on demand
     struct { DevBuf<uint32_t> counts, ids; uint64_t counts_cap = 0, ids_cap = 0; } ex;
+    // gs_coverage_* (gs_coverage.hip; root ctx): N x 16 B gs_coverage_rec, allocated and zeroed on first use, dropped with the scene
+    DevBuf<> cov;
     Event ev[GS_EV_RING][GS_STAGE_COUNT + 1]; // ring of per-frame stage brackets (GS_FLAG_TIMING)
     bool have_events = false;
     uint64_t timed_from = 0; // first frame index included in the stage means
@@ -193,6 +195,13 @@ int32_t wait_one(gs_ctx* c);
 // with (s & mask) == value and, with want_ids, leaves their indices, ascending, in c->ex.ids
 int32_t edit_begin(gs_ctx* c, const char* who, uint32_t mask, uint32_t value);
 int32_t edit_select(gs_ctx* c, uint32_t mask, uint32_t value, bool want_ids, uint64_t* total);
+// gs_state.hip: what every state call checks first (state_begin), the drain of the ring, and the kernels' `matched` partial sums
+// (zeroed before the launch, added up after it: returns when the stream is done)
+int32_t state_begin(gs_ctx* c, const char* who);
+int32_t state_drain(gs_ctx* c);
+int32_t state_counter_zero(gs_ctx* c);
+int32_t state_counter_sum(gs_ctx* c, unsigned long long* total);
+int32_t state_check_op(const char* who, uint32_t op, uint32_t bits);
 inline gs_ctx* last_of(gs_ctx* c) { return (c && c->last) ? c->last : c; }
 inline bool has_state(const gs_ctx* c) { return (c->cfg.flags & GS_FLAG_SPLAT_STATE) != 0; }
 inline GsTint tint_of(uint32_t argb) { // a<<24 | r<<16 | g<<8 | b -> what the projection applies (each quotient one f32 division)

@@ -11,14 +11,14 @@
 #include "gs_runtime.h"
 
 // What every entry point checks first; drains the ring.  An error of the wait is the call's error: nothing is applied.
-static int32_t state_begin(gs_ctx* c, const char* who) {
+int32_t state_begin(gs_ctx* c, const char* who) {
     if (!c) return fail(GS_ERR_INVALID_ARGUMENT, "%s: null ctx", who);
     if (!has_state(c)) return fail(GS_ERR_INVALID_ARGUMENT, "%s: the context was created without GS_FLAG_SPLAT_STATE", who);
     if (!c->scene_mem || !c->scene.state) return fail(GS_ERR_NO_SCENE, "%s: no splats uploaded", who);
     return GS_OK;
 }
 static constexpr size_t kCounterBytes = (size_t)GS_STATE_SLOTS * GS_STATE_SLOT_STRIDE * sizeof(unsigned long long);
-static int32_t state_drain(gs_ctx* c) {
+int32_t state_drain(gs_ctx* c) {
     const int32_t rc = gs_wait(c);
     if (rc != GS_OK) return rc;
     HIP_TRY(hipSetDevice(c->cfg.device));
@@ -26,11 +26,11 @@ static int32_t state_drain(gs_ctx* c) {
     return GS_OK;
 }
 // The kernels' partial sums (gs_kernels.h GS_STATE_SLOTS): zeroed before the launch, added up after it; returns when the stream is done.
-static int32_t counter_zero(gs_ctx* c) {
+int32_t state_counter_zero(gs_ctx* c) {
     HIP_TRY(hipMemsetAsync(c->st.counter, 0, kCounterBytes, c->stream));
     return GS_OK;
 }
-static int32_t counter_sum(gs_ctx* c, unsigned long long* total) {
+int32_t state_counter_sum(gs_ctx* c, unsigned long long* total) {
     unsigned long long h[GS_STATE_SLOTS * GS_STATE_SLOT_STRIDE];
     HIP_TRY(hipMemcpyAsync(h, c->st.counter, kCounterBytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -38,7 +38,7 @@ static int32_t counter_sum(gs_ctx* c, unsigned long long* total) {
     for (int k = 0; k < GS_STATE_SLOTS; ++k) *total += h[k * GS_STATE_SLOT_STRIDE];
     return GS_OK;
 }
-static int32_t check_op(const char* who, uint32_t op, uint32_t bits) {
+int32_t state_check_op(const char* who, uint32_t op, uint32_t bits) {
     if (op < GS_STATE_SET || op > GS_STATE_ASSIGN) return fail(GS_ERR_INVALID_ARGUMENT, "%s: unknown op %u (GS_STATE_SET .. GS_STATE_ASSIGN)", who, op);
     if (bits > 0xFFu) return fail(GS_ERR_INVALID_ARGUMENT, "%s: bits 0x%x do not fit the state byte", who, bits);
     return GS_OK;
@@ -51,7 +51,7 @@ GS_EXPORT int32_t gs_state_region(gs_ctx* c, const gs_region* rg, uint32_t op, u
     if (!rg) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_region: null region");
     if (rg->struct_size != sizeof(gs_region)) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_region: struct_size %u != %zu", rg->struct_size, sizeof(gs_region));
     if (rg->kind > GS_REGION_SCREEN_MASK) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_region: unknown region kind %u", rg->kind);
-    rc = check_op("gs_state_region", op, bits);
+    rc = state_check_op("gs_state_region", op, bits);
     if (rc != GS_OK) return rc;
     if (rg->where_mask > 0xFFu) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_region: where_mask 0x%x does not fit the state byte", rg->where_mask);
     const bool screen = rg->kind == GS_REGION_SCREEN_RECT || rg->kind == GS_REGION_SCREEN_MASK;
@@ -81,12 +81,12 @@ GS_EXPORT int32_t gs_state_region(gs_ctx* c, const gs_region* rg, uint32_t op, u
         HIP_TRY(hipMemcpyAsync(c->st.mask, rg->mask, (size_t)mb, hipMemcpyHostToDevice, c->stream));
         r.mask = c->st.mask;
     }
-    rc = counter_zero(c);
+    rc = state_counter_zero(c);
     if (rc != GS_OK) return rc;
     gs_launch_state_region(rg->kind, plane(c), c->scene, c->n, r, op, bits, rg->where_mask, rg->where_value, c->st.counter, c->stream);
     HIP_TRY(hipGetLastError());
     unsigned long long m = 0;
-    rc = counter_sum(c, &m);
+    rc = state_counter_sum(c, &m);
     if (rc != GS_OK) return rc;
     if (matched) *matched = m;
     return GS_OK;
@@ -96,7 +96,7 @@ GS_EXPORT int32_t gs_state_ids(gs_ctx* c, const uint32_t* ids, uint64_t n, uint3
     int32_t rc = state_begin(c, "gs_state_ids");
     if (rc != GS_OK) return rc;
     if (!ids && n) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_ids: null ids");
-    rc = check_op("gs_state_ids", op, bits);
+    rc = state_check_op("gs_state_ids", op, bits);
     if (rc != GS_OK) return rc;
     for (uint64_t i = 0; i < n; ++i) // before anything is changed
         if (ids[i] >= c->n)
@@ -122,12 +122,12 @@ GS_EXPORT int32_t gs_state_count(gs_ctx* c, uint32_t mask, uint32_t value, uint6
     if (!count) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_count: null count");
     rc = state_drain(c);
     if (rc != GS_OK) return rc;
-    rc = counter_zero(c);
+    rc = state_counter_zero(c);
     if (rc != GS_OK) return rc;
     gs_launch_state_count(c->scene.state, c->n, mask, value, c->st.counter, c->stream);
     HIP_TRY(hipGetLastError());
     unsigned long long m = 0;
-    rc = counter_sum(c, &m);
+    rc = state_counter_sum(c, &m);
     if (rc != GS_OK) return rc;
     *count = m;
     return GS_OK;

@@ -10,11 +10,6 @@
 #include "gs_device.h"
 #include "gs_kernels.h"
 
-// the four operations of gs_abi.h GS_STATE_* on one byte
-__device__ __forceinline__ uint32_t state_apply(uint32_t s, uint32_t op, uint32_t bits) {
-    return op == 1u ? (s | bits) : op == 2u ? (s & ~bits) : op == 3u ? (s ^ bits) : bits;
-}
-
 // Membership of one centre (gs_abi.h: one rounding per operation, the projection's own expression tree for ph, pv, px, py).
 template <int KIND>
 __device__ __forceinline__ bool state_member(const GsRegionDev& r, float x, float y, float z) {
@@ -69,7 +64,7 @@ __global__ __launch_bounds__(256) void gs_state_region_kernel(uint8_t* __restric
             const uint32_t sv = (w >> (8 * k)) & 0xFFu;
             const bool in = ((sv & wmask) == wvalue) && state_member<KIND>(r, X[k], Y[k], Z[k]);
             hits += in ? 1u : 0u;
-            nw |= (in ? state_apply(sv, op, bits) : sv) << (8 * k);
+            nw |= (in ? gs_state_apply(sv, op, bits) : sv) << (8 * k);
         }
         if (nw != w) reinterpret_cast<uint32_t*>(state)[q] = nw; // stored only if it changed
     } else if (first < n) {
@@ -77,7 +72,7 @@ __global__ __launch_bounds__(256) void gs_state_region_kernel(uint8_t* __restric
             const uint32_t sv = state[i];
             const bool in = ((sv & wmask) == wvalue) && state_member<KIND>(r, KIND ? px[i] : 0.0f, KIND ? py[i] : 0.0f, KIND ? pz[i] : 0.0f);
             hits += in ? 1u : 0u;
-            const uint32_t nv = in ? state_apply(sv, op, bits) : sv;
+            const uint32_t nv = in ? gs_state_apply(sv, op, bits) : sv;
             if (nv != sv) state[i] = (uint8_t)nv;
         }
     }

@@ -366,6 +366,96 @@ static napi_value js_pick(napi_env env, napi_callback_info info) {
     return out;
 }
 
+/* ---- coverage: 1:1 wrappers of gs_coverage_* and gs_state_coverage ---------------------------------------------------------- */
+/* accumulateCoverage(handle, region | null) -> pixels; region = {x0, y0, x1, y1, mask, maskWidth, maskHeight} (canvas pixels) */
+static napi_value js_coverage_accumulate(napi_env env, napi_callback_info info) {
+    size_t argc = 2;
+    napi_value argv[2];
+    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    gs_ctx* ctx = argc >= 1 ? unwrap(env, argv[0]) : NULL;
+    if (!ctx) return NULL;
+    gs_cover_region rg;
+    memset(&rg, 0, sizeof(rg));
+    rg.struct_size = sizeof(rg);
+    napi_valuetype t = napi_undefined;
+    if (argc >= 2) NAPI_CALL(env, napi_typeof(env, argv[1], &t));
+    const int have = t == napi_object;
+    if (have) {
+        if (!get_u32_prop(env, argv[1], "x0", &rg.x0) || !get_u32_prop(env, argv[1], "y0", &rg.y0) || !get_u32_prop(env, argv[1], "x1", &rg.x1) ||
+            !get_u32_prop(env, argv[1], "y1", &rg.y1)) {
+            napi_throw_type_error(env, NULL, "gsplat.accumulateCoverage: {x0, y0, x1, y1} required");
+            return NULL;
+        }
+        napi_value v;
+        bool has = false;
+        void* data = NULL;
+        size_t len = 0;
+        if (napi_has_named_property(env, argv[1], "mask", &has) == napi_ok && has &&
+            napi_get_named_property(env, argv[1], "mask", &v) == napi_ok && get_bytes(env, v, &data, &len)) {
+            uint32_t cw = 0, ch = 0; /* the mask covers the CANVAS (the JS Renderer passes its canvas size): checked against the bytes given */
+            if (!get_u32_prop(env, argv[1], "maskWidth", &cw) || !get_u32_prop(env, argv[1], "maskHeight", &ch) || (double)len < (double)cw * (double)ch) {
+                napi_throw_type_error(env, NULL, "gsplat.accumulateCoverage: mask needs maskWidth, maskHeight and width * height bytes");
+                return NULL;
+            }
+            rg.mask = (const uint8_t*)data;
+        }
+    }
+    uint64_t pixels = 0;
+    int32_t rc = gs_coverage_accumulate(ctx, have ? &rg : NULL, &pixels);
+    if (rc != GS_OK) return throw_gs(env, rc);
+    napi_value out;
+    NAPI_CALL(env, napi_create_double(env, (double)pixels, &out));
+    return out;
+}
+
+/* resetCoverage(handle) */
+static napi_value js_coverage_reset(napi_env env, napi_callback_info info) {
+    size_t argc = 1;
+    napi_value argv[1];
+    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    gs_ctx* ctx = argc >= 1 ? unwrap(env, argv[0]) : NULL;
+    if (!ctx) return NULL;
+    int32_t rc = gs_coverage_reset(ctx);
+    return rc == GS_OK ? NULL : throw_gs(env, rc);
+}
+
+/* readCoverage(handle) -> ArrayBuffer (N records of 16 bytes: gs_coverage_rec) */
+static napi_value js_coverage_read(napi_env env, napi_callback_info info) {
+    size_t argc = 1;
+    napi_value argv[1];
+    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    gs_ctx* ctx = argc >= 1 ? unwrap(env, argv[0]) : NULL;
+    if (!ctx) return NULL;
+    uint64_t n = 0;
+    int32_t rc = gs_coverage_read(ctx, NULL, 0, &n);
+    if (rc != GS_OK) return throw_gs(env, rc);
+    void* dst = NULL;
+    napi_value ab;
+    NAPI_CALL(env, napi_create_arraybuffer(env, (size_t)n * sizeof(gs_coverage_rec), &dst, &ab));
+    if (n) rc = gs_coverage_read(ctx, (gs_coverage_rec*)dst, n, &n);
+    return rc == GS_OK ? ab : throw_gs(env, rc);
+}
+
+/* stateCoverage(handle, minHits, minWeight, covered, whereMask, whereValue, op, bits) -> matched */
+static napi_value js_state_coverage(napi_env env, napi_callback_info info) {
+    size_t argc = 8;
+    napi_value argv[8];
+    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    gs_ctx* ctx = argc >= 8 ? unwrap(env, argv[0]) : NULL;
+    if (!ctx) return NULL;
+    uint32_t u[6]; /* minHits, covered, whereMask, whereValue, op, bits */
+    static const int at[6] = {1, 3, 4, 5, 6, 7};
+    for (int k = 0; k < 6; ++k) NAPI_CALL(env, napi_get_value_uint32(env, argv[at[k]], &u[k]));
+    double min_weight = 0;
+    NAPI_CALL(env, napi_get_value_double(env, argv[2], &min_weight));
+    uint64_t matched = 0;
+    int32_t rc = gs_state_coverage(ctx, u[0], (float)min_weight, u[1], u[2], u[3], u[4], u[5], &matched);
+    if (rc != GS_OK) return throw_gs(env, rc);
+    napi_value out;
+    NAPI_CALL(env, napi_create_double(env, (double)matched, &out));
+    return out;
+}
+
 /* ---- splat state (GS_FLAG_SPLAT_STATE): 1:1 wrappers of gs_state_* --------------------------------------------------------- */
 static int get_f32x3_prop(napi_env env, napi_value obj, const char* name, float* out) {
     napi_value v, e;
@@ -960,6 +1050,8 @@ static napi_value init(napi_env env, napi_value exports) {
         {"listState", js_list_state}, {"exportSplats", js_export_splats}, {"compact", js_compact},
         {"exportPly", js_export_ply}, {"savePly", js_save_ply},
         {"composeTransform", js_compose_transform}, {"transformSplats", js_transform_splats},
+        {"accumulateCoverage", js_coverage_accumulate}, {"resetCoverage", js_coverage_reset},
+        {"readCoverage", js_coverage_read}, {"stateCoverage", js_state_coverage},
     };
     for (size_t i = 0; i < sizeof(fns) / sizeof(fns[0]); ++i) {
         napi_value f;
@@ -981,6 +1073,7 @@ static napi_value init(napi_env env, napi_value exports) {
     set_num(env, exports, "PICK_NONE", GS_PICK_NONE);
     set_num(env, exports, "PICK_MAX_QUERIES", GS_PICK_MAX_QUERIES);
     set_num(env, exports, "PICK_MAX_CONTRIB", GS_PICK_MAX_CONTRIB);
+    set_num(env, exports, "COVERAGE_REC_BYTES", (double)sizeof(gs_coverage_rec));
     return exports;
 }
 

@@ -65,7 +65,8 @@ ABI_SYMBOLS = ("gs_last_error", "gs_abi_version", "gs_create", "gs_destroy", "gs
                "gs_render", "gs_render_debug", "gs_render_to", "gs_wait", "gs_render_host", "gs_wait_ticket", "gs_host_alloc", "gs_host_free", "gs_read_rgba8", "gs_read_buffer", "gs_device_ptr",
                "gs_get_stats", "gs_pick", "gs_state_region", "gs_state_ids", "gs_state_count", "gs_state_write",
                "gs_state_list", "gs_export_splats", "gs_export_splats_device", "gs_compact", "gs_ply_save", "gs_export_ply",
-               "gs_xform_compose", "gs_transform_splats", "gs_set_option", "gs_slab_width", "gs_assemble_slabs", "gs_sort_pairs_u32",
+               "gs_xform_compose", "gs_transform_splats",
+               "gs_coverage_accumulate", "gs_coverage_reset", "gs_coverage_read", "gs_state_coverage", "gs_set_option", "gs_slab_width", "gs_assemble_slabs", "gs_sort_pairs_u32",
                "gs_exclusive_scan_u32")
 
 
@@ -113,9 +114,20 @@ class GsXform(ctypes.Structure):
                 ("log_scale", ctypes.c_float), ("sh1", ctypes.c_float * 9), ("sh2", ctypes.c_float * 25), ("sh3", ctypes.c_float * 49)]
 
 
+class GsCoverageRec(ctypes.Structure):
+    _fields_ = [("sum_q", ctypes.c_uint64), ("hits", ctypes.c_uint32), ("max_weight", ctypes.c_float)]
+
+
+class GsCoverRegion(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("x0", ctypes.c_uint32), ("y0", ctypes.c_uint32), ("x1", ctypes.c_uint32),
+                ("y1", ctypes.c_uint32), ("mask", ctypes.c_void_p)]
+
+
 # numpy views of the same records (what Renderer.pick returns)
 PICK_RESULT_DTYPE = np.dtype([(n, np.float32 if t is ctypes.c_float else np.uint32) for n, t in GsPickResult._fields_])
 PICK_CONTRIB_DTYPE = np.dtype([("id", np.uint32), ("weight", np.float32)])
+# gs_coverage_rec (what Renderer.read_coverage returns): sum_q / 2^32 is the sum of the weights alpha T, floor'ed per accepted pair
+COVERAGE_DTYPE = np.dtype([("sum_q", np.uint64), ("hits", np.uint32), ("max_weight", np.float32)])
 
 
 class GsError(RuntimeError):
@@ -173,6 +185,10 @@ def load():
     L.gs_xform_compose.argtypes = [ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.c_float,
                                    ctypes.POINTER(ctypes.c_float), ctypes.POINTER(GsXform)]
     L.gs_transform_splats.argtypes = [vp, u32, u32, ctypes.POINTER(GsXform), ctypes.POINTER(u64)]
+    L.gs_coverage_accumulate.argtypes = [vp, ctypes.POINTER(GsCoverRegion), ctypes.POINTER(u64)]
+    L.gs_coverage_reset.argtypes = [vp]
+    L.gs_coverage_read.argtypes = [vp, vp, u64, ctypes.POINTER(u64)]
+    L.gs_state_coverage.argtypes = [vp, u32, ctypes.c_float, u32, u32, u32, u32, u32, ctypes.POINTER(u64)]
     L.gs_set_option.argtypes = [vp, i32, ctypes.c_int64]
     L.gs_slab_width.argtypes = [vp, ctypes.POINTER(u32), ctypes.POINTER(u32)]
     L.gs_assemble_slabs.argtypes = [vp, vp, ctypes.POINTER(u32), u32, u64, vp]

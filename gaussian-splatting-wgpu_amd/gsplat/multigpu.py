@@ -76,6 +76,25 @@ def merge_picks(per_rank_results):
     return allr[np.argmax(ok, axis=0), np.arange(allr.shape[1])]
 
 
+def merge_coverage(per_rank_planes):
+    """Merges the coverage planes of all ranks (Renderer.read_coverage on every rank's slab context, after the same
+    accumulate_coverage calls): every rank saw its own slab's pixels, so sum_q and hits add (modulo 2^64 / 2^32, as on the
+    device) and max_weight is the largest.  Integer adds and a maximum: the merged planes are what one whole-canvas context
+    accumulates, bit for bit.  `per_rank_planes`: a sequence of _abi.COVERAGE_DTYPE arrays (or one (world, N) array)."""
+    from . import _abi
+    parts = [np.asarray(p) for p in per_rank_planes]
+    if not parts:
+        raise ValueError("merge_coverage: no planes")
+    if any(p.dtype != _abi.COVERAGE_DTYPE or p.shape != parts[0].shape or p.ndim != 1 for p in parts):
+        raise ValueError("merge_coverage: the ranks hold different scenes")
+    allp = np.stack(parts)
+    out = np.zeros(parts[0].shape, _abi.COVERAGE_DTYPE)
+    out["sum_q"] = allp["sum_q"].sum(axis=0, dtype=np.uint64)
+    out["hits"] = allp["hits"].sum(axis=0, dtype=np.uint32)
+    out["max_weight"] = allp["max_weight"].max(axis=0)
+    return out
+
+
 class SlabExchange:
     """Gathers per-rank slab images and assembles the frame.  Works on any torch.distributed backend
     (tested with gloo on CPU); on GPUs the assembly runs in the library (gs_assemble_slabs)."""

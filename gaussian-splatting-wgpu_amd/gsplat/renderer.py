@@ -273,6 +273,61 @@ class Renderer:
     def unhide_all(self):
         return self.state_region(_abi.GS_REGION_ALL, _abi.GS_STATE_CLEAR, _abi.GS_SPLAT_HIDDEN)
 
+    # -- coverage: per-splat contribution of the last frame, select by what is seen ---------------------------
+    def accumulate_coverage(self, rect=None, mask=None):
+        """gs_coverage_accumulate: ADDS to this renderer's coverage planes what the last frame shows of the canvas pixels in
+        rect = (x0, y0, x1, y1) (half open; None = the whole canvas), optionally AND mask = u8[height, width] of the canvas
+        (nonzero = inside): for every pixel and every list entry the blend accepts there, the entry's splat gets hits += 1,
+        sum_q += floor(w 2^32) and max_weight = max(max_weight, w), w = alpha T.  Many views, one accumulation.  Returns the
+        number of pixels of the region in this renderer's slab (0 when the region misses it)."""
+        r = m = None  # (kept alive until the call returns)
+        if rect is not None or mask is not None:
+            r = _abi.GsCoverRegion()
+            r.struct_size = ctypes.sizeof(_abi.GsCoverRegion)
+            r.x0, r.y0, r.x1, r.y1 = (int(v) for v in rect) if rect is not None else (0, 0, self.canvas.width, self.canvas.height)
+            if mask is not None:
+                m = np.ascontiguousarray(mask, dtype=np.uint8)
+                if m.shape != (self.canvas.height, self.canvas.width):
+                    raise ValueError("accumulate_coverage: the mask must be u8[canvas.height, canvas.width]")
+                r.mask = m.ctypes.data
+        pixels = ctypes.c_uint64()
+        check(self._L.gs_coverage_accumulate(self._ctx, ctypes.byref(r) if r is not None else None, ctypes.byref(pixels)))
+        return int(pixels.value)
+
+    def reset_coverage(self):
+        """gs_coverage_reset: zeroes the coverage planes."""
+        check(self._L.gs_coverage_reset(self._ctx))
+
+    def read_coverage(self):
+        """gs_coverage_read: the planes as a structured array (_abi.COVERAGE_DTYPE: sum_q, hits, max_weight), one record per
+        resident splat; all zero before any accumulate and after an upload or a compaction."""
+        n = ctypes.c_uint64()
+        check(self._L.gs_coverage_read(self._ctx, None, 0, ctypes.byref(n)))
+        out = np.zeros(n.value, dtype=_abi.COVERAGE_DTYPE)
+        if n.value:
+            check(self._L.gs_coverage_read(self._ctx, out.ctypes.data, out.size, ctypes.byref(n)))
+        return out
+
+    def state_coverage(self, op, bits, min_hits=1, min_weight=0.0, covered=True, where=(0, 0)):
+        """gs_state_coverage: applies `op` (GS_STATE_*) with `bits` to the splats whose byte passes (s & where[0]) == where[1]
+        and for which (hits >= min_hits and max_weight >= min_weight) == covered; covered=False names everything NOT seen,
+        splats that were never listed included.  Returns how many those are."""
+        matched = ctypes.c_uint64()
+        check(self._L.gs_state_coverage(self._ctx, int(min_hits), float(min_weight), 1 if covered else 0, int(where[0]), int(where[1]),
+                                        int(op), int(bits), ctypes.byref(matched)))
+        return int(matched.value)
+
+    def select_visible(self, rect=None, mask=None, min_weight=0.0, op=_abi.GS_STATE_SET):
+        """Selects what the last frame SHOWS in the region (not what lies behind it): reset + accumulate + state_coverage on
+        GS_SPLAT_SELECTED.  Returns how many splats are covered."""
+        self.reset_coverage()
+        self.accumulate_coverage(rect, mask)
+        return self.state_coverage(op, _abi.GS_SPLAT_SELECTED, 1, min_weight, True)
+
+    def hide_unseen(self, min_hits=1, min_weight=0.0):
+        """Hides every splat the accumulated views do not show (floaters behind surfaces, buried interiors); returns their number."""
+        return self.state_coverage(_abi.GS_STATE_SET, _abi.GS_SPLAT_HIDDEN, min_hits, min_weight, False)
+
     # -- splat edits: list, export, compact and save resident splats by state ------------------------------
     def list_state(self, mask, value):
         """gs_state_list: the indices of the splats with (s & mask) == value, ascending, uint32[n]."""
@@ -490,6 +545,25 @@ class PipelinedRenderer:
 
     def unhide_all(self):
         return self._state_owner().unhide_all()
+
+    # coverage: the planes are the owner's, and so is the frame they describe (slot 0's last one)
+    def accumulate_coverage(self, *a, **kw):
+        return self._state_owner().accumulate_coverage(*a, **kw)
+
+    def reset_coverage(self):
+        return self._state_owner().reset_coverage()
+
+    def read_coverage(self):
+        return self._state_owner().read_coverage()
+
+    def state_coverage(self, *a, **kw):
+        return self._state_owner().state_coverage(*a, **kw)
+
+    def select_visible(self, *a, **kw):
+        return self._state_owner().select_visible(*a, **kw)
+
+    def hide_unseen(self, *a, **kw):
+        return self._state_owner().hide_unseen(*a, **kw)
 
     # splat edits go to the owner too; after a compaction the other members borrow the new scene, as the constructor made them
     def list_state(self, mask, value):

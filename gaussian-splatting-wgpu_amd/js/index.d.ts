@@ -37,6 +37,13 @@ export class Renderer {
   readDepth(normalized?: boolean): Float32Array;
   /** gs_pick on the last frame: queries = x,y pairs of canvas pixels (at most 65536 pairs); the canonical (EXACT) blend's answer. */
   pick(queries: Uint32Array, maxContrib?: number): PickResult;
+  /** Adds what the last frame shows of the region's canvas pixels (null: the whole canvas) to the per-splat coverage planes; returns the region's pixels in this renderer's slab. */
+  accumulateCoverage(region?: CoverRegion | null): number;
+  resetCoverage(): void;
+  /** count records of 16 bytes (gs_coverage_rec); record i: u64[2 i] sumQ, u32[4 i + 2] hits, f32[4 i + 3] maxWeight (COVERAGE_FIELD holds the byte offsets). */
+  readCoverage(): { count: number; bytes: ArrayBuffer; u64: BigUint64Array; u32: Uint32Array; f32: Float32Array };
+  /** FLAG.SPLAT_STATE: applies op with bits to the splats that pass the where filter and for which (hits >= minHits && maxWeight >= minWeight) == covered; returns how many those are. */
+  stateCoverage(filter: { minHits?: number; minWeight?: number; covered?: boolean; whereMask?: number; whereValue?: number }, op: number, bits: number): number;
   setOption(key: number, value: number): void;
   /** FLAG.SPLAT_STATE: applies op (STATE.SET / CLEAR / TOGGLE / ASSIGN) with bits to every splat whose centre lies in the region and whose byte passes the where filter; returns how many those are. */
   stateRegion(region: StateRegion, op: number, bits: number): number;
@@ -63,6 +70,9 @@ export interface StateRegion {
   kind: number; a?: number[]; b?: number[]; x0?: number; y0?: number; x1?: number; y1?: number;
   uniforms?: Float32Array; mask?: Uint8Array; whereMask?: number; whereValue?: number;
 }
+export interface CoverRegion { x0?: number; y0?: number; x1?: number; y1?: number; mask?: Uint8Array }
+export const COVERAGE: { REC_BYTES: 16 };
+export const COVERAGE_FIELD: { sumQ: 0; hits: 8; maxWeight: 12 };
 export const STATE: { HIDDEN: 0x1; SELECTED: 0x2; SET: 1; CLEAR: 2; TOGGLE: 3; ASSIGN: 4 };
 export const REGION: { ALL: 0; SPHERE: 1; BOX: 2; SCREEN_RECT: 3; SCREEN_MASK: 4 };
 export const OPT: { SELECT_TINT: 11 };

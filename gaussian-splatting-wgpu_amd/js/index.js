@@ -1,7 +1,7 @@
 'use strict';
 // gsplat (Node host): the reference's class surface -- Renderer, Camera, InteractiveCamera,
 // PackedGaussians, loadFileAsArrayBuffer -- backed by the MI355X-native C ABI through N-API.
-const { Renderer, loadNative, savePly, composeTransform, PickResult, PICK, PICK_FIELD, STATE, REGION } = require('./renderer');
+const { Renderer, loadNative, savePly, composeTransform, PickResult, PICK, PICK_FIELD, STATE, REGION, COVERAGE, COVERAGE_FIELD } = require('./renderer');
 const { Camera, InteractiveCamera, cameraFromJSON, loadCameraFile, getProjectionMatrix, focal2fov } = require('./camera');
 const { PackedGaussians, loadFileAsArrayBuffer } = require('./ply');
 const { mat4, mat3, vec3 } = require('./mat4');
@@ -23,5 +23,6 @@ module.exports = {
   FLAG: { EXACT_BLEND: 0x1, F32_TAP: 0x2, TIMING: 0x4, AUX_OUTPUTS: 0x8, SPLAT_STATE: 0x10 },
   OPT: { SELECT_TINT: 11 },
   STATE, REGION, // STATE: { HIDDEN: 0x1, SELECTED: 0x2, SET: 1, CLEAR: 2, TOGGLE: 3, ASSIGN: 4 }; REGION: { ALL: 0, SPHERE: 1, BOX: 2, SCREEN_RECT: 3, SCREEN_MASK: 4 }
+  COVERAGE, COVERAGE_FIELD, // COVERAGE: { REC_BYTES: 16 }; COVERAGE_FIELD: { sumQ: 0, hits: 8, maxWeight: 12 } (byte offsets)
   PICK, PICK_FIELD, PickResult, // PICK: { OK: 0, OUTSIDE_SLAB: 1, NONE: 0xFFFFFFFF, MAX_QUERIES: 65536, MAX_CONTRIB: 256 }
 };

@@ -179,6 +179,33 @@ class Renderer {
     if (!(bytes instanceof Uint8Array)) throw new TypeError('gsplat: writeState expects a Uint8Array of N state bytes');
     loadNative().writeState(this.handle, bytes);
   }
+  // Coverage: which splats the last frame actually SHOWS.  accumulateCoverage({x0, y0, x1, y1, mask}) ADDS, for every canvas pixel of
+  // the rect (null: the whole canvas; mask: Uint8Array[height * width] of the canvas, nonzero = inside) and every list entry the blend
+  // accepts there, hits += 1, sumQ += floor(w 2^32) and maxWeight = max(maxWeight, w) to the record of the entry's splat (w = alpha T);
+  // returns the pixels of the region in this renderer's slab.  Many views, one accumulation; an upload or a compaction drops the planes.
+  accumulateCoverage(region = null) {
+    let r = null;
+    if (region) {
+      r = Object.assign({ x0: 0, y0: 0, x1: this.canvas.width, y1: this.canvas.height }, region);
+      if (r.mask) {
+        if (!(r.mask instanceof Uint8Array)) throw new TypeError('gsplat: accumulateCoverage expects mask to be a Uint8Array');
+        r.maskWidth = this.canvas.width; r.maskHeight = this.canvas.height;
+      }
+    }
+    return loadNative().accumulateCoverage(this.handle, r);
+  }
+  resetCoverage() { loadNative().resetCoverage(this.handle); }
+  // -> {count, bytes, u64, u32, f32}: count records of 16 bytes (gs_coverage_rec) and typed-array views over them, record i at
+  // u64[2 i + COVERAGE_FIELD.sumQ / 8], u32[4 i + COVERAGE_FIELD.hits / 4], f32[4 i + COVERAGE_FIELD.maxWeight / 4]
+  readCoverage() {
+    const bytes = loadNative().readCoverage(this.handle);
+    return { count: bytes.byteLength / COVERAGE.REC_BYTES, bytes, u64: new BigUint64Array(bytes), u32: new Uint32Array(bytes), f32: new Float32Array(bytes) };
+  }
+  // FLAG.SPLAT_STATE: applies `op` with `bits` to the splats that pass (s & whereMask) == whereValue and for which
+  // (hits >= minHits && maxWeight >= minWeight) == covered; covered = false names everything NOT seen.  Returns how many those are.
+  stateCoverage({ minHits = 1, minWeight = 0, covered = true, whereMask = 0, whereValue = 0 } = {}, op, bits) {
+    return loadNative().stateCoverage(this.handle, minHits >>> 0, +minWeight, covered ? 1 : 0, whereMask >>> 0, whereValue >>> 0, op >>> 0, bits >>> 0);
+  }
   // Splat edits: bring splats back out of the library and make an edit permanent.  A splat matches when (s & mask) == value;
   // matching splats always come in ascending index order; (0, 0) is every splat and needs no FLAG.SPLAT_STATE.
   listState(mask, value) { return new Uint32Array(loadNative().listState(this.handle, mask >>> 0, value >>> 0)); }
@@ -224,6 +251,10 @@ function savePly(file, gaussians, shDegree = 3) {
 const STATE = { HIDDEN: 0x1, SELECTED: 0x2, SET: 1, CLEAR: 2, TOGGLE: 3, ASSIGN: 4 };
 const REGION = { ALL: 0, SPHERE: 1, BOX: 2, SCREEN_RECT: 3, SCREEN_MASK: 4 };
 
+const COVERAGE = { REC_BYTES: 16 };
+// byte offset of every field of a 16-byte gs_coverage_rec
+const COVERAGE_FIELD = { sumQ: 0, hits: 8, maxWeight: 12 };
+
 const PICK = { OK: 0, OUTSIDE_SLAB: 1, NONE: 0xFFFFFFFF, MAX_QUERIES: 65536, MAX_CONTRIB: 256 };
 // word index of every field of a 48-byte gs_pick_result
 const PICK_FIELD = { status: 0, listLength: 1, hitCount: 2, firstId: 3, firstDepth: 4, maxId: 5, maxWeight: 6, medianId: 7, medianDepth: 8,
@@ -256,4 +287,4 @@ class PickResult {
   }
 }
 
-module.exports = { Renderer, loadNative, savePly, composeTransform, PickResult, PICK, PICK_FIELD, STATE, REGION };
+module.exports = { Renderer, loadNative, savePly, composeTransform, PickResult, PICK, PICK_FIELD, STATE, REGION, COVERAGE, COVERAGE_FIELD };

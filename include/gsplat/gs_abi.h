@@ -432,6 +432,64 @@ int32_t gs_xform_compose(const float rot_rxyz[4], const float translate[3], floa
  * no-op that still reports *matched. */
 int32_t gs_transform_splats(gs_ctx* ctx, uint32_t mask, uint32_t value, const gs_xform* x, uint64_t* matched);
 
+/* ---- coverage: per-splat contribution of the LAST frame, select by what is seen ---------------------
+ * gs_state_region selects THROUGH surfaces and gs_pick answers for one pixel at a time; neither can say which splats the user
+ * actually SEES in a region, nor that a splat contributes to no pixel of any of a set of views (floaters, buried interior
+ * splats, importance scores for decimation).  The coverage planes keep one 16-byte record per resident splat and
+ * gs_coverage_accumulate ADDS to them what the last frame shows of a set P of canvas pixels: a rect, optionally AND a
+ * u8[height][width] mask (nonzero = inside), intersected with the ctx's slab.  Many views, one accumulation.
+ * Every (pixel p in P, entry e of p's tile list) that the blend ACCEPTS contributes to the record of e's gaussian.  Accepted
+ * means cond = 1 exactly as gs_pick defines it above: compute_tiles.wgsl:44-66 in the canonical (GS_FLAG_EXACT_BLEND)
+ * arithmetic -- one f32 rounding per written operation, the oracle's exp, wg_min -- whatever blend the frame itself used.  The
+ * contribution is the entry's weight w = fl(alpha * T), T taken before the entry (0 < w <= 0.99):
+ *     sum_q      += (uint32_t)(w * 4294967296.0f)     floor(w 2^32); the product is exact
+ *     hits       += 1                                  per accepted (pixel, entry) PAIR, not per pixel: a gaussian can sit twice in
+ *                                                      one tile's list (the alias column of write_tile_ids.wgsl:26-31)
+ *     max_weight  = max(max_weight, w)
+ * Integer adds and a maximum (taken on the bit pattern, w > 0): the planes do not depend on the order in which the device adds,
+ * two runs agree bit for bit and a host can restate them exactly (no float sum is involved).  sum_q wraps modulo 2^64 and hits
+ * modulo 2^32; neither can happen before 2^32 accepted pairs of ONE splat (sum_q grows by less than 2^32 per pair).
+ * The mean weight is sum_q / 2^32 / hits; sum_q / 2^32 is the importance score sum of alpha T.
+ * The result is the same for tight and reference binning (a tight list drops only entries no pixel accepts, and an entry whose
+ * sub-block bit is clear reaches 1/255 on no pixel of that block), gs_render and gs_render_debug, every GS_OPT_EMIT_ORDER,
+ * EXACT and fused frames, direct and graph-replayed frames.  Hidden splats are in no list and get nothing.
+ * Ownership: the planes belong to the ctx the calls are made on (the root of a frames-in-flight ring; a borrower of
+ * gs_share_splats keeps its own): N x 16 bytes, allocated and zeroed by the first of the four calls below.  They are DROPPED --
+ * they read as zero again -- by every gs_upload_*, gs_share_splats and gs_compact (the records are not carried through a
+ * compaction), and untouched by state calls and transforms: a host that moves splats resets.  Multi-GPU: every rank accumulates
+ * its own slab's pixels; the host adds the planes (sum_q, hits) and takes the maximum (max_weight). */
+typedef struct gs_coverage_rec { /* 16 bytes, one per resident splat */
+    uint64_t sum_q;      /* sum of floor(w 2^32) over the accepted pairs */
+    uint32_t hits;       /* accepted (pixel, entry) pairs */
+    float max_weight;    /* largest w; 0 if none */
+} gs_coverage_rec;
+typedef struct gs_cover_region {
+    uint32_t struct_size;    /* = sizeof(gs_cover_region) */
+    uint32_t x0, y0, x1, y1; /* canvas pixels [x0, x1) x [y0, y1) */
+    const uint8_t* mask;     /* NULL, or host u8[height][width] of the CANVAS, nonzero = inside (copied): P = rect AND mask */
+} gs_cover_region;
+/* Adds the contribution of the LAST frame enqueued (its ring member, like gs_pick), waiting for it first if it is pending; runs on
+ * that member's stream and returns when done.  region NULL = the whole canvas.  *pixels (may be NULL) receives |P| in THIS ctx's
+ * slab; a region that misses the slab entirely is GS_OK with *pixels = 0, so a multi-GPU host sends one region to every rank.
+ * One wave per 8x8 pixel block that intersects P.  It is not a frame: no tap, statistic, option or captured graph changes.
+ * GS_ERR_NO_SCENE before any upload, GS_ERR_NO_FRAME when no frame has been rendered since gs_create / the last upload or
+ * compaction, GS_ERR_INVALID_ARGUMENT (the message names the numbers) for a wrong struct_size, x1 > width, y1 > height or an empty
+ * rect. */
+int32_t gs_coverage_accumulate(gs_ctx* ctx, const gs_cover_region* region, uint64_t* pixels);
+/* Zeroes the planes.  Completes all frames enqueued on the ctx's ring first, as the state calls do. */
+int32_t gs_coverage_reset(gs_ctx* ctx);
+/* The planes in HOST memory, N records in splat order, with gs_state_list's conventions: dst == NULL: only *n (= N) is written
+ * (query); cap < N: GS_ERR_INVALID_ARGUMENT, the message names the count needed, nothing is written to dst.  Works on any ctx. */
+int32_t gs_coverage_read(gs_ctx* ctx, gs_coverage_rec* dst, uint64_t cap, uint64_t* n);
+/* Applies `op` with `bits` exactly as gs_state_region does, to the splats that pass (s & where_mask) == where_value and for which
+ *     (hits >= min_hits && max_weight >= min_weight) == (covered != 0)
+ * so covered = 0 names everything NOT seen, splats that were never in a list included.  *matched (may be NULL): their number.
+ * Needs GS_FLAG_SPLAT_STATE and is refused like the other state calls without it; a NaN or negative min_weight, bits or
+ * where_mask above 0xFF or an unknown op: GS_ERR_INVALID_ARGUMENT.  Completes the ring's frames first; one streaming pass over
+ * 17 bytes per splat. */
+int32_t gs_state_coverage(gs_ctx* ctx, uint32_t min_hits, float min_weight, uint32_t covered, uint32_t where_mask, uint32_t where_value,
+                          uint32_t op, uint32_t bits, uint64_t* matched);
+
 /* Tuning / profiling knobs. */
 #define GS_OPT_BLEND_ABLATION 1  /* bit 3 (8): the workgroup-per-tile blend kernel at tiles 16 and 32 (identical results; default = one
                                     wave per 8x8 pixel block); bit 2 (4): every blend kernel without its two parking culls (live box,
