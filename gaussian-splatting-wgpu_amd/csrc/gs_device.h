@@ -103,9 +103,27 @@ struct GsScene {
 #define GS_ST_HIDDEN 1u
 #define GS_ST_SELECTED 2u
 struct GsTint { float t[3]; float k; };
-// the four operations of gs_abi.h GS_STATE_* on one byte (k_state.hip, k_coverage.hip)
+// the four operations of gs_abi.h GS_STATE_* on one byte (k_state.hip)
 __device__ __forceinline__ uint32_t gs_state_apply(uint32_t s, uint32_t op, uint32_t bits) {
     return op == 1u ? (s | bits) : op == 2u ? (s & ~bits) : op == 3u ? (s ^ bits) : bits;
+}
+// The state bytes of quad q (splats 4q .. 4q+3) as one word, byte k = splat 4q + k, and how many of them the plane holds (0 beyond
+// N).  The last partial word is read byte by byte: nothing past N is read.  A null plane (a context without GS_FLAG_SPLAT_STATE)
+// reads as all-zero bytes.  The selection's reader (k_export.hip); the state pass (k_state.hip) reads its word the same way, written
+// out, because it also stores what it read.
+struct GsStateQuad { uint32_t w, valid; };
+__device__ __forceinline__ GsStateQuad gs_state_quad(const uint8_t* __restrict__ state, uint32_t n, uint32_t q) {
+    const uint64_t first = (uint64_t)q * 4u;
+    uint32_t w = 0u, valid = 0u;
+    if (first + 4u <= n) {
+        valid = 4u;
+        if (state) w = reinterpret_cast<const uint32_t*>(state)[q];
+    } else if (first < n) {
+        valid = (uint32_t)(n - first);
+        if (state)
+            for (uint32_t k = 0; k < valid; ++k) w |= (uint32_t)state[first + k] << (8u * k);
+    }
+    return GsStateQuad{w, valid};
 }
 
 struct GsPlyTable { // where the 11 + 48 values of a packed record live in a raw .ply vertex (gs_upload_ply)
@@ -260,6 +278,40 @@ __device__ __forceinline__ uint2 gs_tile_range(const uint32_t* __restrict__ rang
     if (end > capacity) end = capacity;
     return make_uint2(start, end);
 }
+
+// ---- an entry of the last frame's lists as a lane holds it between the fetch and the evaluation (k_pick.hip, k_coverage.hip) ------
+struct GsListRec {
+    float ux, uy, cx, cy, cz, z, op; // uv; conic + depth; opacity
+    uint32_t id;
+    bool live;
+};
+// Entry i of [.., end): the three pieces of its GaussianData record.  id_mask: on a tight frame the sub-block mask rides above the
+// id (gs_tight.h); want: the bit of that mask the caller's block needs (0: every entry; an entry without it stays dead and its
+// record is not gathered).
+__device__ __forceinline__ GsListRec gs_list_fetch(const uint4* __restrict__ gdata, const uint32_t* __restrict__ values, uint32_t i, uint32_t end,
+                                                   uint32_t id_mask, uint32_t want, uint32_t n) {
+    GsListRec r;
+    r.ux = r.uy = r.cx = r.cy = r.cz = r.z = r.op = 0.0f;
+    r.id = 0u;
+    r.live = false;
+    if (i < end) {
+        const uint32_t v = values[i];
+        const uint32_t g = v & id_mask;
+        if (g < n && (want == 0u || (v & want) != 0u)) { // (a list never holds an id >= n; never gather out of bounds)
+            const uint4 p0 = gdata[(uint64_t)g * 4 + 0];
+            const uint4 p1 = gdata[(uint64_t)g * 4 + 1];
+            r.op = __uint_as_float(((const uint32_t*)gdata)[(uint64_t)g * 16 + 11]);
+            r.ux = __uint_as_float(p0.x); r.uy = __uint_as_float(p0.y);
+            r.cx = __uint_as_float(p1.x); r.cy = __uint_as_float(p1.y); r.cz = __uint_as_float(p1.z); r.z = __uint_as_float(p1.w);
+            r.id = g;
+            r.live = true;
+        }
+    }
+    return r;
+}
+// lane l's value on every lane (v_readlane: l is wave-uniform)
+__device__ __forceinline__ uint32_t gs_bcast(uint32_t v, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, l); }
+__device__ __forceinline__ float gs_bcast(float v, int l) { return __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(v), l)); }
 
 // Columns of a rect that fall in the slab; column ntx aliases to column 0 of the next tile row
 // (write_tile_ids.wgsl:26-31).  Returns main-run [xa,xb) and whether the alias column is owned.

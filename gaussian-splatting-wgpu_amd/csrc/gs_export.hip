@@ -13,28 +13,15 @@
 
 #include "gs_runtime.h"
 
-// What every entry point checks first; drains the ring.  An error of the wait is the call's error: nothing is done.
-int32_t edit_begin(gs_ctx* c, const char* who, uint32_t mask, uint32_t value) {
-    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, "%s: null ctx", who);
-    if (mask > 0xFFu || value > 0xFFu) return fail(GS_ERR_INVALID_ARGUMENT, "%s: filter (0x%x, 0x%x) does not fit the state byte", who, mask, value);
-    if ((mask | value) && !has_state(c)) // (0, 0) matches every splat: what is resident can be exported without a plane
-        return fail(GS_ERR_INVALID_ARGUMENT, "%s: the context was created without GS_FLAG_SPLAT_STATE", who);
-    if (!c->scene_mem) return fail(GS_ERR_NO_SCENE, "%s: no splats uploaded", who);
-    const int32_t rc = gs_wait(c);
-    if (rc != GS_OK) return rc;
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    return GS_OK;
-}
+// What every entry point does first (gs_runtime.h): the refusals, a filter that needs the plane among them, and the drain of the ring.
+static int32_t edit_begin(gs_ctx* c, const char* who, uint32_t mask, uint32_t value) { return resident_begin(c, who, Plane::filtered, mask, value); }
 
 // Counts the matching splats (count + scan launches, the total read back like the state calls' counter); with want_ids also
 // writes their indices, ascending, to c->ex.ids.
 int32_t edit_select(gs_ctx* c, uint32_t mask, uint32_t value, bool want_ids, uint64_t* total) {
     const uint32_t nb = gs_select_blocks(c->n);
-    if ((uint64_t)nb + 1 > c->ex.counts_cap) {
-        c->ex.counts_cap = 0;
-        HIP_TRY(hipMalloc(c->ex.counts.out(), ((size_t)nb + 1) * 4));
-        c->ex.counts_cap = (uint64_t)nb + 1;
-    }
+    int32_t rc = c->ex.counts.reserve((uint64_t)nb + 1);
+    if (rc != GS_OK) return rc;
     gs_launch_select_count(c->scene.state, c->n, mask, value, c->ex.counts, c->stream);
     HIP_TRY(hipGetLastError());
     uint32_t t = 0;
@@ -42,11 +29,8 @@ int32_t edit_select(gs_ctx* c, uint32_t mask, uint32_t value, bool want_ids, uin
     HIP_TRY(hipStreamSynchronize(c->stream));
     *total = t;
     if (!want_ids || !t) return GS_OK;
-    if (t > c->ex.ids_cap) {
-        c->ex.ids_cap = 0;
-        HIP_TRY(hipMalloc(c->ex.ids.out(), (size_t)t * 4));
-        c->ex.ids_cap = t;
-    }
+    rc = c->ex.ids.reserve(t);
+    if (rc != GS_OK) return rc;
     gs_launch_select_scatter(c->scene.state, c->n, mask, value, c->ex.counts, c->ex.ids, t, c->stream);
     HIP_TRY(hipGetLastError());
     return GS_OK;

@@ -75,6 +75,9 @@ void gs_launch_state_region(uint32_t kind, uint8_t* state, const GsScene& s, uin
                             uint32_t where_mask, uint32_t where_value, unsigned long long* matched, hipStream_t st);
 void gs_launch_state_ids(uint8_t* state, const uint32_t* ids, uint64_t n, uint32_t op, uint32_t bits, hipStream_t st);
 void gs_launch_state_count(const uint8_t* state, uint32_t n, uint32_t mask, uint32_t value, unsigned long long* count, hipStream_t st);
+// gs_state_coverage: the region pass with a membership read from the coverage planes (16 bytes per splat: gs_coverage_rec)
+void gs_launch_state_coverage(uint8_t* state, const void* planes, uint32_t n, uint32_t min_hits, float min_weight, uint32_t covered, uint32_t op,
+                              uint32_t bits, uint32_t where_mask, uint32_t where_value, unsigned long long* matched, hipStream_t st);
 // k_export.hip: the splat edits (gs_export.hip).  Selection = splats with (s & mask) == value in ascending order: `counts` holds
 // gs_select_blocks(n) + 1 words (one per 1024 splats; after the launch their exclusive prefix, the total last), `ids` the total.
 uint32_t gs_select_blocks(uint32_t n);
@@ -94,13 +97,10 @@ void gs_launch_xform(const GsScene& s, uint32_t n, const uint32_t* ids, uint32_t
 void gs_launch_pick(const void* gdata, const uint32_t* values, const uint32_t* ranges, const GsFrame& f, uint32_t id_mask, const void* d_queries,
                     uint32_t n, void* d_results, uint32_t max_contrib, void* d_contrib, hipStream_t st);
 // k_coverage.hip: gs_coverage_accumulate, one wave per 8x8 pixel block [bx0, bx0 + nbx) x [by0, by0 + nby) (in blocks) over the last
-// frame's lists, adding into `planes` (16 bytes per splat: gs_coverage_rec); and the streaming pass of gs_state_coverage
-// (`matched` as for gs_launch_state_region)
+// frame's lists, adding into `planes` (16 bytes per splat: gs_coverage_rec)
 struct GsCoverDev { // a gs_cover_region as the kernel reads it
     uint32_t x0, y0, x1, y1; // canvas pixels [x0, x1) x [y0, y1)
     const uint8_t* mask;     // device u8[height][width] of the canvas, or null
 };
 void gs_launch_coverage(const void* gdata, const uint32_t* values, const uint32_t* ranges, const GsFrame& f, uint32_t id_mask, uint32_t bx0,
                         uint32_t by0, uint32_t nbx, uint32_t nby, const GsCoverDev& r, void* planes, hipStream_t st);
-void gs_launch_state_coverage(uint8_t* state, const void* planes, uint32_t n, uint32_t min_hits, float min_weight, uint32_t covered, uint32_t op,
-                              uint32_t bits, uint32_t where_mask, uint32_t where_value, unsigned long long* matched, hipStream_t st);

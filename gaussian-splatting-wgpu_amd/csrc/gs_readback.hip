@@ -63,6 +63,15 @@ static int32_t state_tap(gs_ctx* c, void** ptr, uint64_t* bytes) {
     return GS_OK;
 }
 
+int32_t last_frame(gs_ctx* root, const char* who, gs_ctx** out) {
+    gs_ctx* c = last_of(root);
+    if (who && !c->have_frame) return fail(GS_ERR_NO_FRAME, "%s: no frame rendered", who);
+    if (c->pending) { int32_t rc = wait_one(c); if (rc != GS_OK) return rc; } // (an overflowed frame has been re-rendered from full lists)
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    *out = c;
+    return GS_OK;
+}
+
 GS_EXPORT int32_t gs_read_buffer(gs_ctx* c, int32_t which, void* dst, uint64_t size, uint64_t* written) {
     if (!c) return fail(GS_ERR_INVALID_ARGUMENT, "gs_read_buffer: null ctx");
     if (which == GS_BUF_SPLAT_STATE) { // (state calls return when done: the plane is at rest; frames in flight only read it)
@@ -77,10 +86,7 @@ GS_EXPORT int32_t gs_read_buffer(gs_ctx* c, int32_t which, void* dst, uint64_t s
         if (bytes) HIP_TRY(hipMemcpy(dst, p, bytes, hipMemcpyDeviceToHost));
         return GS_OK;
     }
-    c = last_of(c);
-    if (!c->have_frame) return fail(GS_ERR_NO_FRAME, "gs_read_buffer: no frame rendered");
-    if (c->pending) { int32_t rc = wait_one(c); if (rc != GS_OK) return rc; }
-    HIP_TRY(hipSetDevice(c->cfg.device));
+    { int32_t rc = last_frame(c, "gs_read_buffer", &c); if (rc != GS_OK) return rc; }
     const bool tight = c->notes.last_tight;
     const uint64_t I = std::min<uint64_t>(c->h_rep->num_intersections, c->capacity);
     // two buffers are made on the host, not copied: the block masks of a frame with the reference's binning (the blend tests every
@@ -149,8 +155,8 @@ GS_EXPORT int32_t gs_device_ptr(gs_ctx* c, int32_t which, void** d_ptr) {
 
 GS_EXPORT int32_t gs_get_stats(gs_ctx* root, gs_stats* out) {
     if (!root || !out) return fail(GS_ERR_INVALID_ARGUMENT, "gs_get_stats: null argument");
-    gs_ctx* c = last_of(root); // everything below describes the context that rendered the last frame ...
-    if (c->pending) { int32_t rc = wait_one(c); if (rc != GS_OK) return rc; }
+    gs_ctx* c = nullptr; // everything below describes the context that rendered the last frame ...
+    { int32_t rc = last_frame(root, nullptr, &c); if (rc != GS_OK) return rc; }
     const FrameNotes& nt = c->notes;
     memset(out, 0, sizeof(*out));
     out->num_gaussians = c->n;
@@ -161,7 +167,6 @@ GS_EXPORT int32_t gs_get_stats(gs_ctx* root, gs_stats* out) {
     out->depth_ordered = (c->have_frame && !nt.last_by_index) ? 1u : 0u;
     if (c->have_frame) {
         if (!c->h_ctl_valid) { // the blend's counters live in the control block: fetched when somebody asks
-            HIP_TRY(hipSetDevice(c->cfg.device));
             HIP_TRY(hipMemcpy(c->h_ctl, c->ctl, offsetof(GsControl, hist), hipMemcpyDeviceToHost));
             c->h_ctl_valid = true;
         }
@@ -238,19 +243,15 @@ GS_EXPORT int32_t gs_pick(gs_ctx* root, const gs_pick_query* queries, uint32_t n
         if (queries[i].x >= root->frame.width || queries[i].y >= root->frame.height)
             return fail(GS_ERR_INVALID_ARGUMENT, "gs_pick: query %u: pixel (%u, %u) is outside the %u x %u canvas", i, queries[i].x, queries[i].y,
                         root->frame.width, root->frame.height);
-    gs_ctx* c = last_of(root);
-    if (!c->have_frame) return fail(GS_ERR_NO_FRAME, "gs_pick: no frame rendered");
-    if (c->pending) { int32_t rc = wait_one(c); if (rc != GS_OK) return rc; } // (an overflowed frame has been re-rendered from full lists)
-    HIP_TRY(hipSetDevice(c->cfg.device));
+    gs_ctx* c = nullptr;
+    int32_t rc = last_frame(root, "gs_pick", &c);
+    if (rc != GS_OK) return rc;
     auto& pk = root->pick;
     if (!pk.q) HIP_TRY(hipMalloc(pk.q.out(), (size_t)GS_PICK_MAX_QUERIES * sizeof(gs_pick_query)));
     if (!pk.r) HIP_TRY(hipMalloc(pk.r.out(), (size_t)GS_PICK_MAX_QUERIES * sizeof(gs_pick_result)));
     const uint64_t cbytes = (uint64_t)n * max_contrib * sizeof(gs_pick_contrib);
-    if (cbytes > pk.c_bytes) {
-        pk.c_bytes = 0;
-        HIP_TRY(hipMalloc(pk.c.out(), (size_t)cbytes)); // (the smaller one goes first; every earlier gs_pick has synchronised)
-        pk.c_bytes = cbytes;
-    }
+    rc = pk.c.reserve(cbytes);
+    if (rc != GS_OK) return rc;
     HIP_TRY(hipMemcpyAsync(pk.q, queries, (size_t)n * sizeof(gs_pick_query), hipMemcpyHostToDevice, c->stream));
     gs_launch_pick(c->gdata, c->notes.valsS, c->ranges, c->frame, c->notes.last_tight ? GS_ID_MASK : 0xFFFFFFFFu, pk.q, n, pk.r, max_contrib,
                    max_contrib ? pk.c.get() : nullptr, c->stream);

@@ -1,5 +1,10 @@
-// gs_runtime.h -- private to the runtime sources (gs_context / gs_frame / gs_readback / gs_state / gs_export / gs_xform / gs_coverage / gs_ply / gs_stages .hip): the error
-// channel, the owners of HIP resources, and the context.
+// gs_runtime.h -- private to the runtime sources (gs_context / gs_frame / gs_readback / gs_state / gs_export / gs_xform / gs_coverage / gs_ply / gs_stages .hip):
+//   the error channel (fail, HIP_TRY);
+//   the owners of HIP resources (Owned: DevBuf, PinnedBuf, Event, Stream, File) and Scratch, a device buffer that grows on demand;
+//   the context (gs_ctx, FrameNotes, GraphKey);
+//   what the calls on the resident splats share: the prologue of a call that drains the ring (Plane, resident_check,
+//   resident_drain, resident_begin), the last frame waited for (last_frame), the staging of a canvas mask (stage_mask), the
+//   coverage planes (cover_planes) and the splat edits' selection (edit_select).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -45,6 +50,20 @@ struct Owned {
 };
 template <class T = void> using DevBuf = Owned<T*, hipFree>;        // hipMalloc
 template <class T = void> using PinnedBuf = Owned<T*, hipHostFree>; // hipHostMalloc
+// A device scratch buffer of `cap` elements that only grows: reserve(count) leaves room for at least count of them.  What it held
+// is not kept, and is freed BEFORE the larger allocation is made (the smaller one goes first; every earlier call that used it has
+// synchronised).  cap is 0 across the allocation, so a failed hipMalloc leaves an empty buffer and not a stale capacity.
+template <class T>
+struct Scratch : DevBuf<T> {
+    uint64_t cap = 0;
+    int32_t reserve(uint64_t count) {
+        if (count <= cap) return GS_OK;
+        cap = 0;
+        HIP_TRY(hipMalloc(this->out(), (size_t)count * sizeof(T)));
+        cap = count;
+        return GS_OK;
+    }
+};
 using Event = Owned<hipEvent_t, hipEventDestroy>;
 using Stream = Owned<hipStream_t, hipStreamDestroy>;
 using File = Owned<FILE*, fclose>;
@@ -154,11 +173,11 @@ struct gs_ctx {
     uint32_t pxb_host[65] = {};
     uint32_t pxb_n = 0;
     // gs_pick (root ctx): device copies of the queries, the results and the contributor records; allocated on first use
-    struct { DevBuf<> q, r, c; uint64_t c_bytes = 0; } pick;
-    // gs_state_* (gs_state.hip): the matched / count word, device copies of an id list and of a screen mask; grown on demand
-    struct { DevBuf<unsigned long long> counter; DevBuf<uint32_t> ids; DevBuf<uint8_t> mask; uint64_t ids_cap = 0, mask_cap = 0; } st;
+    struct { DevBuf<> q, r; Scratch<uint8_t> c; } pick;
+    // gs_state_* (gs_state.hip): the matched / count word, device copies of an id list and of a canvas mask (stage_mask); grown on demand
+    struct { DevBuf<unsigned long long> counter; Scratch<uint32_t> ids; Scratch<uint8_t> mask; } st;
     // splat edits (gs_export.hip): the selection's per-workgroup counts and its id list; grown on demand
-    struct { DevBuf<uint32_t> counts, ids; uint64_t counts_cap = 0, ids_cap = 0; } ex;
+    struct { Scratch<uint32_t> counts, ids; } ex;
     // gs_coverage_* (gs_coverage.hip; root ctx): N x 16 B gs_coverage_rec, allocated and zeroed on first use, dropped with the scene
     DevBuf<> cov;
     Event ev[GS_EV_RING][GS_STAGE_COUNT + 1]; // ring of per-frame stage brackets (GS_FLAG_TIMING)
@@ -191,17 +210,32 @@ void drop_shadows(gs_ctx* c);
 // gs_frame.hip
 void drop_graph(gs_ctx* c);
 int32_t wait_one(gs_ctx* c);
-// gs_export.hip: what the splat edits and gs_transform_splats check first (drains the ring), and their selection: counts the splats
-// with (s & mask) == value and, with want_ids, leaves their indices, ascending, in c->ex.ids
-int32_t edit_begin(gs_ctx* c, const char* who, uint32_t mask, uint32_t value);
+// gs_state.hip: the prologue of a call on the resident splats that drains the ring.  resident_check holds the refusals that cost
+// nothing, in this order: null context, a filter that does not fit the state byte (Plane::filtered), a context without
+// GS_FLAG_SPLAT_STATE where the call needs the plane, no scene.  resident_drain is gs_wait (an error of the wait is the call's
+// error: nothing is applied), hipSetDevice and, with `counter`, the allocation of st.counter.  resident_begin is one after the
+// other, for the calls that check their own arguments after the drain.
+enum class Plane {
+    none,     // the call reads no state plane
+    filtered, // ... reads it for a filter other than (0, 0), which matches every splat
+    always    // ... is refused without it
+};
+int32_t resident_check(gs_ctx* c, const char* who, Plane need, uint32_t mask = 0, uint32_t value = 0);
+int32_t resident_drain(gs_ctx* c, bool counter = false);
+inline int32_t resident_begin(gs_ctx* c, const char* who, Plane need, uint32_t mask = 0, uint32_t value = 0) {
+    const int32_t rc = resident_check(c, who, need, mask, value);
+    return rc != GS_OK ? rc : resident_drain(c);
+}
+// a canvas mask (u8[height][width] of the root's canvas) copied to root->st.mask on `st`; *dev: the device copy
+int32_t stage_mask(gs_ctx* root, const uint8_t* mask, hipStream_t st, const uint8_t** dev);
+// gs_readback.hip: the ring member that rendered the last frame, waited for if it is pending, its device current.  who: refuses
+// with GS_ERR_NO_FRAME when no frame was rendered (null: the caller copes with that)
+int32_t last_frame(gs_ctx* root, const char* who, gs_ctx** c);
+// gs_coverage.hip: the coverage planes of the root context, allocated and zeroed (on `st`) by the first call that needs them
+int32_t cover_planes(gs_ctx* root, hipStream_t st);
+// gs_export.hip: the splat edits' selection: counts the splats with (s & mask) == value and, with want_ids, leaves their indices,
+// ascending, in c->ex.ids
 int32_t edit_select(gs_ctx* c, uint32_t mask, uint32_t value, bool want_ids, uint64_t* total);
-// gs_state.hip: what every state call checks first (state_begin), the drain of the ring, and the kernels' `matched` partial sums
-// (zeroed before the launch, added up after it: returns when the stream is done)
-int32_t state_begin(gs_ctx* c, const char* who);
-int32_t state_drain(gs_ctx* c);
-int32_t state_counter_zero(gs_ctx* c);
-int32_t state_counter_sum(gs_ctx* c, unsigned long long* total);
-int32_t state_check_op(const char* who, uint32_t op, uint32_t bits);
 inline gs_ctx* last_of(gs_ctx* c) { return (c && c->last) ? c->last : c; }
 inline bool has_state(const gs_ctx* c) { return (c->cfg.flags & GS_FLAG_SPLAT_STATE) != 0; }
 inline GsTint tint_of(uint32_t argb) { // a<<24 | r<<16 | g<<8 | b -> what the projection applies (each quotient one f32 division)

@@ -1,6 +1,6 @@
-// gs_state.hip -- the state plane's entry points: region and id selections, counting, restore.  Part of the C ABI
-// (include/gsplat/gs_abi.h "splat state"); the kernels are in k_state.hip, the projection that honours the plane in
-// k_preprocess.hip (STATE).
+// gs_state.hip -- the state plane's entry points: region, id and coverage selections, counting, restore.  Part of the C ABI
+// (include/gsplat/gs_abi.h "splat state"; gs_state_coverage under "coverage"); the kernels are in k_state.hip, the projection that
+// honours the plane in k_preprocess.hip (STATE).  Also what every call on the resident splats does first (gs_runtime.h).
 //
 // The reference has no counterpart: it is a viewer.  An editor on it would edit its own 320-byte records and upload them again
 // (renderer.ts:130-137); here a selection is one streaming pass over 13 bytes per splat.
@@ -10,35 +10,47 @@
 // of the frame state, the statistics or a captured graph is touched (the graph's projection reads the plane when it is replayed).
 #include "gs_runtime.h"
 
-// What every entry point checks first; drains the ring.  An error of the wait is the call's error: nothing is applied.
-int32_t state_begin(gs_ctx* c, const char* who) {
+int32_t resident_check(gs_ctx* c, const char* who, Plane need, uint32_t mask, uint32_t value) {
     if (!c) return fail(GS_ERR_INVALID_ARGUMENT, "%s: null ctx", who);
-    if (!has_state(c)) return fail(GS_ERR_INVALID_ARGUMENT, "%s: the context was created without GS_FLAG_SPLAT_STATE", who);
-    if (!c->scene_mem || !c->scene.state) return fail(GS_ERR_NO_SCENE, "%s: no splats uploaded", who);
+    if (need == Plane::filtered && (mask > 0xFFu || value > 0xFFu))
+        return fail(GS_ERR_INVALID_ARGUMENT, "%s: filter (0x%x, 0x%x) does not fit the state byte", who, mask, value);
+    if ((need == Plane::always || (need == Plane::filtered && (mask | value))) && !has_state(c)) // (0, 0): what is resident needs no plane
+        return fail(GS_ERR_INVALID_ARGUMENT, "%s: the context was created without GS_FLAG_SPLAT_STATE", who);
+    if (!c->scene_mem || (need == Plane::always && !c->scene.state)) return fail(GS_ERR_NO_SCENE, "%s: no splats uploaded", who);
     return GS_OK;
 }
 static constexpr size_t kCounterBytes = (size_t)GS_STATE_SLOTS * GS_STATE_SLOT_STRIDE * sizeof(unsigned long long);
-int32_t state_drain(gs_ctx* c) {
+int32_t resident_drain(gs_ctx* c, bool counter) {
     const int32_t rc = gs_wait(c);
     if (rc != GS_OK) return rc;
     HIP_TRY(hipSetDevice(c->cfg.device));
-    if (!c->st.counter) HIP_TRY(hipMalloc(c->st.counter.out(), kCounterBytes));
+    if (counter && !c->st.counter) HIP_TRY(hipMalloc(c->st.counter.out(), kCounterBytes));
     return GS_OK;
 }
-// The kernels' partial sums (gs_kernels.h GS_STATE_SLOTS): zeroed before the launch, added up after it; returns when the stream is done.
-int32_t state_counter_zero(gs_ctx* c) {
+int32_t stage_mask(gs_ctx* root, const uint8_t* mask, hipStream_t st, const uint8_t** dev) {
+    const uint64_t bytes = (uint64_t)root->frame.width * root->frame.height; // the CANVAS, also on a slab context
+    const int32_t rc = root->st.mask.reserve(bytes);
+    if (rc != GS_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(root->st.mask, mask, (size_t)bytes, hipMemcpyHostToDevice, st));
+    *dev = root->st.mask;
+    return GS_OK;
+}
+// A launch that counts: launch(slots) enqueues a kernel that adds its `matched` into the GS_STATE_SLOTS partial sums (gs_kernels.h).
+// They are zeroed before it and added up after it; returns when the stream is done.  matched may be null.
+template <class Launch>
+static int32_t state_counted(gs_ctx* c, Launch launch, uint64_t* matched) {
     HIP_TRY(hipMemsetAsync(c->st.counter, 0, kCounterBytes, c->stream));
-    return GS_OK;
-}
-int32_t state_counter_sum(gs_ctx* c, unsigned long long* total) {
+    launch(c->st.counter.get());
+    HIP_TRY(hipGetLastError());
     unsigned long long h[GS_STATE_SLOTS * GS_STATE_SLOT_STRIDE];
     HIP_TRY(hipMemcpyAsync(h, c->st.counter, kCounterBytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    *total = 0;
-    for (int k = 0; k < GS_STATE_SLOTS; ++k) *total += h[k * GS_STATE_SLOT_STRIDE];
+    uint64_t total = 0;
+    for (int k = 0; k < GS_STATE_SLOTS; ++k) total += h[k * GS_STATE_SLOT_STRIDE];
+    if (matched) *matched = total;
     return GS_OK;
 }
-int32_t state_check_op(const char* who, uint32_t op, uint32_t bits) {
+static int32_t state_check_op(const char* who, uint32_t op, uint32_t bits) {
     if (op < GS_STATE_SET || op > GS_STATE_ASSIGN) return fail(GS_ERR_INVALID_ARGUMENT, "%s: unknown op %u (GS_STATE_SET .. GS_STATE_ASSIGN)", who, op);
     if (bits > 0xFFu) return fail(GS_ERR_INVALID_ARGUMENT, "%s: bits 0x%x do not fit the state byte", who, bits);
     return GS_OK;
@@ -46,7 +58,7 @@ int32_t state_check_op(const char* who, uint32_t op, uint32_t bits) {
 static uint8_t* plane(gs_ctx* c) { return const_cast<uint8_t*>(c->scene.state); }
 
 GS_EXPORT int32_t gs_state_region(gs_ctx* c, const gs_region* rg, uint32_t op, uint32_t bits, uint64_t* matched) {
-    int32_t rc = state_begin(c, "gs_state_region");
+    int32_t rc = resident_check(c, "gs_state_region", Plane::always);
     if (rc != GS_OK) return rc;
     if (!rg) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_region: null region");
     if (rg->struct_size != sizeof(gs_region)) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_region: struct_size %u != %zu", rg->struct_size, sizeof(gs_region));
@@ -57,7 +69,7 @@ GS_EXPORT int32_t gs_state_region(gs_ctx* c, const gs_region* rg, uint32_t op, u
     const bool screen = rg->kind == GS_REGION_SCREEN_RECT || rg->kind == GS_REGION_SCREEN_MASK;
     if (screen && !rg->uniforms160) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_region: a screen region needs uniforms160 (the camera)");
     if (rg->kind == GS_REGION_SCREEN_MASK && !rg->mask) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_region: GS_REGION_SCREEN_MASK needs a mask");
-    rc = state_drain(c);
+    rc = resident_drain(c, true);
     if (rc != GS_OK) return rc;
 
     GsRegionDev r{};
@@ -72,28 +84,16 @@ GS_EXPORT int32_t gs_state_region(gs_ctx* c, const gs_region* rg, uint32_t op, u
         for (int k = 0; k < 4; ++k) r.viewz[k] = u.view[4 * k + 2];
     }
     if (rg->kind == GS_REGION_SCREEN_MASK) {
-        const uint64_t mb = (uint64_t)r.wi * r.hi;
-        if (mb > c->st.mask_cap) {
-            c->st.mask_cap = 0;
-            HIP_TRY(hipMalloc(c->st.mask.out(), (size_t)mb));
-            c->st.mask_cap = mb;
-        }
-        HIP_TRY(hipMemcpyAsync(c->st.mask, rg->mask, (size_t)mb, hipMemcpyHostToDevice, c->stream));
-        r.mask = c->st.mask;
+        rc = stage_mask(c, rg->mask, c->stream, &r.mask);
+        if (rc != GS_OK) return rc;
     }
-    rc = state_counter_zero(c);
-    if (rc != GS_OK) return rc;
-    gs_launch_state_region(rg->kind, plane(c), c->scene, c->n, r, op, bits, rg->where_mask, rg->where_value, c->st.counter, c->stream);
-    HIP_TRY(hipGetLastError());
-    unsigned long long m = 0;
-    rc = state_counter_sum(c, &m);
-    if (rc != GS_OK) return rc;
-    if (matched) *matched = m;
-    return GS_OK;
+    return state_counted(c, [&](unsigned long long* slots) {
+        gs_launch_state_region(rg->kind, plane(c), c->scene, c->n, r, op, bits, rg->where_mask, rg->where_value, slots, c->stream);
+    }, matched);
 }
 
 GS_EXPORT int32_t gs_state_ids(gs_ctx* c, const uint32_t* ids, uint64_t n, uint32_t op, uint32_t bits) {
-    int32_t rc = state_begin(c, "gs_state_ids");
+    int32_t rc = resident_check(c, "gs_state_ids", Plane::always);
     if (rc != GS_OK) return rc;
     if (!ids && n) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_ids: null ids");
     rc = state_check_op("gs_state_ids", op, bits);
@@ -101,14 +101,11 @@ GS_EXPORT int32_t gs_state_ids(gs_ctx* c, const uint32_t* ids, uint64_t n, uint3
     for (uint64_t i = 0; i < n; ++i) // before anything is changed
         if (ids[i] >= c->n)
             return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_ids: ids[%llu] = %u is not a splat (N = %u)", (unsigned long long)i, ids[i], c->n);
-    rc = state_drain(c);
+    rc = resident_drain(c, true);
     if (rc != GS_OK) return rc;
     if (!n) return GS_OK;
-    if (n > c->st.ids_cap) {
-        c->st.ids_cap = 0;
-        HIP_TRY(hipMalloc(c->st.ids.out(), (size_t)n * 4));
-        c->st.ids_cap = n;
-    }
+    rc = c->st.ids.reserve(n);
+    if (rc != GS_OK) return rc;
     HIP_TRY(hipMemcpyAsync(c->st.ids, ids, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
     gs_launch_state_ids(plane(c), c->st.ids, n, op, bits, c->stream);
     HIP_TRY(hipGetLastError());
@@ -117,28 +114,38 @@ GS_EXPORT int32_t gs_state_ids(gs_ctx* c, const uint32_t* ids, uint64_t n, uint3
 }
 
 GS_EXPORT int32_t gs_state_count(gs_ctx* c, uint32_t mask, uint32_t value, uint64_t* count) {
-    int32_t rc = state_begin(c, "gs_state_count");
+    int32_t rc = resident_check(c, "gs_state_count", Plane::always);
     if (rc != GS_OK) return rc;
     if (!count) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_count: null count");
-    rc = state_drain(c);
+    rc = resident_drain(c, true);
     if (rc != GS_OK) return rc;
-    rc = state_counter_zero(c);
+    return state_counted(c, [&](unsigned long long* slots) { gs_launch_state_count(c->scene.state, c->n, mask, value, slots, c->stream); }, count);
+}
+
+// Select by what is seen: the pass over the coverage planes (gs_coverage.hip), which the first call that needs them allocates.
+GS_EXPORT int32_t gs_state_coverage(gs_ctx* c, uint32_t min_hits, float min_weight, uint32_t covered, uint32_t where_mask, uint32_t where_value,
+                                    uint32_t op, uint32_t bits, uint64_t* matched) {
+    int32_t rc = resident_check(c, "gs_state_coverage", Plane::always);
     if (rc != GS_OK) return rc;
-    gs_launch_state_count(c->scene.state, c->n, mask, value, c->st.counter, c->stream);
-    HIP_TRY(hipGetLastError());
-    unsigned long long m = 0;
-    rc = state_counter_sum(c, &m);
+    rc = state_check_op("gs_state_coverage", op, bits);
     if (rc != GS_OK) return rc;
-    *count = m;
-    return GS_OK;
+    if (!(min_weight >= 0.0f)) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_coverage: min_weight %g is negative or not a number", (double)min_weight);
+    if (where_mask > 0xFFu) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_coverage: where_mask 0x%x does not fit the state byte", where_mask);
+    rc = resident_drain(c, true);
+    if (rc != GS_OK) return rc;
+    rc = cover_planes(c, c->stream);
+    if (rc != GS_OK) return rc;
+    return state_counted(c, [&](unsigned long long* slots) {
+        gs_launch_state_coverage(plane(c), c->cov, c->n, min_hits, min_weight, covered, op, bits, where_mask, where_value, slots, c->stream);
+    }, matched);
 }
 
 GS_EXPORT int32_t gs_state_write(gs_ctx* c, const uint8_t* src, uint64_t n) {
-    int32_t rc = state_begin(c, "gs_state_write");
+    int32_t rc = resident_check(c, "gs_state_write", Plane::always);
     if (rc != GS_OK) return rc;
     if (n != c->n) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_write: n = %llu, the plane holds %u splats (whole plane only)", (unsigned long long)n, c->n);
     if (!src && n) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_write: null source");
-    rc = state_drain(c);
+    rc = resident_drain(c, true);
     if (rc != GS_OK) return rc;
     if (n) HIP_TRY(hipMemcpyAsync(plane(c), src, (size_t)n, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));

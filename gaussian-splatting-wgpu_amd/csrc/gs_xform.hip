@@ -37,7 +37,7 @@ GS_EXPORT int32_t gs_transform_splats(gs_ctx* c, uint32_t mask, uint32_t value, 
     if ((x->flags & GS_XFORM_SIZE) && !std::isfinite(x->log_scale)) return fail(GS_ERR_INVALID_ARGUMENT, "%s: log_scale is not finite", who);
     if (c->scene_mem && c->scene_mem != c->scene_own.get()) // (before the ring is drained: a refusal does nothing at all)
         return fail(GS_ERR_INVALID_ARGUMENT, "%s: this context borrows its splats (gs_share_splats): transform the owner", who);
-    int32_t rc = edit_begin(c, who, mask, value);
+    int32_t rc = resident_begin(c, who, Plane::filtered, mask, value); // the splat edits' prologue (gs_export.hip)
     if (rc != GS_OK) return rc;
     const bool all = !(mask | value); // every splat: no selection runs, the kernel is dense over 0..N
     uint64_t total = c->n;

@@ -1,5 +1,5 @@
-// k_coverage.hip -- gs_coverage_accumulate: per-splat contribution of the last frame over a set of pixels, and the streaming
-// pass of gs_state_coverage.
+// k_coverage.hip -- gs_coverage_accumulate: per-splat contribution of the last frame over a set of pixels (the streaming pass of
+// gs_state_coverage over the planes it fills is in k_state.hip).
 //
 // The reference has no counterpart (a viewer).  What a record holds is DEFINED by its blend, compute_tiles.wgsl:44-66, in the
 // canonical (EXACT) arithmetic, exactly as gs_pick defines an accepted entry and its weight (k_pick.hip): one f32 rounding per
@@ -26,39 +26,6 @@
 #include "gs_kernels.h"
 #include "gs_tight.h"
 
-struct GsCoverRec { // what a lane holds of its entry between the fetch and the evaluation
-    float ux, uy, cx, cy, cz, op;
-    uint32_t id;
-    bool live;
-};
-
-// want: the block's bit of a tight frame's sub-block mask (0: a plain id list)
-__device__ __forceinline__ GsCoverRec gs_cover_fetch(const uint4* __restrict__ gdata, const uint32_t* __restrict__ values, uint32_t i, uint32_t end,
-                                                     uint32_t id_mask, uint32_t want, uint32_t n) {
-    GsCoverRec r;
-    r.ux = r.uy = r.cx = r.cy = r.cz = r.op = 0.0f;
-    r.id = 0u;
-    r.live = false;
-    if (i < end) {
-        const uint32_t v = values[i];
-        const uint32_t g = v & id_mask;
-        if (g < n && (want == 0u || (v & want) != 0u)) { // (a list never holds an id >= n; never gather out of bounds)
-            const uint4 p0 = gdata[(uint64_t)g * 4 + 0];
-            const uint4 p1 = gdata[(uint64_t)g * 4 + 1];
-            r.op = __uint_as_float(((const uint32_t*)gdata)[(uint64_t)g * 16 + 11]);
-            r.ux = __uint_as_float(p0.x); r.uy = __uint_as_float(p0.y);
-            r.cx = __uint_as_float(p1.x); r.cy = __uint_as_float(p1.y); r.cz = __uint_as_float(p1.z);
-            r.id = g;
-            r.live = true;
-        }
-    }
-    return r;
-}
-
-__device__ __forceinline__ float gs_cover_bcast(float v, int l) {
-    return __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(v), l));
-}
-
 // grid: (blocks in x, blocks in y) of the 8x8 blocks [bx0, ...) x [by0, ...) the host found to intersect region, slab and canvas
 __global__ __launch_bounds__(64) void gs_coverage_kernel(const uint4* __restrict__ gdata, const uint32_t* __restrict__ values,
                                                           const uint32_t* __restrict__ ranges, GsFrame f, uint32_t id_mask, uint32_t bx0,
@@ -84,9 +51,9 @@ __global__ __launch_bounds__(64) void gs_coverage_kernel(const uint4* __restrict
     const float Wf = (float)f.width, Hf = (float)f.height;
     const float c255 = (float)(1.0 / 255.0);
     float T = 1.0f;
-    GsCoverRec cur = gs_cover_fetch(gdata, values, start + lane, end, id_mask, want, f.n);
+    GsListRec cur = gs_list_fetch(gdata, values, start + lane, end, id_mask, want, f.n);
     for (uint32_t b = start; b < end; b += 64u) {
-        const GsCoverRec nxt = gs_cover_fetch(gdata, values, b + 64u + lane, end, id_mask, want, f.n); // in flight while this chunk is resolved
+        const GsListRec nxt = gs_list_fetch(gdata, values, b + 64u + lane, end, id_mask, want, f.n); // in flight while this chunk is resolved
         // The blend walkers' two parking culls (gs_device.h; k_blend.hip tells what they save), taken by the lane that fetched the
         // entry: it stays only if its alpha >= 1/255 ellipse reaches the bounding box of the pixels that are still LIVE, and if
         // the largest T among them leaves room for it (Tmax (1 - alpha_lo) >= 1e-4).  Both are conservative with margins and hold
@@ -95,7 +62,7 @@ __global__ __launch_bounds__(64) void gs_coverage_kernel(const uint4* __restrict
         const unsigned long long lv = __ballot(!done);
         if (!lv) break; // every live pixel is final
         const GsLiveBox lb = gs_live_box<false>(lv);
-        const float Tmax = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)wave_incl_max(done ? 0u : __float_as_uint(T)), 63));
+        const float Tmax = __uint_as_float(gs_bcast(wave_incl_max(done ? 0u : __float_as_uint(T)), 63));
         bool rel = cur.live;
         if (rel) {
             const float lim = __builtin_amdgcn_logf(cur.op * 255.0f) * 0.693147182464599609375f + 0.01f; // alpha >= c255 <=> q <= ln(255 op)
@@ -113,9 +80,9 @@ __global__ __launch_bounds__(64) void gs_coverage_kernel(const uint4* __restrict
         while (m) {
             const int l = __builtin_ctzll(m);
             m &= m - 1ull;
-            const float ux = gs_cover_bcast(cur.ux, l), uy = gs_cover_bcast(cur.uy, l);
-            const float cx = gs_cover_bcast(cur.cx, l), cy = gs_cover_bcast(cur.cy, l), cz = gs_cover_bcast(cur.cz, l);
-            const float op = gs_cover_bcast(cur.op, l);
+            const float ux = gs_bcast(cur.ux, l), uy = gs_bcast(cur.uy, l);
+            const float cx = gs_bcast(cur.cx, l), cy = gs_bcast(cur.cy, l), cz = gs_bcast(cur.cz, l);
+            const float op = gs_bcast(cur.op, l);
             // compute_tiles.wgsl:52-63, the head of gs_blend_exact
             const float power = gs_blend_power(cx, cy, cz, ux * Wf - pxf, uy * Hf - pyf);
             const float alpha = gs_blend_alpha(op, power);
@@ -126,7 +93,7 @@ __global__ __launch_bounds__(64) void gs_coverage_kernel(const uint4* __restrict
             const float w = cond ? alpha * T : 0.0f; // the entry's weight: T before the entry
             if (cond) T = test;                      // cond test + (1 - cond) T
             const uint32_t q = (uint32_t)(w * 4294967296.0f); // floor(w 2^32): the product is exact and w <= 0.99
-            const uint32_t wmax = (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_max(__float_as_uint(w)), 63); // w >= 0: the bits order like the floats
+            const uint32_t wmax = gs_bcast(wave_incl_max(__float_as_uint(w)), 63); // w >= 0: the bits order like the floats
             const uint32_t slo = wave_sum(q & 0xFFFFu), shi = wave_sum(q >> 16);
             if (lane == (uint32_t)l) {
                 a_hits = (uint32_t)__popcll(acc);
@@ -150,54 +117,4 @@ void gs_launch_coverage(const void* gdata, const uint32_t* values, const uint32_
                         uint32_t by0, uint32_t nbx, uint32_t nby, const GsCoverDev& r, void* planes, hipStream_t st) {
     if (!nbx || !nby) return;
     gs_coverage_kernel<<<dim3(nbx, nby), 64, 0, st>>>((const uint4*)gdata, values, ranges, f, id_mask, bx0, by0, r, (uint32_t*)planes);
-}
-
-// gs_state_coverage: one thread per four consecutive splats, as gs_state_region_kernel (k_state.hip) -- the state word and four
-// 16-byte records, 17 B per splat.  The last thread of a plane whose length is no multiple of four goes splat by splat.
-__device__ __forceinline__ bool cover_member(uint4 rec, uint32_t min_hits, float min_weight, bool covered) {
-    return (rec.z >= min_hits && __uint_as_float(rec.w) >= min_weight) == covered;
-}
-__global__ __launch_bounds__(256) void gs_state_coverage_kernel(uint8_t* __restrict__ state, const uint4* __restrict__ planes, uint32_t n, uint32_t min_hits,
-                                                                 float min_weight, uint32_t covered, uint32_t op, uint32_t bits, uint32_t wmask,
-                                                                 uint32_t wvalue, unsigned long long* __restrict__ matched) {
-    __shared__ uint32_t s_sum;
-    if (threadIdx.x == 0) s_sum = 0u;
-    __syncthreads();
-    const uint32_t q = blockIdx.x * 256u + threadIdx.x; // splats 4q .. 4q+3
-    const uint64_t first = (uint64_t)q * 4u;
-    const bool cov = covered != 0u;
-    uint32_t hits = 0;
-    if (first + 4u <= n) {
-        const uint32_t w = reinterpret_cast<const uint32_t*>(state)[q];
-        uint32_t nw = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const uint32_t sv = (w >> (8 * k)) & 0xFFu;
-            const bool in = ((sv & wmask) == wvalue) && cover_member(planes[first + k], min_hits, min_weight, cov);
-            hits += in ? 1u : 0u;
-            nw |= (in ? gs_state_apply(sv, op, bits) : sv) << (8 * k);
-        }
-        if (nw != w) reinterpret_cast<uint32_t*>(state)[q] = nw; // stored only if it changed
-    } else if (first < n) {
-        for (uint64_t i = first; i < n; ++i) {
-            const uint32_t sv = state[i];
-            const bool in = ((sv & wmask) == wvalue) && cover_member(planes[i], min_hits, min_weight, cov);
-            hits += in ? 1u : 0u;
-            const uint32_t nv = in ? gs_state_apply(sv, op, bits) : sv;
-            if (nv != sv) state[i] = (uint8_t)nv;
-        }
-    }
-    // matched: wave sum, one LDS add per wave, one global add per workgroup, spread over GS_STATE_SLOTS words (gs_kernels.h)
-    const uint32_t ws = wave_sum(hits);
-    if ((threadIdx.x & 63u) == 0u && ws) atomicAdd(&s_sum, ws);
-    __syncthreads();
-    if (threadIdx.x == 0 && s_sum) atomicAdd(matched + (blockIdx.x % GS_STATE_SLOTS) * GS_STATE_SLOT_STRIDE, (unsigned long long)s_sum);
-}
-
-void gs_launch_state_coverage(uint8_t* state, const void* planes, uint32_t n, uint32_t min_hits, float min_weight, uint32_t covered, uint32_t op,
-                              uint32_t bits, uint32_t where_mask, uint32_t where_value, unsigned long long* matched, hipStream_t st) {
-    if (!n) return;
-    const uint32_t quads = (n + 3u) / 4u, blocks = (quads + 255u) / 256u;
-    hipLaunchKernelGGL(gs_state_coverage_kernel, dim3(blocks), dim3(256), 0, st, state, (const uint4*)planes, n, min_hits, min_weight, covered, op, bits,
-                       where_mask, where_value, matched);
 }

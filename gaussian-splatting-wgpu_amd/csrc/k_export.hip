@@ -20,19 +20,10 @@
 
 // Match flags of splats 4q .. 4q+3 (bit k = splat 4q + k); 0 beyond N.
 __device__ __forceinline__ uint32_t select_flags(const uint8_t* __restrict__ state, uint32_t n, uint32_t q, uint32_t mask, uint32_t value) {
-    const uint64_t first = (uint64_t)q * 4u;
-    uint32_t w = 0u, valid = 0u;
-    if (first + 4u <= n) {
-        valid = 4u;
-        if (state) w = reinterpret_cast<const uint32_t*>(state)[q];
-    } else if (first < n) {
-        valid = (uint32_t)(n - first);
-        if (state)
-            for (uint32_t k = 0; k < valid; ++k) w |= (uint32_t)state[first + k] << (8u * k);
-    }
+    const GsStateQuad s = gs_state_quad(state, n, q);
     uint32_t f = 0u;
 #pragma unroll
-    for (uint32_t k = 0; k < 4u; ++k) f |= (k < valid && (((w >> (8u * k)) & 0xFFu) & mask) == value) ? (1u << k) : 0u;
+    for (uint32_t k = 0; k < 4u; ++k) f |= (k < s.valid && (((s.w >> (8u * k)) & 0xFFu) & mask) == value) ? (1u << k) : 0u;
     return f;
 }
 

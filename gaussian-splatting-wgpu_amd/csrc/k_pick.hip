@@ -21,33 +21,6 @@
 
 #define GS_PICK_NONE_ID 0xFFFFFFFFu
 
-struct GsPickRec { // what a lane holds of its entry between the fetch and the evaluation
-    float ux, uy, cx, cy, cz, z, op;
-    uint32_t id;
-    bool live;
-};
-
-__device__ __forceinline__ GsPickRec gs_pick_fetch(const uint4* __restrict__ gdata, const uint32_t* __restrict__ values, uint32_t i, uint32_t end,
-                                                   uint32_t id_mask, uint32_t n) {
-    GsPickRec r;
-    r.ux = r.uy = r.cx = r.cy = r.cz = r.z = r.op = 0.0f;
-    r.id = 0u;
-    r.live = false;
-    if (i < end) {
-        const uint32_t g = values[i] & id_mask; // tight frames: the sub-block mask rides above the id (gs_tight.h)
-        if (g < n) {                            // (a list never holds anything else; never gather out of bounds)
-            const uint4 p0 = gdata[(uint64_t)g * 4 + 0];
-            const uint4 p1 = gdata[(uint64_t)g * 4 + 1];
-            r.op = __uint_as_float(((const uint32_t*)gdata)[(uint64_t)g * 16 + 11]);
-            r.ux = __uint_as_float(p0.x); r.uy = __uint_as_float(p0.y);
-            r.cx = __uint_as_float(p1.x); r.cy = __uint_as_float(p1.y); r.cz = __uint_as_float(p1.z); r.z = __uint_as_float(p1.w);
-            r.id = g;
-            r.live = true;
-        }
-    }
-    return r;
-}
-
 __global__ __launch_bounds__(64) void gs_pick_kernel(const uint4* __restrict__ gdata, const uint32_t* __restrict__ values,
                                                       const uint32_t* __restrict__ ranges, GsFrame f, uint32_t id_mask,
                                                       const uint2* __restrict__ queries, uint32_t* __restrict__ results,
@@ -68,10 +41,10 @@ __global__ __launch_bounds__(64) void gs_pick_kernel(const uint4* __restrict__ g
         const float pxf = (float)xy.x, pyf = (float)xy.y;
         const float Wf = (float)f.width, Hf = (float)f.height;
         const float c255 = (float)(1.0 / 255.0);
-        GsPickRec cur = gs_pick_fetch(gdata, values, start + lane, end, id_mask, f.n);
+        GsListRec cur = gs_list_fetch(gdata, values, start + lane, end, id_mask, 0u, f.n);
         bool settled = false;
         for (uint32_t b = start; b < end && !settled; b += 64u) {
-            const GsPickRec nxt = gs_pick_fetch(gdata, values, b + 64u + lane, end, id_mask, f.n); // in flight while this chunk is resolved
+            const GsListRec nxt = gs_list_fetch(gdata, values, b + 64u + lane, end, id_mask, 0u, f.n); // in flight while this chunk is resolved
             // compute_tiles.wgsl:52-59, the head of gs_blend_exact
             const float power = gs_blend_power(cur.cx, cur.cy, cur.cz, cur.ux * Wf - pxf, cur.uy * Hf - pyf);
             const float alpha = gs_blend_alpha(cur.op, power);
@@ -79,10 +52,10 @@ __global__ __launch_bounds__(64) void gs_pick_kernel(const uint4* __restrict__ g
             while (m) {
                 const int l = __builtin_ctzll(m);
                 m &= m - 1ull;
-                const float a = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(alpha), l));
+                const float a = gs_bcast(alpha, l);
                 const float test = T * (1.0f - a);
                 if (!(test >= 0.0001f)) continue; // cond = 0: nothing changes (see the head of the file); later entries may still be accepted
-                const float z = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(cur.z), l));
+                const float z = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(cur.z), l)); // gs_bcast, written out: through it two register initialisations swap
                 const uint32_t id = (uint32_t)__builtin_amdgcn_readlane((int)cur.id, l);
                 const float w = a * T; // the entry's weight: T before the entry
                 if (cq && hits < max_contrib && lane == 0u) cq[hits] = make_uint2(id, __float_as_uint(w));

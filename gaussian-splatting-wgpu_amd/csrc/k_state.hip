@@ -1,10 +1,11 @@
-// k_state.hip -- the state plane's streaming kernels: region selection, id selection, counting (gs_state.hip, gs_abi.h
+// k_state.hip -- the state plane's streaming kernels: region, coverage and id selection, counting (gs_state.hip, gs_abi.h
 // "splat state").  The reference has no counterpart: it is a viewer, and an editor built on it would re-upload its records.
 //
 // The plane is u8[N], 256-byte aligned like the position planes (gs_context.hip scene_alloc).  Every write goes through the 32-bit
 // word that holds the byte: the region kernel owns whole words (one thread per four consecutive splats), the id kernel uses word
 // atomics, so no byte read-modify-write ever races with a neighbour.
 //   region : 13 B read per splat (3 x 4 B position, 1 B state), at most 1 B written.  Bound: HBM.  No MFMA (no contraction).
+//   coverage : the same pass, 17 B read per splat (a 16 B coverage record, 1 B state).
 //   ids    : one word atomic (two for ASSIGN) per id.  Bound: atomic latency; the lists are a click or a lasso, not the scene.
 //   count  : 1 B read per splat.
 #include "gs_device.h"
@@ -34,15 +35,32 @@ __device__ __forceinline__ bool state_member(const GsRegionDev& r, float x, floa
     return r.mask[(uint64_t)iy * r.wi + ix] != 0;
 }
 
-// One thread per four consecutive splats: the state word and three float4 of positions.  The last thread of a plane whose
-// length is no multiple of four reads and writes its splats one by one: nothing past N is touched.
+// The kernels' `matched` / `count`: wave sum (DPP), one LDS add per wave, one global add per workgroup, spread over GS_STATE_SLOTS
+// words (gs_kernels.h).  A kernel calls state_block_begin first (every thread), state_block_add last (every thread, once).
+__shared__ uint32_t s_state_sum;
+__device__ __forceinline__ void state_block_begin() {
+    if (threadIdx.x == 0) s_state_sum = 0u;
+    __syncthreads();
+}
+__device__ __forceinline__ void state_block_add(uint32_t hits, unsigned long long* slots) {
+    const uint32_t ws = wave_sum(hits);
+    if ((threadIdx.x & 63u) == 0u && ws) atomicAdd(&s_state_sum, ws);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_state_sum) atomicAdd(slots + (blockIdx.x % GS_STATE_SLOTS) * GS_STATE_SLOT_STRIDE, (unsigned long long)s_state_sum);
+}
+
+// The state pass, which the region and the coverage kernel both are, around their own membership test: thread q owns splats
+// 4q .. 4q+3, i.e. one whole word of the plane, so no byte read-modify-write races with a neighbour.  A splat with
+// (s & wmask) == wvalue that is a member takes the op; the word is stored only if it changed.  The last thread of a plane whose
+// length is no multiple of four reads and writes its splats one by one: nothing past N is touched.  (Written out twice: as one
+// function template around a membership callable the kernels' code changes and the sphere and box kernels come out 4 % slower,
+// profiles/resident_calls_refactor.txt.)
+// Region: 13 B read per splat, a whole quad's positions as three float4.
 template <int KIND>
 __global__ __launch_bounds__(256) void gs_state_region_kernel(uint8_t* __restrict__ state, const float* __restrict__ px, const float* __restrict__ py,
                                                                const float* __restrict__ pz, uint32_t n, GsRegionDev r, uint32_t op, uint32_t bits,
                                                                uint32_t wmask, uint32_t wvalue, unsigned long long* __restrict__ matched) {
-    __shared__ uint32_t s_sum;
-    if (threadIdx.x == 0) s_sum = 0u;
-    __syncthreads();
+    state_block_begin();
     const uint32_t q = blockIdx.x * 256u + threadIdx.x; // splats 4q .. 4q+3
     const uint64_t first = (uint64_t)q * 4u;
     uint32_t hits = 0;
@@ -76,11 +94,7 @@ __global__ __launch_bounds__(256) void gs_state_region_kernel(uint8_t* __restric
             if (nv != sv) state[i] = (uint8_t)nv;
         }
     }
-    // matched: wave sum (DPP), one LDS add per wave, one global add per workgroup, spread over GS_STATE_SLOTS words (gs_kernels.h)
-    const uint32_t ws = wave_sum(hits);
-    if ((threadIdx.x & 63u) == 0u && ws) atomicAdd(&s_sum, ws);
-    __syncthreads();
-    if (threadIdx.x == 0 && s_sum) atomicAdd(matched + (blockIdx.x % GS_STATE_SLOTS) * GS_STATE_SLOT_STRIDE, (unsigned long long)s_sum);
+    state_block_add(hits, matched);
 }
 
 void gs_launch_state_region(uint32_t kind, uint8_t* state, const GsScene& s, uint32_t n, const GsRegionDev& r, uint32_t op, uint32_t bits,
@@ -96,6 +110,49 @@ void gs_launch_state_region(uint32_t kind, uint8_t* state, const GsScene& s, uin
     default: GS_STATE_LAUNCH(4); break;
     }
 #undef GS_STATE_LAUNCH
+}
+
+// gs_state_coverage: the same pass around the coverage planes' record (gs_coverage_rec: hits @8, max_weight @12), 17 B read per
+// splat -- the state word and four 16-byte records.
+__device__ __forceinline__ bool cover_member(uint4 rec, uint32_t min_hits, float min_weight, bool covered) {
+    return (rec.z >= min_hits && __uint_as_float(rec.w) >= min_weight) == covered;
+}
+__global__ __launch_bounds__(256) void gs_state_coverage_kernel(uint8_t* __restrict__ state, const uint4* __restrict__ planes, uint32_t n, uint32_t min_hits,
+                                                                 float min_weight, uint32_t covered, uint32_t op, uint32_t bits, uint32_t wmask,
+                                                                 uint32_t wvalue, unsigned long long* __restrict__ matched) {
+    state_block_begin();
+    const uint32_t q = blockIdx.x * 256u + threadIdx.x; // splats 4q .. 4q+3
+    const uint64_t first = (uint64_t)q * 4u;
+    const bool cov = covered != 0u;
+    uint32_t hits = 0;
+    if (first + 4u <= n) {
+        const uint32_t w = reinterpret_cast<const uint32_t*>(state)[q];
+        uint32_t nw = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const uint32_t sv = (w >> (8 * k)) & 0xFFu;
+            const bool in = ((sv & wmask) == wvalue) && cover_member(planes[first + k], min_hits, min_weight, cov);
+            hits += in ? 1u : 0u;
+            nw |= (in ? gs_state_apply(sv, op, bits) : sv) << (8 * k);
+        }
+        if (nw != w) reinterpret_cast<uint32_t*>(state)[q] = nw; // stored only if it changed
+    } else if (first < n) {
+        for (uint64_t i = first; i < n; ++i) {
+            const uint32_t sv = state[i];
+            const bool in = ((sv & wmask) == wvalue) && cover_member(planes[i], min_hits, min_weight, cov);
+            hits += in ? 1u : 0u;
+            const uint32_t nv = in ? gs_state_apply(sv, op, bits) : sv;
+            if (nv != sv) state[i] = (uint8_t)nv;
+        }
+    }
+    state_block_add(hits, matched);
+}
+void gs_launch_state_coverage(uint8_t* state, const void* planes, uint32_t n, uint32_t min_hits, float min_weight, uint32_t covered, uint32_t op,
+                              uint32_t bits, uint32_t where_mask, uint32_t where_value, unsigned long long* matched, hipStream_t st) {
+    if (!n) return;
+    const uint32_t quads = (n + 3u) / 4u, blocks = (quads + 255u) / 256u;
+    hipLaunchKernelGGL(gs_state_coverage_kernel, dim3(blocks), dim3(256), 0, st, state, (const uint4*)planes, n, min_hits, min_weight, covered, op, bits,
+                       where_mask, where_value, matched);
 }
 
 // One thread per id; the byte is reached through atomics on its word.  Every operation commutes with itself, so duplicates end
@@ -123,9 +180,7 @@ void gs_launch_state_ids(uint8_t* state, const uint32_t* ids, uint64_t n, uint32
 // Splats with (s & mask) == value: one thread per 16 bytes, the tail byte by byte.
 __global__ __launch_bounds__(256) void gs_state_count_kernel(const uint8_t* __restrict__ state, uint32_t n, uint32_t mask, uint32_t value,
                                                               unsigned long long* __restrict__ count) {
-    __shared__ uint32_t s_sum;
-    if (threadIdx.x == 0) s_sum = 0u;
-    __syncthreads();
+    state_block_begin();
     const uint32_t q = blockIdx.x * 256u + threadIdx.x;
     const uint64_t first = (uint64_t)q * 16u;
     uint32_t hits = 0;
@@ -139,10 +194,7 @@ __global__ __launch_bounds__(256) void gs_state_count_kernel(const uint8_t* __re
     } else if (first < n) {
         for (uint64_t i = first; i < n; ++i) hits += (((uint32_t)state[i] & mask) == value) ? 1u : 0u;
     }
-    const uint32_t ws = wave_sum(hits);
-    if ((threadIdx.x & 63u) == 0u && ws) atomicAdd(&s_sum, ws);
-    __syncthreads();
-    if (threadIdx.x == 0 && s_sum) atomicAdd(count + (blockIdx.x % GS_STATE_SLOTS) * GS_STATE_SLOT_STRIDE, (unsigned long long)s_sum);
+    state_block_add(hits, count);
 }
 void gs_launch_state_count(const uint8_t* state, uint32_t n, uint32_t mask, uint32_t value, unsigned long long* count, hipStream_t st) {
     if (!n) return;

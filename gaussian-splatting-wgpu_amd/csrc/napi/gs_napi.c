@@ -11,6 +11,7 @@
 #define NAPI_VERSION 4
 #include <node_api.h>
 #include <stdint.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -49,6 +50,22 @@ static int get_u32_prop(napi_env env, napi_value obj, const char* name, uint32_t
     if (napi_get_value_double(env, v, &d) != napi_ok) return 0;
     *out = (uint32_t)d;
     return 1;
+}
+
+static void set_num(napi_env env, napi_value obj, const char* k, double v) {
+    napi_value n;
+    napi_create_double(env, v, &n);
+    napi_set_named_property(env, obj, k, n);
+}
+
+/* what a wrapper of a call that reports nothing returns: throws on rc */
+static napi_value ret_none(napi_env env, int32_t rc) { return rc == GS_OK ? NULL : throw_gs(env, rc); }
+/* what a wrapper of a call that reports a count returns: throws on rc, otherwise the value as a double */
+static napi_value ret_u64(napi_env env, int32_t rc, uint64_t value) {
+    if (rc != GS_OK) return throw_gs(env, rc);
+    napi_value out;
+    NAPI_CALL(env, napi_create_double(env, (double)value, &out));
+    return out;
 }
 
 /* The external holds a box so that destroy() can null the context.  A gs_ctx is not re-entrant and renderAsync() works on it
@@ -109,11 +126,65 @@ static int get_bytes(napi_env env, napi_value v, void** data, size_t* len) {
     return 0;
 }
 
+/* Every wrapper's prologue.  ARGS(max): argc and argv[max].  CTX_ARGS(max, need) also yields the unwrapped context of argv[0] in
+ * `ctx`, or returns: undefined for a call with fewer than `need` arguments, with unwrap's exception pending otherwise. */
+#define ARGS(max)         \
+    size_t argc = (max);  \
+    napi_value argv[max]; \
+    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL))
+#define CTX_ARGS(max, need)                                     \
+    ARGS(max);                                                  \
+    gs_ctx* ctx = argc >= (need) ? unwrap(env, argv[0]) : NULL; \
+    if (!ctx) return NULL
+
+/* The size protocol of the C ABI as an ArrayBuffer: ask for the count (dst NULL), create count * elem bytes, call again to fill.
+ * a: the call's own arguments. */
+typedef int32_t (*fill_fn)(gs_ctx* ctx, const uint32_t* a, void* dst, uint64_t cap, uint64_t* n);
+static napi_value fill_arraybuffer(napi_env env, gs_ctx* ctx, fill_fn fn, const uint32_t* a, size_t elem) {
+    uint64_t n = 0;
+    int32_t rc = fn(ctx, a, NULL, 0, &n);
+    if (rc != GS_OK) return throw_gs(env, rc);
+    void* dst = NULL;
+    napi_value ab;
+    NAPI_CALL(env, napi_create_arraybuffer(env, (size_t)n * elem, &dst, &ab));
+    if (n) rc = fn(ctx, a, dst, n, &n);
+    return rc == GS_OK ? ab : throw_gs(env, rc);
+}
+static int32_t fill_buffer(gs_ctx* ctx, const uint32_t* a, void* dst, uint64_t cap, uint64_t* n) { /* a[0]: GS_BUF_*; bytes */
+    return gs_read_buffer(ctx, (int32_t)a[0], dst, cap, n);
+}
+static int32_t fill_coverage(gs_ctx* ctx, const uint32_t* a, void* dst, uint64_t cap, uint64_t* n) {
+    (void)a;
+    return gs_coverage_read(ctx, (gs_coverage_rec*)dst, cap, n);
+}
+static int32_t fill_list(gs_ctx* ctx, const uint32_t* a, void* dst, uint64_t cap, uint64_t* n) { /* a: mask, value */
+    return gs_state_list(ctx, a[0], a[1], (uint32_t*)dst, cap, n);
+}
+
+/* obj.mask (bytes) with obj.maskWidth and obj.maskHeight: the mask covers the CANVAS (the JS Renderer passes its canvas size),
+ * checked against the bytes given.  *mask stays as it is without a usable obj.mask.  Returns 0 with a TypeError pending. */
+static int get_mask_prop(napi_env env, napi_value obj, const char* who, const uint8_t** mask) {
+    napi_value v;
+    bool has = false;
+    void* data = NULL;
+    size_t len = 0;
+    if (napi_has_named_property(env, obj, "mask", &has) != napi_ok || !has || napi_get_named_property(env, obj, "mask", &v) != napi_ok ||
+        !get_bytes(env, v, &data, &len))
+        return 1;
+    uint32_t cw = 0, ch = 0;
+    if (!get_u32_prop(env, obj, "maskWidth", &cw) || !get_u32_prop(env, obj, "maskHeight", &ch) || (double)len < (double)cw * (double)ch) {
+        char msg[128];
+        snprintf(msg, sizeof(msg), "gsplat.%s: mask needs maskWidth, maskHeight and width * height bytes", who);
+        napi_throw_type_error(env, NULL, msg);
+        return 0;
+    }
+    *mask = (const uint8_t*)data;
+    return 1;
+}
+
 /* create({width,height,tileSize,device,colBegin,colEnd,flags,maxIntersections}) -> handle */
 static napi_value js_create(napi_env env, napi_callback_info info) {
-    size_t argc = 1;
-    napi_value argv[1];
-    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    ARGS(1);
     gs_config cfg;
     memset(&cfg, 0, sizeof(cfg));
     cfg.struct_size = sizeof(cfg);
@@ -146,9 +217,7 @@ static napi_value js_create(napi_env env, napi_callback_info info) {
 }
 
 static napi_value js_destroy(napi_env env, napi_callback_info info) {
-    size_t argc = 1;
-    napi_value argv[1];
-    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    ARGS(1);
     void* p = NULL;
     if (argc < 1 || napi_get_value_external(env, argv[0], &p) != napi_ok || !p) return NULL;
     ctx_box* box = (ctx_box*)p;
@@ -165,11 +234,7 @@ static napi_value js_destroy(napi_env env, napi_callback_info info) {
 
 /* uploadSplats(handle, bytes, n) */
 static napi_value js_upload(napi_env env, napi_callback_info info) {
-    size_t argc = 3;
-    napi_value argv[3];
-    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-    gs_ctx* ctx = argc >= 3 ? unwrap(env, argv[0]) : NULL;
-    if (!ctx) return NULL;
+    CTX_ARGS(3, 3);
     void* data = NULL;
     size_t len = 0;
     double n = 0;
@@ -178,30 +243,20 @@ static napi_value js_upload(napi_env env, napi_callback_info info) {
         napi_throw_type_error(env, NULL, "gsplat.uploadSplats: need n*320 bytes");
         return NULL;
     }
-    int32_t rc = gs_upload_splats(ctx, data, (uint64_t)n);
-    return rc == GS_OK ? NULL : throw_gs(env, rc);
+    return ret_none(env, gs_upload_splats(ctx, data, (uint64_t)n));
 }
 
 /* shareSplats(handle, ownerHandle): render the owner's resident splats from a second context (gs_share_splats) */
 static napi_value js_share(napi_env env, napi_callback_info info) {
-    size_t argc = 2;
-    napi_value argv[2];
-    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-    gs_ctx* ctx = argc >= 2 ? unwrap(env, argv[0]) : NULL;
-    if (!ctx) return NULL;
+    CTX_ARGS(2, 2);
     gs_ctx* owner = unwrap(env, argv[1]);
     if (!owner) return NULL;
-    int32_t rc = gs_share_splats(ctx, owner);
-    return rc == GS_OK ? NULL : throw_gs(env, rc);
+    return ret_none(env, gs_share_splats(ctx, owner));
 }
 
 /* renderSync(handle, uniforms160[, debug]) : enqueue + wait on the calling thread */
 static napi_value js_render_sync(napi_env env, napi_callback_info info) {
-    size_t argc = 3;
-    napi_value argv[3];
-    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-    gs_ctx* ctx = argc >= 2 ? unwrap(env, argv[0]) : NULL;
-    if (!ctx) return NULL;
+    CTX_ARGS(3, 2);
     void* data = NULL;
     size_t len = 0;
     if (!get_bytes(env, argv[1], &data, &len) || len < GS_UNIFORM_BYTES) {
@@ -236,37 +291,38 @@ static void job_execute(napi_env env, void* data) {
     }
 }
 
-static void job_complete(napi_env env, napi_status status, void* data) {
-    frame_job* j = (frame_job*)data;
+/* What the completion of a renderAsync or renderToSink job does once the job has given the context back (busy = 0, inflight--):
+ * the destroy() (1) or the finalizer (2) that came while frames were in flight, then the promise. */
+static void finish_job(napi_env env, ctx_box* box, napi_deferred deferred, napi_status status, int32_t rc, const char* err) {
     napi_value v;
-    ctx_box* box = j->box;
-    box->busy = 0;
-    if (box->destroy_pending) { /* destroy() (1) or the finalizer (2) came while the frame was in flight */
+    if (!box->inflight && !box->busy && box->destroy_pending) {
         if (box->ctx) gs_destroy(box->ctx);
         box->ctx = NULL;
         if (box->destroy_pending == 2) free(box);
         else box->destroy_pending = 0;
     }
-    if (status == napi_ok && j->rc == GS_OK) {
+    if (status == napi_ok && rc == GS_OK) {
         napi_get_undefined(env, &v);
-        napi_resolve_deferred(env, j->deferred, v);
+        napi_resolve_deferred(env, deferred, v);
     } else {
         napi_value msg;
-        napi_create_string_utf8(env, j->rc != GS_OK ? j->err : "gsplat: async work cancelled", NAPI_AUTO_LENGTH, &msg);
+        napi_create_string_utf8(env, rc != GS_OK ? err : "gsplat: async work cancelled", NAPI_AUTO_LENGTH, &msg);
         napi_create_error(env, NULL, msg, &v);
-        napi_reject_deferred(env, j->deferred, v);
+        napi_reject_deferred(env, deferred, v);
     }
+}
+
+static void job_complete(napi_env env, napi_status status, void* data) {
+    frame_job* j = (frame_job*)data;
+    j->box->busy = 0; /* (no renderToSink frame is in flight beside a renderAsync job: each refuses the other) */
+    finish_job(env, j->box, j->deferred, status, j->rc, j->err);
     napi_delete_async_work(env, j->work);
     free(j);
 }
 
 /* renderAsync(handle, uniforms160) -> Promise<void> */
 static napi_value js_render_async(napi_env env, napi_callback_info info) {
-    size_t argc = 2;
-    napi_value argv[2];
-    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-    gs_ctx* ctx = argc >= 2 ? unwrap(env, argv[0]) : NULL;
-    if (!ctx) return NULL;
+    CTX_ARGS(2, 2);
     void* data = NULL;
     size_t len = 0;
     if (!get_bytes(env, argv[1], &data, &len) || len < GS_UNIFORM_BYTES) {
@@ -299,47 +355,23 @@ static napi_value js_render_async(napi_env env, napi_callback_info info) {
 
 /* readRgba8(handle) -> ArrayBuffer (height*slabWidth*4) */
 static napi_value js_read_rgba8(napi_env env, napi_callback_info info) {
-    size_t argc = 1;
-    napi_value argv[1];
-    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-    gs_ctx* ctx = argc >= 1 ? unwrap(env, argv[0]) : NULL;
-    if (!ctx) return NULL;
-    uint64_t bytes = 0;
-    int32_t rc = gs_read_buffer(ctx, GS_BUF_RGBA8, NULL, 0, &bytes);
-    if (rc != GS_OK) return throw_gs(env, rc);
-    void* dst = NULL;
-    napi_value ab;
-    NAPI_CALL(env, napi_create_arraybuffer(env, (size_t)bytes, &dst, &ab));
-    rc = gs_read_rgba8(ctx, dst, bytes);
-    return rc == GS_OK ? ab : throw_gs(env, rc);
+    CTX_ARGS(1, 1);
+    const uint32_t which = GS_BUF_RGBA8;
+    return fill_arraybuffer(env, ctx, fill_buffer, &which, 1);
 }
 
 /* readBuffer(handle, which) -> ArrayBuffer */
 static napi_value js_read_buffer(napi_env env, napi_callback_info info) {
-    size_t argc = 2;
-    napi_value argv[2];
-    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-    gs_ctx* ctx = argc >= 2 ? unwrap(env, argv[0]) : NULL;
-    if (!ctx) return NULL;
+    CTX_ARGS(2, 2);
     int32_t which = 0;
     NAPI_CALL(env, napi_get_value_int32(env, argv[1], &which));
-    uint64_t bytes = 0;
-    int32_t rc = gs_read_buffer(ctx, which, NULL, 0, &bytes);
-    if (rc != GS_OK) return throw_gs(env, rc);
-    void* dst = NULL;
-    napi_value ab;
-    NAPI_CALL(env, napi_create_arraybuffer(env, (size_t)bytes, &dst, &ab));
-    if (bytes) rc = gs_read_buffer(ctx, which, dst, bytes, NULL);
-    return rc == GS_OK ? ab : throw_gs(env, rc);
+    const uint32_t a = (uint32_t)which;
+    return fill_arraybuffer(env, ctx, fill_buffer, &a, 1);
 }
 
 /* pick(handle, queries ( Uint32Array x,y pairs ), maxContrib) -> {results: ArrayBuffer (48 bytes per query), contrib: ArrayBuffer | null} */
 static napi_value js_pick(napi_env env, napi_callback_info info) {
-    size_t argc = 3;
-    napi_value argv[3];
-    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-    gs_ctx* ctx = argc >= 2 ? unwrap(env, argv[0]) : NULL;
-    if (!ctx) return NULL;
+    CTX_ARGS(3, 2);
     void* q = NULL;
     size_t qlen = 0;
     if (!get_bytes(env, argv[1], &q, &qlen) || qlen % sizeof(gs_pick_query) != 0) {
@@ -369,11 +401,7 @@ static napi_value js_pick(napi_env env, napi_callback_info info) {
 /* ---- coverage: 1:1 wrappers of gs_coverage_* and gs_state_coverage ---------------------------------------------------------- */
 /* accumulateCoverage(handle, region | null) -> pixels; region = {x0, y0, x1, y1, mask, maskWidth, maskHeight} (canvas pixels) */
 static napi_value js_coverage_accumulate(napi_env env, napi_callback_info info) {
-    size_t argc = 2;
-    napi_value argv[2];
-    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-    gs_ctx* ctx = argc >= 1 ? unwrap(env, argv[0]) : NULL;
-    if (!ctx) return NULL;
+    CTX_ARGS(2, 1);
     gs_cover_region rg;
     memset(&rg, 0, sizeof(rg));
     rg.struct_size = sizeof(rg);
@@ -386,63 +414,28 @@ static napi_value js_coverage_accumulate(napi_env env, napi_callback_info info) 
             napi_throw_type_error(env, NULL, "gsplat.accumulateCoverage: {x0, y0, x1, y1} required");
             return NULL;
         }
-        napi_value v;
-        bool has = false;
-        void* data = NULL;
-        size_t len = 0;
-        if (napi_has_named_property(env, argv[1], "mask", &has) == napi_ok && has &&
-            napi_get_named_property(env, argv[1], "mask", &v) == napi_ok && get_bytes(env, v, &data, &len)) {
-            uint32_t cw = 0, ch = 0; /* the mask covers the CANVAS (the JS Renderer passes its canvas size): checked against the bytes given */
-            if (!get_u32_prop(env, argv[1], "maskWidth", &cw) || !get_u32_prop(env, argv[1], "maskHeight", &ch) || (double)len < (double)cw * (double)ch) {
-                napi_throw_type_error(env, NULL, "gsplat.accumulateCoverage: mask needs maskWidth, maskHeight and width * height bytes");
-                return NULL;
-            }
-            rg.mask = (const uint8_t*)data;
-        }
+        if (!get_mask_prop(env, argv[1], "accumulateCoverage", &rg.mask)) return NULL;
     }
     uint64_t pixels = 0;
     int32_t rc = gs_coverage_accumulate(ctx, have ? &rg : NULL, &pixels);
-    if (rc != GS_OK) return throw_gs(env, rc);
-    napi_value out;
-    NAPI_CALL(env, napi_create_double(env, (double)pixels, &out));
-    return out;
+    return ret_u64(env, rc, pixels);
 }
 
 /* resetCoverage(handle) */
 static napi_value js_coverage_reset(napi_env env, napi_callback_info info) {
-    size_t argc = 1;
-    napi_value argv[1];
-    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-    gs_ctx* ctx = argc >= 1 ? unwrap(env, argv[0]) : NULL;
-    if (!ctx) return NULL;
-    int32_t rc = gs_coverage_reset(ctx);
-    return rc == GS_OK ? NULL : throw_gs(env, rc);
+    CTX_ARGS(1, 1);
+    return ret_none(env, gs_coverage_reset(ctx));
 }
 
 /* readCoverage(handle) -> ArrayBuffer (N records of 16 bytes: gs_coverage_rec) */
 static napi_value js_coverage_read(napi_env env, napi_callback_info info) {
-    size_t argc = 1;
-    napi_value argv[1];
-    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-    gs_ctx* ctx = argc >= 1 ? unwrap(env, argv[0]) : NULL;
-    if (!ctx) return NULL;
-    uint64_t n = 0;
-    int32_t rc = gs_coverage_read(ctx, NULL, 0, &n);
-    if (rc != GS_OK) return throw_gs(env, rc);
-    void* dst = NULL;
-    napi_value ab;
-    NAPI_CALL(env, napi_create_arraybuffer(env, (size_t)n * sizeof(gs_coverage_rec), &dst, &ab));
-    if (n) rc = gs_coverage_read(ctx, (gs_coverage_rec*)dst, n, &n);
-    return rc == GS_OK ? ab : throw_gs(env, rc);
+    CTX_ARGS(1, 1);
+    return fill_arraybuffer(env, ctx, fill_coverage, NULL, sizeof(gs_coverage_rec));
 }
 
 /* stateCoverage(handle, minHits, minWeight, covered, whereMask, whereValue, op, bits) -> matched */
 static napi_value js_state_coverage(napi_env env, napi_callback_info info) {
-    size_t argc = 8;
-    napi_value argv[8];
-    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-    gs_ctx* ctx = argc >= 8 ? unwrap(env, argv[0]) : NULL;
-    if (!ctx) return NULL;
+    CTX_ARGS(8, 8);
     uint32_t u[6]; /* minHits, covered, whereMask, whereValue, op, bits */
     static const int at[6] = {1, 3, 4, 5, 6, 7};
     for (int k = 0; k < 6; ++k) NAPI_CALL(env, napi_get_value_uint32(env, argv[at[k]], &u[k]));
@@ -450,10 +443,7 @@ static napi_value js_state_coverage(napi_env env, napi_callback_info info) {
     NAPI_CALL(env, napi_get_value_double(env, argv[2], &min_weight));
     uint64_t matched = 0;
     int32_t rc = gs_state_coverage(ctx, u[0], (float)min_weight, u[1], u[2], u[3], u[4], u[5], &matched);
-    if (rc != GS_OK) return throw_gs(env, rc);
-    napi_value out;
-    NAPI_CALL(env, napi_create_double(env, (double)matched, &out));
-    return out;
+    return ret_u64(env, rc, matched);
 }
 
 /* ---- splat state (GS_FLAG_SPLAT_STATE): 1:1 wrappers of gs_state_* --------------------------------------------------------- */
@@ -472,11 +462,7 @@ static int get_f32x3_prop(napi_env env, napi_value obj, const char* name, float*
 
 /* stateRegion(handle, {kind, a, b, x0, y0, x1, y1, uniforms, mask, whereMask, whereValue}, op, bits) -> matched */
 static napi_value js_state_region(napi_env env, napi_callback_info info) {
-    size_t argc = 4;
-    napi_value argv[4];
-    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-    gs_ctx* ctx = argc >= 4 ? unwrap(env, argv[0]) : NULL;
-    if (!ctx) return NULL;
+    CTX_ARGS(4, 4);
     gs_region rg;
     memset(&rg, 0, sizeof(rg));
     rg.struct_size = sizeof(rg);
@@ -501,34 +487,18 @@ static napi_value js_state_region(napi_env env, napi_callback_info info) {
         if (len < GS_UNIFORM_BYTES) { napi_throw_type_error(env, NULL, "gsplat.stateRegion: uniforms must be the 160-byte block"); return NULL; }
         rg.uniforms160 = data;
     }
-    has = false;
-    if (napi_has_named_property(env, argv[1], "mask", &has) == napi_ok && has &&
-        napi_get_named_property(env, argv[1], "mask", &v) == napi_ok && get_bytes(env, v, &data, &len)) {
-        uint32_t cw = 0, ch = 0; /* the mask covers the CANVAS (the JS Renderer passes its canvas size): checked against the bytes given */
-        if (!get_u32_prop(env, argv[1], "maskWidth", &cw) || !get_u32_prop(env, argv[1], "maskHeight", &ch) || (double)len < (double)cw * (double)ch) {
-            napi_throw_type_error(env, NULL, "gsplat.stateRegion: mask needs maskWidth, maskHeight and width * height bytes");
-            return NULL;
-        }
-        rg.mask = (const uint8_t*)data;
-    }
+    if (!get_mask_prop(env, argv[1], "stateRegion", &rg.mask)) return NULL;
     uint32_t op = 0, bits = 0;
     NAPI_CALL(env, napi_get_value_uint32(env, argv[2], &op));
     NAPI_CALL(env, napi_get_value_uint32(env, argv[3], &bits));
     uint64_t matched = 0;
     int32_t rc = gs_state_region(ctx, &rg, op, bits, &matched);
-    if (rc != GS_OK) return throw_gs(env, rc);
-    napi_value out;
-    NAPI_CALL(env, napi_create_double(env, (double)matched, &out));
-    return out;
+    return ret_u64(env, rc, matched);
 }
 
 /* stateIds(handle, ids (Uint32Array), op, bits) */
 static napi_value js_state_ids(napi_env env, napi_callback_info info) {
-    size_t argc = 4;
-    napi_value argv[4];
-    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-    gs_ctx* ctx = argc >= 4 ? unwrap(env, argv[0]) : NULL;
-    if (!ctx) return NULL;
+    CTX_ARGS(4, 4);
     void* data = NULL;
     size_t len = 0;
     if (!get_bytes(env, argv[1], &data, &len) || len % 4 != 0) {
@@ -538,63 +508,38 @@ static napi_value js_state_ids(napi_env env, napi_callback_info info) {
     uint32_t op = 0, bits = 0;
     NAPI_CALL(env, napi_get_value_uint32(env, argv[2], &op));
     NAPI_CALL(env, napi_get_value_uint32(env, argv[3], &bits));
-    int32_t rc = gs_state_ids(ctx, (const uint32_t*)data, (uint64_t)(len / 4), op, bits);
-    return rc == GS_OK ? NULL : throw_gs(env, rc);
+    return ret_none(env, gs_state_ids(ctx, (const uint32_t*)data, (uint64_t)(len / 4), op, bits));
 }
 
 /* stateCount(handle, mask, value) -> count */
 static napi_value js_state_count(napi_env env, napi_callback_info info) {
-    size_t argc = 3;
-    napi_value argv[3];
-    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-    gs_ctx* ctx = argc >= 3 ? unwrap(env, argv[0]) : NULL;
-    if (!ctx) return NULL;
+    CTX_ARGS(3, 3);
     uint32_t mask = 0, value = 0;
     NAPI_CALL(env, napi_get_value_uint32(env, argv[1], &mask));
     NAPI_CALL(env, napi_get_value_uint32(env, argv[2], &value));
     uint64_t count = 0;
     int32_t rc = gs_state_count(ctx, mask, value, &count);
-    if (rc != GS_OK) return throw_gs(env, rc);
-    napi_value out;
-    NAPI_CALL(env, napi_create_double(env, (double)count, &out));
-    return out;
+    return ret_u64(env, rc, count);
 }
 
 /* readState(handle) -> ArrayBuffer (N bytes): the plane as it is now */
 static napi_value js_read_state(napi_env env, napi_callback_info info) {
-    size_t argc = 1;
-    napi_value argv[1];
-    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-    gs_ctx* ctx = argc >= 1 ? unwrap(env, argv[0]) : NULL;
-    if (!ctx) return NULL;
-    uint64_t bytes = 0;
-    int32_t rc = gs_read_buffer(ctx, GS_BUF_SPLAT_STATE, NULL, 0, &bytes);
-    if (rc != GS_OK) return throw_gs(env, rc);
-    void* dst = NULL;
-    napi_value ab;
-    NAPI_CALL(env, napi_create_arraybuffer(env, (size_t)bytes, &dst, &ab));
-    if (bytes) rc = gs_read_buffer(ctx, GS_BUF_SPLAT_STATE, dst, bytes, NULL);
-    return rc == GS_OK ? ab : throw_gs(env, rc);
+    CTX_ARGS(1, 1);
+    const uint32_t which = GS_BUF_SPLAT_STATE;
+    return fill_arraybuffer(env, ctx, fill_buffer, &which, 1);
 }
 
 /* writeState(handle, bytes (Uint8Array of N)) */
 static napi_value js_write_state(napi_env env, napi_callback_info info) {
-    size_t argc = 2;
-    napi_value argv[2];
-    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-    gs_ctx* ctx = argc >= 2 ? unwrap(env, argv[0]) : NULL;
-    if (!ctx) return NULL;
+    CTX_ARGS(2, 2);
     void* data = NULL;
     size_t len = 0;
     if (!get_bytes(env, argv[1], &data, &len)) {
         napi_throw_type_error(env, NULL, "gsplat.writeState: expects a Uint8Array of N state bytes");
         return NULL;
     }
-    int32_t rc = gs_state_write(ctx, (const uint8_t*)data, (uint64_t)len);
-    return rc == GS_OK ? NULL : throw_gs(env, rc);
+    return ret_none(env, gs_state_write(ctx, (const uint8_t*)data, (uint64_t)len));
 }
-
-static void set_num(napi_env env, napi_value obj, const char* k, double v);
 
 /* ---- splat edits (gs_abi.h "splat edits") ---- */
 static int get_filter(napi_env env, napi_value m, napi_value v, uint32_t* mask, uint32_t* value) {
@@ -603,33 +548,18 @@ static int get_filter(napi_env env, napi_value m, napi_value v, uint32_t* mask, 
 
 /* listState(handle, mask, value) -> ArrayBuffer of u32 indices, ascending */
 static napi_value js_list_state(napi_env env, napi_callback_info info) {
-    size_t argc = 3;
-    napi_value argv[3];
-    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-    gs_ctx* ctx = argc >= 3 ? unwrap(env, argv[0]) : NULL;
-    if (!ctx) return NULL;
-    uint32_t mask = 0, value = 0;
-    if (!get_filter(env, argv[1], argv[2], &mask, &value)) {
+    CTX_ARGS(3, 3);
+    uint32_t a[2] = {0, 0}; /* mask, value */
+    if (!get_filter(env, argv[1], argv[2], &a[0], &a[1])) {
         napi_throw_type_error(env, NULL, "gsplat.listState: mask and value must be numbers");
         return NULL;
     }
-    uint64_t n = 0;
-    int32_t rc = gs_state_list(ctx, mask, value, NULL, 0, &n);
-    if (rc != GS_OK) return throw_gs(env, rc);
-    void* dst = NULL;
-    napi_value ab;
-    NAPI_CALL(env, napi_create_arraybuffer(env, (size_t)n * 4, &dst, &ab));
-    if (n) rc = gs_state_list(ctx, mask, value, (uint32_t*)dst, n, &n);
-    return rc == GS_OK ? ab : throw_gs(env, rc);
+    return fill_arraybuffer(env, ctx, fill_list, a, 4);
 }
 
 /* exportSplats(handle, mask, value) -> {n, records: ArrayBuffer (n x 320 B), ids: ArrayBuffer (n x u32)} */
 static napi_value js_export_splats(napi_env env, napi_callback_info info) {
-    size_t argc = 3;
-    napi_value argv[3];
-    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-    gs_ctx* ctx = argc >= 3 ? unwrap(env, argv[0]) : NULL;
-    if (!ctx) return NULL;
+    CTX_ARGS(3, 3);
     uint32_t mask = 0, value = 0;
     if (!get_filter(env, argv[1], argv[2], &mask, &value)) {
         napi_throw_type_error(env, NULL, "gsplat.exportSplats: mask and value must be numbers");
@@ -653,11 +583,7 @@ static napi_value js_export_splats(napi_env env, napi_callback_info info) {
 
 /* compact(handle, mask, value) -> ArrayBuffer of u32: ids[new index] = old index */
 static napi_value js_compact(napi_env env, napi_callback_info info) {
-    size_t argc = 3;
-    napi_value argv[3];
-    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-    gs_ctx* ctx = argc >= 3 ? unwrap(env, argv[0]) : NULL;
-    if (!ctx) return NULL;
+    CTX_ARGS(3, 3);
     uint32_t mask = 0, value = 0;
     if (!get_filter(env, argv[1], argv[2], &mask, &value)) {
         napi_throw_type_error(env, NULL, "gsplat.compact: mask and value must be numbers");
@@ -691,11 +617,7 @@ static napi_value js_compact(napi_env env, napi_callback_info info) {
 
 /* exportPly(handle, path, mask, value, shDegree) -> n written (gs_export_ply: streamed, no whole-scene host buffer) */
 static napi_value js_export_ply(napi_env env, napi_callback_info info) {
-    size_t argc = 5;
-    napi_value argv[5];
-    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-    gs_ctx* ctx = argc >= 5 ? unwrap(env, argv[0]) : NULL;
-    if (!ctx) return NULL;
+    CTX_ARGS(5, 5);
     char path[4096];
     size_t len = 0;
     uint32_t mask = 0, value = 0;
@@ -707,17 +629,12 @@ static napi_value js_export_ply(napi_env env, napi_callback_info info) {
     }
     uint64_t n = 0;
     int32_t rc = gs_export_ply(ctx, path, mask, value, degree, &n);
-    if (rc != GS_OK) return throw_gs(env, rc);
-    napi_value v;
-    NAPI_CALL(env, napi_create_double(env, (double)n, &v));
-    return v;
+    return ret_u64(env, rc, n);
 }
 
 /* savePly(path, records (ArrayBuffer / typed array of n x 320 B), shDegree): gs_ply_save, no context */
 static napi_value js_save_ply(napi_env env, napi_callback_info info) {
-    size_t argc = 3;
-    napi_value argv[3];
-    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    ARGS(3);
     char path[4096];
     size_t len = 0, bytes = 0;
     void* data = NULL;
@@ -727,8 +644,7 @@ static napi_value js_save_ply(napi_env env, napi_callback_info info) {
         napi_throw_type_error(env, NULL, "gsplat.savePly: expects (path, records of n x 320 bytes, shDegree)");
         return NULL;
     }
-    int32_t rc = gs_ply_save(path, data, (uint64_t)(bytes / GS_SPLAT_RECORD_BYTES), degree);
-    return rc == GS_OK ? NULL : throw_gs(env, rc);
+    return ret_none(env, gs_ply_save(path, data, (uint64_t)(bytes / GS_SPLAT_RECORD_BYTES), degree));
 }
 
 /* ---- splat transforms (gs_abi.h "splat transforms") ---- */
@@ -750,9 +666,7 @@ static int is_nullish(napi_env env, napi_value v) {
     return napi_typeof(env, v, &t) == napi_ok && (t == napi_undefined || t == napi_null);
 }
 static napi_value js_compose_transform(napi_env env, napi_callback_info info) {
-    size_t argc = 4;
-    napi_value argv[4];
-    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    ARGS(4);
     float rot[4] = {1.0f, 0.0f, 0.0f, 0.0f}, tr[3] = {0.0f, 0.0f, 0.0f}, pv[3];
     double scale = 1.0;
     int have_pivot = 0, ok = argc >= 4;
@@ -776,11 +690,7 @@ static napi_value js_compose_transform(napi_env env, napi_callback_info info) {
 
 /* transformSplats(handle, xform (ArrayBuffer / typed array holding a gs_xform), mask, value) -> matched */
 static napi_value js_transform_splats(napi_env env, napi_callback_info info) {
-    size_t argc = 4;
-    napi_value argv[4];
-    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-    gs_ctx* ctx = argc >= 4 ? unwrap(env, argv[0]) : NULL;
-    if (!ctx) return NULL;
+    CTX_ARGS(4, 4);
     void* data = NULL;
     size_t len = 0;
     uint32_t mask = 0, value = 0;
@@ -792,40 +702,22 @@ static napi_value js_transform_splats(napi_env env, napi_callback_info info) {
     memcpy(&x, data, sizeof(x)); /* (a view may be unaligned) */
     uint64_t matched = 0;
     int32_t rc = gs_transform_splats(ctx, mask, value, &x, &matched);
-    if (rc != GS_OK) return throw_gs(env, rc);
-    napi_value v;
-    NAPI_CALL(env, napi_create_double(env, (double)matched, &v));
-    return v;
+    return ret_u64(env, rc, matched);
 }
 
 /* setOption(handle, key, value) */
 static napi_value js_set_option(napi_env env, napi_callback_info info) {
-    size_t argc = 3;
-    napi_value argv[3];
-    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-    gs_ctx* ctx = argc >= 3 ? unwrap(env, argv[0]) : NULL;
-    if (!ctx) return NULL;
+    CTX_ARGS(3, 3);
     int32_t key = 0;
     double value = 0;
     NAPI_CALL(env, napi_get_value_int32(env, argv[1], &key));
     NAPI_CALL(env, napi_get_value_double(env, argv[2], &value));
-    int32_t rc = gs_set_option(ctx, key, (int64_t)value);
-    return rc == GS_OK ? NULL : throw_gs(env, rc);
-}
-
-static void set_num(napi_env env, napi_value obj, const char* k, double v) {
-    napi_value n;
-    napi_create_double(env, v, &n);
-    napi_set_named_property(env, obj, k, n);
+    return ret_none(env, gs_set_option(ctx, key, (int64_t)value));
 }
 
 /* stats(handle) -> {numGaussians, numVisible, numIntersections, numProcessed, numTiles, sortPasses, frames, stageUs:[6], frameUs} */
 static napi_value js_stats(napi_env env, napi_callback_info info) {
-    size_t argc = 1;
-    napi_value argv[1];
-    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-    gs_ctx* ctx = argc >= 1 ? unwrap(env, argv[0]) : NULL;
-    if (!ctx) return NULL;
+    CTX_ARGS(1, 1);
     gs_stats st;
     int32_t rc = gs_get_stats(ctx, &st);
     if (rc != GS_OK) return throw_gs(env, rc);
@@ -857,11 +749,7 @@ static napi_value js_stats(napi_env env, napi_callback_info info) {
 }
 
 static napi_value js_slab(napi_env env, napi_callback_info info) {
-    size_t argc = 1;
-    napi_value argv[1];
-    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-    gs_ctx* ctx = argc >= 1 ? unwrap(env, argv[0]) : NULL;
-    if (!ctx) return NULL;
+    CTX_ARGS(1, 1);
     uint32_t b = 0, w = 0;
     int32_t rc = gs_slab_width(ctx, &b, &w);
     if (rc != GS_OK) return throw_gs(env, rc);
@@ -874,9 +762,7 @@ static napi_value js_slab(napi_env env, napi_callback_info info) {
 
 /* loadPly(path) -> {n, degree, records: ArrayBuffer}: the native PackedGaussians (gs_ply_load) */
 static napi_value js_load_ply(napi_env env, napi_callback_info info) {
-    size_t argc = 1;
-    napi_value argv[1];
-    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    ARGS(1);
     char path[4096];
     size_t len = 0;
     if (argc < 1 || napi_get_value_string_utf8(env, argv[0], path, sizeof(path), &len) != napi_ok) {
@@ -906,11 +792,7 @@ static napi_value js_load_ply(napi_env env, napi_callback_info info) {
 
 /* uploadPly(handle, path) -> n : the streaming loader (file -> pinned chunks -> device scene arrays, gs_upload_ply) */
 static napi_value js_upload_ply(napi_env env, napi_callback_info info) {
-    size_t argc = 2;
-    napi_value argv[2];
-    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-    gs_ctx* ctx = argc >= 2 ? unwrap(env, argv[0]) : NULL;
-    if (!ctx) return NULL;
+    CTX_ARGS(2, 2);
     char path[4096];
     size_t len = 0;
     if (napi_get_value_string_utf8(env, argv[1], path, sizeof(path), &len) != napi_ok) {
@@ -919,18 +801,13 @@ static napi_value js_upload_ply(napi_env env, napi_callback_info info) {
     }
     uint64_t n = 0;
     int32_t rc = gs_upload_ply(ctx, path, &n);
-    if (rc != GS_OK) return throw_gs(env, rc);
-    napi_value v;
-    NAPI_CALL(env, napi_create_double(env, (double)n, &v));
-    return v;
+    return ret_u64(env, rc, n);
 }
 
 /* hostAlloc(bytes) -> ArrayBuffer over page-locked memory (gs_host_alloc): a frame sink renderToSink copies into asynchronously */
 static void finalize_pinned(napi_env env, void* data, void* hint) { (void)env; (void)hint; gs_host_free(data); }
 static napi_value js_host_alloc(napi_env env, napi_callback_info info) {
-    size_t argc = 1;
-    napi_value argv[1];
-    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    ARGS(1);
     double bytes = 0;
     if (argc < 1 || napi_get_value_double(env, argv[0], &bytes) != napi_ok || !(bytes > 0.0) || bytes > 17179869184.0) {
         napi_throw_type_error(env, NULL, "gsplat.hostAlloc: byte count required");
@@ -968,24 +845,8 @@ static void sink_execute(napi_env env, void* data) {
 
 static void sink_complete(napi_env env, napi_status status, void* data) {
     sink_job* j = (sink_job*)data;
-    ctx_box* box = j->box;
-    napi_value v;
-    box->inflight--;
-    if (!box->inflight && !box->busy && box->destroy_pending) {
-        if (box->ctx) gs_destroy(box->ctx);
-        box->ctx = NULL;
-        if (box->destroy_pending == 2) free(box);
-        else box->destroy_pending = 0;
-    }
-    if (status == napi_ok && j->rc == GS_OK) {
-        napi_get_undefined(env, &v);
-        napi_resolve_deferred(env, j->deferred, v);
-    } else {
-        napi_value msg;
-        napi_create_string_utf8(env, j->rc != GS_OK ? j->err : "gsplat: async work cancelled", NAPI_AUTO_LENGTH, &msg);
-        napi_create_error(env, NULL, msg, &v);
-        napi_reject_deferred(env, j->deferred, v);
-    }
+    j->box->inflight--;
+    finish_job(env, j->box, j->deferred, status, j->rc, j->err);
     napi_delete_reference(env, j->sink_ref);
     napi_delete_async_work(env, j->work);
     free(j);
@@ -996,9 +857,7 @@ static void sink_complete(napi_env env, napi_status status, void* data) {
  * Several may be outstanding: frame k+1 is enqueued while frame k is still being rendered and copied.  `sink`: ArrayBuffer or
  * view of at least height * slabWidth * 4 bytes, ideally from hostAlloc(). */
 static napi_value js_render_to_sink(napi_env env, napi_callback_info info) {
-    size_t argc = 3;
-    napi_value argv[3];
-    NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    ARGS(3);
     ctx_box* box = argc >= 3 ? unbox(env, argv[0]) : NULL;
     if (!box) return NULL;
     if (!box->ctx || box->busy || box->destroy_pending) {

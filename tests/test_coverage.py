@@ -302,11 +302,15 @@ def test_coverage_accumulates(oracle):
 
 
 @pytest.mark.gpu
-def test_state_coverage(oracle):
+@pytest.mark.parametrize("length", [10000, 9997], ids=["whole", "n9997"])
+def test_state_coverage(oracle, length):
     """gs_state_coverage against a numpy predicate on the read-back planes: covered 1 and 0, both thresholds, the where filter,
-    *matched, every op; and the refusals."""
+    *matched, every op; and the refusals.  On cfgA whole (N a multiple of four) and on its first 9997 splats (N mod 4 = 1: the
+    last thread of the pass goes splat by splat)."""
     from gsplat import _abi
     s, u, W, H, ref = _scene_of(oracle, "cfgA", 16)
+    assert s.shape[0] == 10000
+    s = np.ascontiguousarray(s[:length])
     n = s.shape[0]
     r = _mk(s, W, H, 16, state=True)
     r.render_uniforms(u)
