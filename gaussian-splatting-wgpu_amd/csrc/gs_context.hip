@@ -48,6 +48,10 @@ int32_t alloc_kv(gs_ctx* c, uint64_t capacity, uint64_t row_cap) {
     HIP_TRY(hipMalloc(c->valsA.out(), kb));
     HIP_TRY(hipMalloc(c->keysB.out(), kb));
     HIP_TRY(hipMalloc(c->valsB.out(), kb));
+    c->sort_index = GsSort{{c->keysA, c->valsA}, {c->keysB, c->valsB}, c->passes, 8, 0, false, false};
+    // (by tile: the balanced emission has written u16 tile ids where they fit, key/1000 is taken by the sweep otherwise; it has
+    // also accumulated the digit counts)
+    c->sort_tile = GsSort{{c->keysA, c->valsA}, {c->keysB, c->valsB}, c->tile_passes, c->tile_bits, c->tile16 ? 0u : 1u, c->tile16, true};
     HIP_TRY(hipMalloc(c->chunk_table.out(), (size_t)gs_emit_chunks(std::max(capacity, row_cap)) * 4));
     if (c->tight_ok) {
         HIP_TRY(hipMalloc(c->arena.out(), (size_t)row_cap * 12));
@@ -118,7 +122,7 @@ GS_EXPORT int32_t gs_create(const gs_config* cfg, gs_ctx** out) {
 
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, cfg->device));
-    c->grid_persist = (uint32_t)prop.multiProcessorCount * 4;
+    c->opt.grid_persist = (uint32_t)prop.multiProcessorCount * 4;
     if (cfg->stream) c->stream = (hipStream_t)cfg->stream;
     else { HIP_TRY(hipStreamCreateWithFlags(c->own_stream.out(), hipStreamNonBlocking)); c->stream = c->own_stream; }
 
@@ -296,22 +300,25 @@ GS_EXPORT int32_t gs_slab_width(gs_ctx* c, uint32_t* px_begin, uint32_t* px_widt
     return GS_OK;
 }
 
+// One member of the ring: the options go into its record (GsOptions) and nowhere else; GS_OPT_RESET_TIMING is no option but a
+// reset of the member's own counters.
 static int32_t set_option_one(gs_ctx* c, int32_t key, int64_t value) {
     c->gr.valid = false; // a captured frame holds the options it was recorded with
+    GsOptions& o = c->opt;
     switch (key) {
-    case GS_OPT_FRAME_GRAPH: c->gr.use = (value != 0); return GS_OK;
-    case GS_OPT_BLEND_ABLATION: c->blend_ablation = (uint32_t)value & 0x3FFFFu; return GS_OK;
-    case GS_OPT_PERSISTENT_GRID: if (value <= 0) break; c->grid_persist = (uint32_t)value; return GS_OK;
+    case GS_OPT_FRAME_GRAPH: o.frame_graph = (value != 0); return GS_OK;
+    case GS_OPT_BLEND_ABLATION: o.blend_ablation = (uint32_t)value & 0x3FFFFu; return GS_OK;
+    case GS_OPT_PERSISTENT_GRID: if (value <= 0) break; o.grid_persist = (uint32_t)value; return GS_OK;
     case GS_OPT_RESET_TIMING: c->timed_from = c->frames; c->max_I_seen = 0; c->truncated_frames = 0; return GS_OK;
-    case GS_OPT_EMIT_ORDER: if (value < 0 || value > 2) break; c->emit_order = (int)value; return GS_OK;
+    case GS_OPT_EMIT_ORDER: if (value < 0 || value > 2) break; o.emit_order = (int)value; return GS_OK;
     case GS_OPT_UNFUSED: return GS_OK; // (removed in ABI 3: the fused projection+scan+emission launch measured slower; accepted, ignored)
-    case GS_OPT_DEBUG_VIEW: if (value < 0 || value > 4) break; c->debug_view = (uint32_t)value; return GS_OK;
-    case GS_OPT_TILE_CULL: c->tile_cull = (value != 0); return GS_OK;
-    case GS_OPT_PROJ_CHUNKS: if (value != 0 && value != 2 && value != 4 && value != 8) break; c->tight_nb = (uint32_t)value; return GS_OK;
+    case GS_OPT_DEBUG_VIEW: if (value < 0 || value > 4) break; o.debug_view = (uint32_t)value; return GS_OK;
+    case GS_OPT_TILE_CULL: o.tile_cull = (value != 0); return GS_OK;
+    case GS_OPT_PROJ_CHUNKS: if (value != 0 && value != 2 && value != 4 && value != 8) break; o.tight_nb = (uint32_t)value; return GS_OK;
     case GS_OPT_SELECT_TINT: // (the captured frame is dropped above: its projection node holds the tint by value)
         if (!has_state(c)) return fail(GS_ERR_INVALID_ARGUMENT, "gs_set_option: GS_OPT_SELECT_TINT needs GS_FLAG_SPLAT_STATE");
         if (value < 0 || value > 0xFFFFFFFFll) break;
-        c->select_tint = (uint32_t)value;
+        o.select_tint = (uint32_t)value;
         return GS_OK;
     default: break;
     }

@@ -9,7 +9,6 @@
 // member's stream and returns when done.  The other two drain the ring (gs_wait) and run on the context's stream, as the state
 // calls do.  None of them is a frame: nothing of the frame state, the statistics or a captured graph is touched.
 #include "gs_runtime.h"
-#include "gs_tight.h"
 
 static_assert(sizeof(gs_coverage_rec) == 16 && offsetof(gs_coverage_rec, hits) == 8 && offsetof(gs_coverage_rec, max_weight) == 12, "gs_coverage_rec layout");
 
@@ -64,8 +63,7 @@ GS_EXPORT int32_t gs_coverage_accumulate(gs_ctx* root, const gs_cover_region* rg
     }
     if (count) { // the 8x8 blocks that hold a pixel of the cut rect
         const uint32_t bx0 = x0 / 8u, bx1 = (x1 + 7u) / 8u, by0 = r.y0 / 8u, by1 = (r.y1 + 7u) / 8u;
-        gs_launch_coverage(c->gdata, c->notes.valsS, c->ranges, c->frame, c->notes.last_tight ? GS_ID_MASK : 0xFFFFFFFFu, bx0, by0, bx1 - bx0, by1 - by0, r,
-                           root->cov, c->stream);
+        gs_launch_coverage(frame_lists(c), bx0, by0, bx1 - bx0, by1 - by0, r, root->cov, c->stream);
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipStreamSynchronize(c->stream)); // (also: the caller's mask has been copied, the planes' first zeroing is done)

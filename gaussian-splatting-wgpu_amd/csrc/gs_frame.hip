@@ -44,87 +44,106 @@ static inline void mark(gs_ctx* c, int i) { // stage boundary i: closes stage i-
 
 static void mark_cb(void* p, int i) { mark((gs_ctx*)p, i); }
 
-// Every launch of one frame, in order, on the context's stream (directly, or into a stream capture).
-static int32_t record_frame(gs_ctx* c, const GsUniforms& u, bool debug, void* ext_rgba8, bool tight) {
-    const GsFrame& f = c->frame;
+GsLists frame_lists(const gs_ctx* c) {
+    return GsLists{c->gdata, c->notes.valsS, c->ranges, c->frame, c->notes.last_tight ? GS_ID_MASK : 0xFFFFFFFFu};
+}
+
+// The projection's launch for this frame, left in c->pre: record_frame launches it, a replay patches the captured node from it.
+static void prepare_projection(gs_ctx* c, const GsUniforms& u, bool tight) {
+    gs_preprocess_prepare(c->pre, c->scene, u, c->frame, c->gdata, c->counts, tight, c->arena, c->rowptr, c->ctl, c->opt.tight_nb, has_state(c),
+                          tint_of(c->opt.select_tint));
+}
+
+// ---- binning: one function per pipeline, from the first launch after the projection (stage mark 1) to `ranges` (mark 5 follows).
+// Each returns the frame's notes: where the sorted lists are and what made them. ------------------------------------------------
+
+// The tight row pipeline (k_rows.hip).  Stage brackets: "scan" = the gaussian-level sort by depth bucket, "emit" = the row sort
+// (the row items take write_tile_ids' place), "sort" = count + scan + expansion into the final lists, "ranges" = nothing (they
+// fall out of the scan).
+static FrameNotes bin_tight(gs_ctx* c) {
     hipStream_t st = c->stream;
-    FrameNotes& nt = c->notes;
+    gs_launch_gsort(c->counts, c->rowptr, c->n, c->gsort_scratch, c->grec, c->chunk_table, (uint32_t)gs_emit_chunks(std::max(c->capacity, c->row_cap)),
+                    &c->ctl->num_visible, &c->ctl->num_slots, c->opt.grid_persist, st);
+    mark(c, 2);
+    gs_launch_rows(c->arena, c->grec, c->chunk_table, c->rows_sorted, c->ctl, c->rows_status, (uint32_t)c->row_cap, c->M3, c->tileoff, c->rowtot, c->frame,
+                   c->valsA, c->ranges, c->opt.grid_persist / 4u, c->sticky, c->h_rep, st, mark_cb, c);
+    mark(c, 4);
+    return FrameNotes{nullptr, c->valsA, /*passes*/ 1u, /*walkers*/ 1u, /*by_index*/ false, /*keys16*/ false, /*tight*/ true};
+}
+
+// What the two reference pipelines share behind their emission into keysA / valsA: the instance sort by `plan`, the ranges.
+static FrameNotes sort_to_ranges(gs_ctx* c, const GsSort& plan, bool by_index) {
+    hipStream_t st = c->stream;
+    mark(c, 3);
+    const GsSortPair sorted = gs_launch_sort(plan, c->ctl, c->sort_status, (uint32_t)c->capacity, c->opt.grid_persist, st);
+    mark(c, 4);
+    const uint32_t grid = c->opt.grid_persist * 2; // streaming: 8 workgroups/CU
+    if (plan.keys16) gs_launch_ranges16((const uint16_t*)sorted.keys, c->ctl, (uint32_t)c->capacity, c->T, c->ranges, grid, c->sticky, c->h_rep, st);
+    else gs_launch_ranges(sorted.keys, c->ctl, (uint32_t)c->capacity, c->T, c->ranges, grid, c->sticky, c->h_rep, st);
+    return FrameNotes{sorted.keys, sorted.vals, plan.passes, /*walkers*/ 1u, by_index, plan.keys16, /*tight*/ false};
+}
+
+// The reference's order: scan counts in gaussian order, emit in gaussian order, sort by the full key.  debug: the unsorted arrays
+// are copied for their taps, between emission and sort.
+static int32_t bin_by_index(gs_ctx* c, bool debug, FrameNotes& nt) {
+    hipStream_t st = c->stream;
+    gs_launch_scan(c->counts, c->n, c->offsets, c->scan_status, &c->ctl->scan_ticket[0], c->ctl, st);
+    mark(c, 2);
+    gs_launch_emit(c->gdata, c->counts, c->offsets, c->frame, c->keysA, c->valsA, c->ctl, st);
+    if (debug) {
+        const size_t kb = (size_t)c->capacity * 4;
+        if (!c->keysU) {
+            HIP_TRY(hipMalloc(c->keysU.out(), kb));
+            HIP_TRY(hipMalloc(c->valsU.out(), kb));
+        }
+        HIP_TRY(hipMemcpyAsync(c->keysU, c->keysA, kb, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(c->valsU, c->valsA, kb, hipMemcpyDeviceToDevice, st));
+    }
+    nt = sort_to_ranges(c, c->sort_index, true);
+    return GS_OK;
+}
+
+// Depth-ordered emission: the key is tile*1000 + bucket, and the required order inside a tile is (bucket, gaussian index).
+// Sorting the N_vis visible GAUSSIANS by bucket first (stable, 10 bits, ~16x fewer elements than instances: k_gsort.hip) and
+// emitting their instances in that order leaves only the tile id for the stable instance sort: 2 digits of key/1000 instead of
+// 3 of the key.  The sorted (key,value) arrays are identical.
+static FrameNotes bin_by_depth(gs_ctx* c) {
+    gs_launch_gsort(c->counts, nullptr, c->n, c->gsort_scratch, c->grec, c->chunk_table, (uint32_t)gs_emit_chunks(std::max(c->capacity, c->row_cap)),
+                    &c->ctl->num_visible, &c->ctl->num_intersections, c->opt.grid_persist, c->stream);
+    mark(c, 2);
+    gs_launch_emit_balanced(c->gdata, c->grec, c->chunk_table, c->frame, c->keysA, c->valsA, c->ctl, c->opt.grid_persist * 2, c->tile_bits, c->tile_passes,
+                            c->tile16, c->stream);
+    return sort_to_ranges(c, c->sort_tile, false);
+}
+
+// Every launch of one frame, in order, on the context's stream (directly, or into a stream capture): zero, projection, binning,
+// blend.  index_order: what a frame of the reference's binning emits in (enqueue_frame decides; a debug frame always does).
+static int32_t record_frame(gs_ctx* c, const GsUniforms& u, bool debug, void* ext_rgba8, bool tight, bool index_order) {
+    hipStream_t st = c->stream;
+    const GsOptions& o = c->opt;
     gs_launch_zero(c->ctl_mem, tight ? c->ctl_bytes_tight : c->ctl_bytes, st); // (every part is a multiple of 256 bytes)
     c->h_ctl_valid = false;
     if (debug) HIP_TRY(hipMemsetAsync(c->gdata, 0, std::max<size_t>((size_t)c->n * 64, 256), st));
     mark(c, 0);
-    gs_preprocess_prepare(c->pre, c->scene, u, f, c->gdata, c->counts, tight, c->arena, c->rowptr, c->ctl, c->tight_nb, has_state(c),
-                          tint_of(c->select_tint));
+    prepare_projection(c, u, tight);
     gs_launch_preprocess(c->pre, st);
     mark(c, 1);
-    const bool by_index = !tight && (debug || c->index_order);
-    bool keys16 = false;
-    if (tight) {
-        // The tight row pipeline (k_rows.hip).  Stage brackets: "scan" = the gaussian-level sort by depth bucket, "emit" = the
-        // row sort (the row items take write_tile_ids' place), "sort" = count + scan + expansion into the final lists,
-        // "ranges" = nothing (they fall out of the scan).
-        gs_launch_gsort(c->counts, c->rowptr, c->n, c->gsort_scratch, c->grec, c->chunk_table, (uint32_t)gs_emit_chunks(std::max(c->capacity, c->row_cap)),
-                        &c->ctl->num_visible, &c->ctl->num_slots, c->grid_persist, st);
-        mark(c, 2);
-        gs_launch_rows(c->arena, c->grec, c->chunk_table, c->rows_sorted, c->ctl, c->rows_status, (uint32_t)c->row_cap, c->M3, c->tileoff, c->rowtot, f, c->valsA,
-                       c->ranges, c->grid_persist / 4u, c->sticky, c->h_rep, st, mark_cb, c);
-        nt.keysS = nullptr;
-        nt.valsS = c->valsA;
-        mark(c, 4);
-    } else if (by_index) {
-        // the reference's order: scan counts in gaussian order, emit in gaussian order, sort by the full key
-        gs_launch_scan(c->counts, c->n, c->offsets, c->scan_status, &c->ctl->scan_ticket[0], c->ctl, st);
-        mark(c, 2);
-        gs_launch_emit(c->gdata, c->counts, c->offsets, nullptr, nullptr, f, c->keysA, c->valsA, c->ctl, st);
-    } else {
-        // Depth-ordered emission: the key is tile*1000 + bucket, and the required order inside a tile is (bucket,
-        // gaussian index).  Sorting the N_vis visible GAUSSIANS by bucket first (stable, 10 bits, ~16x fewer elements
-        // than instances: k_gsort.hip) and emitting their instances in that order leaves only the tile id for the stable
-        // instance sort: 2 digits of key/1000 instead of 3 of the key.  The sorted (key,value) arrays are identical.
-        gs_launch_gsort(c->counts, nullptr, c->n, c->gsort_scratch, c->grec, c->chunk_table, (uint32_t)gs_emit_chunks(std::max(c->capacity, c->row_cap)),
-                        &c->ctl->num_visible, &c->ctl->num_intersections, c->grid_persist, st);
-        mark(c, 2);
-        gs_launch_emit_balanced(c->gdata, c->grec, c->chunk_table, f, c->keysA, c->valsA, c->ctl, c->grid_persist * 2,
-                                c->tile_bits, c->tile_passes, c->tile16, st);
-        keys16 = c->tile16;
-    }
-    if (debug) {
-        if (!c->keysU) {
-            HIP_TRY(hipMalloc(c->keysU.out(), (size_t)c->capacity * 4));
-            HIP_TRY(hipMalloc(c->valsU.out(), (size_t)c->capacity * 4));
-        }
-        HIP_TRY(hipMemcpyAsync(c->keysU, c->keysA, (size_t)c->capacity * 4, hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipMemcpyAsync(c->valsU, c->valsA, (size_t)c->capacity * 4, hipMemcpyDeviceToDevice, st));
-    }
-    if (!tight) {
-        mark(c, 3);
-        if (by_index)
-            gs_launch_sort(c->keysA, c->valsA, c->keysB, c->valsB, c->ctl, c->ctl->sort_ticket, &c->ctl->hist[0][0], &c->ctl->num_intersections,
-                           (uint32_t)c->capacity, c->passes, 8, 0, c->sort_status, c->grid_persist, false, nullptr, nullptr, st, &nt.keysS, &nt.valsS);
-        else
-            gs_launch_sort(c->keysA, c->valsA, c->keysB, c->valsB, c->ctl, c->ctl->sort_ticket, &c->ctl->hist[0][0], &c->ctl->num_intersections,
-                           (uint32_t)c->capacity, c->tile_passes, c->tile_bits, keys16 ? 0 : 1, c->sort_status, c->grid_persist, /*have_hist=*/true,
-                           nullptr, nullptr, st, &nt.keysS, &nt.valsS, keys16);
-        mark(c, 4);
-        if (keys16) gs_launch_ranges16((const uint16_t*)nt.keysS, c->ctl, (uint32_t)c->capacity, c->T, c->ranges, c->grid_persist * 2, c->sticky, c->h_rep, st);
-        else gs_launch_ranges(nt.keysS, c->ctl, (uint32_t)c->capacity, c->T, c->ranges, c->grid_persist * 2, c->sticky, c->h_rep, st); // streaming: 8 workgroups/CU
-    }
-    nt.last_passes = tight ? 1u : (by_index ? c->passes : c->tile_passes);
-    nt.last_by_index = by_index;
-    nt.last_keys16 = keys16;
-    nt.last_tight = tight;
+    FrameNotes& nt = c->notes;
+    if (tight) nt = bin_tight(c);
+    else if (!debug && !index_order) nt = bin_by_depth(c);
+    else if (const int32_t rc = bin_by_index(c, debug, nt); rc != GS_OK) return rc;
     mark(c, 5);
     uint32_t* target = ext_rgba8 ? (uint32_t*)ext_rgba8 : c->rgba8.get();
-    if ((c->blend_ablation & 0x10000u) && !c->blend_prof) HIP_TRY(hipMalloc(c->blend_prof.out(), (size_t)(1u << 20) * 16));
+    const bool prof = (o.blend_ablation & 0x10000u) != 0;
+    if (prof && !c->blend_prof) HIP_TRY(hipMalloc(c->blend_prof.out(), (size_t)(1u << 20) * 16));
     const bool aux = (c->cfg.flags & GS_FLAG_AUX_OUTPUTS) != 0; // the planes go to the context's own buffers, also under gs_render_to
-    const int walkers = gs_launch_blend(c->gdata, nt.valsS, c->ranges, f, target, c->rgbf, aux, c->alpha, c->depth, c->ctl, c->tile_depth,
-                                        (c->cfg.flags & GS_FLAG_EXACT_BLEND) != 0, c->blend_ablation & 0xFFFFu, tight, st,
-                                        (c->blend_ablation & 0x10000u) ? c->blend_prof.get() : nullptr, &c->blend_prof_blocks);
+    const int walkers = gs_launch_blend(frame_lists(c), target, c->rgbf, aux, c->alpha, c->depth, c->ctl, c->tile_depth, (c->cfg.flags & GS_FLAG_EXACT_BLEND) != 0,
+                                        o.blend_ablation & 0xFFFFu, st, prof ? c->blend_prof.get() : nullptr, &c->blend_prof_blocks);
     if (walkers == -2) return fail(GS_ERR_INVALID_ARGUMENT, "blend: GS_FLAG_AUX_OUTPUTS without its alpha / depth planes");
-    if (walkers < 0) return fail(GS_ERR_INVALID_ARGUMENT, "unsupported tile size %u", f.tile_size);
+    if (walkers < 0) return fail(GS_ERR_INVALID_ARGUMENT, "unsupported tile size %u", c->frame.tile_size);
     nt.blend_walkers = (uint32_t)walkers;
     mark(c, 6);
-    if (c->debug_view) gs_launch_debug_view(c->ranges, f, c->debug_view, target, st); // developer views, after the timed stages
+    if (o.debug_view) gs_launch_debug_view(c->ranges, c->frame, o.debug_view, target, st); // developer views, after the timed stages
     return GS_OK; // (no copy back: the frame's report is in host-mapped memory when the stream has drained, gs_device.h GsReport)
 }
 
@@ -137,30 +156,29 @@ void drop_graph(gs_ctx* c) {
 
 static int32_t enqueue_frame(gs_ctx* c, const GsUniforms& u, bool debug, void* ext_rgba8) {
     hipStream_t st = c->stream;
-    if (c->emit_order == 2) {
+    bool index_order = (c->opt.emit_order == 1); // the emission order of this frame, where it takes the reference's binning
+    if (c->opt.emit_order == 2) {
         // auto: the depth-ordered pipeline saves (passes - tile_passes) full sweeps of the instance arrays and the histogram
         // pass, and costs the gaussian-level counting sort (three small kernels, k_gsort.hip).  Measured at config B: whole
         // canvas (18.5 M instances) 1.42 vs 1.50 ms, one of 8 slabs (1.9-2.6 M) 418-508 vs 455-566 us, one of 4 slabs 586-699 vs
         // 618-743 us per frame; below ~1 M instances both are launch-bound and the same.
         const uint64_t saved = c->passes > c->tile_passes ? c->passes - c->tile_passes : 0;
-        c->index_order = !(c->have_frame && saved * (uint64_t)c->h_rep->num_intersections >= 1000000ull);
-    } else {
-        c->index_order = (c->emit_order == 1);
+        index_order = !(c->have_frame && saved * (uint64_t)c->h_rep->num_intersections >= 1000000ull);
     }
     // tight (opacity-aware) binning: product frames only; the sub-block mask shares the value word with the gaussian id
-    const bool tight = !debug && c->tile_cull && c->tight_ok && c->n < (1u << GS_ID_BITS);
+    const bool tight = !debug && c->opt.tile_cull && c->tight_ok && c->n < (1u << GS_ID_BITS);
     // GS_OPT_FRAME_GRAPH: replay the captured frame instead of issuing its ~16 commands one by one (frames without per-stage
     // events or profiler output only).  The capture holds every buffer address and launch geometry of the frame, so anything
     // that moves a buffer or changes an option drops it (gr.valid); the emission order and the output address are part
     // of its identity (GraphKey).
-    const bool graphable = c->gr.use && !debug && !c->have_events && !(c->blend_ablation & 0x10000u) && c->n;
+    const bool graphable = c->opt.frame_graph && !debug && !c->have_events && !(c->opt.blend_ablation & 0x10000u) && c->n;
     if (graphable) {
-        const GraphKey key{c->index_order, tight, ext_rgba8, c->alpha, c->depth};
+        const GraphKey key{index_order, tight, ext_rgba8, c->alpha, c->depth};
         if (!c->gr.exec || !c->gr.valid || !(c->gr.key == key)) {
             if (c->gr.exec) HIP_TRY(hipStreamSynchronize(st)); // a replay of the old capture may still be running: not destroyed under it
             drop_graph(c);
             HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
-            const int32_t rc = record_frame(c, u, debug, ext_rgba8, tight);
+            const int32_t rc = record_frame(c, u, debug, ext_rgba8, tight, index_order);
             const hipError_t e = hipStreamEndCapture(st, &c->gr.graph); // (held by the context at once: drop_graph destroys it)
             if (rc != GS_OK) { drop_graph(c); return rc; }
             if (e != hipSuccess || !c->gr.graph) return fail(GS_ERR_HIP, "frame graph capture: %s", hipGetErrorString(e));
@@ -177,8 +195,8 @@ static int32_t enqueue_frame(gs_ctx* c, const GsUniforms& u, bool debug, void* e
                 hipKernelNodeParams kp;
                 if (hipGraphKernelNodeGetParams(nd, &kp) == hipSuccess && kp.func == c->pre.func) { c->gr.pre_node = nd; ++found; }
             }
-            if (found != 1) { // cannot address the projection's node: this frame still runs from the capture, later ones directly
-                c->gr.use = false;
+            if (found != 1) { // cannot address the projection's node: this frame still runs from the capture, this member's later ones
+                c->opt.frame_graph = false; // directly (until the option is set again)
                 c->gr.pre_node = nullptr;
             }
             c->gr.key = key;
@@ -187,8 +205,7 @@ static int32_t enqueue_frame(gs_ctx* c, const GsUniforms& u, bool debug, void* e
         } else {
             c->notes = c->gr.notes;
             // (the launch descriptor too: the frame in between prepared it for ITS projection -- other kernel, grid and outputs)
-            gs_preprocess_prepare(c->pre, c->scene, u, c->frame, c->gdata, c->counts, tight, c->arena, c->rowptr, c->ctl, c->tight_nb, has_state(c),
-                                  tint_of(c->select_tint));
+            prepare_projection(c, u, tight);
             hipKernelNodeParams kp{};
             kp.func = const_cast<void*>(c->pre.func);
             kp.gridDim = dim3(c->pre.blocks); kp.blockDim = dim3(256); kp.sharedMemBytes = 0;
@@ -198,7 +215,7 @@ static int32_t enqueue_frame(gs_ctx* c, const GsUniforms& u, bool debug, void* e
         HIP_TRY(hipGraphLaunch(c->gr.exec, st));
         c->gr.frames++;
     } else {
-        const int32_t rc = record_frame(c, u, debug, ext_rgba8, tight);
+        const int32_t rc = record_frame(c, u, debug, ext_rgba8, tight, index_order);
         if (rc != GS_OK) return rc;
     }
     c->keysG_valid = false;
@@ -282,9 +299,8 @@ GS_EXPORT int32_t gs_wait(gs_ctx* c) {
         const int32_t rc = wait_one(s);
         if (rc != GS_OK && first == GS_OK) { first = rc; memcpy(msg, g_err, sizeof(msg)); }
     }
-    c->cap_hint = std::max(c->cap_hint, c->capacity);
-    c->row_hint = std::max(c->row_hint, c->row_cap);
-    for (gs_ctx* s : c->shadows) { c->cap_hint = std::max(c->cap_hint, s->capacity); c->row_hint = std::max(c->row_hint, s->row_cap); }
+    c->cap_hint = std::max(c->cap_hint, over_ring(c, [](const gs_ctx* m) { return m->capacity; }, true));
+    c->row_hint = std::max(c->row_hint, over_ring(c, [](const gs_ctx* m) { return m->row_cap; }, true));
     if (first != GS_OK) memcpy(g_err, msg, sizeof(msg));
     return first;
 }
@@ -301,10 +317,7 @@ static int32_t add_shadow(gs_ctx* c) {
     s->is_shadow = true;
     rc = gs_share_splats(s, c);
     if (rc != GS_OK) { gs_destroy(s); return rc; }
-    s->emit_order = c->emit_order; s->tile_cull = c->tile_cull; s->debug_view = c->debug_view;
-    s->blend_ablation = c->blend_ablation; s->grid_persist = c->grid_persist; s->timed_from = 0; s->tight_nb = c->tight_nb;
-    s->select_tint = c->select_tint;
-    s->gr.use = c->gr.use;
+    s->opt = c->opt; // (everything else a member starts with is gs_create's: its own counters, timed_from 0)
     c->shadows.push_back(s);
     return GS_OK;
 }

@@ -24,22 +24,37 @@ uint64_t gs_emit_chunks(uint64_t capacity);
 // grec: the gaussian-level sort's records {id, count word, first output slot, -} in (bucket, index) order
 void gs_launch_emit_balanced(const void* gdata, const void* grec, const uint32_t* chunk_table, const GsFrame& f, uint32_t* keys, uint32_t* values,
                              GsControl* ctl, uint32_t grid, uint32_t hist_bits, uint32_t hist_passes, bool keys16, hipStream_t st);
-void gs_launch_emit(const void* gdata, const uint32_t* counts, const uint32_t* offsets, const uint32_t* perm, const uint32_t* n_dev,
-                    const GsFrame& f, uint32_t* keys, uint32_t* values, GsControl* ctl, hipStream_t st);
+void gs_launch_emit(const void* gdata, const uint32_t* counts, const uint32_t* offsets, const GsFrame& f, uint32_t* keys, uint32_t* values,
+                    GsControl* ctl, hipStream_t st);
 void gs_launch_ranges16(const uint16_t* tiles, const GsControl* ctl, uint32_t capacity, uint32_t T, uint32_t* ranges, uint32_t grid,
                         uint32_t* sticky, GsReport* rep, hipStream_t st);
-void gs_launch_rebuild_keys(const uint16_t* tiles, const uint32_t* vals, const uint32_t* counts, uint32_t count, uint32_t n, uint32_t id_mask,
-                            uint32_t* keys, hipStream_t st);
+void gs_launch_rebuild_keys(const uint16_t* tiles, const uint32_t* vals, const uint32_t* counts, uint32_t count, uint32_t n, uint32_t* keys,
+                            hipStream_t st);
 void gs_launch_ranges(const uint32_t* keys, const GsControl* ctl, uint32_t capacity, uint32_t T, uint32_t* ranges, uint32_t grid,
                       uint32_t* sticky, GsReport* rep, hipStream_t st);
 uint32_t gs_sort_tiles(uint64_t capacity);
-void gs_launch_sort(uint32_t* keysA, uint32_t* valsA, uint32_t* keysB, uint32_t* valsB, GsControl* ctl, uint32_t* tickets, uint32_t* hist,
-                    const uint32_t* n_ptr, uint32_t capacity, uint32_t passes, uint32_t bits, uint32_t by_tile, uint32_t* status,
-                    uint32_t grid, bool have_hist, const uint32_t* aux_table, uint32_t* aux_out, hipStream_t st, uint32_t** out_keys,
-                    uint32_t** out_vals, bool keys16 = false);
-int gs_launch_blend(const void* gdata, const uint32_t* values, const uint32_t* ranges, const GsFrame& f, uint32_t* rgba8, float* rgbf,
-                    bool aux, float* alpha, float* depth, GsControl* ctl, uint32_t* tile_depth, bool exact, uint32_t ablation, bool masked, hipStream_t st, uint32_t* prof = nullptr,
-                    uint32_t* prof_blocks = nullptr);
+// One instance sort: the pair of arrays that holds the input, the pair the sweeps alternate with, and the digit plan -- `passes`
+// digits of `bits` bits of the sort word (the key, or key/1000 when by_tile).  keys16: the key arrays hold uint16_t sort words
+// (by_tile must be 0 and have_hist true).  have_hist: the digit counts are already in ctl->hist (the balanced emission leaves them).
+struct GsSortPair { uint32_t *keys, *vals; };
+struct GsSort {
+    GsSortPair in, alt;
+    uint32_t passes, bits, by_tile;
+    bool keys16, have_hist;
+};
+GsSortPair gs_launch_sort(const GsSort& s, GsControl* ctl, uint32_t* status, uint32_t capacity, uint32_t grid, hipStream_t st); // the pair that holds the result
+// The lists of one frame as their readers take them (blend, pick, coverage): the projection's records, the values in list order, the
+// per-tile ranges, the frame geometry, and the mask that leaves a value's gaussian id (GS_ID_MASK where the sub-block mask of the
+// tight binning rides above it, all ones otherwise).
+struct GsLists {
+    const void* gdata;
+    const uint32_t* values;
+    const uint32_t* ranges;
+    GsFrame f;
+    uint32_t id_mask;
+};
+int gs_launch_blend(const GsLists& L, uint32_t* rgba8, float* rgbf, bool aux, float* alpha, float* depth, GsControl* ctl, uint32_t* tile_depth,
+                    bool exact, uint32_t ablation, hipStream_t st, uint32_t* prof = nullptr, uint32_t* prof_blocks = nullptr);
 void gs_launch_debug_view(const uint32_t* ranges, const GsFrame& f, uint32_t view, uint32_t* rgba8, hipStream_t st);
 void gs_launch_assemble(const void* slabs, void* image, uint32_t width, uint32_t height, const uint32_t* d_px_bounds, uint32_t n_slabs,
                         uint64_t slab_stride_px, hipStream_t st);
@@ -94,13 +109,11 @@ struct gs_xform;
 void gs_launch_xform(const GsScene& s, uint32_t n, const uint32_t* ids, uint32_t m, const gs_xform& x, hipStream_t st);
 // k_pick.hip: gs_pick, one wave per query over the last frame's lists (queries: {x, y} pairs; results: 12 words per query;
 // contrib: max_contrib {id, weight} pairs per query, or null)
-void gs_launch_pick(const void* gdata, const uint32_t* values, const uint32_t* ranges, const GsFrame& f, uint32_t id_mask, const void* d_queries,
-                    uint32_t n, void* d_results, uint32_t max_contrib, void* d_contrib, hipStream_t st);
+void gs_launch_pick(const GsLists& L, const void* d_queries, uint32_t n, void* d_results, uint32_t max_contrib, void* d_contrib, hipStream_t st);
 // k_coverage.hip: gs_coverage_accumulate, one wave per 8x8 pixel block [bx0, bx0 + nbx) x [by0, by0 + nby) (in blocks) over the last
 // frame's lists, adding into `planes` (16 bytes per splat: gs_coverage_rec)
 struct GsCoverDev { // a gs_cover_region as the kernel reads it
     uint32_t x0, y0, x1, y1; // canvas pixels [x0, x1) x [y0, y1)
     const uint8_t* mask;     // device u8[height][width] of the canvas, or null
 };
-void gs_launch_coverage(const void* gdata, const uint32_t* values, const uint32_t* ranges, const GsFrame& f, uint32_t id_mask, uint32_t bx0,
-                        uint32_t by0, uint32_t nbx, uint32_t nby, const GsCoverDev& r, void* planes, hipStream_t st);
+void gs_launch_coverage(const GsLists& L, uint32_t bx0, uint32_t by0, uint32_t nbx, uint32_t nby, const GsCoverDev& r, void* planes, hipStream_t st);

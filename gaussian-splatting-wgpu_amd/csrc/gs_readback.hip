@@ -27,7 +27,7 @@ static int32_t tap(gs_ctx* c, int32_t which, void** ptr, uint64_t* bytes) {
             if (c->pending) { int32_t rc = wait_one(c); if (rc != GS_OK) return rc; }
             if (!c->keysG) HIP_TRY(hipMalloc(c->keysG.out(), (size_t)c->capacity * 4));
             if (nt.last_tight) gs_launch_rows_rebuild_keys(c->ranges, c->T, nt.valsS, c->counts, (uint32_t)I, c->n, c->keysG, c->stream);
-            else gs_launch_rebuild_keys((const uint16_t*)nt.keysS, nt.valsS, c->counts, (uint32_t)I, c->n, 0xFFFFFFFFu, c->keysG, c->stream);
+            else gs_launch_rebuild_keys((const uint16_t*)nt.keysS, nt.valsS, c->counts, (uint32_t)I, c->n, c->keysG, c->stream);
             HIP_TRY(hipStreamSynchronize(c->stream));
             c->keysG_valid = true;
         }
@@ -72,36 +72,40 @@ int32_t last_frame(gs_ctx* root, const char* who, gs_ctx** out) {
     return GS_OK;
 }
 
+// The size protocol of a read, for both kinds of tap: report the size; copy (*copy) only into a destination that is given, and
+// refuse one that is too small.
+static int32_t size_protocol(uint64_t bytes, const void* dst, uint64_t size, uint64_t* written, bool* copy) {
+    if (written) *written = bytes;
+    *copy = dst != nullptr;
+    if (dst && size < bytes) return fail(GS_ERR_INVALID_ARGUMENT, "gs_read_buffer: need %llu bytes, got %llu", (unsigned long long)bytes, (unsigned long long)size);
+    return GS_OK;
+}
+
 GS_EXPORT int32_t gs_read_buffer(gs_ctx* c, int32_t which, void* dst, uint64_t size, uint64_t* written) {
     if (!c) return fail(GS_ERR_INVALID_ARGUMENT, "gs_read_buffer: null ctx");
+    void* p = nullptr;
+    uint64_t bytes = 0;
+    bool copy = false;
     if (which == GS_BUF_SPLAT_STATE) { // (state calls return when done: the plane is at rest; frames in flight only read it)
-        void* p = nullptr;
-        uint64_t bytes = 0;
-        const int32_t rc = state_tap(c, &p, &bytes);
-        if (rc != GS_OK) return rc;
-        if (written) *written = bytes;
-        if (!dst) return GS_OK;
-        if (size < bytes) return fail(GS_ERR_INVALID_ARGUMENT, "gs_read_buffer: need %llu bytes, got %llu", (unsigned long long)bytes, (unsigned long long)size);
+        int32_t rc = state_tap(c, &p, &bytes);
+        if (rc == GS_OK) rc = size_protocol(bytes, dst, size, written, &copy);
+        if (rc != GS_OK || !copy) return rc;
         HIP_TRY(hipSetDevice(c->cfg.device));
         if (bytes) HIP_TRY(hipMemcpy(dst, p, bytes, hipMemcpyDeviceToHost));
         return GS_OK;
     }
     { int32_t rc = last_frame(c, "gs_read_buffer", &c); if (rc != GS_OK) return rc; }
+    const GsLists L = frame_lists(c);
     const bool tight = c->notes.last_tight;
     const uint64_t I = std::min<uint64_t>(c->h_rep->num_intersections, c->capacity);
     // two buffers are made on the host, not copied: the block masks of a frame with the reference's binning (the blend tests every
     // block of the tile itself), and the tile counts of a tight frame (its count words hold row-item slots, k_preprocess.hip:
     // the tile counts of the tap are those of its lists)
     const bool all_masks = which == GS_BUF_BLOCK_MASKS && !tight, list_counts = which == GS_BUF_TILE_COUNTS && tight;
-    void* p = nullptr;
-    uint64_t bytes = 0;
     if (all_masks) bytes = I * 4;
     else if (list_counts) bytes = (uint64_t)c->n * 4;
     else { int32_t rc = tap(c, which, &p, &bytes); if (rc != GS_OK) return rc; }
-    // the size protocol: report the size, copy only into a destination that is given and large enough
-    if (written) *written = bytes;
-    if (!dst) return GS_OK;
-    if (size < bytes) return fail(GS_ERR_INVALID_ARGUMENT, "gs_read_buffer: need %llu bytes, got %llu", (unsigned long long)bytes, (unsigned long long)size);
+    { int32_t rc = size_protocol(bytes, dst, size, written, &copy); if (rc != GS_OK || !copy) return rc; }
     uint32_t* w = (uint32_t*)dst;
     if (all_masks) {
         const uint32_t nb = (c->frame.tile_size / 8) * (c->frame.tile_size / 8);
@@ -111,16 +115,16 @@ GS_EXPORT int32_t gs_read_buffer(gs_ctx* c, int32_t which, void* dst, uint64_t s
     }
     if (list_counts) {
         std::vector<uint32_t> v(I);
-        if (I) HIP_TRY(hipMemcpy(v.data(), c->notes.valsS, I * 4, hipMemcpyDeviceToHost));
+        if (I) HIP_TRY(hipMemcpy(v.data(), L.values, I * 4, hipMemcpyDeviceToHost));
         memset(w, 0, bytes);
-        for (uint64_t i = 0; i < I; ++i) { const uint32_t g = v[i] & GS_ID_MASK; if (g < c->n) w[g]++; }
+        for (uint64_t i = 0; i < I; ++i) { const uint32_t g = v[i] & L.id_mask; if (g < c->n) w[g]++; }
         return GS_OK;
     }
     if (bytes) HIP_TRY(hipMemcpy(dst, p, bytes, hipMemcpyDeviceToHost));
     if (which == GS_BUF_TILE_COUNTS) // device words also carry the depth bucket in their high 10 bits
         for (uint64_t i = 0; i < bytes / 4; ++i) w[i] &= GS_COUNT_MASK;
-    if (which == GS_BUF_VALUES && tight) // strip the sub-block mask
-        for (uint64_t i = 0; i < bytes / 4; ++i) w[i] &= GS_ID_MASK;
+    if (which == GS_BUF_VALUES && L.id_mask != 0xFFFFFFFFu) // strip what rides above the id
+        for (uint64_t i = 0; i < bytes / 4; ++i) w[i] &= L.id_mask;
     if (which == GS_BUF_BLOCK_MASKS) { // tight frame: the mask's sub-blocks (tile/2, or the whole 8-pixel tile) as 8x8-block bits
         const uint32_t ts = c->frame.tile_size;
         for (uint64_t i = 0; i < bytes / 4; ++i) {
@@ -153,6 +157,42 @@ GS_EXPORT int32_t gs_device_ptr(gs_ctx* c, int32_t which, void** d_ptr) {
     return tap(c, which, d_ptr, &bytes);
 }
 
+// GS_FLAG_TIMING: the stages of the last frame and their means over the frames since GS_OPT_RESET_TIMING (at most the event
+// ring's), from the member's per-frame event brackets.
+static void stage_times(const gs_ctx* c, gs_stats* out) {
+    if (!c->have_events || c->frames == 0) return;
+    const uint64_t last = c->frames - 1;
+    uint64_t first = c->timed_from;
+    if (last + 1 > GS_EV_RING && first < last + 1 - GS_EV_RING) first = last + 1 - GS_EV_RING;
+    if (first > last) first = last;
+    double sum[GS_STAGE_COUNT + 1] = {0};
+    uint32_t cnt = 0;
+    for (uint64_t fr = first; fr <= last; ++fr) {
+        const Event* e = c->ev[fr % GS_EV_RING];
+        float ms = 0, tot = 0;
+        bool ok = true;
+        float st[GS_STAGE_COUNT];
+        for (int i = 0; i < GS_STAGE_COUNT && ok; ++i) {
+            ok = hipEventElapsedTime(&ms, e[i], e[i + 1]) == hipSuccess;
+            st[i] = ms * 1000.0f;
+        }
+        ok = ok && hipEventElapsedTime(&tot, e[0], e[GS_STAGE_COUNT]) == hipSuccess;
+        if (!ok) continue;
+        for (int i = 0; i < GS_STAGE_COUNT; ++i) sum[i] += st[i];
+        sum[GS_STAGE_COUNT] += tot * 1000.0f;
+        ++cnt;
+        if (fr == last) {
+            for (int i = 0; i < GS_STAGE_COUNT; ++i) out->stage_us[i] = st[i];
+            out->frame_us = tot * 1000.0f;
+        }
+    }
+    out->frames_timed = cnt;
+    if (cnt) {
+        for (int i = 0; i < GS_STAGE_COUNT; ++i) out->stage_us_mean[i] = (float)(sum[i] / cnt);
+        out->frame_us_mean = (float)(sum[GS_STAGE_COUNT] / cnt);
+    }
+}
+
 GS_EXPORT int32_t gs_get_stats(gs_ctx* root, gs_stats* out) {
     if (!root || !out) return fail(GS_ERR_INVALID_ARGUMENT, "gs_get_stats: null argument");
     gs_ctx* c = nullptr; // everything below describes the context that rendered the last frame ...
@@ -162,8 +202,7 @@ GS_EXPORT int32_t gs_get_stats(gs_ctx* root, gs_stats* out) {
     out->num_gaussians = c->n;
     out->num_tiles = c->T;
     out->sort_passes = nt.last_passes ? nt.last_passes : c->passes;
-    out->frames = root->frames; // ... except the counters that are sums over the ring
-    for (gs_ctx* s : root->shadows) out->frames += s->frames;
+    out->frames = over_ring(root, [](const gs_ctx* m) { return m->frames; }); // ... except the counters that are sums over the ring
     out->depth_ordered = (c->have_frame && !nt.last_by_index) ? 1u : 0u;
     if (c->have_frame) {
         if (!c->h_ctl_valid) { // the blend's counters live in the control block: fetched when somebody asks
@@ -174,11 +213,9 @@ GS_EXPORT int32_t gs_get_stats(gs_ctx* root, gs_stats* out) {
         out->num_intersections = c->h_rep->num_intersections;
         out->capacity = c->capacity;
         out->max_intersections_seen = std::max<uint64_t>(c->max_I_seen, c->h_rep->num_intersections);
-        out->truncated_frames = root->truncated_frames;
-        for (gs_ctx* s : root->shadows) out->truncated_frames += s->truncated_frames;
+        out->truncated_frames = over_ring(root, [](const gs_ctx* m) { return m->truncated_frames; });
         out->frames_in_flight = (uint32_t)root->shadows.size() + 1u;
-        out->graph_frames = root->gr.frames;
-        for (gs_ctx* s : root->shadows) out->graph_frames += s->gr.frames;
+        out->graph_frames = over_ring(root, [](const gs_ctx* m) { return m->gr.frames; });
         out->tight_binning = nt.last_tight ? 1u : 0u;
         out->row_capacity = c->row_cap;
         if (nt.last_tight) {
@@ -192,38 +229,7 @@ GS_EXPORT int32_t gs_get_stats(gs_ctx* root, gs_stats* out) {
                 for (uint32_t v : depth) out->num_processed += v;
         }
         for (int k = 0; k < 64; ++k) out->num_evaluated += c->h_ctl->num_evaluated[k];
-        if (c->have_events && c->frames > 0) {
-            const uint64_t last = c->frames - 1;
-            uint64_t first = c->timed_from;
-            if (last + 1 > GS_EV_RING && first < last + 1 - GS_EV_RING) first = last + 1 - GS_EV_RING;
-            if (first > last) first = last;
-            double sum[GS_STAGE_COUNT + 1] = {0};
-            uint32_t cnt = 0;
-            for (uint64_t fr = first; fr <= last; ++fr) {
-                const Event* e = c->ev[fr % GS_EV_RING];
-                float ms = 0, tot = 0;
-                bool ok = true;
-                float st[GS_STAGE_COUNT];
-                for (int i = 0; i < GS_STAGE_COUNT && ok; ++i) {
-                    ok = hipEventElapsedTime(&ms, e[i], e[i + 1]) == hipSuccess;
-                    st[i] = ms * 1000.0f;
-                }
-                ok = ok && hipEventElapsedTime(&tot, e[0], e[GS_STAGE_COUNT]) == hipSuccess;
-                if (!ok) continue;
-                for (int i = 0; i < GS_STAGE_COUNT; ++i) sum[i] += st[i];
-                sum[GS_STAGE_COUNT] += tot * 1000.0f;
-                ++cnt;
-                if (fr == last) {
-                    for (int i = 0; i < GS_STAGE_COUNT; ++i) out->stage_us[i] = st[i];
-                    out->frame_us = tot * 1000.0f;
-                }
-            }
-            out->frames_timed = cnt;
-            if (cnt) {
-                for (int i = 0; i < GS_STAGE_COUNT; ++i) out->stage_us_mean[i] = (float)(sum[i] / cnt);
-                out->frame_us_mean = (float)(sum[GS_STAGE_COUNT] / cnt);
-            }
-        }
+        stage_times(c, out);
     }
     return GS_OK;
 }
@@ -253,8 +259,7 @@ GS_EXPORT int32_t gs_pick(gs_ctx* root, const gs_pick_query* queries, uint32_t n
     rc = pk.c.reserve(cbytes);
     if (rc != GS_OK) return rc;
     HIP_TRY(hipMemcpyAsync(pk.q, queries, (size_t)n * sizeof(gs_pick_query), hipMemcpyHostToDevice, c->stream));
-    gs_launch_pick(c->gdata, c->notes.valsS, c->ranges, c->frame, c->notes.last_tight ? GS_ID_MASK : 0xFFFFFFFFu, pk.q, n, pk.r, max_contrib,
-                   max_contrib ? pk.c.get() : nullptr, c->stream);
+    gs_launch_pick(frame_lists(c), pk.q, n, pk.r, max_contrib, max_contrib ? pk.c.get() : nullptr, c->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(results, pk.r, (size_t)n * sizeof(gs_pick_result), hipMemcpyDeviceToHost, c->stream));
     if (max_contrib) HIP_TRY(hipMemcpyAsync(contrib, pk.c, (size_t)cbytes, hipMemcpyDeviceToHost, c->stream));

@@ -1,7 +1,7 @@
 // gs_runtime.h -- private to the runtime sources (gs_context / gs_frame / gs_readback / gs_state / gs_export / gs_xform / gs_coverage / gs_ply / gs_stages .hip):
 //   the error channel (fail, HIP_TRY);
 //   the owners of HIP resources (Owned: DevBuf, PinnedBuf, Event, Stream, File) and Scratch, a device buffer that grows on demand;
-//   the context (gs_ctx, FrameNotes, GraphKey);
+//   the context (gs_ctx, GsOptions, FrameNotes, GraphKey), the lists of its last frame (frame_lists) and sums over its ring (over_ring);
 //   what the calls on the resident splats share: the prologue of a call that drains the ring (Plane, resident_check,
 //   resident_drain, resident_begin), the last frame waited for (last_frame), the staging of a canvas mask (stage_mask), the
 //   coverage planes (cover_planes) and the splat edits' selection (edit_select).
@@ -87,6 +87,19 @@ struct GraphKey {
     bool operator==(const GraphKey& o) const { return index == o.index && tight == o.tight && ext == o.ext && alpha == o.alpha && depth == o.depth; }
 };
 
+// What gs_set_option sets and every member of the ring must share: set_option_one writes nowhere else, and a new member takes
+// the record whole (add_shadow) -- an option cannot reach the one and miss the other.
+struct GsOptions {
+    int emit_order = 2;                 // GS_OPT_EMIT_ORDER: 0 depth-bucket order, 1 gaussian-index order (reference), 2 auto
+    uint32_t debug_view = 0;            // GS_OPT_DEBUG_VIEW
+    bool tile_cull = true;              // GS_OPT_TILE_CULL: tight (opacity-aware) binning in gs_render / gs_render_to
+    uint32_t tight_nb = 0;              // GS_OPT_PROJ_CHUNKS: cull chunks per workgroup of the tight projection (0 = automatic)
+    uint32_t blend_ablation = 0;        // profiling only (GS_OPT_BLEND_ABLATION)
+    uint32_t select_tint = 0x80FFFF00u; // GS_OPT_SELECT_TINT (GS_FLAG_SPLAT_STATE): a<<24 | r<<16 | g<<8 | b
+    uint32_t grid_persist = 0;          // GS_OPT_PERSISTENT_GRID: workgroups of the persistent (ticket-loop) kernels; gs_create: 4 per CU
+    bool frame_graph = false;           // GS_OPT_FRAME_GRAPH: replay the captured frame
+};
+
 #define GS_EV_RING 256
 struct gs_ctx {
     ~gs_ctx();
@@ -98,15 +111,7 @@ struct gs_ctx {
     uint32_t tile_passes = 0, tile_bits = 0;  // digits of key/1000 (depth-ordered pipeline)
     bool tile16 = false;                      // every tile id fits 16 bits: the depth-ordered instance sort moves u16 sort words
     bool tight_ok = false;                    // the canvas has at most 255 tile rows and columns (8-bit digits of the row pipeline)
-    uint32_t grid_persist = 0;                // workgroups of the persistent (ticket-loop) kernels
-    // options
-    int emit_order = 2;                       // GS_OPT_EMIT_ORDER: 0 depth-bucket order, 1 gaussian-index order (reference), 2 auto
-    bool index_order = true;                  // what the frame being enqueued uses
-    uint32_t debug_view = 0;                  // GS_OPT_DEBUG_VIEW
-    bool tile_cull = true;                    // GS_OPT_TILE_CULL: tight (opacity-aware) binning in gs_render / gs_render_to
-    uint32_t tight_nb = 0;                    // GS_OPT_PROJ_CHUNKS: cull chunks per workgroup of the tight projection (0 = automatic)
-    uint32_t blend_ablation = 0;              // profiling only (GS_OPT_BLEND_ABLATION)
-    uint32_t select_tint = 0x80FFFF00u;       // GS_OPT_SELECT_TINT (GS_FLAG_SPLAT_STATE): a<<24 | r<<16 | g<<8 | b
+    GsOptions opt;
     DevBuf<uint32_t> blend_prof;              // profiling only (ablation bit 16): 4 words per blend walker
     uint32_t blend_prof_blocks = 0;
     // Frames in flight (GS_OPT_FRAMES_IN_FLIGHT): when gs_render is called while this context's previous frame is still on the
@@ -139,6 +144,7 @@ struct gs_ctx {
     // (key,value) arrays and what grows with them (alloc_kv)
     uint64_t capacity = 0;
     DevBuf<uint32_t> keysA, valsA, keysB, valsB;
+    GsSort sort_index{}, sort_tile{}; // the instance sort of the two reference pipelines over these arrays: full key / tile id only
     DevBuf<uint32_t> keysU, valsU;  // debug copies of the unsorted arrays, allocated by the first gs_render_debug
     DevBuf<uint32_t> keysG;         // full keys rebuilt on demand from a frame that holds u16 tile ids or none (GS_BUF_KEYS)
     bool keysG_valid = false;
@@ -186,7 +192,7 @@ struct gs_ctx {
     // frame graph (GS_OPT_FRAME_GRAPH): the frame's launches captured once, replayed with hipGraphLaunch; only the projection's
     // uniforms change from frame to frame (kernel-node parameter update)
     struct {
-        bool use = false, valid = false;
+        bool valid = false;
         hipGraph_t graph = nullptr; // destroyed by drop_graph, before the buffers the capture points into
         hipGraphExec_t exec = nullptr;
         hipGraphNode_t pre_node = nullptr;
@@ -210,6 +216,16 @@ void drop_shadows(gs_ctx* c);
 // gs_frame.hip
 void drop_graph(gs_ctx* c);
 int32_t wait_one(gs_ctx* c);
+// The lists of the last frame `c` enqueued, as the blend of that frame and the queries on it read them.  The one place that
+// knows that a tight frame's values carry the sub-block mask above the gaussian id.
+GsLists frame_lists(const gs_ctx* c);
+// The sum -- or the maximum -- of get(member) over the ring {root, its shadows}.
+template <class Get>
+uint64_t over_ring(const gs_ctx* root, Get get, bool maximum = false) {
+    uint64_t v = get(root);
+    for (const gs_ctx* s : root->shadows) v = maximum ? std::max<uint64_t>(v, get(s)) : v + get(s);
+    return v;
+}
 // gs_state.hip: the prologue of a call on the resident splats that drains the ring.  resident_check holds the refusals that cost
 // nothing, in this order: null context, a filter that does not fit the state byte (Plane::filtered), a context without
 // GS_FLAG_SPLAT_STATE where the call needs the plane, no scene.  resident_drain is gs_wait (an error of the wait is the call's

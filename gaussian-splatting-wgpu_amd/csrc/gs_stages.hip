@@ -28,15 +28,14 @@ GS_EXPORT int32_t gs_sort_pairs_u32(int32_t device, uint32_t* keys, uint32_t* va
     GsControl* ctl = (GsControl*)ctl_mem.get(); // view into ctl_mem; the sort's status words follow it
     const uint32_t n32 = (uint32_t)n;
     HIP_TRY(hipMemcpy(&ctl->num_intersections, &n32, 4, hipMemcpyHostToDevice));
-    uint32_t *ok = nullptr, *ov = nullptr; // views: the sorted result is in kA/vA or kB/vB
-    gs_launch_sort(kA, vA, kB, vB, ctl, ctl->sort_ticket, &ctl->hist[0][0], &ctl->num_intersections, n32, passes, 8, 0,
-                   (uint32_t*)((char*)ctl_mem.get() + ctl_sz), (uint32_t)prop.multiProcessorCount * 4, false, nullptr, nullptr, nullptr, &ok, &ov);
+    const GsSort plan{{kA, vA}, {kB, vB}, passes, 8, 0, false, false}; // 8-bit digits of the key itself, counted by the sort
+    const GsSortPair sorted = gs_launch_sort(plan, ctl, (uint32_t*)((char*)ctl_mem.get() + ctl_sz), n32, (uint32_t)prop.multiProcessorCount * 4, nullptr);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     uint32_t fault = 0;
     HIP_TRY(hipMemcpy(&fault, &ctl->fault, 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(keys, ok, kb, hipMemcpyDeviceToHost));
-    if (values) HIP_TRY(hipMemcpy(values, ov, kb, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(keys, sorted.keys, kb, hipMemcpyDeviceToHost));
+    if (values) HIP_TRY(hipMemcpy(values, sorted.vals, kb, hipMemcpyDeviceToHost));
     if (fault) return fail(GS_ERR_DEVICE_FAULT, "gs_sort_pairs_u32: look-back spin bound exceeded");
     return GS_OK;
 }

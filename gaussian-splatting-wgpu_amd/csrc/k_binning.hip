@@ -449,11 +449,12 @@ void gs_launch_ranges16(const uint16_t* tiles, const GsControl* ctl, uint32_t ca
                         uint32_t* sticky, GsReport* rep, hipStream_t st) {
     hipLaunchKernelGGL(gs_ranges16_kernel, dim3(grid), dim3(256), 0, st, tiles, ctl, capacity, T, ranges, sticky, rep);
 }
-void gs_launch_rebuild_keys(const uint16_t* tiles, const uint32_t* vals, const uint32_t* counts, uint32_t count, uint32_t n, uint32_t id_mask,
-                            uint32_t* keys, hipStream_t st) {
+void gs_launch_rebuild_keys(const uint16_t* tiles, const uint32_t* vals, const uint32_t* counts, uint32_t count, uint32_t n, uint32_t* keys,
+                            hipStream_t st) {
     if (!count) return;
     const uint32_t blocks = (count + 255u) / 256u;
-    hipLaunchKernelGGL(gs_rebuild_keys_kernel, dim3(blocks < 4096u ? blocks : 4096u), dim3(256), 0, st, tiles, vals, counts, count, n, id_mask, keys);
+    // (id_mask all ones: only frames of the reference binning hold u16 tile ids, and their values are plain gaussian ids)
+    hipLaunchKernelGGL(gs_rebuild_keys_kernel, dim3(blocks < 4096u ? blocks : 4096u), dim3(256), 0, st, tiles, vals, counts, count, n, 0xFFFFFFFFu, keys);
 }
 // The per-frame zeroing of the control block and status words, as a kernel of our own (16-byte stores; `bytes` a multiple of 16):
 // a hipMemsetAsync captured into the frame graph came back as a frame with a garbage control block after other work on the
@@ -480,11 +481,12 @@ void gs_launch_emit_balanced(const void* gdata, const void* grec, const uint32_t
     hipLaunchKernelGGL(gs_emit_balanced_kernel, dim3(grid), dim3(256), 0, st, (const uint4*)gdata, (const uint4*)grec, chunk_table, f, keys,
                        values, ctl, hist_bits, hist_passes, keys16 ? 1u : 0u);
 }
-void gs_launch_emit(const void* gdata, const uint32_t* counts, const uint32_t* offsets, const uint32_t* perm, const uint32_t* n_dev,
-                    const GsFrame& f, uint32_t* keys, uint32_t* values, GsControl* ctl, hipStream_t st) {
+void gs_launch_emit(const void* gdata, const uint32_t* counts, const uint32_t* offsets, const GsFrame& f, uint32_t* keys, uint32_t* values,
+                    GsControl* ctl, hipStream_t st) {
     const uint32_t blocks = (f.n + 255) / 256;
     if (!blocks) return;
-    hipLaunchKernelGGL(gs_emit_kernel, dim3(blocks), dim3(256), 0, st, (const uint4*)gdata, counts, offsets, perm, n_dev, f, keys, values, ctl);
+    const uint32_t* const none = nullptr; // perm / n_dev: every gaussian, in index order (the depth order has its own kernel, gs_emit_balanced_kernel)
+    hipLaunchKernelGGL(gs_emit_kernel, dim3(blocks), dim3(256), 0, st, (const uint4*)gdata, counts, offsets, none, none, f, keys, values, ctl);
 }
 void gs_launch_ranges(const uint32_t* keys, const GsControl* ctl, uint32_t capacity, uint32_t T, uint32_t* ranges, uint32_t grid,
                       uint32_t* sticky, GsReport* rep, hipStream_t st) {

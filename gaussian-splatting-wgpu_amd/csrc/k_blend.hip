@@ -23,6 +23,7 @@
 // Bound: f32 VALU + transcendental issue (about 22 VALU slots per pixel x entry), not HBM:
 // algorithmic bytes are 40 B per staged entry + 4 B per pixel.
 #include "gs_device.h"
+#include "gs_kernels.h"
 #include "gs_tight.h"
 #include <type_traits>
 
@@ -753,16 +754,17 @@ static void launch_quad_t(bool exact, bool masked, bool aux, GsAuxPlanes ap, uin
 // Returns -1 for an unsupported tile size, -2 for aux planes requested without both of them (nothing is launched), 4 when the
 // quadrant kernel ran (gs_stats.num_processed is then the sum of tile_depth[], the per-tile maximum over its four independent
 // walkers), 1 otherwise (ctl->num_processed).  aux: run the AUX instantiation, which writes alpha / depth (f32[H][slab_w] each).
-int gs_launch_blend(const void* gdata, const uint32_t* values, const uint32_t* ranges, const GsFrame& f, uint32_t* rgba8, float* rgbf,
-                    bool aux, float* alpha, float* depth, GsControl* ctl, uint32_t* tile_depth, bool exact, uint32_t ablation, bool masked,
-                    hipStream_t st, uint32_t* prof, uint32_t* prof_blocks) {
+int gs_launch_blend(const GsLists& L, uint32_t* rgba8, float* rgbf, bool aux, float* alpha, float* depth, GsControl* ctl, uint32_t* tile_depth,
+                    bool exact, uint32_t ablation, hipStream_t st, uint32_t* prof, uint32_t* prof_blocks) {
     if (aux && (!alpha || !depth)) return -2; // an AUX kernel only ever sees both planes
     const GsAuxPlanes ap{alpha, depth};
     uint32_t dbg = ablation; // GS_OPT_BLEND_ABLATION: 0 = product path
-    const uint32_t id_mask = masked ? GS_ID_MASK : 0xFFFFFFFFu; // kernels without mask support only strip the bits
+    const GsFrame& f = L.f;
+    const uint32_t *const values = L.values, *const ranges = L.ranges, id_mask = L.id_mask;
+    const bool masked = id_mask != 0xFFFFFFFFu; // the values carry sub-block masks: the MASKED walkers use them, the other kernels only strip the bits
     const dim3 grid(f.col1 - f.col0, f.nty);
     if (grid.x == 0 || grid.y == 0) return 1;
-    const uint4* g = (const uint4*)gdata;
+    const uint4* g = (const uint4*)L.gdata;
     switch (f.tile_size) {
     case 8: launch_blend_t<8>(exact, aux, ap, grid, st, g, values, ranges, f, rgba8, rgbf, ctl, dbg, id_mask); return 1;
     case 16:

@@ -113,8 +113,7 @@ __global__ __launch_bounds__(64) void gs_coverage_kernel(const uint4* __restrict
     }
 }
 
-void gs_launch_coverage(const void* gdata, const uint32_t* values, const uint32_t* ranges, const GsFrame& f, uint32_t id_mask, uint32_t bx0,
-                        uint32_t by0, uint32_t nbx, uint32_t nby, const GsCoverDev& r, void* planes, hipStream_t st) {
+void gs_launch_coverage(const GsLists& L, uint32_t bx0, uint32_t by0, uint32_t nbx, uint32_t nby, const GsCoverDev& r, void* planes, hipStream_t st) {
     if (!nbx || !nby) return;
-    gs_coverage_kernel<<<dim3(nbx, nby), 64, 0, st>>>((const uint4*)gdata, values, ranges, f, id_mask, bx0, by0, r, (uint32_t*)planes);
+    gs_coverage_kernel<<<dim3(nbx, nby), 64, 0, st>>>((const uint4*)L.gdata, L.values, L.ranges, L.f, L.id_mask, bx0, by0, r, (uint32_t*)planes);
 }

@@ -98,9 +98,8 @@ __global__ __launch_bounds__(64) void gs_pick_kernel(const uint4* __restrict__ g
     }
 }
 
-void gs_launch_pick(const void* gdata, const uint32_t* values, const uint32_t* ranges, const GsFrame& f, uint32_t id_mask, const void* d_queries,
-                    uint32_t n, void* d_results, uint32_t max_contrib, void* d_contrib, hipStream_t st) {
+void gs_launch_pick(const GsLists& L, const void* d_queries, uint32_t n, void* d_results, uint32_t max_contrib, void* d_contrib, hipStream_t st) {
     if (!n) return;
-    gs_pick_kernel<<<n, 64, 0, st>>>((const uint4*)gdata, values, ranges, f, id_mask, (const uint2*)d_queries, (uint32_t*)d_results, max_contrib,
-                                     (uint2*)d_contrib);
+    gs_pick_kernel<<<n, 64, 0, st>>>((const uint4*)L.gdata, L.values, L.ranges, L.f, L.id_mask, (const uint2*)d_queries, (uint32_t*)d_results,
+                                     max_contrib, (uint2*)d_contrib);
 }

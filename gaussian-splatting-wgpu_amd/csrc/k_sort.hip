@@ -16,6 +16,7 @@
 //     workgroup as contiguous stores.
 // HBM-bound: histogram 4 B/key once, each sweep 8 B/key read + 8 B/key written.
 #include "gs_binning.h"
+#include "gs_kernels.h"
 
 #define RS_ITEMS 16
 #define RS_WAVES 8 // waves per workgroup: a tile is RS_WAVES * 64 * RS_ITEMS keys
@@ -220,35 +221,28 @@ __global__ __launch_bounds__(RS_THREADS, 4) void gs_sort_sweep_kernel(const KT* 
 
 // ---- host launchers --------------------------------------------------------------------------------
 uint32_t gs_sort_tiles(uint64_t capacity) { return (uint32_t)((capacity + RS_TILE - 1) / RS_TILE); }
-// Sorts `n` (device word *n_ptr) pairs by `passes` digits of `bits` bits of the sort word (the key, or key/1000 when
-// by_tile).  Returns in *out_keys/*out_vals which of the two buffer pairs holds the result.  tickets[passes], hist[passes*256]
-// and status (passes * gs_sort_tiles(capacity) * 256 words) must have been zeroed by the caller.
-// have_hist: the caller already accumulated the digit counts into hist (the scan does it for the gaussian-level sort).
-// aux_table/aux_out (optional): the last sweep also writes aux_out[i] = aux_table[value_i] in sorted order.
-// keys16: the key arrays hold uint16_t sort words (by_tile must be 0 and have_hist true).
-void gs_launch_sort(uint32_t* keysA, uint32_t* valsA, uint32_t* keysB, uint32_t* valsB, GsControl* ctl, uint32_t* tickets, uint32_t* hist,
-                    const uint32_t* n_ptr, uint32_t capacity, uint32_t passes, uint32_t bits, uint32_t by_tile, uint32_t* status,
-                    uint32_t grid, bool have_hist, const uint32_t* aux_table, uint32_t* aux_out, hipStream_t st, uint32_t** out_keys,
-                    uint32_t** out_vals, bool keys16) {
+// Sorts the ctl->num_intersections (at most `capacity`) pairs of s.in by the digit plan of `s` (gs_kernels.h GsSort) and returns
+// which of the two pairs holds the result.  ctl->sort_ticket[passes], ctl->hist[passes][256] and status (passes *
+// gs_sort_tiles(capacity) * 256 words) must have been zeroed by the caller.
+GsSortPair gs_launch_sort(const GsSort& s, GsControl* ctl, uint32_t* status, uint32_t capacity, uint32_t grid, hipStream_t st) {
     SortDigits sd;
-    sd.bits = bits;
-    sd.by_tile = by_tile;
-    if (!have_hist) hipLaunchKernelGGL(gs_sort_hist_kernel, dim3(grid), dim3(256), 0, st, keysA, hist, n_ptr, capacity, passes, sd);
+    sd.bits = s.bits;
+    sd.by_tile = s.by_tile;
+    uint32_t *const tickets = ctl->sort_ticket, *const hist = &ctl->hist[0][0]; // (addresses in device memory: nothing is read here)
+    const uint32_t* const n_ptr = &ctl->num_intersections;
+    if (!s.have_hist) hipLaunchKernelGGL(gs_sort_hist_kernel, dim3(grid), dim3(256), 0, st, s.in.keys, hist, n_ptr, capacity, s.passes, sd);
     const uint64_t per_pass = (uint64_t)gs_sort_tiles(capacity) * 256;
-    uint32_t *ki = keysA, *vi = valsA, *ko = keysB, *vo = valsB;
-    for (uint32_t p = 0; p < passes; ++p) {
-        const bool last = (p + 1 == passes);
-        if (keys16)
-            hipLaunchKernelGGL(gs_sort_sweep_kernel<uint16_t>, dim3(grid), dim3(RS_THREADS), 0, st, (const uint16_t*)ki, vi, (uint16_t*)ko, vo, ctl,
-                               tickets + p, hist + p * 256, n_ptr, capacity, p, sd, status + p * per_pass,
-                               last ? aux_table : (const uint32_t*)nullptr, last ? aux_out : (uint32_t*)nullptr);
+    const uint32_t* const no_table = nullptr; // aux_table / aux_out: no caller orders a second array by the sweep
+    uint32_t* const no_out = nullptr;
+    GsSortPair i = s.in, o = s.alt;
+    for (uint32_t p = 0; p < s.passes; ++p) {
+        if (s.keys16)
+            hipLaunchKernelGGL(gs_sort_sweep_kernel<uint16_t>, dim3(grid), dim3(RS_THREADS), 0, st, (const uint16_t*)i.keys, i.vals, (uint16_t*)o.keys,
+                               o.vals, ctl, tickets + p, hist + p * 256, n_ptr, capacity, p, sd, status + p * per_pass, no_table, no_out);
         else
-            hipLaunchKernelGGL(gs_sort_sweep_kernel<uint32_t>, dim3(grid), dim3(RS_THREADS), 0, st, ki, vi, ko, vo, ctl, tickets + p, hist + p * 256,
-                               n_ptr, capacity, p, sd, status + p * per_pass, last ? aux_table : (const uint32_t*)nullptr,
-                               last ? aux_out : (uint32_t*)nullptr);
-        uint32_t* t = ki; ki = ko; ko = t;
-        t = vi; vi = vo; vo = t;
+            hipLaunchKernelGGL(gs_sort_sweep_kernel<uint32_t>, dim3(grid), dim3(RS_THREADS), 0, st, (const uint32_t*)i.keys, i.vals, o.keys, o.vals, ctl,
+                               tickets + p, hist + p * 256, n_ptr, capacity, p, sd, status + p * per_pass, no_table, no_out);
+        std::swap(i, o);
     }
-    *out_keys = ki;
-    *out_vals = vi;
+    return i;
 }

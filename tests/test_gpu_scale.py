@@ -384,3 +384,51 @@ def test_frames_in_flight_ring(oracle):
     r.render_uniforms(us[5]); r.wait()
     np.testing.assert_array_equal(r.read_rgba8(), want[5])
     r.destroy(); seq.destroy()
+
+
+def test_options_reach_every_ring_member():
+    """gs_set_option and the ring: a member created AFTER an option was set inherits it (phase 1: the options are set on a fresh
+    context, its two shadows open during the bursts), a member that EXISTS when an option is set receives it (phases 2 and 3).
+    Per phase: bursts of 1, 2 and 3 frames without a wait, then three single frames -- consecutive single frames take consecutive
+    slots of the ring, so every one of the three members renders a frame that is read.  Every frame read is, byte for byte, the
+    frame of a one-in-flight context with the same options and camera, and the statistics name the same pipeline.  The four
+    options all show: tile cull and emission order in the statistics (phase 3 returns to the reference's binning so that the
+    index order of phase 2 is seen), the debug view (1: tile borders over the frame, which stays visible) and the tint of the
+    selected splats in the bytes."""
+    from conftest import scene
+    from gsplat import _abi
+    W, H = 200, 120
+    s = scene(3001)
+    SEL = _abi.GS_SPLAT_SELECTED
+    r = make_renderer(s, W, H, 16, flags=_abi.GS_FLAG_SPLAT_STATE)
+    r.set_option(_abi.GS_OPT_FRAMES_IN_FLIGHT, 3)
+    seq = make_renderer(s, W, H, 16, flags=_abi.GS_FLAG_SPLAT_STATE)
+    seq.set_option(_abi.GS_OPT_FRAMES_IN_FLIGHT, 1)
+    u0 = orbit_uniforms(W, H, step=0)
+    seq.render_uniforms(u0); seq.wait()
+    plain = seq.read_rgba8()
+    for x in (r, seq):
+        assert x.select_sphere((0.0, 0.0, 0.0), 1.0) > 0 and x.state_count(SEL, SEL) > 0
+    seq.render_uniforms(u0); seq.wait()
+    assert not np.array_equal(seq.read_rgba8(), plain)  # the selection is on screen: the tint is part of what is compared below
+    phases = [({_abi.GS_OPT_TILE_CULL: 0, _abi.GS_OPT_EMIT_ORDER: 0, _abi.GS_OPT_DEBUG_VIEW: 1, _abi.GS_OPT_SELECT_TINT: 0xC0FF2010}, (0, 1)),
+              ({_abi.GS_OPT_TILE_CULL: 1, _abi.GS_OPT_EMIT_ORDER: 1, _abi.GS_OPT_DEBUG_VIEW: 0, _abi.GS_OPT_SELECT_TINT: 0x6010FF40}, (1, 1)),
+              ({_abi.GS_OPT_TILE_CULL: 0}, (0, 0))]  # (tight_binning, depth_ordered) of the frames that follow
+    step = 0
+    for opts, (tight, depth_ordered) in phases:
+        for key, value in opts.items():
+            r.set_option(key, value)
+            seq.set_option(key, value)
+        for burst in (1, 2, 3, 1, 1, 1):
+            for _ in range(burst):
+                step += 1
+                u = orbit_uniforms(W, H, step=step)
+                r.render_uniforms(u)
+            r.wait()
+            seq.render_uniforms(u); seq.wait()
+            np.testing.assert_array_equal(r.read_rgba8(), seq.read_rgba8())
+            st, sq = r.stats(), seq.stats()
+            assert (sq["tight_binning"], sq["depth_ordered"]) == (tight, depth_ordered)
+            assert (st["tight_binning"], st["depth_ordered"]) == (tight, depth_ordered)
+    assert r.stats()["frames_in_flight"] == 3 and seq.stats()["frames_in_flight"] == 1
+    r.destroy(); seq.destroy()
