@@ -5,11 +5,25 @@ Same constructor shape -- Renderer(canvas, interactiveCamera, device, gaussians,
 ``numGaussians`` and ``gaussiansBuffer`` (the 320-byte records PackedGaussians builds).
 """
 import ctypes
+import functools
+import inspect
 
 import numpy as np
 
 from . import _abi
 from ._abi import GsConfig, GsStats, check
+
+
+def _sized(call, alloc, dst=lambda out: (out.ctypes.data, len(out))):
+    """The C ABI's two-call size protocol.  call(n) reports in n how much there is (bytes or records, as the call counts), alloc(that)
+    makes the destination, call(n, *dst(destination)) -- pointer, capacity and what else the call takes -- fills it; the second
+    call is left out when there is nothing to fill."""
+    n = ctypes.c_uint64()
+    check(call(ctypes.byref(n)))
+    out = alloc(n.value)
+    if n.value:
+        check(call(ctypes.byref(n), *dst(out)))
+    return out
 
 
 class Canvas:
@@ -132,12 +146,9 @@ class Renderer:
         return out
 
     def read_buffer(self, which, dtype=np.uint32):
-        n = ctypes.c_uint64()
-        check(self._L.gs_read_buffer(self._ctx, which, None, 0, ctypes.byref(n)))
-        out = np.empty(n.value // np.dtype(dtype).itemsize, dtype=dtype)
-        if n.value:
-            check(self._L.gs_read_buffer(self._ctx, which, out.ctypes.data, out.nbytes, None))
-        return out
+        return _sized(lambda n, dst=None, size=0: self._L.gs_read_buffer(self._ctx, which, dst, size, n),
+                      lambda nbytes: np.empty(nbytes // np.dtype(dtype).itemsize, dtype=dtype),
+                      lambda out: (out.ctypes.data, out.nbytes))  # (this call counts bytes)
 
     def read_alpha(self):
         """GS_FLAG_AUX_OUTPUTS: the last frame's accumulated opacity A = 1 - T, f32[H, slab_width] (0 where no splat reaches).  The
@@ -213,14 +224,19 @@ class Renderer:
             u = np.ascontiguousarray(uniforms, dtype=np.float32).reshape(40)
             r.uniforms160 = u.ctypes.data
         if mask is not None:
-            m = np.ascontiguousarray(mask, dtype=np.uint8)
-            if m.shape != (self.canvas.height, self.canvas.width):
-                raise ValueError("state_region: the mask must be u8[canvas.height, canvas.width]")
+            m = self._canvas_mask(mask, "state_region")
             r.mask = m.ctypes.data
         r.where_mask, r.where_value = int(where[0]), int(where[1])
         matched = ctypes.c_uint64()
         check(self._L.gs_state_region(self._ctx, ctypes.byref(r), int(op), int(bits), ctypes.byref(matched)))
         return int(matched.value)
+
+    def _canvas_mask(self, mask, who):
+        """The mask as the contiguous u8[canvas.height, canvas.width] the C side reads; the caller holds it until its call returns."""
+        m = np.ascontiguousarray(mask, dtype=np.uint8)
+        if m.shape != (self.canvas.height, self.canvas.width):
+            raise ValueError(who + ": the mask must be u8[canvas.height, canvas.width]")
+        return m
 
     def state_ids(self, ids, op, bits):
         """gs_state_ids: the same for a list of splat indices (what pick / pick_rect return); duplicates behave as the sequential
@@ -239,12 +255,7 @@ class Renderer:
 
     def read_state(self):
         """The state plane as it is now, u8[N] (GS_BUF_SPLAT_STATE): a snapshot for undo, or a filter over the host's own records."""
-        n = ctypes.c_uint64()
-        check(self._L.gs_read_buffer(self._ctx, _abi.GS_BUF_SPLAT_STATE, None, 0, ctypes.byref(n)))
-        out = np.empty(n.value, dtype=np.uint8)
-        if n.value:
-            check(self._L.gs_read_buffer(self._ctx, _abi.GS_BUF_SPLAT_STATE, out.ctypes.data, out.nbytes, None))
-        return out
+        return self.read_buffer(_abi.GS_BUF_SPLAT_STATE, np.uint8)
 
     def write_state(self, arr):
         """gs_state_write: replaces the whole plane (u8[N]): undo / restore."""
@@ -286,9 +297,7 @@ class Renderer:
             r.struct_size = ctypes.sizeof(_abi.GsCoverRegion)
             r.x0, r.y0, r.x1, r.y1 = (int(v) for v in rect) if rect is not None else (0, 0, self.canvas.width, self.canvas.height)
             if mask is not None:
-                m = np.ascontiguousarray(mask, dtype=np.uint8)
-                if m.shape != (self.canvas.height, self.canvas.width):
-                    raise ValueError("accumulate_coverage: the mask must be u8[canvas.height, canvas.width]")
+                m = self._canvas_mask(mask, "accumulate_coverage")
                 r.mask = m.ctypes.data
         pixels = ctypes.c_uint64()
         check(self._L.gs_coverage_accumulate(self._ctx, ctypes.byref(r) if r is not None else None, ctypes.byref(pixels)))
@@ -301,12 +310,8 @@ class Renderer:
     def read_coverage(self):
         """gs_coverage_read: the planes as a structured array (_abi.COVERAGE_DTYPE: sum_q, hits, max_weight), one record per
         resident splat; all zero before any accumulate and after an upload or a compaction."""
-        n = ctypes.c_uint64()
-        check(self._L.gs_coverage_read(self._ctx, None, 0, ctypes.byref(n)))
-        out = np.zeros(n.value, dtype=_abi.COVERAGE_DTYPE)
-        if n.value:
-            check(self._L.gs_coverage_read(self._ctx, out.ctypes.data, out.size, ctypes.byref(n)))
-        return out
+        return _sized(lambda n, dst=None, cap=0: self._L.gs_coverage_read(self._ctx, dst, cap, n),
+                      lambda count: np.zeros(count, dtype=_abi.COVERAGE_DTYPE))
 
     def state_coverage(self, op, bits, min_hits=1, min_weight=0.0, covered=True, where=(0, 0)):
         """gs_state_coverage: applies `op` (GS_STATE_*) with `bits` to the splats whose byte passes (s & where[0]) == where[1]
@@ -331,12 +336,9 @@ class Renderer:
     # -- splat edits: list, export, compact and save resident splats by state ------------------------------
     def list_state(self, mask, value):
         """gs_state_list: the indices of the splats with (s & mask) == value, ascending, uint32[n]."""
-        n = ctypes.c_uint64()
-        check(self._L.gs_state_list(self._ctx, int(mask), int(value), None, 0, ctypes.byref(n)))
-        ids = np.empty(n.value, dtype=np.uint32)
-        if n.value:
-            check(self._L.gs_state_list(self._ctx, int(mask), int(value), ids.ctypes.data, ids.size, ctypes.byref(n)))
-        return ids
+        mask, value = int(mask), int(value)
+        return _sized(lambda n, dst=None, cap=0: self._L.gs_state_list(self._ctx, mask, value, dst, cap, n),
+                      lambda count: np.empty(count, dtype=np.uint32))
 
     def export_splats(self, mask=0, value=0, with_ids=False, device=False):
         """gs_export_splats: the resident splats with (s & mask) == value as float32[n, 80] records (what PackedGaussians and the
@@ -344,24 +346,25 @@ class Renderer:
         GS_FLAG_SPLAT_STATE.  with_ids: returns (records, uint32[n] old indices).  device=True: torch tensors on this device
         (gs_export_splats_device), never a host copy."""
         mask, value = int(mask), int(value)
-        n = ctypes.c_uint64()
-        check(self._L.gs_export_splats(self._ctx, mask, value, None, 0, ctypes.byref(n), None))
-        m = n.value
         if device:
             import torch
             dev = torch.device("cuda", self.device)
-            rec = torch.empty((m, 80), dtype=torch.float32, device=dev)
-            ids = torch.empty((m,), dtype=torch.int32, device=dev) if with_ids else None
-            torch.cuda.current_stream(dev).synchronize()  # the allocator may hand out memory another stream still uses
-            if m:
-                check(self._L.gs_export_splats_device(self._ctx, mask, value, rec.data_ptr(), m, ctypes.byref(n),
-                                                      ids.data_ptr() if with_ids else None))
-            return (rec, ids) if with_ids else rec
-        rec = np.empty((m, 80), dtype=np.float32)
-        ids = np.empty(m, dtype=np.uint32) if with_ids else None
-        if m:
-            check(self._L.gs_export_splats(self._ctx, mask, value, rec.ctypes.data, m, ctypes.byref(n),
-                                           ids.ctypes.data if with_ids else None))
+            fill, ptr = self._L.gs_export_splats_device, torch.Tensor.data_ptr
+
+            def alloc(m):
+                rec = torch.empty((m, 80), dtype=torch.float32, device=dev)
+                ids = torch.empty((m,), dtype=torch.int32, device=dev) if with_ids else None
+                torch.cuda.current_stream(dev).synchronize()  # the allocator may hand out memory another stream still uses
+                return rec, ids
+        else:
+            fill, ptr = self._L.gs_export_splats, lambda a: a.ctypes.data
+
+            def alloc(m):
+                return np.empty((m, 80), dtype=np.float32), np.empty(m, dtype=np.uint32) if with_ids else None
+
+        def call(n, dst=None, cap=0, dst_ids=None):  # (the size is asked of gs_export_splats on either path)
+            return (fill if dst else self._L.gs_export_splats)(self._ctx, mask, value, dst, cap, n, dst_ids)
+        rec, ids = _sized(call, alloc, lambda out: (ptr(out[0]), len(out[0]), ptr(out[1]) if with_ids else None))
         return (rec, ids) if with_ids else rec
 
     def compact(self, mask, value):
@@ -416,10 +419,7 @@ class Renderer:
     def stats(self):
         s = GsStats()
         check(self._L.gs_get_stats(self._ctx, ctypes.byref(s)))
-        d = {k: getattr(s, k) for k in ("num_gaussians", "num_visible", "num_intersections", "num_processed", "num_tiles",
-                                        "sort_passes", "frames", "frame_us", "frame_us_mean", "frames_timed", "num_evaluated", "depth_ordered",
-                                        "capacity", "max_intersections_seen", "truncated_frames", "tight_binning", "frames_in_flight", "graph_frames",
-                                        "num_row_items", "num_row_slots", "row_capacity")}
+        d = {k: getattr(s, k) for k, t in GsStats._fields_ if not issubclass(t, ctypes.Array)}  # (the two arrays go in by stage name)
         d["stage_us"] = {n: s.stage_us[i] for i, n in enumerate(_abi.GS_STAGE_NAMES)}
         d["stage_us_mean"] = {n: s.stage_us_mean[i] for i, n in enumerate(_abi.GS_STAGE_NAMES)}
         self.numIntersections = d["num_intersections"]
@@ -484,22 +484,6 @@ class PipelinedRenderer:
                 r.wait()
                 self._busy[k] = False
 
-    def read_rgba8(self, slot):
-        self.wait(slot)
-        return self.renderers[slot].read_rgba8()
-
-    def read_alpha(self, slot):
-        self.wait(slot)
-        return self.renderers[slot].read_alpha()
-
-    def read_depth(self, slot, normalized=False):
-        self.wait(slot)
-        return self.renderers[slot].read_depth(normalized)
-
-    def pick(self, slot, xy, max_contrib=0):
-        self.wait(slot)
-        return self.renderers[slot].pick(xy, max_contrib)
-
     def set_option(self, key, value):
         for r in self.renderers:
             r.set_option(key, value)
@@ -510,82 +494,35 @@ class PipelinedRenderer:
         self.wait()
         return self.renderers[0]
 
-    def state_region(self, *a, **kw):
-        return self._state_owner().state_region(*a, **kw)
+    # coverage: the planes are the owner's, and so is the frame they describe (slot 0's last one).  Splat edits and transforms go to
+    # the owner too; after a compaction the other members borrow the new scene, as the constructor made them (compact, below)
+    _OWNER_CALLS = ("state_region", "state_ids", "state_count", "read_state", "write_state", "select_rect", "select_mask", "select_sphere",
+                    "select_box", "clear_selection", "hide_selected", "unhide_all",
+                    "accumulate_coverage", "reset_coverage", "read_coverage", "state_coverage", "select_visible", "hide_unseen",
+                    "list_state", "export_splats", "save_ply", "transform", "translate_selected", "rotate_selected", "scale_selected")
+    # per-frame outputs: `slot` (what render_uniforms returned) comes first, the slot's frame is waited for, its renderer answers
+    _SLOT_CALLS = ("read_rgba8", "read_alpha", "read_depth", "pick")
 
-    def state_ids(self, ids, op, bits):
-        return self._state_owner().state_ids(ids, op, bits)
+    def _owner_call(name):
+        @functools.wraps(getattr(Renderer, name))
+        def call(self, *a, **kw):
+            return getattr(self._state_owner(), name)(*a, **kw)
+        return call
 
-    def state_count(self, mask, value):
-        return self._state_owner().state_count(mask, value)
+    def _slot_call(name):
+        @functools.wraps(getattr(Renderer, name))
+        def call(self, slot, *a, **kw):
+            self.wait(slot)
+            return getattr(self.renderers[slot], name)(*a, **kw)
+        own, *rest = inspect.signature(call).parameters.values()  # (Renderer's parameters: `slot` goes in behind self)
+        call.__signature__ = inspect.Signature([own, inspect.Parameter("slot", inspect.Parameter.POSITIONAL_OR_KEYWORD)] + rest)
+        return call
 
-    def read_state(self):
-        return self._state_owner().read_state()
-
-    def write_state(self, arr):
-        return self._state_owner().write_state(arr)
-
-    def select_rect(self, *a, **kw):
-        return self._state_owner().select_rect(*a, **kw)
-
-    def select_mask(self, *a, **kw):
-        return self._state_owner().select_mask(*a, **kw)
-
-    def select_sphere(self, *a, **kw):
-        return self._state_owner().select_sphere(*a, **kw)
-
-    def select_box(self, *a, **kw):
-        return self._state_owner().select_box(*a, **kw)
-
-    def clear_selection(self):
-        return self._state_owner().clear_selection()
-
-    def hide_selected(self):
-        return self._state_owner().hide_selected()
-
-    def unhide_all(self):
-        return self._state_owner().unhide_all()
-
-    # coverage: the planes are the owner's, and so is the frame they describe (slot 0's last one)
-    def accumulate_coverage(self, *a, **kw):
-        return self._state_owner().accumulate_coverage(*a, **kw)
-
-    def reset_coverage(self):
-        return self._state_owner().reset_coverage()
-
-    def read_coverage(self):
-        return self._state_owner().read_coverage()
-
-    def state_coverage(self, *a, **kw):
-        return self._state_owner().state_coverage(*a, **kw)
-
-    def select_visible(self, *a, **kw):
-        return self._state_owner().select_visible(*a, **kw)
-
-    def hide_unseen(self, *a, **kw):
-        return self._state_owner().hide_unseen(*a, **kw)
-
-    # splat edits go to the owner too; after a compaction the other members borrow the new scene, as the constructor made them
-    def list_state(self, mask, value):
-        return self._state_owner().list_state(mask, value)
-
-    def export_splats(self, *a, **kw):
-        return self._state_owner().export_splats(*a, **kw)
-
-    def save_ply(self, *a, **kw):
-        return self._state_owner().save_ply(*a, **kw)
-
-    def transform(self, *a, **kw):
-        return self._state_owner().transform(*a, **kw)
-
-    def translate_selected(self, t):
-        return self._state_owner().translate_selected(t)
-
-    def rotate_selected(self, rot, pivot=None):
-        return self._state_owner().rotate_selected(rot, pivot)
-
-    def scale_selected(self, s, pivot=None):
-        return self._state_owner().scale_selected(s, pivot)
+    for _name in _OWNER_CALLS:  # (plain functions while the class body runs; the methods they make are ordinary class attributes)
+        locals()[_name] = _owner_call(_name)
+    for _name in _SLOT_CALLS:
+        locals()[_name] = _slot_call(_name)
+    del _name, _owner_call, _slot_call
 
     def compact(self, mask, value):
         first = self._state_owner()

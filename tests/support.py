@@ -1,0 +1,500 @@
+"""What the test modules share: paths, the issue scenes with their oracle frames (one cache), the renderer factory, and the
+blocks every feature's tests repeat (run a Node check script, compile a layout probe against the header, read the hosts'
+sources).  A plain module like gpu_checks and the *_restate modules; a helper only one test file uses stays in that file.
+"""
+import collections
+import ctypes
+import hashlib
+import json
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import scene
+import export_restate as er
+import state_restate as sr
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+HEADER = os.path.join(ROOT, "include", "gsplat", "gs_abi.h")
+JS_DIR = os.path.join(ROOT, "gaussian-splatting-wgpu_amd", "js")
+NAPI_SRC = os.path.join(ROOT, "gaussian-splatting-wgpu_amd", "csrc", "napi", "gs_napi.c")
+F = np.float32
+NODE = shutil.which("node")
+
+_CACHE = {}
+
+
+def cached(key, make):
+    """make() once per key and session.  The key names everything the value depends on."""
+    if key not in _CACHE:
+        _CACHE[key] = make()
+    return _CACHE[key]
+
+
+def oracle_frame(oracle, name, s, u, W, H, ts, **kw):
+    """oracle.render of the scene called `name` (the name stands for s and u), once per (scene, canvas, tile size, arguments).  A
+    frame rendered with other arguments is never handed out; an argument left out and one given as None / False are the same call
+    (gs_oracle.render's defaults)."""
+    args = tuple(sorted((k, v) for k, v in kw.items() if v is not None and v is not False))
+    return cached(("render", name, W, H, ts, args), lambda: oracle.render(s, u, W, H, ts, **kw))
+
+
+# ---- the splat-state scenes: config A and the ragged golden, their regions, planes and constructed frames ---------------------------
+FRAME_CASES = [("cfgA", 8), ("cfgA", 16), ("cfgA", 32), ("ragged", 8)]  # (scene, tile size)
+
+
+def state_scene(name):
+    """(splats, uniforms, W, H) of "cfgA" or "ragged"."""
+    def make():
+        if name == "cfgA":
+            from gpu_checks import orbit_uniforms
+            return scene(10000), orbit_uniforms(256, 256), 256, 256
+        from gsplat import synth
+        z = np.load(os.path.join(GOLDEN, "ragged_3001_200x120_t8.npz"))
+        n, W, H, _, _ = (int(v) for v in z["params"])
+        return synth.bicycle_like(n), np.array(z["uniforms"], F), W, H
+    return cached(("state_scene", name), make)
+
+
+def in_region(name, region):
+    """Membership of the scene's splats in one of state_restate.issue_regions."""
+    def make():
+        s, u, W, H = state_scene(name)
+        kind, kw = sr.issue_regions(W, H, u)[region]
+        return sr.member(kind, s, W, H, **kw)
+    return cached(("inside", name, region), make)
+
+
+def hidden_plane(name, which):
+    s, _, _, _ = state_scene(name)
+    n = s.shape[0]
+    if which == "every_third":
+        h = np.arange(n) % 3 == 1
+    elif which == "centre_half_rect":
+        h = in_region(name, "centre_half_rect")
+    else:
+        h = np.ones(n, bool)
+    return np.where(h, sr.HIDDEN, 0).astype(np.uint8)
+
+
+def state_ref(oracle, name, ts, key, state, tint=sr.TINT_DEFAULT, cols=None):
+    """The constructed reference frame of a state plane (`key` names the plane), computed once per (scene, tile size, plane, tint,
+    slab) and shared."""
+    def make():
+        s, u, W, H = state_scene(name)
+        return sr.state_frame(oracle, s, u, W, H, ts, state, tint, cols, want_illcond=True)
+    return cached(("state_ref", name, ts, key, tint, cols), make)
+
+
+# ---- the margin scenes of the blend's parking culls (test_blend_culls.py), built in pixel space ------------------------------------
+def pixel_uniforms(W, H):
+    u = np.zeros(40, dtype=np.float32)
+    u[0] = u[5] = u[10] = u[15] = 1.0      # view = I (column-major)
+    u[16] = u[21] = u[26] = u[31] = 1.0    # proj = I: ndc = pos
+    u[35] = u[36] = 0.5                    # tan_fov
+    u[37], u[38] = W / 2.0, H / 2.0        # focal: one world unit at depth 1 = W / 2 pixels
+    u[39] = 1.0
+    return u
+
+
+def make_splats(W, H, px, py, sig_long, sig_short, theta, logit, color=None, rng=None):
+    """Records with centres (px, py) in pixels, pixel-space standard deviations (before the projection's +0.3 px^2) along the
+    axes of a rotation by theta about the view axis, opacity logits.  Depth 1 for all: the list order is the record order."""
+    n = np.size(px)
+    s = np.zeros((n, 80), dtype=np.float32)
+    s[:, 0] = 2.0 * np.asarray(px, np.float64) / W - 1.0
+    s[:, 1] = 2.0 * np.asarray(py, np.float64) / H - 1.0
+    s[:, 2] = 1.0
+    f = W / 2.0  # = H / 2 * (W / H): both focal lengths map one unit to W / 2 resp. H / 2 pixels
+    s[:, 4] = np.log(np.maximum(np.asarray(sig_long, np.float64), 1e-30) / f)
+    s[:, 5] = np.log(np.maximum(np.asarray(sig_short, np.float64), 1e-30) / (H / 2.0))
+    s[:, 6] = -30.0  # flat along the view axis: the projected covariance does not depend on the centre
+    th = np.asarray(theta, np.float64)
+    s[:, 8] = np.cos(th / 2.0)
+    s[:, 11] = np.sin(th / 2.0)
+    s[:, 12] = logit
+    if color is None:
+        color = (rng.uniform(-1.5, 1.5, (n, 3)) if rng is not None else np.zeros((n, 3)))
+    s[:, 16:19] = color
+    return s
+
+
+def opacity_logits(oracle, targets):
+    """Logits whose f32 opacity in the oracle's gdata (word 11) is the largest one <= target, by bisection (all at once)."""
+    targets = np.asarray(targets, np.float64)
+    lo = np.full(targets.shape, -20.0)
+    hi = np.full(targets.shape, 20.0)
+    W = H = 64
+    u = pixel_uniforms(W, H)
+    for _ in range(60):
+        mid = 0.5 * (lo + hi)
+        s = make_splats(W, H, np.full(mid.size, 32.0), np.full(mid.size, 32.0), 4.0, 4.0, 0.0, mid.astype(np.float32))
+        op = oracle.preprocess(s, u, W, H, 8)[0][:, 11].view(np.float32).astype(np.float64)
+        ok = op <= targets
+        lo = np.where(ok, mid, lo)
+        hi = np.where(ok, hi, mid)
+    return lo.astype(np.float32)
+
+
+def gdata_f32(gdata):
+    return gdata.view(np.float32).reshape(-1, 16)
+
+
+def box_qmin_f64(cx, cy, cz, dxlo, dxhi, dylo, dyhi):
+    """min over [dxlo,dxhi] x [dylo,dyhi] of 0.5 (cx dx^2 + cz dy^2) + cy dx dy (positive-definite conics), in f64."""
+    q = lambda dx, dy: 0.5 * (cx * dx * dx + cz * dy * dy) + cy * dx * dy
+    inside = (dxlo <= 0) & (dxhi >= 0) & (dylo <= 0) & (dyhi >= 0)
+    best = np.full(np.shape(cx), np.inf)
+    with np.errstate(all="ignore"):
+        for X in (dxlo, dxhi):  # vertical edges: dy = argmin clamped
+            dy = np.clip(-cy * X / cz, dylo, dyhi)
+            best = np.minimum(best, q(X, dy))
+        for Y in (dylo, dyhi):
+            dx = np.clip(-cy * Y / cx, dxlo, dxhi)
+            best = np.minimum(best, q(dx, Y))
+    return np.where(inside, 0.0, best)
+
+
+HUGE = 1.0e5  # pixels of sigma: conic ~ 1e-10, alpha uniform over the canvas to ~1e-6
+
+
+def _front(oracle, W, H, T0):
+    """Two huge, near-uniform splats: T = 1 -> 0.01 -> T0 on every pixel."""
+    ops = np.array([0.99, 1.0 - T0 / 0.01])
+    lg = opacity_logits(oracle, ops)
+    return make_splats(W, H, np.full(2, W / 2.0), np.full(2, H / 2.0), HUGE, HUGE, 0.0, lg, color=[[0.4, -0.2, 0.1], [-0.3, 0.6, 0.2]])
+
+
+def transmittance_edge_scene(oracle, seed=0):
+    """T just above the final threshold on most pixels, spread across pixels (so that Tmax is not most pixels' own T), then a
+    sweep of huge, uniform entries whose T (1 - alpha) puts each block's Tmax pixel at 1e-4 (1 +- delta), and entries at the
+    0.99 clamp.  Returns (splats, uniforms, W, H)."""
+    W, H = 115, 83
+    rng = np.random.Generator(np.random.Philox(key=[4101, seed]))
+    parts = [_front(oracle, W, H, 1.048e-4)]
+    # the spread: moderate splats, peak alpha 0.02 .. 0.044 (T0 (1 - alpha) >= 1e-4 needs alpha <= 0.0458)
+    k = 9
+    lg = opacity_logits(oracle, rng.uniform(0.02, 0.044, k))
+    parts.append(make_splats(W, H, rng.uniform(0, W, k), rng.uniform(0, H, k), rng.uniform(15, 45, k), rng.uniform(15, 45, k),
+                             rng.uniform(0, np.pi, k), lg, rng=rng))
+    # the sweep: threshold tau = 1e-4 / (1 - alpha) from 1.048e-4 down in steps of ~0.05 %, with jitter
+    tau = np.sort(1e-4 * np.exp(rng.uniform(np.log(1.0039), np.log(1.0485), 90)))[::-1]
+    lg = opacity_logits(oracle, 1.0 - 1e-4 / tau)
+    parts.append(make_splats(W, H, np.full(tau.size, W / 2.0), np.full(tau.size, H / 2.0), HUGE, HUGE, 0.0, lg, rng=rng))
+    # ... and the 0.99 clamp: logits >= 4.6 (alpha = 0.99, alo = 0.99 * 0.99), uniform and local
+    k = 6
+    lg = np.array([4.6, 4.7, 6.0, 9.0, 12.0, 30.0], np.float32)
+    parts.append(make_splats(W, H, rng.uniform(0, W, k), rng.uniform(0, H, k), np.where(np.arange(k) < 3, HUGE, 20.0),
+                             np.where(np.arange(k) < 3, HUGE, 6.0), rng.uniform(0, np.pi, k), lg, rng=rng))
+    return np.concatenate(parts), pixel_uniforms(W, H), W, H
+
+
+def _live_patterns(bx0, by0, bw, bh):
+    """Live pixel sets of an 8x8 block whose in-canvas part is bw x bh: one corner, one row, one column, two opposite corners."""
+    xr, yb = bx0 + bw - 1, by0 + bh - 1
+    return [[(bx0, by0)], [(xr, by0)], [(bx0, yb)], [(xr, yb)],
+            [(x, by0) for x in range(bx0, xr + 1)], [(x, yb) for x in range(bx0, xr + 1)],
+            [(bx0, y) for y in range(by0, yb + 1)], [(xr, y) for y in range(by0, yb + 1)],
+            [(bx0, by0), (xr, yb)], [(xr, by0), (bx0, yb)]]
+
+
+def live_box_scene(oracle, seed=0):
+    """Blocks whose pixels are all final but for one corner, one row, one column or two opposite corners (every block of the
+    canvas but a few, the partial ones at the right and bottom edges included), then thin rotated splats centred outside the
+    block whose alpha = 1/255 contour passes just inside or just outside the live box: q_min(box) - ln(255 op) = +-3e-4 .. 1e-2.
+    How: two huge, uniform splats bring every pixel to T0 = 5e-4; a tiny splat with alpha 0.005 at each pixel to be kept live
+    (its neighbours see alpha < 1/255); a huge, uniform finisher with T0 (1 - alpha_f) = 1.002e-4 then leaves every other pixel
+    final (T in [1e-4, 1.0039e-4)) and is rejected by the live ones (0.995 T0 (1 - alpha_f) < 1e-4)."""
+    W, H = 101, 75
+    rng = np.random.Generator(np.random.Philox(key=[4102, seed]))
+    T0 = 5e-4
+    front = _front(oracle, W, H, T0)
+    live, boxes = [], []
+    for by0 in range(0, H, 8):
+        for bx0 in range(0, W, 8):
+            if rng.uniform() < 0.25:
+                continue  # left fully final
+            pats = _live_patterns(bx0, by0, min(8, W - bx0), min(8, H - by0))
+            pix = pats[int(rng.integers(len(pats)))]
+            live += pix
+            xs, ys = [p[0] for p in pix], [p[1] for p in pix]
+            boxes.append((bx0, by0, min(xs), max(xs), min(ys), max(ys)))
+    live = np.array(live, np.float64)
+    nb = live.shape[0]
+    blockers = make_splats(W, H, live[:, 0], live[:, 1], 1e-4, 1e-4, 0.0, opacity_logits(oracle, np.full(nb, 0.005)), rng=rng)
+    fin = make_splats(W, H, [W / 2.0], [H / 2.0], HUGE, HUGE, 0.0, opacity_logits(oracle, [1.0 - 1.002e-4 / T0]), color=[[0.2, 0.2, 0.2]])
+    # the probes: per live box, targets on its corners (outward quadrant) and edges (outward normal, only where the edge is
+    # on the block's boundary, so that the centre lies outside the block)
+    P, U = [], []
+    for bx0, by0, x0, x1, y0, y1 in boxes:
+        for _ in range(7):
+            if rng.uniform() < 0.5:  # a corner of the box
+                sx, sy = rng.choice([-1.0, 1.0]), rng.choice([-1.0, 1.0])
+                phi = rng.uniform(0.15, 1.42)
+                P.append((x0 if sx < 0 else x1, y0 if sy < 0 else y1))
+                U.append((sx * np.cos(phi), sy * np.sin(phi)))
+            else:  # an edge
+                side = int(rng.integers(4))
+                psi = rng.uniform(-0.9, 0.9)
+                if side == 0:
+                    P.append((rng.uniform(x0, x1), y0)); U.append((np.sin(psi), -np.cos(psi)))
+                elif side == 1:
+                    P.append((rng.uniform(x0, x1), y1)); U.append((np.sin(psi), np.cos(psi)))
+                elif side == 2:
+                    P.append((x0, rng.uniform(y0, y1))); U.append((-np.cos(psi), np.sin(psi)))
+                else:
+                    P.append((x1, rng.uniform(y0, y1))); U.append((np.cos(psi), np.sin(psi)))
+    P, U = np.array(P), np.array(U)
+    bidx = np.repeat(np.arange(len(boxes)), 7)
+    bx = np.array(boxes, np.float64)[bidx]
+    n = P.shape[0]
+    theta = np.arctan2(U[:, 1], U[:, 0]) + rng.uniform(-0.5, 0.5, n)  # long axis roughly along the approach, rotated
+    lg = np.where(rng.uniform(size=n) < 0.3, rng.uniform(-5.52, -5.45, n), rng.uniform(-4.0, 3.0, n)).astype(np.float32)
+    sigl = rng.uniform(18.0, 30.0, n)  # eigenvalues of the projected covariance >= 324 : 0.3, a ratio >= 1e3
+    probe = make_splats(W, H, P[:, 0], P[:, 1], sigl, 1e-4, theta, lg, rng=rng)
+    g = gdata_f32(oracle.preprocess(probe, pixel_uniforms(W, H), W, H, 8)[0])
+    cx, cy, cz, op = [g[:, k].astype(np.float64) for k in (4, 5, 6, 11)]
+    target = np.log(255.0 * op) + rng.choice([-1e-2, -3e-3, -1e-3, -3e-4, 3e-4, 1e-3, 3e-3, 1e-2], n)
+    lo, hi = np.zeros(n), np.full(n, 400.0)
+    for _ in range(60):  # the distance along U at which min over the live box of q reaches the target
+        t = 0.5 * (lo + hi)
+        ex, ey = P[:, 0] + t * U[:, 0], P[:, 1] + t * U[:, 1]
+        q = box_qmin_f64(cx, cy, cz, ex - bx[:, 3], ex - bx[:, 2], ey - bx[:, 5], ey - bx[:, 4])
+        lo, hi = np.where(q < target, t, lo), np.where(q < target, hi, t)
+    ex, ey = P[:, 0] + lo * U[:, 0], P[:, 1] + lo * U[:, 1]
+    out = ~((ex > bx[:, 0] - 0.5) & (ex < bx[:, 0] + 7.5) & (ey > bx[:, 1] - 0.5) & (ey < bx[:, 1] + 7.5))
+    ok = out & (ex > -0.04 * W) & (ex < 1.04 * W) & (ey > -0.04 * H) & (ey < 1.04 * H)
+    probe = make_splats(W, H, ex[ok], ey[ok], sigl[ok], 1e-4, theta[ok], lg[ok], rng=rng)
+    return np.concatenate([front, blockers, fin, probe]), pixel_uniforms(W, H), W, H
+
+
+def degenerate_conic_scene(oracle, seed=0):
+    """Extreme scales (the 0.3 px^2 floor .. 1e4 px) and anisotropy: at 45 degrees the projected covariance's determinant
+    cancels in f32 (conics that fail the kernels' positive-definiteness test: such an entry must be kept), axis-aligned the
+    conic has a tiny cx or cz (the rcp in block_qmin is huge); over a half-transparent front layer, so that blocks stay live.
+    (No non-finite records: a NaN colour reaches a FINAL pixel's f32 accumulator as cond * NaN = NaN when the entry is
+    evaluated there, so the culls and the early exit change such pixels by design; test_non_finite_splats covers them.)"""
+    W, H = 77, 61
+    rng = np.random.Generator(np.random.Philox(key=[4103, seed]))
+    parts = [make_splats(W, H, [W / 2.0], [H / 2.0], HUGE, HUGE, 0.0, opacity_logits(oracle, [0.6]), color=[[0.3, 0.1, -0.2]])]
+    k = 160
+    sigl = np.exp(rng.uniform(0.0, np.log(1e4), k))
+    theta = np.where(np.arange(k) % 2 == 0, np.pi / 4 + rng.uniform(-1e-3, 1e-3, k), np.where(np.arange(k) % 4 == 1, 0.0, np.pi / 2))
+    parts.append(make_splats(W, H, rng.uniform(0, W, k), rng.uniform(0, H, k), sigl, 1e-4, theta, rng.uniform(-5.5, 4.0, k).astype(np.float32), rng=rng))
+    k = 24  # both axes at the floor, and both huge at 45 degrees
+    parts.append(make_splats(W, H, rng.uniform(0, W, k), rng.uniform(0, H, k), np.where(np.arange(k) < 12, 1e-4, 1e4),
+                             np.where(np.arange(k) < 12, 1e-4, 5e3), np.pi / 4, rng.uniform(-5.5, 4.0, k).astype(np.float32), rng=rng))
+    return np.concatenate(parts), pixel_uniforms(W, H), W, H
+
+
+SCENES = {"transmittance_edge": transmittance_edge_scene, "live_box": live_box_scene, "degenerate_conic": degenerate_conic_scene}
+SLAB_COLS = {8: (3, 9), 16: (2, 5), 32: (1, 3)}         # one tile-column slab per tile size (px0 != 0, the right edge included)
+
+
+def margin_scene(oracle, name):
+    """(splats, uniforms, W, H) of one of SCENES."""
+    return cached(("margin_scene", name), lambda: SCENES[name](oracle))
+
+
+def margin_ref(oracle, name, ts, cols=None):
+    s, u, W, H = margin_scene(oracle, name)
+    return oracle_frame(oracle, name, s, u, W, H, ts, cols=cols, want_illcond=True)
+
+
+# ---- the cases of gs_pick (test_pick.py), which the coverage tests fold per splat ---------------------------------------------------
+def lattice(W, H, x0, dx, y0, dy):
+    return np.array([(x, y) for y in range(y0, H, dy) for x in range(x0, W, dx)], np.uint32)
+
+
+def weight_ties_scene(oracle):
+    """16 pairs of splats centred on 16 pixels of a 64 x 64 canvas (pixel space, all at depth 1: list order = record order).  At
+    its centre pixel a splat has power = 0, so alpha is its opacity a.  The front splat of pair k gets an opacity a_k in
+    [0.26, 0.33) and the one behind it the f32 opacity b_k with fl(b_k fl(1 - a_k)) == a_k (one exists: b steps by one ulp, the
+    product by less than an ulp of a): the two weights a_k * 1 and b_k * T are then the same f32.  Returns (splats, uniforms, W, H,
+    centres); whether the ties came about is asserted on the restatement, not assumed."""
+    W = H = 64
+    u = pixel_uniforms(W, H)
+
+    def opacities(logits):
+        s = make_splats(W, H, np.full(logits.size, 32.0), np.full(logits.size, 32.0), 4.0, 4.0, 0.0, logits)
+        return oracle.preprocess(s, u, W, H, 8)[0][:, 11].view(np.float32).copy()
+
+    cx = np.array([8 + 16 * i for j in range(4) for i in range(4)], np.float64)
+    cy = np.array([8 + 16 * j for j in range(4) for i in range(4)], np.float64)
+    la = opacity_logits(oracle, np.linspace(0.26, 0.33, 16))
+    a = opacities(la)
+    b = np.zeros_like(a)
+    for k in range(a.size):
+        c = F(a[k] / F(F(1.0) - a[k]))
+        near = [c]
+        for _ in range(4):
+            near = [np.nextafter(near[0], F(0.0), dtype=F)] + near + [np.nextafter(near[-1], F(2.0), dtype=F)]
+        hit = [v for v in near if F(v * F(F(1.0) - a[k])) == a[k]]
+        b[k] = hit[0] if hit else c
+    lb = opacity_logits(oracle, b.astype(np.float64))  # (the largest reachable opacity <= b: b itself for most pairs)
+    s = make_splats(W, H, np.repeat(cx, 2), np.repeat(cy, 2), 1.5, 1.5, 0.0, np.stack([la, lb], axis=1).ravel(),
+                    rng=np.random.default_rng(5))
+    return s, u, W, H, np.stack([cx, cy], axis=1).astype(np.uint32)
+
+
+def pick_case(oracle, name, ts):
+    """(splats, uniforms, W, H, oracle frame, query pixels) of one case: config A, the ragged golden, a margin scene or
+    "weight_ties"."""
+    def make():
+        if name == "cfgA":
+            s, u, W, H = state_scene("cfgA")
+            ref = oracle_frame(oracle, name, s, u, W, H, ts)
+            xy = lattice(W, H, 5, 13, 3, 17)
+        elif name == "ragged":
+            from gsplat import synth
+            z = np.load(os.path.join(GOLDEN, "ragged_3001_200x120_t8.npz"))
+            n, W, H, gts, _ = (int(v) for v in z["params"])
+            assert gts == ts
+            s, u = synth.bicycle_like(n), z["uniforms"]
+            gdata, _ = oracle.preprocess(s, u, W, H, ts)
+            assert hashlib.sha256(np.ascontiguousarray(gdata).tobytes()).hexdigest() == str(z["gdata_sha256"])
+            ref = {"gdata": gdata, "sorted_values": z["sorted_values"], "ranges": z["ranges"]}
+            xy = lattice(W, H, 2, 7, 1, 5)
+        elif name == "weight_ties":
+            s, u, W, H, centres = weight_ties_scene(oracle)
+            ref = oracle_frame(oracle, name, s, u, W, H, ts)
+            xy = np.concatenate([centres, lattice(W, H, 2, 7, 1, 5)])
+        else:
+            s, u, W, H = margin_scene(oracle, name)
+            ref = margin_ref(oracle, name, ts)
+            xy = lattice(W, H, 2, 7, 1, 5)
+        return s, u, W, H, ref, xy
+    return cached(("pick_case", name, ts), make)
+
+
+# ---- records with special floats, and a guarded export (test_export.py, test_transform.py) -----------------------------------------
+def special(rec):
+    """A copy with a handful of floats overwritten by a NaN, a payload NaN, -0.0, +-inf and a denormal (carried floats), and the
+    padding floats of two records filled with junk that must NOT come back."""
+    out = np.array(rec, dtype=F, copy=True).reshape(-1, 80)
+    w = out.view(np.uint32)
+    n = out.shape[0]
+    vals = [0x7FC00000, 0x7FA12345, 0x80000000, 0x7F800000, 0xFF800000, 0x00000001, 0xFFC0BEEF]
+    slots = [0, 5, 9, 12, 16, 18, 17 + 4 * 15, 4, 2, 22]
+    for k, v in enumerate(vals * 2):
+        w[(k * 7) % n, slots[k % len(slots)]] = v
+    w[0, er.PADDING] = 0xA5A5A5A5
+    w[n - 1, er.PADDING] = 0x3F800000
+    return out
+
+
+def special_records(n):
+    """n records of synth.bicycle_like (the ragged fixture's own scene for 3001) with the special floats."""
+    def make():
+        from gsplat import synth
+        return special(synth.bicycle_like(3001) if n == 3001 else scene(10000)[:n])
+    return cached(("special_records", n), make)
+
+
+def guarded(shape, dtype):
+    a = np.empty(shape, dtype)
+    a.view(np.uint8).fill(0xA5)
+    return a
+
+
+def is_fill(a):
+    return bool((np.ascontiguousarray(a).view(np.uint8) == 0xA5).all())
+
+
+def raw_export(r, mask, value, with_ids, device=False):
+    """gs_export_splats[_device] into buffers one record and one id longer than needed, pre-filled with 0xA5; returns (records,
+    ids or None) after checking the guards."""
+    from gsplat import _abi
+    L = _abi.load()
+    n = ctypes.c_uint64()
+    _abi.check(L.gs_export_splats(r._ctx, mask, value, None, 0, ctypes.byref(n), None))
+    m = n.value
+    if device:
+        import torch
+        rec_t = torch.full((m + 1, 80), 0, dtype=torch.float32, device="cuda")
+        rec_t.view(torch.uint8).fill_(0xA5)
+        ids_t = torch.zeros(m + 1, dtype=torch.int32, device="cuda")
+        ids_t.view(torch.uint8).fill_(0xA5)
+        torch.cuda.synchronize()
+        n2 = ctypes.c_uint64()
+        _abi.check(L.gs_export_splats_device(r._ctx, mask, value, rec_t.data_ptr(), m + 1, ctypes.byref(n2), ids_t.data_ptr() if with_ids else None))
+        rec, ids = rec_t.cpu().numpy(), ids_t.cpu().numpy().view(np.uint32)
+    else:
+        rec, ids = guarded((m + 1, 80), F), guarded(m + 1, np.uint32)
+        n2 = ctypes.c_uint64()
+        _abi.check(L.gs_export_splats(r._ctx, mask, value, rec.ctypes.data, m + 1, ctypes.byref(n2), ids.ctypes.data if with_ids else None))
+    assert n2.value == m
+    assert is_fill(rec[m:]) and is_fill(ids[m:])
+    if not with_ids:
+        assert is_fill(ids)
+    return rec[:m], (ids[:m] if with_ids else None)
+
+
+# ---- renderers and frames ----------------------------------------------------------------------------------------------------------
+def mk(s, W, H, ts, exact=False, state=False, aux=False, cols=None, flags=0, **kw):
+    """gpu_checks.make_renderer with the feature flags by name; a test file binds its own defaults with functools.partial."""
+    from gpu_checks import make_renderer
+    from gsplat import _abi
+    fl = (flags | (_abi.GS_FLAG_EXACT_BLEND if exact else 0) | (_abi.GS_FLAG_SPLAT_STATE if state else 0) |
+          (_abi.GS_FLAG_AUX_OUTPUTS if aux else 0))
+    return make_renderer(s, W, H, ts, flags=fl, cols=cols, **kw)
+
+
+def code_of(fn):
+    """(code, message) of the GsError fn() must raise."""
+    from gsplat import _abi
+    with pytest.raises(_abi.GsError) as e:
+        fn()
+    return e.value.code, str(e.value)
+
+
+def timeless(st):
+    """stats() without what a clock measured."""
+    return {k: v for k, v in st.items() if k not in ("frame_us", "frame_us_mean", "frames_timed", "stage_us", "stage_us_mean")}
+
+
+TAPS = ("TILE_COUNTS", "GAUSSIAN_DATA", "KEYS", "VALUES", "RANGES")
+
+
+def frame_taps(r, u, debug):
+    """One frame: its TAPS, the image and the f32 tap."""
+    from gsplat import _abi
+    r.render_uniforms(u, debug=debug)
+    r.wait()
+    out = {t: r.read_buffer(getattr(_abi, "GS_BUF_" + t)) for t in TAPS}
+    out["rgba8"] = r.read_rgba8()
+    out["rgbf"] = r.read_buffer(_abi.GS_BUF_RGB_F32)
+    return out
+
+
+# ---- the other hosts ---------------------------------------------------------------------------------------------------------------
+def run_node(script, args, timeout=300):
+    """Runs tests/js/<script> under Node with `args`; returns the JSON on the last line of its output."""
+    res = subprocess.run([NODE, os.path.join(ROOT, "tests", "js", script)] + [str(a) for a in args], capture_output=True, text=True,
+                         timeout=timeout)
+    assert res.returncode == 0, res.stderr
+    return json.loads(res.stdout.strip().splitlines()[-1])
+
+
+def c_layout(tmp_path, name, body):
+    """Compiles the statements `body` (printfs of sizeof / offsetof / constants) into a C program against gs_abi.h, runs it and
+    returns the integers it prints."""
+    src, exe = tmp_path / (name + ".c"), tmp_path / name
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "gsplat/gs_abi.h"\nint main(void){' + body + "return 0;}\n")
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    return [int(x) for x in subprocess.check_output([str(exe)]).split()]
+
+
+HostSources = collections.namedtuple("HostSources", "rjs idx dts napi hdr")
+
+
+def host_sources():
+    """The texts of js/renderer.js, js/index.js, js/index.d.ts, csrc/napi/gs_napi.c and gs_abi.h, read once."""
+    def make():
+        paths = [os.path.join(JS_DIR, f) for f in ("renderer.js", "index.js", "index.d.ts")] + [NAPI_SRC, HEADER]
+        return HostSources(*(open(p).read() for p in paths))
+    return cached("host_sources", make)

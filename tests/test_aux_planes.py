@@ -6,21 +6,19 @@ term added; the CPU tests prove that its colour IS the oracle's, bit for bit, on
 both planes bit-equal to it in every blend kernel and binning, fused frames must stay within the colour's envelope, and the
 flag must change nothing else (image, f32 tap, evaluation count).
 """
+import functools
 import hashlib
 import os
 import re
-import shutil
-import subprocess
-import json
 
 import numpy as np
 import pytest
 
 from conftest import scene
+from support import (F, GOLDEN, NODE, SLAB_COLS, host_sources, make_splats, margin_ref, margin_scene, mk, oracle_frame, pixel_uniforms,
+                     run_node)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden")
-F = np.float32
+_mk = functools.partial(mk, aux=True)
 
 _CACHE = {}
 
@@ -35,11 +33,8 @@ def _restated(key, ref, W, H, ts, cols=None):
 
 def _config_a(oracle, ts, want_illcond=False):
     from gpu_checks import orbit_uniforms
-    k = ("cfgA", ts, want_illcond)
-    if k not in _CACHE:
-        s, u = scene(10000), orbit_uniforms(256, 256)
-        _CACHE[k] = (s, u, oracle.render(s, u, 256, 256, ts, want_illcond=want_illcond))
-    return _CACHE[k]
+    s, u = scene(10000), orbit_uniforms(256, 256)
+    return s, u, oracle_frame(oracle, "cfgA", s, u, 256, 256, ts, want_illcond=want_illcond)
 
 
 def _ragged(oracle):
@@ -83,16 +78,15 @@ def test_restatement_colour_is_the_oracle_ragged_golden(oracle):
 
 @pytest.mark.parametrize("name", ["transmittance_edge", "live_box", "degenerate_conic"])
 def test_restatement_colour_is_the_oracle_margin_scenes(oracle, name):
-    import test_blend_culls as tbc
-    s, u, W, H = tbc._scene(oracle, name)
-    for ts, cols in ((8, None), (16, tbc.SLAB_COLS[16])):
-        ref = tbc._ref(oracle, name, ts, cols)
+    s, u, W, H = margin_scene(oracle, name)
+    for ts, cols in ((8, None), (16, SLAB_COLS[16])):
+        ref = margin_ref(oracle, name, ts, cols)
         rgbf, A, D = _restated(name, ref, W, H, ts, cols)
         _same_bits(rgbf, ref["rgbf"])
 
 
 def test_abi_constants_agree_across_hosts():
-    hdr = open(os.path.join(ROOT, "include", "gsplat", "gs_abi.h")).read()
+    rjs, idx, dts, napi, hdr = host_sources()
     assert int(re.search(r"#define GS_FLAG_AUX_OUTPUTS (0x[0-9a-fA-F]+)u", hdr).group(1), 16) == 0x8
     assert int(re.search(r"GS_BUF_ALPHA_F32 = (\d+)", hdr).group(1)) == 13
     assert int(re.search(r"GS_BUF_DEPTH_F32 = (\d+)", hdr).group(1)) == 14
@@ -101,25 +95,14 @@ def test_abi_constants_agree_across_hosts():
     assert (_abi.GS_FLAG_AUX_OUTPUTS, _abi.GS_BUF_ALPHA_F32, _abi.GS_BUF_DEPTH_F32) == (0x8, 13, 14)
     # no id collides with an existing flag bit / tap
     assert _abi.GS_FLAG_AUX_OUTPUTS & (_abi.GS_FLAG_EXACT_BLEND | _abi.GS_FLAG_F32_TAP | _abi.GS_FLAG_TIMING) == 0
-    js = os.path.join(ROOT, "gaussian-splatting-wgpu_amd", "js")
-    dts = open(os.path.join(js, "index.d.ts")).read()
     assert re.search(r"ALPHA_F32: 13\b", dts) and re.search(r"DEPTH_F32: 14\b", dts) and re.search(r"AUX_OUTPUTS: 0x8\b", dts)
     assert "readAlpha(): Float32Array" in dts and "readDepth(normalized?: boolean): Float32Array" in dts
-    idx = open(os.path.join(js, "index.js")).read()
     assert re.search(r"ALPHA_F32: 13\b", idx) and re.search(r"DEPTH_F32: 14\b", idx) and re.search(r"AUX_OUTPUTS: 0x8\b", idx)
-    napi = open(os.path.join(ROOT, "gaussian-splatting-wgpu_amd", "csrc", "napi", "gs_napi.c")).read()
     for name in ("FLAG_AUX_OUTPUTS", "BUF_ALPHA_F32", "BUF_DEPTH_F32"):
         assert '"%s", GS_%s' % (name, name) in napi
 
 
 # ---- GPU ----------------------------------------------------------------------------------------------------------------------
-def _mk(s, W, H, ts, exact, aux=True, cols=None, **kw):
-    from gpu_checks import make_renderer
-    from gsplat import _abi
-    flags = (_abi.GS_FLAG_EXACT_BLEND if exact else 0) | (_abi.GS_FLAG_AUX_OUTPUTS if aux else 0)
-    return make_renderer(s, W, H, ts, flags=flags, cols=cols, **kw)
-
-
 def _frame(r, u, debug=False):
     r.render_uniforms(u, debug=debug)
     r.wait()
@@ -191,12 +174,11 @@ def test_planes_at_the_cull_margins(oracle, name, kernel):
     """The scenes of test_blend_culls.py (decisions at the margins of both parking culls, ragged canvases): the planes with the culls
     on equal those with the culls off bit for bit, in every kernel, binning and mode, on the whole canvas and on a tile-column slab
     that does not start at column 0; EXACT planes equal the restatement."""
-    import test_blend_culls as tbc
     from gsplat import _abi
     ts, abl = kernel
-    s, u, W, H = tbc._scene(oracle, name)
-    for cols in (None, tbc.SLAB_COLS[ts]):
-        ref = tbc._ref(oracle, name, ts, cols)
+    s, u, W, H = margin_scene(oracle, name)
+    for cols in (None, SLAB_COLS[ts]):
+        ref = margin_ref(oracle, name, ts, cols)
         restated = _restated(name, ref, W, H, ts, cols)
         for exact in (True, False):
             r = _mk(s, W, H, ts, exact=exact, cols=cols)
@@ -296,10 +278,9 @@ def test_flag_changes_nothing_else_config_b():
 
 def _pixel_scene(W, H, px, py, z, sig, logit, color):
     """Records in pixel space (identity view and projection; the centre (px, py) in pixels at depth z)."""
-    import test_blend_culls as tbc
-    s = tbc.make_splats(W, H, px, py, sig, sig, 0.0, np.asarray(logit, np.float32), color=color)
+    s = make_splats(W, H, px, py, sig, sig, 0.0, np.asarray(logit, np.float32), color=color)
     s[:, 2] = z  # (the projected size scales with 1 / z)
-    return s, tbc.pixel_uniforms(W, H)
+    return s, pixel_uniforms(W, H)
 
 
 @pytest.mark.gpu
@@ -439,9 +420,6 @@ def test_plane_taps_errors(oracle):
     r.destroy()
 
 
-NODE = shutil.which("node")
-
-
 @pytest.mark.gpu
 @pytest.mark.skipif(NODE is None, reason="node is not installed")
 def test_node_host_planes_match_python(tmp_path):
@@ -452,10 +430,7 @@ def test_node_host_planes_match_python(tmp_path):
     rec, ub, out = str(tmp_path / "rec.bin"), str(tmp_path / "u.bin"), str(tmp_path / "planes.bin")
     s.tofile(rec)
     u.tofile(ub)
-    res = subprocess.run([NODE, os.path.join(ROOT, "tests", "js", "aux_check.js")] + [str(a) for a in (rec, n, W, H, ts, ub, out)],
-                         capture_output=True, text=True, timeout=300)
-    assert res.returncode == 0, res.stderr
-    info = json.loads(res.stdout.strip().splitlines()[-1])
+    info = run_node("aux_check.js", (rec, n, W, H, ts, ub, out))
     assert info["n"] == W * H
     planes = np.fromfile(out, dtype=np.float32).reshape(3, H, W)
     r = _mk(s, W, H, ts, exact=True)

@@ -7,20 +7,13 @@ bit -- EXACT and fused frames, every binning, emission order and frame path --, 
 editor verbs, the ring, slabs, the lifecycle and the Node host.
 """
 import ctypes
-import json
-import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import scene
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "gsplat", "gs_abi.h")
-F = np.float32
+from support import NODE, c_layout, code_of, host_sources, mk as _mk, pick_case, run_node, timeless
 MARGIN = ("transmittance_edge", "live_box", "degenerate_conic")
 RECT_A = (37, 51, 98, 96)    # [37,98) x [51,96): aligned to neither 8 nor a tile, crosses tile borders at every tile size
 RECT_M = (3, 2, 60, 45)      # the margin scenes' first rect; their second is the canvas's bottom-right corner ("corner")
@@ -34,8 +27,7 @@ _CACHE = {}
 
 def _scene_of(oracle, name, ts):
     """(splats, uniforms, W, H, oracle frame) of a case: the scenes and frames of test_pick.py."""
-    import test_pick
-    s, u, W, H, ref, _ = test_pick._case(oracle, name, ts)
+    s, u, W, H, ref, _ = pick_case(oracle, name, ts)
     return s, u, W, H, ref
 
 
@@ -89,15 +81,10 @@ def test_coverage_abi(tmp_path):
     rec_fields = [n for n, _ in _abi.GsCoverageRec._fields_]
     reg_fields = [n for n, _ in _abi.GsCoverRegion._fields_]
     assert rec_fields == ["sum_q", "hits", "max_weight"] and reg_fields == ["struct_size", "x0", "y0", "x1", "y1", "mask"]
-    prog = '#include <stdio.h>\n#include <stddef.h>\n#include "gsplat/gs_abi.h"\nint main(void){'
-    prog += 'printf("%d %zu %zu", GS_ABI_VERSION, sizeof(gs_coverage_rec), sizeof(gs_cover_region));'
+    prog = 'printf("%d %zu %zu", GS_ABI_VERSION, sizeof(gs_coverage_rec), sizeof(gs_cover_region));'
     prog += "".join('printf(" %%zu", offsetof(gs_coverage_rec, %s));' % n for n in rec_fields)
     prog += "".join('printf(" %%zu", offsetof(gs_cover_region, %s));' % n for n in reg_fields)
-    prog += "return 0;}\n"
-    src, exe = tmp_path / "coverage_layout.c", tmp_path / "coverage_layout"
-    src.write_text(prog)
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    out = [int(x) for x in subprocess.check_output([str(exe)]).split()]
+    out = c_layout(tmp_path, "coverage_layout", prog)
     assert out[0] == 3 and L.gs_abi_version() == 3
     assert out[1] == 16 == ctypes.sizeof(_abi.GsCoverageRec) == _abi.COVERAGE_DTYPE.itemsize == cr.COVERAGE_DTYPE.itemsize
     assert out[2] == ctypes.sizeof(_abi.GsCoverRegion) == 32
@@ -106,23 +93,18 @@ def test_coverage_abi(tmp_path):
     for dt in (_abi.COVERAGE_DTYPE, cr.COVERAGE_DTYPE):
         assert list(dt.names) == rec_fields and [dt.fields[n][1] for n in rec_fields] == [0, 8, 12]
         assert [dt.fields[n][0] for n in rec_fields] == [np.uint64, np.uint32, np.float32]
-    hdr = open(HEADER).read()
+    rjs, idx, dts, napi, hdr = host_sources()
     assert re.search(r"#define GS_ABI_VERSION 3\b", hdr)
     for name in names:
         assert re.search(r"int32_t %s\(gs_ctx\*" % name, hdr)
     assert "2^64" in hdr and "2^32 accepted pairs" in hdr  # the wrap-around is documented
-    js = os.path.join(ROOT, "gaussian-splatting-wgpu_amd", "js")
-    rjs = open(os.path.join(js, "renderer.js")).read()
     assert re.search(r"COVERAGE = \{ REC_BYTES: 16 \}", rjs)
     m = re.search(r"COVERAGE_FIELD = \{([^}]*)\}", rjs)
     assert [(k, int(v)) for k, v in re.findall(r"(\w+):\s*(\d+)", m.group(1))] == [("sumQ", 0), ("hits", 8), ("maxWeight", 12)]
-    idx = open(os.path.join(js, "index.js")).read()
     assert re.search(r"\bCOVERAGE\b", idx) and "sumQ: 0, hits: 8, maxWeight: 12" in idx
-    dts = open(os.path.join(js, "index.d.ts")).read()
     assert "COVERAGE_FIELD: { sumQ: 0; hits: 8; maxWeight: 12 }" in dts and "REC_BYTES: 16" in dts
     for fn in ("accumulateCoverage", "resetCoverage", "readCoverage", "stateCoverage"):
         assert re.search(r"\b%s\(" % fn, dts) and re.search(r"\b%s\(" % fn, rjs)
-    napi = open(os.path.join(ROOT, "gaussian-splatting-wgpu_amd", "csrc", "napi", "gs_napi.c")).read()
     for fn in ("accumulateCoverage", "resetCoverage", "readCoverage", "stateCoverage"):
         assert '{"%s", js_' % fn in napi
     assert '"COVERAGE_REC_BYTES", (double)sizeof(gs_coverage_rec)' in napi
@@ -208,23 +190,9 @@ def test_merge_coverage():
 
 
 # ---- GPU -----------------------------------------------------------------------------------------------------------------------
-def _mk(s, W, H, ts, exact=False, state=False, cols=None, **kw):
-    from gpu_checks import make_renderer
-    from gsplat import _abi
-    flags = (_abi.GS_FLAG_EXACT_BLEND if exact else 0) | (_abi.GS_FLAG_SPLAT_STATE if state else 0)
-    return make_renderer(s, W, H, ts, flags=flags, cols=cols, **kw)
-
-
 def _same(got, want, cell=""):
     import coverage_restate as cr
     np.testing.assert_array_equal(cr.words(got), cr.words(want), err_msg=str(cell))
-
-
-def _code(fn):
-    from gsplat import _abi
-    with pytest.raises(_abi.GsError) as e:
-        fn()
-    return e.value.code, str(e.value)
 
 
 # (GS_OPT_TILE_CULL, gs_render_debug, GS_OPT_EMIT_ORDER, GS_OPT_FRAME_GRAPH): every value of every knob, the product path first
@@ -357,7 +325,7 @@ def test_state_coverage(oracle, length):
     q.wait()
     q.accumulate_coverage()
     np.testing.assert_array_equal(q.read_coverage().view(np.uint32), p.view(np.uint32))
-    c, msg = _code(lambda: q.state_coverage(_abi.GS_STATE_SET, 2))
+    c, msg = code_of(lambda: q.state_coverage(_abi.GS_STATE_SET, 2))
     assert c == _abi.GS_ERR_INVALID_ARGUMENT and "GS_FLAG_SPLAT_STATE" in msg
     q.destroy()
 
@@ -412,10 +380,6 @@ def test_select_visible_and_hide_unseen(oracle):
     r.destroy()
 
 
-def _timeless(st):
-    return {k: v for k, v in st.items() if k not in ("frame_us", "frame_us_mean", "frames_timed", "stage_us", "stage_us_mean")}
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("graph", [0, 1])
 def test_coverage_disturbs_nothing(oracle, graph):
@@ -430,13 +394,13 @@ def test_coverage_disturbs_nothing(oracle, graph):
         r.render_uniforms(u0)
         r.wait()
     taps = (_abi.GS_BUF_VALUES, _abi.GS_BUF_RANGES, _abi.GS_BUF_TILE_COUNTS, _abi.GS_BUF_GAUSSIAN_DATA, _abi.GS_BUF_RGB_F32)
-    before = [a.read_rgba8()] + [a.read_buffer(t) for t in taps] + [_timeless(a.stats())]
+    before = [a.read_rgba8()] + [a.read_buffer(t) for t in taps] + [timeless(a.stats())]
     a.accumulate_coverage(RECT_A)
     first = a.read_coverage()
     a.reset_coverage()
     a.accumulate_coverage(RECT_A)  # a second run: the same planes, whatever order the adds arrived in
     _same(a.read_coverage(), first, "two runs")
-    after = [a.read_rgba8()] + [a.read_buffer(t) for t in taps] + [_timeless(a.stats())]
+    after = [a.read_rgba8()] + [a.read_buffer(t) for t in taps] + [timeless(a.stats())]
     for x, y in zip(before[:-1], after[:-1]):
         np.testing.assert_array_equal(x, y)
     assert before[-1] == after[-1]
@@ -448,7 +412,7 @@ def test_coverage_disturbs_nothing(oracle, graph):
         np.testing.assert_array_equal(a.read_rgba8(), b.read_rgba8())
         np.testing.assert_array_equal(a.read_buffer(_abi.GS_BUF_RGB_F32), b.read_buffer(_abi.GS_BUF_RGB_F32))
         np.testing.assert_array_equal(a.read_buffer(_abi.GS_BUF_VALUES), b.read_buffer(_abi.GS_BUF_VALUES))
-        assert _timeless(a.stats()) == _timeless(b.stats())
+        assert timeless(a.stats()) == timeless(b.stats())
         assert a.stats()["graph_frames"] == (k + 2 if graph else 0)
     a.destroy()
     b.destroy()
@@ -516,20 +480,20 @@ def test_coverage_lifecycle_and_errors(oracle):
     assert L.gs_state_coverage(ctx, 1, 0.0, 1, 0, 0, 1, 2, None) == _abi.GS_ERR_NO_SCENE
     L.gs_destroy(ctx)
     r = _mk(s, W, H, 16, state=True)
-    assert _code(lambda: r.accumulate_coverage())[0] == _abi.GS_ERR_NO_FRAME  # after the upload, before any frame
+    assert code_of(lambda: r.accumulate_coverage())[0] == _abi.GS_ERR_NO_FRAME  # after the upload, before any frame
     r.render_uniforms(u)
     r.wait()
     # bad regions: the message names the numbers; nothing is added
     reg = _abi.GsCoverRegion()
     reg.struct_size, reg.x0, reg.y0, reg.x1, reg.y1 = 8, 0, 0, 4, 4
     assert L.gs_coverage_accumulate(r._ctx, ctypes.byref(reg), None) == _abi.GS_ERR_INVALID_ARGUMENT and b"struct_size 8" in L.gs_last_error()
-    c, msg = _code(lambda: r.accumulate_coverage((0, 0, W + 1, H)))
+    c, msg = code_of(lambda: r.accumulate_coverage((0, 0, W + 1, H)))
     assert c == _abi.GS_ERR_INVALID_ARGUMENT and str(W + 1) in msg and "%u x %u" % (W, H) in msg
-    c, msg = _code(lambda: r.accumulate_coverage((0, 3, W, H + 2)))
+    c, msg = code_of(lambda: r.accumulate_coverage((0, 3, W, H + 2)))
     assert c == _abi.GS_ERR_INVALID_ARGUMENT and str(H + 2) in msg
-    c, msg = _code(lambda: r.accumulate_coverage((40, 7, 40, 9)))
+    c, msg = code_of(lambda: r.accumulate_coverage((40, 7, 40, 9)))
     assert c == _abi.GS_ERR_INVALID_ARGUMENT and "empty" in msg and "[40, 40)" in msg
-    assert _code(lambda: r.accumulate_coverage((9, 30, 12, 20)))[0] == _abi.GS_ERR_INVALID_ARGUMENT
+    assert code_of(lambda: r.accumulate_coverage((9, 30, 12, 20)))[0] == _abi.GS_ERR_INVALID_ARGUMENT
     with pytest.raises(ValueError):
         r.accumulate_coverage(mask=np.zeros((H, W + 1), np.uint8))
     zero = np.zeros(s.shape[0], cr.COVERAGE_DTYPE)
@@ -554,7 +518,7 @@ def test_coverage_lifecycle_and_errors(oracle):
     # an upload drops the planes and the frame
     arr = np.ascontiguousarray(s, dtype=np.float32)
     _abi.check(L.gs_upload_splats(r._ctx, arr.ctypes.data, arr.shape[0]))
-    assert _code(lambda: r.accumulate_coverage())[0] == _abi.GS_ERR_NO_FRAME
+    assert code_of(lambda: r.accumulate_coverage())[0] == _abi.GS_ERR_NO_FRAME
     _same(r.read_coverage(), zero, "after an upload")
     r.render_uniforms(u)
     r.wait()
@@ -565,7 +529,7 @@ def test_coverage_lifecycle_and_errors(oracle):
     assert keep == int((want["hits"] > 0).sum())
     ids = r.compact(0x40, 0x40)
     assert ids.size == keep
-    assert _code(lambda: r.accumulate_coverage())[0] == _abi.GS_ERR_NO_FRAME
+    assert code_of(lambda: r.accumulate_coverage())[0] == _abi.GS_ERR_NO_FRAME
     _same(r.read_coverage(), np.zeros(keep, cr.COVERAGE_DTYPE), "after a compaction")
     r.render_uniforms(u)
     r.wait()
@@ -574,9 +538,6 @@ def test_coverage_lifecycle_and_errors(oracle):
     assert got.shape == (keep,)
     _same(got, want[ids], "the compacted scene shows what the covered splats showed")
     r.destroy()
-
-
-NODE = shutil.which("node")
 
 
 @pytest.mark.gpu
@@ -592,10 +553,7 @@ def test_node_host_coverage_matches_python(tmp_path):
     s.tofile(rec)
     u.tofile(ub)
     mask.tofile(mb)
-    res = subprocess.run([NODE, os.path.join(ROOT, "tests", "js", "coverage_check.js")] + [str(a) for a in (rec, n, W, H, ts, ub) + rect + (mb, out)],
-                         capture_output=True, text=True, timeout=300)
-    assert res.returncode == 0, res.stderr
-    info = json.loads(res.stdout.strip().splitlines()[-1])
+    info = run_node("coverage_check.js", (rec, n, W, H, ts, ub) + rect + (mb, out))
     r = _mk(s, W, H, ts, state=True)
     r.render_uniforms(u)
     r.wait()

@@ -7,10 +7,8 @@ gives it: the context must be indistinguishable from a fresh one given gs_upload
 bytes) -- every tap and the image, bit for bit.
 """
 import ctypes
-import json
+import functools
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -18,39 +16,14 @@ import pytest
 from conftest import scene
 import export_restate as er
 import state_restate as sr
+from support import (F, FRAME_CASES, NODE, TAPS, code_of, frame_taps, guarded, hidden_plane, host_sources, in_region, is_fill, mk, raw_export, run_node,
+                     special, special_records, state_ref, state_scene)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden")
-F = np.float32
-NODE = shutil.which("node")
+_mk = functools.partial(mk, exact=True, state=True)
 HID, SEL = er.HIDDEN, er.SELECTED
 SYMBOLS = ("gs_state_list", "gs_export_splats", "gs_export_splats_device", "gs_compact", "gs_ply_save", "gs_export_ply")
 FILTERS = [(0, 0), (HID, 0), (SEL, SEL), (0xFF, 0x83), (0, 1), (HID | SEL, SEL)]
 _CACHE = {}
-
-
-def _special(rec):
-    """A copy with a handful of floats overwritten by a NaN, a payload NaN, -0.0, +-inf and a denormal (carried floats), and the
-    padding floats of two records filled with junk that must NOT come back."""
-    out = np.array(rec, dtype=F, copy=True).reshape(-1, 80)
-    w = out.view(np.uint32)
-    n = out.shape[0]
-    vals = [0x7FC00000, 0x7FA12345, 0x80000000, 0x7F800000, 0xFF800000, 0x00000001, 0xFFC0BEEF]
-    slots = [0, 5, 9, 12, 16, 18, 17 + 4 * 15, 4, 2, 22]
-    for k, v in enumerate(vals * 2):
-        w[(k * 7) % n, slots[k % len(slots)]] = v
-    w[0, er.PADDING] = 0xA5A5A5A5
-    w[n - 1, er.PADDING] = 0x3F800000
-    return out
-
-
-def _records(n):
-    """n records of synth.bicycle_like (the ragged fixture's own scene for 3001) with the special floats."""
-    if ("rec", n) not in _CACHE:
-        from gsplat import synth
-        base = synth.bicycle_like(3001) if n == 3001 else scene(10000)[:n]
-        _CACHE[("rec", n)] = _special(base)
-    return _CACHE[("rec", n)]
 
 
 # ---- CPU --------------------------------------------------------------------------------------------------------------------------
@@ -72,16 +45,13 @@ def test_export_abi():
         assert call() == _abi.GS_ERR_INVALID_ARGUMENT
         assert who in L.gs_last_error() and b"null" in L.gs_last_error()
     assert n.value == 77
-    hdr = open(os.path.join(ROOT, "include", "gsplat", "gs_abi.h")).read()
+    rjs, idx, dts, napi, hdr = host_sources()
     for name in SYMBOLS:
         assert "int32_t %s(" % name in hdr
     assert "splat edits" in hdr and "#define GS_ABI_VERSION 3\n" in hdr
-    js = os.path.join(ROOT, "gaussian-splatting-wgpu_amd", "js")
-    dts, rjs, idx = (open(os.path.join(js, f)).read() for f in ("index.d.ts", "renderer.js", "index.js"))
     for m in ("listState(", "exportSplats(", "compact(", "deleteHidden(", "savePly("):
         assert m in dts and m in rjs
     assert "savePly" in idx and "export function savePly(" in dts
-    napi = open(os.path.join(ROOT, "gaussian-splatting-wgpu_amd", "csrc", "napi", "gs_napi.c")).read()
     for name in ("listState", "exportSplats", "compact", "exportPly", "savePly"):
         assert '{"%s", js_' % name in napi
 
@@ -96,10 +66,10 @@ def test_restatement_sanity():
     st = np.array([0, 1, 2, 3, 0x83, 0x80], np.uint8)
     assert er.ids_of(st, HID, 0).tolist() == [0, 2, 5] and er.ids_of(st, 0, 0).tolist() == [0, 1, 2, 3, 4, 5]
     assert er.ids_of(st, 0, 1).size == 0 and er.ids_of(st, 0xFF, 0x83).tolist() == [4]
-    names, cols = er.ply_columns(_records(5), 1)
+    names, cols = er.ply_columns(special_records(5), 1)
     assert names[9:18] == ["f_rest_%d" % k for k in range(9)] and cols.shape == (5, 26)
     # f_rest_{cK+i} is coefficient i + 1, channel c
-    np.testing.assert_array_equal(cols[:, 9 + 1 * 3 + 2], er.bits(_records(5))[:, 16 + 4 * 3 + 1])
+    np.testing.assert_array_equal(cols[:, 9 + 1 * 3 + 2], er.bits(special_records(5))[:, 16 + 4 * 3 + 1])
 
 
 @pytest.mark.parametrize("n", [0, 1, 5, 3001])
@@ -108,7 +78,7 @@ def test_ply_save_round_trip(tmp_path, degree, n):
     """gs_ply_save -> gs_ply_load: the records come back with the padding zeroed and the coefficients above the degree zeroed, bit
     for bit, special floats included; the header is the property list of the restatement and the data has the stated size."""
     from gsplat import _abi
-    rec = _special(_records(3001)[:n]) if n else np.zeros((0, 80), F)  # (the special floats land inside the first n records)
+    rec = special(special_records(3001)[:n]) if n else np.zeros((0, 80), F)  # (the special floats land inside the first n records)
     path = str(tmp_path / "out.ply")
     _abi.save_ply(path, rec, degree)
     back, deg = _abi.load_ply(path)
@@ -128,7 +98,7 @@ def test_ply_save_round_trip(tmp_path, degree, n):
 def test_ply_save_errors(tmp_path):
     from gsplat import _abi
     L = _abi.load()
-    rec = _records(5)
+    rec = special_records(5)
     good = str(tmp_path / "good.ply").encode()
     for degree in (4, -1):
         assert L.gs_ply_save(good, rec.ctypes.data, 5, degree) == _abi.GS_ERR_INVALID_ARGUMENT
@@ -146,20 +116,6 @@ def test_ply_save_errors(tmp_path):
 
 
 # ---- GPU --------------------------------------------------------------------------------------------------------------------------
-def _mk(s, W, H, ts, exact=True, state=True, cols=None, flags=0, **kw):
-    from gpu_checks import make_renderer
-    from gsplat import _abi
-    fl = flags | (_abi.GS_FLAG_EXACT_BLEND if exact else 0) | (_abi.GS_FLAG_SPLAT_STATE if state else 0)
-    return make_renderer(s, W, H, ts, flags=fl, cols=cols, **kw)
-
-
-def _code(fn):
-    from gsplat import _abi
-    with pytest.raises(_abi.GsError) as e:
-        fn()
-    return e.value.code, str(e.value)
-
-
 def _planes(n):
     rng = np.random.default_rng(1234 + n)
     first, last = np.full(n, 0xFF, np.uint8), np.full(n, 0xFF, np.uint8)
@@ -172,45 +128,6 @@ def _planes(n):
             "only_first": first, "only_last": last}
 
 
-def _guarded(shape, dtype):
-    a = np.empty(shape, dtype)
-    a.view(np.uint8).fill(0xA5)
-    return a
-
-
-def _is_fill(a):
-    return bool((np.ascontiguousarray(a).view(np.uint8) == 0xA5).all())
-
-
-def _raw_export(r, mask, value, with_ids, device=False):
-    """gs_export_splats[_device] into buffers one record and one id longer than needed, pre-filled with 0xA5; returns (records,
-    ids or None) after checking the guards."""
-    from gsplat import _abi
-    L = _abi.load()
-    n = ctypes.c_uint64()
-    _abi.check(L.gs_export_splats(r._ctx, mask, value, None, 0, ctypes.byref(n), None))
-    m = n.value
-    if device:
-        import torch
-        rec_t = torch.full((m + 1, 80), 0, dtype=torch.float32, device="cuda")
-        rec_t.view(torch.uint8).fill_(0xA5)
-        ids_t = torch.zeros(m + 1, dtype=torch.int32, device="cuda")
-        ids_t.view(torch.uint8).fill_(0xA5)
-        torch.cuda.synchronize()
-        n2 = ctypes.c_uint64()
-        _abi.check(L.gs_export_splats_device(r._ctx, mask, value, rec_t.data_ptr(), m + 1, ctypes.byref(n2), ids_t.data_ptr() if with_ids else None))
-        rec, ids = rec_t.cpu().numpy(), ids_t.cpu().numpy().view(np.uint32)
-    else:
-        rec, ids = _guarded((m + 1, 80), F), _guarded(m + 1, np.uint32)
-        n2 = ctypes.c_uint64()
-        _abi.check(L.gs_export_splats(r._ctx, mask, value, rec.ctypes.data, m + 1, ctypes.byref(n2), ids.ctypes.data if with_ids else None))
-    assert n2.value == m
-    assert _is_fill(rec[m:]) and _is_fill(ids[m:])
-    if not with_ids:
-        assert _is_fill(ids)
-    return rec[:m], (ids[:m] if with_ids else None)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("n", [1, 3, 4, 5, 1023, 1024, 1025, 3001, 10000])
 def test_list_and_export_kernels(n):
@@ -219,7 +136,7 @@ def test_list_and_export_kernels(n):
     the word tail; 1023, 1024, 1025: one workgroup less one splat, exactly one, one plus one splat; 3001: the ragged fixture."""
     from gsplat import _abi
     L = _abi.load()
-    rec = _records(n)
+    rec = special_records(n)
     r = _mk(rec, 64, 64, 8)
     seen = 0
     for pname, plane in _planes(n).items():
@@ -232,14 +149,14 @@ def test_list_and_export_kernels(n):
             cnt = ctypes.c_uint64()
             _abi.check(L.gs_state_list(r._ctx, mask, value, None, 0, ctypes.byref(cnt)))
             assert cnt.value == m == r.state_count(mask, value), (pname, mask, value)
-            ids = _guarded(m + 1, np.uint32)
+            ids = guarded(m + 1, np.uint32)
             _abi.check(L.gs_state_list(r._ctx, mask, value, ids.ctypes.data, m + 1, ctypes.byref(cnt)))
-            assert cnt.value == m and _is_fill(ids[m:])
+            assert cnt.value == m and is_fill(ids[m:])
             np.testing.assert_array_equal(ids[:m], want_ids, err_msg="%s (%#x, %#x)" % (pname, mask, value))
             np.testing.assert_array_equal(r.list_state(mask, value), want_ids)
             for with_ids in (False, True):
                 for device in (False, True):
-                    got, gids = _raw_export(r, mask, value, with_ids, device)
+                    got, gids = raw_export(r, mask, value, with_ids, device)
                     np.testing.assert_array_equal(er.bits(got), er.bits(want_rec), err_msg="%s (%#x, %#x) device=%s" % (pname, mask, value, device))
                     if with_ids:
                         np.testing.assert_array_equal(gids, want_ids)
@@ -270,12 +187,12 @@ def test_large_list():
 def test_unflagged_context(tmp_path):
     """Without GS_FLAG_SPLAT_STATE (0, 0) exports, lists and saves what is resident; any other filter is refused."""
     from gsplat import _abi
-    rec = _records(3001)
+    rec = special_records(3001)
     r = _mk(rec, 64, 64, 8, state=False)
-    got, ids = _raw_export(r, 0, 0, True)
+    got, ids = raw_export(r, 0, 0, True)
     np.testing.assert_array_equal(er.bits(got), er.bits(er.zero_padding(rec)))
     np.testing.assert_array_equal(ids, np.arange(3001, dtype=np.uint32))
-    got, ids = _raw_export(r, 0, 0, True, device=True)
+    got, ids = raw_export(r, 0, 0, True, device=True)
     np.testing.assert_array_equal(er.bits(got), er.bits(er.zero_padding(rec)))
     np.testing.assert_array_equal(ids, np.arange(3001, dtype=np.uint32))
     np.testing.assert_array_equal(r.list_state(0, 0), np.arange(3001, dtype=np.uint32))
@@ -284,7 +201,7 @@ def test_unflagged_context(tmp_path):
     np.testing.assert_array_equal(er.bits(_abi.load_ply(path)[0]), er.bits(er.zero_padding(rec)))
     for fn in (lambda: r.list_state(HID, 0), lambda: r.export_splats(HID, 0), lambda: r.export_splats(0, 1, device=True),
                lambda: r.compact(HID, 0), lambda: r.save_ply(path, SEL, SEL)):
-        c, msg = _code(fn)
+        c, msg = code_of(fn)
         assert c == _abi.GS_ERR_INVALID_ARGUMENT and "GS_FLAG_SPLAT_STATE" in msg
     np.testing.assert_array_equal(r.compact(0, 0), np.arange(3001, dtype=np.uint32))  # everything kept: the same path
     np.testing.assert_array_equal(er.bits(r.export_splats()), er.bits(er.zero_padding(rec)))
@@ -305,23 +222,23 @@ def test_export_errors():
     r = _mk(rec, W, H, 16)
     r.write_state(plane)
     cnt = ctypes.c_uint64()
-    ids = _guarded(m, np.uint32)
-    out = _guarded((m, 80), F)
+    ids = guarded(m, np.uint32)
+    out = guarded((m, 80), F)
     assert L.gs_state_list(r._ctx, HID, 0, ids.ctypes.data, m - 1, ctypes.byref(cnt)) == _abi.GS_ERR_INVALID_ARGUMENT
-    assert str(m).encode() in L.gs_last_error() and _is_fill(ids)
+    assert str(m).encode() in L.gs_last_error() and is_fill(ids)
     assert L.gs_export_splats(r._ctx, HID, 0, out.ctypes.data, m - 1, ctypes.byref(cnt), ids.ctypes.data) == _abi.GS_ERR_INVALID_ARGUMENT
-    assert str(m).encode() in L.gs_last_error() and _is_fill(ids) and _is_fill(out)
+    assert str(m).encode() in L.gs_last_error() and is_fill(ids) and is_fill(out)
     import torch
     d = torch.zeros((m, 80), dtype=torch.float32, device="cuda")
     d.view(torch.uint8).fill_(0xA5)
     torch.cuda.synchronize()
     assert L.gs_export_splats_device(r._ctx, HID, 0, d.data_ptr(), m - 1, ctypes.byref(cnt), None) == _abi.GS_ERR_INVALID_ARGUMENT
-    assert str(m).encode() in L.gs_last_error() and _is_fill(d.cpu().numpy())
+    assert str(m).encode() in L.gs_last_error() and is_fill(d.cpu().numpy())
     for fn in (lambda: r.list_state(0x100, 0), lambda: r.export_splats(0, 0x100), lambda: r.compact(0x100, 0),
                lambda: r.save_ply("/nonexistent/x.ply", 0x1FF, 0)):
-        assert _code(fn)[0] == _abi.GS_ERR_INVALID_ARGUMENT
-    assert _code(lambda: r.save_ply("/nonexistent_dir_of_the_test/x.ply", HID, 0))[0] == _abi.GS_ERR_INVALID_ARGUMENT
-    assert _code(lambda: r.save_ply("x.ply", HID, 0, sh_degree=4))[0] == _abi.GS_ERR_INVALID_ARGUMENT
+        assert code_of(fn)[0] == _abi.GS_ERR_INVALID_ARGUMENT
+    assert code_of(lambda: r.save_ply("/nonexistent_dir_of_the_test/x.ply", HID, 0))[0] == _abi.GS_ERR_INVALID_ARGUMENT
+    assert code_of(lambda: r.save_ply("x.ply", HID, 0, sh_degree=4))[0] == _abi.GS_ERR_INVALID_ARGUMENT
     np.testing.assert_array_equal(r.read_state(), plane)
     # before any upload
     cfg = _abi.GsConfig()
@@ -340,7 +257,7 @@ def test_export_errors():
         x.render_uniforms(u)
         x.wait()
         before.append(x.read_rgba8())
-    c, msg = _code(lambda: b.compact(HID, 0))
+    c, msg = code_of(lambda: b.compact(HID, 0))
     assert c == _abi.GS_ERR_INVALID_ARGUMENT and "owner" in msg
     np.testing.assert_array_equal(b.list_state(HID, 0), er.ids_of(plane, HID, 0))  # listing and exporting a borrowed scene is fine
     for x, img in zip((r, b), before):
@@ -354,29 +271,17 @@ def test_export_errors():
 
 # ---- compaction is a filtered upload -----------------------------------------------------------------------------------------------
 def _compaction_plane(name, which):
-    import test_splat_state as tss
-    s = tss._scene(name)[0]
+    s = state_scene(name)[0]
     n = s.shape[0]
     host = (np.random.default_rng(99).integers(0, 64, n, dtype=np.uint8) << 2).astype(np.uint8)  # bits 2-7 belong to the host
     if which == "every_third":
-        return tss._hidden_plane(name, "every_third") | host
+        return hidden_plane(name, "every_third") | host
     if which == "rect_sphere":
-        return (tss._hidden_plane(name, "centre_half_rect") | np.where(tss._inside(name, "sphere_r1"), SEL, 0).astype(np.uint8)) | host
+        return (hidden_plane(name, "centre_half_rect") | np.where(in_region(name, "sphere_r1"), SEL, 0).astype(np.uint8)) | host
     return host  # nothing hidden: kept == N takes the same path
 
 
 COMPACTIONS = [("every_third", (HID, 0)), ("rect_sphere", (HID, 0)), ("rect_sphere", (SEL, SEL)), ("host_bits", (HID, 0))]
-TAPS = ("TILE_COUNTS", "GAUSSIAN_DATA", "KEYS", "VALUES", "RANGES")
-
-
-def _frame(r, u, debug):
-    from gsplat import _abi
-    r.render_uniforms(u, debug=debug)
-    r.wait()
-    out = {t: r.read_buffer(getattr(_abi, "GS_BUF_" + t)) for t in TAPS}
-    out["rgba8"] = r.read_rgba8()
-    out["rgbf"] = r.read_buffer(_abi.GS_BUF_RGB_F32)
-    return out
 
 
 @pytest.mark.gpu
@@ -384,12 +289,11 @@ def _frame(r, u, debug):
 @pytest.mark.parametrize("which,filt", COMPACTIONS, ids=["%s-%x-%x" % (w, f[0], f[1]) for w, f in COMPACTIONS])
 @pytest.mark.parametrize("case", [("cfgA", 8), ("cfgA", 16), ("cfgA", 32), ("ragged", 8)], ids=lambda c: "%s-t%d" % c)
 def test_compaction_is_a_filtered_upload(oracle, case, which, filt, exact):
-    import test_splat_state as tss
     from gpu_checks import check_image
     from gsplat import _abi
-    assert list(tss.FRAME_CASES) == [("cfgA", 8), ("cfgA", 16), ("cfgA", 32), ("ragged", 8)]
+    assert list(FRAME_CASES) == [("cfgA", 8), ("cfgA", 16), ("cfgA", 32), ("ragged", 8)]
     name, ts = case
-    s, u, W, H = tss._scene(name)
+    s, u, W, H = state_scene(name)
     plane = _compaction_plane(name, which)
     want_ids = er.ids_of(plane, *filt)
     hidden_filter = filt == (HID, 0)
@@ -397,7 +301,7 @@ def test_compaction_is_a_filtered_upload(oracle, case, which, filt, exact):
         assert 0 < want_ids.size < s.shape[0]
     r = _mk(s, W, H, ts, exact=exact)
     r.write_state(plane)
-    old = _frame(r, u, False) if hidden_filter else None
+    old = frame_taps(r, u, False) if hidden_filter else None
     ids = r.compact(*filt)
     np.testing.assert_array_equal(ids, want_ids)
     assert r.numGaussians == want_ids.size
@@ -406,7 +310,7 @@ def test_compaction_is_a_filtered_upload(oracle, case, which, filt, exact):
     fresh = _mk(np.ascontiguousarray(s[want_ids]), W, H, ts, exact=exact)
     fresh.write_state(plane[want_ids])
     for debug in (False, True):
-        a, b = _frame(r, u, debug), _frame(fresh, u, debug)
+        a, b = frame_taps(r, u, debug), frame_taps(fresh, u, debug)
         assert r.stats()["num_gaussians"] == want_ids.size
         for t in TAPS:
             np.testing.assert_array_equal(a[t], b[t], err_msg="%s debug=%s" % (t, debug))
@@ -435,15 +339,14 @@ def test_compaction_is_a_filtered_upload(oracle, case, which, filt, exact):
 def test_compaction_on_frame_paths(oracle):
     """Frames in flight, a captured frame graph, a slab, PipelinedRenderer and kept == 0."""
     import gsplat
-    import test_splat_state as tss
     from gpu_checks import check_image
     from gsplat import _abi
     name, ts = "cfgA", 16
-    s, u, W, H = tss._scene(name)
+    s, u, W, H = state_scene(name)
     n = s.shape[0]
-    plane = tss._hidden_plane(name, "every_third")
+    plane = hidden_plane(name, "every_third")
     ids = er.ids_of(plane, HID, 0)
-    ref = tss._ref(oracle, name, ts, "every_third", plane)  # hidden in place: the image a compacted scene must render too
+    ref = state_ref(oracle, name, ts, "every_third", plane)  # hidden in place: the image a compacted scene must render too
     # three frames enqueued and not waited for: the call drains them
     r = _mk(s, W, H, ts)
     r.write_state(plane)
@@ -521,12 +424,11 @@ def test_compaction_on_frame_paths(oracle):
 @pytest.mark.gpu
 def test_pick_after_compaction(oracle):
     """gs_pick needs a new frame after a compaction; its ids are then those of the compacted scene."""
-    import test_splat_state as tss
     from gsplat import _abi
     from pick_restate import restate_ref
     name, ts = "cfgA", 16
-    s, u, W, H = tss._scene(name)
-    plane = tss._hidden_plane(name, "centre_half_rect")
+    s, u, W, H = state_scene(name)
+    plane = hidden_plane(name, "centre_half_rect")
     ids = er.ids_of(plane, HID, 0)
     xy = np.array([(x, y) for y in range(3, H, 17) for x in range(5, W, 13)], np.uint32)
     r = _mk(s, W, H, ts)
@@ -535,9 +437,9 @@ def test_pick_after_compaction(oracle):
     r.wait()
     r.pick(xy)
     np.testing.assert_array_equal(r.delete_hidden(), ids)
-    assert _code(lambda: r.pick(xy))[0] == _abi.GS_ERR_NO_FRAME
-    assert _code(lambda: r.read_rgba8())[0] == _abi.GS_ERR_NO_FRAME
-    assert _code(lambda: r.read_buffer(_abi.GS_BUF_VALUES))[0] == _abi.GS_ERR_NO_FRAME
+    assert code_of(lambda: r.pick(xy))[0] == _abi.GS_ERR_NO_FRAME
+    assert code_of(lambda: r.read_rgba8())[0] == _abi.GS_ERR_NO_FRAME
+    assert code_of(lambda: r.read_buffer(_abi.GS_BUF_VALUES))[0] == _abi.GS_ERR_NO_FRAME
     r.render_uniforms(u)
     r.wait()
     ref = oracle.render(np.ascontiguousarray(s[ids]), u, W, H, ts)
@@ -551,11 +453,10 @@ def test_pick_after_compaction(oracle):
 
 @pytest.mark.gpu
 def test_export_ply(tmp_path):
-    import test_splat_state as tss
     from gsplat import _abi
     name, ts = "cfgA", 16
-    s, u, W, H = tss._scene(name)
-    plane = tss._hidden_plane(name, "every_third")
+    s, u, W, H = state_scene(name)
+    plane = hidden_plane(name, "every_third")
     ids = er.ids_of(plane, HID, 0)
     r = _mk(s, W, H, ts)
     r.write_state(plane)
@@ -587,7 +488,7 @@ def test_export_ply(tmp_path):
     r.destroy()
     # 70 001 records exported whole: a second chunk and a ragged last one
     n = 70001
-    big = np.tile(_records(10000), (8, 1))[:n].copy()
+    big = np.tile(special_records(10000), (8, 1))[:n].copy()
     big[:, 0] += np.arange(n, dtype=F)  # every record distinct
     b = _mk(big, 64, 64, 8, state=False)
     pb = str(tmp_path / "big.ply")
@@ -601,19 +502,15 @@ def test_export_ply(tmp_path):
 def test_node_host_export_matches_python(tmp_path):
     """tests/js/export_check.js hides, deletes, renders, exports and saves through the Node host: the ids, the image, the exported
     records and the file equal what the Python host makes of the same sequence, byte for byte."""
-    import test_splat_state as tss
-    s, u, W, H = tss._scene("cfgA")
+    s, u, W, H = state_scene("cfgA")
     n, ts = s.shape[0], 16
-    plane = tss._hidden_plane("cfgA", "every_third")
+    plane = hidden_plane("cfgA", "every_third")
     hide = np.flatnonzero(plane).astype(np.uint32)
     rec, ub, hb, out, ply, ply2 = (str(tmp_path / f) for f in ("rec.bin", "u.bin", "hide.bin", "out.bin", "node.ply", "node2.ply"))
     s.tofile(rec)
     np.ascontiguousarray(u, F).tofile(ub)
     hide.tofile(hb)
-    res = subprocess.run([NODE, os.path.join(ROOT, "tests", "js", "export_check.js")] + [str(a) for a in (rec, n, W, H, ts, ub, hb, out, ply, ply2)],
-                         capture_output=True, text=True, timeout=300)
-    assert res.returncode == 0, res.stderr
-    info = json.loads(res.stdout.strip().splitlines()[-1])
+    info = run_node("export_check.js", (rec, n, W, H, ts, ub, hb, out, ply, ply2))
     r = _mk(s, W, H, ts, exact=False)
     r.state_ids(hide, sr.SET, HID)
     listed = r.list_state(HID, 0)

@@ -1,26 +1,19 @@
 """The Node host (gaussian-splatting-wgpu_amd/js + the N-API addon): Camera / PackedGaussians parity
 with the Python mirror on CPU, and an end-to-end Renderer.animate() frame on the GPU."""
 import json
-import os
-import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import scene
+from support import NODE, run_node
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SCRIPT = os.path.join(ROOT, "tests", "js", "host_check.js")
-NODE = shutil.which("node")
 pytestmark = pytest.mark.skipif(NODE is None, reason="node is not installed")
 
 
 def _node(*args):
-    out = subprocess.run([NODE, SCRIPT] + [str(a) for a in args], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stderr
-    return json.loads(out.stdout.strip().splitlines()[-1])
+    return run_node("host_check.js", args)
 
 
 def test_camera_matches_python_mirror():

@@ -7,22 +7,14 @@ the GPU tests hold every field of every result, and every contributor record, to
 frames, every binning, emission order and frame path --, and prove that a pick disturbs nothing.
 """
 import ctypes
-import hashlib
-import json
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import scene
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden")
-HEADER = os.path.join(ROOT, "include", "gsplat", "gs_abi.h")
-F = np.float32
+from support import GOLDEN, NODE, c_layout, host_sources, lattice, mk, pick_case, run_node, timeless
 MARGIN = ("transmittance_edge", "live_box", "degenerate_conic")
 # (scene, tile size): config A at every tile size, the ragged golden, the three scenes of test_blend_culls.py, and a scene built
 # so that two accepted entries of a pixel have the SAME weight (the earliest must win; random scenes hold no such pixel)
@@ -33,80 +25,12 @@ MAX_CONTRIBS = (0, 4, 256)
 _CACHE = {}
 
 
-def _lattice(W, H, x0, dx, y0, dy):
-    return np.array([(x, y) for y in range(y0, H, dy) for x in range(x0, W, dx)], np.uint32)
-
-
-def _weight_ties_scene(oracle):
-    """16 pairs of splats centred on 16 pixels of a 64 x 64 canvas (pixel space, all at depth 1: list order = record order).  At
-    its centre pixel a splat has power = 0, so alpha is its opacity a.  The front splat of pair k gets an opacity a_k in
-    [0.26, 0.33) and the one behind it the f32 opacity b_k with fl(b_k fl(1 - a_k)) == a_k (one exists: b steps by one ulp, the
-    product by less than an ulp of a): the two weights a_k * 1 and b_k * T are then the same f32.  Returns (splats, uniforms, W, H,
-    centres); whether the ties came about is asserted on the restatement, not assumed."""
-    import test_blend_culls as tbc
-    W = H = 64
-    u = tbc.pixel_uniforms(W, H)
-
-    def opacities(logits):
-        s = tbc.make_splats(W, H, np.full(logits.size, 32.0), np.full(logits.size, 32.0), 4.0, 4.0, 0.0, logits)
-        return oracle.preprocess(s, u, W, H, 8)[0][:, 11].view(np.float32).copy()
-
-    cx = np.array([8 + 16 * i for j in range(4) for i in range(4)], np.float64)
-    cy = np.array([8 + 16 * j for j in range(4) for i in range(4)], np.float64)
-    la = tbc.opacity_logits(oracle, np.linspace(0.26, 0.33, 16))
-    a = opacities(la)
-    b = np.zeros_like(a)
-    for k in range(a.size):
-        c = F(a[k] / F(F(1.0) - a[k]))
-        near = [c]
-        for _ in range(4):
-            near = [np.nextafter(near[0], F(0.0), dtype=F)] + near + [np.nextafter(near[-1], F(2.0), dtype=F)]
-        hit = [v for v in near if F(v * F(F(1.0) - a[k])) == a[k]]
-        b[k] = hit[0] if hit else c
-    lb = tbc.opacity_logits(oracle, b.astype(np.float64))  # (the largest reachable opacity <= b: b itself for most pairs)
-    s = tbc.make_splats(W, H, np.repeat(cx, 2), np.repeat(cy, 2), 1.5, 1.5, 0.0, np.stack([la, lb], axis=1).ravel(),
-                        rng=np.random.default_rng(5))
-    return s, u, W, H, np.stack([cx, cy], axis=1).astype(np.uint32)
-
-
-def _case(oracle, name, ts):
-    """(splats, uniforms, W, H, oracle frame, query pixels) of one case."""
-    k = ("case", name, ts)
-    if k not in _CACHE:
-        if name == "cfgA":
-            from gpu_checks import orbit_uniforms
-            s, u, W, H = scene(10000), orbit_uniforms(256, 256), 256, 256
-            ref = oracle.render(s, u, W, H, ts)
-            xy = _lattice(W, H, 5, 13, 3, 17)
-        elif name == "ragged":
-            from gsplat import synth
-            z = np.load(os.path.join(GOLDEN, "ragged_3001_200x120_t8.npz"))
-            n, W, H, gts, _ = (int(v) for v in z["params"])
-            assert gts == ts
-            s, u = synth.bicycle_like(n), z["uniforms"]
-            gdata, _ = oracle.preprocess(s, u, W, H, ts)
-            assert hashlib.sha256(np.ascontiguousarray(gdata).tobytes()).hexdigest() == str(z["gdata_sha256"])
-            ref = {"gdata": gdata, "sorted_values": z["sorted_values"], "ranges": z["ranges"]}
-            xy = _lattice(W, H, 2, 7, 1, 5)
-        elif name == "weight_ties":
-            s, u, W, H, centres = _weight_ties_scene(oracle)
-            ref = oracle.render(s, u, W, H, ts)
-            xy = np.concatenate([centres, _lattice(W, H, 2, 7, 1, 5)])
-        else:
-            import test_blend_culls as tbc
-            s, u, W, H = tbc._scene(oracle, name)
-            ref = tbc._ref(oracle, name, ts)
-            xy = _lattice(W, H, 2, 7, 1, 5)
-        _CACHE[k] = (s, u, W, H, ref, xy)
-    return _CACHE[k]
-
-
 def _restated(oracle, name, ts):
     """The restatement of the case's queries with the largest max_contrib (a smaller one is its leading columns)."""
     from pick_restate import restate_ref
     k = ("restate", name, ts)
     if k not in _CACHE:
-        s, u, W, H, ref, xy = _case(oracle, name, ts)
+        s, u, W, H, ref, xy = pick_case(oracle, name, ts)
         _CACHE[k] = restate_ref(ref, W, H, ts, xy, max(MAX_CONTRIBS))
     return _CACHE[k]
 
@@ -124,7 +48,7 @@ def test_restatement_is_the_oracle(oracle, case):
     test_aux_planes.py), which applies EVERY entry of the list as written."""
     from aux_restate import restate_ref as planes
     name, ts = case
-    s, u, W, H, ref, xy = _case(oracle, name, ts)
+    s, u, W, H, ref, xy = pick_case(oracle, name, ts)
     res, con, _ = _restated(oracle, name, ts)
     _, A, D = planes(ref, W, H, ts)
     ys, xs = xy[:, 1].astype(np.int64), xy[:, 0].astype(np.int64)
@@ -177,15 +101,11 @@ def test_pick_abi(tmp_path):
     assert hasattr(L, "gs_pick") and "gs_pick" in _abi.ABI_SYMBOLS
     assert ctypes.sizeof(_abi.GsPickResult) == 48 and ctypes.sizeof(_abi.GsPickQuery) == 8 and ctypes.sizeof(_abi.GsPickContrib) == 8
     fields = [n for n, _ in _abi.GsPickResult._fields_]
-    prog = '#include <stdio.h>\n#include <stddef.h>\n#include "gsplat/gs_abi.h"\nint main(void){'
-    prog += 'printf("%zu %zu %zu", sizeof(gs_pick_result), sizeof(gs_pick_query), sizeof(gs_pick_contrib));'
+    prog = 'printf("%zu %zu %zu", sizeof(gs_pick_result), sizeof(gs_pick_query), sizeof(gs_pick_contrib));'
     prog += "".join('printf(" %%zu", offsetof(gs_pick_result, %s));' % n for n in fields)
     prog += 'printf(" %zu %zu %zu %zu", offsetof(gs_pick_query, x), offsetof(gs_pick_query, y), offsetof(gs_pick_contrib, id), offsetof(gs_pick_contrib, weight));'
-    prog += 'printf(" %u %u %u %u %u", GS_PICK_OK, GS_PICK_OUTSIDE_SLAB, GS_PICK_NONE, GS_PICK_MAX_QUERIES, GS_PICK_MAX_CONTRIB);return 0;}\n'
-    src, exe = tmp_path / "pick_layout.c", tmp_path / "pick_layout"
-    src.write_text(prog)
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    out = [int(x) for x in subprocess.check_output([str(exe)]).split()]
+    prog += 'printf(" %u %u %u %u %u", GS_PICK_OK, GS_PICK_OUTSIDE_SLAB, GS_PICK_NONE, GS_PICK_MAX_QUERIES, GS_PICK_MAX_CONTRIB);'
+    out = c_layout(tmp_path, "pick_layout", prog)
     assert out[:3] == [48, 8, 8]
     assert out[3:15] == [getattr(_abi.GsPickResult, n).offset for n in fields] == [4 * k for k in range(12)]
     assert out[15:19] == [_abi.GsPickQuery.x.offset, _abi.GsPickQuery.y.offset, _abi.GsPickContrib.id.offset, _abi.GsPickContrib.weight.offset]
@@ -199,20 +119,15 @@ def test_pick_abi(tmp_path):
             assert dt.fields[n][1] == getattr(_abi.GsPickResult, n).offset
             assert dt.fields[n][0] == (np.float32 if t is ctypes.c_float else np.uint32)
     assert _abi.PICK_CONTRIB_DTYPE == CONTRIB_DTYPE and CONTRIB_DTYPE.itemsize == 8
-    hdr = open(HEADER).read()
+    rjs, idx, dts, napi, hdr = host_sources()
     assert re.search(r"#define GS_ABI_VERSION 3\b", hdr) and "compute_tiles.wgsl:44-66" in hdr
-    js = os.path.join(ROOT, "gaussian-splatting-wgpu_amd", "js")
-    rjs = open(os.path.join(js, "renderer.js")).read()
     assert re.search(r"PICK = \{ OK: 0, OUTSIDE_SLAB: 1, NONE: 0xFFFFFFFF, MAX_QUERIES: 65536, MAX_CONTRIB: 256 \}", rjs)
-    idx = open(os.path.join(js, "index.js")).read()
     assert re.search(r"\bPICK\b", idx) and "OK: 0, OUTSIDE_SLAB: 1, NONE: 0xFFFFFFFF, MAX_QUERIES: 65536, MAX_CONTRIB: 256" in idx
-    dts = open(os.path.join(js, "index.d.ts")).read()
     assert "pick(queries: Uint32Array, maxContrib?: number): PickResult" in dts
     assert "OK: 0; OUTSIDE_SLAB: 1; NONE: 0xFFFFFFFF; MAX_QUERIES: 65536; MAX_CONTRIB: 256" in dts
     m = re.search(r"PICK_FIELD = \{([^}]*)\}", rjs)
     words = [int(v) for v in re.findall(r":\s*(\d+)", m.group(1))]
     assert words == list(range(12))  # the JS field table walks the record word by word, in the header's order
-    napi = open(os.path.join(ROOT, "gaussian-splatting-wgpu_amd", "csrc", "napi", "gs_napi.c")).read()
     for name in ("PICK_OK", "PICK_OUTSIDE_SLAB", "PICK_NONE", "PICK_MAX_QUERIES", "PICK_MAX_CONTRIB"):
         assert '"%s", GS_%s' % (name, name) in napi
     # no context: refused, with a message, before anything else is looked at
@@ -258,13 +173,6 @@ def test_merge_picks():
 
 
 # ---- GPU ----------------------------------------------------------------------------------------------------------------------
-def _mk(s, W, H, ts, exact, aux=False, cols=None, **kw):
-    from gpu_checks import make_renderer
-    from gsplat import _abi
-    flags = (_abi.GS_FLAG_EXACT_BLEND if exact else 0) | (_abi.GS_FLAG_AUX_OUTPUTS if aux else 0)
-    return make_renderer(s, W, H, ts, flags=flags, cols=cols, **kw)
-
-
 def _check(got, want, tight, cell, ref_len=None):
     """Every field bit-equal; list_length equal for the reference's binning, at most the reference's for tight lists."""
     res, con = got if isinstance(got, tuple) else (got, None)
@@ -295,9 +203,9 @@ def test_pick_bit_equal(oracle, case, exact):
     emission order and frame path rendered the frame."""
     from gsplat import _abi
     name, ts = case
-    s, u, W, H, ref, xy = _case(oracle, name, ts)
+    s, u, W, H, ref, xy = pick_case(oracle, name, ts)
     wres, wcon, _ = _restated(oracle, name, ts)
-    r = _mk(s, W, H, ts, exact=exact)
+    r = mk(s, W, H, ts, exact=exact)
     r.set_option(_abi.GS_OPT_FRAMES_IN_FLIGHT, 1)
     for tight, debug, order, graph in FRAME_PATHS:
         r.set_option(_abi.GS_OPT_TILE_CULL, tight)
@@ -321,11 +229,11 @@ def test_pick_agrees_with_the_planes_and_pick_rect(oracle):
     """AUX | EXACT: alpha and depth_acc of a whole-canvas pick equal read_alpha() / read_depth() bit for bit; every field of the
     65536 answers equals the restatement; pick_rect over the canvas is np.unique of the restatement's field."""
     from pick_restate import restate_ref
-    s, u, W, H, ref, _ = _case(oracle, "cfgA", 16)
+    s, u, W, H, ref, _ = pick_case(oracle, "cfgA", 16)
     yy, xx = np.meshgrid(np.arange(H, dtype=np.uint32), np.arange(W, dtype=np.uint32), indexing="ij")
     xy = np.stack([xx.ravel(), yy.ravel()], axis=1)
     assert xy.shape[0] == 65536
-    r = _mk(s, W, H, 16, exact=True, aux=True)
+    r = mk(s, W, H, 16, exact=True, aux=True)
     r.render_uniforms(u)
     r.wait()
     res = r.pick(xy)
@@ -348,29 +256,25 @@ def test_pick_agrees_with_the_planes_and_pick_rect(oracle):
     r.destroy()
 
 
-def _timeless(st):
-    return {k: v for k, v in st.items() if k not in ("frame_us", "frame_us_mean", "frames_timed", "stage_us", "stage_us_mean")}
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("graph", [0, 1])
 def test_pick_disturbs_nothing(oracle, graph):
     from gsplat import _abi, synth
-    s, _, W, H, _, xy = _case(oracle, "cfgA", 16)
+    s, _, W, H, _, xy = pick_case(oracle, "cfgA", 16)
     u0, u1 = (synth.orbit_camera(k, W, H).uniforms(W, H) for k in (2, 6))
-    a = _mk(s, W, H, 16, exact=False)  # picks between its frames
-    b = _mk(s, W, H, 16, exact=False)  # never picks
+    a = mk(s, W, H, 16, exact=False)  # picks between its frames
+    b = mk(s, W, H, 16, exact=False)  # never picks
     for r in (a, b):
         r.set_option(_abi.GS_OPT_FRAME_GRAPH, graph)
         r.set_option(_abi.GS_OPT_FRAMES_IN_FLIGHT, 1)
         r.render_uniforms(u0)
         r.wait()
-    before = (a.read_rgba8(), a.read_buffer(_abi.GS_BUF_VALUES), a.read_buffer(_abi.GS_BUF_RANGES), _timeless(a.stats()))
+    before = (a.read_rgba8(), a.read_buffer(_abi.GS_BUF_VALUES), a.read_buffer(_abi.GS_BUF_RANGES), timeless(a.stats()))
     first = a.pick(xy, 4)
     again = a.pick(xy, 4)  # a second pick: the same answer
     np.testing.assert_array_equal(_words(first[0]), _words(again[0]))
     np.testing.assert_array_equal(_words(first[1]), _words(again[1]))
-    after = (a.read_rgba8(), a.read_buffer(_abi.GS_BUF_VALUES), a.read_buffer(_abi.GS_BUF_RANGES), _timeless(a.stats()))
+    after = (a.read_rgba8(), a.read_buffer(_abi.GS_BUF_VALUES), a.read_buffer(_abi.GS_BUF_RANGES), timeless(a.stats()))
     for x, y in zip(before[:3], after[:3]):
         np.testing.assert_array_equal(x, y)
     assert before[3] == after[3]
@@ -382,7 +286,7 @@ def test_pick_disturbs_nothing(oracle, graph):
         np.testing.assert_array_equal(a.read_rgba8(), b.read_rgba8())
         np.testing.assert_array_equal(a.read_buffer(_abi.GS_BUF_RGB_F32), b.read_buffer(_abi.GS_BUF_RGB_F32))
         np.testing.assert_array_equal(a.read_buffer(_abi.GS_BUF_VALUES), b.read_buffer(_abi.GS_BUF_VALUES))
-        assert _timeless(a.stats()) == _timeless(b.stats())
+        assert timeless(a.stats()) == timeless(b.stats())
         assert a.stats()["graph_frames"] == (k + 2 if graph else 0)  # keeps counting up across the picks, as without them
     a.destroy()
     b.destroy()
@@ -396,13 +300,13 @@ def test_pick_ring_and_slabs(oracle):
     import gsplat
     W, H, ts = 256, 256, 16
     s = scene(10000)
-    xy = _lattice(W, H, 5, 13, 3, 17)
+    xy = lattice(W, H, 5, 13, 3, 17)
     us = [synth.orbit_camera(k, W, H).uniforms(W, H) for k in (1, 4, 7)]
     refs = [oracle.render(s, u, W, H, ts) for u in us]
     want = [restate(f["gdata"], f["sorted_values"], f["ranges"], W, H, ts, xy, 4)[:2] for f in refs]
     assert not np.array_equal(_words(want[0][0]), _words(want[2][0]))  # the cameras see different splats
     # three frames enqueued, no gs_wait: the pick waits for and answers the LAST one
-    r = _mk(s, W, H, ts, exact=False)
+    r = mk(s, W, H, ts, exact=False)
     for u in us:
         r.render_uniforms(u)
     got = r.pick(xy, 4)
@@ -416,7 +320,7 @@ def test_pick_ring_and_slabs(oracle):
         _check(p.pick(slot, xy, 4), want[k], True, "pipelined slot %d" % slot)
     p.destroy()
     # two slab contexts over one scene: each refuses the other's pixels; merged, they are the whole-canvas context's answer
-    whole = _mk(s, W, H, ts, exact=False)
+    whole = mk(s, W, H, ts, exact=False)
     whole.render_uniforms(us[1])
     full = whole.pick(xy)
     whole.destroy()
@@ -424,7 +328,7 @@ def test_pick_ring_and_slabs(oracle):
     ntx = W // ts
     parts = []
     for cols in ((0, 5), (5, ntx)):
-        sl = _mk(s, W, H, ts, exact=False, cols=cols)
+        sl = mk(s, W, H, ts, exact=False, cols=cols)
         sl.render_uniforms(us[1])
         res = sl.pick(xy)
         sl.destroy()
@@ -450,9 +354,9 @@ def test_pick_ring_and_slabs(oracle):
 @pytest.mark.gpu
 def test_pick_errors(oracle):
     from gsplat import _abi
-    s, u, W, H, ref, xy = _case(oracle, "ragged", 8)
+    s, u, W, H, ref, xy = pick_case(oracle, "ragged", 8)
     wres, wcon, _ = _restated(oracle, "ragged", 8)
-    r = _mk(s, W, H, 8, exact=True)
+    r = mk(s, W, H, 8, exact=True)
     L = _abi.load()
 
     def code(fn):
@@ -490,7 +394,7 @@ def test_pick_errors(oracle):
     np.testing.assert_array_equal(r.read_rgba8(), np.load(os.path.join(GOLDEN, "ragged_3001_200x120_t8.npz"))["rgba8"])
     _check(r.pick(xy, 4), (wres, wcon), False, "a frame after the errors")
     # a new upload takes the frame away again
-    r2 = _mk(s, W, H, 8, exact=True)
+    r2 = mk(s, W, H, 8, exact=True)
     r2.render_uniforms(u)
     r2.wait()
     arr = np.ascontiguousarray(s, dtype=np.float32)
@@ -500,9 +404,6 @@ def test_pick_errors(oracle):
     r.destroy()
 
 
-NODE = shutil.which("node")
-
-
 @pytest.mark.gpu
 @pytest.mark.skipif(NODE is None, reason="node is not installed")
 def test_node_host_pick_matches_python(tmp_path):
@@ -510,16 +411,13 @@ def test_node_host_pick_matches_python(tmp_path):
     n, W, H, ts, mc = 8000, 200, 120, 16, 4
     s = scene(n)
     u = synth.orbit_camera(4, W, H).uniforms(W, H)
-    xy = _lattice(W, H, 3, 11, 2, 7)
+    xy = lattice(W, H, 3, 11, 2, 7)
     rec, ub, qb, out = (str(tmp_path / f) for f in ("rec.bin", "u.bin", "q.bin", "pick.bin"))
     s.tofile(rec)
     u.tofile(ub)
     np.ascontiguousarray(xy, np.uint32).tofile(qb)
-    res = subprocess.run([NODE, os.path.join(ROOT, "tests", "js", "pick_check.js")] + [str(a) for a in (rec, n, W, H, ts, ub, qb, mc, out)],
-                         capture_output=True, text=True, timeout=300)
-    assert res.returncode == 0, res.stderr
-    info = json.loads(res.stdout.strip().splitlines()[-1])
-    r = _mk(s, W, H, ts, exact=False)
+    info = run_node("pick_check.js", (rec, n, W, H, ts, ub, qb, mc, out))
+    r = mk(s, W, H, ts, exact=False)
     r.render_uniforms(u)
     r.wait()
     pres, pcon = r.pick(xy, mc)

@@ -9,75 +9,22 @@ context with the flag and an all-zero plane renders what a context without it re
 gpu_checks.check_image for the fused blend, used as it stands.
 """
 import ctypes
-import json
-import os
+import functools
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import scene
 import state_restate as sr
+from support import F, FRAME_CASES, NODE, c_layout, hidden_plane, host_sources, in_region, mk, run_node, state_ref, state_scene, timeless
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden")
-HEADER = os.path.join(ROOT, "include", "gsplat", "gs_abi.h")
-F = np.float32
-NODE = shutil.which("node")
+_mk = functools.partial(mk, exact=True, state=True)
 
 # matched splats per region, checked on the CPU when the feature was specified
 EXPECTED = {"cfgA": {"centre_half_rect": 2394, "strip": 441, "sphere_r1": 489, "sphere_r075": 214, "box": 615, "mask": 1280},
             "ragged": {"centre_half_rect": 477, "strip": 118, "sphere_r1": 144, "sphere_r075": 67, "box": 189, "mask": 158}}
-FRAME_CASES = [("cfgA", 8), ("cfgA", 16), ("cfgA", 32), ("ragged", 8)]
 FRAME_IDS = ["%s-t%d" % c for c in FRAME_CASES]
 HIDDEN_SETS = ("every_third", "centre_half_rect", "all")
-_CACHE = {}
-
-
-def _scene(name):
-    """(splats, uniforms, W, H)"""
-    if name not in _CACHE:
-        if name == "cfgA":
-            from gpu_checks import orbit_uniforms
-            _CACHE[name] = (scene(10000), orbit_uniforms(256, 256), 256, 256)
-        else:
-            from gsplat import synth
-            z = np.load(os.path.join(GOLDEN, "ragged_3001_200x120_t8.npz"))
-            n, W, H, _, _ = (int(v) for v in z["params"])
-            _CACHE[name] = (synth.bicycle_like(n), np.array(z["uniforms"], F), W, H)
-    return _CACHE[name]
-
-
-def _inside(name, region):
-    k = ("inside", name, region)
-    if k not in _CACHE:
-        s, u, W, H = _scene(name)
-        kind, kw = sr.issue_regions(W, H, u)[region]
-        _CACHE[k] = sr.member(kind, s, W, H, **kw)
-    return _CACHE[k]
-
-
-def _hidden_plane(name, which):
-    s, _, _, _ = _scene(name)
-    n = s.shape[0]
-    if which == "every_third":
-        h = np.arange(n) % 3 == 1
-    elif which == "centre_half_rect":
-        h = _inside(name, "centre_half_rect")
-    else:
-        h = np.ones(n, bool)
-    return np.where(h, sr.HIDDEN, 0).astype(np.uint8)
-
-
-def _ref(oracle, name, ts, key, state, tint=sr.TINT_DEFAULT, cols=None):
-    """The constructed reference frame, computed once per (scene, tile size, plane) and shared."""
-    k = ("ref", name, ts, key, tint, cols)
-    if k not in _CACHE:
-        s, u, W, H = _scene(name)
-        _CACHE[k] = sr.state_frame(oracle, s, u, W, H, ts, state, tint, cols, want_illcond=True)
-    return _CACHE[k]
 
 
 # ---- CPU --------------------------------------------------------------------------------------------------------------------------
@@ -93,13 +40,10 @@ def test_state_abi(tmp_path):
     consts = ["GS_FLAG_SPLAT_STATE", "GS_BUF_SPLAT_STATE", "GS_OPT_SELECT_TINT", "GS_SPLAT_HIDDEN", "GS_SPLAT_SELECTED", "GS_STATE_SET",
               "GS_STATE_CLEAR", "GS_STATE_TOGGLE", "GS_STATE_ASSIGN", "GS_REGION_ALL", "GS_REGION_SPHERE", "GS_REGION_BOX",
               "GS_REGION_SCREEN_RECT", "GS_REGION_SCREEN_MASK", "GS_ABI_VERSION"]
-    prog = '#include <stdio.h>\n#include <stddef.h>\n#include "gsplat/gs_abi.h"\nint main(void){printf("%zu", sizeof(gs_region));'
+    prog = 'printf("%zu", sizeof(gs_region));'
     prog += "".join('printf(" %%zu", offsetof(gs_region, %s));' % n for n in fields)
-    prog += "".join('printf(" %%u", (unsigned)%s);' % c for c in consts) + "return 0;}\n"
-    src, exe = tmp_path / "state_layout.c", tmp_path / "state_layout"
-    src.write_text(prog)
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    out = [int(x) for x in subprocess.check_output([str(exe)]).split()]
+    prog += "".join('printf(" %%u", (unsigned)%s);' % c for c in consts)
+    out = c_layout(tmp_path, "state_layout", prog)
     assert out[0] == ctypes.sizeof(_abi.GsRegion) == 72
     assert out[1:1 + len(fields)] == [getattr(_abi.GsRegion, n).offset for n in fields]
     got = out[1 + len(fields):]
@@ -107,21 +51,16 @@ def test_state_abi(tmp_path):
     assert got[:-1] == [getattr(_abi, c) for c in consts[:-1]]
     assert [sr.HIDDEN, sr.SELECTED, sr.SET, sr.CLEAR, sr.TOGGLE, sr.ASSIGN, sr.ALL, sr.SPHERE, sr.BOX, sr.RECT, sr.MASK] == got[3:14]
     assert _abi.GS_SELECT_TINT_DEFAULT == sr.TINT_DEFAULT == 0x80FFFF00
-    hdr = open(HEADER).read()
+    rjs, idx, dts, napi, hdr = host_sources()
     assert re.search(r"#define GS_ABI_VERSION 3\b", hdr) and "default 0x80FFFF00" in hdr and "no counterpart" in hdr
-    js = os.path.join(ROOT, "gaussian-splatting-wgpu_amd", "js")
-    rjs = open(os.path.join(js, "renderer.js")).read()
     assert "STATE = { HIDDEN: 0x1, SELECTED: 0x2, SET: 1, CLEAR: 2, TOGGLE: 3, ASSIGN: 4 }" in rjs
     assert "REGION = { ALL: 0, SPHERE: 1, BOX: 2, SCREEN_RECT: 3, SCREEN_MASK: 4 }" in rjs
-    idx = open(os.path.join(js, "index.js")).read()
     assert re.search(r"\bSTATE, REGION\b", idx) and re.search(r"SPLAT_STATE: 15\b", idx) and re.search(r"SPLAT_STATE: 0x10\b", idx)
     assert re.search(r"SELECT_TINT: 11\b", idx)
-    dts = open(os.path.join(js, "index.d.ts")).read()
     assert "HIDDEN: 0x1; SELECTED: 0x2; SET: 1; CLEAR: 2; TOGGLE: 3; ASSIGN: 4" in dts
     assert "ALL: 0; SPHERE: 1; BOX: 2; SCREEN_RECT: 3; SCREEN_MASK: 4" in dts
     for m in ("stateRegion(", "stateIds(", "stateCount(", "readState(", "writeState("):
         assert m in dts and m in rjs
-    napi = open(os.path.join(ROOT, "gaussian-splatting-wgpu_amd", "csrc", "napi", "gs_napi.c")).read()
     for name in ("stateRegion", "stateIds", "stateCount", "readState", "writeState"):
         assert '{"%s", js_' % name in napi
     for name in ("FLAG_SPLAT_STATE", "BUF_SPLAT_STATE", "OPT_SELECT_TINT"):
@@ -142,7 +81,7 @@ def test_state_abi(tmp_path):
 @pytest.mark.parametrize("name,ts,count", [("cfgA", 16, 5813), ("ragged", 8, 1347)])
 def test_restated_projection_is_the_oracles(oracle, name, ts, count):
     """uv of the restatement is bit-equal to words 0 and 1 of the oracle's GaussianData for every splat with a count."""
-    s, u, W, H = _scene(name)
+    s, u, W, H = state_scene(name)
     gdata, counts = oracle.preprocess(s, u, W, H, ts)
     uvx, uvy, px, py, _ = sr.project(s, u, W, H)
     vis = counts > 0
@@ -157,9 +96,9 @@ def test_restated_projection_is_the_oracles(oracle, name, ts, count):
 def test_frame_construction_is_right(oracle, name, ts):
     """Hidden = i % 3 == 1: the constructed frame's f32 image is bit-equal to the oracle's frame of the scene with those records
     REMOVED (another route to the same pixels: the ids differ, the image cannot), and differs from the full frame."""
-    s, u, W, H = _scene(name)
-    state = _hidden_plane(name, "every_third")
-    fr = _ref(oracle, name, ts, "every_third", state)
+    s, u, W, H = state_scene(name)
+    state = hidden_plane(name, "every_third")
+    fr = state_ref(oracle, name, ts, "every_third", state)
     removed = oracle.render(s[state == 0], u, W, H, ts)
     np.testing.assert_array_equal(fr["rgbf"].view(np.uint32), removed["rgbf"].view(np.uint32))
     np.testing.assert_array_equal(fr["rgba8"], removed["rgba8"])
@@ -168,7 +107,7 @@ def test_frame_construction_is_right(oracle, name, ts):
     print("\n%s: %d pixels change against the full frame" % (name, changed))
     assert changed > W * H // 10
     # a selected splat changes the frame too, and a = 0 does not
-    sel = np.where(_inside(name, "centre_half_rect"), sr.SELECTED, 0).astype(np.uint8)
+    sel = np.where(in_region(name, "centre_half_rect"), sr.SELECTED, 0).astype(np.uint8)
     tinted = sr.state_frame(oracle, s, u, W, H, ts, sel)
     assert (tinted["rgbf"].view(np.uint32) != full["rgbf"].view(np.uint32)).any()
     untinted = sr.state_frame(oracle, s, u, W, H, ts, sel, tint=0x00FF00FF)
@@ -180,9 +119,9 @@ def test_frame_construction_is_right(oracle, name, ts):
 def test_regions_are_non_trivial(name):
     """Every region matches the number of splats it was specified with: more than 1 % and less than 50 % of N, so a kernel that
     matches nothing or everything cannot pass."""
-    s, u, W, H = _scene(name)
+    s, u, W, H = state_scene(name)
     n = s.shape[0]
-    got = {r: int(_inside(name, r).sum()) for r in sr.issue_regions(W, H, u)}
+    got = {r: int(in_region(name, r).sum()) for r in sr.issue_regions(W, H, u)}
     print("\n%s: %s" % (name, got))
     assert got == EXPECTED[name]
     for r, m in got.items():
@@ -206,22 +145,15 @@ def test_restated_operations():
 
 
 # ---- GPU --------------------------------------------------------------------------------------------------------------------------
-def _mk(s, W, H, ts, exact=True, state=True, cols=None, flags=0, **kw):
-    from gpu_checks import make_renderer
-    from gsplat import _abi
-    fl = flags | (_abi.GS_FLAG_EXACT_BLEND if exact else 0) | (_abi.GS_FLAG_SPLAT_STATE if state else 0)
-    return make_renderer(s, W, H, ts, flags=fl, cols=cols, **kw)
-
-
 def _kernel_scene(n):
     """(splats, uniforms, W, H) with n splats: the two issue scenes, and for 1 and 5 a few of config A's splats, members and
     non-members of the regions alternating."""
     if n == 10000:
-        return _scene("cfgA")
+        return state_scene("cfgA")
     if n == 3001:
-        return _scene("ragged")
-    s, u, W, H = _scene("cfgA")
-    inr = _inside("cfgA", "centre_half_rect") & _inside("cfgA", "box")
+        return state_scene("ragged")
+    s, u, W, H = state_scene("cfgA")
+    inr = in_region("cfgA", "centre_half_rect") & in_region("cfgA", "box")
     pick = np.stack([np.flatnonzero(inr)[:n], np.flatnonzero(~inr)[:n]], axis=1).ravel()[:n]
     return np.ascontiguousarray(s[pick]), u, W, H
 
@@ -323,7 +255,7 @@ def test_state_kernels(n):
 def test_state_errors():
     """Every refused call leaves the plane as it was; a context without the flag refuses every call, the tap and the option."""
     from gsplat import _abi
-    s, u, W, H = _scene("ragged")
+    s, u, W, H = state_scene("ragged")
     n = s.shape[0]
     L = _abi.load()
     r = _mk(s, W, H, 8)
@@ -409,9 +341,9 @@ def test_hidden_frames(oracle, case, hidden):
     from gpu_checks import check_image, check_stages
     from gsplat import _abi
     name, ts = case
-    s, u, W, H = _scene(name)
-    state = _hidden_plane(name, hidden)
-    ref = _ref(oracle, name, ts, hidden, state)
+    s, u, W, H = state_scene(name)
+    state = hidden_plane(name, hidden)
+    ref = state_ref(oracle, name, ts, hidden, state)
     if hidden == "all":
         assert ref["num_intersections"] == 0 and not ref["rgba8"][..., :3].any()
     r = _mk(s, W, H, ts, exact=True)
@@ -446,9 +378,9 @@ def test_hidden_frames_on_slabs(oracle, cols):
     from gpu_checks import check_stages
     from gsplat import _abi
     name, ts = "cfgA", 16
-    s, u, W, H = _scene(name)
-    state = _hidden_plane(name, "every_third")
-    ref = _ref(oracle, name, ts, "every_third", state, cols=cols)
+    s, u, W, H = state_scene(name)
+    state = hidden_plane(name, "every_third")
+    ref = state_ref(oracle, name, ts, "every_third", state, cols=cols)
     r = _mk(s, W, H, ts, exact=True, cols=cols)
     r.write_state(state)
     r.render_uniforms(u, debug=True)
@@ -467,7 +399,7 @@ def test_hidden_frames_on_slabs(oracle, cols):
 
 def _tint_plane(name):
     """selected = the centre-half rect, hidden = every third: some splats are both."""
-    state = _hidden_plane(name, "every_third") | np.where(_inside(name, "centre_half_rect"), sr.SELECTED, 0).astype(np.uint8)
+    state = hidden_plane(name, "every_third") | np.where(in_region(name, "centre_half_rect"), sr.SELECTED, 0).astype(np.uint8)
     assert ((state & 3) == 3).any() and ((state & 3) == 2).any()
     return state
 
@@ -479,7 +411,7 @@ def test_tint(oracle):
     from gpu_checks import check_stages
     from gsplat import _abi
     name, ts = "cfgA", 16
-    s, u, W, H = _scene(name)
+    s, u, W, H = state_scene(name)
     state = _tint_plane(name)
     r = _mk(s, W, H, ts, exact=True)
     r.set_option(_abi.GS_OPT_FRAMES_IN_FLIGHT, 1)
@@ -489,7 +421,7 @@ def test_tint(oracle):
         if tint is not None:
             r.set_option(_abi.GS_OPT_SELECT_TINT, tint)
         t = sr.TINT_DEFAULT if tint is None else tint
-        ref = _ref(oracle, name, ts, "tint", state, tint=t)
+        ref = state_ref(oracle, name, ts, "tint", state, tint=t)
         r.render_uniforms(u, debug=True)
         r.wait()
         check_stages(r, ref, True, debug=True)
@@ -499,14 +431,10 @@ def test_tint(oracle):
         vals = r.read_buffer(_abi.GS_BUF_VALUES)
         assert not (state[vals] & sr.HIDDEN).any() and (state[vals] & sr.SELECTED).any()
         frames[t] = ref["rgbf"]
-    untinted = _ref(oracle, name, ts, "every_third", _hidden_plane(name, "every_third"))
+    untinted = state_ref(oracle, name, ts, "every_third", hidden_plane(name, "every_third"))
     np.testing.assert_array_equal(frames[0x00FF00FF].view(np.uint32), untinted["rgbf"].view(np.uint32))
     assert (frames[sr.TINT_DEFAULT] != untinted["rgbf"]).any() and (frames[0xC03380E6] != frames[sr.TINT_DEFAULT]).any()
     r.destroy()
-
-
-def _timeless(st):
-    return {k: v for k, v in st.items() if k not in ("frame_us", "frame_us_mean", "frames_timed", "stage_us", "stage_us_mean")}
 
 
 @pytest.mark.gpu
@@ -515,7 +443,7 @@ def test_nothing_changes_by_default(ts):
     """A context with the flag and an all-zero plane renders what a context without it renders: image, f32 tap, lists, ranges,
     counts and statistics, on the product path and on gs_render_debug."""
     from gsplat import _abi, synth
-    s, _, W, H = _scene("cfgA")
+    s, _, W, H = state_scene("cfgA")
     a = _mk(s, W, H, ts, exact=False, state=True)
     b = _mk(s, W, H, ts, exact=False, state=False)
     for k, debug in ((2, False), (6, False), (3, True)):
@@ -528,7 +456,7 @@ def test_nothing_changes_by_default(ts):
             np.testing.assert_array_equal(a.read_buffer(which), b.read_buffer(which), err_msg=str(which))
         if debug:
             np.testing.assert_array_equal(a.read_buffer(_abi.GS_BUF_GAUSSIAN_DATA), b.read_buffer(_abi.GS_BUF_GAUSSIAN_DATA))
-        assert _timeless(a.stats()) == _timeless(b.stats())
+        assert timeless(a.stats()) == timeless(b.stats())
     assert not a.read_state().any()
     a.destroy()
     b.destroy()
@@ -541,8 +469,8 @@ def test_frame_paths(oracle):
     from gpu_checks import check_image
     from gsplat import _abi
     name, ts = "cfgA", 16
-    s, u, W, H = _scene(name)
-    planes = [("every_third", _hidden_plane(name, "every_third")), ("centre_half_rect", _hidden_plane(name, "centre_half_rect")),
+    s, u, W, H = state_scene(name)
+    planes = [("every_third", hidden_plane(name, "every_third")), ("centre_half_rect", hidden_plane(name, "centre_half_rect")),
               ("tint", _tint_plane(name))]
     # three frames in flight, the state edited between the batches (the call drains the ring itself)
     r = _mk(s, W, H, ts, exact=True)
@@ -550,7 +478,7 @@ def test_frame_paths(oracle):
         r.write_state(plane)
         for _ in range(3):
             r.render_uniforms(u)
-        check_image(r, _ref(oracle, name, ts, key, plane), True)
+        check_image(r, state_ref(oracle, name, ts, key, plane), True)
     assert r.stats()["frames_in_flight"] == 3 and r.stats()["frames"] == 9
     r.destroy()
     # the frame graph: capture, edit the state and replay, change the tint and replay
@@ -567,12 +495,12 @@ def test_frame_paths(oracle):
             g.render_uniforms(u)
             g.wait()
             frames += 1
-            check_image(g, _ref(oracle, name, ts, key, plane, tint=sr.TINT_DEFAULT if tint is None else tint), True)
+            check_image(g, state_ref(oracle, name, ts, key, plane, tint=sr.TINT_DEFAULT if tint is None else tint), True)
             assert g.stats()["graph_frames"] == frames
     # a state call is not a frame: taps and statistics still describe what was rendered
-    before = (g.read_rgba8(), g.read_buffer(_abi.GS_BUF_VALUES), _timeless(g.stats()))
+    before = (g.read_rgba8(), g.read_buffer(_abi.GS_BUF_VALUES), timeless(g.stats()))
     g.state_region(sr.ALL, sr.ASSIGN, sr.HIDDEN)
-    after = (g.read_rgba8(), g.read_buffer(_abi.GS_BUF_VALUES), _timeless(g.stats()))
+    after = (g.read_rgba8(), g.read_buffer(_abi.GS_BUF_VALUES), timeless(g.stats()))
     np.testing.assert_array_equal(before[0], after[0])
     np.testing.assert_array_equal(before[1], after[1])
     assert before[2] == after[2]
@@ -594,7 +522,7 @@ def test_frame_paths(oracle):
         slots = [p.render_uniforms(u) for _ in range(2)]
         for slot in slots:
             p.wait(slot)
-            check_image(p.renderers[slot], _ref(oracle, name, ts, key, plane), True)
+            check_image(p.renderers[slot], state_ref(oracle, name, ts, key, plane), True)
     assert p.select_sphere((0.0, 0.0, 0.0), 1.0) == EXPECTED[name]["sphere_r1"]
     assert p.state_count(sr.SELECTED, sr.SELECTED) == p.renderers[1].state_count(sr.SELECTED, sr.SELECTED) == EXPECTED[name]["sphere_r1"]
     p.destroy()
@@ -607,14 +535,14 @@ def test_pick_after_hiding(oracle, exact):
     the constructed reference, and no hidden id appears in any field or contributor slot."""
     from pick_restate import restate_ref
     name, ts = "cfgA", 16
-    s, u, W, H = _scene(name)
+    s, u, W, H = state_scene(name)
     xy = np.array([(x, y) for y in range(3, H, 17) for x in range(5, W, 13)], np.uint32)
     r = _mk(s, W, H, ts, exact=exact)
     assert r.select_rect(W // 4, H // 4, 3 * W // 4, 3 * H // 4, u) == EXPECTED[name]["centre_half_rect"]
     assert r.hide_selected() == EXPECTED[name]["centre_half_rect"]
     state = r.read_state()
-    np.testing.assert_array_equal(state, np.where(_inside(name, "centre_half_rect"), 3, 0).astype(np.uint8))
-    ref = _ref(oracle, name, ts, "hidden_selected", state)
+    np.testing.assert_array_equal(state, np.where(in_region(name, "centre_half_rect"), 3, 0).astype(np.uint8))
+    ref = state_ref(oracle, name, ts, "hidden_selected", state)
     wres, wcon, _ = restate_ref(ref, W, H, ts, xy, 8)
     r.render_uniforms(u)
     r.wait()
@@ -637,7 +565,7 @@ def test_node_host_state_matches_python(tmp_path):
     """tests/js/state_check.js runs a short sequence through the Node host and writes the plane and a frame: both equal what the
     Python host makes of the same sequence, byte for byte."""
     from gsplat import _abi
-    s, u, W, H = _scene("ragged")
+    s, u, W, H = state_scene("ragged")
     n, ts = s.shape[0], 8
     mask = sr.issue_mask(W, H)
     ids = np.array([5, 5, 9, 2999, 3000, 17, 5], np.uint32)
@@ -646,10 +574,7 @@ def test_node_host_state_matches_python(tmp_path):
     np.ascontiguousarray(u, F).tofile(ub)
     mask.tofile(mb)
     ids.tofile(ib)
-    res = subprocess.run([NODE, os.path.join(ROOT, "tests", "js", "state_check.js")] + [str(a) for a in (rec, n, W, H, ts, ub, mb, ib, out)],
-                         capture_output=True, text=True, timeout=300)
-    assert res.returncode == 0, res.stderr
-    info = json.loads(res.stdout.strip().splitlines()[-1])
+    info = run_node("state_check.js", (rec, n, W, H, ts, ub, mb, ib, out))
     r = _mk(s, W, H, ts, exact=False)
     m = [r.state_region(sr.RECT, sr.SET, sr.SELECTED, rect=(W // 4, H // 4, 3 * W // 4, 3 * H // 4), uniforms=u),
          r.state_region(sr.MASK, sr.SET, 0x10, where=(sr.SELECTED, 0), mask=mask, uniforms=u),
@@ -676,3 +601,107 @@ def test_node_host_state_matches_python(tmp_path):
     np.testing.assert_array_equal(raw[n + W * H * 4:].reshape(H, W, 4), img0)  # after writeState(zeros): the plain frame
     assert (img != img0).any() and plane.any()
     assert info["errors"] == {"badId": "-1", "unflagged": "-1", "notTyped": "TypeError"}
+
+
+def _outcome(fn):
+    """What a call gives: its value, or the code and message of the GsError it raises."""
+    from gsplat import _abi
+    try:
+        return ("value", fn())
+    except _abi.GsError as e:
+        return ("error", e.code, str(e))
+
+
+def _assert_same(a, b, what):
+    assert type(a) is type(b), what
+    if isinstance(a, tuple):
+        assert len(a) == len(b), what
+        for k, (x, y) in enumerate(zip(a, b)):
+            _assert_same(x, y, "%s[%d]" % (what, k))
+    elif isinstance(a, np.ndarray):
+        assert a.dtype == b.dtype, what
+        np.testing.assert_array_equal(a.view(np.uint8), b.view(np.uint8), err_msg=what)  # floats compared as bits
+    else:
+        assert a == b, what
+
+
+@pytest.mark.gpu
+def test_pipelined_forwards_reach_the_owner(tmp_path):
+    """Every call PipelinedRenderer forwards to the owner of the splats, made while each of its two slots holds a frame nobody
+    waited for: the slots are drained, and the return value and the plane afterwards are those of a lone Renderer given the same
+    frames and calls.  The four per-slot calls answer what the slot's own renderer answers."""
+    import gsplat
+    from gsplat import _abi
+    from gpu_checks import orbit_uniforms
+    s, W, H, ts = np.ascontiguousarray(state_scene("cfgA")[0][:64]), 64, 64, 8
+    u = orbit_uniforms(W, H)
+    flags = _abi.GS_FLAG_EXACT_BLEND | _abi.GS_FLAG_F32_TAP | _abi.GS_FLAG_SPLAT_STATE
+    p = gsplat.PipelinedRenderer(gsplat.Canvas(W, H), None, 0, gsplat.PackedGaussians(s), ts, frames_in_flight=2, flags=flags)
+    lone = gsplat.Renderer(gsplat.Canvas(W, H), None, 0, gsplat.PackedGaussians(s), ts, flags=flags)
+    SEL, HID = sr.SELECTED, sr.HIDDEN
+    mask = sr.issue_mask(W, H)
+    snap = {}
+    turn = _abi.compose_xform(rot=(0.9, 0.1, -0.2, 0.3), translate=(0.01, 0.0, -0.02), scale=1.25, pivot=(0.1, 0.2, 0.3))
+    ply = lambda r: str(tmp_path / ("lone.ply" if r is lone else "ring.ply"))  # noqa: E731
+    calls = [
+        ("select_sphere", lambda r: r.select_sphere((0.0, 0.0, 0.0), 2.0)),
+        ("state_count", lambda r: r.state_count(SEL, SEL)),
+        ("state_ids", lambda r: r.state_ids(np.array([1, 2, 2, 63], np.uint32), sr.SET, 0x10)),
+        ("read_state", lambda r: snap.setdefault(id(r), r.read_state())),
+        ("state_region", lambda r: r.state_region(sr.ALL, sr.TOGGLE, 0x20, (0x10, 0x10))),
+        ("write_state", lambda r: r.write_state(snap[id(r)])),
+        ("select_box", lambda r: r.select_box((-2.0, -1.0, -2.0), (1.0, 2.0, 3.0), op=sr.TOGGLE)),
+        ("select_rect", lambda r: r.select_rect(8, 8, 56, 40, u, op=sr.SET)),
+        ("select_mask", lambda r: r.select_mask(mask, u, op=sr.TOGGLE)),
+        ("list_state", lambda r: r.list_state(SEL, SEL)),
+        ("export_splats", lambda r: r.export_splats(SEL, SEL, with_ids=True)),
+        ("translate_selected", lambda r: r.translate_selected((0.05, -0.02, 0.01))),
+        ("rotate_selected", lambda r: r.rotate_selected((0.8, 0.0, 0.6, 0.0), pivot=(0.0, 0.1, 0.0))),
+        ("scale_selected", lambda r: r.scale_selected(0.9)),
+        ("transform", lambda r: r.transform(turn, 0x10, 0x10)),
+        ("export_splats", lambda r: r.export_splats()),
+        ("reset_coverage", lambda r: r.reset_coverage()),
+        ("accumulate_coverage", lambda r: r.accumulate_coverage((4, 4, 60, 50), mask)),
+        ("read_coverage", lambda r: r.read_coverage()),
+        ("state_coverage", lambda r: r.state_coverage(sr.SET, 0x40, min_hits=2)),
+        ("select_visible", lambda r: r.select_visible((0, 0, 32, 64))),
+        ("hide_unseen", lambda r: r.hide_unseen()),
+        ("hide_selected", lambda r: r.hide_selected()),
+        ("save_ply", lambda r: (r.save_ply(ply(r), HID, 0, sh_degree=1), np.fromfile(ply(r), np.uint8))),
+        ("unhide_all", lambda r: r.unhide_all()),
+        ("clear_selection", lambda r: r.clear_selection()),
+    ]
+    owner_calls = {"state_region", "state_ids", "state_count", "read_state", "write_state", "select_rect", "select_mask", "select_sphere",
+                   "select_box", "clear_selection", "hide_selected", "unhide_all", "accumulate_coverage", "reset_coverage", "read_coverage",
+                   "state_coverage", "select_visible", "hide_unseen", "list_state", "export_splats", "save_ply", "transform",
+                   "translate_selected", "rotate_selected", "scale_selected"}
+    assert {name for name, _ in calls} == owner_calls
+    moved = 0
+    for name, call in calls:
+        for _ in range(2):  # a frame on each slot, in flight when the call comes
+            p.render_uniforms(u)
+            lone.render_uniforms(u)
+        assert p._busy == [True, True]
+        before = lone.read_state()
+        got, want = call(p), call(lone)
+        assert p._busy == [False, False], name  # every slot was drained before the owner was asked
+        _assert_same(got, want, name)
+        np.testing.assert_array_equal(p.read_state(), lone.read_state(), err_msg="plane after " + name)
+        moved += int(not np.array_equal(before, lone.read_state()))
+    assert moved >= 8  # the calls move the plane
+    # the per-slot calls: the slot is waited for, then its own renderer answers
+    xy = np.array([(x, y) for y in range(3, H, 11) for x in range(5, W, 7)], np.uint32)
+    for name, via_ring, direct, ok in (("read_rgba8", lambda k: p.read_rgba8(k), lambda r: r.read_rgba8(), True),
+                                       ("pick", lambda k: p.pick(k, xy, 4), lambda r: r.pick(xy, 4), True),
+                                       ("read_alpha", lambda k: p.read_alpha(k), lambda r: r.read_alpha(), False),  # (no GS_FLAG_AUX_OUTPUTS)
+                                       ("read_depth", lambda k: p.read_depth(k, normalized=True), lambda r: r.read_depth(normalized=True), False)):
+        slots = [p.render_uniforms(u) for _ in range(2)]
+        for slot in slots:
+            assert p._busy[slot]
+            got = _outcome(lambda: via_ring(slot))
+            assert not p._busy[slot], name
+            _assert_same(got, _outcome(lambda: direct(p.renderers[slot])), name)
+            assert got[0] == ("value" if ok else "error"), (name, got)
+    assert p.read_rgba8(slots[0])[..., :3].any()
+    p.destroy()
+    lone.destroy()

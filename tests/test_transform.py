@@ -12,9 +12,8 @@ everywhere else -- every float of an unflagged part, every non-matching record -
 payload must survive.
 """
 import ctypes
-import json
+import functools
 import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -24,12 +23,11 @@ from conftest import scene
 import export_restate as er
 import state_restate as sr
 import xform_restate as xr
+from support import (F, NODE, ROOT, TAPS, c_layout, code_of, frame_taps, host_sources, in_region, mk, raw_export, run_node, special_records,
+                     state_scene)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "gsplat", "gs_abi.h")
 CSRC = os.path.join(ROOT, "gaussian-splatting-wgpu_amd", "csrc")
-F = np.float32
-NODE = shutil.which("node")
+_mk = functools.partial(mk, exact=True, state=True)
 HID, SEL = er.HIDDEN, er.SELECTED
 ALL_FLAGS = xr.POSITION | xr.ORIENT | xr.SIZE
 _CACHE = {}
@@ -59,13 +57,10 @@ def test_xform_abi(tmp_path):
     assert L.gs_abi_version() == 3
     fields = [n for n, _ in _abi.GsXform._fields_]
     consts = ["GS_XFORM_POSITION", "GS_XFORM_ORIENT", "GS_XFORM_SIZE", "GS_ABI_VERSION"]
-    prog = '#include <stdio.h>\n#include <stddef.h>\n#include "gsplat/gs_abi.h"\nint main(void){printf("%zu", sizeof(gs_xform));'
+    prog = 'printf("%zu", sizeof(gs_xform));'
     prog += "".join('printf(" %%zu", offsetof(gs_xform, %s));' % n for n in fields)
-    prog += "".join('printf(" %%u", (unsigned)%s);' % c for c in consts) + "return 0;}\n"
-    src, exe = tmp_path / "xform_layout.c", tmp_path / "xform_layout"
-    src.write_text(prog)
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    out = [int(v) for v in subprocess.check_output([str(exe)]).split()]
+    prog += "".join('printf(" %%u", (unsigned)%s);' % c for c in consts)
+    out = c_layout(tmp_path, "xform_layout", prog)
     assert out[0] == ctypes.sizeof(_abi.GsXform) == 408
     assert out[1:1 + len(fields)] == [getattr(_abi.GsXform, n).offset for n in fields]
     assert out[1 + len(fields):] == [1, 2, 4, 3]
@@ -89,17 +84,14 @@ def test_xform_abi(tmp_path):
     n = ctypes.c_uint64(77)
     assert L.gs_transform_splats(None, 0, 0, ctypes.byref(x), ctypes.byref(n)) == _abi.GS_ERR_INVALID_ARGUMENT
     assert b"gs_transform_splats" in L.gs_last_error() and b"null" in L.gs_last_error() and n.value == 77
-    hdr = open(HEADER).read()
+    rjs, idx, dts, napi, hdr = host_sources()
     assert "splat transforms" in hdr and "#define GS_ABI_VERSION 3\n" in hdr
     for decl in ("int32_t gs_xform_compose(", "int32_t gs_transform_splats(", "typedef struct gs_xform {"):
         assert decl in hdr
     for words in ("12 B read, 12 B written", "16 + 180 B each way", "12 B read, 16 B written", "NOT a bit-exact undo", "NON-UNIFORM"):
         assert words in hdr
-    js = os.path.join(ROOT, "gaussian-splatting-wgpu_amd", "js")
-    dts, rjs, idx = (open(os.path.join(js, f)).read() for f in ("index.d.ts", "renderer.js", "index.js"))
     assert "transformSplats(" in dts and "transformSplats(" in rjs
     assert "composeTransform" in idx and "export function composeTransform(" in dts
-    napi = open(os.path.join(CSRC, "napi", "gs_napi.c")).read()
     for name in ("composeTransform", "transformSplats"):
         assert '{"%s", js_' % name in napi
 
@@ -201,8 +193,7 @@ def test_compose_covariance_invariance():
 
 def test_restatement_sanity():
     """flags = 0 returns the records bit for bit; each single flag changes exactly its own floats (uint32 view)."""
-    import test_export as te
-    rec = te._records(1025)
+    rec = special_records(1025)
     x, _ = _compose_pair(xr.axis_angle((0.3, -0.5, 0.81), 0.65), TRANSLATE, 1.7, PIVOT)
     X = xr.Xform.from_struct(x)
     np.testing.assert_array_equal(er.bits(xr.apply(rec, X.with_flags(0))), er.bits(rec))
@@ -330,12 +321,11 @@ def test_transform_kernel(n):
     bytes: the export after the call equals the restatement of the export before it on the matching records, every other record
     and every unflagged float is untouched bit for bit, the state plane is unchanged, *matched is the restated count.  Once with
     guard-filled device memory around the exported buffer."""
-    import test_export as te
     from gsplat import _abi
-    rec = te._records(n)
+    rec = special_records(n)
     rng = np.random.default_rng(900 + n)
     plane = rng.choice(np.array([0, HID, SEL, HID | SEL, 0x83, 0x80, 0x42], np.uint8), size=n)
-    r = te._mk(rec, 64, 64, 8)
+    r = _mk(rec, 64, 64, 8)
     r.write_state(plane)
     cur = r.export_splats()
     np.testing.assert_array_equal(er.bits(cur), er.bits(er.zero_padding(rec)))
@@ -362,24 +352,13 @@ def test_transform_kernel(n):
     x.flags = ALL_FLAGS
     want = xr.apply(cur, xr.Xform.from_struct(x))
     assert r.transform(x, 0, 0) == n
-    got, ids = te._raw_export(r, 0, 0, True, device=True)  # guards behind the records and the ids are checked inside
+    got, ids = raw_export(r, 0, 0, True, device=True)  # guards behind the records and the ids are checked inside
     _assert_records(got, want, np.arange(n), ALL_FLAGS, "guarded n=%d" % n)
     np.testing.assert_array_equal(ids, np.arange(n, dtype=np.uint32))
     r.destroy()
 
 
-TAPS = ("TILE_COUNTS", "GAUSSIAN_DATA", "KEYS", "VALUES", "RANGES")
 CASES = [("cfgA", 8), ("cfgA", 16), ("cfgA", 32), ("ragged", 8)]
-
-
-def _frame(r, u, debug):
-    from gsplat import _abi
-    r.render_uniforms(u, debug=debug)
-    r.wait()
-    out = {t: r.read_buffer(getattr(_abi, "GS_BUF_" + t)) for t in TAPS}
-    out["rgba8"] = r.read_rgba8()
-    out["rgbf"] = r.read_buffer(_abi.GS_BUF_RGB_F32)
-    return out
 
 
 def _similarity():
@@ -391,11 +370,10 @@ def _similarity():
 
 def _selected_and_moved(name):
     """(plane with the unit sphere selected, restated records after the similarity on the selection)"""
-    import test_splat_state as tss
     k = ("moved", name)
     if k not in _CACHE:
-        s = tss._scene(name)[0]
-        inside = tss._inside(name, "sphere_r1")
+        s = state_scene(name)[0]
+        inside = in_region(name, "sphere_r1")
         assert 0 < inside.sum() < s.shape[0]
         plane = np.where(inside, SEL, 0).astype(np.uint8)
         _CACHE[k] = (plane, xr.apply(s, xr.Xform.from_struct(_similarity()), inside))
@@ -411,23 +389,21 @@ def test_transform_is_an_upload_of_the_transformed_records(oracle, case, exact, 
     one given gs_upload_splats(restated records) + gs_state_write(the bytes): every tap of a gs_render_debug frame and of a tight
     gs_render frame and the image, bit for bit; in EXACT mode the image is also the oracle's render of the restated records.  The
     slab contexts reach the smax path (the conservative radius of the slab cull)."""
-    import test_splat_state as tss
     from gpu_checks import check_image
     name, ts = case
-    s, u, W, H = tss._scene(name)
+    s, u, W, H = state_scene(name)
     plane, moved = _selected_and_moved(name)
     ntx = oracle.num_tiles(W, H, ts)[0]
     cols = (ntx // 4, ntx - ntx // 8) if slab else None
-    import test_export as te
-    r = te._mk(s, W, H, ts, exact=exact, cols=cols)
+    r = _mk(s, W, H, ts, exact=exact, cols=cols)
     assert r.select_sphere((0.0, 0.0, 0.0), 1.0) == int((plane != 0).sum())
     assert r.transform(_similarity()) == int((plane != 0).sum())
     np.testing.assert_array_equal(r.read_state(), plane)
     np.testing.assert_array_equal(er.bits(r.export_splats()), er.bits(er.zero_padding(moved)))
-    fresh = te._mk(moved, W, H, ts, exact=exact, cols=cols)
+    fresh = _mk(moved, W, H, ts, exact=exact, cols=cols)
     fresh.write_state(plane)
     for debug in (True, False):
-        a, b = _frame(r, u, debug), _frame(fresh, u, debug)
+        a, b = frame_taps(r, u, debug), frame_taps(fresh, u, debug)
         for t in TAPS + ("rgba8", "rgbf"):
             np.testing.assert_array_equal(a[t], b[t], err_msg="%s debug=%s" % (t, debug))
         if exact:
@@ -443,14 +419,12 @@ def test_transform_is_an_upload_of_the_transformed_records(oracle, case, exact, 
 @pytest.mark.gpu
 def test_transform_on_frame_paths(oracle):
     """The ring, a captured frame graph, gs_pick, a borrower, an unflagged context and the refusals."""
-    import test_export as te
-    import test_splat_state as tss
     from gpu_checks import check_image
     from gsplat import _abi
     from pick_restate import restate_ref
     L = _abi.load()
     name, ts = "cfgA", 16
-    s, u, W, H = tss._scene(name)
+    s, u, W, H = state_scene(name)
     plane, moved = _selected_and_moved(name)
     m = int((plane != 0).sum())
     ref = sr.state_frame(oracle, moved, u, W, H, ts, plane)
@@ -458,7 +432,7 @@ def test_transform_on_frame_paths(oracle):
     assert (ref["rgba8"] != old["rgba8"]).any()
     x = _similarity()
     # the ring: three frames enqueued and not waited for; the call drains them; it is not a frame
-    r = te._mk(s, W, H, ts)
+    r = _mk(s, W, H, ts)
     r.write_state(plane)
     for _ in range(3):
         r.render_uniforms(u)
@@ -479,9 +453,9 @@ def test_transform_on_frame_paths(oracle):
         np.testing.assert_array_equal(got[f], want[f], err_msg=f)
     assert (got["hit_count"] > 0).any()
     # a borrower is refused itself and renders the owner's transformed scene
-    b = te._mk(s, W, H, ts, share_with=r)
+    b = _mk(s, W, H, ts, share_with=r)
     before = r.export_splats()
-    c, msg = te._code(lambda: b.transform(x))
+    c, msg = code_of(lambda: b.transform(x))
     assert c == _abi.GS_ERR_INVALID_ARGUMENT and "owner" in msg and "gs_transform_splats" in msg
     np.testing.assert_array_equal(er.bits(r.export_splats()), er.bits(before))
     b.render_uniforms(u)
@@ -524,7 +498,7 @@ def test_transform_on_frame_paths(oracle):
     b.destroy()
     r.destroy()
     # a captured graph: a replay after the transform is the fresh context's frame and graph_frames goes on counting
-    g = te._mk(s, W, H, ts)
+    g = _mk(s, W, H, ts)
     g.set_option(_abi.GS_OPT_FRAMES_IN_FLIGHT, 1)
     g.set_option(_abi.GS_OPT_FRAME_GRAPH, 1)
     g.write_state(plane)
@@ -542,8 +516,8 @@ def test_transform_on_frame_paths(oracle):
         assert g.stats()["graph_frames"] == 3 + k
     g.destroy()
     # without GS_FLAG_SPLAT_STATE: (0, 0) is accepted, anything else refused; before an upload: GS_ERR_NO_SCENE
-    f = te._mk(s, W, H, ts, state=False)
-    c, msg = te._code(lambda: f.transform(x))
+    f = _mk(s, W, H, ts, state=False)
+    c, msg = code_of(lambda: f.transform(x))
     assert c == _abi.GS_ERR_INVALID_ARGUMENT and "GS_FLAG_SPLAT_STATE" in msg
     np.testing.assert_array_equal(er.bits(f.export_splats()), er.bits(er.zero_padding(s)))
     assert f.transform(x, 0, 0) == s.shape[0]
@@ -563,9 +537,8 @@ def test_transform_on_frame_paths(oracle):
 
 def _frame_values(s, plane, u, W, H, ts):
     """GS_BUF_VALUES of the product frame of (s, plane) on a context that is not transformed afterwards."""
-    import test_export as te
     from gsplat import _abi
-    r = te._mk(s, W, H, ts)
+    r = _mk(s, W, H, ts)
     r.write_state(plane)
     for _ in range(3):
         r.render_uniforms(u)
@@ -580,12 +553,10 @@ def test_python_hosts():
     """Renderer.translate_selected / rotate_selected / scale_selected are transform(compose_xform(...)) on the selection, and
     PipelinedRenderer.transform drains every slot and asks the owner."""
     import gsplat
-    import test_export as te
-    import test_splat_state as tss
     from gsplat import _abi
     name, ts = "cfgA", 16
-    s, u, W, H = tss._scene(name)
-    inside = tss._inside(name, "sphere_r1")
+    s, u, W, H = state_scene(name)
+    inside = in_region(name, "sphere_r1")
     m = int(inside.sum())
     q, piv = _f32(xr.axis_angle((1, 2, -1), 0.4)), (0.1, -0.2, 0.3)
     steps = [_abi.compose_xform(translate=(0.5, 0.0, -0.25)), _abi.compose_xform(rot=q, pivot=piv), _abi.compose_xform(scale=0.75, pivot=piv)]
@@ -593,7 +564,7 @@ def test_python_hosts():
     want = s
     for x in steps:
         want = xr.apply(want, xr.Xform.from_struct(x), inside)
-    r = te._mk(s, W, H, ts)
+    r = _mk(s, W, H, ts)
     assert r.select_sphere((0.0, 0.0, 0.0), 1.0) == m
     assert r.translate_selected((0.5, 0.0, -0.25)) == m and r.rotate_selected(q, piv) == m and r.scale_selected(0.75, piv) == m
     np.testing.assert_array_equal(er.bits(r.export_splats()), er.bits(er.zero_padding(want)))
@@ -621,20 +592,15 @@ def test_python_hosts():
 def test_node_host_transform_matches_python(tmp_path):
     """tests/js/xform_check.js selects a sphere, composes and applies a similarity, renders and exports through the Node host: the
     struct, the records and the image equal what the Python host makes of the same sequence, byte for byte."""
-    import test_export as te
-    import test_splat_state as tss
     from gsplat import _abi
-    s, u, W, H = tss._scene("cfgA")
+    s, u, W, H = state_scene("cfgA")
     n, ts = s.shape[0], 16
     rec, ub, out = (str(tmp_path / f) for f in ("rec.bin", "u.bin", "out.bin"))
     s.tofile(rec)
     np.ascontiguousarray(u, F).tofile(ub)
-    res = subprocess.run([NODE, os.path.join(ROOT, "tests", "js", "xform_check.js")] + [str(a) for a in (rec, n, W, H, ts, ub, out)],
-                         capture_output=True, text=True, timeout=300)
-    assert res.returncode == 0, res.stderr
-    info = json.loads(res.stdout.strip().splitlines()[-1])
+    info = run_node("xform_check.js", (rec, n, W, H, ts, ub, out))
     x = _abi.compose_xform(rot=(0.9, 0.1, -0.3, 0.2), translate=(0.15, 0.1, -0.2), scale=1.3, pivot=(0.1, 0.0, -0.1))
-    r = te._mk(s, W, H, ts, exact=False)
+    r = _mk(s, W, H, ts, exact=False)
     m = r.select_sphere((0.0, 0.0, 0.0), 1.0)
     assert r.transform(x) == m
     r.render_uniforms(u)
