@@ -93,6 +93,24 @@ void gs_launch_state_count(const uint8_t* state, uint32_t n, uint32_t mask, uint
 // gs_state_coverage: the region pass with a membership read from the coverage planes (16 bytes per splat: gs_coverage_rec)
 void gs_launch_state_coverage(uint8_t* state, const void* planes, uint32_t n, uint32_t min_hits, float min_weight, uint32_t covered, uint32_t op,
                               uint32_t bits, uint32_t where_mask, uint32_t where_value, unsigned long long* matched, hipStream_t st);
+// k_attr.hip: the splat attributes (gs_attr.hip; gs_state_attr in gs_state.hip).  kind: GS_ATTR_* (checked by the caller); cov: the
+// coverage planes, read by the COVER_* kinds only; state: null = every splat passes (the (0, 0) filter: the plane is not read).
+struct GsAttrDev { float p[4]; }; // a gs_attr's parameters as the kernels read them
+// the state pass of gs_launch_state_region around (v >= lo && v <= hi) == inside
+void gs_launch_attr_state(uint32_t kind, uint8_t* state, const GsScene& s, const void* cov, uint32_t n, const GsAttrDev& a, float lo, float hi,
+                          uint32_t inside, uint32_t op, uint32_t bits, uint32_t where_mask, uint32_t where_value, unsigned long long* matched,
+                          hipStream_t st);
+// slots: GS_STATE_SLOTS records GS_STATE_SLOT_STRIDE words apart, a workgroup folds into record (workgroup % GS_STATE_SLOTS); the
+// caller initialises them (matched = nan = 0, kmin = 0xFFFFFFFF, kmax = 0) and folds them.  Keys: the order-preserving map of gs_abi.h.
+struct GsAttrSlot { unsigned long long matched, nan; uint32_t kmin, kmax; };
+void gs_launch_attr_summary(uint32_t kind, const uint8_t* state, const GsScene& s, const void* cov, uint32_t n, const GsAttrDev& a, uint32_t mask,
+                            uint32_t value, unsigned long long* slots, hipStream_t st);
+// counts: bins + 3 words, zeroed by the caller (bins, below, above, NaN); grid: workgroups of the grid-stride loop (clamped to the work)
+void gs_launch_attr_histogram(uint32_t kind, const uint8_t* state, const GsScene& s, const void* cov, uint32_t n, const GsAttrDev& a, uint32_t mask,
+                              uint32_t value, float lo, float hi, float scale, uint32_t bins, unsigned long long* counts, uint32_t grid, hipStream_t st);
+// out[g] = v of splat ids[first + g], or of splat first + g when ids is null, g = 0 .. m
+void gs_launch_attr_values(uint32_t kind, const GsScene& s, const void* cov, uint32_t n, const GsAttrDev& a, const uint32_t* ids, uint32_t first,
+                           uint32_t m, float* out, hipStream_t st);
 // k_export.hip: the splat edits (gs_export.hip).  Selection = splats with (s & mask) == value in ascending order: `counts` holds
 // gs_select_blocks(n) + 1 words (one per 1024 splats; after the launch their exclusive prefix, the total last), `ids` the total.
 uint32_t gs_select_blocks(uint32_t n);

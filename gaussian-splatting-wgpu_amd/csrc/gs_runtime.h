@@ -1,10 +1,10 @@
-// gs_runtime.h -- private to the runtime sources (gs_context / gs_frame / gs_readback / gs_state / gs_export / gs_xform / gs_coverage / gs_ply / gs_stages .hip):
+// gs_runtime.h -- private to the runtime sources (gs_context / gs_frame / gs_readback / gs_state / gs_export / gs_xform / gs_coverage / gs_attr / gs_ply / gs_stages .hip):
 //   the error channel (fail, HIP_TRY);
 //   the owners of HIP resources (Owned: DevBuf, PinnedBuf, Event, Stream, File) and Scratch, a device buffer that grows on demand;
 //   the context (gs_ctx, GsOptions, FrameNotes, GraphKey), the lists of its last frame (frame_lists) and sums over its ring (over_ring);
 //   what the calls on the resident splats share: the prologue of a call that drains the ring (Plane, resident_check,
 //   resident_drain, resident_begin), the last frame waited for (last_frame), the staging of a canvas mask (stage_mask), the
-//   coverage planes (cover_planes) and the splat edits' selection (edit_select).
+//   coverage planes (cover_planes), the splat edits' selection (edit_select) and the check of a gs_attr (attr_check).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -184,6 +184,8 @@ struct gs_ctx {
     struct { DevBuf<unsigned long long> counter; Scratch<uint32_t> ids; Scratch<uint8_t> mask; } st;
     // splat edits (gs_export.hip): the selection's per-workgroup counts and its id list; grown on demand
     struct { Scratch<uint32_t> counts, ids; } ex;
+    // splat attributes (gs_attr.hip): the summary's slot records, the histogram's bins + 3 words, one trip of values; grown on demand
+    struct { DevBuf<unsigned long long> slots; Scratch<unsigned long long> hist; Scratch<float> vals; } at;
     // gs_coverage_* (gs_coverage.hip; root ctx): N x 16 B gs_coverage_rec, allocated and zeroed on first use, dropped with the scene
     DevBuf<> cov;
     Event ev[GS_EV_RING][GS_STAGE_COUNT + 1]; // ring of per-frame stage brackets (GS_FLAG_TIMING)
@@ -252,6 +254,10 @@ int32_t cover_planes(gs_ctx* root, hipStream_t st);
 // gs_export.hip: the splat edits' selection: counts the splats with (s & mask) == value and, with want_ids, leaves their indices,
 // ascending, in c->ex.ids
 int32_t edit_select(gs_ctx* c, uint32_t mask, uint32_t value, bool want_ids, uint64_t* total);
+// gs_attr.hip: the refusals of a gs_attr (null, struct_size, kind, a non-finite p of the kinds that read it) in `who`'s name; *dev:
+// its parameters as the kernels take them.  attr_needs_cover: the kind reads the coverage planes (cover_planes first)
+int32_t attr_check(const char* who, const gs_attr* a, GsAttrDev* dev);
+inline bool attr_needs_cover(const gs_attr* a) { return a->kind >= GS_ATTR_COVER_HITS; }
 inline gs_ctx* last_of(gs_ctx* c) { return (c && c->last) ? c->last : c; }
 inline bool has_state(const gs_ctx* c) { return (c->cfg.flags & GS_FLAG_SPLAT_STATE) != 0; }
 inline GsTint tint_of(uint32_t argb) { // a<<24 | r<<16 | g<<8 | b -> what the projection applies (each quotient one f32 division)

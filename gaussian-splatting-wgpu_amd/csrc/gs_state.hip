@@ -1,5 +1,5 @@
-// gs_state.hip -- the state plane's entry points: region, id and coverage selections, counting, restore.  Part of the C ABI
-// (include/gsplat/gs_abi.h "splat state"; gs_state_coverage under "coverage"); the kernels are in k_state.hip, the projection that
+// gs_state.hip -- the state plane's entry points: region, id, coverage and attribute selections, counting, restore.  Part of the C ABI
+// (include/gsplat/gs_abi.h "splat state"; gs_state_coverage under "coverage", gs_state_attr under "splat attributes"); the kernels are in k_state.hip, the projection that
 // honours the plane in k_preprocess.hip (STATE).  Also what every call on the resident splats does first (gs_runtime.h).
 //
 // The reference has no counterpart: it is a viewer.  An editor on it would edit its own 320-byte records and upload them again
@@ -137,6 +137,29 @@ GS_EXPORT int32_t gs_state_coverage(gs_ctx* c, uint32_t min_hits, float min_weig
     if (rc != GS_OK) return rc;
     return state_counted(c, [&](unsigned long long* slots) {
         gs_launch_state_coverage(plane(c), c->cov, c->n, min_hits, min_weight, covered, op, bits, where_mask, where_value, slots, c->stream);
+    }, matched);
+}
+
+// Select by value: the pass around a splat attribute (gs_attr.hip, k_attr.hip).
+GS_EXPORT int32_t gs_state_attr(gs_ctx* c, const gs_attr* a, float lo, float hi, uint32_t inside, uint32_t where_mask, uint32_t where_value, uint32_t op,
+                                uint32_t bits, uint64_t* matched) {
+    int32_t rc = resident_check(c, "gs_state_attr", Plane::always);
+    if (rc != GS_OK) return rc;
+    GsAttrDev dev;
+    rc = attr_check("gs_state_attr", a, &dev);
+    if (rc != GS_OK) return rc;
+    rc = state_check_op("gs_state_attr", op, bits);
+    if (rc != GS_OK) return rc;
+    if (lo != lo || hi != hi) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_attr: range [%g, %g] has a bound that is not a number", (double)lo, (double)hi);
+    if (where_mask > 0xFFu) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_attr: where_mask 0x%x does not fit the state byte", where_mask);
+    rc = resident_drain(c, true);
+    if (rc != GS_OK) return rc;
+    if (attr_needs_cover(a)) {
+        rc = cover_planes(c, c->stream);
+        if (rc != GS_OK) return rc;
+    }
+    return state_counted(c, [&](unsigned long long* slots) {
+        gs_launch_attr_state(a->kind, plane(c), c->scene, c->cov, c->n, dev, lo, hi, inside, op, bits, where_mask, where_value, slots, c->stream);
     }, matched);
 }
 

@@ -10,6 +10,7 @@
 //   count  : 1 B read per splat.
 #include "gs_device.h"
 #include "gs_kernels.h"
+#include "gs_state_sum.h"
 
 // Membership of one centre (gs_abi.h: one rounding per operation, the projection's own expression tree for ph, pv, px, py).
 template <int KIND>
@@ -35,19 +36,7 @@ __device__ __forceinline__ bool state_member(const GsRegionDev& r, float x, floa
     return r.mask[(uint64_t)iy * r.wi + ix] != 0;
 }
 
-// The kernels' `matched` / `count`: wave sum (DPP), one LDS add per wave, one global add per workgroup, spread over GS_STATE_SLOTS
-// words (gs_kernels.h).  A kernel calls state_block_begin first (every thread), state_block_add last (every thread, once).
-__shared__ uint32_t s_state_sum;
-__device__ __forceinline__ void state_block_begin() {
-    if (threadIdx.x == 0) s_state_sum = 0u;
-    __syncthreads();
-}
-__device__ __forceinline__ void state_block_add(uint32_t hits, unsigned long long* slots) {
-    const uint32_t ws = wave_sum(hits);
-    if ((threadIdx.x & 63u) == 0u && ws) atomicAdd(&s_state_sum, ws);
-    __syncthreads();
-    if (threadIdx.x == 0 && s_state_sum) atomicAdd(slots + (blockIdx.x % GS_STATE_SLOTS) * GS_STATE_SLOT_STRIDE, (unsigned long long)s_state_sum);
-}
+// The kernels' `matched` / `count` go through state_block_begin / state_block_add (gs_state_sum.h).
 
 // The state pass, which the region and the coverage kernel both are, around their own membership test: thread q owns splats
 // 4q .. 4q+3, i.e. one whole word of the plane, so no byte read-modify-write races with a neighbour.  A splat with

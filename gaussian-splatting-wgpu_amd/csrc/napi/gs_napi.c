@@ -446,6 +446,90 @@ static napi_value js_state_coverage(napi_env env, napi_callback_info info) {
     return ret_u64(env, rc, matched);
 }
 
+/* ---- splat attributes: 1:1 wrappers of gs_attr_* and gs_state_attr ----------------------------------------------------------- */
+/* (kind, p) of two arguments -> gs_attr; p: a Float32Array of four.  Returns 0 with a TypeError pending. */
+static int get_attr(napi_env env, napi_value kind, napi_value p, gs_attr* a) {
+    void* data = NULL;
+    size_t len = 0;
+    memset(a, 0, sizeof(*a));
+    a->struct_size = sizeof(*a);
+    if (napi_get_value_uint32(env, kind, &a->kind) != napi_ok || !get_bytes(env, p, &data, &len) || len < sizeof(a->p)) {
+        napi_throw_type_error(env, NULL, "gsplat: an attribute is a kind (ATTR.*) and a Float32Array of four parameters");
+        return 0;
+    }
+    memcpy(a->p, data, sizeof(a->p));
+    return 1;
+}
+
+/* attrSummary(handle, kind, p, mask, value) -> {matched, nan, min, max} */
+static napi_value js_attr_summary(napi_env env, napi_callback_info info) {
+    CTX_ARGS(5, 5);
+    gs_attr a;
+    uint32_t mask = 0, value = 0;
+    if (!get_attr(env, argv[1], argv[2], &a)) return NULL;
+    NAPI_CALL(env, napi_get_value_uint32(env, argv[3], &mask));
+    NAPI_CALL(env, napi_get_value_uint32(env, argv[4], &value));
+    struct gs_attr_summary sm;
+    int32_t rc = gs_attr_summary(ctx, &a, mask, value, &sm);
+    if (rc != GS_OK) return throw_gs(env, rc);
+    napi_value out;
+    NAPI_CALL(env, napi_create_object(env, &out));
+    set_num(env, out, "matched", (double)sm.matched);
+    set_num(env, out, "nan", (double)sm.nan);
+    set_num(env, out, "min", (double)sm.min);
+    set_num(env, out, "max", (double)sm.max);
+    return out;
+}
+
+/* attrHistogram(handle, kind, p, mask, value, lo, hi, bins) -> ArrayBuffer (bins + 3 u64: the bins, below, above, NaN) */
+static napi_value js_attr_histogram(napi_env env, napi_callback_info info) {
+    CTX_ARGS(8, 8);
+    gs_attr a;
+    uint32_t mask = 0, value = 0, bins = 0;
+    double lo = 0, hi = 0;
+    if (!get_attr(env, argv[1], argv[2], &a)) return NULL;
+    NAPI_CALL(env, napi_get_value_uint32(env, argv[3], &mask));
+    NAPI_CALL(env, napi_get_value_uint32(env, argv[4], &value));
+    NAPI_CALL(env, napi_get_value_double(env, argv[5], &lo));
+    NAPI_CALL(env, napi_get_value_double(env, argv[6], &hi));
+    NAPI_CALL(env, napi_get_value_uint32(env, argv[7], &bins));
+    void* dst = NULL;
+    napi_value ab;
+    NAPI_CALL(env, napi_create_arraybuffer(env, ((size_t)(bins <= 1024u ? bins : 0u) + 3) * sizeof(uint64_t), &dst, &ab)); /* (out of range: refused below) */
+    int32_t rc = gs_attr_histogram(ctx, &a, mask, value, (float)lo, (float)hi, bins, (uint64_t*)dst);
+    return rc == GS_OK ? ab : throw_gs(env, rc);
+}
+
+/* attrValues(handle, kind, p, mask, value) -> ArrayBuffer (one f32 per matching splat, ascending index order) */
+static int32_t fill_attr_values(gs_ctx* ctx, const uint32_t* a, void* dst, uint64_t cap, uint64_t* n) { /* a: mask, value, then the gs_attr */
+    return gs_attr_read(ctx, (const gs_attr*)(a + 2), a[0], a[1], (float*)dst, cap, n, NULL);
+}
+static napi_value js_attr_values(napi_env env, napi_callback_info info) {
+    CTX_ARGS(5, 5);
+    uint32_t w[2 + sizeof(gs_attr) / 4];
+    gs_attr a;
+    if (!get_attr(env, argv[1], argv[2], &a)) return NULL;
+    NAPI_CALL(env, napi_get_value_uint32(env, argv[3], &w[0]));
+    NAPI_CALL(env, napi_get_value_uint32(env, argv[4], &w[1]));
+    memcpy(w + 2, &a, sizeof(a));
+    return fill_arraybuffer(env, ctx, fill_attr_values, w, sizeof(float));
+}
+
+/* stateAttr(handle, kind, p, lo, hi, inside, whereMask, whereValue, op, bits) -> matched */
+static napi_value js_state_attr(napi_env env, napi_callback_info info) {
+    CTX_ARGS(10, 10);
+    gs_attr a;
+    if (!get_attr(env, argv[1], argv[2], &a)) return NULL;
+    double lo = 0, hi = 0;
+    NAPI_CALL(env, napi_get_value_double(env, argv[3], &lo));
+    NAPI_CALL(env, napi_get_value_double(env, argv[4], &hi));
+    uint32_t u[5]; /* inside, whereMask, whereValue, op, bits */
+    for (int k = 0; k < 5; ++k) NAPI_CALL(env, napi_get_value_uint32(env, argv[5 + k], &u[k]));
+    uint64_t matched = 0;
+    int32_t rc = gs_state_attr(ctx, &a, (float)lo, (float)hi, u[0], u[1], u[2], u[3], u[4], &matched);
+    return ret_u64(env, rc, matched);
+}
+
 /* ---- splat state (GS_FLAG_SPLAT_STATE): 1:1 wrappers of gs_state_* --------------------------------------------------------- */
 static int get_f32x3_prop(napi_env env, napi_value obj, const char* name, float* out) {
     napi_value v, e;
@@ -911,6 +995,8 @@ static napi_value init(napi_env env, napi_value exports) {
         {"composeTransform", js_compose_transform}, {"transformSplats", js_transform_splats},
         {"accumulateCoverage", js_coverage_accumulate}, {"resetCoverage", js_coverage_reset},
         {"readCoverage", js_coverage_read}, {"stateCoverage", js_state_coverage},
+        {"attrSummary", js_attr_summary}, {"attrHistogram", js_attr_histogram},
+        {"attrValues", js_attr_values}, {"stateAttr", js_state_attr},
     };
     for (size_t i = 0; i < sizeof(fns) / sizeof(fns[0]); ++i) {
         napi_value f;
@@ -933,6 +1019,7 @@ static napi_value init(napi_env env, napi_value exports) {
     set_num(env, exports, "PICK_MAX_QUERIES", GS_PICK_MAX_QUERIES);
     set_num(env, exports, "PICK_MAX_CONTRIB", GS_PICK_MAX_CONTRIB);
     set_num(env, exports, "COVERAGE_REC_BYTES", (double)sizeof(gs_coverage_rec));
+    set_num(env, exports, "ATTR_COUNT", (double)GS_ATTR_COUNT);
     return exports;
 }
 

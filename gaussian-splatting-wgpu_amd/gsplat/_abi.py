@@ -58,6 +58,14 @@ GS_SELECT_TINT_DEFAULT = 0x80FFFF00
 # splat transforms
 GS_XFORM_POSITION, GS_XFORM_ORIENT, GS_XFORM_SIZE = 0x1, 0x2, 0x4
 
+# splat attributes (gs_attr.kind)
+(GS_ATTR_POS_X, GS_ATTR_POS_Y, GS_ATTR_POS_Z, GS_ATTR_OPACITY_LOGIT, GS_ATTR_LOG_SCALE_MIN, GS_ATTR_LOG_SCALE_MAX, GS_ATTR_LOG_SCALE_SUM,
+ GS_ATTR_ANISOTROPY, GS_ATTR_DC_R, GS_ATTR_DC_G, GS_ATTR_DC_B, GS_ATTR_DIST2, GS_ATTR_PLANE, GS_ATTR_COVER_HITS, GS_ATTR_COVER_MAX_WEIGHT,
+ GS_ATTR_COVER_SUM, GS_ATTR_COUNT) = range(17)
+GS_ATTR_NAMES = ("POS_X", "POS_Y", "POS_Z", "OPACITY_LOGIT", "LOG_SCALE_MIN", "LOG_SCALE_MAX", "LOG_SCALE_SUM", "ANISOTROPY", "DC_R", "DC_G",
+                 "DC_B", "DIST2", "PLANE", "COVER_HITS", "COVER_MAX_WEIGHT", "COVER_SUM")
+GS_ATTR_MAX_BINS = 1024
+
 # every symbol include/gsplat/gs_abi.h declares
 ABI_SYMBOLS = ("gs_last_error", "gs_abi_version", "gs_create", "gs_destroy", "gs_upload_splats", "gs_upload_splats_device",
                "gs_share_splats",
@@ -66,7 +74,8 @@ ABI_SYMBOLS = ("gs_last_error", "gs_abi_version", "gs_create", "gs_destroy", "gs
                "gs_get_stats", "gs_pick", "gs_state_region", "gs_state_ids", "gs_state_count", "gs_state_write",
                "gs_state_list", "gs_export_splats", "gs_export_splats_device", "gs_compact", "gs_ply_save", "gs_export_ply",
                "gs_xform_compose", "gs_transform_splats",
-               "gs_coverage_accumulate", "gs_coverage_reset", "gs_coverage_read", "gs_state_coverage", "gs_set_option", "gs_slab_width", "gs_assemble_slabs", "gs_sort_pairs_u32",
+               "gs_coverage_accumulate", "gs_coverage_reset", "gs_coverage_read", "gs_state_coverage",
+               "gs_attr_summary", "gs_attr_histogram", "gs_attr_read", "gs_state_attr", "gs_set_option", "gs_slab_width", "gs_assemble_slabs", "gs_sort_pairs_u32",
                "gs_exclusive_scan_u32")
 
 
@@ -121,6 +130,14 @@ class GsCoverageRec(ctypes.Structure):
 class GsCoverRegion(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("x0", ctypes.c_uint32), ("y0", ctypes.c_uint32), ("x1", ctypes.c_uint32),
                 ("y1", ctypes.c_uint32), ("mask", ctypes.c_void_p)]
+
+
+class GsAttr(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("kind", ctypes.c_uint32), ("p", ctypes.c_float * 4)]
+
+
+class GsAttrSummary(ctypes.Structure):
+    _fields_ = [("matched", ctypes.c_uint64), ("nan", ctypes.c_uint64), ("min", ctypes.c_float), ("max", ctypes.c_float)]
 
 
 # numpy views of the same records (what Renderer.pick returns)
@@ -189,6 +206,11 @@ def load():
     L.gs_coverage_reset.argtypes = [vp]
     L.gs_coverage_read.argtypes = [vp, vp, u64, ctypes.POINTER(u64)]
     L.gs_state_coverage.argtypes = [vp, u32, ctypes.c_float, u32, u32, u32, u32, u32, ctypes.POINTER(u64)]
+    f32 = ctypes.c_float
+    L.gs_attr_summary.argtypes = [vp, ctypes.POINTER(GsAttr), u32, u32, ctypes.POINTER(GsAttrSummary)]
+    L.gs_attr_histogram.argtypes = [vp, ctypes.POINTER(GsAttr), u32, u32, f32, f32, u32, vp]
+    L.gs_attr_read.argtypes = [vp, ctypes.POINTER(GsAttr), u32, u32, vp, u64, ctypes.POINTER(u64), vp]
+    L.gs_state_attr.argtypes = [vp, ctypes.POINTER(GsAttr), f32, f32, u32, u32, u32, u32, u32, ctypes.POINTER(u64)]
     L.gs_set_option.argtypes = [vp, i32, ctypes.c_int64]
     L.gs_slab_width.argtypes = [vp, ctypes.POINTER(u32), ctypes.POINTER(u32)]
     L.gs_assemble_slabs.argtypes = [vp, vp, ctypes.POINTER(u32), u32, u64, vp]

@@ -44,6 +44,12 @@ export class Renderer {
   readCoverage(): { count: number; bytes: ArrayBuffer; u64: BigUint64Array; u32: Uint32Array; f32: Float32Array };
   /** FLAG.SPLAT_STATE: applies op with bits to the splats that pass the where filter and for which (hits >= minHits && maxWeight >= minWeight) == covered; returns how many those are. */
   stateCoverage(filter: { minHits?: number; minWeight?: number; covered?: boolean; whereMask?: number; whereValue?: number }, op: number, bits: number): number;
+  /** Splat attributes: one f32 per resident splat (attr.kind = ATTR.*; attr.p: the point of DIST2 or the plane of PLANE). */
+  attrSummary(attr: SplatAttr, where?: { mask?: number; value?: number }): { matched: number; nan: number; min: number; max: number };
+  attrHistogram(attr: SplatAttr, lo: number, hi: number, bins?: number, where?: { mask?: number; value?: number }): { counts: number[]; below: number; above: number; nan: number };
+  attrValues(attr: SplatAttr, where?: { mask?: number; value?: number }, withIds?: boolean): { values: Float32Array; ids: Uint32Array | null };
+  /** FLAG.SPLAT_STATE: op / bits on the splats that pass the where filter and for which (lo <= v <= hi) == inside; returns how many. */
+  stateAttr(attr: SplatAttr, range: { lo?: number; hi?: number; inside?: boolean; whereMask?: number; whereValue?: number }, op: number, bits: number): number;
   setOption(key: number, value: number): void;
   /** FLAG.SPLAT_STATE: applies op (STATE.SET / CLEAR / TOGGLE / ASSIGN) with bits to every splat whose centre lies in the region and whose byte passes the where filter; returns how many those are. */
   stateRegion(region: StateRegion, op: number, bits: number): number;
@@ -71,6 +77,9 @@ export interface StateRegion {
   uniforms?: Float32Array; mask?: Uint8Array; whereMask?: number; whereValue?: number;
 }
 export interface CoverRegion { x0?: number; y0?: number; x1?: number; y1?: number; mask?: Uint8Array }
+export interface SplatAttr { kind: number; p?: ArrayLike<number> }
+export const ATTR: { POS_X: 0; POS_Y: 1; POS_Z: 2; OPACITY_LOGIT: 3; LOG_SCALE_MIN: 4; LOG_SCALE_MAX: 5; LOG_SCALE_SUM: 6; ANISOTROPY: 7; DC_R: 8; DC_G: 9;
+                     DC_B: 10; DIST2: 11; PLANE: 12; COVER_HITS: 13; COVER_MAX_WEIGHT: 14; COVER_SUM: 15 };
 export const COVERAGE: { REC_BYTES: 16 };
 export const COVERAGE_FIELD: { sumQ: 0; hits: 8; maxWeight: 12 };
 export const STATE: { HIDDEN: 0x1; SELECTED: 0x2; SET: 1; CLEAR: 2; TOGGLE: 3; ASSIGN: 4 };

@@ -206,6 +206,31 @@ class Renderer {
   stateCoverage({ minHits = 1, minWeight = 0, covered = true, whereMask = 0, whereValue = 0 } = {}, op, bits) {
     return loadNative().stateCoverage(this.handle, minHits >>> 0, +minWeight, covered ? 1 : 0, whereMask >>> 0, whereValue >>> 0, op >>> 0, bits >>> 0);
   }
+  // Splat attributes: one f32 per resident splat, named by attr = {kind: ATTR.*, p: [..4]} -- p is the point of DIST2 (p[0..2]) or the
+  // plane of PLANE (p . (x, y, z, 1); row 2 of the view matrix gives the depth) and ignored otherwise.  where = {mask, value} filters
+  // like stateCount; the default is every splat, which needs no FLAG.SPLAT_STATE.  Every call completes the frames in flight first.
+  // -> {matched, nan, min, max}: min / max over the values that are not NaN (-0 below +0), (Infinity, -Infinity) without any
+  attrSummary(attr, { mask = 0, value = 0 } = {}) {
+    return loadNative().attrSummary(this.handle, attr.kind >>> 0, attrParams(attr), mask >>> 0, value >>> 0);
+  }
+  // -> {counts: number[bins], below, above, nan}: v < lo below, v >= hi above, else bin min(trunc((v - lo) * f32(bins) / (hi - lo)), bins - 1)
+  attrHistogram(attr, lo, hi, bins = 256, { mask = 0, value = 0 } = {}) {
+    const c = new BigUint64Array(loadNative().attrHistogram(this.handle, attr.kind >>> 0, attrParams(attr), mask >>> 0, value >>> 0, +lo, +hi, bins >>> 0));
+    const counts = Array.from(c.subarray(0, bins), Number);
+    return { counts, below: Number(c[bins]), above: Number(c[bins + 1]), nan: Number(c[bins + 2]) };
+  }
+  // -> {values: Float32Array, ids: Uint32Array | null}: the matching splats' values in ascending index order (ids: their indices)
+  attrValues(attr, { mask = 0, value = 0 } = {}, withIds = false) {
+    const values = new Float32Array(loadNative().attrValues(this.handle, attr.kind >>> 0, attrParams(attr), mask >>> 0, value >>> 0));
+    return { values, ids: withIds ? this.listState(mask, value) : null };
+  }
+  // FLAG.SPLAT_STATE: applies `op` with `bits` to the splats that pass (s & whereMask) == whereValue and for which
+  // (lo <= v <= hi) == inside; a NaN is in no range, so {lo: -Infinity, hi: Infinity, inside: false} finds the broken splats.
+  // Returns how many those are.
+  stateAttr(attr, { lo = -Infinity, hi = Infinity, inside = true, whereMask = 0, whereValue = 0 } = {}, op, bits) {
+    return loadNative().stateAttr(this.handle, attr.kind >>> 0, attrParams(attr), +lo, +hi, inside ? 1 : 0, whereMask >>> 0, whereValue >>> 0,
+                                  op >>> 0, bits >>> 0);
+  }
   // Splat edits: bring splats back out of the library and make an edit permanent.  A splat matches when (s & mask) == value;
   // matching splats always come in ascending index order; (0, 0) is every splat and needs no FLAG.SPLAT_STATE.
   listState(mask, value) { return new Uint32Array(loadNative().listState(this.handle, mask >>> 0, value >>> 0)); }
@@ -246,6 +271,12 @@ function savePly(file, gaussians, shDegree = 3) {
   const buf = gaussians.gaussiansBuffer;
   const bytes = gaussians.numGaussians * 320;
   loadNative().savePly(String(file), bytes === buf.byteLength ? buf : buf.slice(0, bytes), shDegree | 0);
+}
+
+function attrParams(attr) {
+  const p = new Float32Array(4);
+  if (attr.p) p.set(Array.from(attr.p).slice(0, 4));
+  return p;
 }
 
 const STATE = { HIDDEN: 0x1, SELECTED: 0x2, SET: 1, CLEAR: 2, TOGGLE: 3, ASSIGN: 4 };

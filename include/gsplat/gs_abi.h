@@ -490,6 +490,72 @@ int32_t gs_coverage_read(gs_ctx* ctx, gs_coverage_rec* dst, uint64_t cap, uint64
 int32_t gs_state_coverage(gs_ctx* ctx, uint32_t min_hits, float min_weight, uint32_t covered, uint32_t where_mask, uint32_t where_value,
                           uint32_t op, uint32_t bits, uint64_t* matched);
 
+/* ---- splat attributes: summarise, histogram, read and select resident splats by VALUE -------------------
+ * gs_state_region selects by where a splat is, gs_pick and gs_state_coverage by what a frame shows of it; these select by what a
+ * splat IS -- opacity, size, anisotropy, base colour, distance from a point or a plane, accumulated importance -- the histogram
+ * with a range slider of every splat editor ("opacity below x", "the largest 1 %", "everything broken"), without the
+ * gs_export_splats / host / gs_state_ids round trip (244 B read, 320 B written and a PCIe copy per splat for one float of it).
+ * The reference has no counterpart (a viewer).
+ * The value v of splat i is ONE f32, defined like the region tests: one rounding per written operation, no contraction, left to
+ * right, so that a host can restate it bit for bit.  "Record float k" is float k of the 320-byte record as uploaded (after a
+ * gs_transform_splats: as a gs_export_splats would return it):
+ *     POS_X / Y / Z      record float 0 / 1 / 2
+ *     OPACITY_LOGIT      record float 12, raw: monotonic in the opacity, so a host turns a threshold o into log(o / (1 - o));
+ *                        no transcendental runs on the device
+ *     LOG_SCALE_MAX      fmaxf(l0, fmaxf(l1, l2)), l = record floats 4, 5, 6 (the upload's own expression for the slab cull's plane)
+ *     LOG_SCALE_MIN      fminf(l0, fminf(l1, l2))         fmaxf / fminf: a NaN operand, quiet or signalling, is missing data and the
+ *                        result is a NaN only when both are (IEEE 754-2019 maximumNumber / minimumNumber, numpy's fmax / fmin)
+ *     LOG_SCALE_SUM      (l0 + l1) + l2                                    the log of the volume
+ *     ANISOTROPY         LOG_SCALE_MAX - LOG_SCALE_MIN                     the log of the axis ratio, >= 0
+ *     DC_R / G / B       record float 16 / 17 / 18
+ *     DIST2              d = position - p[0..2];  (dx dx + dy dy) + dz dz  the SPHERE region's expression
+ *     PLANE              ((p[0] x + p[1] y) + p[2] z) + p[3]               p = row 2 of `view`: the projection's depth pv.z
+ *     COVER_HITS         (float)hits of the ctx's coverage record
+ *     COVER_MAX_WEIGHT   max_weight
+ *     COVER_SUM          (float)(uint32_t)(sum_q >> 32) + (float)(uint32_t)sum_q * 0x1p-32f     the importance, sum of alpha T
+ * p is ignored by the kinds that do not name it.  The COVER_* kinds read the planes of the ctx the call is made on, allocated and
+ * zeroed on first need exactly as gs_state_coverage does.  "Bit for bit" has two exceptions a restating host must know: a NaN that
+ * an expression produces or propagates is a NaN on every machine but its sign and payload are open (compare "NaN on both sides");
+ * and the sign of a zero that fminf / fmaxf chose between -0 and +0 is unspecified (LOG_SCALE_MIN / MAX, ANISOTROPY).
+ * Filter, refusals and ordering are those of the splat edits: (mask, value) as gs_state_count, above 0xFF refused, (0, 0) matches
+ * every splat and is accepted on a ctx without GS_FLAG_SPLAT_STATE, any other filter on such a ctx is refused.  Every call first
+ * completes all frames enqueued on the ctx's ring, runs on the ctx's stream and returns when done; none is a frame or an upload
+ * (taps, statistics, gs_pick, the shadows and a captured graph stay).  GS_ERR_NO_SCENE before any upload; N == 0: zero results,
+ * GS_OK.  The three read-only calls work on a borrower of gs_share_splats; gs_state_attr has gs_state_region's rules.  A wrong
+ * struct_size, kind >= GS_ATTR_COUNT or a non-finite p of DIST2 / PLANE: GS_ERR_INVALID_ARGUMENT and a message.  Multi-GPU: every
+ * rank holds the scene; the scene kinds answer the same on every rank, the COVER_* kinds for the rank's own planes. */
+enum { GS_ATTR_POS_X = 0, GS_ATTR_POS_Y, GS_ATTR_POS_Z, GS_ATTR_OPACITY_LOGIT,
+       GS_ATTR_LOG_SCALE_MIN, GS_ATTR_LOG_SCALE_MAX, GS_ATTR_LOG_SCALE_SUM, GS_ATTR_ANISOTROPY,
+       GS_ATTR_DC_R, GS_ATTR_DC_G, GS_ATTR_DC_B, GS_ATTR_DIST2, GS_ATTR_PLANE,
+       GS_ATTR_COVER_HITS, GS_ATTR_COVER_MAX_WEIGHT, GS_ATTR_COVER_SUM, GS_ATTR_COUNT };
+typedef struct gs_attr { uint32_t struct_size, kind; float p[4]; } gs_attr;   /* 24 bytes; struct_size = sizeof(gs_attr) */
+/* (The record shares its name with the call that fills it, so it is a struct TAG only, not a typedef: C keeps tags and functions
+ * in separate name spaces, and C++ reaches the tag through `struct gs_attr_summary` as written below.) */
+struct gs_attr_summary { uint64_t matched, nan; float min, max; };  /* 24 bytes */
+/* matched: splats that pass the filter; nan: how many of them have a NaN v; min / max over the others, +-inf included, in the
+ * total order of the order-preserving map of the bit pattern, k = b ^ (b >> 31 ? 0xFFFFFFFF : 0x80000000) -- so -0 < +0 and the
+ * result does not depend on the order in which the device reduces.  No non-NaN value: min = +inf, max = -inf.  There is no mean:
+ * a float sum depends on the order of the adds, and a host can restate every number this layer returns; the pivot an editor
+ * wants is the centre of the bounds. */
+int32_t gs_attr_summary(gs_ctx* ctx, const gs_attr* attr, uint32_t mask, uint32_t value, struct gs_attr_summary* out);
+/* counts: HOST u64[bins + 3]: [0, bins) the bins, [bins] below, [bins + 1] above, [bins + 2] NaN; they add up to matched.
+ * scale = (float)bins / (hi - lo), once, in f32.  Per matching splat: a NaN v goes to the NaN slot, v < lo below, v >= hi above,
+ * otherwise b = (uint32_t)((v - lo) * scale) truncated, then min(b, bins - 1).  (The conversion saturates, and a NaN product --
+ * only an infinite scale over a denormal width makes one, for v == lo -- is 0.)  Integer adds only: two runs agree bit for bit.
+ * bins outside 1..1024, a non-finite lo or hi, !(lo < hi) or hi - lo not finite in f32: GS_ERR_INVALID_ARGUMENT. */
+int32_t gs_attr_histogram(gs_ctx* ctx, const gs_attr* attr, uint32_t mask, uint32_t value, float lo, float hi, uint32_t bins, uint64_t* counts);
+/* The values of the matching splats in ascending index order, HOST pointers, gs_state_list's conventions: dst == NULL: only *n
+ * (query); cap < *n: GS_ERR_INVALID_ARGUMENT, the message names the count needed, nothing is written.  ids (may be NULL, else cap
+ * entries) receives the indices.  (0, 0): dense over 0 .. N, no selection runs.  4 B moved per match where an export moves 320. */
+int32_t gs_attr_read(gs_ctx* ctx, const gs_attr* attr, uint32_t mask, uint32_t value, float* dst, uint64_t cap, uint64_t* n, uint32_t* ids);
+/* Applies `op` with `bits` exactly as gs_state_region does, to the splats that pass (s & where_mask) == where_value and for which
+ *     (v >= lo && v <= hi) == (inside != 0)
+ * A NaN v is in no range: inside = 0 with lo = -inf, hi = +inf selects exactly the NaN splats.  A NaN lo or hi is refused,
+ * infinite bounds are allowed, lo > hi is a valid empty range.  Needs GS_FLAG_SPLAT_STATE; *matched (may be NULL) as for
+ * gs_state_region.  One streaming pass: the state byte and the kind's bytes per splat. */
+int32_t gs_state_attr(gs_ctx* ctx, const gs_attr* attr, float lo, float hi, uint32_t inside, uint32_t where_mask, uint32_t where_value,
+                      uint32_t op, uint32_t bits, uint64_t* matched);
+
 /* Tuning / profiling knobs. */
 #define GS_OPT_BLEND_ABLATION 1  /* bit 3 (8): the workgroup-per-tile blend kernel at tiles 16 and 32 (identical results; default = one
                                     wave per 8x8 pixel block); bit 2 (4): every blend kernel without its two parking culls (live box,
