@@ -93,7 +93,9 @@ __global__ __launch_bounds__(SCAN_THREADS) void gs_scan_kernel(const uint32_t* _
         block_total = sat_add(block_total, t);
         block_nz += z;
     }
-    uint32_t run = sat_add(wave_excl, incl - tsum); // incl - tsum: the exclusive in-wave prefix (exact unless incl saturated)
+    // the exclusive in-wave prefix is the lane below's inclusive one (incl - tsum is not: a saturated incl has lost the sum)
+    const uint32_t below = __shfl_up(incl, 1, 64);
+    uint32_t run = sat_add(wave_excl, lane ? below : 0u);
 
     if (w == 0) {
         const unsigned long long mine = ((unsigned long long)block_nz << 32) | (unsigned long long)block_total;
@@ -144,17 +146,17 @@ __global__ __launch_bounds__(SCAN_THREADS) void gs_scan_kernel(const uint32_t* _
 #pragma unroll
         for (int j = 0; j < SCAN_ITEMS / 4; ++j) {
             uint4 q;
-            q.x = run; run += v[4 * j] & GS_COUNT_MASK;
-            q.y = run; run += v[4 * j + 1] & GS_COUNT_MASK;
-            q.z = run; run += v[4 * j + 2] & GS_COUNT_MASK;
-            q.w = run; run += v[4 * j + 3] & GS_COUNT_MASK;
+            q.x = run; run = sat_add(run, v[4 * j] & GS_COUNT_MASK);
+            q.y = run; run = sat_add(run, v[4 * j + 1] & GS_COUNT_MASK);
+            q.z = run; run = sat_add(run, v[4 * j + 2] & GS_COUNT_MASK);
+            q.w = run; run = sat_add(run, v[4 * j + 3] & GS_COUNT_MASK);
             p[j] = q;
         }
     } else {
 #pragma unroll
         for (int j = 0; j < SCAN_ITEMS; ++j) {
             if (base + j < n) offsets[base + j] = run;
-            run += v[j] & GS_COUNT_MASK;
+            run = sat_add(run, v[j] & GS_COUNT_MASK);
         }
     }
 }

@@ -617,8 +617,8 @@ int32_t gs_assemble_slabs(gs_ctx* ctx, const void* d_slabs, const uint32_t* col_
 /* GPUSorter.sort (radix_sort/sort.ts:341-350): stable ascending sort of n u32 keys with u32 payloads,
  * host buffers, in place.  values may be NULL (keys only, as testSort does: radix_sort/utils.ts:55-81). */
 int32_t gs_sort_pairs_u32(int32_t device, uint32_t* keys, uint32_t* values, uint64_t n, uint32_t key_bits);
-/* ExclusiveScanner.scan (exclusive_scan.ts:208-325): in-place exclusive scan of n u32 (each < 2^22, the
- * sum < 2^32), returns the total. */
+/* ExclusiveScanner.scan (exclusive_scan.ts:208-325): in-place exclusive scan of n u32 (each < 2^22), returns the
+ * total.  Sums saturate instead of wrapping: every offset is min(true prefix, 2^32 - 1), and so is the total. */
 int32_t gs_exclusive_scan_u32(int32_t device, uint32_t* data, uint64_t n, uint64_t* total);
 
 #ifdef __cplusplus

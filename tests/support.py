@@ -101,6 +101,19 @@ def pixel_uniforms(W, H):
     return u
 
 
+def pinhole(W, H):
+    """Identity view, w = z: depth = the splat's z, ndc = (x, y) / z, focal = half the canvas."""
+    u = np.zeros(40, dtype=np.float32)
+    u[0] = u[5] = u[10] = u[15] = 1.0
+    u[16] = u[21] = 1.0
+    u[26] = 1.0
+    u[27] = 1.0
+    u[35] = u[36] = 1.0
+    u[37], u[38] = W / 2.0, H / 2.0
+    u[39] = 1.0
+    return u
+
+
 def make_splats(W, H, px, py, sig_long, sig_short, theta, logit, color=None, rng=None):
     """Records with centres (px, py) in pixels, pixel-space standard deviations (before the projection's +0.3 px^2) along the
     axes of a rotation by theta about the view axis, opacity logits.  Depth 1 for all: the list order is the record order."""

@@ -361,6 +361,98 @@ def test_scan_definition(n):
     assert total == int(data.sum())
 
 
+def _check_sort(keys, key_bits, with_values=True):
+    from gsplat import _abi
+    keys = np.asarray(keys, dtype=np.uint32)
+    vals = np.arange(keys.size, dtype=np.uint32)[::-1].copy() if with_values else None
+    k, v = _abi.sort_pairs(keys, vals, key_bits=key_bits)
+    order = np.argsort(keys, kind="stable")
+    np.testing.assert_array_equal(k, keys[order])
+    if with_values:
+        np.testing.assert_array_equal(v, vals[order])
+    else:
+        assert v is None
+
+
+_SORT_TILE_N = [8191, 8192, 8193, 16384, 16385]  # one full tile of k_sort.hip's 8192 pairs -1 / 0 / +1, two full tiles 0 / +1
+
+
+@pytest.mark.parametrize("n", _SORT_TILE_N)
+@pytest.mark.parametrize("pattern", ["equal", "sorted", "reversed", "two_keys", "all_pad_value", "top_digit_only"])
+def test_sort_pairs_key_patterns_around_the_sort_tile(n, pattern):
+    """Full and padded sort tiles on keys that put a whole tile into one digit, into two, or leave only the last pass anything
+    to do; keys equal to the pad's own value (0xFFFFFFFF) must still come out, all of them, in their order."""
+    rng = np.random.default_rng(n)
+    bits = 32
+    if pattern == "equal":
+        keys = np.full(n, 0x00C0FFEE, np.uint32)
+    elif pattern == "sorted":
+        keys = np.sort(rng.integers(0, 1 << 32, size=n, dtype=np.uint64)).astype(np.uint32)
+    elif pattern == "reversed":
+        keys = np.sort(rng.integers(0, 1 << 32, size=n, dtype=np.uint64))[::-1].astype(np.uint32)
+    elif pattern == "two_keys":
+        keys = np.where(rng.integers(0, 2, n) == 1, 0xFFFFFFFE, 0x00000100).astype(np.uint32)
+    elif pattern == "all_pad_value":
+        keys = np.full(n, 0xFFFFFFFF, np.uint32)
+    else:
+        keys = (rng.integers(0, 256, n).astype(np.uint32) << np.uint32(24)) | np.uint32(0x00345678)
+    _check_sort(keys, bits)
+
+
+@pytest.mark.parametrize("n", _SORT_TILE_N)
+@pytest.mark.parametrize("key_bits", [1, 8, 9, 16, 17, 24, 25])
+def test_sort_pairs_key_bits_around_the_pass_counts(n, key_bits):
+    """key_bits on either side of every pass count (1 .. 4 passes of 8 bits), keys below 2**key_bits, the largest one included."""
+    rng = np.random.default_rng(1000 * key_bits + n)
+    keys = rng.integers(0, 1 << key_bits, size=n, dtype=np.uint64).astype(np.uint32)
+    keys[n // 2] = (1 << key_bits) - 1
+    keys[n - 1] = (1 << key_bits) - 1  # the last slot of the last tile, next to the pads
+    _check_sort(keys, key_bits)
+
+
+def test_sort_pairs_without_values():
+    rng = np.random.default_rng(5)
+    _check_sort(rng.integers(0, 1 << 32, size=8193, dtype=np.uint64).astype(np.uint32), 32, with_values=False)
+
+
+_COUNT_MAX = (1 << 22) - 1  # the documented extreme of a tile count (gs_abi.h gs_exclusive_scan_u32)
+
+
+def _check_scan(data):
+    from gsplat import _abi
+    data = np.asarray(data, dtype=np.uint32)
+    out, total = _abi.exclusive_scan(data)
+    csum = np.cumsum(data, dtype=np.uint64)
+    ref = np.minimum(np.concatenate([[0], csum[:-1]]).astype(np.uint64), np.uint64(0xFFFFFFFF)).astype(np.uint32)
+    np.testing.assert_array_equal(out, ref)
+    assert total == min(int(csum[-1]), 0xFFFFFFFF)
+    return out
+
+
+@pytest.mark.parametrize("n", [23, 24, 25, 24575, 24576, 24577, 49153])
+def test_scan_around_its_own_block_sizes(n):
+    """k_binning.hip: a thread scans 24 counts (one vector path for whole threads), a workgroup 24576; two workgroups + 1."""
+    rng = np.random.default_rng(n)
+    _check_scan(rng.integers(0, 50, size=n, dtype=np.uint32))
+    big = rng.integers(0, 50, size=n, dtype=np.uint32)
+    big[rng.integers(0, n, 20)] = _COUNT_MAX  # the extreme value, at the ends too; 22 of them stay below 2^32
+    big[0] = big[n - 1] = _COUNT_MAX
+    _check_scan(big)
+    if n <= 1024:
+        _check_scan(np.full(n, _COUNT_MAX, np.uint32))  # every count at the extreme
+
+
+def test_scan_saturates_instead_of_wrapping():
+    """3000 counts of 2^22 - 1 sum to 1.26e10: every offset is min(true prefix, 2^32 - 1) and so is the total (a frame of more
+    than 2^32 instances reports I = 0xFFFFFFFF and gs_wait answers GS_ERR_CAPACITY).  The prefix of index 1024 (4 294 966 272) is
+    the last one below 2^32; the first saturated offset is index 1025."""
+    out = _check_scan(np.full(3000, _COUNT_MAX, np.uint32))
+    assert out[1024] == 1024 * _COUNT_MAX and out[1025] == 0xFFFFFFFF and (out[1025:] == 0xFFFFFFFF).all()
+    # ... and across workgroups: 49153 counts of 2^17 reach 2^32 at index 32768, inside the second workgroup's 24576
+    out = _check_scan(np.full(49153, 1 << 17, np.uint32))
+    assert out[32767] == 0xFFFE0000 and out[32768] == 0xFFFFFFFF
+
+
 def test_determinism_and_reuse(oracle):
     """Same frame twice => identical bytes; a second camera on the same ctx matches the oracle."""
     from gsplat import _abi

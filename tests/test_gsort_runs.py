@@ -13,6 +13,7 @@ import pytest
 
 from conftest import scene
 from gpu_checks import check_stages, make_renderer, orbit_uniforms
+from support import pinhole as _pinhole
 
 pytestmark = pytest.mark.gpu
 
@@ -45,19 +46,6 @@ def _both_binnings(oracle, s, u, G, ref=None, W=W, H=H):
 
 def _buckets(ref):
     return np.unique(ref["sorted_keys"].astype(np.int64) % 1000)
-
-
-def _pinhole(W, H):
-    """Identity view, w = z: depth = the splat's z, focal = half the canvas."""
-    u = np.zeros(40, dtype=np.float32)
-    u[0] = u[5] = u[10] = u[15] = 1.0
-    u[16] = u[21] = 1.0
-    u[26] = 1.0
-    u[27] = 1.0
-    u[35] = u[36] = 1.0
-    u[37], u[38] = W / 2.0, H / 2.0
-    u[39] = 1.0
-    return u
 
 
 def _small_splats(n, z, key):
