@@ -40,7 +40,8 @@ int32_t alloc_kv(gs_ctx* c, uint64_t capacity, uint64_t row_cap) {
     c->gr.valid = false; // (callers have drained the stream: no replay of the captured frame is in flight)
     c->keysA.reset(); c->valsA.reset(); c->keysB.reset(); c->valsB.reset(); c->keysU.reset(); c->valsU.reset();
     c->keysG.reset(); c->chunk_table.reset(); c->arena.reset(); c->rows_sorted.reset(); c->M3.reset(); c->ctl_mem.reset();
-    c->keysG_valid = false;
+    c->valsG.reset();
+    c->keysG_valid = c->valsG_valid = c->gdataG_valid = false;
     capacity = std::max<uint64_t>(capacity, 4096);
     row_cap = (std::max<uint64_t>(row_cap, 4096) + 15) & ~(uint64_t)15;
     const size_t kb = (size_t)capacity * 4;
@@ -179,15 +180,15 @@ static int32_t alloc_per_gaussian(gs_ctx* c, uint64_t n, uint64_t min_capacity =
     c->frame.n = (uint32_t)n;
     c->have_frame = false;
     c->cov.reset(); // the coverage planes describe the scene that goes: they read as zero afterwards
-    c->counts.reset(); c->offsets.reset(); c->grec.reset(); c->rowptr.reset(); c->gsort_scratch.reset(); c->gdata.reset();
+    c->counts.reset(); c->offsets.reset(); c->grec.reset(); c->rowptr.reset(); c->gsort_scratch.reset(); c->gdata.reset(); c->gdataG.reset();
     const size_t np = ((size_t)n + 63) & ~(size_t)63;
     HIP_TRY(hipMalloc(c->counts.out(), std::max<size_t>(np * 4, 256)));
     HIP_TRY(hipMalloc(c->offsets.out(), std::max<size_t>(np * 4, 256)));
     HIP_TRY(hipMalloc(c->grec.out(), std::max<size_t>(np * 16, 256)));
     HIP_TRY(hipMalloc(c->rowptr.out(), std::max<size_t>(np * 4, 256)));
     HIP_TRY(hipMalloc(c->gsort_scratch.out(), gs_gsort_scratch_bytes((uint32_t)n)));
-    HIP_TRY(hipMalloc(c->gdata.out(), std::max<size_t>((size_t)n * 64, 256)));
-    HIP_TRY(hipMemsetAsync(c->gdata, 0, std::max<size_t>((size_t)n * 64, 256), c->stream));
+    HIP_TRY(hipMalloc(c->gdata.out(), ((size_t)n + GS_RECORD_SLACK) * 64));
+    HIP_TRY(hipMemsetAsync(c->gdata, 0, ((size_t)n + GS_RECORD_SLACK) * 64, c->stream));
     uint64_t cap = c->cfg.max_intersections ? c->cfg.max_intersections : std::max<uint64_t>(4 * n, 1u << 22);
     cap = std::max<uint64_t>(cap, min_capacity);
     cap = std::min<uint64_t>(cap, (1ull << 30) - 1);

@@ -40,6 +40,7 @@ struct GsControl {
     uint32_t num_visible;
     uint32_t pad0;
     uint32_t row_cursor[16];  // tight projection: slots handed out of each of the arena's 16 shards
+    uint32_t rec_cursor[16];  // ... and GaussianData records handed out of each of the record array's 16 shards (k_preprocess.hip)
     unsigned long long num_processed[64]; // blend: staged list entries (64 partial sums)
     unsigned long long num_evaluated[64]; // blend: (wave, entry) pairs that survived the 8x8 cull
     uint32_t hist[4][256];    // instance sort: digit histograms -> exclusive digit bases
@@ -86,7 +87,12 @@ __device__ __forceinline__ void gs_frame_report(const GsControl* ctl, uint32_t I
 
 struct GsTightOut { // product-path outputs of the tight projection beside GaussianData and the count words (k_preprocess.hip)
     uint32_t* arena; uint32_t* rowptr; GsControl* ctl;
+    uint32_t rec_shard_cap; // records each of the 16 shards of the record array holds
 };
+// Records the GaussianData array of a scene of n gaussians holds: the tight projection hands out record slots in 16 shards of
+// ceil(workgroups / 16) workgroups' worth of gaussians each (at most 8 cull chunks of 512 per workgroup), so up to 15 workgroups'
+// worth lie beyond n.  A frame of the reference's binning uses the first n (slot = index).
+#define GS_RECORD_SLACK (16u * 512u * 8u)
 
 struct GsScene {
     const float* px; const float* py; const float* pz; // f32[N] each: all the cull reads
@@ -285,11 +291,13 @@ struct GsListRec {
     uint32_t id;
     bool live;
 };
-// Entry i of [.., end): the three pieces of its GaussianData record.  id_mask: on a tight frame the sub-block mask rides above the
-// id (gs_tight.h); want: the bit of that mask the caller's block needs (0: every entry; an entry without it stays dead and its
-// record is not gathered).
+// Entry i of [.., end): the three pieces of its GaussianData record.  A list value names the record's SLOT (the gaussian's index
+// on a frame of the reference's binning, a slot of the tight projection's otherwise); the gaussian's id is word 2 of the record,
+// fetched with the uv.  id_mask: on a tight frame the sub-block mask rides above the slot (gs_tight.h); want: the bit of that mask
+// the caller's block needs (0: every entry; an entry without it stays dead and its record is not gathered).  nrec: records the
+// array holds; n: gaussians.
 __device__ __forceinline__ GsListRec gs_list_fetch(const uint4* __restrict__ gdata, const uint32_t* __restrict__ values, uint32_t i, uint32_t end,
-                                                   uint32_t id_mask, uint32_t want, uint32_t n) {
+                                                   uint32_t id_mask, uint32_t want, uint32_t nrec, uint32_t n) {
     GsListRec r;
     r.ux = r.uy = r.cx = r.cy = r.cz = r.z = r.op = 0.0f;
     r.id = 0u;
@@ -297,14 +305,14 @@ __device__ __forceinline__ GsListRec gs_list_fetch(const uint4* __restrict__ gda
     if (i < end) {
         const uint32_t v = values[i];
         const uint32_t g = v & id_mask;
-        if (g < n && (want == 0u || (v & want) != 0u)) { // (a list never holds an id >= n; never gather out of bounds)
+        if (g < nrec && (want == 0u || (v & want) != 0u)) { // (a list never holds a slot >= nrec; never gather out of bounds)
             const uint4 p0 = gdata[(uint64_t)g * 4 + 0];
             const uint4 p1 = gdata[(uint64_t)g * 4 + 1];
             r.op = __uint_as_float(((const uint32_t*)gdata)[(uint64_t)g * 16 + 11]);
             r.ux = __uint_as_float(p0.x); r.uy = __uint_as_float(p0.y);
             r.cx = __uint_as_float(p1.x); r.cy = __uint_as_float(p1.y); r.cz = __uint_as_float(p1.z); r.z = __uint_as_float(p1.w);
-            r.id = g;
-            r.live = true;
+            r.id = p0.z;
+            r.live = p0.z < n; // (a listed record was written by this frame's projection: always; keeps a caller's per-splat array safe)
         }
     }
     return r;

@@ -45,7 +45,9 @@ static inline void mark(gs_ctx* c, int i) { // stage boundary i: closes stage i-
 static void mark_cb(void* p, int i) { mark((gs_ctx*)p, i); }
 
 GsLists frame_lists(const gs_ctx* c) {
-    return GsLists{c->gdata, c->notes.valsS, c->ranges, c->frame, c->notes.last_tight ? GS_ID_MASK : 0xFFFFFFFFu};
+    // (records: a tight frame's slots reach into the slack behind the first n, and its n is below 2^28; any other frame's are its n)
+    return GsLists{c->gdata, c->notes.valsS, c->ranges, c->frame, c->notes.last_tight ? GS_ID_MASK : 0xFFFFFFFFu,
+                   c->notes.last_tight ? c->n + GS_RECORD_SLACK : c->n};
 }
 
 // The projection's launch for this frame, left in c->pre: record_frame launches it, a replay patches the captured node from it.
@@ -165,8 +167,9 @@ static int32_t enqueue_frame(gs_ctx* c, const GsUniforms& u, bool debug, void* e
         const uint64_t saved = c->passes > c->tile_passes ? c->passes - c->tile_passes : 0;
         index_order = !(c->have_frame && saved * (uint64_t)c->h_rep->num_intersections >= 1000000ull);
     }
-    // tight (opacity-aware) binning: product frames only; the sub-block mask shares the value word with the gaussian id
-    const bool tight = !debug && c->opt.tile_cull && c->tight_ok && c->n < (1u << GS_ID_BITS);
+    // tight (opacity-aware) binning: product frames only; the sub-block mask shares the value word with the record slot, and the
+    // largest slot the projection can hand out is below n + GS_RECORD_SLACK
+    const bool tight = !debug && c->opt.tile_cull && c->tight_ok && (uint64_t)c->n + GS_RECORD_SLACK <= (1ull << GS_ID_BITS);
     // GS_OPT_FRAME_GRAPH: replay the captured frame instead of issuing its ~16 commands one by one (frames without per-stage
     // events or profiler output only).  The capture holds every buffer address and launch geometry of the frame, so anything
     // that moves a buffer or changes an option drops it (gr.valid); the emission order and the output address are part
@@ -218,7 +221,7 @@ static int32_t enqueue_frame(gs_ctx* c, const GsUniforms& u, bool debug, void* e
         const int32_t rc = record_frame(c, u, debug, ext_rgba8, tight, index_order);
         if (rc != GS_OK) return rc;
     }
-    c->keysG_valid = false;
+    c->keysG_valid = c->valsG_valid = c->gdataG_valid = false;
     c->h_ctl_valid = false; // (a replayed frame too: record_frame, which also clears it, only runs for the capture)
     HIP_TRY(hipGetLastError());
     c->pending = true;

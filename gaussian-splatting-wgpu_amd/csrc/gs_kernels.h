@@ -44,14 +44,16 @@ struct GsSort {
 };
 GsSortPair gs_launch_sort(const GsSort& s, GsControl* ctl, uint32_t* status, uint32_t capacity, uint32_t grid, hipStream_t st); // the pair that holds the result
 // The lists of one frame as their readers take them (blend, pick, coverage): the projection's records, the values in list order, the
-// per-tile ranges, the frame geometry, and the mask that leaves a value's gaussian id (GS_ID_MASK where the sub-block mask of the
-// tight binning rides above it, all ones otherwise).
+// per-tile ranges, the frame geometry, and the mask that leaves a value's record slot (GS_ID_MASK where the sub-block mask of the
+// tight binning rides above it, all ones otherwise).  A value names the record at gdata + 64 * slot; the gaussian's id is word 2
+// of that record (slot = id on a frame of the reference's binning).  nrec: records the array holds.
 struct GsLists {
     const void* gdata;
     const uint32_t* values;
     const uint32_t* ranges;
     GsFrame f;
     uint32_t id_mask;
+    uint32_t nrec;
 };
 int gs_launch_blend(const GsLists& L, uint32_t* rgba8, float* rgbf, bool aux, float* alpha, float* depth, GsControl* ctl, uint32_t* tile_depth,
                     bool exact, uint32_t ablation, hipStream_t st, uint32_t* prof = nullptr, uint32_t* prof_blocks = nullptr);
@@ -69,8 +71,13 @@ uint32_t gs_rows_chunks(uint64_t row_cap);
 void gs_launch_rows(const uint32_t* arena, const void* grec, const uint32_t* chunk_table, uint32_t* rows_sorted, GsControl* ctl, uint32_t* sort_status, uint32_t row_cap,
                     uint32_t* M3, uint32_t* tileoff, uint32_t* rowtot, const GsFrame& f, uint32_t* values, uint32_t* ranges, uint32_t cus,
                     uint32_t* sticky, GsReport* rep, hipStream_t st, void (*mark)(void*, int), void* mark_arg);
-void gs_launch_rows_rebuild_keys(const uint32_t* ranges, uint32_t T, const uint32_t* vals, const uint32_t* counts, uint32_t count, uint32_t n,
-                                 uint32_t* keys, hipStream_t st);
+// the taps of a tight frame, whose lists name record slots (gdata: its records, nrec of them): the keys; the values with the
+// gaussian's id in the slot's place (ids_out, may be null); the records in index order, id word cleared (gdata_out, zeroed by the
+// caller, may be null)
+void gs_launch_rows_rebuild_keys(const uint32_t* ranges, uint32_t T, const uint32_t* vals, const void* gdata, uint32_t nrec, const uint32_t* counts,
+                                 uint32_t count, uint32_t n, uint32_t* keys, hipStream_t st);
+void gs_launch_rows_rebuild_taps(const uint32_t* vals, const void* gdata, uint32_t nrec, uint32_t count, uint32_t n, uint32_t* ids_out, void* gdata_out,
+                                 hipStream_t st);
 // k_state.hip: the state plane's streaming kernels (gs_state.hip).  The plane is 256-byte aligned with np >= n bytes behind it.
 struct GsRegionDev { // a gs_region as the kernel reads it
     float a[3], b[3];       // SPHERE: centre, radius in b[0].  BOX: min, max

@@ -6,6 +6,26 @@
 #include "gs_runtime.h"
 #include "gs_tight.h"
 
+// A tight frame's lists name record slots and its records lie in slot order (k_preprocess.hip).  The taps keep their documented
+// contents -- gaussian ids in the values, records at 64 * gaussian index -- in buffers rebuilt from the frame once, on demand.
+static int32_t tight_tap(gs_ctx* c, bool want_gdata) {
+    if (want_gdata ? c->gdataG_valid : c->valsG_valid) return GS_OK;
+    if (c->pending) { int32_t rc = wait_one(c); if (rc != GS_OK) return rc; }
+    const uint64_t I = std::min<uint64_t>(c->h_rep->num_intersections, c->capacity); // (of the frame waited for)
+    const GsLists L = frame_lists(c);
+    const size_t gbytes = std::max<size_t>((size_t)c->n * 64, 256);
+    if (want_gdata) {
+        if (!c->gdataG) HIP_TRY(hipMalloc(c->gdataG.out(), gbytes));
+        HIP_TRY(hipMemsetAsync(c->gdataG, 0, gbytes, c->stream)); // gaussians without a record: all-zero
+    } else if (!c->valsG) HIP_TRY(hipMalloc(c->valsG.out(), (size_t)c->capacity * 4));
+    gs_launch_rows_rebuild_taps(L.values, L.gdata, L.nrec, (uint32_t)I, c->n, want_gdata ? nullptr : c->valsG.get(),
+                                want_gdata ? c->gdataG.get() : nullptr, c->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    (want_gdata ? c->gdataG_valid : c->valsG_valid) = true;
+    return GS_OK;
+}
+
 static int32_t tap(gs_ctx* c, int32_t which, void** ptr, uint64_t* bytes) {
     const FrameNotes& nt = c->notes;
     const uint64_t I = std::min<uint64_t>(c->h_rep->num_intersections, c->capacity);
@@ -15,7 +35,12 @@ static int32_t tap(gs_ctx* c, int32_t which, void** ptr, uint64_t* bytes) {
     case GS_BUF_TILE_OFFSETS:
         if (!c->last_debug) return fail(GS_ERR_NO_FRAME, "the offsets tap needs gs_render_debug (index-order scan)");
         *ptr = c->offsets; *bytes = (uint64_t)c->n * 4; return GS_OK;
-    case GS_BUF_GAUSSIAN_DATA: *ptr = c->gdata; *bytes = (uint64_t)c->n * 64; return GS_OK;
+    case GS_BUF_GAUSSIAN_DATA:
+        *bytes = (uint64_t)c->n * 64;
+        if (!nt.last_tight) { *ptr = c->gdata; return GS_OK; } // (word 2 of a record holds the gaussian's id: gs_read_buffer clears it)
+        if (const int32_t rc = tight_tap(c, true); rc != GS_OK) return rc;
+        *ptr = c->gdataG;
+        return GS_OK;
     case GS_BUF_KEYS_UNSORTED:
     case GS_BUF_VALUES_UNSORTED:
         if (!c->last_debug || !c->keysU) return fail(GS_ERR_NO_FRAME, "unsorted taps need gs_render_debug");
@@ -26,7 +51,7 @@ static int32_t tap(gs_ctx* c, int32_t which, void** ptr, uint64_t* bytes) {
         if (!c->keysG_valid) { // the frame never held full keys (16-bit tile ids, or no keys at all on the tight row pipeline): rebuild tile*1000 + bucket once
             if (c->pending) { int32_t rc = wait_one(c); if (rc != GS_OK) return rc; }
             if (!c->keysG) HIP_TRY(hipMalloc(c->keysG.out(), (size_t)c->capacity * 4));
-            if (nt.last_tight) gs_launch_rows_rebuild_keys(c->ranges, c->T, nt.valsS, c->counts, (uint32_t)I, c->n, c->keysG, c->stream);
+            if (nt.last_tight) gs_launch_rows_rebuild_keys(c->ranges, c->T, nt.valsS, c->gdata, c->n + GS_RECORD_SLACK, c->counts, (uint32_t)I, c->n, c->keysG, c->stream);
             else gs_launch_rebuild_keys((const uint16_t*)nt.keysS, nt.valsS, c->counts, (uint32_t)I, c->n, c->keysG, c->stream);
             HIP_TRY(hipStreamSynchronize(c->stream));
             c->keysG_valid = true;
@@ -34,7 +59,12 @@ static int32_t tap(gs_ctx* c, int32_t which, void** ptr, uint64_t* bytes) {
         *ptr = c->keysG;
         return GS_OK;
     case GS_BUF_VALUES:
-    case GS_BUF_BLOCK_MASKS: *ptr = nt.valsS; *bytes = I * 4; return GS_OK; // tight frames: id | mask << 28 (gs_read_buffer separates them)
+    case GS_BUF_BLOCK_MASKS: // tight frames: id | mask << 28 (gs_read_buffer separates them), rebuilt from the frame's slot | mask << 28
+        *bytes = I * 4;
+        if (!nt.last_tight) { *ptr = nt.valsS; return GS_OK; }
+        if (const int32_t rc = tight_tap(c, false); rc != GS_OK) return rc;
+        *ptr = c->valsG;
+        return GS_OK;
     case GS_BUF_RANGES: *ptr = c->ranges; *bytes = (uint64_t)c->T * 4; return GS_OK;
     case GS_BUF_RGBA8: *ptr = c->last_ext ? c->last_ext : (void*)c->rgba8.get(); *bytes = px * 4; return GS_OK;
     case 12: // TESTS ONLY: the resident scene arrays as one block (position planes, largest log-scale, geometry, SH records)
@@ -115,7 +145,9 @@ GS_EXPORT int32_t gs_read_buffer(gs_ctx* c, int32_t which, void* dst, uint64_t s
     }
     if (list_counts) {
         std::vector<uint32_t> v(I);
-        if (I) HIP_TRY(hipMemcpy(v.data(), L.values, I * 4, hipMemcpyDeviceToHost));
+        uint64_t vbytes = 0;
+        { int32_t rc = tap(c, GS_BUF_VALUES, &p, &vbytes); if (rc != GS_OK) return rc; } // (gaussian ids: the frame's own values name record slots)
+        if (I) HIP_TRY(hipMemcpy(v.data(), p, I * 4, hipMemcpyDeviceToHost));
         memset(w, 0, bytes);
         for (uint64_t i = 0; i < I; ++i) { const uint32_t g = v[i] & L.id_mask; if (g < c->n) w[g]++; }
         return GS_OK;
@@ -123,6 +155,8 @@ GS_EXPORT int32_t gs_read_buffer(gs_ctx* c, int32_t which, void* dst, uint64_t s
     if (bytes) HIP_TRY(hipMemcpy(dst, p, bytes, hipMemcpyDeviceToHost));
     if (which == GS_BUF_TILE_COUNTS) // device words also carry the depth bucket in their high 10 bits
         for (uint64_t i = 0; i < bytes / 4; ++i) w[i] &= GS_COUNT_MASK;
+    if (which == GS_BUF_GAUSSIAN_DATA && !tight) // the record's id word: padding in the reference's record (a tight frame's copy has it cleared)
+        for (uint64_t i = 0; i < bytes / 64; ++i) w[i * 16 + 2] = 0u;
     if (which == GS_BUF_VALUES && L.id_mask != 0xFFFFFFFFu) // strip what rides above the id
         for (uint64_t i = 0; i < bytes / 4; ++i) w[i] &= L.id_mask;
     if (which == GS_BUF_BLOCK_MASKS) { // tight frame: the mask's sub-blocks (tile/2, or the whole 8-pixel tile) as 8x8-block bits

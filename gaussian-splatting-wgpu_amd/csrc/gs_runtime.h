@@ -138,7 +138,7 @@ struct gs_ctx {
     uint32_t n = 0;
     // per-gaussian frame buffers (alloc_per_gaussian)
     DevBuf<uint32_t> counts, offsets, rowptr;
-    DevBuf<> gdata;
+    DevBuf<> gdata;             // n + GS_RECORD_SLACK records (the tight projection's record slots, gs_device.h)
     DevBuf<> grec;              // visible gaussians in (depth bucket, index) order: {id, count word, prefix, arena address} (k_gsort.hip)
     DevBuf<> gsort_scratch;     // (bucket, run) table of the gaussian-level counting sort
     // (key,value) arrays and what grows with them (alloc_kv)
@@ -148,6 +148,11 @@ struct gs_ctx {
     DevBuf<uint32_t> keysU, valsU;  // debug copies of the unsorted arrays, allocated by the first gs_render_debug
     DevBuf<uint32_t> keysG;         // full keys rebuilt on demand from a frame that holds u16 tile ids or none (GS_BUF_KEYS)
     bool keysG_valid = false;
+    // a tight frame's lists name record slots and its records lie in slot order (k_preprocess.hip): the taps that document gaussian
+    // ids / index order are rebuilt on demand, once per frame, like keysG (gs_readback.hip)
+    DevBuf<uint32_t> valsG;         // GS_BUF_VALUES / GS_BUF_BLOCK_MASKS: gaussian id | sub-block mask << 28
+    DevBuf<> gdataG;                // GS_BUF_GAUSSIAN_DATA: N x 64 B in index order, id word cleared, all-zero where the frame left no record
+    bool valsG_valid = false, gdataG_valid = false;
     DevBuf<uint32_t> chunk_table;   // balanced emission: first gaussian of every EMIT_CHUNK output slots
     // tight row pipeline (k_rows.hip): row items in projection order / sorted by tile row, slot addresses in depth order
     uint64_t row_cap = 0;
@@ -219,7 +224,7 @@ void drop_shadows(gs_ctx* c);
 void drop_graph(gs_ctx* c);
 int32_t wait_one(gs_ctx* c);
 // The lists of the last frame `c` enqueued, as the blend of that frame and the queries on it read them.  The one place that
-// knows that a tight frame's values carry the sub-block mask above the gaussian id.
+// knows that a tight frame's values carry the sub-block mask above the record slot.
 GsLists frame_lists(const gs_ctx* c);
 // The sum -- or the maximum -- of get(member) over the ring {root, its shadows}.
 template <class Get>

@@ -24,7 +24,8 @@
 #pragma once
 #include "gs_device.h"
 
-#define GS_ID_BITS 28                // sorted values of a tight frame: gaussian id | sub-block mask << 28
+#define GS_ID_BITS 28                // sorted values of a tight frame: record slot | sub-block mask << 28 (the slot names the gaussian's
+                                     // GaussianData record, whose word 2 holds the gaussian's id: k_preprocess.hip)
 #define GS_ID_MASK 0x0FFFFFFFu
 
 struct TightG {
@@ -218,7 +219,7 @@ __device__ __forceinline__ void tight_substrips(const TightG& g, uint32_t ty, ui
 // 12-byte ROW ITEM; everything downstream (sorting the items by tile row, expanding them into per-tile lists) is integer work
 // on these records -- round 2's emission recomputed the chords of every row from the 64-byte GaussianData record
 // (295 lane-instructions per instance, instruction bound at 0.147 of the HBM roofline).
-//   w0  gaussian id (28 bits); 0xFFFFFFFF = hole (a slot whose row turned out empty)
+//   w0  record slot of the gaussian (28 bits; NOT its id: the record holds that); 0xFFFFFFFF = hole (a slot whose row turned out empty)
 //   w1  tile row | first tile column << 8 | (tiles - 1) << 16                     (each < 256: tight binning needs ntx, nty <= 255)
 //   w2  l0 | h0 << 8 | l1 << 16 | h1 << 24: sub-block columns [l, h) touched in the upper / lower half strip, relative to the
 //       run's first sub-block column (sub-block = tile_size / 2, or the whole 8-pixel tile: then only l0, h0); h = 255 = no end

@@ -28,7 +28,7 @@
 
 // grid: (blocks in x, blocks in y) of the 8x8 blocks [bx0, ...) x [by0, ...) the host found to intersect region, slab and canvas
 __global__ __launch_bounds__(64) void gs_coverage_kernel(const uint4* __restrict__ gdata, const uint32_t* __restrict__ values,
-                                                          const uint32_t* __restrict__ ranges, GsFrame f, uint32_t id_mask, uint32_t bx0,
+                                                          const uint32_t* __restrict__ ranges, GsFrame f, uint32_t id_mask, uint32_t nrec, uint32_t bx0,
                                                           uint32_t by0, GsCoverDev r, uint32_t* __restrict__ planes) {
     const uint32_t lane = lane_id();
     const uint32_t ox = (bx0 + blockIdx.x) * 8u, oy = (by0 + blockIdx.y) * 8u; // the block's first pixel
@@ -51,9 +51,9 @@ __global__ __launch_bounds__(64) void gs_coverage_kernel(const uint4* __restrict
     const float Wf = (float)f.width, Hf = (float)f.height;
     const float c255 = (float)(1.0 / 255.0);
     float T = 1.0f;
-    GsListRec cur = gs_list_fetch(gdata, values, start + lane, end, id_mask, want, f.n);
+    GsListRec cur = gs_list_fetch(gdata, values, start + lane, end, id_mask, want, nrec, f.n);
     for (uint32_t b = start; b < end; b += 64u) {
-        const GsListRec nxt = gs_list_fetch(gdata, values, b + 64u + lane, end, id_mask, want, f.n); // in flight while this chunk is resolved
+        const GsListRec nxt = gs_list_fetch(gdata, values, b + 64u + lane, end, id_mask, want, nrec, f.n); // in flight while this chunk is resolved
         // The blend walkers' two parking culls (gs_device.h; k_blend.hip tells what they save), taken by the lane that fetched the
         // entry: it stays only if its alpha >= 1/255 ellipse reaches the bounding box of the pixels that are still LIVE, and if
         // the largest T among them leaves room for it (Tmax (1 - alpha_lo) >= 1e-4).  Both are conservative with margins and hold
@@ -115,5 +115,5 @@ __global__ __launch_bounds__(64) void gs_coverage_kernel(const uint4* __restrict
 
 void gs_launch_coverage(const GsLists& L, uint32_t bx0, uint32_t by0, uint32_t nbx, uint32_t nby, const GsCoverDev& r, void* planes, hipStream_t st) {
     if (!nbx || !nby) return;
-    gs_coverage_kernel<<<dim3(nbx, nby), 64, 0, st>>>((const uint4*)L.gdata, L.values, L.ranges, L.f, L.id_mask, bx0, by0, r, (uint32_t*)planes);
+    gs_coverage_kernel<<<dim3(nbx, nby), 64, 0, st>>>((const uint4*)L.gdata, L.values, L.ranges, L.f, L.id_mask, L.nrec, bx0, by0, r, (uint32_t*)planes);
 }

@@ -22,7 +22,7 @@
 #define GS_PICK_NONE_ID 0xFFFFFFFFu
 
 __global__ __launch_bounds__(64) void gs_pick_kernel(const uint4* __restrict__ gdata, const uint32_t* __restrict__ values,
-                                                      const uint32_t* __restrict__ ranges, GsFrame f, uint32_t id_mask,
+                                                      const uint32_t* __restrict__ ranges, GsFrame f, uint32_t id_mask, uint32_t nrec,
                                                       const uint2* __restrict__ queries, uint32_t* __restrict__ results,
                                                       uint32_t max_contrib, uint2* __restrict__ contrib) {
     const uint32_t q = blockIdx.x, lane = lane_id();
@@ -41,10 +41,10 @@ __global__ __launch_bounds__(64) void gs_pick_kernel(const uint4* __restrict__ g
         const float pxf = (float)xy.x, pyf = (float)xy.y;
         const float Wf = (float)f.width, Hf = (float)f.height;
         const float c255 = (float)(1.0 / 255.0);
-        GsListRec cur = gs_list_fetch(gdata, values, start + lane, end, id_mask, 0u, f.n);
+        GsListRec cur = gs_list_fetch(gdata, values, start + lane, end, id_mask, 0u, nrec, f.n);
         bool settled = false;
         for (uint32_t b = start; b < end && !settled; b += 64u) {
-            const GsListRec nxt = gs_list_fetch(gdata, values, b + 64u + lane, end, id_mask, 0u, f.n); // in flight while this chunk is resolved
+            const GsListRec nxt = gs_list_fetch(gdata, values, b + 64u + lane, end, id_mask, 0u, nrec, f.n); // in flight while this chunk is resolved
             // compute_tiles.wgsl:52-59, the head of gs_blend_exact
             const float power = gs_blend_power(cur.cx, cur.cy, cur.cz, cur.ux * Wf - pxf, cur.uy * Hf - pyf);
             const float alpha = gs_blend_alpha(cur.op, power);
@@ -100,6 +100,6 @@ __global__ __launch_bounds__(64) void gs_pick_kernel(const uint4* __restrict__ g
 
 void gs_launch_pick(const GsLists& L, const void* d_queries, uint32_t n, void* d_results, uint32_t max_contrib, void* d_contrib, hipStream_t st) {
     if (!n) return;
-    gs_pick_kernel<<<n, 64, 0, st>>>((const uint4*)L.gdata, L.values, L.ranges, L.f, L.id_mask, (const uint2*)d_queries, (uint32_t*)d_results,
+    gs_pick_kernel<<<n, 64, 0, st>>>((const uint4*)L.gdata, L.values, L.ranges, L.f, L.id_mask, L.nrec, (const uint2*)d_queries, (uint32_t*)d_results,
                                      max_contrib, (uint2*)d_contrib);
 }

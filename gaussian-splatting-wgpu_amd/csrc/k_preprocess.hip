@@ -217,6 +217,13 @@ typedef uint32_t gs_row_u32x3 __attribute__((ext_vector_type(3), aligned(4)));
 // Product-path outputs of the tight projection (TIGHT = true), beside GaussianData and the count words:
 //   arena   : 12-byte row items (gs_tight.h), handed out to workgroups by 16 bump cursors (GsControl::row_cursor; shard =
 //             workgroup % 16 owns arena slots [shard * f.row_cap / 16, ...)): a gaussian's slots are consecutive, in row order
+//   gdata   : the GaussianData record goes to a RECORD SLOT, not to 64 * gaussian index: the survivors with slots of a workgroup
+//             trip take consecutive records from the same shard's second cursor (GsControl::rec_cursor; shard s owns records
+//             [s * rec_shard_cap, ...)), so the record stores of a frame are 16 dense streams instead of 64-byte sectors at 40 %
+//             density over the whole array.  Nothing downstream needs the old address: the row items carry the slot in w0, the
+//             lists hold slot | mask << 28, and the gaussian's id is word 2 of the record.  rec_shard_cap = (workgroups of the
+//             shard) x (gaussians of a workgroup): a shard cannot overflow.  A survivor whose items all turn out empty leaves
+//             its record slot unwritten, as it leaves holes in the arena
 //   rowptr  : first arena slot of every visible gaussian
 //   counts  : SLOTS of the gaussian (rows, twice that with an aliased column) | depth bucket << 22 -- what the gaussian-level
 //             sort (k_gsort.hip) scans; 0 when no tile survives (the tile-count tap of a tight frame is derived from the lists)
@@ -454,7 +461,6 @@ __global__ __launch_bounds__(256, PRE_WAVES) void gs_preprocess_kernel(GsScene s
                     s_tB[tid] = make_float4(tg.qb, tg.rcx, tg.xmax, tg.dyR);
                     s_tC[tid] = make_float4(tg.eR, __uint_as_float(tg.mode), __uint_as_float(ra | (nrows << 16)),
                                             __uint_as_float(t_xa | (t_wmain << 16) | (t_alias << 31)));
-                    s_tgid[tid] = i;
                 }
             } else {
                 count = 0u;
@@ -464,22 +470,34 @@ __global__ __launch_bounds__(256, PRE_WAVES) void gs_preprocess_kernel(GsScene s
             const uint32_t rincl = wave_incl_scan(nslots, lane);
             const uint32_t Rw = (uint32_t)__builtin_amdgcn_readlane((int)rincl, 63); // slots of this wave's survivors
             const uint32_t myrp = rincl - nslots;
-            if (lane == 63) s_tw[w] = rincl;
+            // survivors with slots take a RECORD slot each: their number rides above the wave's slot count (64 survivors of at
+            // most 2 * 255 slots: 15 bits) through the same LDS word, their rank in the wave is a ballot's prefix
+            const unsigned long long recb = __ballot(nslots != 0u);
+            const uint32_t recrank = (uint32_t)__popcll(recb & ((1ull << lane) - 1ull));
+            if (lane == 63) s_tw[w] = rincl | ((uint32_t)__popcll(recb) << 16);
             __syncthreads();
-            uint32_t wbase = 0, R = 0;
+            uint32_t wbase = 0, R = 0, cbase = 0, C = 0;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) { if (k < (int)w) wbase += s_tw[k]; R += s_tw[k]; }
-            if (tid == 0) { // this trip's slots: one bump of the shard's cursor
-                uint32_t at = 0, ok = 1u;
+            for (int k = 0; k < 4; ++k) {
+                const uint32_t t = s_tw[k];
+                if (k < (int)w) { wbase += t & 0xFFFFu; cbase += t >> 16; }
+                R += t & 0xFFFFu; C += t >> 16;
+            }
+            if (tid == 0) { // this trip's slots and records: one bump of each of the shard's two cursors
+                uint32_t at = 0, rat = 0, ok = 1u;
                 if (R) {
                     at = atomicAdd(&to.ctl->row_cursor[shard], R);
+                    rat = atomicAdd(&to.ctl->rec_cursor[shard], C); // (cannot overflow: see rec_shard_cap)
                     if (at > shard_cap || R > shard_cap - at) { ok = 0u; to.ctl->overflow = 1u; } // the frame does not fit: gs_wait grows the arena and re-renders
                 }
-                s_misc[2] = at; s_misc[3] = ok;
+                s_misc[2] = at; s_misc[3] = ok; s_misc[4] = rat;
             }
             __syncthreads();
             const uint32_t abase = shard * shard_cap + s_misc[2] + wbase;
             const bool ok = s_misc[3] != 0u;
+            // the survivor's record slot, where its row items and so the lists name it (read by its own wave below, and by the
+            // survivor itself in phase 3)
+            if (nslots) s_tgid[tid] = shard * to.rec_shard_cap + s_misc[4] + cbase + recrank;
             PRE_STAMP(2);
             uint32_t jcarry = 0u; // owner (+1) of the slot just before the batch
             for (uint32_t rb0 = 0; rb0 < Rw; rb0 += 64u) {
@@ -539,8 +557,10 @@ __global__ __launch_bounds__(256, PRE_WAVES) void gs_preprocess_kernel(GsScene s
         }
         if (!TIGHT) opacity = sigmoid_ref(so.w);
         // GaussianData record (:97-104), 64 B as four 16-byte stores
-        uint4* o4 = gdata + (uint64_t)i * 4;
-        o4[0] = make_uint4(__float_as_uint(uvx), __float_as_uint(uvy), 0u, 0u);
+        // at the survivor's record slot (TIGHT; the gaussian's index otherwise); the gaussian's id rides in the first piece's
+        // free third word, where the consumers that need it find it in the piece they fetch anyway (gs_list_fetch)
+        uint4* o4 = gdata + (uint64_t)(TIGHT ? s_tgid[tid] : i) * 4;
+        o4[0] = make_uint4(__float_as_uint(uvx), __float_as_uint(uvy), i, 0u);
         o4[1] = make_uint4(__float_as_uint(conx), __float_as_uint(cony), __float_as_uint(conz), __float_as_uint(pv[2]));
         o4[2] = make_uint4(__float_as_uint(col[0]), __float_as_uint(col[1]), __float_as_uint(col[2]), __float_as_uint(opacity));
         o4[3] = make_uint4(rminx, rminy, rmaxx, rmaxy);
@@ -592,6 +612,7 @@ void gs_preprocess_prepare(GsPreprocessLaunch& L, const GsScene& s, const GsUnif
     }
     L.s = s; L.u = u; L.f = f; L.gdata = gdata; L.counts = counts; L.tint = tint;
     L.to.arena = arena; L.to.rowptr = rowptr; L.to.ctl = ctl;
+    L.to.rec_shard_cap = ((L.blocks + 15u) / 16u) * (PRE_G * nb); // 16 of them are at most n + GS_RECORD_SLACK records for every nb <= 8
     L.args[0] = &L.s; L.args[1] = &L.u; L.args[2] = &L.f; L.args[3] = &L.gdata; L.args[4] = &L.counts; L.args[5] = &L.to; L.args[6] = &L.tint;
 }
 void gs_launch_preprocess(GsPreprocessLaunch& L, hipStream_t st) {
