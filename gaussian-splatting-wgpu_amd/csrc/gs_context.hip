@@ -180,6 +180,7 @@ static int32_t alloc_per_gaussian(gs_ctx* c, uint64_t n, uint64_t min_capacity =
     c->frame.n = (uint32_t)n;
     c->have_frame = false;
     c->cov.reset(); // the coverage planes describe the scene that goes: they read as zero afterwards
+    c->ng = gs_ctx::Neigh{}; // ... and so does the neighbour count plane (its scratch is sized for that scene)
     c->counts.reset(); c->offsets.reset(); c->grec.reset(); c->rowptr.reset(); c->gsort_scratch.reset(); c->gdata.reset(); c->gdataG.reset();
     const size_t np = ((size_t)n + 63) & ~(size_t)63;
     HIP_TRY(hipMalloc(c->counts.out(), std::max<size_t>(np * 4, 256)));

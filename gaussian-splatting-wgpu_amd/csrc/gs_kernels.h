@@ -118,6 +118,30 @@ void gs_launch_attr_histogram(uint32_t kind, const uint8_t* state, const GsScene
 // out[g] = v of splat ids[first + g], or of splat first + g when ids is null, g = 0 .. m
 void gs_launch_attr_values(uint32_t kind, const GsScene& s, const void* cov, uint32_t n, const GsAttrDev& a, const uint32_t* ids, uint32_t first,
                            uint32_t m, float* out, hipStream_t st);
+// k_neigh.hip: neighbourhoods (gs_neigh.hip).  The cell grid over the finite sources: cell coordinate of x on axis k =
+// clamp((int)floorf((x - lo[k]) * inv_h), 0, g[k] - 1), key = cz << bxy | cy << bx | cx (bx, bxy - bx: the bits of g[0] - 1,
+// g[1] - 1).  `none` = g[2] << bxy is above every key and marks a splat that is no member (filter, non-finite coordinate): it sorts
+// last.  The {start, end} table has `blocks` = none >> shift entries, one per 2^shift consecutive keys (shift 0: one per cell).
+struct GsNeighGrid { float lo[3]; float inv_h; uint32_t g[3]; uint32_t bx, bxy, shift, blocks, none; };
+// out: 16 words the caller initialises ([0..2] all ones, the rest 0): min / max order-preserving keys of x, y, z over the finite
+// sources, then sources, finite sources, queries, finite queries.  state null: every splat passes both filters.
+void gs_launch_neigh_bounds(const uint8_t* state, const GsScene& s, uint32_t n, uint32_t smask, uint32_t svalue, uint32_t qmask, uint32_t qvalue,
+                            uint32_t* out, hipStream_t st);
+void gs_launch_neigh_keys(const uint8_t* state, const GsScene& s, uint32_t n, uint32_t mask, uint32_t value, const GsNeighGrid& g, uint32_t* keys,
+                          uint32_t* vals, hipStream_t st);
+// the sorted pairs -> {x, y, z, id} records (16 B, n of them allocated) and, with `table` (blocks x {start, end}, zeroed), the
+// members' keys in sorted order (skeys, n allocated) and each block's run
+void gs_launch_neigh_records(const uint32_t* keys, const uint32_t* vals, uint32_t n, const GsNeighGrid& g, const GsScene& s, void* rec, uint32_t* skeys,
+                             void* table, hipStream_t st);
+// sums[b]: candidates of sorted queries 256 b .. 256 b + 255; nrec: source records
+void gs_launch_neigh_cands(const void* qrec, uint32_t nq, const void* srec, const uint32_t* skeys, const void* table, uint32_t nrec, const GsNeighGrid& g,
+                           unsigned long long* sums, hipStream_t st);
+// the query pass over workgroups [first_block, first_block + blocks) of 256 sorted queries: plane[id] = min(limit, count)
+void gs_launch_neigh_query(const void* qrec, uint32_t nq, uint32_t first_block, uint32_t blocks, const void* srec, const uint32_t* skeys, const void* table,
+                           uint32_t nrec, const GsNeighGrid& g, float r2, uint32_t limit, uint32_t n, uint32_t* plane, hipStream_t st);
+// gs_state_neigh: the state pass with a membership read from the count plane (u32[n], 16-byte aligned)
+void gs_launch_state_neigh(uint8_t* state, const uint32_t* plane, uint32_t n, uint32_t min_count, uint32_t max_count, uint32_t inside, uint32_t op,
+                           uint32_t bits, uint32_t where_mask, uint32_t where_value, unsigned long long* matched, hipStream_t st);
 // k_export.hip: the splat edits (gs_export.hip).  Selection = splats with (s & mask) == value in ascending order: `counts` holds
 // gs_select_blocks(n) + 1 words (one per 1024 splats; after the launch their exclusive prefix, the total last), `ids` the total.
 uint32_t gs_select_blocks(uint32_t n);

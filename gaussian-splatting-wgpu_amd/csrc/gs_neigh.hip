@@ -1,0 +1,194 @@
+// gs_neigh.hip -- neighbourhoods' entry points: count the sources within a radius of every query into the count plane, read the
+// plane (the selection by count, gs_state_neigh, is with the state calls in gs_state.hip).  Part of the C ABI
+// (include/gsplat/gs_abi.h "neighbourhoods"); the kernels are in k_neigh.hip.
+//
+// The reference has no counterpart: it is a viewer.  An editor on it would export its 320-byte records and build a k-d tree on the
+// host; here the positions are resident, a cell grid is one radix sort of (cell, id) pairs away, and 4 bytes per splat come back.
+//
+// A count is: bounds of the finite sources (one pass, one word-sized read-back: the grid is chosen on the host), keys, the Onesweep
+// pair sort behind a private control block (as gs_sort_pairs_u32 drives it), records + keys + cell table, the same for the queries when
+// their filter differs, the candidates per workgroup of queries (second read-back: the budget and the slices), the query pass.
+// Every call drains the context's ring first (gs_wait), runs on the context's stream and returns when done.  None of them launches
+// anything in a frame: a context that never calls them launches exactly what it did before.
+#include <cmath>
+
+#include "gs_runtime.h"
+
+static_assert(sizeof(gs_neigh) == 40 && offsetof(gs_neigh, max_candidates) == 32, "gs_neigh layout");
+static_assert(sizeof(gs_neigh_info) == 40 && offsetof(gs_neigh_info, cells) == 24 && offsetof(gs_neigh_info, cell_edge) == 36, "gs_neigh_info layout");
+
+static size_t plane_bytes(const gs_ctx* c) { return std::max<size_t>((((size_t)c->n * 4) + 15) & ~(size_t)15, 256); }
+int32_t neigh_plane(gs_ctx* c, hipStream_t st) {
+    if (c->ng.plane) return GS_OK;
+    HIP_TRY(hipMalloc(c->ng.plane.out(), plane_bytes(c)));
+    HIP_TRY(hipMemsetAsync(c->ng.plane, 0, plane_bytes(c), st));
+    return GS_OK;
+}
+
+static uint32_t bits_of(uint32_t v) { uint32_t b = 0; while (b < 32 && (v >> b)) ++b; return b; }
+// The grid for sources with the finite bounds lo .. hi and a radius r: the smallest cell edge h >= 1.0011 r (k_neigh.hip: the
+// margin the cell expression's rounding needs) that leaves at most 1024 cells per axis; the key layout and the table's blocks.
+static void choose_grid(const float lo[3], const float hi[3], float radius, GsNeighGrid* g, float* edge) {
+    double ext[3], widest = 0.0;
+    for (int k = 0; k < 3; ++k) { ext[k] = (double)hi[k] - (double)lo[k]; widest = std::max(widest, ext[k]); }
+    float h = radius * 1.0011f;
+    h = std::max(h, (float)(widest / 1024.0 * 1.000001));
+    if (!(h >= 1e-30f)) h = widest > 0.0 ? 1e-30f : 1.0f; // (all sources in one point and radius 0: any edge does)
+    if (!std::isfinite(h)) h = 3.0e38f;
+    for (int k = 0; k < 3; ++k) {
+        g->g[k] = (uint32_t)std::min(std::floor(ext[k] / (double)h) + 1.0, 1024.0);
+        g->lo[k] = lo[k];
+    }
+    g->inv_h = 1.0f / h;
+    g->bx = bits_of(g->g[0] - 1u);
+    g->bxy = g->bx + bits_of(g->g[1] - 1u);
+    g->none = g->g[2] << g->bxy; // <= 2^30
+    const uint32_t kb = bits_of(g->none - 1u);
+    g->shift = kb > 24u ? kb - 24u : 0u; // < bxy, so `none` is a multiple of 2^shift
+    g->blocks = g->none >> g->shift;     // <= 2^24
+    *edge = h;
+}
+
+static float key_value(uint32_t key) { // the inverse of the kernels' order-preserving map
+    const uint32_t b = (key >> 31) ? key ^ 0x80000000u : ~key;
+    float v;
+    memcpy(&v, &b, 4);
+    return v;
+}
+
+// One filter's members in cell order: keys, the pair sort, the records (and the cell table when `table`).
+static int32_t sorted_records(gs_ctx* c, const uint8_t* state, uint32_t mask, uint32_t value, const GsNeighGrid& g, void* rec, void* table) {
+    gs_ctx::Neigh& s = c->ng;
+    const uint32_t passes = (bits_of(g.none) + 7) / 8; // the keys reach `none` itself (no member)
+    const size_t ctl_sz = (sizeof(GsControl) + 255) & ~(size_t)255;
+    const size_t st_sz = (size_t)passes * gs_sort_tiles(c->n) * 256 * 4;
+    HIP_TRY(hipMemsetAsync(s.ctl, 0, ctl_sz + st_sz, c->stream));
+    GsControl* ctl = (GsControl*)s.ctl.get(); // view; the sort's status words follow it
+    s.n32 = c->n;
+    HIP_TRY(hipMemcpyAsync(&ctl->num_intersections, &s.n32, 4, hipMemcpyHostToDevice, c->stream));
+    gs_launch_neigh_keys(state, c->scene, c->n, mask, value, g, s.keysA, s.valsA, c->stream);
+    const GsSort plan{{s.keysA, s.valsA}, {s.keysB, s.valsB}, passes, 8, 0, false, false}; // 8-bit digits of the key itself, counted by the sort
+    const GsSortPair sorted = gs_launch_sort(plan, ctl, (uint32_t*)(s.ctl.get() + ctl_sz), c->n, std::max(c->opt.grid_persist, 1u), c->stream);
+    gs_launch_neigh_records(sorted.keys, sorted.vals, c->n, g, c->scene, rec, s.skeys, table, c->stream);
+    HIP_TRY(hipGetLastError());
+    return GS_OK;
+}
+
+GS_EXPORT int32_t gs_neigh_count(gs_ctx* c, const gs_neigh* q, gs_neigh_info* info) {
+    const char* who = "gs_neigh_count";
+    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, "%s: null ctx", who);
+    if (!q) return fail(GS_ERR_INVALID_ARGUMENT, "%s: null query", who);
+    if (q->struct_size != sizeof(gs_neigh)) return fail(GS_ERR_INVALID_ARGUMENT, "%s: struct_size %u != %zu", who, q->struct_size, sizeof(gs_neigh));
+    int32_t rc = resident_check(c, who, Plane::filtered, q->src_mask, q->src_value);
+    if (rc != GS_OK) return rc;
+    rc = resident_check(c, who, Plane::filtered, q->qry_mask, q->qry_value);
+    if (rc != GS_OK) return rc;
+    if (!std::isfinite(q->radius) || q->radius < 0.0f) return fail(GS_ERR_INVALID_ARGUMENT, "%s: radius %g is negative or not finite", who, (double)q->radius);
+    const float r2 = q->radius * q->radius; // once, in f32: the kernel and a restating host compare with the same number
+    if (!std::isfinite(r2)) return fail(GS_ERR_INVALID_ARGUMENT, "%s: radius %g squared is not finite in f32", who, (double)q->radius);
+    if (q->limit == 0u) return fail(GS_ERR_INVALID_ARGUMENT, "%s: limit %u is not 1 .. 2^32-1", who, q->limit);
+    if (q->reserved != 0u) return fail(GS_ERR_INVALID_ARGUMENT, "%s: reserved %u is not 0", who, q->reserved);
+    rc = resident_drain(c);
+    if (rc != GS_OK) return rc;
+    rc = neigh_plane(c, c->stream);
+    if (rc != GS_OK) return rc;
+    gs_neigh_info out{};
+    if (info) *info = out;
+    const uint32_t n = c->n;
+    if (!n) { HIP_TRY(hipStreamSynchronize(c->stream)); return GS_OK; }
+    if (n >= (1u << 30)) return fail(GS_ERR_CAPACITY, "%s: %u splats, the cell sort takes fewer than 2^30", who, n); // (gs_sort_pairs_u32's limit)
+    gs_ctx::Neigh& s = c->ng;
+    const bool same = q->src_mask == q->qry_mask && q->src_value == q->qry_value;
+    const uint8_t* state = (q->src_mask | q->src_value | q->qry_mask | q->qry_value) ? c->scene.state : nullptr;
+
+    // scratch (all of it before the first launch: a failed allocation leaves the plane as it was)
+    const uint32_t nblocks_max = (n + 255u) / 256u;
+    const size_t ctl_sz = (sizeof(GsControl) + 255) & ~(size_t)255;
+    if ((rc = s.bounds.reserve(16)) != GS_OK || (rc = s.keysA.reserve(n)) != GS_OK || (rc = s.valsA.reserve(n)) != GS_OK ||
+        (rc = s.keysB.reserve(n)) != GS_OK || (rc = s.valsB.reserve(n)) != GS_OK || (rc = s.skeys.reserve(n)) != GS_OK || (rc = s.src.reserve((uint64_t)n * 16)) != GS_OK ||
+        (rc = s.sums.reserve(nblocks_max)) != GS_OK || (rc = s.ctl.reserve(ctl_sz + (size_t)4 * gs_sort_tiles(n) * 256 * 4)) != GS_OK)
+        return rc;
+    if (!same && (rc = s.qry.reserve((uint64_t)n * 16)) != GS_OK) return rc;
+
+    // 1. the bounds of the finite sources and the four counts
+    uint32_t hb[16] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+    HIP_TRY(hipMemcpyAsync(s.bounds, hb, sizeof(hb), hipMemcpyHostToDevice, c->stream));
+    gs_launch_neigh_bounds(state, c->scene, n, q->src_mask, q->src_value, q->qry_mask, q->qry_value, s.bounds, c->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(hb, s.bounds, sizeof(hb), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    out.sources = hb[6];
+    out.queried = hb[8];
+    const uint32_t nsrc = hb[7], nqry = hb[9]; // with finite coordinates: the others have no neighbours
+    if (!nsrc || !nqry) { // nothing to find: every count is 0
+        if (info) *info = out;
+        HIP_TRY(hipMemsetAsync(s.plane, 0, plane_bytes(c), c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        return GS_OK;
+    }
+    float lo[3], hi[3];
+    for (int k = 0; k < 3; ++k) { lo[k] = key_value(hb[k]); hi[k] = key_value(hb[3 + k]); }
+    GsNeighGrid g{};
+    choose_grid(lo, hi, q->radius, &g, &out.cell_edge);
+    for (int k = 0; k < 3; ++k) out.cells[k] = g.g[k];
+
+    // 2. sources, then queries, in cell order
+    rc = s.table.reserve((uint64_t)g.blocks * 8);
+    if (rc != GS_OK) return rc;
+    HIP_TRY(hipMemsetAsync(s.table, 0, (size_t)g.blocks * 8, c->stream));
+    rc = sorted_records(c, state, q->src_mask, q->src_value, g, s.src, s.table);
+    if (rc != GS_OK) return rc;
+    uint32_t fault[2] = {0u, 0u};
+    const GsControl* ctl = (const GsControl*)s.ctl.get();
+    HIP_TRY(hipMemcpyAsync(&fault[0], &ctl->fault, 4, hipMemcpyDeviceToHost, c->stream));
+    const void* qrec = s.src;
+    if (!same) {
+        HIP_TRY(hipStreamSynchronize(c->stream)); // fault[0] is read before the control block is zeroed again
+        rc = sorted_records(c, state, q->qry_mask, q->qry_value, g, s.qry, nullptr);
+        if (rc != GS_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(&fault[1], &ctl->fault, 4, hipMemcpyDeviceToHost, c->stream));
+        qrec = s.qry;
+    }
+
+    // 3. the candidates, exactly, per workgroup of 256 sorted queries: the budget, then the slices
+    const uint32_t nblocks = (nqry + 255u) / 256u;
+    gs_launch_neigh_cands(qrec, nqry, s.src, s.skeys, s.table, nsrc, g, s.sums, c->stream);
+    HIP_TRY(hipGetLastError());
+    std::vector<unsigned long long> sums(nblocks);
+    HIP_TRY(hipMemcpyAsync(sums.data(), s.sums, (size_t)nblocks * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (fault[0] | fault[1]) return fail(GS_ERR_DEVICE_FAULT, "%s: look-back spin bound exceeded in the cell sort", who);
+    for (uint32_t b = 0; b < nblocks; ++b) out.candidates += sums[b];
+    if (info) *info = out;
+    const uint64_t budget = q->max_candidates ? q->max_candidates : GS_NEIGH_DEFAULT_CANDIDATES;
+    if (out.candidates > budget)
+        return fail(GS_ERR_CAPACITY, "%s: %llu candidates exceed the work budget max_candidates = %llu (radius %g puts too many splats into one cell)", who,
+                    (unsigned long long)out.candidates, (unsigned long long)budget, (double)q->radius);
+
+    // 4. the query pass, in slices of whole workgroups
+    HIP_TRY(hipMemsetAsync(s.plane, 0, plane_bytes(c), c->stream));
+    for (uint32_t b0 = 0; b0 < nblocks;) {
+        uint64_t sum = sums[b0];
+        uint32_t b1 = b0 + 1u;
+        while (b1 < nblocks && sum + sums[b1] <= GS_NEIGH_SLICE_CANDIDATES) sum += sums[b1++];
+        gs_launch_neigh_query(qrec, nqry, b0, b1 - b0, s.src, s.skeys, s.table, nsrc, g, r2, q->limit, n, s.plane, c->stream);
+        b0 = b1;
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return GS_OK;
+}
+
+GS_EXPORT int32_t gs_neigh_read(gs_ctx* c, uint32_t* dst, uint64_t cap, uint64_t* n) {
+    int32_t rc = resident_begin(c, "gs_neigh_read", Plane::none);
+    if (rc != GS_OK) return rc;
+    rc = neigh_plane(c, c->stream);
+    if (rc != GS_OK) return rc;
+    if (!n) return fail(GS_ERR_INVALID_ARGUMENT, "gs_neigh_read: null n");
+    *n = c->n;
+    if (!dst) { HIP_TRY(hipStreamSynchronize(c->stream)); return GS_OK; }
+    if (cap < c->n) return fail(GS_ERR_INVALID_ARGUMENT, "gs_neigh_read: %llu counts needed, the buffer holds %llu", (unsigned long long)c->n, (unsigned long long)cap);
+    if (c->n) HIP_TRY(hipMemcpyAsync(dst, c->ng.plane, (size_t)c->n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return GS_OK;
+}

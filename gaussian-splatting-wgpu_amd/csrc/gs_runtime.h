@@ -1,10 +1,11 @@
-// gs_runtime.h -- private to the runtime sources (gs_context / gs_frame / gs_readback / gs_state / gs_export / gs_xform / gs_coverage / gs_attr / gs_ply / gs_stages .hip):
+// gs_runtime.h -- private to the runtime sources (gs_context / gs_frame / gs_readback / gs_state / gs_export / gs_xform / gs_coverage / gs_attr / gs_neigh / gs_ply / gs_stages .hip):
 //   the error channel (fail, HIP_TRY);
 //   the owners of HIP resources (Owned: DevBuf, PinnedBuf, Event, Stream, File) and Scratch, a device buffer that grows on demand;
 //   the context (gs_ctx, GsOptions, FrameNotes, GraphKey), the lists of its last frame (frame_lists) and sums over its ring (over_ring);
 //   what the calls on the resident splats share: the prologue of a call that drains the ring (Plane, resident_check,
 //   resident_drain, resident_begin), the last frame waited for (last_frame), the staging of a canvas mask (stage_mask), the
-//   coverage planes (cover_planes), the splat edits' selection (edit_select) and the check of a gs_attr (attr_check).
+//   coverage planes (cover_planes), the neighbour count plane (neigh_plane), the splat edits' selection (edit_select) and the
+//   check of a gs_attr (attr_check).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -193,6 +194,16 @@ struct gs_ctx {
     struct { DevBuf<unsigned long long> slots; Scratch<unsigned long long> hist; Scratch<float> vals; } at;
     // gs_coverage_* (gs_coverage.hip; root ctx): N x 16 B gs_coverage_rec, allocated and zeroed on first use, dropped with the scene
     DevBuf<> cov;
+    // neighbourhoods (gs_neigh.hip): the count plane u32[N], allocated and zeroed on first use, dropped with the scene like cov; the
+    // scratch of a count -- the sort's two pairs and private control block, the sorted source / query records, the cell table, the
+    // candidates per workgroup, the bounds words -- grown on demand, dropped with the scene too
+    struct Neigh {
+        DevBuf<uint32_t> plane;
+        Scratch<uint32_t> keysA, valsA, keysB, valsB, skeys, bounds;
+        Scratch<uint8_t> ctl, src, qry, table;
+        Scratch<unsigned long long> sums;
+        uint32_t n32 = 0; // the sort's count, copied from here into the private control block
+    } ng;
     Event ev[GS_EV_RING][GS_STAGE_COUNT + 1]; // ring of per-frame stage brackets (GS_FLAG_TIMING)
     bool have_events = false;
     uint64_t timed_from = 0; // first frame index included in the stage means
@@ -256,6 +267,8 @@ int32_t stage_mask(gs_ctx* root, const uint8_t* mask, hipStream_t st, const uint
 int32_t last_frame(gs_ctx* root, const char* who, gs_ctx** c);
 // gs_coverage.hip: the coverage planes of the root context, allocated and zeroed (on `st`) by the first call that needs them
 int32_t cover_planes(gs_ctx* root, hipStream_t st);
+// gs_neigh.hip: the neighbour count plane of `c`, allocated and zeroed (on `st`) by the first call that needs it
+int32_t neigh_plane(gs_ctx* c, hipStream_t st);
 // gs_export.hip: the splat edits' selection: counts the splats with (s & mask) == value and, with want_ids, leaves their indices,
 // ascending, in c->ex.ids
 int32_t edit_select(gs_ctx* c, uint32_t mask, uint32_t value, bool want_ids, uint64_t* total);

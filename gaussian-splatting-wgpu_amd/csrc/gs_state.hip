@@ -163,6 +163,23 @@ GS_EXPORT int32_t gs_state_attr(gs_ctx* c, const gs_attr* a, float lo, float hi,
     }, matched);
 }
 
+// Select by neighbour count: the pass over the count plane (gs_neigh.hip), which the first call that needs it allocates.
+GS_EXPORT int32_t gs_state_neigh(gs_ctx* c, uint32_t min_count, uint32_t max_count, uint32_t inside, uint32_t where_mask, uint32_t where_value, uint32_t op,
+                                 uint32_t bits, uint64_t* matched) {
+    int32_t rc = resident_check(c, "gs_state_neigh", Plane::always);
+    if (rc != GS_OK) return rc;
+    rc = state_check_op("gs_state_neigh", op, bits);
+    if (rc != GS_OK) return rc;
+    if (where_mask > 0xFFu) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_neigh: where_mask 0x%x does not fit the state byte", where_mask);
+    rc = resident_drain(c, true);
+    if (rc != GS_OK) return rc;
+    rc = neigh_plane(c, c->stream);
+    if (rc != GS_OK) return rc;
+    return state_counted(c, [&](unsigned long long* slots) {
+        gs_launch_state_neigh(plane(c), c->ng.plane, c->n, min_count, max_count, inside, op, bits, where_mask, where_value, slots, c->stream);
+    }, matched);
+}
+
 GS_EXPORT int32_t gs_state_write(gs_ctx* c, const uint8_t* src, uint64_t n) {
     int32_t rc = resident_check(c, "gs_state_write", Plane::always);
     if (rc != GS_OK) return rc;

@@ -530,6 +530,58 @@ static napi_value js_state_attr(napi_env env, napi_callback_info info) {
     return ret_u64(env, rc, matched);
 }
 
+/* ---- neighbourhoods: 1:1 wrappers of gs_neigh_* and gs_state_neigh -------------------------------------------------------- */
+/* neighCount(handle, radius, limit, srcMask, srcValue, qryMask, qryValue, maxCandidates) -> {queried, sources, candidates, cells, cellEdge} */
+static napi_value js_neigh_count(napi_env env, napi_callback_info info) {
+    CTX_ARGS(8, 8);
+    gs_neigh q;
+    memset(&q, 0, sizeof(q));
+    q.struct_size = sizeof(q);
+    double radius = 0, budget = 0;
+    NAPI_CALL(env, napi_get_value_double(env, argv[1], &radius));
+    q.radius = (float)radius;
+    uint32_t* u[5] = {&q.limit, &q.src_mask, &q.src_value, &q.qry_mask, &q.qry_value};
+    for (int k = 0; k < 5; ++k) NAPI_CALL(env, napi_get_value_uint32(env, argv[2 + k], u[k]));
+    NAPI_CALL(env, napi_get_value_double(env, argv[7], &budget));
+    q.max_candidates = budget >= 1.0 ? (budget < 18446744073709549568.0 ? (uint64_t)budget : UINT64_MAX) : 0;
+    gs_neigh_info ni;
+    int32_t rc = gs_neigh_count(ctx, &q, &ni);
+    if (rc != GS_OK) return throw_gs(env, rc);
+    napi_value out, cells, v;
+    NAPI_CALL(env, napi_create_object(env, &out));
+    set_num(env, out, "queried", (double)ni.queried);
+    set_num(env, out, "sources", (double)ni.sources);
+    set_num(env, out, "candidates", (double)ni.candidates);
+    set_num(env, out, "cellEdge", (double)ni.cell_edge);
+    NAPI_CALL(env, napi_create_array_with_length(env, 3, &cells));
+    for (uint32_t k = 0; k < 3; ++k) {
+        NAPI_CALL(env, napi_create_uint32(env, ni.cells[k], &v));
+        NAPI_CALL(env, napi_set_element(env, cells, k, v));
+    }
+    NAPI_CALL(env, napi_set_named_property(env, out, "cells", cells));
+    return out;
+}
+
+/* neighRead(handle) -> ArrayBuffer (N counts, u32) */
+static int32_t fill_neigh(gs_ctx* ctx, const uint32_t* a, void* dst, uint64_t cap, uint64_t* n) {
+    (void)a;
+    return gs_neigh_read(ctx, (uint32_t*)dst, cap, n);
+}
+static napi_value js_neigh_read(napi_env env, napi_callback_info info) {
+    CTX_ARGS(1, 1);
+    return fill_arraybuffer(env, ctx, fill_neigh, NULL, sizeof(uint32_t));
+}
+
+/* stateNeigh(handle, minCount, maxCount, inside, whereMask, whereValue, op, bits) -> matched */
+static napi_value js_state_neigh(napi_env env, napi_callback_info info) {
+    CTX_ARGS(8, 8);
+    uint32_t u[7]; /* minCount, maxCount, inside, whereMask, whereValue, op, bits */
+    for (int k = 0; k < 7; ++k) NAPI_CALL(env, napi_get_value_uint32(env, argv[1 + k], &u[k]));
+    uint64_t matched = 0;
+    int32_t rc = gs_state_neigh(ctx, u[0], u[1], u[2], u[3], u[4], u[5], u[6], &matched);
+    return ret_u64(env, rc, matched);
+}
+
 /* ---- splat state (GS_FLAG_SPLAT_STATE): 1:1 wrappers of gs_state_* --------------------------------------------------------- */
 static int get_f32x3_prop(napi_env env, napi_value obj, const char* name, float* out) {
     napi_value v, e;
@@ -997,6 +1049,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"readCoverage", js_coverage_read}, {"stateCoverage", js_state_coverage},
         {"attrSummary", js_attr_summary}, {"attrHistogram", js_attr_histogram},
         {"attrValues", js_attr_values}, {"stateAttr", js_state_attr},
+        {"neighCount", js_neigh_count}, {"neighRead", js_neigh_read}, {"stateNeigh", js_state_neigh},
     };
     for (size_t i = 0; i < sizeof(fns) / sizeof(fns[0]); ++i) {
         napi_value f;

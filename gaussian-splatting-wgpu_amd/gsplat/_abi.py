@@ -66,6 +66,10 @@ GS_ATTR_NAMES = ("POS_X", "POS_Y", "POS_Z", "OPACITY_LOGIT", "LOG_SCALE_MIN", "L
                  "DC_B", "DIST2", "PLANE", "COVER_HITS", "COVER_MAX_WEIGHT", "COVER_SUM")
 GS_ATTR_MAX_BINS = 1024
 
+# neighbourhoods
+GS_ERR_CAPACITY = -8
+GS_NEIGH_LIMIT_NONE = 0xFFFFFFFF  # gs_neigh.limit: count every neighbour
+
 # every symbol include/gsplat/gs_abi.h declares
 ABI_SYMBOLS = ("gs_last_error", "gs_abi_version", "gs_create", "gs_destroy", "gs_upload_splats", "gs_upload_splats_device",
                "gs_share_splats",
@@ -75,7 +79,8 @@ ABI_SYMBOLS = ("gs_last_error", "gs_abi_version", "gs_create", "gs_destroy", "gs
                "gs_state_list", "gs_export_splats", "gs_export_splats_device", "gs_compact", "gs_ply_save", "gs_export_ply",
                "gs_xform_compose", "gs_transform_splats",
                "gs_coverage_accumulate", "gs_coverage_reset", "gs_coverage_read", "gs_state_coverage",
-               "gs_attr_summary", "gs_attr_histogram", "gs_attr_read", "gs_state_attr", "gs_set_option", "gs_slab_width", "gs_assemble_slabs", "gs_sort_pairs_u32",
+               "gs_attr_summary", "gs_attr_histogram", "gs_attr_read", "gs_state_attr",
+               "gs_neigh_count", "gs_neigh_read", "gs_state_neigh", "gs_set_option", "gs_slab_width", "gs_assemble_slabs", "gs_sort_pairs_u32",
                "gs_exclusive_scan_u32")
 
 
@@ -138,6 +143,17 @@ class GsAttr(ctypes.Structure):
 
 class GsAttrSummary(ctypes.Structure):
     _fields_ = [("matched", ctypes.c_uint64), ("nan", ctypes.c_uint64), ("min", ctypes.c_float), ("max", ctypes.c_float)]
+
+
+class GsNeigh(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("radius", ctypes.c_float), ("limit", ctypes.c_uint32), ("src_mask", ctypes.c_uint32),
+                ("src_value", ctypes.c_uint32), ("qry_mask", ctypes.c_uint32), ("qry_value", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("max_candidates", ctypes.c_uint64)]
+
+
+class GsNeighInfo(ctypes.Structure):
+    _fields_ = [("queried", ctypes.c_uint64), ("sources", ctypes.c_uint64), ("candidates", ctypes.c_uint64), ("cells", ctypes.c_uint32 * 3),
+                ("cell_edge", ctypes.c_float)]
 
 
 # numpy views of the same records (what Renderer.pick returns)
@@ -211,6 +227,9 @@ def load():
     L.gs_attr_histogram.argtypes = [vp, ctypes.POINTER(GsAttr), u32, u32, f32, f32, u32, vp]
     L.gs_attr_read.argtypes = [vp, ctypes.POINTER(GsAttr), u32, u32, vp, u64, ctypes.POINTER(u64), vp]
     L.gs_state_attr.argtypes = [vp, ctypes.POINTER(GsAttr), f32, f32, u32, u32, u32, u32, u32, ctypes.POINTER(u64)]
+    L.gs_neigh_count.argtypes = [vp, ctypes.POINTER(GsNeigh), ctypes.POINTER(GsNeighInfo)]
+    L.gs_neigh_read.argtypes = [vp, vp, u64, ctypes.POINTER(u64)]
+    L.gs_state_neigh.argtypes = [vp, u32, u32, u32, u32, u32, u32, u32, ctypes.POINTER(u64)]
     L.gs_set_option.argtypes = [vp, i32, ctypes.c_int64]
     L.gs_slab_width.argtypes = [vp, ctypes.POINTER(u32), ctypes.POINTER(u32)]
     L.gs_assemble_slabs.argtypes = [vp, vp, ctypes.POINTER(u32), u32, u64, vp]

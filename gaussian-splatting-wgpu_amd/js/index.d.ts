@@ -50,6 +50,12 @@ export class Renderer {
   attrValues(attr: SplatAttr, where?: { mask?: number; value?: number }, withIds?: boolean): { values: Float32Array; ids: Uint32Array | null };
   /** FLAG.SPLAT_STATE: op / bits on the splats that pass the where filter and for which (lo <= v <= hi) == inside; returns how many. */
   stateAttr(attr: SplatAttr, range: { lo?: number; hi?: number; inside?: boolean; whereMask?: number; whereValue?: number }, op: number, bits: number): number;
+  /** Neighbourhoods: counts, for every splat passing the qry filter, the splats passing the src filter within radius (self excluded, <= inclusive), saturated at limit, into a resident u32 plane. Throws with code -8 beyond maxCandidates. */
+  neighCount(opts: { radius: number; limit?: number; srcMask?: number; srcValue?: number; qryMask?: number; qryValue?: number; maxCandidates?: number }): { queried: number; sources: number; candidates: number; cells: number[]; cellEdge: number };
+  /** The count plane in splat order. */
+  neighRead(): Uint32Array;
+  /** FLAG.SPLAT_STATE: op / bits on the splats that pass the where filter and whose count c has (minCount <= c <= maxCount) == inside; returns how many. */
+  stateNeigh(opts: { minCount?: number; maxCount?: number; inside?: boolean; whereMask?: number; whereValue?: number }, op: number, bits: number): number;
   setOption(key: number, value: number): void;
   /** FLAG.SPLAT_STATE: applies op (STATE.SET / CLEAR / TOGGLE / ASSIGN) with bits to every splat whose centre lies in the region and whose byte passes the where filter; returns how many those are. */
   stateRegion(region: StateRegion, op: number, bits: number): number;

@@ -231,6 +231,20 @@ class Renderer {
     return loadNative().stateAttr(this.handle, attr.kind >>> 0, attrParams(attr), +lo, +hi, inside ? 1 : 0, whereMask >>> 0, whereValue >>> 0,
                                   op >>> 0, bits >>> 0);
   }
+  // Neighbourhoods: for every splat that passes (qryMask, qryValue), how many splats that pass (srcMask, srcValue) lie within
+  // `radius` of it (itself excluded, <= inclusive, the SPHERE region's f32 expression), saturated at `limit`, into a resident u32
+  // plane; every other splat gets 0.  -> {queried, sources, candidates, cells, cellEdge}.  maxCandidates: the work budget (0: the
+  // library's default); beyond it the call throws (code -8) and the plane stays.  Move or re-filter splats: count again.
+  neighCount({ radius, limit = 0xFFFFFFFF, srcMask = 0, srcValue = 0, qryMask = 0, qryValue = 0, maxCandidates = 0 }) {
+    return loadNative().neighCount(this.handle, +radius, limit >>> 0, srcMask >>> 0, srcValue >>> 0, qryMask >>> 0, qryValue >>> 0, +maxCandidates);
+  }
+  // -> Uint32Array: the count plane in splat order (zeros before the first neighCount and after an upload or a compaction)
+  neighRead() { return new Uint32Array(loadNative().neighRead(this.handle)); }
+  // FLAG.SPLAT_STATE: applies `op` with `bits` to the splats that pass (s & whereMask) == whereValue and whose count c has
+  // (minCount <= c <= maxCount) == inside.  Returns how many those are.
+  stateNeigh({ minCount = 0, maxCount = 0xFFFFFFFF, inside = true, whereMask = 0, whereValue = 0 } = {}, op, bits) {
+    return loadNative().stateNeigh(this.handle, minCount >>> 0, maxCount >>> 0, inside ? 1 : 0, whereMask >>> 0, whereValue >>> 0, op >>> 0, bits >>> 0);
+  }
   // Splat edits: bring splats back out of the library and make an edit permanent.  A splat matches when (s & mask) == value;
   // matching splats always come in ascending index order; (0, 0) is every splat and needs no FLAG.SPLAT_STATE.
   listState(mask, value) { return new Uint32Array(loadNative().listState(this.handle, mask >>> 0, value >>> 0)); }

@@ -556,6 +556,64 @@ int32_t gs_attr_read(gs_ctx* ctx, const gs_attr* attr, uint32_t mask, uint32_t v
 int32_t gs_state_attr(gs_ctx* ctx, const gs_attr* attr, float lo, float hi, uint32_t inside, uint32_t where_mask, uint32_t where_value,
                       uint32_t op, uint32_t bits, uint64_t* matched);
 
+/* ---- neighbourhoods: count the splats within a radius, select by that count ---------------------------------
+ * Every selection above asks about one splat at a time; these ask about a splat in relation to the others, which is what a splat
+ * editor builds "remove floaters" (fewer than k others within r), "grow / shrink the selection" and a local density on -- without
+ * the gs_export_splats / host k-d tree / gs_state_ids round trip.  The reference has no counterpart (a viewer).
+ * THE COUNT.  Sources are the splats j with (s_j & src_mask) == src_value, queries the splats i with (s_i & qry_mask) == qry_value.
+ * For a query i
+ *     c_i = min(limit, #{ j != i : j is a source and d2(i, j) <= r2 })
+ *     d = p_j - p_i per component;  d2 = (dx dx + dy dy) + dz dz;  r2 = radius * radius
+ * -- the SPHERE region's expression: one f32 rounding per written operation, no contraction, so a host can restate it bit for bit.
+ * It is symmetric in i and j (the negation is exact).  The comparison <= is INCLUSIVE.  A splat that is not a query gets 0.  A NaN
+ * or infinite coordinate makes every comparison false: such a splat has no neighbours and is nobody's neighbour.  radius = 0 (or
+ * one whose square is 0) counts exact duplicates.  Self is excluded by index, not by distance.  The result is an integer and does
+ * not depend on the order in which the device visits anything: two runs agree bit for bit; a slab ctx, a borrower and a fresh ctx
+ * answer the same.  `limit` saturates the count and lets the device stop early (limit = 1: "has a neighbour").
+ * THE PLANE is u32[N] and belongs to the ctx the call is made on (the root of a ring; a borrower of gs_share_splats keeps its own).
+ * It is allocated and zeroed by the first of the three calls, overwritten as a whole by gs_neigh_count, and DROPPED -- it reads as
+ * zero again -- by every gs_upload_*, gs_share_splats and gs_compact, like the coverage planes.  State calls and transforms leave
+ * it untouched: it describes the positions and states at the time of the count, and a host that moves splats counts again.
+ * WORK BUDGET.  A radius that puts the scene into one cell of the device's grid makes the candidates N^2.  Before the query pass
+ * the call computes `candidates` exactly; above max_candidates (0: GS_NEIGH_DEFAULT_CANDIDATES) it returns GS_ERR_CAPACITY with
+ * both numbers in the message and leaves the plane as it was.  The query pass is issued in slices of whole workgroups (256
+ * queries) of at most GS_NEIGH_SLICE_CANDIDATES candidates each (one workgroup where a single one exceeds that), so that no launch
+ * is long.  The two constants come from the measured candidate rate (profiles/neighbours.txt): what finishes in 1 s and in 50 ms.
+ * Prologue, ordering and refusals are those of the splat attributes: each (mask, value) as gs_state_count, above 0xFF refused,
+ * (0, 0) matches every splat and is accepted on a ctx without GS_FLAG_SPLAT_STATE, any other filter on such a ctx is refused.
+ * Every call first completes all frames enqueued on the ctx's ring, runs on the ctx's stream and returns when done; none is a
+ * frame or an upload (taps, statistics, gs_pick, the shadows and a captured graph stay).  GS_ERR_NO_SCENE before any upload;
+ * N == 0: zero results, GS_OK.  gs_neigh_count and gs_neigh_read work on a borrower; gs_state_neigh has gs_state_region's rules.
+ * A wrong struct_size, a radius that is negative or not finite, a radius * radius that is not finite in f32, limit == 0 or
+ * reserved != 0: GS_ERR_INVALID_ARGUMENT and a message that names the number. */
+#define GS_NEIGH_DEFAULT_CANDIDATES (1ull << 38) /* 0.93 s at the measured 2.95e11 candidates / s */
+#define GS_NEIGH_SLICE_CANDIDATES (1ull << 33)   /* 29 ms */
+typedef struct gs_neigh {          /* 40 bytes */
+    uint32_t struct_size;          /* = sizeof(gs_neigh) */
+    float    radius;               /* finite, >= 0; r2 = radius * radius, ONE f32 product, must be finite */
+    uint32_t limit;                /* 1 .. 2^32-1: counts saturate here, the device may stop at it */
+    uint32_t src_mask, src_value;  /* SOURCES: splats j with (s_j & src_mask) == src_value */
+    uint32_t qry_mask, qry_value;  /* QUERIES: splats i with (s_i & qry_mask) == qry_value */
+    uint32_t reserved;             /* 0 */
+    uint64_t max_candidates;       /* work budget, 0 = GS_NEIGH_DEFAULT_CANDIDATES */
+} gs_neigh;
+typedef struct gs_neigh_info {     /* 40 bytes */
+    uint64_t queried, sources;     /* splats that pass the two filters */
+    uint64_t candidates;           /* sum over the queries of the sources in the 27 cells around them, self included */
+    uint32_t cells[3]; float cell_edge; /* the grid that was used (diagnostic; no result depends on it) */
+} gs_neigh_info;
+/* Counts into the plane.  info (may be NULL) is written whenever the grid was built, also when the budget refuses the call. */
+int32_t gs_neigh_count(gs_ctx* ctx, const gs_neigh* q, gs_neigh_info* info);
+/* The plane in HOST memory, N counts in splat order, with gs_coverage_read's conventions: dst == NULL: only *n (= N) is written
+ * (query); cap < N: GS_ERR_INVALID_ARGUMENT, the message names the count needed, nothing is written to dst. */
+int32_t gs_neigh_read(gs_ctx* ctx, uint32_t* dst, uint64_t cap, uint64_t* n);
+/* Applies `op` with `bits` exactly as gs_state_region does, to the splats that pass (s & where_mask) == where_value and for which
+ *     (c >= min_count && c <= max_count) == (inside != 0)
+ * min_count > max_count is a valid empty range.  Needs GS_FLAG_SPLAT_STATE; *matched (may be NULL) as for gs_state_region.  One
+ * streaming pass over 5 bytes per splat. */
+int32_t gs_state_neigh(gs_ctx* ctx, uint32_t min_count, uint32_t max_count, uint32_t inside, uint32_t where_mask, uint32_t where_value,
+                       uint32_t op, uint32_t bits, uint64_t* matched);
+
 /* Tuning / profiling knobs. */
 #define GS_OPT_BLEND_ABLATION 1  /* bit 3 (8): the workgroup-per-tile blend kernel at tiles 16 and 32 (identical results; default = one
                                     wave per 8x8 pixel block); bit 2 (4): every blend kernel without its two parking culls (live box,
