@@ -182,11 +182,18 @@ static int32_t alloc_per_gaussian(gs_ctx* c, uint64_t n, uint64_t min_capacity =
     c->cov.reset(); // the coverage planes describe the scene that goes: they read as zero afterwards
     c->ng = gs_ctx::Neigh{}; // ... and so does the neighbour count plane (its scratch is sized for that scene)
     c->counts.reset(); c->offsets.reset(); c->grec.reset(); c->rowptr.reset(); c->gsort_scratch.reset(); c->gdata.reset(); c->gdataG.reset();
+    c->unit_off.reset(); c->unit_n.reset();
     const size_t np = ((size_t)n + 63) & ~(size_t)63;
-    HIP_TRY(hipMalloc(c->counts.out(), std::max<size_t>(np * 4, 256)));
+    // the entry planes of a tight frame (counts, rowptr, unit_off: k_gsort.hip) hold whole chunks of the gaussian-level sort, and the
+    // unit counts one pair per chunk and a pair more; the counts past the last unit are zeroed here and never written
+    const size_t ne = (size_t)gs_gsort_tiles((uint32_t)(n ? n : 1)) * 2048, nu = ne / 1024 + 2;
+    HIP_TRY(hipMalloc(c->counts.out(), ne * 4));
     HIP_TRY(hipMalloc(c->offsets.out(), std::max<size_t>(np * 4, 256)));
     HIP_TRY(hipMalloc(c->grec.out(), std::max<size_t>(np * 16, 256)));
-    HIP_TRY(hipMalloc(c->rowptr.out(), std::max<size_t>(np * 4, 256)));
+    HIP_TRY(hipMalloc(c->rowptr.out(), ne * 4));
+    HIP_TRY(hipMalloc(c->unit_off.out(), ne * 2));
+    HIP_TRY(hipMalloc(c->unit_n.out(), nu * 4));
+    HIP_TRY(hipMemsetAsync(c->unit_n, 0, nu * 4, c->stream));
     HIP_TRY(hipMalloc(c->gsort_scratch.out(), gs_gsort_scratch_bytes((uint32_t)n)));
     HIP_TRY(hipMalloc(c->gdata.out(), ((size_t)n + GS_RECORD_SLACK) * 64));
     HIP_TRY(hipMemsetAsync(c->gdata, 0, ((size_t)n + GS_RECORD_SLACK) * 64, c->stream));

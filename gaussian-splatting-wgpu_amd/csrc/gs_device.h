@@ -87,6 +87,7 @@ __device__ __forceinline__ void gs_frame_report(const GsControl* ctl, uint32_t I
 
 struct GsTightOut { // product-path outputs of the tight projection beside GaussianData and the count words (k_preprocess.hip)
     uint32_t* arena; uint32_t* rowptr; GsControl* ctl;
+    unsigned short* unit_off; uint32_t* unit_n; // the entries' third plane and the survivors of every 1024-index unit
     uint32_t rec_shard_cap; // records each of the 16 shards of the record array holds
 };
 // Records the GaussianData array of a scene of n gaussians holds: the tight projection hands out record slots in 16 shards of

@@ -52,8 +52,8 @@ GsLists frame_lists(const gs_ctx* c) {
 
 // The projection's launch for this frame, left in c->pre: record_frame launches it, a replay patches the captured node from it.
 static void prepare_projection(gs_ctx* c, const GsUniforms& u, bool tight) {
-    gs_preprocess_prepare(c->pre, c->scene, u, c->frame, c->gdata, c->counts, tight, c->arena, c->rowptr, c->ctl, c->opt.tight_nb, has_state(c),
-                          tint_of(c->opt.select_tint));
+    gs_preprocess_prepare(c->pre, c->scene, u, c->frame, c->gdata, c->counts, tight, c->arena, c->rowptr, c->unit_off, c->unit_n, c->ctl, c->opt.tight_nb,
+                          has_state(c), tint_of(c->opt.select_tint));
 }
 
 // ---- binning: one function per pipeline, from the first launch after the projection (stage mark 1) to `ranges` (mark 5 follows).
@@ -62,10 +62,12 @@ static void prepare_projection(gs_ctx* c, const GsUniforms& u, bool tight) {
 // The tight row pipeline (k_rows.hip).  Stage brackets: "scan" = the gaussian-level sort by depth bucket, "emit" = the row sort
 // (the row items take write_tile_ids' place), "sort" = count + scan + expansion into the final lists, "ranges" = nothing (they
 // fall out of the scan).
+// A tight frame's `counts` and `rowptr` hold the projection's ENTRIES (the cull's survivors of every 1024-index unit, dense from
+// the unit's start), not a word per gaussian index; a frame of the reference's binning rewrites counts[i] for every i.
 static FrameNotes bin_tight(gs_ctx* c) {
     hipStream_t st = c->stream;
-    gs_launch_gsort(c->counts, c->rowptr, c->n, c->gsort_scratch, c->grec, c->chunk_table, (uint32_t)gs_emit_chunks(std::max(c->capacity, c->row_cap)),
-                    &c->ctl->num_visible, &c->ctl->num_slots, c->opt.grid_persist, st);
+    gs_launch_gsort(c->counts, c->rowptr, c->unit_off, c->unit_n, c->n, c->gsort_scratch, c->grec, c->chunk_table,
+                    (uint32_t)gs_emit_chunks(std::max(c->capacity, c->row_cap)), &c->ctl->num_visible, &c->ctl->num_slots, c->opt.grid_persist, st);
     mark(c, 2);
     gs_launch_rows(c->arena, c->grec, c->chunk_table, c->rows_sorted, c->ctl, c->rows_status, (uint32_t)c->row_cap, c->M3, c->tileoff, c->rowtot, c->frame,
                    c->valsA, c->ranges, c->opt.grid_persist / 4u, c->sticky, c->h_rep, st, mark_cb, c);
@@ -110,7 +112,7 @@ static int32_t bin_by_index(gs_ctx* c, bool debug, FrameNotes& nt) {
 // emitting their instances in that order leaves only the tile id for the stable instance sort: 2 digits of key/1000 instead of
 // 3 of the key.  The sorted (key,value) arrays are identical.
 static FrameNotes bin_by_depth(gs_ctx* c) {
-    gs_launch_gsort(c->counts, nullptr, c->n, c->gsort_scratch, c->grec, c->chunk_table, (uint32_t)gs_emit_chunks(std::max(c->capacity, c->row_cap)),
+    gs_launch_gsort(c->counts, nullptr, nullptr, nullptr, c->n, c->gsort_scratch, c->grec, c->chunk_table, (uint32_t)gs_emit_chunks(std::max(c->capacity, c->row_cap)),
                     &c->ctl->num_visible, &c->ctl->num_intersections, c->opt.grid_persist, c->stream);
     mark(c, 2);
     gs_launch_emit_balanced(c->gdata, c->grec, c->chunk_table, c->frame, c->keysA, c->valsA, c->ctl, c->opt.grid_persist * 2, c->tile_bits, c->tile_passes,

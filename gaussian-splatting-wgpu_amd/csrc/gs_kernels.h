@@ -13,8 +13,8 @@ struct GsPreprocessLaunch { // the projection's launch as data (its uniforms are
 };
 // state: the STATE instantiation (honours s.state and the tint); false launches exactly the kernels a context without the plane has
 void gs_preprocess_prepare(GsPreprocessLaunch& L, const GsScene& s, const GsUniforms& u, const GsFrame& f, void* gdata, uint32_t* counts,
-                           bool tight, uint32_t* arena, uint32_t* rowptr, GsControl* ctl, uint32_t tight_nb = 0, bool state = false,
-                           GsTint tint = GsTint{});
+                           bool tight, uint32_t* arena, uint32_t* rowptr, unsigned short* unit_off, uint32_t* unit_n, GsControl* ctl,
+                           uint32_t tight_nb = 0, bool state = false, GsTint tint = GsTint{});
 void gs_launch_preprocess(GsPreprocessLaunch& L, hipStream_t st);
 void gs_launch_zero(void* p, uint64_t bytes, hipStream_t st); // bytes: a multiple of 16
 uint32_t gs_scan_blocks(uint32_t n);
@@ -63,8 +63,11 @@ void gs_launch_assemble(const void* slabs, void* image, uint32_t width, uint32_t
 // k_gsort.hip: the visible gaussians sorted by depth bucket (stable) with their quantity (tile count / row-item slots) scanned in that order
 uint32_t gs_gsort_tiles(uint32_t n);
 uint64_t gs_gsort_scratch_bytes(uint32_t n);
-void gs_launch_gsort(const uint32_t* words, const uint32_t* aux_in, uint32_t n, void* scratch, void* grec, uint32_t* chunk_table, uint32_t chunk_cap,
-                     uint32_t* tot_visible, uint32_t* tot_quantity, uint32_t grid, hipStream_t st);
+// Two input forms.  unit_n == nullptr: words (and aux_in, optional) hold one word per gaussian INDEX.  Otherwise the tight projection's
+// entries: per 1024-index unit u, unit_n[u] survivors in index order at u * 1024 + e of words / aux_in / unit_off (the index inside the
+// unit); the planes hold gs_gsort_tiles(n) * 2048 entries, unit_n 2 * gs_gsort_tiles(n) + 2 words (zero past the last unit).
+void gs_launch_gsort(const uint32_t* words, const uint32_t* aux_in, const unsigned short* unit_off, const uint32_t* unit_n, uint32_t n, void* scratch,
+                     void* grec, uint32_t* chunk_table, uint32_t chunk_cap, uint32_t* tot_visible, uint32_t* tot_quantity, uint32_t grid, hipStream_t st);
 // k_rows.hip: the tight row pipeline (row sort, per-chunk counts, scan, expansion into the final per-tile lists + ranges)
 uint32_t gs_rows_sort_tiles(uint64_t row_cap);
 uint32_t gs_rows_chunks(uint64_t row_cap);
@@ -74,8 +77,8 @@ void gs_launch_rows(const uint32_t* arena, const void* grec, const uint32_t* chu
 // the taps of a tight frame, whose lists name record slots (gdata: its records, nrec of them): the keys; the values with the
 // gaussian's id in the slot's place (ids_out, may be null); the records in index order, id word cleared (gdata_out, zeroed by the
 // caller, may be null)
-void gs_launch_rows_rebuild_keys(const uint32_t* ranges, uint32_t T, const uint32_t* vals, const void* gdata, uint32_t nrec, const uint32_t* counts,
-                                 uint32_t count, uint32_t n, uint32_t* keys, hipStream_t st);
+void gs_launch_rows_rebuild_keys(const uint32_t* ranges, uint32_t T, const uint32_t* vals, const void* gdata, uint32_t nrec, uint32_t count, uint32_t n,
+                                 uint32_t* keys, hipStream_t st);
 void gs_launch_rows_rebuild_taps(const uint32_t* vals, const void* gdata, uint32_t nrec, uint32_t count, uint32_t n, uint32_t* ids_out, void* gdata_out,
                                  hipStream_t st);
 // k_state.hip: the state plane's streaming kernels (gs_state.hip).  The plane is 256-byte aligned with np >= n bytes behind it.

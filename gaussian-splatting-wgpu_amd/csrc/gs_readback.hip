@@ -31,6 +31,8 @@ static int32_t tap(gs_ctx* c, int32_t which, void** ptr, uint64_t* bytes) {
     const uint64_t I = std::min<uint64_t>(c->h_rep->num_intersections, c->capacity);
     const uint64_t px = (uint64_t)c->frame.slab_w * c->frame.height;
     switch (which) {
+    // (device words of a tight frame: the count plane of the projection's entries, not indexed by the gaussian -- gs_read_buffer
+    // derives that frame's tile counts from its lists)
     case GS_BUF_TILE_COUNTS: *ptr = c->counts; *bytes = (uint64_t)c->n * 4; return GS_OK;
     case GS_BUF_TILE_OFFSETS:
         if (!c->last_debug) return fail(GS_ERR_NO_FRAME, "the offsets tap needs gs_render_debug (index-order scan)");
@@ -51,7 +53,7 @@ static int32_t tap(gs_ctx* c, int32_t which, void** ptr, uint64_t* bytes) {
         if (!c->keysG_valid) { // the frame never held full keys (16-bit tile ids, or no keys at all on the tight row pipeline): rebuild tile*1000 + bucket once
             if (c->pending) { int32_t rc = wait_one(c); if (rc != GS_OK) return rc; }
             if (!c->keysG) HIP_TRY(hipMalloc(c->keysG.out(), (size_t)c->capacity * 4));
-            if (nt.last_tight) gs_launch_rows_rebuild_keys(c->ranges, c->T, nt.valsS, c->gdata, c->n + GS_RECORD_SLACK, c->counts, (uint32_t)I, c->n, c->keysG, c->stream);
+            if (nt.last_tight) gs_launch_rows_rebuild_keys(c->ranges, c->T, nt.valsS, c->gdata, c->n + GS_RECORD_SLACK, (uint32_t)I, c->n, c->keysG, c->stream);
             else gs_launch_rebuild_keys((const uint16_t*)nt.keysS, nt.valsS, c->counts, (uint32_t)I, c->n, c->keysG, c->stream);
             HIP_TRY(hipStreamSynchronize(c->stream));
             c->keysG_valid = true;

@@ -138,7 +138,9 @@ struct gs_ctx {
     GsScene scene{};            // views into scene_mem
     uint32_t n = 0;
     // per-gaussian frame buffers (alloc_per_gaussian)
-    DevBuf<uint32_t> counts, offsets, rowptr;
+    DevBuf<uint32_t> counts, offsets, rowptr; // (counts / rowptr hold whole 2048-index chunks: a tight frame keeps its entries there)
+    DevBuf<unsigned short> unit_off;          // tight frames: the entries' third plane, the gaussian's index inside its 1024-index unit
+    DevBuf<uint32_t> unit_n;                  // ... and the survivors of every unit (2 per chunk + 2; zero past the last unit)
     DevBuf<> gdata;             // n + GS_RECORD_SLACK records (the tight projection's record slots, gs_device.h)
     DevBuf<> grec;              // visible gaussians in (depth bucket, index) order: {id, count word, prefix, arena address} (k_gsort.hip)
     DevBuf<> gsort_scratch;     // (bucket, run) table of the gaussian-level counting sort

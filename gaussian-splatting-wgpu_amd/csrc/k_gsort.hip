@@ -27,6 +27,11 @@
 // index ranges, so the order inside a bucket is the gaussian index order, which is what write_tile_ids.wgsl:31 plus a stable
 // sort gives.  The table is written by one kernel and read by the next: launch boundaries are the only ordering needed.
 //
+// Two input forms (template parameter DENSE of hist and scatter).  The reference's binning hands over one count word per gaussian
+// INDEX.  The tight projection hands over ENTRIES: per unit of 1024 indices the cull's survivors in index order, dense from the
+// unit's start, and their number (see gs_gsort_hist_kernel) -- at 40 % visible the N-indexed form read 12 N bytes to sort 0.4 N
+// records and spent three fifths of its ranking lanes on zero words.
+//
 // Saturation.  Quantities are summed in 64 bits and stored as sat32(sum).  For non-negative terms
 // sat32(sat32(a) + b) == sat32(a + b), so the carried base stays 32 bits wide in LDS (a 64-bit base would cost 4 KB and the
 // fourth workgroup of a CU) and still equals sat32(true 64-bit base) at every chunk: `off`, the chunk table and the totals
@@ -49,27 +54,54 @@ __device__ __forceinline__ uint64_t m_index(uint32_t b, uint32_t col, uint32_t n
 
 // One workgroup per run: chunks [run * cpr, min((run + 1) * cpr, NT)); the loads of chunk k + 1 are issued before the LDS
 // atomics of chunk k.
-__global__ __launch_bounds__(GC_THREADS) void gs_gsort_hist_kernel(const uint32_t* __restrict__ words, uint32_t n, uint2* __restrict__ M, uint32_t ncol,
-                                                                   uint32_t cpr, uint32_t NT) {
+//
+// DENSE (the tight pipeline): `words` is not indexed by the gaussian.  The projection compacts the cull's survivors of every
+// UNIT of GU = 1024 consecutive indices in index order (k_preprocess.hip): unit_n[u] of them, survivor e of unit u at entry
+// u * GU + e of three planes -- the count word (0: ends without a tile), the aux word, and the gaussian's offset inside the
+// unit (u16).  A chunk is two units, T = n0 + n1 entries; position p < T of the chunk is entry p of unit 2c when p < n0, else
+// entry p - n0 of unit 2c + 1: positions ascend with the gaussian index.  The sort neither loads nor ranks the culled 60 %.
+// unit_n holds 2 NT + 2 words, those past the last unit zero: a chunk's pair is one aligned 8-byte load.
+#define GU (GC / 2)
+// (clamped: the planes hold whole chunks, so no value of a count can take a load out of them)
+__device__ __forceinline__ uint2 unit_pair(const uint2* __restrict__ unit_n, uint32_t c) {
+    const uint2 v = unit_n[c];
+    return make_uint2(v.x < GU ? v.x : GU, v.y < GU ? v.y : GU);
+}
+template <bool DENSE>
+__global__ __launch_bounds__(GC_THREADS) void gs_gsort_hist_kernel(const uint32_t* __restrict__ words, const uint2* __restrict__ unit_n, uint32_t n,
+                                                                   uint2* __restrict__ M, uint32_t ncol, uint32_t cpr, uint32_t NT) {
     __shared__ uint32_t s_cnt[GBINS];
     __shared__ unsigned long long s_sum[GBINS]; // a run's quantity can exceed 32 bits (2048 x 2^22 tiles a chunk): saturated on store
     const uint32_t run = blockIdx.x, tid = threadIdx.x;
     const uint32_t c0 = run * cpr, c1 = c0 + cpr < NT ? c0 + cpr : NT;
     for (uint32_t b = tid; b < GBINS; b += GC_THREADS) { s_cnt[b] = 0u; s_sum[b] = 0ull; }
     uint32_t wv[GC_ITEMS];
+    // DENSE: item j of thread t is entry (j % 4) * 256 + t of unit 2c + j / 4 (the order inside a chunk is free here)
+    uint2 un = make_uint2(0u, 0u); // the units' survivors of the chunk being loaded
+    auto load = [&](uint32_t c, uint32_t (&o)[GC_ITEMS]) {
 #pragma unroll
-    for (int j = 0; j < GC_ITEMS; ++j) {
-        const uint32_t k = c0 * GC + j * GC_THREADS + tid;
-        wv[j] = (k < n) ? words[k] : 0u;
-    }
+        for (int j = 0; j < GC_ITEMS; ++j) {
+            if (DENSE) {
+                const uint32_t e = (uint32_t)(j & 3) * GC_THREADS + tid;
+                o[j] = (e < (j < 4 ? un.x : un.y)) ? words[c * GC + (uint32_t)(j >> 2) * GU + e] : 0u;
+            } else {
+                const uint32_t k = c * GC + j * GC_THREADS + tid;
+                o[j] = (k < n) ? words[k] : 0u;
+            }
+        }
+    };
+    if (DENSE) un = unit_pair(unit_n, c0);
+    load(c0, wv);
+    if (DENSE) un = c0 + 1u < c1 ? unit_pair(unit_n, c0 + 1u) : make_uint2(0u, 0u);
     __syncthreads();
     for (uint32_t c = c0; c < c1; ++c) {
         uint32_t nx[GC_ITEMS];
+        if (c + 1u < c1) load(c + 1u, nx); // (uniform)
+        else {
 #pragma unroll
-        for (int j = 0; j < GC_ITEMS; ++j) {
-            const uint32_t k = (c + 1u) * GC + j * GC_THREADS + tid;
-            nx[j] = (c + 1u < c1 && k < n) ? words[k] : 0u;
+            for (int j = 0; j < GC_ITEMS; ++j) nx[j] = 0u;
         }
+        if (DENSE) un = c + 2u < c1 ? unit_pair(unit_n, c + 2u) : make_uint2(0u, 0u); // (consumed by the next trip's loads)
 #pragma unroll
         for (int j = 0; j < GC_ITEMS; ++j) {
             const uint32_t w = wv[j];
@@ -170,7 +202,12 @@ static_assert(sizeof(GsortShared) <= 40 * 1024, "four workgroups per CU");
 // are loaded before the first barrier; inside the loop the next chunk's words (+ aux) are loaded into registers before the
 // current one is ranked, so only the first chunk's load latency is exposed.  Every barrier of a trip is reached by all 256
 // threads: the trip count and `nc` are uniform over the workgroup.
-__global__ __launch_bounds__(GC_THREADS) void gs_gsort_scatter_kernel(const uint32_t* __restrict__ words, const uint32_t* __restrict__ aux_in, uint32_t n,
+// DENSE: wave w owns positions [w L, (w + 1) L) of the chunk's T entries, L = 64 ceil(T / 256): item j of lane l is position
+// w L + 64 j + l, so (item, lane) is still the index order and waves still own ascending ranges; the rounds past T hold
+// nothing and the uniform `if (vis)` skips them.  The index inside the chunk comes from the entry's offset plane.
+template <bool DENSE>
+__global__ __launch_bounds__(GC_THREADS) void gs_gsort_scatter_kernel(const uint32_t* __restrict__ words, const uint32_t* __restrict__ aux_in,
+                                                                      const unsigned short* __restrict__ unit_off, const uint2* __restrict__ unit_n, uint32_t n,
                                                                       const uint2* __restrict__ M, uint32_t ncol, uint32_t cpr, uint32_t NT,
                                                                       const uint2* __restrict__ rowtot, uint4* __restrict__ grec,
                                                                       uint32_t* __restrict__ chunk_table, uint32_t chunk_cap,
@@ -184,8 +221,34 @@ __global__ __launch_bounds__(GC_THREADS) void gs_gsort_scatter_kernel(const uint
 
     // ---- every global load of the prologue up front: the first chunk's count words (+ aux), the row totals, the run's column ----
     uint32_t nwv[GC_ITEMS], nav[GC_ITEMS]; // the NEXT trip's words: wave w reads indices w * 512 + j * 64 + lane of its chunk
+    uint32_t nid[GC_ITEMS];                // DENSE: ... and their indices inside the chunk
+    uint2 un = make_uint2(0u, 0u);         // DENSE: the units' survivors of the chunk that load_chunk loads next ...
+    uint2 unx = make_uint2(0u, 0u);        // ... and of the chunk whose entries nwv / nav / nid hold
+#pragma unroll
+    for (int j = 0; j < GC_ITEMS; ++j) nwv[j] = nav[j] = nid[j] = 0u;
     const uint32_t whole = n / GC;         // chunks below this one need no bounds checks
     auto load_chunk = [&](uint32_t c) {
+        if (DENSE) {
+            // Round j < R (uniform) loads its three values WHATEVER the lane holds -- a position past T reads entry 0 of the chunk
+            // -- and nothing here depends on a loaded value: the validity test, the unit's half and the id wait for the trip that
+            // consumes them (a load under a lane's condition, or arithmetic on its result, is waited for right behind its issue,
+            // eight load latencies a trip instead of one).  Rounds past R keep what an earlier trip left: masked as well.
+            const uint32_t T = un.x + un.y;
+            const uint32_t R = (T + 255u) >> 8; // rounds that hold an entry: a wave's range is 64 R positions
+            const uint32_t p0 = w * (R << 6) + lane;
+#pragma unroll
+            for (int j = 0; j < GC_ITEMS; ++j) {
+                if ((uint32_t)j < R) {
+                    const uint32_t p = p0 + j * 64 < T ? p0 + j * 64 : 0u;
+                    const uint32_t e = c * GC + (p >= un.x ? GU + (p - un.x) : p);
+                    nwv[j] = words[e];
+                    nav[j] = aux_in[e];
+                    nid[j] = (uint32_t)unit_off[e];
+                }
+            }
+            unx = un;
+            return;
+        }
         const uint32_t k0 = c * GC + w * (64 * GC_ITEMS) + lane;
         if (c < whole) { // (uniform)
 #pragma unroll
@@ -201,7 +264,9 @@ __global__ __launch_bounds__(GC_THREADS) void gs_gsort_scatter_kernel(const uint
             }
         }
     };
+    if (DENSE) un = unit_pair(unit_n, chunk0);
     load_chunk(chunk0);
+    if (DENSE) un = chunk0 + 1u < chunk1 ? unit_pair(unit_n, chunk0 + 1u) : make_uint2(0u, 0u);
     {
         uint2 t[BPT], mm[BPT];
 #pragma unroll
@@ -226,7 +291,20 @@ __global__ __launch_bounds__(GC_THREADS) void gs_gsort_scatter_kernel(const uint
         uint32_t wv[GC_ITEMS], av[GC_ITEMS];
 #pragma unroll
         for (int j = 0; j < GC_ITEMS; ++j) { wv[j] = nwv[j]; av[j] = nav[j]; }
+        uint32_t idv[GC_ITEMS];
+#pragma unroll
+        for (int j = 0; j < GC_ITEMS; ++j) idv[j] = 0u;
+        if (DENSE) { // what load_chunk left undecided: which positions hold an entry, and the index inside the chunk
+            const uint32_t T = unx.x + unx.y, R = (T + 255u) >> 8, p0 = w * (R << 6) + lane;
+#pragma unroll
+            for (int j = 0; j < GC_ITEMS; ++j) {
+                const uint32_t p = p0 + j * 64;
+                if (!((uint32_t)j < R && p < T)) wv[j] = 0u; // (j >= R: the position is the next wave's)
+                idv[j] = (p >= unx.x ? GU : 0u) + nid[j];
+            }
+        }
         if (chunk + 1u < chunk1) load_chunk(chunk + 1u); // (uniform) prefetch: consumed at the top of the next trip
+        if (DENSE) un = chunk + 2u < chunk1 ? unit_pair(unit_n, chunk + 2u) : make_uint2(0u, 0u); // (the pair of the chunk after that)
         {   // zero this wave's ranking counters (2 KB: 32 bytes a lane)
             S.u.zero[w * (GBINS / 8) + lane] = make_uint4(0u, 0u, 0u, 0u);
             S.u.zero[w * (GBINS / 8) + 64 + lane] = make_uint4(0u, 0u, 0u, 0u);
@@ -283,7 +361,7 @@ __global__ __launch_bounds__(GC_THREADS) void gs_gsort_scatter_kernel(const uint
                 const uint32_t d = wv[j] >> GS_COUNT_BITS;
                 const uint32_t r = rank2_get(rank2, j);
                 const uint32_t pos = (uint32_t)S.binstart[d] + (uint32_t)S.u.whist[w][d] + r;
-                S.id[pos] = (unsigned short)(w * (64 * GC_ITEMS) + j * 64 + lane);
+                S.id[pos] = (unsigned short)(DENSE ? idv[j] : w * (64 * GC_ITEMS) + j * 64 + lane);
                 S.word[pos] = wv[j];
                 S.aux[pos] = av[j];
             }
@@ -356,8 +434,10 @@ uint64_t gs_gsort_scratch_bytes(uint32_t n) { return ((uint64_t)GBINS * gs_gsort
 // words: one word per gaussian INDEX (quantity in the low 22 bits, depth bucket in the high 10; 0 = not visible); scratch:
 // gs_gsort_scratch_bytes(n) bytes; grid: the context's persistent grid, from which the number of runs follows.  Output
 // records in (bucket, index) order; tot_visible / tot_quantity: device words.
-void gs_launch_gsort(const uint32_t* words, const uint32_t* aux_in, uint32_t n, void* scratch, void* grec, uint32_t* chunk_table, uint32_t chunk_cap,
-                     uint32_t* tot_visible, uint32_t* tot_quantity, uint32_t grid, hipStream_t st) {
+// unit_n != nullptr: the DENSE input form -- words, aux_in and unit_off are the entry planes (whole chunks: gs_gsort_tiles(n) * 2048
+// entries each), unit_n the 2 * gs_gsort_tiles(n) + 2 unit counts.
+void gs_launch_gsort(const uint32_t* words, const uint32_t* aux_in, const unsigned short* unit_off, const uint32_t* unit_n, uint32_t n, void* scratch,
+                     void* grec, uint32_t* chunk_table, uint32_t chunk_cap, uint32_t* tot_visible, uint32_t* tot_quantity, uint32_t grid, hipStream_t st) {
     if (!n) return;
     const uint32_t NT = gs_gsort_tiles(n);
     uint64_t want = (uint64_t)grid * GS_GSORT_RUNS_Q / 4u;
@@ -366,8 +446,12 @@ void gs_launch_gsort(const uint32_t* words, const uint32_t* aux_in, uint32_t n, 
     const uint32_t G = (NT + cpr - 1) / cpr;                 // runs that hold a chunk: min(NT, want) at most
     uint2* M = (uint2*)scratch;
     uint2* rowtot = M + (uint64_t)GBINS * G;
-    hipLaunchKernelGGL(gs_gsort_hist_kernel, dim3(G), dim3(GC_THREADS), 0, st, words, n, M, G, cpr, NT);
+    const uint2* un = (const uint2*)unit_n;
+    if (un) hipLaunchKernelGGL(gs_gsort_hist_kernel<true>, dim3(G), dim3(GC_THREADS), 0, st, words, un, n, M, G, cpr, NT);
+    else hipLaunchKernelGGL(gs_gsort_hist_kernel<false>, dim3(G), dim3(GC_THREADS), 0, st, words, un, n, M, G, cpr, NT);
     hipLaunchKernelGGL(gs_gsort_rowscan_kernel, dim3(GBINS / 8), dim3(GR_THREADS), 0, st, M, G, rowtot);
-    hipLaunchKernelGGL(gs_gsort_scatter_kernel, dim3(G), dim3(GC_THREADS), 0, st, words, aux_in, n, (const uint2*)M, G, cpr, NT, (const uint2*)rowtot,
-                       (uint4*)grec, chunk_table, chunk_cap, tot_visible, tot_quantity);
+    if (un) hipLaunchKernelGGL(gs_gsort_scatter_kernel<true>, dim3(G), dim3(GC_THREADS), 0, st, words, aux_in, unit_off, un, n, (const uint2*)M, G, cpr, NT,
+                               (const uint2*)rowtot, (uint4*)grec, chunk_table, chunk_cap, tot_visible, tot_quantity);
+    else hipLaunchKernelGGL(gs_gsort_scatter_kernel<false>, dim3(G), dim3(GC_THREADS), 0, st, words, aux_in, unit_off, un, n, (const uint2*)M, G, cpr, NT,
+                            (const uint2*)rowtot, (uint4*)grec, chunk_table, chunk_cap, tot_visible, tot_quantity);
 }

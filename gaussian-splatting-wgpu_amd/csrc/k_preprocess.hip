@@ -17,7 +17,8 @@
 //   3. the 192 B of SH: colour, sigmoid, the 64-byte GaussianData store.
 // A culled gaussian costs 12 B, a visible one 12 + 32 + 192 B (round 2 kept geometry and SH in one 256-byte record
 // whose first 128-byte line was fetched by phase 2 AND, long after, by phase 3: 1.53x the algorithmic traffic).
-// Algorithmic bytes per gaussian: 12 (culled) or 236 (visible) read; 4 (count) + 56 (visible) written.
+// Algorithmic bytes per gaussian: 12 (culled) or 236 (visible) read; 4 (count) + 56 (visible) written -- the tight path writes
+// no count for a culled gaussian and 10 bytes of entry per survivor of the cull (see "entries" below).
 // Bound: HBM.  No MFMA (no contraction on this path).
 #include "gs_device.h"
 #include "gs_kernels.h"
@@ -224,9 +225,16 @@ typedef uint32_t gs_row_u32x3 __attribute__((ext_vector_type(3), aligned(4)));
 //             lists hold slot | mask << 28, and the gaussian's id is word 2 of the record.  rec_shard_cap = (workgroups of the
 //             shard) x (gaussians of a workgroup): a shard cannot overflow.  A survivor whose items all turn out empty leaves
 //             its record slot unwritten, as it leaves holes in the arena
-//   rowptr  : first arena slot of every visible gaussian
-//   counts  : SLOTS of the gaussian (rows, twice that with an aliased column) | depth bucket << 22 -- what the gaussian-level
-//             sort (k_gsort.hip) scans; 0 when no tile survives (the tile-count tap of a tight frame is derived from the lists)
+//   entries : what the gaussian-level sort (k_gsort.hip) reads.  A UNIT is 1024 consecutive gaussian indices (two cull chunks; a
+//             workgroup covers NB / 2 of them).  The cull's survivors of a unit are compacted in index order, and survivor e of
+//             unit u owns entry u * 1024 + e of three planes:
+//               counts   SLOTS of the gaussian (rows, twice that with an aliased column) | depth bucket << 22; 0 when no tile
+//                        survives (the sort skips it; the tile-count tap of a tight frame is derived from the lists)
+//               rowptr   its first arena slot
+//               unit_off its index inside the unit (u16)
+//             plus unit_n[u], the unit's survivors.  Nothing is indexed by the gaussian and nothing is written for a culled one
+//             (the kernel used to store a zero word under the cull's mask for each of them, and two scattered words per survivor);
+//             a trip's 256 threads store 256 consecutive entries of each plane.  TIGHT = false keeps counts[i] per gaussian
 //   GsControl::rowhist[r] += items of tile row r (the digit histogram of the row sort, k_rows.hip)
 
 // TIGHT = true : the product path's opacity-aware binning (gs_tight.h): an instance (gaussian, tile) exists only if the tile
@@ -251,6 +259,9 @@ __global__ __launch_bounds__(256, PRE_WAVES) void gs_preprocess_kernel(GsScene s
     __shared__ float s_pos[3][KEEP_POS ? PRE_G * NB : 1];
     __shared__ uint32_t s_cnt[2][4];
     __shared__ uint32_t s_misc[8];
+    // TIGHT: survivors of every (cull round, wave) and the first survivor of every 1024-index unit (ordered compaction, below)
+    __shared__ alignas(16) uint32_t s_rc[TIGHT ? 2 * NB : 1][4];
+    __shared__ uint32_t s_ust[TIGHT ? 4 : 1];
     // TIGHT: per-survivor records of the row-item loop (written and read by the survivor's own wave)
     __shared__ float4 s_tA[TIGHT ? 256 : 1], s_tB[TIGHT ? 256 : 1], s_tC[TIGHT ? 256 : 1]; // gx gy kc qa | qb rcx xmax dyR | eR mode rows cols
     __shared__ uint32_t s_mark[TIGHT ? 256 : 1], s_tcnt[TIGHT ? 256 : 1], s_tgid[TIGHT ? 256 : 1];
@@ -268,10 +279,16 @@ __global__ __launch_bounds__(256, PRE_WAVES) void gs_preprocess_kernel(GsScene s
     // ---- phase 1: in_frustum (:108-125) on the position planes, survivors compacted ----
     uint32_t nvis = 0;
     if (NB > 1) {
-        // survivors are appended wave by wave through one LDS counter: their order in the list is free, every output is
-        // indexed by the gaussian
-        if (tid == 0) s_misc[1] = 0u;
-        __syncthreads();
+        // !TIGHT: survivors are appended wave by wave through one LDS counter: their order in the list is free, every output is
+        // indexed by the gaussian.  TIGHT: the list is in INDEX order -- round r of thread t holds index base + 256 r + t, so the
+        // order is (round, wave, lane): the ballots of a group's rounds, their counts per (round, wave) in LDS, one barrier, a
+        // prefix (what the NB == 1 branch does for its two rounds); `carried` takes the total from group to group.  Survivor
+        // number e of a 1024-index unit then owns entry e of the unit in the planes the gaussian-level sort reads (see "entries")
+        if (!TIGHT) {
+            if (tid == 0) s_misc[1] = 0u;
+            __syncthreads();
+        }
+        uint32_t carried = 0;
         constexpr int GRP = 2 * NB < 8 ? 2 * NB : 8; // positions a thread keeps in flight
 #pragma unroll 1
         for (int h = 0; h < 2 * NB / GRP; ++h) {
@@ -296,6 +313,36 @@ __global__ __launch_bounds__(256, PRE_WAVES) void gs_preprocess_kernel(GsScene s
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
+            if (TIGHT) {
+                uint32_t vm = 0;
+#pragma unroll
+                for (int k = 0; k < GRP; ++k) {
+                    const uint32_t i = base + (uint32_t)(h * GRP + k) * 256u + tid;
+                    bool v = false;
+                    if (i < f.n) {
+                        v = in_frustum_slab(u, f, X[k], Y[k], Z[k], S[k]);
+                        if (STATE && (B[k] & GS_ST_HIDDEN)) v = false; // a hidden splat: exactly a culled one
+                    }
+                    vm |= (v ? 1u : 0u) << k;
+                    const uint32_t c = (uint32_t)__popcll(__ballot(v));
+                    if (lane == 0) s_rc[h * GRP + k][w] = c;
+                }
+                __syncthreads(); // (the rounds of group h have rows of their own: nothing of an earlier group is overwritten)
+#pragma unroll
+                for (int k = 0; k < GRP; ++k) {
+                    const uint4 c = make_uint4(s_rc[h * GRP + k][0], s_rc[h * GRP + k][1], s_rc[h * GRP + k][2], s_rc[h * GRP + k][3]);
+                    const bool v = (vm >> k) & 1u;
+                    const unsigned long long b = __ballot(v);
+                    if (v) {
+                        const uint32_t off = (uint32_t)(h * GRP + k) * 256u + tid;
+                        const uint32_t slot = carried + (w > 0 ? c.x : 0u) + (w > 1 ? c.y : 0u) + (w > 2 ? c.z : 0u) + (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
+                        s_ids[slot] = STATE ? (off | (B[k] << 16)) : off;
+                        if (KEEP_POS) { s_pos[0][slot] = X[k]; s_pos[1][slot] = Y[k]; s_pos[2][slot] = Z[k]; } // the survivor's position rides along
+                    }
+                    carried += (c.x + c.y) + (c.z + c.w);
+                }
+                continue;
+            }
 #pragma unroll
             for (int k = 0; k < GRP; ++k) {
                 const uint32_t off = (uint32_t)(h * GRP + k) * 256u + tid;
@@ -319,8 +366,21 @@ __global__ __launch_bounds__(256, PRE_WAVES) void gs_preprocess_kernel(GsScene s
                 }
             }
         }
+        if (TIGHT && tid < NB / 2) { // unit tid of the workgroup: rounds 4 tid .. 4 tid + 3 (their counts are behind the last group's barrier)
+            uint32_t first = 0, cnt = 0;
+#pragma unroll
+            for (int r = 0; r < 2 * NB; ++r) {
+                const uint4 c = make_uint4(s_rc[r][0], s_rc[r][1], s_rc[r][2], s_rc[r][3]);
+                const uint32_t t = (c.x + c.y) + (c.z + c.w);
+                if (r < 4 * (int)tid) first += t;
+                else if (r < 4 * (int)tid + 4) cnt += t;
+            }
+            s_ust[tid] = first;
+            const uint32_t un = bid * (NB / 2) + tid;
+            if (un < ((f.n + 1023u) >> 10)) to.unit_n[un] = cnt;
+        }
         __syncthreads();
-        nvis = s_misc[1];
+        nvis = TIGHT ? carried : s_misc[1];
     } else {
         bool vis[2];
         uint32_t sb[2] = {0u, 0u};
@@ -544,9 +604,15 @@ __global__ __launch_bounds__(256, PRE_WAVES) void gs_preprocess_kernel(GsScene s
         }
         // low 22 bits: tile count (TIGHT: row-item slots); high 10: the key's depth bucket, u32(min(50*depth, 999)) (write_tile_ids.wgsl:31)
         const uint32_t bucket = f2u_sat(wg_min(50.0f * pv[2], 999.0f));
-        tile_counts[i] = count ? ((TIGHT ? nslots : count) | (bucket << GS_COUNT_BITS)) : 0u;
+        const uint32_t word = count ? ((TIGHT ? nslots : count) | (bucket << GS_COUNT_BITS)) : 0u;
+        if (TIGHT) { // the survivor's entry: a trip's 256 threads store 256 consecutive entries of each plane
+            const uint32_t off = STATE ? (sid & 0xFFFFu) : sid, uk = off >> 10;
+            const uint32_t e = ((bid * (NB / 2) + uk) << 10) + (v - (NB == 2 ? 0u : s_ust[uk]));
+            tile_counts[e] = word;
+            to.rowptr[e] = rowptr;
+            to.unit_off[e] = (unsigned short)(off & 1023u);
+        } else tile_counts[i] = word;
         if (count == 0) continue; // det == 0, no tile survives, or (slab mode) no instance in this rank's tile columns
-        if (TIGHT) to.rowptr[i] = rowptr;
 
         // ---- phase 3: colour (:240-280) and opacity (:282-294) ----
         float col[3];
@@ -591,7 +657,8 @@ void gs_launch_repack(const void* d_aos, uint32_t n, const GsScene& s, hipStream
 // The projection's launch as data: the one kernel of a frame whose arguments change from frame to frame (the uniforms, by
 // value), so a captured frame graph (gs_frame.hip) re-launches it with updated parameters.
 void gs_preprocess_prepare(GsPreprocessLaunch& L, const GsScene& s, const GsUniforms& u, const GsFrame& f, void* gdata, uint32_t* counts,
-                           bool tight, uint32_t* arena, uint32_t* rowptr, GsControl* ctl, uint32_t tight_nb, bool state, GsTint tint) {
+                           bool tight, uint32_t* arena, uint32_t* rowptr, unsigned short* unit_off, uint32_t* unit_n, GsControl* ctl,
+                           uint32_t tight_nb, bool state, GsTint tint) {
     // cull chunks per workgroup (see NB).  Reference binning: 8 for a slab narrower than 30 % of the canvas, 4 up to 75 %, else 1.
     // Tight: 2 on the whole canvas (5 958 workgroups at 6.1 M gaussians: with 8 the 1 490 workgroups were 1.45 residency rounds,
     // the second one half empty), 8 / 4 for slabs as above.
@@ -611,7 +678,7 @@ void gs_preprocess_prepare(GsPreprocessLaunch& L, const GsScene& s, const GsUnif
                                                                                                    : (const void*)&gs_preprocess_kernel<false, 1, false>;
     }
     L.s = s; L.u = u; L.f = f; L.gdata = gdata; L.counts = counts; L.tint = tint;
-    L.to.arena = arena; L.to.rowptr = rowptr; L.to.ctl = ctl;
+    L.to.arena = arena; L.to.rowptr = rowptr; L.to.unit_off = unit_off; L.to.unit_n = unit_n; L.to.ctl = ctl;
     L.to.rec_shard_cap = ((L.blocks + 15u) / 16u) * (PRE_G * nb); // 16 of them are at most n + GS_RECORD_SLACK records for every nb <= 8
     L.args[0] = &L.s; L.args[1] = &L.u; L.args[2] = &L.f; L.args[3] = &L.gdata; L.args[4] = &L.counts; L.args[5] = &L.to; L.args[6] = &L.tint;
 }

@@ -641,8 +641,9 @@ __global__ __launch_bounds__(256) void gs_rows_expand_kernel(const uint32_t* __r
 }
 
 // GS_BUF_KEYS tap of a tight frame: key = tile * 1000 + depth bucket of the gaussian (write_tile_ids.wgsl:31); the tile of list
-// entry j is found in `ranges`, the bucket in the high bits of the gaussian's count word.  The entry names a record slot; the
-// gaussian's id is word 2 of that record (k_preprocess.hip).
+// entry j is found in `ranges`, the bucket is recomputed from the depth word (word 7) of the gaussian's record: a tight frame
+// keeps no count word per gaussian index.  The entry names a record slot; the gaussian's id is word 2 of that record
+// (k_preprocess.hip).
 __device__ __forceinline__ uint32_t rows_entry_id(const uint32_t* __restrict__ gdata, uint32_t nrec, uint32_t v, uint32_t n) {
     const uint32_t slot = v & GS_ID_MASK;
     if (slot >= nrec) return n; // (never: a list holds slots the projection handed out)
@@ -650,8 +651,7 @@ __device__ __forceinline__ uint32_t rows_entry_id(const uint32_t* __restrict__ g
     return g < n ? g : n;
 }
 __global__ __launch_bounds__(256) void gs_rows_rebuild_keys_kernel(const uint32_t* __restrict__ ranges, uint32_t T, const uint32_t* __restrict__ vals,
-                                                                   const uint32_t* __restrict__ gdata, uint32_t nrec,
-                                                                   const uint32_t* __restrict__ counts, uint32_t count, uint32_t n,
+                                                                   const uint32_t* __restrict__ gdata, uint32_t nrec, uint32_t count, uint32_t n,
                                                                    uint32_t* __restrict__ keys) {
     for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < count; i += gridDim.x * 256u) {
         uint32_t lo = 0, hi = T; // first tile whose end is > i
@@ -659,8 +659,11 @@ __global__ __launch_bounds__(256) void gs_rows_rebuild_keys_kernel(const uint32_
             const uint32_t mid = (lo + hi) >> 1;
             if (ranges[mid] > i) hi = mid; else lo = mid + 1u;
         }
-        const uint32_t g = rows_entry_id(gdata, nrec, vals[i], n);
-        keys[i] = lo * 1000u + (g < n ? counts[g] >> GS_COUNT_BITS : 0u);
+        const uint32_t v = vals[i];
+        const uint32_t g = rows_entry_id(gdata, nrec, v, n);
+        // (the projection's own expression on the depth it stored bit for bit: k_preprocess.hip)
+        const uint32_t bucket = g < n ? f2u_sat(wg_min(50.0f * __uint_as_float(gdata[(uint64_t)(v & GS_ID_MASK) * 16u + 7u]), 999.0f)) : 0u;
+        keys[i] = lo * 1000u + bucket;
     }
 }
 // GS_BUF_VALUES / GS_BUF_GAUSSIAN_DATA taps of a tight frame: the list values with the gaussian's id where the frame keeps the
@@ -706,12 +709,12 @@ void gs_launch_rows(const uint32_t* arena, const void* grec, const uint32_t* chu
     hipLaunchKernelGGL(gs_rows_expand_kernel, dim3(cus * RB_EXP_WG), dim3(256), 0, st, (const uint32_t*)rows_sorted, ctl, (const uint32_t*)M3,
                        (const uint32_t*)tileoff, (const uint32_t*)rowtot, f, values, ranges, chunk_cap, row_cap, sticky, rep);
 }
-void gs_launch_rows_rebuild_keys(const uint32_t* ranges, uint32_t T, const uint32_t* vals, const void* gdata, uint32_t nrec, const uint32_t* counts,
-                                 uint32_t count, uint32_t n, uint32_t* keys, hipStream_t st) {
+void gs_launch_rows_rebuild_keys(const uint32_t* ranges, uint32_t T, const uint32_t* vals, const void* gdata, uint32_t nrec, uint32_t count, uint32_t n,
+                                 uint32_t* keys, hipStream_t st) {
     if (!count) return;
     const uint32_t blocks = (count + 255u) / 256u;
     hipLaunchKernelGGL(gs_rows_rebuild_keys_kernel, dim3(blocks < 4096u ? blocks : 4096u), dim3(256), 0, st, ranges, T, vals, (const uint32_t*)gdata, nrec,
-                       counts, count, n, keys);
+                       count, n, keys);
 }
 void gs_launch_rows_rebuild_taps(const uint32_t* vals, const void* gdata, uint32_t nrec, uint32_t count, uint32_t n, uint32_t* ids_out, void* gdata_out,
                                  hipStream_t st) {
