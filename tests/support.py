@@ -318,6 +318,284 @@ def margin_ref(oracle, name, ts, cols=None):
     return oracle_frame(oracle, name, s, u, W, H, ts, cols=cols, want_illcond=True)
 
 
+# ---- the margin scene of the tight binning (test_tight_margins.py, test_tight_host.py), built in pixel space ------------------------
+# gs_tight.h drops an instance before the blend sees it; each of its tests is conservative by an explicit margin.  The scene puts
+# the alpha = 1/255 contour within 1e-7 .. 1e-2 of the pixels a tile or a sub-block hangs on, the ellipse's extreme points on the
+# strip boundaries, conics at the cancellation threshold, opacities at 1/255 and the aliased column, in labelled families.
+TIGHT_FAMILIES = ("contour", "extreme_x", "extreme_y", "cancellation", "opacity_floor", "alias")
+TIGHT_W, TIGHT_H = 500, 116  # 62.5 x 14.5 blocks: partial blocks and tiles at the right and bottom edges at every tile size
+
+
+def pixel_ellipse(W, H, sig_long, sig_short, theta):
+    """make_splats' (sig_long, sig_short, theta) for which the PIXEL-space covariance (before the +0.3 px^2) has standard deviations
+    sig_long, sig_short along axes rotated by theta: make_splats scales the world axes by W/2 and H/2, so on a non-square canvas
+    its own parameters name another ellipse."""
+    sl, ss, th = (np.asarray(a, np.float64) for a in np.broadcast_arrays(sig_long, sig_short, theta))
+    c, s = np.cos(th), np.sin(th)
+    jx, jy = W / 2.0, H / 2.0
+    M = np.empty(sl.shape + (2, 2))
+    M[..., 0, 0] = (sl * sl * c * c + ss * ss * s * s) / (jx * jx)
+    M[..., 0, 1] = M[..., 1, 0] = (sl * sl - ss * ss) * s * c / (jx * jy)
+    M[..., 1, 1] = (sl * sl * s * s + ss * ss * c * c) / (jy * jy)
+    w, v = np.linalg.eigh(M)
+    return np.sqrt(w[..., 1]) * jx, np.sqrt(np.maximum(w[..., 0], 1e-16)) * jy, np.arctan2(v[..., 1, 1], v[..., 0, 1])
+
+
+def tight_geometry(gdata, W, H):
+    """f64 (gx, gy, cx, cy, cz, ln(255 op)) of the oracle's records: the centre is the f32 product the blend forms."""
+    g = gdata_f32(gdata)
+    with np.errstate(all="ignore"):
+        return ((g[:, 0] * F(W)).astype(np.float64), (g[:, 1] * F(H)).astype(np.float64), g[:, 4].astype(np.float64),
+                g[:, 5].astype(np.float64), g[:, 6].astype(np.float64), np.log(255.0 * g[:, 11].astype(np.float64)))
+
+
+def block_qmin_pixels(gx, gy, cx, cy, cz, W, H):
+    """[n, blocks down, blocks across]: the f64 minimum over the in-canvas PIXELS of every 8x8 block of
+    q = 0.5 (cx dx^2 + cz dy^2) + cy dx dy, d = centre - pixel."""
+    nbx, nby = -(-W // 8), -(-H // 8)
+    px, py = np.arange(nbx * 8, dtype=np.float64), np.arange(nby * 8, dtype=np.float64)
+    out = np.empty((np.size(gx), nby, nbx))
+    for i in range(0, np.size(gx), 32):
+        k = slice(i, i + 32)
+        dx = gx[k, None, None] - px[None, None, :]
+        dy = gy[k, None, None] - py[None, :, None]
+        q = 0.5 * (cx[k, None, None] * dx * dx + cz[k, None, None] * dy * dy) + cy[k, None, None] * dx * dy
+        q[:, :, W:] = np.inf
+        q[:, H:, :] = np.inf
+        out[k] = q.reshape(q.shape[0], nby, 8, nbx, 8).min(axis=(2, 4))
+    return out
+
+
+def facing_corner(gx, gy, W, H):
+    """[n, blocks down, blocks across]: the block is the corner block of its 32-pixel tile (so of its 16-pixel tile too) on the
+    side that faces the centre (gx, gy), the canvas's partial last tiles included."""
+    nbx, nby = -(-W // 8), -(-H // 8)
+
+    def side(c, nb):
+        b = np.arange(nb)
+        first, last = (b % 4 == 0), (b % 4 == 3) | (b == nb - 1)
+        lo, hi = c[:, None] < 8.0 * b[None, :], c[:, None] > 8.0 * b[None, :] + 7.0
+        return np.where(lo, first[None, :], np.where(hi, last[None, :], True))
+    return side(gy, nby)[:, :, None] & side(gx, nbx)[:, None, :]
+
+
+def _land_on_blocks(oracle, rng, s, W, H, allow=None, corner_share=0.0, decades=(-7.0, -2.0)):
+    """Sets the opacity of every record of s so that ln(255 op) = qmin + delta for one 8x8 block of its reference rect (tile 8) whose
+    f64 pixel minimum of q lies in (0.2, 5.5): delta = +-10^U(decades) max(1, qmin).  allow(bx, by) restricts the blocks; a
+    corner_share of the records tries the tiles' corner blocks facing the centre first, and every record prefers a block the
+    contour touches at a pixel (below).  Returns (keep, block x, block y)."""
+    n = s.shape[0]
+    u = pixel_uniforms(W, H)
+    gd = oracle.preprocess(s, u, W, H, 8)[0]
+    gx, gy, cx, cy, cz, _ = tight_geometry(gd, W, H)
+    nbx, nby = -(-W // 8), -(-H // 8)
+    qm = block_qmin_pixels(gx, gy, cx, cy, cz, W, H)
+    bx, by = np.arange(nbx)[None, None, :], np.arange(nby)[None, :, None]
+    r = gd[:, 12:16].astype(np.int64)
+    ok = (qm > 0.2) & (qm < 5.5) & (bx >= r[:, 0, None, None]) & (bx < r[:, 2, None, None]) & (by >= r[:, 1, None, None]) & (by < r[:, 3, None, None])
+    if allow is not None:
+        ok &= allow(bx, by)
+    # a block is TOUCHED at a pixel when the minimum of q over its pixels is the minimum over their bounding box too: the contour
+    # then meets the box at that pixel, where the strip and column tests of gs_tight.h have nothing but their margins to spare
+    # (touched[ts]: the same with the box of the block's whole ts-pixel tile: the tile, or the 16-pixel sub-block, hangs on that pixel)
+    e = lambda a: a[:, None, None]
+    touched = {}
+    for ts in (8, 16, 32):
+        x0, y0 = float(ts) * (8 * bx // ts), float(ts) * (8 * by // ts)
+        x1, y1 = np.minimum(x0 + ts - 1.0, W - 1.0), np.minimum(y0 + ts - 1.0, H - 1.0)
+        box = box_qmin_f64(e(cx), e(cy), e(cz), e(gx) - x1, e(gx) - x0, e(gy) - y1, e(gy) - y0)
+        touched[ts] = ok & (qm - box <= 1e-9 * np.maximum(1.0, qm))
+    corner = ok & facing_corner(gx, gy, W, H)
+    want_corner = rng.uniform(size=n) < corner_share
+    pick = rng.uniform(size=n)
+    sign = np.where(rng.uniform(size=n) < 0.5, -1.0, 1.0)
+    mag = 10.0 ** rng.uniform(decades[0], decades[1], n)
+    keep = np.zeros(n, bool)
+    tbx, tby = np.zeros(n, np.int64), np.zeros(n, np.int64)
+    target = np.full(n, 1.0 / 255.0)
+    for i in range(n):
+        pools = ([corner[i] & touched[32][i], corner[i] & touched[8][i], corner[i]] if want_corner[i] else []) + [touched[32][i], touched[16][i], touched[8][i], ok[i]]
+        cand = next((np.argwhere(p) for p in pools if p.any()), None)
+        if cand is None:
+            continue
+        tby[i], tbx[i] = cand[int(pick[i] * len(cand))]
+        q = qm[i, tby[i], tbx[i]]
+        op = np.exp(q + sign[i] * mag[i] * max(1.0, q)) / 255.0
+        if op < 0.999:
+            keep[i], target[i] = True, op
+    s[:, 12] = opacity_logits(oracle, target)
+    return keep, tbx, tby
+
+
+def _extreme_centres(rng, cx, cy, cz, L, W, H, vertical):
+    """Centres that put the rightmost / leftmost (vertical: topmost / bottommost) point of E = {q <= L} within +-10^U(-3, log 0.3)
+    px of a strip boundary row (a multiple of 8; vertical: the first or last pixel row of a tile) and of the first or last pixel
+    centre of an 8-pixel column (vertical: of a pixel column).  Returns (px, py, keep): a splat whose centre would leave the canvas
+    for every boundary and both signs is not placed."""
+    n = cx.size
+    D = cx * cz - cy * cy
+    if vertical:
+        ey = np.sqrt(2.0 * L * cx / D)
+        ex = -cy * ey / cx
+    else:
+        ex = np.sqrt(2.0 * L * cz / D)
+        ey = -cy * ex / cz  # dy = -cy xmax / cz
+    nbx, nby = -(-W // 8), -(-H // 8)
+    px, py, keep = np.zeros(n), np.zeros(n), np.zeros(n, bool)
+    rows = 8.0 * np.arange(1, nby) if not vertical else np.concatenate([8.0 * np.arange(1, nby), 8.0 * np.arange(1, nby) - 1.0])
+    cols = (np.concatenate([8.0 * np.arange(nbx), np.minimum(8.0 * np.arange(nbx) + 7.0, W - 1.0)]) if not vertical
+            else np.arange(W, dtype=np.float64))
+    for i in range(n):
+        opts = [(X, Y, sg) for sg in (-1.0, 1.0) for Y in rows if 0.0 < Y + sg * ey[i] < H - 1.0
+                for X in cols[rng.integers(cols.size, size=3)] if 0.0 < X + sg * ex[i] < W - 1.0]
+        if not opts:
+            continue
+        X, Y, sg = opts[int(rng.integers(len(opts)))]
+        eps = rng.choice([-1.0, 1.0], 2) * 10.0 ** rng.uniform(-3.0, np.log10(0.3), 2)
+        px[i], py[i], keep[i] = X + eps[0] + sg * ex[i], Y + eps[1] + sg * ey[i], True  # the point is at centre - d
+    return px, py, keep
+
+
+def _tip_centres(rng, cx, cy, cz, L, W, H):
+    """Centres for thin diagonal splats near the cancellation threshold, aimed at tight_strip's `dyR +- eR` branches.  gs_tight.h works
+    with three nested ellipses: the exact E, the chords' (discriminant inflated by 1e-5 of its terms S = cx cz + cy^2) and the
+    extents' (Dlo = D - 1.14e-5 S), whose rightmost point is the dyR it compares with the strip.  Where S / D is in the thousands the
+    extents' rightmost point lies ABOVE the chords' topmost point.  A strip boundary row between the two sees no chord there, and
+    only eR tells the strip that it holds the extreme point.  The boundary row is a multiple of 32 (a boundary at every tile size)
+    and the exact tip ends 0.5 .. 6 px past a multiple-of-32 column, so that the tip's pixels are a tile of their own.  Returns
+    (px, py, keep); a conic without such a window, or whose centre would leave the canvas, is not placed."""
+    n = cx.size
+    S, D = cx * cz + cy * cy, cx * cz - cy * cy
+    Dc, Dlo, lim2 = D - 1.0e-5 * S, D - 1.14e-5 * S, 2.0 * (L + 0.01)
+    px, py, keep = np.zeros(n), np.zeros(n), np.zeros(n, bool)
+    with np.errstate(all="ignore"):
+        top_c = np.sqrt(lim2 * 1.00001 * cx / Dc)                                            # the chords' topmost dy
+        dyr = np.abs(cy) / cz * (np.sqrt(lim2 * 1.0001 * cz / Dlo) * 1.0002 + 0.02)          # |dyR| of tight_setup
+        xs = np.sqrt(2.0 * L * cz / D)                                                       # the exact tip: (xs, -cy xs / cz)
+        ys = np.abs(cy) * xs / cz
+    for i in range(n):
+        if not (Dlo[i] > 0.3 * D[i] and dyr[i] > top_c[i] + 0.05):
+            continue
+        b = top_c[i] + rng.uniform(0.15, 0.85) * (dyr[i] - top_c[i])
+        opts = [(Y, sg) for sg in (-1.0, 1.0) for Y in 32.0 * np.arange(1, -(-H // 32)) if 0.0 < Y + sg * b < H - 1.0 and 0.0 <= Y + sg * (b - ys[i]) <= H - 1.0]
+        if not opts:
+            continue
+        Y, sg = opts[int(rng.integers(len(opts)))]
+        right = sg == -np.sign(cy[i])  # the extreme point at dy of sign sg is the rightmost in d = centre - pixel: it points to -x on screen
+        dtip = xs[i] if right else -xs[i]
+        cols = [X for X in 32.0 * np.arange(1, -(-W // 32)) if 0.0 < X + dtip < W - 1.0]
+        if not cols:
+            continue
+        X = cols[int(rng.integers(len(cols)))]
+        tip = X - 1.0 - rng.uniform(0.5, 6.0) if right else X + rng.uniform(0.5, 6.0)
+        px[i], py[i], keep[i] = tip + dtip, Y + sg * b, True
+    return px, py, keep
+
+
+def _angles(rng, n):
+    """Thirds: generic, within +-0.3 of 45 degrees (either diagonal), within +-0.05 of the axes."""
+    k = np.arange(n) % 3
+    diag = np.pi / 4 + np.pi / 2 * rng.integers(2, size=n) + rng.uniform(-0.3, 0.3, n)
+    axis = np.pi / 2 * rng.integers(2, size=n) + rng.uniform(-0.05, 0.05, n)
+    return np.where(k == 0, rng.uniform(0.0, np.pi, n), np.where(k == 1, diag, axis))
+
+
+def tight_margin_scene(oracle, seed=0):
+    """The labelled margin scene of the tight binning.  Returns a dict: splats, uniforms, W, H, family (index into TIGHT_FAMILIES
+    per splat), block (the 8x8 block a splat's opacity was landed on, -1: none), drawn (per family, and for the tip-placed part of
+    the cancellation family: how many splats the construction drew and how many it could place)."""
+    W, H = TIGHT_W, TIGHT_H
+    rng = np.random.Generator(np.random.Philox(key=[4201, seed]))
+    u = pixel_uniforms(W, H)
+    FLOOR = 1e-4  # a pixel-space deviation far below the projection's 0.3 px^2
+    parts, fam, blocks, drawn = [], [], [], {}
+
+    def records(px, py, sl, ss, th, logit=0.0):
+        a, b, t = pixel_ellipse(W, H, sl, ss, th)
+        return make_splats(W, H, px, py, a, b, t, logit, rng=rng)
+
+    def conics(sl, ss, th, op):
+        s = records(np.full(np.size(sl), W / 2.0), np.full(np.size(sl), H / 2.0), sl, ss, th, opacity_logits(oracle, op))
+        return s, tight_geometry(oracle.preprocess(s, u, W, H, 8)[0], W, H)
+
+    def add(name, s, keep, tb=None):
+        drawn[name] = (int(keep.size), int(keep.sum()))
+        parts.append(s[keep])
+        fam.append(np.full(int(keep.sum()), TIGHT_FAMILIES.index(name)))
+        blocks.append(np.stack([tb[0][keep], tb[1][keep]], axis=1) if tb is not None else np.full((int(keep.sum()), 2), -1))
+
+    # contour on a block
+    n = 520
+    sl = np.exp(rng.uniform(np.log(2.0), np.log(300.0), n))
+    ss = np.where(rng.uniform(size=n) < 0.4, FLOOR, np.exp(rng.uniform(np.log(0.3), np.log(sl))))
+    s = records(rng.uniform(-0.03 * W, 1.03 * W, n), rng.uniform(-0.03 * H, 1.03 * H, n), sl, ss, _angles(rng, n))
+    keep, tbx, tby = _land_on_blocks(oracle, rng, s, W, H, corner_share=0.6)
+    add("contour", s, keep, (tbx, tby))
+    # extreme points on the strip boundaries, in x and in y
+    for name, n, vertical in (("extreme_x", 130, False), ("extreme_y", 100, True)):
+        sl = np.exp(rng.uniform(np.log(3.0), np.log(20.0), n))
+        ss = np.where(rng.uniform(size=n) < 0.6, FLOOR, np.exp(rng.uniform(np.log(0.3), np.log(sl))))
+        th = rng.uniform(0.08, np.pi / 2 - 0.08, n) + np.pi / 2 * rng.integers(2, size=n)
+        s, (_, _, cx, cy, cz, L) = conics(sl, ss, th, np.exp(rng.uniform(0.5, 4.0, n)) / 255.0)
+        px, py, keep = _extreme_centres(rng, cx, cy, cz, L, W, H, vertical)
+        s[:, 0], s[:, 1] = 2.0 * px / W - 1.0, 2.0 * py / H - 1.0
+        add(name, s, keep)
+    # cancellation threshold: thin at 45 degrees, the long axis swept across Dlo > 0.25 D, the opacity landed on a block
+    n = 400
+    sl = np.exp(rng.uniform(np.log(30.0), np.log(400.0), n))
+    th = np.pi / 4 + np.pi / 2 * rng.integers(2, size=n) + rng.uniform(-0.03, 0.03, n)
+    s = records(rng.uniform(-0.03 * W, 1.03 * W, n), rng.uniform(-0.03 * H, 1.03 * H, n), sl, FLOOR, th)
+    keep, tbx, tby = _land_on_blocks(oracle, rng, s, W, H, corner_share=0.6, decades=(-7.0, -4.5))
+    # ... and a part of them placed by their extreme point (the opacity drawn, the centre placed: _tip_centres)
+    # S / D of a thin splat is about sl^2 sin^2 cos^2 / 0.15: drawn in 8e3 .. 5e4, with the angle between 15 and 45 degrees of either
+    # axis direction and the opacity such that the tip lies 25 .. 80 px above or below the centre (the canvas is 116 px high)
+    k = 150
+    ratio, th = np.exp(rng.uniform(np.log(8.0e3), np.log(5.0e4), k)), rng.uniform(0.26, 0.78, k)
+    sl = np.sqrt(0.15 * ratio) / (np.sin(th) * np.cos(th))
+    Lt = np.clip(0.5 * (rng.uniform(25.0, 80.0, k) / (sl * np.sin(th))) ** 2, 0.2, 3.0)
+    th = np.where(rng.uniform(size=k) < 0.5, th, np.pi - th)
+    s2, (_, _, cx, cy, cz, L) = conics(sl, FLOOR, th, np.exp(Lt) / 255.0)
+    px, py, keep2 = _tip_centres(rng, cx, cy, cz, L, W, H)
+    s2[:, 0], s2[:, 1] = 2.0 * px / W - 1.0, 2.0 * py / H - 1.0
+    drawn["cancellation_tips"] = (k, int(keep2.sum()))
+    add("cancellation", np.concatenate([s, s2]), np.concatenate([keep, keep2]),
+        (np.concatenate([tbx, np.full(k, -1)]), np.concatenate([tby, np.full(k, -1)])))
+    # opacity at 1/255: ln(255 op) in [-0.02, 0.02], centres on corner pixels of tiles and sub-blocks and half a pixel off them
+    n = 100
+    sl = np.exp(rng.uniform(np.log(0.05), np.log(0.9), n))
+    ss = np.where(rng.uniform(size=n) < 0.5, FLOOR, sl * rng.uniform(0.3, 1.0, n))
+    px = np.minimum(8.0 * rng.integers(-(-W // 8), size=n) + 7.0 * rng.integers(2, size=n), W - 1.0) + 0.5 * rng.integers(2, size=n)
+    py = np.minimum(8.0 * rng.integers(-(-H // 8), size=n) + 7.0 * rng.integers(2, size=n), H - 1.0) + 0.5 * rng.integers(2, size=n)
+    s = records(px, py, sl, ss, rng.uniform(0.0, np.pi, n), opacity_logits(oracle, np.exp(rng.uniform(-0.02, 0.02, n)) / 255.0))
+    add("opacity_floor", s, np.ones(n, bool))
+    # aliased column: the rect reaches column ntx, a long near-horizontal axis reaches, misses or just reaches the first columns
+    n = 100
+    free = np.arange(n) % 10 >= 7  # three in ten keep a free opacity (far misses and plain reaches), the others land on a block
+    sl = np.where(free, rng.uniform(140.0, 260.0, n), rng.uniform(190.0, 260.0, n))
+    ss = np.where(rng.uniform(size=n) < 0.4, FLOOR, np.exp(rng.uniform(np.log(0.3), np.log(6.0), n)))
+    px, py = rng.uniform(W - 12.0, 1.045 * W, n), rng.uniform(0.0, H, n)
+    s = records(px, py, sl, ss, rng.uniform(-0.05, 0.05, n))
+    near = rng.uniform(size=n) < 0.5
+    keep, tbx, tby = _land_on_blocks(oracle, rng, s, W, H, allow=lambda bx, by: bx < np.where(near, 1, 4)[:, None, None])
+    s[free, 12] = opacity_logits(oracle, np.exp(rng.uniform(0.1, 5.5, int(free.sum()))) / 255.0)
+    tbx[free] = tby[free] = -1
+    add("alias", s, keep | free, (tbx, tby))
+    return {"splats": np.concatenate(parts), "uniforms": u, "W": W, "H": H, "family": np.concatenate(fam), "block": np.concatenate(blocks),
+            "drawn": drawn}
+
+
+TIGHT_SCENES = {"tight_margins": tight_margin_scene}
+
+
+def tight_scene(oracle, name="tight_margins"):
+    return cached(("tight_scene", name), lambda: TIGHT_SCENES[name](oracle))
+
+
+def tight_ref(oracle, name, ts, cols=None):
+    t = tight_scene(oracle, name)
+    return oracle_frame(oracle, name, t["splats"], t["uniforms"], t["W"], t["H"], ts, cols=cols, want_illcond=True)
+
+
 # ---- the cases of gs_pick (test_pick.py), which the coverage tests fold per splat ---------------------------------------------------
 def lattice(W, H, x0, dx, y0, dy):
     return np.array([(x, y) for y in range(y0, H, dy) for x in range(x0, W, dx)], np.uint32)

@@ -76,16 +76,17 @@ int main(int argc, char** argv) {
         if (em) { contributing++; exactbits += __builtin_popcount(esub); }
         auto it = sets[g].find(tile);
         if (it == sets[g].end()) {
-            if (em) { if (bad < 5) printf("DROPPED contributing: g=%u tile=%u mask=%x\n", g, tile, em); bad++; }
+            if (em) { if (bad < 100) printf("DROPPED contributing: g=%u tile=%u mask=%x\n", g, tile, em); bad++; }
         } else {
             kept++;
             bits += __builtin_popcount(it->second & 0xF);
-            if (esub & ~it->second) { if (badmask < 5) printf("MASK miss: g=%u tile=%u exact=%x got=%x\n", g, tile, esub, it->second & 0xF); badmask++; }
+            if (esub & ~it->second) { if (badmask < 100) printf("MASK miss: g=%u tile=%u exact=%x got=%x\n", g, tile, esub, it->second & 0xF); badmask++; }
         }
     }
     printf("reference instances %zu | exactly contributing %.4f | kept by tight binning %.4f (tight total %lu) | mask bits per kept %.3f | "
-           "exact sub-blocks per contributing %.3f | dropped-but-contributing %lu | mask misses %lu\n",
+           "exact sub-blocks per contributing %.3f | dropped-but-contributing %lu | mask misses %lu | contributing %lu | kept %lu\n",
            keys.size(), (double)contributing / keys.size(), (double)kept / keys.size(), (unsigned long)total_tight,
-           (double)bits / (kept ? kept : 1), (double)exactbits / (contributing ? contributing : 1), (unsigned long)bad, (unsigned long)badmask);
+           (double)bits / (kept ? kept : 1), (double)exactbits / (contributing ? contributing : 1), (unsigned long)bad, (unsigned long)badmask,
+           (unsigned long)contributing, (unsigned long)kept);
     return (bad || badmask) ? 1 : 0;
 }
