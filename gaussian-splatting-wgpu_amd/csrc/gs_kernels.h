@@ -145,6 +145,27 @@ void gs_launch_neigh_query(const void* qrec, uint32_t nq, uint32_t first_block, 
 // gs_state_neigh: the state pass with a membership read from the count plane (u32[n], 16-byte aligned)
 void gs_launch_state_neigh(uint8_t* state, const uint32_t* plane, uint32_t n, uint32_t min_count, uint32_t max_count, uint32_t inside, uint32_t op,
                            uint32_t bits, uint32_t where_mask, uint32_t where_value, unsigned long long* matched, hipStream_t st);
+// k_cluster.hip: clusters (gs_cluster.hip): a union-find over parent[n] (indexed by splat: a member starts as its own root, a
+// non-member holds GS_CLUSTER_NONE) fed by the neighbourhoods' candidate walk over the members' sorted records.
+// parent / count of every splat: count = 1 for a member with a non-finite coordinate (it has no record), else 0
+void gs_launch_cluster_init(const uint8_t* state, const GsScene& s, uint32_t n, uint32_t mask, uint32_t value, uint32_t* parent, uint32_t* count,
+                            hipStream_t st);
+// the edge pass over workgroups [first_block, first_block + blocks) of 256 sorted members (rec: nrec records, queries and sources
+// alike); *changed |= 1 when a root was hooked
+void gs_launch_cluster_edges(const void* rec, uint32_t nrec, uint32_t first_block, uint32_t blocks, const uint32_t* skeys, const void* table,
+                             const GsNeighGrid& g, float r2, uint32_t n, uint32_t* parent, uint32_t* changed, hipStream_t st);
+void gs_launch_cluster_flatten(const void* rec, uint32_t nrec, uint32_t n, uint32_t* parent, hipStream_t st); // parent[id] = its root
+// count[root] += the records under it (flat trees); fold: one add per wave and distinct root
+void gs_launch_cluster_sizes(const void* rec, uint32_t nrec, uint32_t n, const uint32_t* parent, uint32_t* count, bool fold, hipStream_t st);
+// the two planes from parent / count; slots: the GS_STATE_SLOTS partial records (zeroed by the caller), word 0 += clusters, word 1 =
+// max(word 1, largest size)
+void gs_launch_cluster_commit(const uint32_t* parent, const uint32_t* count, uint32_t n, uint32_t* labels, uint32_t* sizes, unsigned long long* slots,
+                              hipStream_t st);
+// gs_state_cluster_linked: flag[label[i]] = 1 for every splat i with (s_i & mask) == value and a label (flag: n words, zeroed), then
+// the state pass over the label plane with the membership flag[label] != 0
+void gs_launch_cluster_seeds(const uint8_t* state, const uint32_t* labels, uint32_t n, uint32_t mask, uint32_t value, uint32_t* flag, hipStream_t st);
+void gs_launch_state_cluster_linked(uint8_t* state, const uint32_t* labels, uint32_t n, const uint32_t* flag, uint32_t op, uint32_t bits, uint32_t where_mask,
+                                    uint32_t where_value, unsigned long long* matched, hipStream_t st);
 // k_export.hip: the splat edits (gs_export.hip).  Selection = splats with (s & mask) == value in ascending order: `counts` holds
 // gs_select_blocks(n) + 1 words (one per 1024 splats; after the launch their exclusive prefix, the total last), `ids` the total.
 uint32_t gs_select_blocks(uint32_t n);

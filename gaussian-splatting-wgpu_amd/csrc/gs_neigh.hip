@@ -17,7 +17,7 @@
 static_assert(sizeof(gs_neigh) == 40 && offsetof(gs_neigh, max_candidates) == 32, "gs_neigh layout");
 static_assert(sizeof(gs_neigh_info) == 40 && offsetof(gs_neigh_info, cells) == 24 && offsetof(gs_neigh_info, cell_edge) == 36, "gs_neigh_info layout");
 
-static size_t plane_bytes(const gs_ctx* c) { return std::max<size_t>((((size_t)c->n * 4) + 15) & ~(size_t)15, 256); }
+size_t plane_bytes(const gs_ctx* c) { return std::max<size_t>((((size_t)c->n * 4) + 15) & ~(size_t)15, 256); }
 int32_t neigh_plane(gs_ctx* c, hipStream_t st) {
     if (c->ng.plane) return GS_OK;
     HIP_TRY(hipMalloc(c->ng.plane.out(), plane_bytes(c)));
@@ -74,6 +74,87 @@ static int32_t sorted_records(gs_ctx* c, const uint8_t* state, uint32_t mask, ui
     return GS_OK;
 }
 
+// Steps 1 to 3 of a count, which a labelling (gs_cluster.hip) shares: the bounds of the finite sources, the grid, the sources and
+// -- when their filter differs -- the queries in cell order, the candidates per workgroup of 256 sorted queries.  The caller has
+// drained the ring and c->n is 1 .. 2^30 - 1.  b->grid stays false when there is no finite source or no finite query (nothing to
+// find; only the two counts are set).
+int32_t neigh_build(gs_ctx* c, const char* who, float radius, uint32_t smask, uint32_t svalue, uint32_t qmask, uint32_t qvalue, NeighBuilt* b) {
+    gs_ctx::Neigh& s = c->ng;
+    const uint32_t n = c->n;
+    const bool same = smask == qmask && svalue == qvalue;
+    b->state = (smask | svalue | qmask | qvalue) ? c->scene.state : nullptr;
+    int32_t rc;
+
+    // scratch (all of it before the first launch: a failed allocation leaves the planes as they were)
+    const uint32_t nblocks_max = (n + 255u) / 256u;
+    const size_t ctl_sz = (sizeof(GsControl) + 255) & ~(size_t)255;
+    if ((rc = s.bounds.reserve(16)) != GS_OK || (rc = s.keysA.reserve(n)) != GS_OK || (rc = s.valsA.reserve(n)) != GS_OK ||
+        (rc = s.keysB.reserve(n)) != GS_OK || (rc = s.valsB.reserve(n)) != GS_OK || (rc = s.skeys.reserve(n)) != GS_OK || (rc = s.src.reserve((uint64_t)n * 16)) != GS_OK ||
+        (rc = s.sums.reserve(nblocks_max)) != GS_OK || (rc = s.ctl.reserve(ctl_sz + (size_t)4 * gs_sort_tiles(n) * 256 * 4)) != GS_OK)
+        return rc;
+    if (!same && (rc = s.qry.reserve((uint64_t)n * 16)) != GS_OK) return rc;
+
+    // 1. the bounds of the finite sources and the four counts
+    uint32_t hb[16] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+    HIP_TRY(hipMemcpyAsync(s.bounds, hb, sizeof(hb), hipMemcpyHostToDevice, c->stream));
+    gs_launch_neigh_bounds(b->state, c->scene, n, smask, svalue, qmask, qvalue, s.bounds, c->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(hb, s.bounds, sizeof(hb), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    b->sources = hb[6];
+    b->queried = hb[8];
+    b->nsrc = hb[7]; // with finite coordinates: the others have no neighbours
+    b->nqry = hb[9];
+    if (!b->nsrc || !b->nqry) return GS_OK;
+    float lo[3], hi[3];
+    for (int k = 0; k < 3; ++k) { lo[k] = key_value(hb[k]); hi[k] = key_value(hb[3 + k]); }
+    GsNeighGrid& g = b->g;
+    choose_grid(lo, hi, radius, &g, &b->cell_edge);
+
+    // 2. sources, then queries, in cell order
+    rc = s.table.reserve((uint64_t)g.blocks * 8);
+    if (rc != GS_OK) return rc;
+    HIP_TRY(hipMemsetAsync(s.table, 0, (size_t)g.blocks * 8, c->stream));
+    rc = sorted_records(c, b->state, smask, svalue, g, s.src, s.table);
+    if (rc != GS_OK) return rc;
+    uint32_t fault[2] = {0u, 0u};
+    const GsControl* ctl = (const GsControl*)s.ctl.get();
+    HIP_TRY(hipMemcpyAsync(&fault[0], &ctl->fault, 4, hipMemcpyDeviceToHost, c->stream));
+    b->qrec = s.src;
+    if (!same) {
+        HIP_TRY(hipStreamSynchronize(c->stream)); // fault[0] is read before the control block is zeroed again
+        rc = sorted_records(c, b->state, qmask, qvalue, g, s.qry, nullptr);
+        if (rc != GS_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(&fault[1], &ctl->fault, 4, hipMemcpyDeviceToHost, c->stream));
+        b->qrec = s.qry;
+    }
+
+    // 3. the candidates, exactly, per workgroup of 256 sorted queries: the caller checks the budget and cuts the slices
+    const uint32_t nblocks = (b->nqry + 255u) / 256u;
+    gs_launch_neigh_cands(b->qrec, b->nqry, s.src, s.skeys, s.table, b->nsrc, g, s.sums, c->stream);
+    HIP_TRY(hipGetLastError());
+    b->sums.resize(nblocks);
+    HIP_TRY(hipMemcpyAsync(b->sums.data(), s.sums, (size_t)nblocks * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (fault[0] | fault[1]) return fail(GS_ERR_DEVICE_FAULT, "%s: look-back spin bound exceeded in the cell sort", who);
+    for (uint32_t k = 0; k < nblocks; ++k) b->candidates += b->sums[k];
+    b->grid = true;
+    return GS_OK;
+}
+int32_t neigh_budget(const char* who, uint64_t candidates, uint64_t max_candidates, float radius) {
+    const uint64_t budget = max_candidates ? max_candidates : GS_NEIGH_DEFAULT_CANDIDATES;
+    if (candidates > budget)
+        return fail(GS_ERR_CAPACITY, "%s: %llu candidates exceed the work budget max_candidates = %llu (radius %g puts too many splats into one cell)", who,
+                    (unsigned long long)candidates, (unsigned long long)budget, (double)radius);
+    return GS_OK;
+}
+int32_t neigh_check_radius(const char* who, float radius, float* r2) {
+    if (!std::isfinite(radius) || radius < 0.0f) return fail(GS_ERR_INVALID_ARGUMENT, "%s: radius %g is negative or not finite", who, (double)radius);
+    *r2 = radius * radius; // once, in f32: the kernel and a restating host compare with the same number
+    if (!std::isfinite(*r2)) return fail(GS_ERR_INVALID_ARGUMENT, "%s: radius %g squared is not finite in f32", who, (double)radius);
+    return GS_OK;
+}
+
 GS_EXPORT int32_t gs_neigh_count(gs_ctx* c, const gs_neigh* q, gs_neigh_info* info) {
     const char* who = "gs_neigh_count";
     if (!c) return fail(GS_ERR_INVALID_ARGUMENT, "%s: null ctx", who);
@@ -83,9 +164,9 @@ GS_EXPORT int32_t gs_neigh_count(gs_ctx* c, const gs_neigh* q, gs_neigh_info* in
     if (rc != GS_OK) return rc;
     rc = resident_check(c, who, Plane::filtered, q->qry_mask, q->qry_value);
     if (rc != GS_OK) return rc;
-    if (!std::isfinite(q->radius) || q->radius < 0.0f) return fail(GS_ERR_INVALID_ARGUMENT, "%s: radius %g is negative or not finite", who, (double)q->radius);
-    const float r2 = q->radius * q->radius; // once, in f32: the kernel and a restating host compare with the same number
-    if (!std::isfinite(r2)) return fail(GS_ERR_INVALID_ARGUMENT, "%s: radius %g squared is not finite in f32", who, (double)q->radius);
+    float r2;
+    rc = neigh_check_radius(who, q->radius, &r2);
+    if (rc != GS_OK) return rc;
     if (q->limit == 0u) return fail(GS_ERR_INVALID_ARGUMENT, "%s: limit %u is not 1 .. 2^32-1", who, q->limit);
     if (q->reserved != 0u) return fail(GS_ERR_INVALID_ARGUMENT, "%s: reserved %u is not 0", who, q->reserved);
     rc = resident_drain(c);
@@ -98,82 +179,28 @@ GS_EXPORT int32_t gs_neigh_count(gs_ctx* c, const gs_neigh* q, gs_neigh_info* in
     if (!n) { HIP_TRY(hipStreamSynchronize(c->stream)); return GS_OK; }
     if (n >= (1u << 30)) return fail(GS_ERR_CAPACITY, "%s: %u splats, the cell sort takes fewer than 2^30", who, n); // (gs_sort_pairs_u32's limit)
     gs_ctx::Neigh& s = c->ng;
-    const bool same = q->src_mask == q->qry_mask && q->src_value == q->qry_value;
-    const uint8_t* state = (q->src_mask | q->src_value | q->qry_mask | q->qry_value) ? c->scene.state : nullptr;
-
-    // scratch (all of it before the first launch: a failed allocation leaves the plane as it was)
-    const uint32_t nblocks_max = (n + 255u) / 256u;
-    const size_t ctl_sz = (sizeof(GsControl) + 255) & ~(size_t)255;
-    if ((rc = s.bounds.reserve(16)) != GS_OK || (rc = s.keysA.reserve(n)) != GS_OK || (rc = s.valsA.reserve(n)) != GS_OK ||
-        (rc = s.keysB.reserve(n)) != GS_OK || (rc = s.valsB.reserve(n)) != GS_OK || (rc = s.skeys.reserve(n)) != GS_OK || (rc = s.src.reserve((uint64_t)n * 16)) != GS_OK ||
-        (rc = s.sums.reserve(nblocks_max)) != GS_OK || (rc = s.ctl.reserve(ctl_sz + (size_t)4 * gs_sort_tiles(n) * 256 * 4)) != GS_OK)
-        return rc;
-    if (!same && (rc = s.qry.reserve((uint64_t)n * 16)) != GS_OK) return rc;
-
-    // 1. the bounds of the finite sources and the four counts
-    uint32_t hb[16] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
-    HIP_TRY(hipMemcpyAsync(s.bounds, hb, sizeof(hb), hipMemcpyHostToDevice, c->stream));
-    gs_launch_neigh_bounds(state, c->scene, n, q->src_mask, q->src_value, q->qry_mask, q->qry_value, s.bounds, c->stream);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(hb, s.bounds, sizeof(hb), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    out.sources = hb[6];
-    out.queried = hb[8];
-    const uint32_t nsrc = hb[7], nqry = hb[9]; // with finite coordinates: the others have no neighbours
-    if (!nsrc || !nqry) { // nothing to find: every count is 0
-        if (info) *info = out;
+    NeighBuilt b;
+    rc = neigh_build(c, who, q->radius, q->src_mask, q->src_value, q->qry_mask, q->qry_value, &b);
+    if (rc != GS_OK) return rc;
+    out.sources = b.sources;
+    out.queried = b.queried;
+    out.candidates = b.candidates;
+    out.cell_edge = b.cell_edge;
+    for (int k = 0; k < 3; ++k) out.cells[k] = b.g.g[k];
+    if (info) *info = out;
+    if (!b.grid) { // nothing to find: every count is 0
         HIP_TRY(hipMemsetAsync(s.plane, 0, plane_bytes(c), c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         return GS_OK;
     }
-    float lo[3], hi[3];
-    for (int k = 0; k < 3; ++k) { lo[k] = key_value(hb[k]); hi[k] = key_value(hb[3 + k]); }
-    GsNeighGrid g{};
-    choose_grid(lo, hi, q->radius, &g, &out.cell_edge);
-    for (int k = 0; k < 3; ++k) out.cells[k] = g.g[k];
-
-    // 2. sources, then queries, in cell order
-    rc = s.table.reserve((uint64_t)g.blocks * 8);
+    rc = neigh_budget(who, b.candidates, q->max_candidates, q->radius);
     if (rc != GS_OK) return rc;
-    HIP_TRY(hipMemsetAsync(s.table, 0, (size_t)g.blocks * 8, c->stream));
-    rc = sorted_records(c, state, q->src_mask, q->src_value, g, s.src, s.table);
-    if (rc != GS_OK) return rc;
-    uint32_t fault[2] = {0u, 0u};
-    const GsControl* ctl = (const GsControl*)s.ctl.get();
-    HIP_TRY(hipMemcpyAsync(&fault[0], &ctl->fault, 4, hipMemcpyDeviceToHost, c->stream));
-    const void* qrec = s.src;
-    if (!same) {
-        HIP_TRY(hipStreamSynchronize(c->stream)); // fault[0] is read before the control block is zeroed again
-        rc = sorted_records(c, state, q->qry_mask, q->qry_value, g, s.qry, nullptr);
-        if (rc != GS_OK) return rc;
-        HIP_TRY(hipMemcpyAsync(&fault[1], &ctl->fault, 4, hipMemcpyDeviceToHost, c->stream));
-        qrec = s.qry;
-    }
-
-    // 3. the candidates, exactly, per workgroup of 256 sorted queries: the budget, then the slices
-    const uint32_t nblocks = (nqry + 255u) / 256u;
-    gs_launch_neigh_cands(qrec, nqry, s.src, s.skeys, s.table, nsrc, g, s.sums, c->stream);
-    HIP_TRY(hipGetLastError());
-    std::vector<unsigned long long> sums(nblocks);
-    HIP_TRY(hipMemcpyAsync(sums.data(), s.sums, (size_t)nblocks * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (fault[0] | fault[1]) return fail(GS_ERR_DEVICE_FAULT, "%s: look-back spin bound exceeded in the cell sort", who);
-    for (uint32_t b = 0; b < nblocks; ++b) out.candidates += sums[b];
-    if (info) *info = out;
-    const uint64_t budget = q->max_candidates ? q->max_candidates : GS_NEIGH_DEFAULT_CANDIDATES;
-    if (out.candidates > budget)
-        return fail(GS_ERR_CAPACITY, "%s: %llu candidates exceed the work budget max_candidates = %llu (radius %g puts too many splats into one cell)", who,
-                    (unsigned long long)out.candidates, (unsigned long long)budget, (double)q->radius);
 
     // 4. the query pass, in slices of whole workgroups
     HIP_TRY(hipMemsetAsync(s.plane, 0, plane_bytes(c), c->stream));
-    for (uint32_t b0 = 0; b0 < nblocks;) {
-        uint64_t sum = sums[b0];
-        uint32_t b1 = b0 + 1u;
-        while (b1 < nblocks && sum + sums[b1] <= GS_NEIGH_SLICE_CANDIDATES) sum += sums[b1++];
-        gs_launch_neigh_query(qrec, nqry, b0, b1 - b0, s.src, s.skeys, s.table, nsrc, g, r2, q->limit, n, s.plane, c->stream);
-        b0 = b1;
-    }
+    neigh_slices(b.sums, [&](uint32_t b0, uint32_t blocks) {
+        gs_launch_neigh_query(b.qrec, b.nqry, b0, blocks, s.src, s.skeys, s.table, b.nsrc, b.g, r2, q->limit, n, s.plane, c->stream);
+    });
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
     return GS_OK;

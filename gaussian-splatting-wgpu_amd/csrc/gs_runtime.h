@@ -1,11 +1,12 @@
-// gs_runtime.h -- private to the runtime sources (gs_context / gs_frame / gs_readback / gs_state / gs_export / gs_xform / gs_coverage / gs_attr / gs_neigh / gs_ply / gs_stages .hip):
+// gs_runtime.h -- private to the runtime sources (gs_context / gs_frame / gs_readback / gs_state / gs_export / gs_xform / gs_coverage / gs_attr / gs_neigh / gs_cluster / gs_ply / gs_stages .hip):
 //   the error channel (fail, HIP_TRY);
 //   the owners of HIP resources (Owned: DevBuf, PinnedBuf, Event, Stream, File) and Scratch, a device buffer that grows on demand;
 //   the context (gs_ctx, GsOptions, FrameNotes, GraphKey), the lists of its last frame (frame_lists) and sums over its ring (over_ring);
 //   what the calls on the resident splats share: the prologue of a call that drains the ring (Plane, resident_check,
 //   resident_drain, resident_begin), the last frame waited for (last_frame), the staging of a canvas mask (stage_mask), the
-//   coverage planes (cover_planes), the neighbour count plane (neigh_plane), the splat edits' selection (edit_select) and the
-//   check of a gs_attr (attr_check).
+//   coverage planes (cover_planes), the neighbour count plane (neigh_plane), the cell grid a count and a labelling build
+//   (neigh_build, neigh_budget, neigh_slices), the cluster planes (cluster_planes), the splat edits' selection (edit_select) and
+//   the check of a gs_attr (attr_check).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -206,6 +207,9 @@ struct gs_ctx {
         Scratch<unsigned long long> sums;
         uint32_t n32 = 0; // the sort's count, copied from here into the private control block
     } ng;
+    // clusters (gs_cluster.hip): the label and size planes u32[N], allocated (label = GS_CLUSTER_NONE, size = 0) on first use and
+    // dropped with the scene like the count plane; a labelling works in ng's scratch and commits into them at its end
+    struct Cluster { DevBuf<uint32_t> label, size; } cl;
     Event ev[GS_EV_RING][GS_STAGE_COUNT + 1]; // ring of per-frame stage brackets (GS_FLAG_TIMING)
     bool have_events = false;
     uint64_t timed_from = 0; // first frame index included in the stage means
@@ -271,6 +275,40 @@ int32_t last_frame(gs_ctx* root, const char* who, gs_ctx** c);
 int32_t cover_planes(gs_ctx* root, hipStream_t st);
 // gs_neigh.hip: the neighbour count plane of `c`, allocated and zeroed (on `st`) by the first call that needs it
 int32_t neigh_plane(gs_ctx* c, hipStream_t st);
+size_t plane_bytes(const gs_ctx* c); // of a u32[N] plane: whole 16-byte groups (the state pass reads a uint4 per thread)
+// What a count and a labelling share (gs_neigh.hip).  neigh_check_radius: the refusals of a radius; *r2 = radius * radius, once,
+// in f32.  neigh_build: the cell grid over the finite sources, the sources (c->ng.src, skeys, table) and the queries (qrec: the
+// sources' records when both filters are the same) in cell order, and the candidates of every workgroup of 256 sorted queries.
+// neigh_budget: GS_ERR_CAPACITY when the candidates exceed max_candidates (0: GS_NEIGH_DEFAULT_CANDIDATES).  neigh_slices: cuts the
+// workgroups into runs of at most GS_NEIGH_SLICE_CANDIDATES (one workgroup where a single one exceeds that) and calls
+// launch(first workgroup, workgroups) for each.
+struct NeighBuilt {
+    GsNeighGrid g{};
+    const uint8_t* state = nullptr;    // the state plane, or null when both filters are (0, 0)
+    uint64_t sources = 0, queried = 0; // splats that pass the two filters ...
+    uint32_t nsrc = 0, nqry = 0;       // ... and those of them with finite coordinates: the records
+    bool grid = false;                 // what follows is set: there was something to find
+    float cell_edge = 0.0f;
+    const void* qrec = nullptr;
+    std::vector<unsigned long long> sums;
+    uint64_t candidates = 0;
+};
+int32_t neigh_check_radius(const char* who, float radius, float* r2);
+int32_t neigh_build(gs_ctx* c, const char* who, float radius, uint32_t smask, uint32_t svalue, uint32_t qmask, uint32_t qvalue, NeighBuilt* b);
+int32_t neigh_budget(const char* who, uint64_t candidates, uint64_t max_candidates, float radius);
+template <class Launch>
+void neigh_slices(const std::vector<unsigned long long>& sums, Launch launch) {
+    const uint32_t nblocks = (uint32_t)sums.size();
+    for (uint32_t b0 = 0; b0 < nblocks;) {
+        uint64_t sum = sums[b0];
+        uint32_t b1 = b0 + 1u;
+        while (b1 < nblocks && sum + sums[b1] <= GS_NEIGH_SLICE_CANDIDATES) sum += sums[b1++];
+        launch(b0, b1 - b0);
+        b0 = b1;
+    }
+}
+// gs_cluster.hip: the label and size planes of `c`, allocated and set to their initial reading (on `st`) by the first call that needs them
+int32_t cluster_planes(gs_ctx* c, hipStream_t st);
 // gs_export.hip: the splat edits' selection: counts the splats with (s & mask) == value and, with want_ids, leaves their indices,
 // ascending, in c->ex.ids
 int32_t edit_select(gs_ctx* c, uint32_t mask, uint32_t value, bool want_ids, uint64_t* total);

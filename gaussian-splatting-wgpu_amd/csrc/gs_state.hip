@@ -1,5 +1,5 @@
 // gs_state.hip -- the state plane's entry points: region, id, coverage and attribute selections, counting, restore.  Part of the C ABI
-// (include/gsplat/gs_abi.h "splat state"; gs_state_coverage under "coverage", gs_state_attr under "splat attributes"); the kernels are in k_state.hip, the projection that
+// (include/gsplat/gs_abi.h "splat state"; gs_state_coverage under "coverage", gs_state_attr under "splat attributes", gs_state_neigh under "neighbourhoods", gs_state_cluster and gs_state_cluster_linked under "clusters"); the kernels are in k_state.hip, the projection that
 // honours the plane in k_preprocess.hip (STATE).  Also what every call on the resident splats does first (gs_runtime.h).
 //
 // The reference has no counterpart: it is a viewer.  An editor on it would edit its own 320-byte records and upload them again
@@ -177,6 +177,48 @@ GS_EXPORT int32_t gs_state_neigh(gs_ctx* c, uint32_t min_count, uint32_t max_cou
     if (rc != GS_OK) return rc;
     return state_counted(c, [&](unsigned long long* slots) {
         gs_launch_state_neigh(plane(c), c->ng.plane, c->n, min_count, max_count, inside, op, bits, where_mask, where_value, slots, c->stream);
+    }, matched);
+}
+
+// Select by cluster size: gs_state_neigh's pass over the size plane (gs_cluster.hip), which the first call that needs it allocates.
+GS_EXPORT int32_t gs_state_cluster(gs_ctx* c, uint32_t min_size, uint32_t max_size, uint32_t inside, uint32_t where_mask, uint32_t where_value, uint32_t op,
+                                   uint32_t bits, uint64_t* matched) {
+    int32_t rc = resident_check(c, "gs_state_cluster", Plane::always);
+    if (rc != GS_OK) return rc;
+    rc = state_check_op("gs_state_cluster", op, bits);
+    if (rc != GS_OK) return rc;
+    if (where_mask > 0xFFu) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_cluster: where_mask 0x%x does not fit the state byte", where_mask);
+    rc = resident_drain(c, true);
+    if (rc != GS_OK) return rc;
+    rc = cluster_planes(c, c->stream);
+    if (rc != GS_OK) return rc;
+    return state_counted(c, [&](unsigned long long* slots) {
+        gs_launch_state_neigh(plane(c), c->cl.size, c->n, min_size, max_size, inside, op, bits, where_mask, where_value, slots, c->stream);
+    }, matched);
+}
+
+// Select the clusters that hold a seed: every seed sets the flag word of its label (n zeroed words of the neighbourhoods' scratch),
+// then the state pass over the label plane reads the flag of every splat's label.
+GS_EXPORT int32_t gs_state_cluster_linked(gs_ctx* c, uint32_t seed_mask, uint32_t seed_value, uint32_t where_mask, uint32_t where_value, uint32_t op,
+                                          uint32_t bits, uint64_t* matched) {
+    int32_t rc = resident_check(c, "gs_state_cluster_linked", Plane::always);
+    if (rc != GS_OK) return rc;
+    rc = state_check_op("gs_state_cluster_linked", op, bits);
+    if (rc != GS_OK) return rc;
+    if (seed_mask > 0xFFu) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_cluster_linked: seed_mask 0x%x does not fit the state byte", seed_mask);
+    if (where_mask > 0xFFu) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_cluster_linked: where_mask 0x%x does not fit the state byte", where_mask);
+    rc = resident_drain(c, true);
+    if (rc != GS_OK) return rc;
+    rc = cluster_planes(c, c->stream);
+    if (rc != GS_OK) return rc;
+    if (!c->n) { if (matched) *matched = 0; return GS_OK; }
+    rc = c->ng.keysA.reserve(c->n);
+    if (rc != GS_OK) return rc;
+    uint32_t* flag = c->ng.keysA;
+    HIP_TRY(hipMemsetAsync(flag, 0, (size_t)c->n * 4, c->stream));
+    gs_launch_cluster_seeds(c->scene.state, c->cl.label, c->n, seed_mask, seed_value, flag, c->stream);
+    return state_counted(c, [&](unsigned long long* slots) {
+        gs_launch_state_cluster_linked(plane(c), c->cl.label, c->n, flag, op, bits, where_mask, where_value, slots, c->stream);
     }, matched);
 }
 

@@ -38,21 +38,12 @@
 //             construction, a search halves its interval); no spin, no hand-off between workgroups, no float atomics, no scratch,
 //             no LDS.  Bound: VALU issue (uniform path) / L1 gather rate (per-lane path).  VGPRs and occupancy: gs_neigh_query_kernel.
 //   state   : gs_state_coverage's quad mapping around the u32 plane: 5 B read per splat, at most 1 B written.
-#include "gs_device.h"
-#include "gs_kernels.h"
-#include "gs_state_sum.h"
+#include "gs_neigh_dev.h" // the cell expression, NeighSources, neigh_run and the state pass around a plane: shared with k_cluster.hip
 
 __device__ __forceinline__ uint32_t neigh_order_key(float v) { // order-preserving map of the bit pattern (gs_abi.h, splat attributes)
     const uint32_t b = __float_as_uint(v);
     return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
 }
-__device__ __forceinline__ bool neigh_finite(float x, float y, float z) {
-    return fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(z) < INFINITY; // (a NaN fails)
-}
-__device__ __forceinline__ int neigh_cell(float x, float lo, float inv_h, uint32_t g) {
-    return (int)fminf(fmaxf(floorf((x - lo) * inv_h), 0.0f), (float)(g - 1u)); // (fmaxf: a NaN product -- 0 * inf -- is cell 0)
-}
-
 // out[16]: [0..2] min keys of x, y, z over the finite sources, [3..5] max keys, [6] sources, [7] finite sources, [8] queries,
 // [9] finite queries.  The caller initialises it (min keys all ones, the rest 0).
 __global__ __launch_bounds__(256) void gs_neigh_bounds_kernel(const uint8_t* __restrict__ state, const float* __restrict__ px, const float* __restrict__ py,
@@ -148,38 +139,6 @@ void gs_launch_neigh_records(const uint32_t* keys, const uint32_t* vals, uint32_
                        (uint2*)table);
 }
 
-// What the candidates kernel and the query pass read of the sources.  nrec bounds what a table entry may name (it never names
-// more: gs_neigh_records_kernel).
-struct NeighSources {
-    const float4* __restrict__ rec;
-    const uint32_t* __restrict__ keys;
-    const uint2* __restrict__ table;
-    uint32_t nrec;
-};
-// The spans of source records of the x-run around cell x of row (y, z): cells max(x - 1, 0) .. min(x + 1, Gx - 1), consecutive
-// keys k0 .. k1, in every block they touch (one or two; three when a block is a cell).  f(lo, hi) takes each non-empty span.
-template <class F>
-__device__ __forceinline__ void neigh_run(const NeighSources& S, const GsNeighGrid& g, int x, int y, int z, F&& f) {
-    if (y < 0 || y >= (int)g.g[1] || z < 0 || z >= (int)g.g[2]) return;
-    const uint32_t base = ((uint32_t)z << g.bxy) | ((uint32_t)y << g.bx);
-    const uint32_t k0 = base + (uint32_t)(x > 0 ? x - 1 : 0), k1 = base + (uint32_t)(x + 1 < (int)g.g[0] ? x + 1 : (int)g.g[0] - 1);
-    for (uint32_t p = k0 >> g.shift; p <= (k1 >> g.shift) && p < g.blocks; ++p) {
-        uint2 e = S.table[p]; // an empty block holds {0, 0}
-        if (e.y > S.nrec) e.y = S.nrec;
-        if (e.x >= e.y) continue;
-        uint32_t lo = e.x, hi = e.y;
-        if (g.shift) { // the first key >= k0 and the first key > k1 of the block: each search halves [a, b)
-            uint32_t a = e.x, b = e.y;
-            while (a < b) { const uint32_t m = (a + b) >> 1; if (S.keys[m] < k0) a = m + 1u; else b = m; }
-            lo = a;
-            b = e.y;
-            while (a < b) { const uint32_t m = (a + b) >> 1; if (S.keys[m] <= k1) a = m + 1u; else b = m; }
-            hi = a;
-        }
-        if (lo < hi) f(lo, hi);
-    }
-}
-
 // sums[b]: the candidates of sorted queries 256 b .. 256 b + 255 (those below nq), self included where the query is a source.
 __global__ __launch_bounds__(256) void gs_neigh_cands_kernel(const float4* __restrict__ qrec, uint32_t nq, NeighSources S, GsNeighGrid g,
                                                               unsigned long long* __restrict__ sums) {
@@ -262,44 +221,21 @@ void gs_launch_neigh_query(const void* qrec, uint32_t nq, uint32_t first_block, 
     hipLaunchKernelGGL(gs_neigh_query_kernel, dim3(blocks), dim3(256), 0, st, (const float4*)qrec, nq, first_block, S, g, r2, limit, n, plane);
 }
 
-// gs_state_neigh: the state pass (k_state.hip) around the count plane, 5 B read per splat -- the state word and one uint4 of counts.
-__device__ __forceinline__ bool neigh_member(uint32_t c, uint32_t lo, uint32_t hi, bool inside) { return (c >= lo && c <= hi) == inside; }
+// gs_state_neigh (and gs_state_cluster over the size plane): the state pass around a u32 plane (gs_neigh_dev.h) with the range
+// membership (c >= lo && c <= hi) == inside.
+struct NeighRange {
+    uint32_t lo, hi;
+    bool inside;
+    __device__ __forceinline__ bool operator()(uint32_t c) const { return (c >= lo && c <= hi) == inside; }
+};
 __global__ __launch_bounds__(256) void gs_state_neigh_kernel(uint8_t* __restrict__ state, const uint32_t* __restrict__ plane, uint32_t n, uint32_t lo, uint32_t hi,
                                                               uint32_t inside, uint32_t op, uint32_t bits, uint32_t wmask, uint32_t wvalue,
                                                               unsigned long long* __restrict__ matched) {
-    state_block_begin();
-    const uint32_t q = blockIdx.x * 256u + threadIdx.x; // splats 4q .. 4q+3
-    const uint64_t first = (uint64_t)q * 4u;
-    const bool in_range = inside != 0u;
-    uint32_t hits = 0;
-    if (first + 4u <= n) {
-        const uint32_t w = reinterpret_cast<const uint32_t*>(state)[q];
-        const uint4 c4 = reinterpret_cast<const uint4*>(plane)[q];
-        const uint32_t C[4] = {c4.x, c4.y, c4.z, c4.w};
-        uint32_t nw = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const uint32_t sv = (w >> (8 * k)) & 0xFFu;
-            const bool in = ((sv & wmask) == wvalue) && neigh_member(C[k], lo, hi, in_range);
-            hits += in ? 1u : 0u;
-            nw |= (in ? gs_state_apply(sv, op, bits) : sv) << (8 * k);
-        }
-        if (nw != w) reinterpret_cast<uint32_t*>(state)[q] = nw; // stored only if it changed
-    } else if (first < n) {
-        for (uint64_t i = first; i < n; ++i) {
-            const uint32_t sv = state[i];
-            const bool in = ((sv & wmask) == wvalue) && neigh_member(plane[i], lo, hi, in_range);
-            hits += in ? 1u : 0u;
-            const uint32_t nv = in ? gs_state_apply(sv, op, bits) : sv;
-            if (nv != sv) state[i] = (uint8_t)nv;
-        }
-    }
-    state_block_add(hits, matched);
+    state_plane_pass(state, plane, n, NeighRange{lo, hi, inside != 0u}, op, bits, wmask, wvalue, matched);
 }
 void gs_launch_state_neigh(uint8_t* state, const uint32_t* plane, uint32_t n, uint32_t min_count, uint32_t max_count, uint32_t inside, uint32_t op,
                            uint32_t bits, uint32_t where_mask, uint32_t where_value, unsigned long long* matched, hipStream_t st) {
     if (!n) return;
-    const uint32_t quads = (n + 3u) / 4u, blocks = (quads + 255u) / 256u;
-    hipLaunchKernelGGL(gs_state_neigh_kernel, dim3(blocks), dim3(256), 0, st, state, plane, n, min_count, max_count, inside, op, bits, where_mask,
-                       where_value, matched);
+    hipLaunchKernelGGL(gs_state_neigh_kernel, dim3(state_plane_blocks(n)), dim3(256), 0, st, state, plane, n, min_count, max_count, inside, op, bits,
+                       where_mask, where_value, matched);
 }

@@ -70,6 +70,10 @@ GS_ATTR_MAX_BINS = 1024
 GS_ERR_CAPACITY = -8
 GS_NEIGH_LIMIT_NONE = 0xFFFFFFFF  # gs_neigh.limit: count every neighbour
 
+# clusters
+GS_CLUSTER_NONE = 0xFFFFFFFF  # the label of a splat that is no member
+GS_CLUSTER_MAX_ROUNDS = 64
+
 # every symbol include/gsplat/gs_abi.h declares
 ABI_SYMBOLS = ("gs_last_error", "gs_abi_version", "gs_create", "gs_destroy", "gs_upload_splats", "gs_upload_splats_device",
                "gs_share_splats",
@@ -80,7 +84,8 @@ ABI_SYMBOLS = ("gs_last_error", "gs_abi_version", "gs_create", "gs_destroy", "gs
                "gs_xform_compose", "gs_transform_splats",
                "gs_coverage_accumulate", "gs_coverage_reset", "gs_coverage_read", "gs_state_coverage",
                "gs_attr_summary", "gs_attr_histogram", "gs_attr_read", "gs_state_attr",
-               "gs_neigh_count", "gs_neigh_read", "gs_state_neigh", "gs_set_option", "gs_slab_width", "gs_assemble_slabs", "gs_sort_pairs_u32",
+               "gs_neigh_count", "gs_neigh_read", "gs_state_neigh",
+               "gs_cluster_label", "gs_cluster_read", "gs_state_cluster", "gs_state_cluster_linked", "gs_set_option", "gs_slab_width", "gs_assemble_slabs", "gs_sort_pairs_u32",
                "gs_exclusive_scan_u32")
 
 
@@ -154,6 +159,16 @@ class GsNeigh(ctypes.Structure):
 class GsNeighInfo(ctypes.Structure):
     _fields_ = [("queried", ctypes.c_uint64), ("sources", ctypes.c_uint64), ("candidates", ctypes.c_uint64), ("cells", ctypes.c_uint32 * 3),
                 ("cell_edge", ctypes.c_float)]
+
+
+class GsCluster(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("radius", ctypes.c_float), ("mask", ctypes.c_uint32), ("value", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32 * 2), ("max_candidates", ctypes.c_uint64)]
+
+
+class GsClusterInfo(ctypes.Structure):
+    _fields_ = [("members", ctypes.c_uint64), ("clusters", ctypes.c_uint64), ("largest", ctypes.c_uint64), ("candidates", ctypes.c_uint64),
+                ("rounds", ctypes.c_uint32), ("cells", ctypes.c_uint32 * 3), ("cell_edge", ctypes.c_float), ("reserved", ctypes.c_uint32)]
 
 
 # numpy views of the same records (what Renderer.pick returns)
@@ -230,6 +245,10 @@ def load():
     L.gs_neigh_count.argtypes = [vp, ctypes.POINTER(GsNeigh), ctypes.POINTER(GsNeighInfo)]
     L.gs_neigh_read.argtypes = [vp, vp, u64, ctypes.POINTER(u64)]
     L.gs_state_neigh.argtypes = [vp, u32, u32, u32, u32, u32, u32, u32, ctypes.POINTER(u64)]
+    L.gs_cluster_label.argtypes = [vp, ctypes.POINTER(GsCluster), ctypes.POINTER(GsClusterInfo)]
+    L.gs_cluster_read.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64)]
+    L.gs_state_cluster.argtypes = [vp, u32, u32, u32, u32, u32, u32, u32, ctypes.POINTER(u64)]
+    L.gs_state_cluster_linked.argtypes = [vp, u32, u32, u32, u32, u32, u32, ctypes.POINTER(u64)]
     L.gs_set_option.argtypes = [vp, i32, ctypes.c_int64]
     L.gs_slab_width.argtypes = [vp, ctypes.POINTER(u32), ctypes.POINTER(u32)]
     L.gs_assemble_slabs.argtypes = [vp, vp, ctypes.POINTER(u32), u32, u64, vp]

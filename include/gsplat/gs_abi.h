@@ -614,6 +614,76 @@ int32_t gs_neigh_read(gs_ctx* ctx, uint32_t* dst, uint64_t cap, uint64_t* n);
 int32_t gs_state_neigh(gs_ctx* ctx, uint32_t min_count, uint32_t max_count, uint32_t inside, uint32_t where_mask, uint32_t where_value,
                        uint32_t op, uint32_t bits, uint64_t* matched);
 
+/* ---- clusters: label the splats that are connected within a radius, select by cluster ------------------------
+ * A neighbour count is a local answer.  "Select the whole object I clicked on", "delete every island smaller than 200 splats" and
+ * "keep only the main body" are global ones: a detached blob of floaters is dense inside and survives every count.  These calls
+ * label the connected components on the device, with the neighbourhoods' grid, distance expression, work budget and slices.
+ * THE DEFINITION.  MEMBERS are the splats i with (s_i & mask) == value (gs_state_count's filter).  Two members i != j are LINKED when
+ *     d2(i, j) <= r2;   d = p_j - p_i per component;  d2 = (dx dx + dy dy) + dz dz;  r2 = radius * radius
+ * -- the neighbourhoods' expression with nothing changed: one f32 rounding per written operation, no contraction, r2 ONE f32
+ * product, the comparison <= INCLUSIVE.  A member with a NaN or infinite coordinate is linked to nobody.  A CLUSTER is a connected
+ * component of that graph.  For every resident splat i
+ *     member:                                label[i] = the smallest splat index in i's cluster,  size[i] = its members (>= 1)
+ *     member with a non-finite coordinate:   label[i] = i (a singleton),                          size[i] = 1
+ *     non-member:                            label[i] = GS_CLUSTER_NONE,                          size[i] = 0
+ * Both planes are integers and depend on nothing but the positions, the state bytes and the radius: two runs, a slab ctx, a
+ * borrower of gs_share_splats, a fresh ctx and a brute-force host restatement agree bit for bit.  radius = 0 (or one whose square
+ * is 0) clusters exact duplicates.
+ * THE PLANES are u32[N] each and belong to the ctx the call is made on (the root of a ring; a borrower keeps its own), like the
+ * count plane.  They are allocated by the first call that needs them and read label = GS_CLUSTER_NONE, size = 0 before the first
+ * labelling; gs_cluster_label overwrites both as a whole; they are DROPPED -- they read as before the first labelling again -- by
+ * every gs_upload_*, gs_share_splats and gs_compact.  State calls and transforms leave them untouched: they describe the
+ * positions and states at the time of the labelling, and a host that moves or re-filters splats labels again.
+ * WORK.  A labelling builds the neighbourhoods' grid over the members, then runs ROUNDS: an edge pass over the candidates (a
+ * concurrent union-find: each linked pair hooks the larger of its two roots under the smaller) followed by a pass that flattens the
+ * trees, until a whole edge pass hooked nothing; one round does the work, the next one proves it.  max_candidates (0:
+ * GS_NEIGH_DEFAULT_CANDIDATES) is the budget of ONE round: above it the call returns GS_ERR_CAPACITY with both numbers in the
+ * message.  Every edge pass is issued in slices of at most GS_NEIGH_SLICE_CANDIDATES, as a count's query pass.  More than
+ * GS_CLUSTER_MAX_ROUNDS rounds: GS_ERR_DEVICE_FAULT with the count in the message (unreachable; the bound that keeps the call
+ * from running away).  A call that fails for any reason -- budget, allocation, round cap -- leaves both planes as they were.
+ * Prologue, ordering and refusals are the neighbourhoods': the filter as gs_state_count, above 0xFF refused, (0, 0) matches every
+ * splat and is accepted on a ctx without GS_FLAG_SPLAT_STATE, any other filter on such a ctx is refused.  Every call first
+ * completes all frames enqueued on the ctx's ring, runs on the ctx's stream and returns when done; none is a frame or an upload.
+ * GS_ERR_NO_SCENE before any upload; N == 0: zero results, GS_OK.  gs_cluster_label and gs_cluster_read work on a borrower; the
+ * two state calls need GS_FLAG_SPLAT_STATE and have gs_state_region's rules (bits / where_mask / seed_mask above 0xFF and an
+ * unknown op are refused, nothing is applied).  A wrong struct_size, a radius that is negative or not finite, a radius * radius
+ * that is not finite in f32 or reserved != 0: GS_ERR_INVALID_ARGUMENT and a message that names the number. */
+#define GS_CLUSTER_NONE 0xFFFFFFFFu
+#define GS_CLUSTER_MAX_ROUNDS 64u
+typedef struct gs_cluster {        /* 32 bytes */
+    uint32_t struct_size;          /* = sizeof(gs_cluster) */
+    float    radius;               /* finite, >= 0; r2 = radius * radius must be finite in f32 */
+    uint32_t mask, value;          /* MEMBERS: splats i with (s_i & mask) == value */
+    uint32_t reserved[2];          /* 0 */
+    uint64_t max_candidates;       /* work budget PER ROUND, 0 = GS_NEIGH_DEFAULT_CANDIDATES */
+} gs_cluster;
+typedef struct gs_cluster_info {   /* 56 bytes */
+    uint64_t members;              /* splats that pass the filter */
+    uint64_t clusters;             /* members whose label is their own index */
+    uint64_t largest;              /* the maximum of size */
+    uint64_t candidates;           /* distance tests of one round: the members in the 27 cells around every member, self included */
+    uint32_t rounds;               /* edge passes that were run */
+    uint32_t cells[3]; float cell_edge; /* the grid that was used (diagnostic; no result depends on it) */
+    uint32_t reserved;
+} gs_cluster_info;
+/* Labels into the two planes.  info (may be NULL) is written whenever the grid was built, also when the budget refuses the call
+ * (members, candidates and the grid; clusters, largest and rounds are those of a completed labelling). */
+int32_t gs_cluster_label(gs_ctx* ctx, const gs_cluster* q, gs_cluster_info* info);
+/* The planes in HOST memory, N words each in splat order, with gs_neigh_read's conventions: labels and sizes may each be NULL, both
+ * NULL: only *n (= N) is written (query); cap < N: GS_ERR_INVALID_ARGUMENT, the message names the count needed, nothing is written. */
+int32_t gs_cluster_read(gs_ctx* ctx, uint32_t* labels, uint32_t* sizes, uint64_t cap, uint64_t* n);
+/* Applies `op` with `bits` exactly as gs_state_region does, to the splats that pass (s & where_mask) == where_value and for which
+ *     (size >= min_size && size <= max_size) == (inside != 0)
+ * -- the plain expression on the plane value, so a non-member's 0 takes part, as in gs_state_neigh (whose pass this is, over the
+ * size plane).  min_size > max_size is a valid empty range.  *matched (may be NULL) as for gs_state_region. */
+int32_t gs_state_cluster(gs_ctx* ctx, uint32_t min_size, uint32_t max_size, uint32_t inside, uint32_t where_mask, uint32_t where_value,
+                         uint32_t op, uint32_t bits, uint64_t* matched);
+/* Applies `op` with `bits` to the splats that pass `where`, have label != GS_CLUSTER_NONE and whose cluster holds at least one
+ * splat that passes (s & seed_mask) == seed_value as the state plane is NOW; the labels are those of the last labelling.  Two
+ * passes: every seed sets the flag word of its label, then the state pass reads the flag of every splat's label. */
+int32_t gs_state_cluster_linked(gs_ctx* ctx, uint32_t seed_mask, uint32_t seed_value, uint32_t where_mask, uint32_t where_value,
+                                uint32_t op, uint32_t bits, uint64_t* matched);
+
 /* Tuning / profiling knobs. */
 #define GS_OPT_BLEND_ABLATION 1  /* bit 3 (8): the workgroup-per-tile blend kernel at tiles 16 and 32 (identical results; default = one
                                     wave per 8x8 pixel block); bit 2 (4): every blend kernel without its two parking culls (live box,
