@@ -180,6 +180,10 @@ void gs_launch_compact_planes(const GsScene& o, uint32_t n_old, const uint32_t* 
 // x.flags are transformed in place.
 struct gs_xform;
 void gs_launch_xform(const GsScene& s, uint32_t n, const uint32_t* ids, uint32_t m, const gs_xform& x, hipStream_t st);
+// k_grade.hip: gs_grade_splats.  Entries as for gs_launch_xform; the parts named in x.flags (SH coefficients, band 0, the opacity
+// logit) are graded in place.
+struct gs_grade;
+void gs_launch_grade(const GsScene& s, uint32_t n, const uint32_t* ids, uint32_t m, const gs_grade& x, hipStream_t st);
 // k_pick.hip: gs_pick, one wave per query over the last frame's lists (queries: {x, y} pairs; results: 12 words per query;
 // contrib: max_contrib {id, weight} pairs per query, or null)
 void gs_launch_pick(const GsLists& L, const void* d_queries, uint32_t n, void* d_results, uint32_t max_contrib, void* d_contrib, hipStream_t st);

@@ -58,6 +58,9 @@ GS_SELECT_TINT_DEFAULT = 0x80FFFF00
 # splat transforms
 GS_XFORM_POSITION, GS_XFORM_ORIENT, GS_XFORM_SIZE = 0x1, 0x2, 0x4
 
+# colour grades
+GS_GRADE_MATRIX, GS_GRADE_OFFSET, GS_GRADE_OPACITY = 0x1, 0x2, 0x4
+
 # splat attributes (gs_attr.kind)
 (GS_ATTR_POS_X, GS_ATTR_POS_Y, GS_ATTR_POS_Z, GS_ATTR_OPACITY_LOGIT, GS_ATTR_LOG_SCALE_MIN, GS_ATTR_LOG_SCALE_MAX, GS_ATTR_LOG_SCALE_SUM,
  GS_ATTR_ANISOTROPY, GS_ATTR_DC_R, GS_ATTR_DC_G, GS_ATTR_DC_B, GS_ATTR_DIST2, GS_ATTR_PLANE, GS_ATTR_COVER_HITS, GS_ATTR_COVER_MAX_WEIGHT,
@@ -81,7 +84,7 @@ ABI_SYMBOLS = ("gs_last_error", "gs_abi_version", "gs_create", "gs_destroy", "gs
                "gs_render", "gs_render_debug", "gs_render_to", "gs_wait", "gs_render_host", "gs_wait_ticket", "gs_host_alloc", "gs_host_free", "gs_read_rgba8", "gs_read_buffer", "gs_device_ptr",
                "gs_get_stats", "gs_pick", "gs_state_region", "gs_state_ids", "gs_state_count", "gs_state_write",
                "gs_state_list", "gs_export_splats", "gs_export_splats_device", "gs_compact", "gs_ply_save", "gs_export_ply",
-               "gs_xform_compose", "gs_transform_splats",
+               "gs_xform_compose", "gs_transform_splats", "gs_grade_compose", "gs_grade_splats",
                "gs_coverage_accumulate", "gs_coverage_reset", "gs_coverage_read", "gs_state_coverage",
                "gs_attr_summary", "gs_attr_histogram", "gs_attr_read", "gs_state_attr",
                "gs_neigh_count", "gs_neigh_read", "gs_state_neigh",
@@ -131,6 +134,11 @@ class GsRegion(ctypes.Structure):
 class GsXform(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("m", ctypes.c_float * 12), ("q", ctypes.c_float * 4),
                 ("log_scale", ctypes.c_float), ("sh1", ctypes.c_float * 9), ("sh2", ctypes.c_float * 25), ("sh3", ctypes.c_float * 49)]
+
+
+class GsGrade(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("a", ctypes.c_float * 9), ("dc", ctypes.c_float * 3),
+                ("opacity_logit", ctypes.c_float), ("reserved", ctypes.c_float)]
 
 
 class GsCoverageRec(ctypes.Structure):
@@ -233,6 +241,9 @@ def load():
     L.gs_xform_compose.argtypes = [ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.c_float,
                                    ctypes.POINTER(ctypes.c_float), ctypes.POINTER(GsXform)]
     L.gs_transform_splats.argtypes = [vp, u32, u32, ctypes.POINTER(GsXform), ctypes.POINTER(u64)]
+    L.gs_grade_compose.argtypes = [ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.c_float, ctypes.c_float,
+                                   ctypes.c_float, ctypes.c_float, ctypes.POINTER(GsGrade)]
+    L.gs_grade_splats.argtypes = [vp, u32, u32, ctypes.POINTER(GsGrade), ctypes.POINTER(u64)]
     L.gs_coverage_accumulate.argtypes = [vp, ctypes.POINTER(GsCoverRegion), ctypes.POINTER(u64)]
     L.gs_coverage_reset.argtypes = [vp]
     L.gs_coverage_read.argtypes = [vp, vp, u64, ctypes.POINTER(u64)]
@@ -312,3 +323,15 @@ def compose_xform(rot=(1, 0, 0, 0), translate=(0, 0, 0), scale=1.0, pivot=None):
     check(load().gs_xform_compose(f4(*[float(v) for v in rot]), f3(*[float(v) for v in translate]), float(scale),
                                   None if pivot is None else f3(*[float(v) for v in pivot]), ctypes.byref(x)))
     return x
+
+
+def compose_grade(gain=None, offset=None, saturation=1.0, black=0.0, white=1.0, opacity_gain=1.0):
+    """gs_grade_compose: the GsGrade of C' = diag(gain) Sat(saturation) ((C - black) / (white - black)) + offset on the displayed
+    colour, and of the opacity's odds multiplied by opacity_gain.  Host mathematics in double, no GPU: the 3x3 matrix over the SH
+    coefficients, the band-0 offset and log(opacity_gain).  gain, offset: three numbers or None ((1, 1, 1) / (0, 0, 0))."""
+    f3 = ctypes.c_float * 3
+    g = GsGrade()
+    check(load().gs_grade_compose(None if gain is None else f3(*[float(v) for v in gain]),
+                                  None if offset is None else f3(*[float(v) for v in offset]), float(saturation), float(black),
+                                  float(white), float(opacity_gain), ctypes.byref(g)))
+    return g

@@ -432,6 +432,68 @@ int32_t gs_xform_compose(const float rot_rxyz[4], const float translate[3], floa
  * no-op that still reports *matched. */
 int32_t gs_transform_splats(gs_ctx* ctx, uint32_t mask, uint32_t value, const gs_xform* x, uint64_t* matched);
 
+/* ---- colour grades: recolour and fade resident splats in place ------------------------------------
+ * The transforms move splats; a grade changes what they look like: brighten, tint, desaturate, set black and white points, fade --
+ * on the resident splats that pass a state filter, in ONE streaming pass over their SH records (and the opacity logit), instead of
+ * gs_export_splats (320 B per splat), a host edit of 48 coefficients per splat and a re-upload that drops the frame, the shadows,
+ * a captured graph and the coverage / neighbour / cluster planes.  The reference has no counterpart (a viewer); the convention is
+ * its compute_color_from_sh (process_gaussians.wgsl:221-280): C = max(0, SH_C0 sh_0 + sum_k b_k(d) sh_k + 0.5) per channel.
+ * An affine map of the displayed colour, C' = A C + o (A 3x3 over (r,g,b)), holds in EVERY view direction when it is applied to the
+ * coefficients:  sh_k' = A sh_k for k >= 1,  sh_0' = A sh_0 + (A h + o - h) / SH_C0,  h = (1/2, 1/2, 1/2) -- exact in real
+ * arithmetic wherever the final clamp is inactive before and after.  Non-affine grades (gamma, curves) are out of scope; so is a
+ * multiplicative opacity (it needs a sigmoid and its inverse): the opacity term is ADDED to the logit, which multiplies the ODDS
+ * op / (1 - op) -- about the opacity itself where it is small.
+ * Two layers, as for the transforms.  gs_grade_splats applies exactly the f32 numbers of a gs_grade (one f32 rounding per written
+ * operation, no contraction, left to right); gs_grade_compose is plain host code in double, no ctx, no GPU, no transcendental on
+ * the device.  A host may also fill the struct itself.
+ * Per matching splat; only the parts named in `flags` are read or written, the others keep their bit patterns (NaN payloads
+ * included); positions, log-scales, rot and the state byte are never written:
+ *   MATRIX   for k = 0 .. 15, (r, g, b) = record floats 16 + 4k + 0..2:  out_c = (a[3c] r + a[3c+1] g) + a[3c+2] b,  c = 0, 1, 2,
+ *            every output from the OLD triple
+ *   OFFSET   band 0, channel c: v_c + dc[c], v = MATRIX's output when that flag is set, the stored value otherwise
+ *   OPACITY  logit' = logit + opacity_logit   (record float 12)
+ * Traffic per matched splat: MATRIX 192 B read, 192 B written; OFFSET 12 B each way when MATRIX is not set (nothing more when it
+ * is); OPACITY 4 B each way; plus the selection's cost when a filter other than (0, 0) is given, as stated for the transforms.
+ * No resident plane is derived from the SH or the opacity at upload (the largest log-scale is the only derived plane): a graded
+ * ctx and one freshly uploaded with the graded records agree in every plane.
+ * Filter, refusals and ordering are those of gs_transform_splats: (mask, value) as gs_state_count, above 0xFF refused, (0, 0)
+ * matches every splat and is accepted on a ctx without GS_FLAG_SPLAT_STATE, any other filter on such a ctx is refused.  The call
+ * first completes all frames enqueued on the ctx's ring, runs on the ctx's stream and returns when done.  It is NOT a frame and
+ * NOT an upload: taps, statistics, gs_pick, the shadows, the capacities, a captured frame graph and the coverage, neighbour and
+ * cluster planes stay; the NEXT frame shows the grade.  A ctx that borrows its scene (gs_share_splats) is refused: grade the
+ * owner.  GS_ERR_NO_SCENE before any upload; N == 0: *matched = 0, GS_OK.
+ * The inverse grade is NOT a bit-exact undo.  The transforms' one exception to "bit for bit" holds here too: a NaN that an
+ * operation above produces or propagates is compared as "NaN on both sides"; floats of parts not flagged and of splats that do not
+ * match are never computed. */
+#define GS_GRADE_MATRIX  0x1u   /* all 16 coefficient triples through a (192 B read, 192 B written per matched splat) */
+#define GS_GRADE_OFFSET  0x2u   /* dc added to band 0 (12 B each way when MATRIX is not set) */
+#define GS_GRADE_OPACITY 0x4u   /* opacity_logit added to the logit (4 B each way) */
+typedef struct gs_grade {       /* 64 bytes */
+    uint32_t struct_size, flags; /* = sizeof(gs_grade), GS_GRADE_* */
+    float a[9];                 /* row-major 3x3 over (r,g,b) */
+    float dc[3];                /* added to SH coefficient 0 */
+    float opacity_logit;        /* added to the opacity logit */
+    float reserved;             /* 0 */
+} gs_grade;
+/* Fills *out for C' = diag(gain) Sat(saturation) ((C - black) / (white - black)) + offset, Sat(t) = t I + (1 - t) 1 w^T with the
+ * Rec. 709 luma weights w = (0.2126, 0.7152, 0.0722), and for the opacity's odds multiplied by opacity_gain.  gain NULL = (1,1,1),
+ * offset NULL = (0,0,0).  In double, with s = 1 / ((double)white - (double)black) and SH_C0 = 0.28209479177387814, every output
+ * rounded ONCE to f32:
+ *   A[c][j] = (gain[c] * (saturation * delta_cj + (1 - saturation) * w[j])) * s          -> a[3c + j]
+ *   o_c     = offset[c] - (gain[c] * black) * s
+ *   dc[c]   = ((((A[c][0] + A[c][1]) + A[c][2]) * 0.5 + o_c) - 0.5) / SH_C0              (the double A)
+ *   opacity_logit = (float)log((double)opacity_gain)
+ * flags = MATRIX unless the rounded a is exactly the identity, OFFSET unless all three rounded dc are 0, OPACITY unless
+ * opacity_gain == 1: the defaults (NULL, NULL, 1, 0, 1, 1) give flags == 0.  A null out, a non-finite input, white == black (or a
+ * non-finite s), opacity_gain <= 0, an output that is not finite in f32: GS_ERR_INVALID_ARGUMENT and a message naming the
+ * argument; nothing is written. */
+int32_t gs_grade_compose(const float gain[3], const float offset[3], float saturation, float black, float white,
+                         float opacity_gain, gs_grade* out);
+/* Applies *g to every resident splat with (s & mask) == value; *matched (may be NULL) receives their number.  A wrong struct_size,
+ * unknown flag bits, reserved != 0 or a non-finite member of a flagged part: GS_ERR_INVALID_ARGUMENT, nothing is applied.
+ * flags == 0 is a valid no-op that still reports *matched. */
+int32_t gs_grade_splats(gs_ctx* ctx, uint32_t mask, uint32_t value, const gs_grade* g, uint64_t* matched);
+
 /* ---- coverage: per-splat contribution of the LAST frame, select by what is seen ---------------------
  * gs_state_region selects THROUGH surfaces and gs_pick answers for one pixel at a time; neither can say which splats the user
  * actually SEES in a region, nor that a splat contributes to no pixel of any of a set of views (floaters, buried interior
