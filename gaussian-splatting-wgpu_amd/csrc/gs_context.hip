@@ -207,36 +207,63 @@ static int32_t alloc_per_gaussian(gs_ctx* c, uint64_t n, uint64_t min_capacity =
     return alloc_kv(c, cap, rows);
 }
 
-// Drops the previous scene, allocates the per-gaussian work arrays and the resident scene arrays for n gaussians.
-int32_t scene_alloc(gs_ctx* c, uint64_t n, uint64_t min_capacity, uint64_t min_rows) {
-    int32_t rc = alloc_per_gaussian(c, n, min_capacity, min_rows);
-    if (rc != GS_OK) return rc;
+// Where the planes of a scene of n gaussians lie behind `base` (gs_runtime.h): the one copy of this arithmetic.
+GsSceneLayout scene_layout(void* base, uint64_t n, bool state) {
+    GsSceneLayout L;
     const size_t np = ((size_t)n + 63) & ~(size_t)63; // plane stride keeps every plane and both record arrays 256-byte aligned
     // (GS_FLAG_SPLAT_STATE: the state plane follows the SH records, on the next 256-byte boundary; np bytes, so that whole words
     // and 16-byte groups of it are the context's own)
     const size_t sh_end = np * 4 * 4 + np * 32 + (size_t)n * 192, state_at = (sh_end + 255) & ~(size_t)255;
-    const size_t bytes = has_state(c) ? state_at + np : sh_end;
-    HIP_TRY(hipMalloc(c->scene_own.out(), std::max<size_t>(bytes, 256)));
-    c->scene_mem = c->scene_own;
-    c->scene_bytes = bytes;
-    char* p = (char*)c->scene_mem;
-    GsScene& s = c->scene;
+    L.np = np;
+    L.state_at = state_at;
+    L.bytes = state ? state_at + np : sh_end;
+    char* p = (char*)base;
+    GsScene& s = L.scene;
     s.px = (float*)p; p += np * 4; s.py = (float*)p; p += np * 4; s.pz = (float*)p; p += np * 4;
     s.smax = (float*)p; p += np * 4;
     s.geo = (float4*)p; p += np * 32;
     s.sh = (float4*)p;
-    s.state = nullptr;
-    if (has_state(c)) { // zeroed by every upload
-        s.state = (const uint8_t*)c->scene_mem + state_at;
-        HIP_TRY(hipMemsetAsync((char*)c->scene_mem + state_at, 0, std::max<size_t>(np, 4), c->stream));
+    s.state = state ? (const uint8_t*)base + state_at : nullptr;
+    return L;
+}
+// c->scene_own holds a scene of n gaussians: the views into it.
+static void scene_views(gs_ctx* c, uint64_t n) {
+    const GsSceneLayout L = scene_layout(c->scene_own.get(), n, has_state(c));
+    c->scene_mem = c->scene_own;
+    c->scene_bytes = L.bytes;
+    c->scene = L.scene;
+}
+
+// Drops the previous scene, allocates the per-gaussian work arrays and the resident scene arrays for n gaussians.
+int32_t scene_alloc(gs_ctx* c, uint64_t n, uint64_t min_capacity, uint64_t min_rows) {
+    int32_t rc = alloc_per_gaussian(c, n, min_capacity, min_rows);
+    if (rc != GS_OK) return rc;
+    const GsSceneLayout L = scene_layout(nullptr, n, has_state(c));
+    HIP_TRY(hipMalloc(c->scene_own.out(), std::max<size_t>(L.bytes, 256)));
+    scene_views(c, n);
+    if (has_state(c)) // zeroed by every upload
+        HIP_TRY(hipMemsetAsync((char*)c->scene_mem + L.state_at, 0, std::max<size_t>(L.np, 4), c->stream));
+    return GS_OK;
+}
+
+// Drops the previous scene, allocates the per-gaussian work arrays for n gaussians and takes `mem`, a complete scene of n gaussians
+// laid out by scene_layout, as the resident one (gs_insert.hip).  On an error the context holds no scene, as after an upload that failed.
+int32_t scene_install(gs_ctx* c, DevBuf<>&& mem, uint64_t n, uint64_t min_capacity, uint64_t min_rows) {
+    const int32_t rc = alloc_per_gaussian(c, n, min_capacity, min_rows);
+    if (rc != GS_OK) {
+        c->scene = GsScene{};
+        c->n = c->frame.n = 0;
+        return rc;
     }
+    c->scene_own = std::move(mem);
+    scene_views(c, n);
     return GS_OK;
 }
 
 static int32_t upload_common(gs_ctx* c, const void* d_aos, uint64_t n) {
     int32_t rc = scene_alloc(c, n);
     if (rc != GS_OK) return rc;
-    if (n) gs_launch_repack(d_aos, (uint32_t)n, c->scene, c->stream);
+    if (n) gs_launch_repack(d_aos, (uint32_t)n, 0, c->scene, c->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
     return GS_OK;

@@ -2,7 +2,7 @@
 #pragma once
 #include "gs_device.h"
 
-void gs_launch_repack(const void* d_aos, uint32_t n, const GsScene& s, hipStream_t st);
+void gs_launch_repack(const void* d_aos, uint32_t n, uint32_t first, const GsScene& s, hipStream_t st); // record r -> splat first + r
 void gs_launch_ply_chunk(const void* d_raw, uint32_t m, uint32_t first, const GsPlyTable& t, const GsScene& s, hipStream_t st);
 struct GsPreprocessLaunch { // the projection's launch as data (its uniforms are the only kernel arguments that change per frame)
     const void* func;
@@ -174,8 +174,13 @@ void gs_launch_select_scatter(const uint8_t* state, uint32_t n, uint32_t mask, u
                               hipStream_t st);
 // records [first, first + m) of the selection (ids null: of the scene) as 320-byte records; out_ids (may be null): their indices
 void gs_launch_unpack(const GsScene& s, uint32_t n, const uint32_t* ids, uint32_t first, uint32_t m, void* d_aos, uint32_t* out_ids, hipStream_t st);
-// new splat g of `d` = splat ids[g] of `o` (every plane, the state byte included when both keep one)
-void gs_launch_compact_planes(const GsScene& o, uint32_t n_old, const uint32_t* ids, uint32_t m, const GsScene& d, hipStream_t st);
+// new splat first + g of `d` = splat ids[g] of `o` (every plane; with_state, which needs first == 0: the state byte too when both keep one)
+void gs_launch_compact_planes(const GsScene& o, uint32_t n_old, const uint32_t* ids, uint32_t m, const GsScene& d, hipStream_t st, uint32_t first = 0,
+                              bool with_state = true);
+// k_insert.hip: the splat insertion's grow pass (gs_insert.hip): splats 0 .. n_old of `o` to the same indices of `d`, a scene laid
+// out for n_new >= n_old splats (every plane moves: the plane stride depends on N), and the WHOLE state plane of `d`, when it keeps
+// one: the old bytes, then new_state for splats n_old .. n_new, then 0 up to the plane stride
+void gs_launch_grow(const GsScene& o, uint32_t n_old, const GsScene& d, uint32_t n_new, uint32_t new_state, uint32_t grid, hipStream_t st);
 // k_xform.hip: gs_transform_splats.  Entry g (0 .. m) is splat ids[g], or splat g when ids is null (then m = n); the parts named in
 // x.flags are transformed in place.
 struct gs_xform;

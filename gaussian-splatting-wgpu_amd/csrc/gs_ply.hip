@@ -15,16 +15,7 @@
 
 struct PlyProp { std::string name; int type; /* 0 other (0 bytes), 1 float, 2 uchar */ uint32_t offset; };
 
-// What decodeHeader (ply.ts:49-102) and PackedGaussians' constructor (:162-228) derive from the header: where the vertex data
-// starts, the vertex count and stride, and for each of the 11 + 3 (degree + 1)^2 values of a packed record its byte offset and
-// type in a vertex and its float slot in the 320-byte record (ply.ts:190-198).
-struct PlyLayout {
-    uint64_t data_off = 0, vertex_count = 0;
-    uint32_t stride = 0;
-    int degree = 0, nsrc = 0;
-    uint32_t soff[11 + 48], stype[11 + 48], slot[11 + 48];
-    bool all_float = true;
-};
+// (PlyLayout, what the header says about a vertex, is in gs_runtime.h: the splat insertion streams a file too.)
 
 // header: the first bytes of the file (at least up to and including "end_header\n")
 static int32_t ply_parse_header(const unsigned char* buf, size_t len, PlyLayout& L) {
@@ -167,28 +158,34 @@ GS_EXPORT void gs_ply_free(void* records) { free(records); }
 // two pinned staging buffers, copied to the device and converted THERE into the final layout (position planes, geometry and SH
 // records: gs_ply_chunk_kernel) while the next chunk is being read.  No N x 320-byte array exists on either side: peak host
 // memory is the two staging buffers (2 x 64 Ki x vertex stride, ~32 MB), whatever the size of the scene.  The reference builds
-// the whole packed buffer in JS first (ply.ts:204-228: "seconds to a couple of minutes", index.html:16).
-GS_EXPORT int32_t gs_upload_ply(gs_ctx* c, const char* path, uint64_t* n_out) {
-    if (!c || !path) return fail(GS_ERR_INVALID_ARGUMENT, "gs_upload_ply: null argument");
-    File fp(fopen(path, "rb"));
-    if (!fp) return fail(GS_ERR_INVALID_ARGUMENT, "gs_upload_ply: cannot open %s", path);
+// the whole packed buffer in JS first (ply.ts:204-228: "seconds to a couple of minutes", index.html:16).  Two callers share the two
+// halves below: gs_upload_ply streams into a new scene, gs_append_ply (gs_insert.hip) into the tail of a grown one.
+//
+// Opens the file, reads its header and refuses what cannot be streamed: a count of 2^31 or more, a file shorter than its header says.
+int32_t ply_open(const char* who, const char* path, PlySource* src) {
+    src->fp = File(fopen(path, "rb"));
+    if (!src->fp) return fail(GS_ERR_INVALID_ARGUMENT, "%s: cannot open %s", who, path);
     std::vector<unsigned char> head(1 << 16);
-    const size_t got = fread(head.data(), 1, head.size(), fp);
-    PlyLayout L;
+    const size_t got = fread(head.data(), 1, head.size(), src->fp);
+    PlyLayout& L = src->L;
     int32_t rc = ply_parse_header(head.data(), got, L);
     if (rc != GS_OK) return rc;
-    fseek(fp, 0, SEEK_END);
-    const uint64_t fsize = (uint64_t)ftell(fp);
+    fseek(src->fp, 0, SEEK_END);
+    const uint64_t fsize = (uint64_t)ftell(src->fp);
     const uint64_t n = L.vertex_count;
-    if (n >= (1ull << 31)) return fail(GS_ERR_INVALID_ARGUMENT, "gs_upload_ply: too many gaussians");
-    if (fsize < L.data_off + n * (uint64_t)L.stride) return fail(GS_ERR_INVALID_ARGUMENT, "gs_upload_ply: vertex data truncated");
-    hipError_t he = hipSetDevice(c->cfg.device);
-    if (he != hipSuccess) return fail(GS_ERR_HIP, "hipSetDevice: %s", hipGetErrorString(he));
-    drop_shadows(c);
-    rc = scene_alloc(c, n);
-    if (rc != GS_OK) return rc;
+    if (n >= (1ull << 31)) return fail(GS_ERR_INVALID_ARGUMENT, "%s: too many gaussians", who);
+    if (fsize < L.data_off + n * (uint64_t)L.stride) return fail(GS_ERR_INVALID_ARGUMENT, "%s: vertex data truncated", who);
+    return GS_OK;
+}
+
+// The two-buffer stream: vertex v of the file becomes splat first + v of `dst` (a scene that has room for them), converted on the
+// device while the next chunk is being read.  Returns when the stream is done.
+int32_t ply_stream(const char* who, gs_ctx* c, PlySource& src, const GsScene& dst, uint64_t first) {
+    const PlyLayout& L = src.L;
+    FILE* const fp = src.fp;
+    const uint64_t n = L.vertex_count;
     if (L.degree < 3 && n) { // coefficients the file does not have stay 0 (the shader hard-codes 16: process_gaussians.wgsl:6)
-        hipError_t e0 = hipMemsetAsync((void*)c->scene.sh, 0, (size_t)n * 192, c->stream);
+        hipError_t e0 = hipMemsetAsync((char*)dst.sh + (size_t)first * 192, 0, (size_t)n * 192, c->stream);
         if (e0 != hipSuccess) return fail(GS_ERR_HIP, "hipMemsetAsync: %s", hipGetErrorString(e0));
     }
     const uint64_t CH = 65536;
@@ -204,20 +201,36 @@ GS_EXPORT int32_t gs_upload_ply(gs_ctx* c, const char* path, uint64_t* n_out) {
     GsPlyTable tab;
     tab.stride = L.stride; tab.nsrc = (uint32_t)L.nsrc; tab.all_float = L.all_float ? 1u : 0u;
     for (int k = 0; k < L.nsrc; ++k) { tab.soff[k] = (uint16_t)L.soff[k]; tab.stype[k] = (uint8_t)L.stype[k]; tab.slot[k] = (uint8_t)L.slot[k]; }
-    if (L.stride > 0xFFFFu) return fail(GS_ERR_INVALID_ARGUMENT, "gs_upload_ply: vertex stride %u too large", L.stride);
+    if (L.stride > 0xFFFFu) return fail(GS_ERR_INVALID_ARGUMENT, "%s: vertex stride %u too large", who, L.stride);
     fseek(fp, (long)L.data_off, SEEK_SET);
     uint32_t it = 0;
     for (uint64_t v0 = 0; v0 < n; v0 += CH, ++it) {
         const int k = (int)(it & 1u);
         const uint64_t m = std::min<uint64_t>(CH, n - v0);
         if (it >= 2) HIP_TRY(hipEventSynchronize(done[k])); // the copy out of this staging buffer two chunks ago has finished
-        if (fread(h_stage[k], 1, (size_t)(m * L.stride), fp) != (size_t)(m * L.stride)) return fail(GS_ERR_INVALID_ARGUMENT, "gs_upload_ply: short read");
+        if (fread(h_stage[k], 1, (size_t)(m * L.stride), fp) != (size_t)(m * L.stride)) return fail(GS_ERR_INVALID_ARGUMENT, "%s: short read", who);
         HIP_TRY(hipMemcpyAsync(d_stage[k], h_stage[k], (size_t)(m * L.stride), hipMemcpyHostToDevice, c->stream));
-        gs_launch_ply_chunk(d_stage[k], (uint32_t)m, (uint32_t)v0, tab, c->scene, c->stream);
+        gs_launch_ply_chunk(d_stage[k], (uint32_t)m, (uint32_t)(first + v0), tab, dst, c->stream);
         HIP_TRY(hipEventRecord(done[k], c->stream));
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
+    return GS_OK;
+}
+
+GS_EXPORT int32_t gs_upload_ply(gs_ctx* c, const char* path, uint64_t* n_out) {
+    if (!c || !path) return fail(GS_ERR_INVALID_ARGUMENT, "gs_upload_ply: null argument");
+    PlySource src;
+    int32_t rc = ply_open("gs_upload_ply", path, &src);
+    if (rc != GS_OK) return rc;
+    const uint64_t n = src.L.vertex_count;
+    hipError_t he = hipSetDevice(c->cfg.device);
+    if (he != hipSuccess) return fail(GS_ERR_HIP, "hipSetDevice: %s", hipGetErrorString(he));
+    drop_shadows(c);
+    rc = scene_alloc(c, n);
+    if (rc != GS_OK) return rc;
+    rc = ply_stream("gs_upload_ply", c, src, c->scene, 0);
+    if (rc != GS_OK) return rc;
     if (n_out) *n_out = n;
     return GS_OK;
 }

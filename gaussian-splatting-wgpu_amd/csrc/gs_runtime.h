@@ -1,12 +1,13 @@
-// gs_runtime.h -- private to the runtime sources (gs_context / gs_frame / gs_readback / gs_state / gs_export / gs_xform / gs_coverage / gs_attr / gs_neigh / gs_cluster / gs_ply / gs_stages .hip):
+// gs_runtime.h -- private to the runtime sources (gs_context / gs_frame / gs_readback / gs_state / gs_export / gs_insert / gs_xform / gs_coverage / gs_attr / gs_neigh / gs_cluster / gs_ply / gs_stages .hip):
 //   the error channel (fail, HIP_TRY);
 //   the owners of HIP resources (Owned: DevBuf, PinnedBuf, Event, Stream, File) and Scratch, a device buffer that grows on demand;
 //   the context (gs_ctx, GsOptions, FrameNotes, GraphKey), the lists of its last frame (frame_lists) and sums over its ring (over_ring);
 //   what the calls on the resident splats share: the prologue of a call that drains the ring (Plane, resident_check,
 //   resident_drain, resident_begin), the last frame waited for (last_frame), the staging of a canvas mask (stage_mask), the
 //   coverage planes (cover_planes), the neighbour count plane (neigh_plane), the cell grid a count and a labelling build
-//   (neigh_build, neigh_budget, neigh_slices), the cluster planes (cluster_planes), the splat edits' selection (edit_select) and
-//   the check of a gs_attr (attr_check).
+//   (neigh_build, neigh_budget, neigh_slices), the cluster planes (cluster_planes), the splat edits' selection (edit_select), the
+//   check of a gs_attr (attr_check), the layout of a scene allocation (scene_layout, scene_install) and a .ply being streamed
+//   (PlySource, ply_open, ply_stream).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -236,6 +237,17 @@ struct gs_ctx {
 // gs_context.hip
 int32_t alloc_kv(gs_ctx* c, uint64_t capacity, uint64_t row_cap); // the caller has drained the stream
 int32_t scene_alloc(gs_ctx* c, uint64_t n, uint64_t min_capacity = 0, uint64_t min_rows = 0); // min_*: capacities a compaction keeps
+// The layout of a scene allocation as a function of (n, state plane or not): the views of a scene of n gaussians that starts at
+// `base` (null: only np, state_at and bytes mean anything), the plane stride in gaussians, the offset of the state plane and the
+// bytes of the whole.  scene_alloc and the splat insertion (which builds the new scene beside the old one) share this one copy.
+struct GsSceneLayout {
+    GsScene scene{};
+    size_t np = 0, state_at = 0, bytes = 0;
+};
+GsSceneLayout scene_layout(void* base, uint64_t n, bool state);
+// scene_alloc with the scene given: drops the previous scene and the per-gaussian work arrays, allocates those for n gaussians
+// and takes `mem` (complete, laid out by scene_layout) as the resident scene
+int32_t scene_install(gs_ctx* c, DevBuf<>&& mem, uint64_t n, uint64_t min_capacity, uint64_t min_rows);
 void drop_shadows(gs_ctx* c);
 // gs_frame.hip
 void drop_graph(gs_ctx* c);
@@ -312,6 +324,23 @@ int32_t cluster_planes(gs_ctx* c, hipStream_t st);
 // gs_export.hip: the splat edits' selection: counts the splats with (s & mask) == value and, with want_ids, leaves their indices,
 // ascending, in c->ex.ids
 int32_t edit_select(gs_ctx* c, uint32_t mask, uint32_t value, bool want_ids, uint64_t* total);
+// gs_ply.hip: what decodeHeader (ply.ts:49-102) and PackedGaussians' constructor (:162-228) derive from the header: where the vertex
+// data starts, the vertex count and stride, and for each of the 11 + 3 (degree + 1)^2 values of a packed record its byte offset and
+// type in a vertex and its float slot in the 320-byte record (ply.ts:190-198).
+struct PlyLayout {
+    uint64_t data_off = 0, vertex_count = 0;
+    uint32_t stride = 0;
+    int degree = 0, nsrc = 0;
+    uint32_t soff[11 + 48], stype[11 + 48], slot[11 + 48];
+    bool all_float = true;
+};
+// A file being streamed (gs_upload_ply, gs_append_ply).  ply_open: opens it, reads the header, refuses 2^31 vertices or more and
+// a file shorter than data_off + count * stride; allocates nothing on the device.  ply_stream: vertex v becomes splat first + v of
+// `dst` (the SH of those splats zeroed first when the file's degree is below 3), through two pinned and two device staging buffers
+// of 64 Ki vertices; returns when the stream is done.  `who` names the caller in the messages.
+struct PlySource { File fp; PlyLayout L; };
+int32_t ply_open(const char* who, const char* path, PlySource* src);
+int32_t ply_stream(const char* who, gs_ctx* c, PlySource& src, const GsScene& dst, uint64_t first);
 // gs_attr.hip: the refusals of a gs_attr (null, struct_size, kind, a non-finite p of the kinds that read it) in `who`'s name; *dev:
 // its parameters as the kernels take them.  attr_needs_cover: the kind reads the coverage planes (cover_planes first)
 int32_t attr_check(const char* who, const gs_attr* a, GsAttrDev* dev);

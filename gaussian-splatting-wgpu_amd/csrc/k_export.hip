@@ -121,12 +121,14 @@ void gs_launch_unpack(const GsScene& s, uint32_t n, const uint32_t* ids, uint32_
                        (const float*)s.sh, n, ids, first, m, (float4*)d_aos, out_ids);
 }
 
-// ---- old scene -> new scene: new splat g is old splat ids[g] -------------------------------------------------------------------
+// ---- old scene -> new scene: new splat first + g is old splat ids[g] -----------------------------------------------------------
 // One thread per (new splat, column), 16 columns: 0 the four plane floats, 1-2 geometry, 3-14 SH, 15 the state byte.  The state
 // plane is written one whole word by the column-15 thread of every fourth splat (its own byte and its three neighbours', 0 past
-// the new N), so no byte store races with a neighbour's.
-__global__ __launch_bounds__(256) void gs_compact_planes_kernel(GsScene o, uint32_t n_old, const uint32_t* __restrict__ ids, uint32_t m, float* px,
-                                                                 float* py, float* pz, float* smax, float4* geo, float4* sh, uint32_t* state_words) {
+// the new N), so no byte store races with a neighbour's.  A compaction passes first = 0; a duplication (gs_insert.hip) the old N
+// and no state words: the words of its plane do not start at a gathered splat, the grow pass has written them.
+__global__ __launch_bounds__(256) void gs_compact_planes_kernel(GsScene o, uint32_t n_old, const uint32_t* __restrict__ ids, uint32_t m, uint32_t first,
+                                                                 float* px, float* py, float* pz, float* smax, float4* geo, float4* sh,
+                                                                 uint32_t* state_words) {
     const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (t >= (uint64_t)m * 16) return;
     const uint32_t g = (uint32_t)(t >> 4), c = (uint32_t)(t & 15u);
@@ -142,14 +144,16 @@ __global__ __launch_bounds__(256) void gs_compact_planes_kernel(GsScene o, uint3
     }
     const uint32_t id = ids[g];
     if (id >= n_old) return; // (never: ids come from the selection over the old scene)
-    if (c == 0u) { px[g] = o.px[id]; py[g] = o.py[id]; pz[g] = o.pz[id]; smax[g] = o.smax[id]; }
-    else if (c < 3u) geo[(uint64_t)g * 2 + (c - 1u)] = o.geo[(uint64_t)id * 2 + (c - 1u)];
-    else sh[(uint64_t)g * 12 + (c - 3u)] = o.sh[(uint64_t)id * 12 + (c - 3u)];
+    const uint64_t d = (uint64_t)first + g;
+    if (c == 0u) { px[d] = o.px[id]; py[d] = o.py[id]; pz[d] = o.pz[id]; smax[d] = o.smax[id]; }
+    else if (c < 3u) geo[d * 2 + (c - 1u)] = o.geo[(uint64_t)id * 2 + (c - 1u)];
+    else sh[d * 12 + (c - 3u)] = o.sh[(uint64_t)id * 12 + (c - 3u)];
 }
-void gs_launch_compact_planes(const GsScene& o, uint32_t n_old, const uint32_t* ids, uint32_t m, const GsScene& d, hipStream_t st) {
+void gs_launch_compact_planes(const GsScene& o, uint32_t n_old, const uint32_t* ids, uint32_t m, const GsScene& d, hipStream_t st, uint32_t first,
+                              bool with_state) {
     const uint64_t total = (uint64_t)m * 16;
     if (!total) return;
-    hipLaunchKernelGGL(gs_compact_planes_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, st, o, n_old, ids, m, (float*)d.px, (float*)d.py,
-                       (float*)d.pz, (float*)d.smax, (float4*)d.geo, (float4*)d.sh,
-                       reinterpret_cast<uint32_t*>(const_cast<uint8_t*>(d.state)));
+    hipLaunchKernelGGL(gs_compact_planes_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, st, o, n_old, ids, m, first, (float*)d.px,
+                       (float*)d.py, (float*)d.pz, (float*)d.smax, (float4*)d.geo, (float4*)d.sh,
+                       with_state ? reinterpret_cast<uint32_t*>(const_cast<uint8_t*>(d.state)) : nullptr);
 }

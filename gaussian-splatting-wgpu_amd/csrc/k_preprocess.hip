@@ -25,13 +25,14 @@
 #include "gs_tight.h"
 
 // ---- upload: 320-byte AoS (ply.ts:190-198) -> position planes + geometry / SH records ---------------
-// One thread per (gaussian, 16-byte column of the source record); runs once per scene.
-__global__ __launch_bounds__(256) void gs_repack_kernel(const float4* __restrict__ aos, uint32_t n, float* px, float* py,
+// One thread per (gaussian, 16-byte column of the source record); runs once per scene.  Record r becomes splat first + r: an upload
+// passes 0, an insertion (gs_insert.hip) the number of splats that are resident already.
+__global__ __launch_bounds__(256) void gs_repack_kernel(const float4* __restrict__ aos, uint32_t n, uint32_t first, float* px, float* py,
                                                          float* pz, float* smax, float* geo, float* sh) {
     const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     const uint64_t total = (uint64_t)n * 20; // 20 float4 per source record
     if (t >= total) return;
-    const uint32_t g = (uint32_t)(t / 20), c = (uint32_t)(t % 20);
+    const uint32_t g = first + (uint32_t)(t / 20), c = (uint32_t)(t % 20);
     const float4 v = aos[t];
     float* r = geo + (uint64_t)g * 8;
     if (c == 0) { px[g] = v.x; py[g] = v.y; pz[g] = v.z; }
@@ -647,11 +648,11 @@ __global__ __launch_bounds__(256, PRE_WAVES) void gs_preprocess_kernel(GsScene s
 }
 
 // ---- host launchers --------------------------------------------------------------------------------
-void gs_launch_repack(const void* d_aos, uint32_t n, const GsScene& s, hipStream_t st) {
+void gs_launch_repack(const void* d_aos, uint32_t n, uint32_t first, const GsScene& s, hipStream_t st) {
     const uint64_t total = (uint64_t)n * 20;
     const uint32_t blocks = (uint32_t)((total + 255) / 256);
     if (!blocks) return;
-    hipLaunchKernelGGL(gs_repack_kernel, dim3(blocks), dim3(256), 0, st, (const float4*)d_aos, n, (float*)s.px, (float*)s.py,
+    hipLaunchKernelGGL(gs_repack_kernel, dim3(blocks), dim3(256), 0, st, (const float4*)d_aos, n, first, (float*)s.px, (float*)s.py,
                        (float*)s.pz, (float*)s.smax, (float*)s.geo, (float*)s.sh);
 }
 // The projection's launch as data: the one kernel of a frame whose arguments change from frame to frame (the uniforms, by

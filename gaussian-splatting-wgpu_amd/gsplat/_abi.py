@@ -84,6 +84,7 @@ ABI_SYMBOLS = ("gs_last_error", "gs_abi_version", "gs_create", "gs_destroy", "gs
                "gs_render", "gs_render_debug", "gs_render_to", "gs_wait", "gs_render_host", "gs_wait_ticket", "gs_host_alloc", "gs_host_free", "gs_read_rgba8", "gs_read_buffer", "gs_device_ptr",
                "gs_get_stats", "gs_pick", "gs_state_region", "gs_state_ids", "gs_state_count", "gs_state_write",
                "gs_state_list", "gs_export_splats", "gs_export_splats_device", "gs_compact", "gs_ply_save", "gs_export_ply",
+               "gs_append_splats", "gs_append_splats_device", "gs_append_ply", "gs_duplicate_splats",
                "gs_xform_compose", "gs_transform_splats", "gs_grade_compose", "gs_grade_splats",
                "gs_coverage_accumulate", "gs_coverage_reset", "gs_coverage_read", "gs_state_coverage",
                "gs_attr_summary", "gs_attr_histogram", "gs_attr_read", "gs_state_attr",
@@ -238,6 +239,10 @@ def load():
     L.gs_compact.argtypes = [vp, u32, u32, ctypes.POINTER(u64), vp]
     L.gs_ply_save.argtypes = [ctypes.c_char_p, vp, u64, i32]
     L.gs_export_ply.argtypes = [vp, ctypes.c_char_p, u32, u32, i32, ctypes.POINTER(u64)]
+    L.gs_append_splats.argtypes = [vp, vp, u64, u32, ctypes.POINTER(u64)]
+    L.gs_append_splats_device.argtypes = [vp, vp, u64, u32, ctypes.POINTER(u64)]
+    L.gs_append_ply.argtypes = [vp, ctypes.c_char_p, u32, ctypes.POINTER(u64), ctypes.POINTER(u64)]
+    L.gs_duplicate_splats.argtypes = [vp, u32, u32, u32, ctypes.POINTER(u64), ctypes.POINTER(u64), vp]
     L.gs_xform_compose.argtypes = [ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.c_float,
                                    ctypes.POINTER(ctypes.c_float), ctypes.POINTER(GsXform)]
     L.gs_transform_splats.argtypes = [vp, u32, u32, ctypes.POINTER(GsXform), ctypes.POINTER(u64)]

@@ -369,6 +369,55 @@ int32_t gs_ply_save(const char* path, const void* records, uint64_t n, int32_t s
  * mirror image.  Host memory does not grow with N.  *n (may be NULL): records written. */
 int32_t gs_export_ply(gs_ctx* ctx, const char* path, uint32_t mask, uint32_t value, int32_t sh_degree, uint64_t* n);
 
+/* ---- splat insertion: append records, a .ply or a copy of a selection to the resident splats ---------
+ * The edits above select, hide, delete, export and save; these ADD splats to a ctx that already holds some, where gs_upload_*
+ * would replace the whole scene: a second capture merged into the first (then moved and graded to match it: splat transforms,
+ * colour grades), or the editor's "duplicate the selection".  The reference has no counterpart: its host keeps the records it
+ * uploaded (renderer.ts:130-137) and would concatenate and upload them again; a scene streamed in by gs_upload_ply has no such
+ * host copy, and gs_export_splats of everything + a host concatenation + a new upload is what these calls replace.  gs_compact's
+ * mirror image: a new scene of another N is built from the old one on the device.
+ * Where the new splats go: before the call the ctx holds N splats, afterwards N + m.  Old splats keep their indices and every bit
+ * of their records and state bytes.  The new splats take the indices *first = N .. N + m - 1 in the order given: record order for
+ * an append, file order for a .ply, ASCENDING source index for a duplicate (the reference's tie-break order and the splat edits'
+ * rule); ids[j] is the source index of new splat *first + j.
+ * What the ctx equals afterwards: a fresh ctx that was given gs_upload_splats(old records ++ new records) followed by
+ * gs_state_write(old bytes ++ m x new_state) -- every tap and the image, bit for bit.  For gs_append_ply the new records are what
+ * gs_ply_load makes of the file: coefficients above the file's SH degree are +0.0f, a uchar property is value / 255 evaluated in
+ * double, any property order is accepted (the kernel and the two-buffer stream of gs_upload_ply, with a destination offset).
+ * new_state: ONE byte, given to every new splat (GS_SPLAT_SELECTED: the new capture is what the next transform or grade acts on).
+ * Above 0xFF: GS_ERR_INVALID_ARGUMENT.  Non-zero on a ctx without GS_FLAG_SPLAT_STATE: refused as the state calls refuse such a
+ * ctx.  (mask, value) of a duplicate follow the splat edits' filter rules: above 0xFF refused, (0, 0) duplicates every splat and
+ * works without the flag, any other filter needs it.
+ * Like gs_compact in everything else: the call first completes all frames enqueued on the ctx's ring (an error of that wait is
+ * the call's error and nothing is done), runs on the ctx's stream and returns when done; the frames-in-flight shadows are
+ * dropped, a captured frame graph is invalidated, taps, gs_read_rgba8 and gs_pick return GS_ERR_NO_FRAME until the next frame;
+ * statistics windows are untouched; the per-gaussian work arrays are re-sized for N + m while the (key,value) and row capacities
+ * stay at least as large as they were.  The coverage, neighbour-count and cluster planes are dropped and read as their initial
+ * values (0, 0, GS_CLUSTER_NONE): carrying them across an insertion is out of scope, accumulate / count / label again.  A ctx that
+ * borrows its scene (gs_share_splats) is refused with GS_ERR_INVALID_ARGUMENT: insert into the owner; for the owner's borrowers
+ * an insertion counts as a re-upload: the owner must not insert while they render, and they must gs_share_splats again
+ * afterwards.  GS_ERR_NO_SCENE before any upload; a ctx that holds an EMPTY scene (gs_upload_splats(ctx, NULL, 0)) accepts
+ * insertions.  Multi-GPU: the same call on every rank (the result is deterministic).
+ * m == 0 -- an empty append, a .ply of 0 vertices, a filter that matches nothing -- is a no-op: *first = N, *m = 0, GS_OK, nothing
+ * is reallocated, the shadows, a captured graph and the last frame stay (taps and gs_pick keep answering).
+ * Atomic: every refusal -- a null or bad argument, N + m >= 2^31, a file that cannot be opened, a bad header, a file smaller than
+ * data_off + m x stride, a vertex stride above 0xFFFF -- is decided before anything is allocated or freed.  The new scene is
+ * then built BESIDE the old one and installed only when its tail is complete: a HIP error or a short read on the way leaves the
+ * ctx with the old scene, its last frame and its planes exactly as they were.  (Only the re-sizing of the work arrays comes after
+ * the install; should that run out of memory the ctx holds no scene, as after an upload that failed.)  Peak device memory is
+ * therefore 245 B x (2 N + m) for the two scenes, plus the 320 B x m bounce buffer of a host append or the two 64 Ki-vertex
+ * staging buffers of a .ply.  Every call costs O(N): amortised over-allocation for many small appends is out of scope.
+ * *first, *m and ids may be NULL. */
+int32_t gs_append_splats(gs_ctx* ctx, const void* aos320, uint64_t m, uint32_t new_state, uint64_t* first);
+/* Same, DEVICE pointer: no PCIe copy.  The records must be complete before the call (it reads them on the ctx's stream). */
+int32_t gs_append_splats_device(gs_ctx* ctx, const void* d_aos320, uint64_t m, uint32_t new_state, uint64_t* first);
+/* gs_ply_load + gs_append_splats without the host records: the file is streamed into the tail of the new scene. */
+int32_t gs_append_ply(gs_ctx* ctx, const char* path, uint32_t new_state, uint64_t* first, uint64_t* m);
+/* Appends a copy of every splat with (s & mask) == value, in ascending source order; the copies get new_state, not their source's
+ * byte.  ids (HOST, may be NULL, capacity = N before the call): ids[j] = source index of new splat *first + j. */
+int32_t gs_duplicate_splats(gs_ctx* ctx, uint32_t mask, uint32_t value, uint32_t new_state, uint64_t* first, uint64_t* m,
+                            uint32_t* ids /* HOST, may be NULL, capacity N */);
+
 /* ---- splat transforms: move, rotate and scale resident splats in place -----------------------------
  * The verb the edits above lack: a similarity p' = s R (p - pivot) + pivot + t, uniform s > 0, applied to the resident splats that
  * pass a state filter, in ONE streaming pass over the affected planes -- no export / edit / re-upload round trip, no reallocation,
