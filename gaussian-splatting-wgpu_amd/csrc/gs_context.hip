@@ -4,6 +4,7 @@
 // Replaces the setup/teardown of Renderer (reference src/renderer.ts:96-347).  Where the reference allocates six sort buffers
 // and clears three buffers per frame, every buffer here is allocated once (capacity-based) and grown geometrically only when a
 // frame overflows (wait_one, gs_frame.hip).  Every allocation is held by an owner (gs_runtime.h): the context frees itself.
+#include <atomic>
 #include <cmath>
 #include <cstdarg>
 #include <memory>
@@ -235,7 +236,12 @@ static void scene_views(gs_ctx* c, uint64_t n) {
 }
 
 // Drops the previous scene, allocates the per-gaussian work arrays and the resident scene arrays for n gaussians.
+uint64_t scene_new_serial() {
+    static std::atomic<uint64_t> next{1};
+    return next.fetch_add(1, std::memory_order_relaxed);
+}
 int32_t scene_alloc(gs_ctx* c, uint64_t n, uint64_t min_capacity, uint64_t min_rows) {
+    c->scene_serial = scene_new_serial(); // an upload or a compaction: the splats are numbered anew (an insertion installs, and keeps it)
     int32_t rc = alloc_per_gaussian(c, n, min_capacity, min_rows);
     if (rc != GS_OK) return rc;
     const GsSceneLayout L = scene_layout(nullptr, n, has_state(c));
@@ -295,6 +301,7 @@ GS_EXPORT int32_t gs_share_splats(gs_ctx* c, gs_ctx* owner) {
     c->scene_mem = owner->scene_mem; // borrowed, read-only during a frame; the owner must outlive this context
     c->scene_bytes = owner->scene_bytes;
     c->scene = owner->scene;
+    c->scene_serial = scene_new_serial(); // (a borrower takes no snapshots; what it held before is another scene in any case)
     HIP_TRY(hipStreamSynchronize(c->stream));
     return GS_OK;
 }

@@ -51,9 +51,6 @@ GS_EXPORT int32_t gs_state_list(gs_ctx* c, uint32_t mask, uint32_t value, uint32
     return GS_OK;
 }
 
-// records of the selection per trip through the host export's bounce buffer (320 MB)
-static constexpr uint64_t kBounceRecords = 1ull << 20;
-
 static int32_t export_common(gs_ctx* c, const char* who, uint32_t mask, uint32_t value, void* out, uint64_t cap, uint64_t* n, uint32_t* ids_out,
                              bool device) {
     int32_t rc = edit_begin(c, who, mask, value);

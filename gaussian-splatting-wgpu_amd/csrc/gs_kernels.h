@@ -181,6 +181,23 @@ void gs_launch_compact_planes(const GsScene& o, uint32_t n_old, const uint32_t* 
 // out for n_new >= n_old splats (every plane moves: the plane stride depends on N), and the WHOLE state plane of `d`, when it keeps
 // one: the old bytes, then new_state for splats n_old .. n_new, then 0 up to the plane stride
 void gs_launch_grow(const GsScene& o, uint32_t n_old, const GsScene& d, uint32_t n_new, uint32_t new_state, uint32_t grid, hipStream_t st);
+// k_snapshot.hip: snapshots and write-back (gs_snapshot.hip).  A snapshot's device memory as the kernels take it: entry g (0 .. m) is
+// splat ids[g], or splat g when ids is null (a dense snapshot); x, y, z: f32[m] each; geo: float4[m][2]; sh: float4[m][12]; state:
+// u8[m] in whole words.  A part that was not taken has null pointers and is never asked for.
+struct GsSnapshotDev {
+    const uint32_t* ids;
+    float *x, *y, *z;
+    float4 *geo, *sh;
+    uint32_t* state;
+};
+// mode 0: take (scene -> snapshot), 1: restore (snapshot -> scene), 2: swap; parts: GS_PART_*, only their columns are launched
+void gs_launch_snapshot(uint32_t mode, const GsScene& sc, uint32_t n, const GsSnapshotDev& s, uint32_t m, uint32_t parts, hipStream_t st);
+// record g (0 .. m) of d_aos -> the parts named of splat ids[g], or of splat g when ids is null; d_states: one byte per record, read
+// with GS_PART_STATE only.  The caller has checked the ids (gs_launch_ids_ascending, or on the host).
+void gs_launch_write(const void* d_aos, const uint8_t* d_states, uint32_t m, const uint32_t* ids, const GsScene& s, uint32_t n, uint32_t parts,
+                     hipStream_t st);
+// *first_bad (set to all ones by the caller) = the first position g with ids[g] >= n or ids[g] <= ids[g - 1], if there is one
+void gs_launch_ids_ascending(const uint32_t* ids, uint64_t m, uint32_t n, unsigned long long* first_bad, hipStream_t st);
 // k_xform.hip: gs_transform_splats.  Entry g (0 .. m) is splat ids[g], or splat g when ids is null (then m = n); the parts named in
 // x.flags are transformed in place.
 struct gs_xform;

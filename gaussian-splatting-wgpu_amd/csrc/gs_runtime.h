@@ -1,4 +1,4 @@
-// gs_runtime.h -- private to the runtime sources (gs_context / gs_frame / gs_readback / gs_state / gs_export / gs_insert / gs_xform / gs_coverage / gs_attr / gs_neigh / gs_cluster / gs_ply / gs_stages .hip):
+// gs_runtime.h -- private to the runtime sources (gs_context / gs_frame / gs_readback / gs_state / gs_export / gs_insert / gs_snapshot / gs_xform / gs_coverage / gs_attr / gs_neigh / gs_cluster / gs_ply / gs_stages .hip):
 //   the error channel (fail, HIP_TRY);
 //   the owners of HIP resources (Owned: DevBuf, PinnedBuf, Event, Stream, File) and Scratch, a device buffer that grows on demand;
 //   the context (gs_ctx, GsOptions, FrameNotes, GraphKey), the lists of its last frame (frame_lists) and sums over its ring (over_ring);
@@ -6,8 +6,9 @@
 //   resident_drain, resident_begin), the last frame waited for (last_frame), the staging of a canvas mask (stage_mask), the
 //   coverage planes (cover_planes), the neighbour count plane (neigh_plane), the cell grid a count and a labelling build
 //   (neigh_build, neigh_budget, neigh_slices), the cluster planes (cluster_planes), the splat edits' selection (edit_select), the
-//   check of a gs_attr (attr_check), the layout of a scene allocation (scene_layout, scene_install) and a .ply being streamed
-//   (PlySource, ply_open, ply_stream).
+//   check of a gs_attr (attr_check), the layout of a scene allocation (scene_layout, scene_install), the serial that tells one
+//   numbering of the resident splats from the next (gs_ctx::scene_serial, scene_new_serial: what a gs_snapshot is valid for) and a
+//   .ply being streamed (PlySource, ply_open, ply_stream).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -139,6 +140,10 @@ struct gs_ctx {
     size_t scene_bytes = 0;
     GsScene scene{};            // views into scene_mem
     uint32_t n = 0;
+    // Which numbering of splats the scene is: drawn from one process-wide counter (scene_new_serial) whenever a scene is installed
+    // by gs_upload_*, gs_share_splats or gs_compact; an insertion KEEPS it (old splats keep their indices).  A gs_snapshot names
+    // splats by index and stores the serial it was taken under: gs_snapshot_restore / _swap refuse any other (gs_snapshot.hip).
+    uint64_t scene_serial = 0;  // 0: no scene yet
     // per-gaussian frame buffers (alloc_per_gaussian)
     DevBuf<uint32_t> counts, offsets, rowptr; // (counts / rowptr hold whole 2048-index chunks: a tight frame keeps its entries there)
     DevBuf<unsigned short> unit_off;          // tight frames: the entries' third plane, the gaussian's index inside its 1024-index unit
@@ -248,6 +253,9 @@ GsSceneLayout scene_layout(void* base, uint64_t n, bool state);
 // scene_alloc with the scene given: drops the previous scene and the per-gaussian work arrays, allocates those for n gaussians
 // and takes `mem` (complete, laid out by scene_layout) as the resident scene
 int32_t scene_install(gs_ctx* c, DevBuf<>&& mem, uint64_t n, uint64_t min_capacity, uint64_t min_rows);
+// the next value of the process-wide scene counter (never 0): scene_alloc and gs_share_splats give it to c->scene_serial,
+// scene_install does not
+uint64_t scene_new_serial();
 void drop_shadows(gs_ctx* c);
 // gs_frame.hip
 void drop_graph(gs_ctx* c);
@@ -324,6 +332,8 @@ int32_t cluster_planes(gs_ctx* c, hipStream_t st);
 // gs_export.hip: the splat edits' selection: counts the splats with (s & mask) == value and, with want_ids, leaves their indices,
 // ascending, in c->ex.ids
 int32_t edit_select(gs_ctx* c, uint32_t mask, uint32_t value, bool want_ids, uint64_t* total);
+// records per trip through the bounce buffer of the host export and of the host write-back (320 MB)
+static constexpr uint64_t kBounceRecords = 1ull << 20;
 // gs_ply.hip: what decodeHeader (ply.ts:49-102) and PackedGaussians' constructor (:162-228) derive from the header: where the vertex
 // data starts, the vertex count and stride, and for each of the 11 + 3 (degree + 1)^2 values of a packed record its byte offset and
 // type in a vertex and its float slot in the 320-byte record (ply.ts:190-198).

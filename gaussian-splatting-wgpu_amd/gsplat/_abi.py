@@ -61,6 +61,10 @@ GS_XFORM_POSITION, GS_XFORM_ORIENT, GS_XFORM_SIZE = 0x1, 0x2, 0x4
 # colour grades
 GS_GRADE_MATRIX, GS_GRADE_OFFSET, GS_GRADE_OPACITY = 0x1, 0x2, 0x4
 
+# snapshots and write-back
+GS_PART_POSITION, GS_PART_GEOMETRY, GS_PART_SH, GS_PART_STATE = 0x1, 0x2, 0x4, 0x8
+GS_PART_RECORD = 0x7
+
 # splat attributes (gs_attr.kind)
 (GS_ATTR_POS_X, GS_ATTR_POS_Y, GS_ATTR_POS_Z, GS_ATTR_OPACITY_LOGIT, GS_ATTR_LOG_SCALE_MIN, GS_ATTR_LOG_SCALE_MAX, GS_ATTR_LOG_SCALE_SUM,
  GS_ATTR_ANISOTROPY, GS_ATTR_DC_R, GS_ATTR_DC_G, GS_ATTR_DC_B, GS_ATTR_DIST2, GS_ATTR_PLANE, GS_ATTR_COVER_HITS, GS_ATTR_COVER_MAX_WEIGHT,
@@ -86,6 +90,8 @@ ABI_SYMBOLS = ("gs_last_error", "gs_abi_version", "gs_create", "gs_destroy", "gs
                "gs_state_list", "gs_export_splats", "gs_export_splats_device", "gs_compact", "gs_ply_save", "gs_export_ply",
                "gs_append_splats", "gs_append_splats_device", "gs_append_ply", "gs_duplicate_splats",
                "gs_xform_compose", "gs_transform_splats", "gs_grade_compose", "gs_grade_splats",
+               "gs_write_splats", "gs_write_splats_device", "gs_snapshot_take", "gs_snapshot_restore", "gs_snapshot_swap",
+               "gs_snapshot_get_info", "gs_snapshot_free",
                "gs_coverage_accumulate", "gs_coverage_reset", "gs_coverage_read", "gs_state_coverage",
                "gs_attr_summary", "gs_attr_histogram", "gs_attr_read", "gs_state_attr",
                "gs_neigh_count", "gs_neigh_read", "gs_state_neigh",
@@ -140,6 +146,11 @@ class GsXform(ctypes.Structure):
 class GsGrade(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("a", ctypes.c_float * 9), ("dc", ctypes.c_float * 3),
                 ("opacity_logit", ctypes.c_float), ("reserved", ctypes.c_float)]
+
+
+class GsSnapshotInfo(ctypes.Structure):
+    _fields_ = [("count", ctypes.c_uint64), ("n_at_take", ctypes.c_uint64), ("device_bytes", ctypes.c_uint64), ("parts", ctypes.c_uint32),
+                ("dense", ctypes.c_uint32)]
 
 
 class GsCoverageRec(ctypes.Structure):
@@ -249,6 +260,13 @@ def load():
     L.gs_grade_compose.argtypes = [ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.c_float, ctypes.c_float,
                                    ctypes.c_float, ctypes.c_float, ctypes.POINTER(GsGrade)]
     L.gs_grade_splats.argtypes = [vp, u32, u32, ctypes.POINTER(GsGrade), ctypes.POINTER(u64)]
+    L.gs_write_splats.argtypes = [vp, vp, u64, vp, vp, u32, ctypes.POINTER(u64)]
+    L.gs_write_splats_device.argtypes = [vp, vp, u64, vp, vp, u32, ctypes.POINTER(u64)]
+    L.gs_snapshot_take.argtypes = [vp, u32, u32, u32, ctypes.POINTER(vp)]
+    L.gs_snapshot_restore.argtypes = [vp, vp, u32, ctypes.POINTER(u64)]
+    L.gs_snapshot_swap.argtypes = [vp, vp, u32, ctypes.POINTER(u64)]
+    L.gs_snapshot_get_info.argtypes = [vp, ctypes.POINTER(GsSnapshotInfo)]
+    L.gs_snapshot_free.argtypes = [vp]
     L.gs_coverage_accumulate.argtypes = [vp, ctypes.POINTER(GsCoverRegion), ctypes.POINTER(u64)]
     L.gs_coverage_reset.argtypes = [vp]
     L.gs_coverage_read.argtypes = [vp, vp, u64, ctypes.POINTER(u64)]

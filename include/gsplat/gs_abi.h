@@ -454,6 +454,7 @@ int32_t gs_duplicate_splats(gs_ctx* ctx, uint32_t mask, uint32_t value, uint32_t
  * owner -- its borrowers then render the new scene, and as for a state call the host drains them first.  GS_ERR_NO_SCENE before
  * any upload; N == 0: *matched = 0, GS_OK.  Multi-GPU: the same call on every rank (the result is deterministic).
  * The inverse transform is NOT a bit-exact undo (every step rounds): a host that wants one exports the selection first.
+ * (Or takes a gs_snapshot of the parts the transform names, on the device: "snapshots and write-back" below.)
  * "Bit for bit" has one exception a restating host must know: a NaN that an operation above PRODUCES or propagates (a NaN or an
  * infinite input in a flagged part: inf * 0, inf - inf) is a NaN on every machine, but IEEE 754 leaves its sign and payload open
  * and the device's choice differs from that of other processors (x86 produces 0xFFC00000 for inf * 0): compare such floats as
@@ -511,7 +512,8 @@ int32_t gs_transform_splats(gs_ctx* ctx, uint32_t mask, uint32_t value, const gs
  * NOT an upload: taps, statistics, gs_pick, the shadows, the capacities, a captured frame graph and the coverage, neighbour and
  * cluster planes stay; the NEXT frame shows the grade.  A ctx that borrows its scene (gs_share_splats) is refused: grade the
  * owner.  GS_ERR_NO_SCENE before any upload; N == 0: *matched = 0, GS_OK.
- * The inverse grade is NOT a bit-exact undo.  The transforms' one exception to "bit for bit" holds here too: a NaN that an
+ * The inverse grade is NOT a bit-exact undo.  (A gs_snapshot of GS_PART_SH, or of GS_PART_GEOMETRY for the opacity, is one:
+ * "snapshots and write-back" below.)  The transforms' one exception to "bit for bit" holds here too: a NaN that an
  * operation above produces or propagates is compared as "NaN on both sides"; floats of parts not flagged and of splats that do not
  * match are never computed. */
 #define GS_GRADE_MATRIX  0x1u   /* all 16 coefficient triples through a (192 B read, 192 B written per matched splat) */
@@ -542,6 +544,78 @@ int32_t gs_grade_compose(const float gain[3], const float offset[3], float satur
  * unknown flag bits, reserved != 0 or a non-finite member of a flagged part: GS_ERR_INVALID_ARGUMENT, nothing is applied.
  * flags == 0 is a valid no-op that still reports *matched. */
 int32_t gs_grade_splats(gs_ctx* ctx, uint32_t mask, uint32_t value, const gs_grade* g, uint64_t* matched);
+
+/* ---- snapshots and write-back: exact undo for resident splat edits, records scattered back by index ----
+ * The edits above change resident splats in place and none of them can be taken back: the inverse of a transform or a grade rounds
+ * again.  gs_export_splats brings the records of a selection out; these calls are its inverse.  The reference has no counterpart: its
+ * host keeps the PackedGaussians buffer it uploaded (renderer.ts:130-137), edits that and uploads it again -- here an upload of
+ * N x 320 B that a scene streamed in by gs_upload_ply has no host copy for, and that drops the last frame, the frames-in-flight
+ * shadows, a captured frame graph and the coverage, neighbour and cluster planes.
+ * Two layers.  gs_write_splats scatters records (and state bytes) a host holds -- what gs_export_splats returned, edited in the
+ * host's own code -- into the resident planes by index.  A gs_snapshot is a device-resident copy of the named parts of a selection
+ * that is restored, or swapped with the scene, in place: no PCIe traffic, no reallocation.  A swap leaves the edited values in the
+ * snapshot, so a second swap redoes the edit: undo and redo from one object; a journal of many edits is a host's stack of them.
+ * Parts: what a call reads or writes of a splat, by the floats of its 320-byte record (the 21 padding floats belong to no part and
+ * are ignored, whatever they hold).  FLOATS ARE COPIED AS WORDS: nothing is computed but the derived largest log-scale, so every
+ * bit pattern -- NaN payloads, -0, infinities -- arrives unchanged, and a host restates every result exactly.  Every float of a part
+ * that is not named keeps its bit pattern, and so does every splat that is not named.  A ctx written with records R at ids I
+ * equals, in every plane, a fresh ctx that was given gs_upload_splats(the record array with R at I) followed by gs_state_write.
+ * Traffic per splat and direction: POSITION 12 B, GEOMETRY 32 B (+ 4 B of the derived plane written), SH 192 B, STATE 1 B (through
+ * its word), + 4 B of index unless dense; a write-back reads the 16-byte columns of the named parts of each 320-byte record (16 / 48
+ * / 256 B); a swap moves its parts both ways.  Bound: HBM; rates: profiles/snapshots.txt.
+ * Everything else follows gs_transform_splats.  (mask, value) as gs_state_count: above 0xFF refused, (0, 0) matches every splat and
+ * works on a ctx without GS_FLAG_SPLAT_STATE, any other filter -- and GS_PART_STATE -- on such a ctx is refused as the state calls
+ * refuse it.  Unknown part bits: GS_ERR_INVALID_ARGUMENT.  A ctx that borrows its scene (gs_share_splats) is refused by all five ctx
+ * calls, before the ring is drained: write to / snapshot the owner (its borrowers read the owner's planes and render the result).
+ * Otherwise the call first completes all frames enqueued on the ctx's ring (an error of that wait is the call's error, nothing is
+ * done), runs on the ctx's stream and returns when done.  It is NOT a frame and NOT an upload: taps, statistics, gs_pick, the
+ * shadows, the capacities, a captured frame graph and the coverage, neighbour and cluster planes stay; the NEXT frame shows the
+ * written splats.  GS_ERR_NO_SCENE before any upload.  Every refusal is decided before anything is written.  Multi-GPU: the same
+ * call on every rank (a snapshot belongs to its rank's ctx). */
+#define GS_PART_POSITION 0x1u /* record floats 0..2                                  12 B */
+#define GS_PART_GEOMETRY 0x2u /* record floats 4..6, 8..11, 12: log-scales, rot, opacity logit 32 B;
+                                 the derived largest log-scale is recomputed as fmaxf(l0, fmaxf(l1, l2)),
+                                 the upload's own expression */
+#define GS_PART_SH       0x4u /* the 48 SH coefficients (record floats 16+4k+c)       192 B */
+#define GS_PART_STATE    0x8u /* the state byte (needs GS_FLAG_SPLAT_STATE)             1 B */
+#define GS_PART_RECORD   0x7u
+/* Write-back.  Record g of the m given 320-byte records goes to splat ids[g]; ids == NULL: to splat g, and m <= N is required.
+ * Only the parts named are written, from the corresponding floats of the record.  states: one byte per given record, read only
+ * with GS_PART_STATE (may be NULL otherwise, must not be with it), assigned through word atomics as gs_state_ids' ASSIGN does.
+ * ids must be strictly ascending and < N -- the order gs_state_list, gs_export_splats and gs_compact deliver; it rules out
+ * duplicates, so the result depends on no order.  The host variant checks the list on the host before anything is copied; the
+ * device variant with one small kernel whose answer is read back before the scatter is launched.  Both refuse with
+ * GS_ERR_INVALID_ARGUMENT and a message that names the position and the two ids (or the id that is no splat); nothing is written.
+ * The host variant stages through a bounce buffer, at most 2^20 records (320 MB) per trip, as the export does.  parts == 0 or
+ * m == 0 is a valid no-op.  *written (may be NULL): m, or 0 for a no-op. */
+int32_t gs_write_splats(gs_ctx* ctx, const uint32_t* ids, uint64_t m, const void* aos320, const uint8_t* states, uint32_t parts,
+                        uint64_t* written);                                                              /* HOST pointers   */
+/* Same, DEVICE pointers (d_ids, d_aos320, d_states): no PCIe copy.  They must be complete before the call (it reads them on the
+ * ctx's stream). */
+int32_t gs_write_splats_device(gs_ctx* ctx, const uint32_t* d_ids, uint64_t m, const void* d_aos320, const uint8_t* d_states,
+                               uint32_t parts, uint64_t* written);                                       /* DEVICE pointers */
+/* Snapshots.  gs_snapshot_take runs the splat edits' selection ((0, 0): dense, no selection runs and no id list is kept) and
+ * gathers the named parts of the matching splats into ONE device allocation of the snapshot's own, compact SoA: the id list, 3 x
+ * f32[m] positions, 2 x float4[m] geometry, 12 x float4[m] SH, u8[m] state (sections rounded up to 16 bytes).  Memory follows the
+ * parts: a POSITION snapshot of a translate costs 16 B per splat (12 + the index), not 320.  count == 0 is a valid object.
+ * gs_snapshot_restore scatters parts back (parts == 0: all that were taken; a part that was not taken is refused) and leaves the
+ * snapshot unchanged: it can be applied again.  gs_snapshot_swap exchanges scene and snapshot contents in one pass.  A restored or
+ * swapped GS_PART_GEOMETRY also stores the derived largest log-scale, so the ctx equals one freshly uploaded with those records.
+ * Validity: a snapshot names splats by index.  Every scene carries a 64-bit serial, drawn from one process-wide counter whenever a
+ * scene is installed by gs_upload_*, gs_share_splats or gs_compact; the snapshot stores it, and restore / swap on a ctx whose serial
+ * differs -- another ctx, or the same ctx after an upload or a compaction -- are refused with GS_ERR_INVALID_ARGUMENT: the scene
+ * was replaced or renumbered.  An insertion KEEPS the serial (old splats keep their indices): a snapshot stays valid across
+ * gs_append_* and gs_duplicate_splats and leaves the new splats alone.  Snapshots that survive a compaction are out of scope.
+ * Ownership: the snapshot owns its memory and remembers its device; gs_snapshot_free works at any time, also after gs_destroy of
+ * the ctx, and gs_destroy frees no snapshot.  gs_snapshot_get_info needs no ctx and makes no GPU call.  *restored / *swapped (may
+ * be NULL): the snapshot's count, or 0 when nothing was to be moved. */
+typedef struct gs_snapshot gs_snapshot;
+typedef struct gs_snapshot_info { uint64_t count, n_at_take, device_bytes; uint32_t parts, dense; } gs_snapshot_info; /* 32 B */
+int32_t gs_snapshot_take(gs_ctx* ctx, uint32_t mask, uint32_t value, uint32_t parts, gs_snapshot** out);
+int32_t gs_snapshot_restore(gs_ctx* ctx, const gs_snapshot* snapshot, uint32_t parts, uint64_t* restored); /* snapshot -> scene  */
+int32_t gs_snapshot_swap(gs_ctx* ctx, gs_snapshot* snapshot, uint32_t parts, uint64_t* swapped);           /* snapshot <-> scene */
+int32_t gs_snapshot_get_info(const gs_snapshot* snapshot, gs_snapshot_info* out);
+int32_t gs_snapshot_free(gs_snapshot* snapshot);                                                           /* NULL is GS_OK      */
 
 /* ---- coverage: per-splat contribution of the LAST frame, select by what is seen ---------------------
  * gs_state_region selects THROUGH surfaces and gs_pick answers for one pixel at a time; neither can say which splats the user
