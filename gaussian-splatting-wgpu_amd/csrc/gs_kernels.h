@@ -4,13 +4,15 @@
 
 void gs_launch_repack(const void* d_aos, uint32_t n, uint32_t first, const GsScene& s, hipStream_t st); // record r -> splat first + r
 void gs_launch_ply_chunk(const void* d_raw, uint32_t m, uint32_t first, const GsPlyTable& t, const GsScene& s, hipStream_t st);
-struct GsPreprocessLaunch { // the projection's launch as data (its uniforms are the only kernel arguments that change per frame)
+struct GsPreprocessLaunch { // the projection's launch as data (its uniforms, and w2 derived from them, are the only kernel arguments that change per frame)
     const void* func;
     uint32_t blocks;
     GsScene s; GsUniforms u; GsFrame f;
     void* gdata; uint32_t* counts; GsTightOut to; GsTint tint;
-    void* args[7];
+    float w2; // slab reach cull: >= the squared spectral norm of u.view's 3x3 (gs_view_norm2)
+    void* args[8];
 };
+float gs_view_norm2(const GsUniforms& u);
 // state: the STATE instantiation (honours s.state and the tint); false launches exactly the kernels a context without the plane has
 void gs_preprocess_prepare(GsPreprocessLaunch& L, const GsScene& s, const GsUniforms& u, const GsFrame& f, void* gdata, uint32_t* counts,
                            bool tight, uint32_t* arena, uint32_t* rowptr, unsigned short* unit_off, uint32_t* unit_n, GsControl* ctl,

@@ -163,7 +163,7 @@ __device__ __forceinline__ void sh_colour(const float4* __restrict__ sh, float x
 }
 
 // in_frustum (process_gaussians.wgsl:108-125) and, for a tile-column slab, a conservative reach test on the position alone.
-__device__ __forceinline__ bool in_frustum_slab(const GsUniforms& u, const GsFrame& f, float x, float y, float z, float smax_log) {
+__device__ __forceinline__ bool in_frustum_slab(const GsUniforms& u, const GsFrame& f, float w2, float x, float y, float z, float smax_log) {
     float ph[4], pv[4];
     m4_mulv(u.proj, x, y, z, ph);
     const float pw = 1.0f / (ph[3] + 0.0000001f);
@@ -172,13 +172,15 @@ __device__ __forceinline__ bool in_frustum_slab(const GsUniforms& u, const GsFra
     if ((pv[2] <= 0.2f) || (ndx <= -1.1f || ndx >= 1.1f || ndy <= -1.1f || ndy >= 1.1f)) return false;
     if (f.full) return true;
     // Tile-column slab: drop the gaussian here, before its record is touched, if even a conservative
-    // bound of its screen radius cannot reach this rank's columns.  lambda_max(cov2d) <= |J|_F^2 * s_max^2
-    // (W is orthonormal), |J|_F^2 <= (fx/z)^2 (1+limx^2) + (fy/z)^2 (1+limy^2) after the clamp of :180-186,
-    // and lambda_1 <= (a+c) + sqrt(0.1) <= 2*lambda_max(cov) + 0.92; margins cover the f32 rounding.
+    // bound of its screen radius cannot reach this rank's columns.  cov2d = J W Sigma W^T J^T with W the view's 3x3, ANY
+    // matrix the host wrote (scaled, sheared: nothing makes it orthonormal), so lambda_max(cov2d) <= |J|_F^2 * |W|_2^2 * s_max^2;
+    // w2 >= |W|_2^2 comes with the launch (gs_view_norm2: 1 to 1e-6 for a rigid view).  |J|_F^2 <= (fx/z)^2 (1+limx^2) +
+    // (fy/z)^2 (1+limy^2) after the clamp of :180-186, and lambda_1 <= (a+c) + sqrt(0.1) <= 2*lambda_max(cov) + 0.92; margins
+    // cover the f32 rounding.  A w2 that is NaN or infinite makes rb NaN or infinite: the gaussian is kept.
     const float sm = __expf(smax_log) * u.scale_modifier * 1.001f;
     const float limx = 1.3f * u.tan_fovx, limy = 1.3f * u.tan_fovy;
     const float iz = 1.0f / pv[2];
-    const float jf2 = (u.focal_x * iz) * (u.focal_x * iz) * (1.0f + limx * limx) + (u.focal_y * iz) * (u.focal_y * iz) * (1.0f + limy * limy);
+    const float jf2 = ((u.focal_x * iz) * (u.focal_x * iz) * (1.0f + limx * limx) + (u.focal_y * iz) * (u.focal_y * iz) * (1.0f + limy * limy)) * w2;
     const float rb = 3.0f * __builtin_sqrtf(2.0f * jf2 * sm * sm + 0.92f) * 1.001f + 2.0f;
     const float pxs = ((ndx * 0.5f) + 0.5f) * (float)f.width;
     const float ts = (float)f.tile_size;
@@ -254,7 +256,7 @@ typedef uint32_t gs_row_u32x3 __attribute__((ext_vector_type(3), aligned(4)));
 //                STATE = false is the code a context without the plane has always launched: nothing of this is in it.
 template <bool TIGHT, int NB, bool STATE>
 __global__ __launch_bounds__(256, PRE_WAVES) void gs_preprocess_kernel(GsScene s, GsUniforms u, GsFrame f, uint4* __restrict__ gdata,
-                                                             uint32_t* __restrict__ tile_counts, GsTightOut to, GsTint tint) {
+                                                             uint32_t* __restrict__ tile_counts, GsTightOut to, GsTint tint, float w2) {
     __shared__ uint32_t s_ids[PRE_G * NB];
     constexpr bool KEEP_POS = NB == 2; // (whole canvas; at NB = 8 the 48 KB would halve the slab workgroups per CU: 65-100 -> 128-184 us per rank)
     __shared__ float s_pos[3][KEEP_POS ? PRE_G * NB : 1];
@@ -321,7 +323,7 @@ __global__ __launch_bounds__(256, PRE_WAVES) void gs_preprocess_kernel(GsScene s
                     const uint32_t i = base + (uint32_t)(h * GRP + k) * 256u + tid;
                     bool v = false;
                     if (i < f.n) {
-                        v = in_frustum_slab(u, f, X[k], Y[k], Z[k], S[k]);
+                        v = in_frustum_slab(u, f, w2, X[k], Y[k], Z[k], S[k]);
                         if (STATE && (B[k] & GS_ST_HIDDEN)) v = false; // a hidden splat: exactly a culled one
                     }
                     vm |= (v ? 1u : 0u) << k;
@@ -350,7 +352,7 @@ __global__ __launch_bounds__(256, PRE_WAVES) void gs_preprocess_kernel(GsScene s
                 const uint32_t i = base + off;
                 bool v = false;
                 if (i < f.n) {
-                    v = in_frustum_slab(u, f, X[k], Y[k], Z[k], S[k]);
+                    v = in_frustum_slab(u, f, w2, X[k], Y[k], Z[k], S[k]);
                     if (STATE && (B[k] & GS_ST_HIDDEN)) v = false; // a hidden splat: exactly a culled one
                     if (!v) tile_counts[i] = 0u;
                 }
@@ -391,7 +393,7 @@ __global__ __launch_bounds__(256, PRE_WAVES) void gs_preprocess_kernel(GsScene s
             const uint32_t i = base + k * 256 + tid;
             vis[k] = false;
             if (i < f.n) {
-                vis[k] = in_frustum_slab(u, f, s.px[i], s.py[i], s.pz[i], f.full ? 0.0f : s.smax[i]);
+                vis[k] = in_frustum_slab(u, f, w2, s.px[i], s.py[i], s.pz[i], f.full ? 0.0f : s.smax[i]);
                 if (STATE) {
                     sb[k] = (uint32_t)s.state[i];
                     if (sb[k] & GS_ST_HIDDEN) vis[k] = false;
@@ -655,8 +657,34 @@ void gs_launch_repack(const void* d_aos, uint32_t n, uint32_t first, const GsSce
     hipLaunchKernelGGL(gs_repack_kernel, dim3(blocks), dim3(256), 0, st, (const float4*)d_aos, n, first, (float*)s.px, (float*)s.py,
                        (float*)s.pz, (float*)s.smax, (float*)s.geo, (float*)s.sh);
 }
+// The factor w2 of the slab reach cull (in_frustum_slab): an upper bound of the squared spectral norm of the view matrix's 3x3,
+// in double on the host, once per frame.  It is the largest eigenvalue of the symmetric A = W^T W in closed form (q + 2 p cos phi
+// with q = tr A / 3, p^2 = tr (A - q I)^2 / 6, cos 3 phi = det((A - q I) / p) / 2), a hair (1e-7) up for its own rounding and the
+// conversion to f32.  An orthonormal W rounded to f32 gives 1 + O(1e-7): a rigid view's slabs keep the survivors they kept with
+// the factor 1 (the Frobenius norm would give 3: every rank's survivor set would grow by 3x in radius^2).  A NaN or an infinity
+// anywhere in W comes out as NaN or infinity, which the cull answers by keeping every gaussian.
+float gs_view_norm2(const GsUniforms& u) {
+    double A[3][3];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            A[i][j] = 0.0; // (W^T W)[i][j] = column i of W . column j of W; column c of the column-major view starts at 4 c
+            for (int r = 0; r < 3; ++r) A[i][j] += (double)u.view[4 * i + r] * (double)u.view[4 * j + r];
+        }
+    const double q = (A[0][0] + A[1][1] + A[2][2]) / 3.0;
+    const double d0 = A[0][0] - q, d1 = A[1][1] - q, d2 = A[2][2] - q;
+    const double p2 = (d0 * d0 + d1 * d1 + d2 * d2 + 2.0 * (A[0][1] * A[0][1] + A[0][2] * A[0][2] + A[1][2] * A[1][2])) / 6.0;
+    const double p = sqrt(p2);
+    double lam = q; // A = q I
+    if (!(p <= 1e-14 * fabs(q))) { // (also taken by a NaN, which then goes through)
+        const double b01 = A[0][1] / p, b02 = A[0][2] / p, b12 = A[1][2] / p, b0 = d0 / p, b1 = d1 / p, b2 = d2 / p;
+        double r = 0.5 * (b0 * (b1 * b2 - b12 * b12) - b01 * (b01 * b2 - b12 * b02) + b02 * (b01 * b12 - b1 * b02));
+        r = r < -1.0 ? -1.0 : (r > 1.0 ? 1.0 : r); // (a NaN passes both comparisons)
+        lam = q + 2.0 * p * cos(acos(r) / 3.0);
+    }
+    return (float)(lam * (1.0 + 1e-7));
+}
 // The projection's launch as data: the one kernel of a frame whose arguments change from frame to frame (the uniforms, by
-// value), so a captured frame graph (gs_frame.hip) re-launches it with updated parameters.
+// value, and the factor derived from them), so a captured frame graph (gs_frame.hip) re-launches it with updated parameters.
 void gs_preprocess_prepare(GsPreprocessLaunch& L, const GsScene& s, const GsUniforms& u, const GsFrame& f, void* gdata, uint32_t* counts,
                            bool tight, uint32_t* arena, uint32_t* rowptr, unsigned short* unit_off, uint32_t* unit_n, GsControl* ctl,
                            uint32_t tight_nb, bool state, GsTint tint) {
@@ -679,9 +707,10 @@ void gs_preprocess_prepare(GsPreprocessLaunch& L, const GsScene& s, const GsUnif
                                                                                                    : (const void*)&gs_preprocess_kernel<false, 1, false>;
     }
     L.s = s; L.u = u; L.f = f; L.gdata = gdata; L.counts = counts; L.tint = tint;
+    L.w2 = f.full ? 1.0f : gs_view_norm2(u); // (the whole canvas has no reach cull: in_frustum_slab returns before it uses the factor)
     L.to.arena = arena; L.to.rowptr = rowptr; L.to.unit_off = unit_off; L.to.unit_n = unit_n; L.to.ctl = ctl;
     L.to.rec_shard_cap = ((L.blocks + 15u) / 16u) * (PRE_G * nb); // 16 of them are at most n + GS_RECORD_SLACK records for every nb <= 8
-    L.args[0] = &L.s; L.args[1] = &L.u; L.args[2] = &L.f; L.args[3] = &L.gdata; L.args[4] = &L.counts; L.args[5] = &L.to; L.args[6] = &L.tint;
+    L.args[0] = &L.s; L.args[1] = &L.u; L.args[2] = &L.f; L.args[3] = &L.gdata; L.args[4] = &L.counts; L.args[5] = &L.to; L.args[6] = &L.tint; L.args[7] = &L.w2;
 }
 void gs_launch_preprocess(GsPreprocessLaunch& L, hipStream_t st) {
     if (!L.f.n) return;

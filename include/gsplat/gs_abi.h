@@ -75,7 +75,9 @@ typedef struct gs_config {
     uint32_t width, height;     /* canvas.width / canvas.height (renderer.ts:157,199,366)                       */
     uint32_t tile_size;         /* 8, 16 or 32 (index.html:20-24, app.ts:29,45)                                 */
     int32_t device;             /* HIP device ordinal                                                           */
-    uint32_t col_begin, col_end;/* tile-column slab owned by this ctx, [begin,end); 0,0 = whole screen          */
+    uint32_t col_begin, col_end;/* tile-column slab owned by this ctx, [begin,end); 0,0 = whole screen.  A slab only
+                                   filters: its frame is the whole screen's frame cut to its columns, bit for bit, for
+                                   any finite view matrix in the uniform block (scaled, sheared, non-rigid included) */
     uint32_t flags;             /* GS_FLAG_*                                                                     */
     uint64_t max_intersections; /* capacity hint for the (key,value) arrays; 0 = derive from the scene         */
     void* stream;               /* hipStream_t to run on; NULL = the ctx creates its own (so the legacy default stream,
