@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """CPU-only logic check of the tight binning (gs_tight.h) against the oracle's exact contribution masks.
-Usage: python tools/tight_check/run.py [n] [W] [H] [ts] [camera step] [scale_modifier]
-As a module: check(splats, uniforms, W, H, ts, header=None) -> the counts host_check prints (see check)."""
+Usage: python tools/tight_check/run.py [dump] [n] [W] [H] [ts] [camera step] [scale_modifier]
+As a module: check(splats, uniforms, W, H, ts, header=None) -> the counts host_check prints (see check);
+dump(splats, uniforms, W, H, ts, cols=None) -> every row-item slot the tight projection hands the row pipeline (see dump)."""
 import hashlib, os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(ROOT, "gaussian-splatting-wgpu_amd")); sys.path.insert(0, ROOT)
@@ -64,6 +65,30 @@ def check(splats, uniforms, W, H, ts, header=None):
             "ratio": kept / max(contributing, 1), "returncode": out.returncode, "stdout": out.stdout}
 
 
+def dump(splats, uniforms, W, H, ts, cols=None, header=None):
+    """host_check's second mode on one frame (cols: a tile-column slab, None: the whole canvas): every row-item slot the tight
+    projection hands the row pipeline, as a uint32 [slots, 5] array of (gaussian index, slot number, tile row, first tile column,
+    tiles; tiles == 0: a hole), gaussians in index order, and the depth bucket of every gaussian (uint32 [n]; the oracle's key
+    % 1000 where the gaussian has an instance, else 0)."""
+    from oracle import gs_oracle as o
+    exe = build(header)
+    gd, cnt = o.preprocess(splats, uniforms, W, H, ts, cols)
+    off, I = o.scan(cnt)
+    k, v = o.emit(gd, off, cnt, I, W, ts, cols)
+    bucket = np.zeros(gd.shape[0], np.uint32)
+    bucket[v] = k % 1000
+    c0, c1 = cols if cols is not None else (0, o.num_tiles(W, H, ts)[0])
+    with tempfile.TemporaryDirectory(dir=_tmp()) as d:
+        names = [os.path.join(d, x + ".bin") for x in ("gd", "cnt", "out")]
+        gd.astype(np.uint32).tofile(names[0])
+        cnt.astype(np.uint32).tofile(names[1])
+        out = subprocess.run([exe, "dump", names[0], names[1], str(W), str(H), str(ts), str(c0), str(c1), names[2]], capture_output=True, text=True)
+        if out.returncode:
+            raise RuntimeError("host_check dump failed (%d): %s" % (out.returncode, out.stderr[-500:]))
+        slots = np.fromfile(names[2], np.uint32).reshape(-1, 5)
+    return slots, bucket
+
+
 def bicycle_case(n, W, H, ts, step, mod=1.0):
     """(splats, uniforms) of the command line's scene: synth.bicycle_like from the orbit camera's step."""
     from gsplat import synth
@@ -74,6 +99,14 @@ def bicycle_case(n, W, H, ts, step, mod=1.0):
 
 
 def main(argv):
+    if len(argv) > 1 and argv[1] == "dump":  # the slots of the same scene: their number, the items and the instances among them
+        argv = argv[:1] + argv[2:]
+        n, W, H, ts, step = (int(x) for x in (argv[1:6] + ["200000", "1920", "1080", "16", "0"][len(argv) - 1:]))
+        s, u = bicycle_case(n, W, H, ts, step, float(argv[6]) if len(argv) > 6 else 1.0)
+        slots, _ = dump(s, u, W, H, ts)
+        print("slots %d | items %d | instances %d | gaussians with slots %d" % (slots.shape[0], int((slots[:, 4] > 0).sum()), int(slots[:, 4].sum()),
+                                                                             np.unique(slots[:, 0]).size))
+        return 0
     n, W, H, ts, step = (int(x) for x in (argv[1:6] + ["200000", "1920", "1080", "16", "0"][len(argv) - 1:]))
     mod = float(argv[6]) if len(argv) > 6 else 1.0
     s, u = bicycle_case(n, W, H, ts, step, mod)
