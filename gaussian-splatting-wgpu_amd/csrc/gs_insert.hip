@@ -124,6 +124,32 @@ GS_EXPORT int32_t gs_append_ply(gs_ctx* c, const char* path, uint32_t new_state,
     return GS_OK;
 }
 
+// gs_append_ply with the packed file's two halves (gs_pack.hip): the same refusals in the same order, the same install.
+GS_EXPORT int32_t gs_append_packed(gs_ctx* c, const char* path, uint32_t new_state, uint64_t* first, uint64_t* m_out) {
+    static const char who[] = "gs_append_packed";
+    int32_t rc = new_state_check(who, new_state);
+    if (rc != GS_OK) return rc;
+    if (!path) return fail(GS_ERR_INVALID_ARGUMENT, "%s: null path", who);
+    rc = insert_check(c, who, new_state);
+    if (rc != GS_OK) return rc;
+    PackSource src;
+    rc = pack_open(who, path, &src); // cannot be opened, a header that is not exactly the format's, a size other than the header implies
+    if (rc != GS_OK) return rc;
+    const uint64_t m = src.L.n;
+    rc = insert_fits(c, who, m);
+    if (rc != GS_OK) return rc;
+    rc = resident_drain(c);
+    if (rc != GS_OK) return rc;
+    const uint32_t n_old = c->n;
+    if (m) {
+        rc = insert_grow(c, m, new_state, [&](const GsScene& dst) { return pack_stream(who, c, src, dst, n_old); });
+        if (rc != GS_OK) return rc;
+    }
+    if (first) *first = n_old;
+    if (m_out) *m_out = m;
+    return GS_OK;
+}
+
 GS_EXPORT int32_t gs_duplicate_splats(gs_ctx* c, uint32_t mask, uint32_t value, uint32_t new_state, uint64_t* first, uint64_t* m_out,
                                       uint32_t* ids) {
     static const char who[] = "gs_duplicate_splats";

@@ -208,6 +208,26 @@ void gs_launch_xform(const GsScene& s, uint32_t n, const uint32_t* ids, uint32_t
 // logit) are graded in place.
 struct gs_grade;
 void gs_launch_grade(const GsScene& s, uint32_t n, const uint32_t* ids, uint32_t m, const gs_grade& x, hipStream_t st);
+// k_pack.hip: the packed scenes (gs_pack.hip).  Entry g (0 .. m) is splat ids[g], or splat g when ids is null.
+struct GsPackBox { float lo[3], hi[3]; }; // the bounds of the selection's splats with three finite coordinates
+// keys[g] = the Morton key of entry g under `box` (GS_PACK_KEY_LAST with a non-finite coordinate), vals[g] = its splat
+void gs_launch_pack_keys(const GsScene& s, uint32_t n, const uint32_t* ids, uint32_t m, const GsPackBox& box, uint32_t* keys, uint32_t* vals,
+                         hipStream_t st);
+// The three sections of the m entries: C = ceil(m / 256) chunk records (18 floats), m vertices (16 B), and with K > 0 the SH bytes,
+// 256 x 3K per chunk (the buffer holds whole chunks; the bytes behind entry m are 0 or untouched).  bad: 5 C words, the replaced
+// floats per chunk (C words of the vertices, then 4 C of the SH bytes): the caller adds them up.
+void gs_launch_pack_encode(const GsScene& s, uint32_t n, const uint32_t* ids, uint32_t m, uint32_t K, float* chunks, void* vertices, void* sh_bytes,
+                           uint32_t* bad, hipStream_t st);
+// One trip of a packed file on the device: m vertices that start at a chunk boundary (16-byte aligned), their chunk records, their
+// 3K SH bytes each (null with K = 0) and the 256 logits.  Vertex v becomes splat first + v of `dst`.
+struct GsPackTrip {
+    const uint4* vertices;
+    const float* chunks;
+    const uint8_t* sh;
+    const float* table;
+    uint32_t m, K;
+};
+void gs_launch_pack_decode(const GsPackTrip& t, uint32_t first, const GsScene& dst, hipStream_t st);
 // k_pick.hip: gs_pick, one wave per query over the last frame's lists (queries: {x, y} pairs; results: 12 words per query;
 // contrib: max_contrib {id, weight} pairs per query, or null)
 void gs_launch_pick(const GsLists& L, const void* d_queries, uint32_t n, void* d_results, uint32_t max_contrib, void* d_contrib, hipStream_t st);

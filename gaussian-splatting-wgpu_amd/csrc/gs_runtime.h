@@ -8,7 +8,7 @@
 //   (neigh_build, neigh_budget, neigh_slices), the cluster planes (cluster_planes), the splat edits' selection (edit_select), the
 //   check of a gs_attr (attr_check), the layout of a scene allocation (scene_layout, scene_install), the serial that tells one
 //   numbering of the resident splats from the next (gs_ctx::scene_serial, scene_new_serial: what a gs_snapshot is valid for) and a
-//   .ply being streamed (PlySource, ply_open, ply_stream).
+//   .ply being streamed (PlySource, ply_open, ply_stream) and a packed file being streamed (PackSource, pack_open, pack_stream).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -21,6 +21,7 @@
 
 #include "../../include/gsplat/gs_abi.h"
 #include "gs_kernels.h"
+#include "gs_pack_host.h"
 
 #define GS_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -351,6 +352,13 @@ struct PlyLayout {
 struct PlySource { File fp; PlyLayout L; };
 int32_t ply_open(const char* who, const char* path, PlySource* src);
 int32_t ply_stream(const char* who, gs_ctx* c, PlySource& src, const GsScene& dst, uint64_t first);
+// gs_pack.hip: a packed file being streamed (gs_upload_packed, gs_append_packed), the two halves as for a .ply.  pack_open: opens it,
+// checks its header against its size (gs_pack_host.h) and allocates nothing on the device.  pack_stream: vertex v becomes splat
+// first + v of `dst`, in trips of 256 whole chunks through two pinned and two device staging buffers, decoded on the device; returns
+// when the stream is done.
+struct PackSource { File fp; GsPackLayout L; };
+int32_t pack_open(const char* who, const char* path, PackSource* src);
+int32_t pack_stream(const char* who, gs_ctx* c, PackSource& src, const GsScene& dst, uint64_t first);
 // gs_attr.hip: the refusals of a gs_attr (null, struct_size, kind, a non-finite p of the kinds that read it) in `who`'s name; *dev:
 // its parameters as the kernels take them.  attr_needs_cover: the kind reads the coverage planes (cover_planes first)
 int32_t attr_check(const char* who, const gs_attr* a, GsAttrDev* dev);

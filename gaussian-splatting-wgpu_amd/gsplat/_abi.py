@@ -81,6 +81,9 @@ GS_NEIGH_LIMIT_NONE = 0xFFFFFFFF  # gs_neigh.limit: count every neighbour
 GS_CLUSTER_NONE = 0xFFFFFFFF  # the label of a splat that is no member
 GS_CLUSTER_MAX_ROUNDS = 64
 
+# packed scenes (gs_export_packed's order)
+GS_PACK_ORDER_INDEX, GS_PACK_ORDER_MORTON = 0, 1
+
 # every symbol include/gsplat/gs_abi.h declares
 ABI_SYMBOLS = ("gs_last_error", "gs_abi_version", "gs_create", "gs_destroy", "gs_upload_splats", "gs_upload_splats_device",
                "gs_share_splats",
@@ -95,7 +98,9 @@ ABI_SYMBOLS = ("gs_last_error", "gs_abi_version", "gs_create", "gs_destroy", "gs
                "gs_coverage_accumulate", "gs_coverage_reset", "gs_coverage_read", "gs_state_coverage",
                "gs_attr_summary", "gs_attr_histogram", "gs_attr_read", "gs_state_attr",
                "gs_neigh_count", "gs_neigh_read", "gs_state_neigh",
-               "gs_cluster_label", "gs_cluster_read", "gs_state_cluster", "gs_state_cluster_linked", "gs_set_option", "gs_slab_width", "gs_assemble_slabs", "gs_sort_pairs_u32",
+               "gs_cluster_label", "gs_cluster_read", "gs_state_cluster", "gs_state_cluster_linked",
+               "gs_pack_encode", "gs_pack_decode", "gs_pack_save", "gs_pack_load", "gs_pack_logit_table", "gs_export_packed", "gs_upload_packed",
+               "gs_append_packed", "gs_set_option", "gs_slab_width", "gs_assemble_slabs", "gs_sort_pairs_u32",
                "gs_exclusive_scan_u32")
 
 
@@ -191,6 +196,10 @@ class GsClusterInfo(ctypes.Structure):
                 ("rounds", ctypes.c_uint32), ("cells", ctypes.c_uint32 * 3), ("cell_edge", ctypes.c_float), ("reserved", ctypes.c_uint32)]
 
 
+class GsPackInfo(ctypes.Structure):
+    _fields_ = [("count", ctypes.c_uint64), ("chunks", ctypes.c_uint64), ("file_bytes", ctypes.c_uint64), ("nonfinite", ctypes.c_uint64)]
+
+
 # numpy views of the same records (what Renderer.pick returns)
 PICK_RESULT_DTYPE = np.dtype([(n, np.float32 if t is ctypes.c_float else np.uint32) for n, t in GsPickResult._fields_])
 PICK_CONTRIB_DTYPE = np.dtype([("id", np.uint32), ("weight", np.float32)])
@@ -283,6 +292,14 @@ def load():
     L.gs_cluster_read.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64)]
     L.gs_state_cluster.argtypes = [vp, u32, u32, u32, u32, u32, u32, u32, ctypes.POINTER(u64)]
     L.gs_state_cluster_linked.argtypes = [vp, u32, u32, u32, u32, u32, u32, ctypes.POINTER(u64)]
+    L.gs_pack_encode.argtypes = [vp, u64, i32, vp, vp, vp, ctypes.POINTER(u64)]
+    L.gs_pack_decode.argtypes = [vp, vp, vp, u64, i32, vp]
+    L.gs_pack_save.argtypes = [ctypes.c_char_p, vp, u64, i32]
+    L.gs_pack_load.argtypes = [ctypes.c_char_p, ctypes.POINTER(vp), ctypes.POINTER(u64), ctypes.POINTER(i32)]
+    L.gs_pack_logit_table.argtypes = [vp]
+    L.gs_export_packed.argtypes = [vp, ctypes.c_char_p, u32, u32, i32, i32, ctypes.POINTER(GsPackInfo), vp]
+    L.gs_upload_packed.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(u64)]
+    L.gs_append_packed.argtypes = [vp, ctypes.c_char_p, u32, ctypes.POINTER(u64), ctypes.POINTER(u64)]
     L.gs_set_option.argtypes = [vp, i32, ctypes.c_int64]
     L.gs_slab_width.argtypes = [vp, ctypes.POINTER(u32), ctypes.POINTER(u32)]
     L.gs_assemble_slabs.argtypes = [vp, vp, ctypes.POINTER(u32), u32, u64, vp]

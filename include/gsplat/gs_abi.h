@@ -928,6 +928,74 @@ int32_t gs_slab_width(gs_ctx* ctx, uint32_t* px_begin, uint32_t* px_width);
 int32_t gs_assemble_slabs(gs_ctx* ctx, const void* d_slabs, const uint32_t* col_bounds, uint32_t n_slabs,
                           uint64_t slab_stride_bytes, void* d_image);
 
+/* ---- packed scenes: save, load and append the 16-byte chunked splat format ---------------------------------
+ * The float .ply is 248 bytes per splat at SH degree 3.  The packed file keeps position, rotation, log-scale and colour in four
+ * 32-bit words per splat, quantised against the bounds of its chunk of 256 splats, plus one byte per higher SH coefficient: 16 bytes
+ * per splat at degree 0, 61 at degree 3, and 72 bytes per chunk.  The reference has no counterpart (ply.ts:49-228 reads the float
+ * .ply only).  No interoperability with third-party files is claimed: the files carry the line `comment gsplat-packed 1` and only
+ * files with it are read.  THE DEFINITION (csrc/gs_pack_math.h is its one copy in code; all arithmetic f32, one IEEE rounding per
+ * written operation; record floats f[] numbered as in a 320-byte record: 0..2 position, 4..6 log-scales, 8..11 rotation r x y z,
+ * 12 opacity logit, 16 + 4 k + c SH coefficient k channel c; min / max as wg_min / wg_max below):
+ *   fin(v) = v when finite, else +0.   unorm(v, b) = f2u_sat(min(T, max(0, v T + 0.5))), T = 2^b - 1 (a NaN gives 0).
+ *   norm(v, lo, hi) = hi > lo ? (v - lo) / (hi - lo) : 0.   lerp(lo, hi, t) = lo (1 - t) + hi t.   dn(code, b) = (float)code / T.
+ *   Entry g of the output belongs to chunk g / 256; the last chunk may be partial and its bounds come from its real entries only.
+ *   Per entry: p_k = fin(f[k]); s_k = max(-20, min(20, fin(f[4 + k]))); c_k = fin(f[16 + k]) * 0.28209479177387814f + 0.5f;
+ *   alpha a from o = f[12]: NaN -> 0; o >= 0 -> 1 / (1 + exp(-o)); else ez / (1 + ez), ez = exp(o) (exp: the canonical one);
+ *   rotation from q = fin(f[8..11]): len = sqrt(((q0 q0 + q1 q1) + q2 q2) + q3 q3); not (len > 0) or len not finite -> q = (1,0,0,0),
+ *   else q_k / len; L = the lowest index with the largest |q_k|; q_L < 0 negates all four; t0 t1 t2 = the other three, ascending.
+ *   Chunk record, 18 floats: min xyz, max xyz of p; the same of s; min rgb, max rgb of c -- exact minima and maxima in the total
+ *   order of the bit patterns (-0 below +0; all values are finite), so that every reduction order gives the same bits.
+ *   Vertex, four u32: packed_position = unorm(nx,11)<<21 | unorm(ny,10)<<11 | unorm(nz,11), n* = norm(p, lo, hi);
+ *   packed_rotation = L<<30 | unorm(t0 h + 0.5, 10)<<20 | unorm(t1 h + 0.5, 10)<<10 | unorm(t2 h + 0.5, 10), h = 0.70710678118654752f;
+ *   packed_scale like packed_position over s; packed_color = unorm(nr,8)<<24 | unorm(ng,8)<<16 | unorm(nb,8)<<8 | unorm(a,8).
+ *   SH rest, degree d >= 1, K = (d+1)^2 - 1, 3K bytes per splat: byte c K + i = f2u_sat(min(255, max(0, (fin(f[16 + 4 (i+1) + c]) / 8
+ *   + 0.5) * 256))).
+ *   Decode: position and log-scale lerp(lo, hi, dn); f[16 + k] = (lerp(lo, hi, dn) - 0.5f) / 0.28209479177387814f;
+ *   t_i = (dn(code_i, 10) - 0.5f) * 1.41421356237309505f, m = sqrt(max(0, 1 - ((t0 t0 + t1 t1) + t2 t2))) at index L, the t's at the
+ *   others (not renormalised: the projection normalises); logit = table[a8], the 256 floats of gs_pack_logit_table:
+ *   (float)log(x / (1 - x)) in double, x = a8 / 255, but 0.5 / 255 for code 0 and 254.5 / 255 for code 255 (every logit finite);
+ *   SH rest (((float)byte + 0.5f) / 256 - 0.5f) * 8; coefficients above the file's degree and the 21 padding floats are +0.
+ *   Morton order: lo_k, hi_k = the bounds of the selection's splats whose three coordinates are finite; per axis
+ *   q_k = min(1023, f2i_sat(norm(p_k, lo_k, hi_k) * 1024)); bit b of x, y, z goes to key bit 3b, 3b+1, 3b+2; a splat with a non-finite
+ *   coordinate gets the key 1<<30; the order is the stable ascending sort of the selection's ascending ids by key.
+ * THE FILE: a little-endian binary .ply with exactly this header, then C = ceil(n / 256) chunk records, n vertices and, at degree
+ * >= 1 only, n SH records:
+ *     ply / format binary_little_endian 1.0 / comment gsplat-packed 1 / element chunk C / property float min_x min_y min_z max_x max_y
+ *     max_z min_scale_x min_scale_y min_scale_z max_scale_x max_scale_y max_scale_z min_r min_g min_b max_r max_g max_b (one line
+ *     each) / element vertex n / property uint packed_position packed_rotation packed_scale packed_color / [element sh n /
+ *     property uchar f_rest_0 .. f_rest_{3K-1}] / end_header
+ * A loader requires the marker, these names and types in this order, C consistent with n, n below 2^31 and a file of exactly the
+ * implied size; anything else is GS_ERR_INVALID_ARGUMENT with a message naming the path and the defect, and nothing is allocated
+ * from a count before the size check.  A refused file leaves every output as it was.
+ * Host codec (no GPU, no context).  chunks: C x 18 floats; vertices: n x 4 words; sh: n x 3K bytes (may be NULL at degree 0);
+ * nonfinite (may be NULL): the carried floats that fin replaced plus the NaN logits.  gs_pack_load's records are n x 320 bytes,
+ * released with gs_ply_free. */
+#define GS_PACK_ORDER_INDEX 0   /* ascending splat index */
+#define GS_PACK_ORDER_MORTON 1  /* along a Morton curve through the selection's bounds: a chunk's splats are neighbours, its bounds tight */
+int32_t gs_pack_encode(const void* aos320, uint64_t n, int32_t sh_degree, float* chunks, uint32_t* vertices, uint8_t* sh, uint64_t* nonfinite);
+int32_t gs_pack_decode(const float* chunks, const uint32_t* vertices, const uint8_t* sh, uint64_t n, int32_t sh_degree, void* aos320);
+int32_t gs_pack_save(const char* path, const void* records, uint64_t n, int32_t sh_degree);
+int32_t gs_pack_load(const char* path, void** records, uint64_t* n, int32_t* sh_degree);
+int32_t gs_pack_logit_table(float out[256]);
+/* Resident scenes.  Each call drains the ring first, runs on the context's stream, returns when done and launches nothing in a
+ * frame.  gs_export_packed writes the splats with (s & mask) == value ((0, 0): all, also without GS_FLAG_SPLAT_STATE) in `order`:
+ * the whole selection is encoded on the device (at most 61 bytes per splat of device scratch) and streamed to the file through two
+ * pinned buffers; the host never holds the scene.  ids (may be NULL; room for every resident splat): record g of the file is splat
+ * ids[g].  info (may be NULL) is written on success.  A file that could not be completed is removed.  The scene is not changed.
+ * gs_upload_packed replaces the scene like gs_upload_ply, gs_append_packed appends like gs_append_ply (same refusals, installed
+ * only when complete, the old scene untouched by a failure); both read the file in trips of whole chunks and decode on the device.
+ * The decoded records are exactly gs_pack_decode's, the derived planes what gs_upload_splats of those records derives. */
+typedef struct gs_pack_info { /* 32 bytes */
+    uint64_t count;      /* splats written                                          */
+    uint64_t chunks;     /* ceil(count / 256)                                       */
+    uint64_t file_bytes; /* the whole file, header included                         */
+    uint64_t nonfinite;  /* carried floats that fin replaced, plus the NaN logits   */
+} gs_pack_info;
+int32_t gs_export_packed(gs_ctx* ctx, const char* path, uint32_t mask, uint32_t value, int32_t sh_degree, int32_t order, gs_pack_info* info,
+                         uint32_t* ids);
+int32_t gs_upload_packed(gs_ctx* ctx, const char* path, uint64_t* n);
+int32_t gs_append_packed(gs_ctx* ctx, const char* path, uint32_t new_state, uint64_t* first, uint64_t* m);
+
 /* ---- stand-alone stages, mirroring the reference's reusable classes ---------------------------- */
 /* GPUSorter.sort (radix_sort/sort.ts:341-350): stable ascending sort of n u32 keys with u32 payloads,
  * host buffers, in place.  values may be NULL (keys only, as testSort does: radix_sort/utils.ts:55-81). */
