@@ -8,9 +8,7 @@
 //
 // Every call drains the context's ring first (gs_wait), runs on the context's stream and returns when done, as gs_state_* do.
 // None of them launches anything in a frame: a context that never calls them launches exactly what it did before.
-#include <cerrno>
-#include <string>
-
+#include "gs_file_writer.h"
 #include "gs_runtime.h"
 
 // What every entry point does first (gs_runtime.h): the refusals, a filter that needs the plane among them, and the drain of the ring.
@@ -150,35 +148,7 @@ static std::string ply_header(uint64_t n, int K) {
     for (const char* nm : {"opacity", "scale_0", "scale_1", "scale_2", "rot_0", "rot_1", "rot_2", "rot_3"}) prop(nm);
     return h + "end_header\n";
 }
-// The file being written: closed by the destructor and, unless finish() succeeded, removed.
-struct PlyWriter {
-    const char* who;
-    std::string path;
-    FILE* fp = nullptr;
-    bool done = false;
-    PlyWriter(const char* w, const char* p) : who(w), path(p) {}
-    ~PlyWriter() {
-        if (fp) fclose(fp);
-        if (fp && !done) remove(path.c_str());
-    }
-    int32_t err(const char* what) const { return fail(GS_ERR_INVALID_ARGUMENT, "%s: cannot %s %s: %s", who, what, path.c_str(), strerror(errno)); }
-    int32_t open(uint64_t n, int K) {
-        fp = fopen(path.c_str(), "wb");
-        if (!fp) return err("create");
-        const std::string h = ply_header(n, K);
-        return fwrite(h.data(), 1, h.size(), fp) == h.size() ? GS_OK : err("write");
-    }
-    int32_t write(const uint32_t* words, size_t count) { return fwrite(words, 4, count, fp) == count ? GS_OK : err("write"); }
-    int32_t finish() { // (a full disk may only show when the buffered tail is flushed)
-        FILE* f = fp;
-        fp = nullptr;
-        if (fclose(f) == 0) { done = true; return GS_OK; }
-        const int32_t rc = err("write");
-        remove(path.c_str());
-        return rc;
-    }
-};
-static constexpr uint64_t kPlyChunk = 65536; // records per trip, as gs_upload_ply
+static constexpr uint64_t kPlyChunk = kStreamTrip; // records per trip, as a streamed upload
 
 GS_EXPORT int32_t gs_ply_save(const char* path, const void* records, uint64_t n, int32_t sh_degree) {
     if (!path) return fail(GS_ERR_INVALID_ARGUMENT, "gs_ply_save: null path");
@@ -186,22 +156,23 @@ GS_EXPORT int32_t gs_ply_save(const char* path, const void* records, uint64_t n,
     if (sh_degree < 0 || sh_degree > 3) return fail(GS_ERR_INVALID_ARGUMENT, "gs_ply_save: sh_degree %d is not 0..3 (%s)", sh_degree, path);
     const int K = (sh_degree + 1) * (sh_degree + 1) - 1;
     const size_t row = 17 + 3 * (size_t)K;
-    PlyWriter w("gs_ply_save", path);
-    int32_t rc = w.open(n, K);
+    FileWriter w("gs_ply_save", path);
+    int32_t rc = w.open(ply_header(n, K));
     if (rc != GS_OK) return rc;
     std::vector<uint32_t> rows((size_t)std::min<uint64_t>(std::max<uint64_t>(n, 1), kPlyChunk) * row);
     for (uint64_t first = 0; first < n; first += kPlyChunk) {
         const uint64_t m = std::min(kPlyChunk, n - first);
         ply_rows((const uint32_t*)records + first * 80, m, K, rows.data());
-        rc = w.write(rows.data(), (size_t)m * row);
+        rc = w.write(rows.data(), (size_t)m * row * 4);
         if (rc != GS_OK) return rc;
     }
     return w.finish();
 }
 
 // gs_upload_ply's mirror image: the unpack kernel fills a device staging buffer with at most 64 Ki records, the buffer is copied
-// to one of two pinned host buffers, and the host turns the PREVIOUS chunk into vertices and writes it while that copy runs.  Peak
-// host memory is the two pinned buffers (2 x 20 MB) and one chunk of vertices, whatever the size of the scene.
+// to one of the ring's two pinned host buffers, and the host turns the PREVIOUS chunk into vertices and writes it while that copy
+// runs (TripRing::drain, gs_runtime.h).  Peak host memory is the two pinned buffers (2 x 20 MB) and one chunk of vertices, whatever
+// the size of the scene.
 GS_EXPORT int32_t gs_export_ply(gs_ctx* c, const char* path, uint32_t mask, uint32_t value, int32_t sh_degree, uint64_t* n_out) {
     int32_t rc = edit_begin(c, "gs_export_ply", mask, value);
     if (rc != GS_OK) return rc;
@@ -217,37 +188,28 @@ GS_EXPORT int32_t gs_export_ply(gs_ctx* c, const char* path, uint32_t mask, uint
     const int K = (sh_degree + 1) * (sh_degree + 1) - 1;
     const size_t row = 17 + 3 * (size_t)K;
     const size_t chunk_bytes = (size_t)kPlyChunk * GS_SPLAT_RECORD_BYTES;
-    PlyWriter w("gs_export_ply", path);
-    rc = w.open(total, K);
+    FileWriter w("gs_export_ply", path);
+    rc = w.open(ply_header(total, K));
     if (rc != GS_OK) return rc;
-    DevBuf<> d_stage;
-    PinnedBuf<uint32_t> h_stage[2]; // (an early exit frees them under a copy still in flight: the free waits for the device)
-    Event done[2];
+    DevBuf<> d_stage; // one: the unpack of a chunk waits, in stream order, for the copy of the chunk before it out of this buffer
+    TripRing ring;
     HIP_TRY(hipMalloc(d_stage.out(), chunk_bytes));
-    for (int k = 0; k < 2; ++k) {
-        HIP_TRY(hipHostMalloc(h_stage[k].out(), chunk_bytes, hipHostMallocDefault));
-        HIP_TRY(hipEventCreateWithFlags(done[k].out(), hipEventDisableTiming));
-    }
+    rc = ring.init(chunk_bytes, false);
+    if (rc != GS_OK) return rc;
     std::vector<uint32_t> rows((size_t)kPlyChunk * row);
-    const uint64_t chunks = (total + kPlyChunk - 1) / kPlyChunk;
-    for (uint64_t it = 0; it <= chunks; ++it) {
-        if (it < chunks) { // enqueue chunk `it` (the kernel waits, in stream order, for the copy out of d_stage before it)
-            const int k = (int)(it & 1u);
-            const uint64_t first = it * kPlyChunk, m = std::min(kPlyChunk, total - first);
-            gs_launch_unpack(c->scene, c->n, sel, (uint32_t)first, (uint32_t)m, d_stage, nullptr, c->stream);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(h_stage[k], d_stage, (size_t)m * GS_SPLAT_RECORD_BYTES, hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipEventRecord(done[k], c->stream));
-        }
-        if (it >= 1) { // write chunk `it - 1`: its pinned buffer is not written again before chunk `it + 1` is enqueued
-            const int j = (int)((it - 1) & 1u);
-            const uint64_t first = (it - 1) * kPlyChunk, m = std::min(kPlyChunk, total - first);
-            HIP_TRY(hipEventSynchronize(done[j]));
-            ply_rows(h_stage[j], m, K, rows.data());
-            rc = w.write(rows.data(), (size_t)m * row);
-            if (rc != GS_OK) return rc;
-        }
-    }
+    auto records = [&](uint64_t it) { return std::min(kPlyChunk, total - it * kPlyChunk); };
+    rc = ring.drain((total + kPlyChunk - 1) / kPlyChunk, c->stream,
+                    [&](uint64_t it, unsigned char* h) {
+                        gs_launch_unpack(c->scene, c->n, sel, (uint32_t)(it * kPlyChunk), (uint32_t)records(it), d_stage, nullptr, c->stream);
+                        HIP_TRY(hipGetLastError());
+                        HIP_TRY(hipMemcpyAsync(h, d_stage, (size_t)records(it) * GS_SPLAT_RECORD_BYTES, hipMemcpyDeviceToHost, c->stream));
+                        return (int32_t)GS_OK;
+                    },
+                    [&](uint64_t it, unsigned char* h) {
+                        ply_rows((const uint32_t*)h, records(it), K, rows.data());
+                        return w.write(rows.data(), (size_t)records(it) * row * 4);
+                    });
+    if (rc != GS_OK) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     rc = w.finish();
     if (rc != GS_OK) return rc;

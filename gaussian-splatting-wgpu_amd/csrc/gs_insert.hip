@@ -98,56 +98,37 @@ GS_EXPORT int32_t gs_append_splats_device(gs_ctx* c, const void* d_aos320, uint6
     return append_common(c, "gs_append_splats_device", d_aos320, m, new_state, first, true);
 }
 
-GS_EXPORT int32_t gs_append_ply(gs_ctx* c, const char* path, uint32_t new_state, uint64_t* first, uint64_t* m_out) {
-    static const char who[] = "gs_append_ply";
+// A file behind the resident splats, over either source (PlySource, PackSource: gs_runtime.h).  The refusals in this order: new_state,
+// a null path, insert_check, what the source's open refuses, insert_fits; then the drain.
+template <class Source>
+static int32_t append_source(const char* who, gs_ctx* c, const char* path, uint32_t new_state, uint64_t* first, uint64_t* m_out) {
     int32_t rc = new_state_check(who, new_state);
     if (rc != GS_OK) return rc;
     if (!path) return fail(GS_ERR_INVALID_ARGUMENT, "%s: null path", who);
     rc = insert_check(c, who, new_state);
     if (rc != GS_OK) return rc;
-    PlySource src;
-    rc = ply_open(who, path, &src); // cannot be opened, a bad header, 2^31 vertices, a file shorter than the header says
+    Source src;
+    rc = src.open(who, path);
     if (rc != GS_OK) return rc;
-    if (src.L.stride > 0xFFFFu) return fail(GS_ERR_INVALID_ARGUMENT, "%s: vertex stride %u too large", who, src.L.stride);
-    const uint64_t m = src.L.vertex_count;
+    const uint64_t m = src.count();
     rc = insert_fits(c, who, m);
     if (rc != GS_OK) return rc;
     rc = resident_drain(c);
     if (rc != GS_OK) return rc;
     const uint32_t n_old = c->n;
     if (m) {
-        rc = insert_grow(c, m, new_state, [&](const GsScene& dst) { return ply_stream(who, c, src, dst, n_old); });
+        rc = insert_grow(c, m, new_state, [&](const GsScene& dst) { return src.stream(who, c, dst, n_old); });
         if (rc != GS_OK) return rc;
     }
     if (first) *first = n_old;
     if (m_out) *m_out = m;
     return GS_OK;
 }
-
-// gs_append_ply with the packed file's two halves (gs_pack.hip): the same refusals in the same order, the same install.
+GS_EXPORT int32_t gs_append_ply(gs_ctx* c, const char* path, uint32_t new_state, uint64_t* first, uint64_t* m_out) {
+    return append_source<PlySource>("gs_append_ply", c, path, new_state, first, m_out);
+}
 GS_EXPORT int32_t gs_append_packed(gs_ctx* c, const char* path, uint32_t new_state, uint64_t* first, uint64_t* m_out) {
-    static const char who[] = "gs_append_packed";
-    int32_t rc = new_state_check(who, new_state);
-    if (rc != GS_OK) return rc;
-    if (!path) return fail(GS_ERR_INVALID_ARGUMENT, "%s: null path", who);
-    rc = insert_check(c, who, new_state);
-    if (rc != GS_OK) return rc;
-    PackSource src;
-    rc = pack_open(who, path, &src); // cannot be opened, a header that is not exactly the format's, a size other than the header implies
-    if (rc != GS_OK) return rc;
-    const uint64_t m = src.L.n;
-    rc = insert_fits(c, who, m);
-    if (rc != GS_OK) return rc;
-    rc = resident_drain(c);
-    if (rc != GS_OK) return rc;
-    const uint32_t n_old = c->n;
-    if (m) {
-        rc = insert_grow(c, m, new_state, [&](const GsScene& dst) { return pack_stream(who, c, src, dst, n_old); });
-        if (rc != GS_OK) return rc;
-    }
-    if (first) *first = n_old;
-    if (m_out) *m_out = m;
-    return GS_OK;
+    return append_source<PackSource>("gs_append_packed", c, path, new_state, first, m_out);
 }
 
 GS_EXPORT int32_t gs_duplicate_splats(gs_ctx* c, uint32_t mask, uint32_t value, uint32_t new_state, uint64_t* first, uint64_t* m_out,

@@ -6,12 +6,13 @@
 // host; here the positions are resident, a cell grid is one radix sort of (cell, id) pairs away, and 4 bytes per splat come back.
 //
 // A count is: bounds of the finite sources (one pass, one word-sized read-back: the grid is chosen on the host), keys, the Onesweep
-// pair sort behind a private control block (as gs_sort_pairs_u32 drives it), records + keys + cell table, the same for the queries when
+// pair sort behind a private control block (private_sort, gs_runtime.h), records + keys + cell table, the same for the queries when
 // their filter differs, the candidates per workgroup of queries (second read-back: the budget and the slices), the query pass.
 // Every call drains the context's ring first (gs_wait), runs on the context's stream and returns when done.  None of them launches
 // anything in a frame: a context that never calls them launches exactly what it did before.
 #include <cmath>
 
+#include "gs_pack_math.h"
 #include "gs_runtime.h"
 
 static_assert(sizeof(gs_neigh) == 40 && offsetof(gs_neigh, max_candidates) == 32, "gs_neigh layout");
@@ -49,26 +50,26 @@ static void choose_grid(const float lo[3], const float hi[3], float radius, GsNe
     *edge = h;
 }
 
-static float key_value(uint32_t key) { // the inverse of the kernels' order-preserving map
-    const uint32_t b = (key >> 31) ? key ^ 0x80000000u : ~key;
-    float v;
-    memcpy(&v, &b, 4);
-    return v;
+int32_t neigh_bounds(gs_ctx* c, const uint8_t* state, uint32_t smask, uint32_t svalue, uint32_t qmask, uint32_t qvalue, uint32_t hb[16]) {
+    gs_ctx::Neigh& s = c->ng;
+    const int32_t rc = s.bounds.reserve(16);
+    if (rc != GS_OK) return rc;
+    for (int k = 0; k < 16; ++k) hb[k] = k < 3 ? 0xFFFFFFFFu : 0u; // (the three minima start at the largest key)
+    HIP_TRY(hipMemcpyAsync(s.bounds, hb, 16 * 4, hipMemcpyHostToDevice, c->stream));
+    gs_launch_neigh_bounds(state, c->scene, c->n, smask, svalue, qmask, qvalue, s.bounds, c->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(hb, s.bounds, 16 * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return GS_OK;
 }
 
 // One filter's members in cell order: keys, the pair sort, the records (and the cell table when `table`).
 static int32_t sorted_records(gs_ctx* c, const uint8_t* state, uint32_t mask, uint32_t value, const GsNeighGrid& g, void* rec, void* table) {
     gs_ctx::Neigh& s = c->ng;
     const uint32_t passes = (bits_of(g.none) + 7) / 8; // the keys reach `none` itself (no member)
-    const size_t ctl_sz = (sizeof(GsControl) + 255) & ~(size_t)255;
-    const size_t st_sz = (size_t)passes * gs_sort_tiles(c->n) * 256 * 4;
-    HIP_TRY(hipMemsetAsync(s.ctl, 0, ctl_sz + st_sz, c->stream));
-    GsControl* ctl = (GsControl*)s.ctl.get(); // view; the sort's status words follow it
-    s.n32 = c->n;
-    HIP_TRY(hipMemcpyAsync(&ctl->num_intersections, &s.n32, 4, hipMemcpyHostToDevice, c->stream));
-    gs_launch_neigh_keys(state, c->scene, c->n, mask, value, g, s.keysA, s.valsA, c->stream);
-    const GsSort plan{{s.keysA, s.valsA}, {s.keysB, s.valsB}, passes, 8, 0, false, false}; // 8-bit digits of the key itself, counted by the sort
-    const GsSortPair sorted = gs_launch_sort(plan, ctl, (uint32_t*)(s.ctl.get() + ctl_sz), c->n, std::max(c->opt.grid_persist, 1u), c->stream);
+    GsSortPair sorted;
+    const int32_t rc = private_sort(c, c->n, passes, [&] { gs_launch_neigh_keys(state, c->scene, c->n, mask, value, g, s.keysA, s.valsA, c->stream); }, &sorted);
+    if (rc != GS_OK) return rc;
     gs_launch_neigh_records(sorted.keys, sorted.vals, c->n, g, c->scene, rec, s.skeys, table, c->stream);
     HIP_TRY(hipGetLastError());
     return GS_OK;
@@ -87,27 +88,20 @@ int32_t neigh_build(gs_ctx* c, const char* who, float radius, uint32_t smask, ui
 
     // scratch (all of it before the first launch: a failed allocation leaves the planes as they were)
     const uint32_t nblocks_max = (n + 255u) / 256u;
-    const size_t ctl_sz = (sizeof(GsControl) + 255) & ~(size_t)255;
-    if ((rc = s.bounds.reserve(16)) != GS_OK || (rc = s.keysA.reserve(n)) != GS_OK || (rc = s.valsA.reserve(n)) != GS_OK ||
-        (rc = s.keysB.reserve(n)) != GS_OK || (rc = s.valsB.reserve(n)) != GS_OK || (rc = s.skeys.reserve(n)) != GS_OK || (rc = s.src.reserve((uint64_t)n * 16)) != GS_OK ||
-        (rc = s.sums.reserve(nblocks_max)) != GS_OK || (rc = s.ctl.reserve(ctl_sz + (size_t)4 * gs_sort_tiles(n) * 256 * 4)) != GS_OK)
+    if ((rc = private_sort_reserve(c, n, 4)) != GS_OK || (rc = s.skeys.reserve(n)) != GS_OK || (rc = s.src.reserve((uint64_t)n * 16)) != GS_OK ||
+        (rc = s.sums.reserve(nblocks_max)) != GS_OK || (!same && (rc = s.qry.reserve((uint64_t)n * 16)) != GS_OK))
         return rc;
-    if (!same && (rc = s.qry.reserve((uint64_t)n * 16)) != GS_OK) return rc;
 
-    // 1. the bounds of the finite sources and the four counts
-    uint32_t hb[16] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
-    HIP_TRY(hipMemcpyAsync(s.bounds, hb, sizeof(hb), hipMemcpyHostToDevice, c->stream));
-    gs_launch_neigh_bounds(b->state, c->scene, n, smask, svalue, qmask, qvalue, s.bounds, c->stream);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(hb, s.bounds, sizeof(hb), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    // 1. the bounds of the finite sources and the four counts (the bounds words are reserved there, before the launch)
+    uint32_t hb[16];
+    if ((rc = neigh_bounds(c, b->state, smask, svalue, qmask, qvalue, hb)) != GS_OK) return rc;
     b->sources = hb[6];
     b->queried = hb[8];
     b->nsrc = hb[7]; // with finite coordinates: the others have no neighbours
     b->nqry = hb[9];
     if (!b->nsrc || !b->nqry) return GS_OK;
     float lo[3], hi[3];
-    for (int k = 0; k < 3; ++k) { lo[k] = key_value(hb[k]); hi[k] = key_value(hb[3 + k]); }
+    for (int k = 0; k < 3; ++k) { lo[k] = pk_okey_value(hb[k]); hi[k] = pk_okey_value(hb[3 + k]); }
     GsNeighGrid& g = b->g;
     choose_grid(lo, hi, radius, &g, &b->cell_edge);
 
@@ -118,14 +112,13 @@ int32_t neigh_build(gs_ctx* c, const char* who, float radius, uint32_t smask, ui
     rc = sorted_records(c, b->state, smask, svalue, g, s.src, s.table);
     if (rc != GS_OK) return rc;
     uint32_t fault[2] = {0u, 0u};
-    const GsControl* ctl = (const GsControl*)s.ctl.get();
-    HIP_TRY(hipMemcpyAsync(&fault[0], &ctl->fault, 4, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = private_sort_fault(c, &fault[0])) != GS_OK) return rc;
     b->qrec = s.src;
     if (!same) {
         HIP_TRY(hipStreamSynchronize(c->stream)); // fault[0] is read before the control block is zeroed again
         rc = sorted_records(c, b->state, qmask, qvalue, g, s.qry, nullptr);
         if (rc != GS_OK) return rc;
-        HIP_TRY(hipMemcpyAsync(&fault[1], &ctl->fault, 4, hipMemcpyDeviceToHost, c->stream));
+        if ((rc = private_sort_fault(c, &fault[1])) != GS_OK) return rc;
         b->qrec = s.qry;
     }
 

@@ -1,19 +1,17 @@
 // gs_pack.hip -- the packed scenes' entry points: the host codec's forwards, the export of resident splats into the 16-byte chunked
-// format, the upload of such a file and the two halves of its stream (gs_append_packed is with the other insertions in
+// format, the upload of such a file and the file as a source (PackSource; gs_append_packed is with the other insertions in
 // gs_insert.hip: it shares their refusals and their install).  Part of the C ABI (include/gsplat/gs_abi.h "packed scenes"); the
 // kernels are in k_pack.hip, the codec in gs_pack_math.h, the file's header, writer and loader in gs_pack_host.hip.
 //
 // The reference has no counterpart: its only container is the float .ply (ply.ts:49-228), 248 bytes per splat at degree 3, and for a
 // scene streamed in from a file that file is the only host copy there would ever be.  An export here encodes the whole selection on
-// the device (at most 61 bytes per splat of scratch beside the scene) and streams the three sections to the file through two pinned
-// buffers; an upload reads the file in trips of whole chunks through two pinned buffers and decodes on the device.  Neither holds
-// the scene on the host.
+// the device (at most 61 bytes per splat of scratch beside the scene) and streams the three sections to the file; an upload reads the
+// file in trips of whole chunks and decodes on the device.  Both go through the one trip ring (TripRing, gs_runtime.h): neither
+// holds the scene on the host.
 //
 // Every resident call drains the context's ring first (resident_begin), runs on the context's stream and returns when done.  None
 // of them launches anything in a frame: a context that never calls them launches exactly what it did before.
-#include <cerrno>
-#include <string>
-
+#include "gs_file_writer.h"
 #include "gs_pack_math.h"
 #include "gs_runtime.h"
 
@@ -56,103 +54,28 @@ GS_EXPORT int32_t gs_pack_load(const char* path, void** records, uint64_t* n, in
 
 // ---- export -------------------------------------------------------------------------------------------------------------------------
 // The selection's ids (sel, ascending; null: every index) in Morton order: the bounds of its splats with three finite coordinates
-// (the neighbourhoods' bounds kernel under the selection's filter), the keys, the frame path's pair sort behind a private control
-// block, driven as gs_neigh.hip's sorted_records drives it (four 8-bit passes: the keys reach 1 << 30).  *out: the sorted values,
-// in the neighbourhoods' scratch.
+// (neigh_bounds under the selection's filter on both sides), the keys, the pair sort behind a private control block (private_sort,
+// gs_runtime.h; four 8-bit passes: the keys reach 1 << 30).  *out: the sorted values, in the neighbourhoods' scratch.
 static int32_t morton_order(gs_ctx* c, const char* who, uint32_t mask, uint32_t value, const uint32_t* sel, uint32_t m, const uint32_t** out) {
     gs_ctx::Neigh& s = c->ng;
     if (m >= (1u << 30)) return fail(GS_ERR_CAPACITY, "%s: %u splats, the Morton sort takes fewer than 2^30", who, m);
-    const uint32_t passes = 4;
-    const size_t ctl_sz = (sizeof(GsControl) + 255) & ~(size_t)255;
-    const size_t st_sz = (size_t)passes * gs_sort_tiles(m) * 256 * 4;
-    int32_t rc;
-    if ((rc = s.bounds.reserve(16)) != GS_OK || (rc = s.keysA.reserve(m)) != GS_OK || (rc = s.valsA.reserve(m)) != GS_OK ||
-        (rc = s.keysB.reserve(m)) != GS_OK || (rc = s.valsB.reserve(m)) != GS_OK || (rc = s.ctl.reserve(ctl_sz + st_sz)) != GS_OK)
-        return rc;
-    uint32_t hb[16] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
-    HIP_TRY(hipMemcpyAsync(s.bounds, hb, sizeof(hb), hipMemcpyHostToDevice, c->stream));
-    gs_launch_neigh_bounds((mask | value) ? c->scene.state : nullptr, c->scene, c->n, mask, value, mask, value, s.bounds, c->stream);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(hb, s.bounds, sizeof(hb), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    uint32_t hb[16];
+    int32_t rc = neigh_bounds(c, (mask | value) ? c->scene.state : nullptr, mask, value, mask, value, hb);
+    if (rc != GS_OK) return rc;
     GsPackBox box{};
     if (hb[7]) // (no splat with finite coordinates: every key is GS_PACK_KEY_LAST, the box is not read)
         for (int k = 0; k < 3; ++k) { box.lo[k] = pk_okey_value(hb[k]); box.hi[k] = pk_okey_value(hb[3 + k]); }
-    HIP_TRY(hipMemsetAsync(s.ctl, 0, ctl_sz + st_sz, c->stream));
-    GsControl* ctl = (GsControl*)s.ctl.get(); // view; the sort's status words follow it
-    s.n32 = m;
-    HIP_TRY(hipMemcpyAsync(&ctl->num_intersections, &s.n32, 4, hipMemcpyHostToDevice, c->stream));
-    gs_launch_pack_keys(c->scene, c->n, sel, m, box, s.keysA, s.valsA, c->stream);
-    const GsSort plan{{s.keysA, s.valsA}, {s.keysB, s.valsB}, passes, 8, 0, false, false}; // 8-bit digits of the key itself, counted by the sort
-    const GsSortPair sorted = gs_launch_sort(plan, ctl, (uint32_t*)(s.ctl.get() + ctl_sz), m, std::max(c->opt.grid_persist, 1u), c->stream);
+    GsSortPair sorted;
+    rc = private_sort(c, m, 4, [&] { gs_launch_pack_keys(c->scene, c->n, sel, m, box, s.keysA, s.valsA, c->stream); }, &sorted);
+    if (rc != GS_OK) return rc;
     HIP_TRY(hipGetLastError());
     uint32_t fault = 0;
-    HIP_TRY(hipMemcpyAsync(&fault, &ctl->fault, 4, hipMemcpyDeviceToHost, c->stream));
+    rc = private_sort_fault(c, &fault);
+    if (rc != GS_OK) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (fault) return fail(GS_ERR_DEVICE_FAULT, "%s: look-back spin bound exceeded in the Morton sort", who);
     *out = sorted.vals;
     return GS_OK;
-}
-
-// The file being written: closed by the destructor and, unless finish() succeeded, removed.
-namespace {
-struct PackWriter {
-    const char* who;
-    std::string path;
-    FILE* fp = nullptr;
-    bool done = false;
-    PackWriter(const char* w, const char* p) : who(w), path(p) {}
-    ~PackWriter() {
-        if (fp) fclose(fp);
-        if (fp && !done) remove(path.c_str());
-    }
-    int32_t err(const char* what) const { return fail(GS_ERR_INVALID_ARGUMENT, "%s: cannot %s %s: %s", who, what, path.c_str(), strerror(errno)); }
-    int32_t open(const std::string& header) {
-        fp = fopen(path.c_str(), "wb");
-        if (!fp) return err("create");
-        return fwrite(header.data(), 1, header.size(), fp) == header.size() ? GS_OK : err("write");
-    }
-    int32_t write(const void* p, size_t bytes) { return fwrite(p, 1, bytes, fp) == bytes ? GS_OK : err("write"); }
-    int32_t finish() { // (a full disk may only show when the buffered tail is flushed)
-        FILE* f = fp;
-        fp = nullptr;
-        if (fclose(f) == 0) { done = true; return GS_OK; }
-        const int32_t rc = err("write");
-        remove(path.c_str());
-        return rc;
-    }
-};
-// The two pinned bounce buffers of an export: `bytes` of device memory go to the file, the host writing trip k - 1 while trip k is
-// being copied (gs_export_ply's scheme).
-struct Bounce {
-    static constexpr size_t kTrip = (size_t)1 << 20; // 65 536 vertices
-    PinnedBuf<unsigned char> h[2]; // (an early exit frees them under a copy still in flight: the free waits for the device)
-    Event done[2];
-    int32_t init(size_t largest) {
-        for (int k = 0; k < 2; ++k) {
-            HIP_TRY(hipHostMalloc(h[k].out(), std::max<size_t>(std::min(largest, kTrip), 256), hipHostMallocDefault));
-            HIP_TRY(hipEventCreateWithFlags(done[k].out(), hipEventDisableTiming));
-        }
-        return GS_OK;
-    }
-    int32_t drain(const unsigned char* dev, size_t bytes, PackWriter& w, hipStream_t st) {
-        const size_t trips = (bytes + kTrip - 1) / kTrip;
-        for (size_t it = 0; it <= trips && trips; ++it) {
-            if (it < trips) {
-                const size_t at = it * kTrip, m = std::min(kTrip, bytes - at);
-                HIP_TRY(hipMemcpyAsync(h[it & 1], dev + at, m, hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipEventRecord(done[it & 1], st));
-            }
-            if (it >= 1) { // its pinned buffer is not written again before trip it + 1 is enqueued
-                const size_t at = (it - 1) * kTrip, m = std::min(kTrip, bytes - at);
-                HIP_TRY(hipEventSynchronize(done[(it - 1) & 1]));
-                const int32_t rc = w.write(h[(it - 1) & 1], m);
-                if (rc != GS_OK) return rc;
-            }
-        }
-        return GS_OK;
-    }
-};
 }
 
 GS_EXPORT int32_t gs_export_packed(gs_ctx* c, const char* path, uint32_t mask, uint32_t value, int32_t sh_degree, int32_t order, gs_pack_info* info,
@@ -195,15 +118,26 @@ GS_EXPORT int32_t gs_export_packed(gs_ctx* c, const char* path, uint32_t mask, u
     for (uint32_t b : bad) out.nonfinite += b;
     const std::string header = gs_pack_header(m, sh_degree);
     out.file_bytes = header.size() + C * 72 + (uint64_t)m * 16 + (uint64_t)m * 3 * K;
-    PackWriter w(who, path);
+    FileWriter w(who, path);
     rc = w.open(header);
     if (rc != GS_OK) return rc;
-    Bounce bounce;
-    rc = bounce.init(std::max<size_t>({(size_t)C * 72, (size_t)m * 16, (size_t)m * 3 * K})); // the largest section (or one trip)
+    // the three sections go to the file in trips of 1 MiB (65 536 vertices), the host writing one trip while the next is being copied
+    constexpr size_t kTrip = (size_t)1 << 20;
+    TripRing ring;
+    rc = ring.init(std::max<size_t>(std::min(std::max<size_t>({(size_t)C * 72, (size_t)m * 16, (size_t)m * 3 * K}), kTrip), 256), false);
     if (rc != GS_OK) return rc;
-    if ((rc = bounce.drain(enc.get() + chunk_at, (size_t)C * 72, w, c->stream)) != GS_OK) return rc;
-    if ((rc = bounce.drain(enc.get() + vert_at, (size_t)m * 16, w, c->stream)) != GS_OK) return rc;
-    if ((rc = bounce.drain(enc.get() + sh_at, (size_t)m * 3 * K, w, c->stream)) != GS_OK) return rc;
+    auto section = [&](size_t from, size_t bytes) {
+        auto part = [&](uint64_t it) { return std::min(kTrip, bytes - (size_t)it * kTrip); };
+        return ring.drain((bytes + kTrip - 1) / kTrip, c->stream,
+                          [&](uint64_t it, unsigned char* h) {
+                              HIP_TRY(hipMemcpyAsync(h, enc.get() + from + (size_t)it * kTrip, part(it), hipMemcpyDeviceToHost, c->stream));
+                              return (int32_t)GS_OK;
+                          },
+                          [&](uint64_t it, unsigned char* h) { return w.write(h, part(it)); });
+    };
+    if ((rc = section(chunk_at, (size_t)C * 72)) != GS_OK || (rc = section(vert_at, (size_t)m * 16)) != GS_OK ||
+        (rc = section(sh_at, (size_t)m * 3 * K)) != GS_OK)
+        return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     rc = w.finish();
     if (rc != GS_OK) return rc;
@@ -215,73 +149,48 @@ GS_EXPORT int32_t gs_export_packed(gs_ctx* c, const char* path, uint32_t mask, u
     return GS_OK;
 }
 
-// ---- upload: the two halves (gs_runtime.h), shared with gs_append_packed ------------------------------------------------------------
-int32_t pack_open(const char* who, const char* path, PackSource* src) {
-    src->fp = File(fopen(path, "rb"));
-    if (!src->fp) return fail(GS_ERR_INVALID_ARGUMENT, "%s: cannot open %s", who, path);
+// ---- upload: the packed file as a source (gs_runtime.h), shared with gs_append_packed ------------------------------------------------
+int32_t PackSource::open(const char* who, const char* path) {
+    fp = File(fopen(path, "rb"));
+    if (!fp) return fail(GS_ERR_INVALID_ARGUMENT, "%s: cannot open %s", who, path);
     unsigned char head[8192];
-    const size_t got = fread(head, 1, sizeof(head), src->fp);
-    if (fseek(src->fp, 0, SEEK_END) != 0) return fail(GS_ERR_INVALID_ARGUMENT, "%s: cannot seek in %s", who, path);
-    const long fsize = ftell(src->fp);
+    const size_t got = fread(head, 1, sizeof(head), fp);
+    if (fseek(fp, 0, SEEK_END) != 0) return fail(GS_ERR_INVALID_ARGUMENT, "%s: cannot seek in %s", who, path);
+    const long fsize = ftell(fp);
     char err[480] = "";
-    const int32_t rc = gs_pack_parse_header(who, path, head, got, (uint64_t)(fsize < 0 ? 0 : fsize), &src->L, err, sizeof(err));
+    const int32_t rc = gs_pack_parse_header(who, path, head, got, (uint64_t)(fsize < 0 ? 0 : fsize), &L, err, sizeof(err));
     return rc == GS_OK ? rc : fail(rc, "%s", err);
 }
 
-int32_t pack_stream(const char* who, gs_ctx* c, PackSource& src, const GsScene& dst, uint64_t first) {
-    const GsPackLayout& L = src.L;
-    FILE* const fp = src.fp;
+// A trip is its vertices, their whole chunks' records and their SH bytes, read from the file's three sections into one staging buffer.
+int32_t PackSource::stream(const char* who, gs_ctx* c, const GsScene& dst, uint64_t first) {
     const uint64_t n = L.n, K = (uint64_t)gs_pack_rest(L.degree), K3 = 3 * K;
-    const uint64_t CH = 65536; // vertices per trip: 256 whole chunks
-    const size_t stage_bytes = (size_t)(std::min<uint64_t>(CH, std::max<uint64_t>(n, 1)) * (16 + K3) + 256 * 72);
-    PinnedBuf<unsigned char> h_stage[2]; // (an early exit frees them under copies still in flight: both frees wait for the device)
-    DevBuf<unsigned char> d_stage[2];
+    TripRing ring;
+    int32_t rc = ring.init((size_t)(std::min(kStreamTrip, std::max<uint64_t>(n, 1)) * (16 + K3) + 256 * 72), true);
+    if (rc != GS_OK) return rc;
     DevBuf<float> d_table;
-    Event done[2];
-    for (int k = 0; k < 2; ++k) {
-        HIP_TRY(hipHostMalloc(h_stage[k].out(), stage_bytes, hipHostMallocDefault));
-        HIP_TRY(hipMalloc(d_stage[k].out(), stage_bytes));
-        HIP_TRY(hipEventCreateWithFlags(done[k].out(), hipEventDisableTiming));
-    }
     HIP_TRY(hipMalloc(d_table.out(), 256 * sizeof(float)));
     HIP_TRY(hipMemcpyAsync(d_table, gs_pack_logits(), 256 * sizeof(float), hipMemcpyHostToDevice, c->stream)); // the table as data
     auto section = [&](uint64_t at, void* to, size_t bytes) {
         return !bytes || (fseek(fp, (long)at, SEEK_SET) == 0 && fread(to, 1, bytes, fp) == bytes);
     };
-    uint32_t it = 0;
-    for (uint64_t v0 = 0; v0 < n; v0 += CH, ++it) {
-        const int k = (int)(it & 1u);
-        const uint64_t m = std::min<uint64_t>(CH, n - v0), cm = gs_pack_chunks(m);
+    rc = ring.feed((n + kStreamTrip - 1) / kStreamTrip, c->stream, [&](uint64_t it, unsigned char* h, unsigned char* d) {
+        const uint64_t v0 = it * kStreamTrip, m = std::min(kStreamTrip, n - v0), cm = gs_pack_chunks(m);
         const size_t chunk_at = (size_t)m * 16, sh_at = chunk_at + (size_t)cm * 72, bytes = sh_at + (size_t)(m * K3);
-        if (it >= 2) HIP_TRY(hipEventSynchronize(done[k])); // the copy out of this staging buffer two trips ago has finished
-        unsigned char* h = h_stage[k];
         if (!section(L.vertex_off + v0 * 16, h, (size_t)m * 16) || !section(L.chunk_off + (v0 / 256) * 72, h + chunk_at, (size_t)cm * 72) ||
             !section(L.sh_off + v0 * K3, h + sh_at, (size_t)(m * K3)))
             return fail(GS_ERR_INVALID_ARGUMENT, "%s: short read", who);
-        HIP_TRY(hipMemcpyAsync(d_stage[k], h, bytes, hipMemcpyHostToDevice, c->stream));
-        const unsigned char* d = d_stage[k];
+        HIP_TRY(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, c->stream));
         const GsPackTrip trip{(const uint4*)d, (const float*)(d + chunk_at), K ? d + sh_at : nullptr, d_table, (uint32_t)m, (uint32_t)K};
         gs_launch_pack_decode(trip, (uint32_t)(first + v0), dst, c->stream);
-        HIP_TRY(hipEventRecord(done[k], c->stream));
-    }
+        return (int32_t)GS_OK;
+    });
+    if (rc != GS_OK) return rc;
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
     return GS_OK;
 }
 
 GS_EXPORT int32_t gs_upload_packed(gs_ctx* c, const char* path, uint64_t* n_out) {
-    if (!c || !path) return fail(GS_ERR_INVALID_ARGUMENT, "gs_upload_packed: null argument");
-    PackSource src;
-    int32_t rc = pack_open("gs_upload_packed", path, &src);
-    if (rc != GS_OK) return rc;
-    const uint64_t n = src.L.n;
-    hipError_t he = hipSetDevice(c->cfg.device);
-    if (he != hipSuccess) return fail(GS_ERR_HIP, "hipSetDevice: %s", hipGetErrorString(he));
-    drop_shadows(c);
-    rc = scene_alloc(c, n);
-    if (rc != GS_OK) return rc;
-    rc = pack_stream("gs_upload_packed", c, src, c->scene, 0);
-    if (rc != GS_OK) return rc;
-    if (n_out) *n_out = n;
-    return GS_OK;
+    return upload_source<PackSource>("gs_upload_packed", c, path, n_out);
 }

@@ -154,83 +154,54 @@ GS_EXPORT int32_t gs_ply_load(const char* path, void** records, uint64_t* n_out,
 
 GS_EXPORT void gs_ply_free(void* records) { free(records); }
 
-// Streams a .ply straight into the resident scene arrays: the file is read in chunks of 64 Ki vertices into one of
+// Streams a .ply straight into the resident scene arrays: the file is read in trips of 64 Ki vertices into one of
 // two pinned staging buffers, copied to the device and converted THERE into the final layout (position planes, geometry and SH
-// records: gs_ply_chunk_kernel) while the next chunk is being read.  No N x 320-byte array exists on either side: peak host
-// memory is the two staging buffers (2 x 64 Ki x vertex stride, ~32 MB), whatever the size of the scene.  The reference builds
-// the whole packed buffer in JS first (ply.ts:204-228: "seconds to a couple of minutes", index.html:16).  Two callers share the two
-// halves below: gs_upload_ply streams into a new scene, gs_append_ply (gs_insert.hip) into the tail of a grown one.
-//
-// Opens the file, reads its header and refuses what cannot be streamed: a count of 2^31 or more, a file shorter than its header says.
-int32_t ply_open(const char* who, const char* path, PlySource* src) {
-    src->fp = File(fopen(path, "rb"));
-    if (!src->fp) return fail(GS_ERR_INVALID_ARGUMENT, "%s: cannot open %s", who, path);
+// records: gs_ply_chunk_kernel) while the next trip is being read (TripRing::feed, gs_runtime.h).  No N x 320-byte array exists on
+// either side: peak host memory is the two staging buffers (2 x 64 Ki x vertex stride, ~32 MB), whatever the size of the scene.  The
+// reference builds the whole packed buffer in JS first (ply.ts:204-228: "seconds to a couple of minutes", index.html:16).  The
+// callers are upload_source (gs_runtime.h) and append_source (gs_insert.hip): into a new scene, or into the tail of a grown one.
+int32_t PlySource::open(const char* who, const char* path) {
+    fp = File(fopen(path, "rb"));
+    if (!fp) return fail(GS_ERR_INVALID_ARGUMENT, "%s: cannot open %s", who, path);
     std::vector<unsigned char> head(1 << 16);
-    const size_t got = fread(head.data(), 1, head.size(), src->fp);
-    PlyLayout& L = src->L;
+    const size_t got = fread(head.data(), 1, head.size(), fp);
     int32_t rc = ply_parse_header(head.data(), got, L);
     if (rc != GS_OK) return rc;
-    fseek(src->fp, 0, SEEK_END);
-    const uint64_t fsize = (uint64_t)ftell(src->fp);
+    fseek(fp, 0, SEEK_END);
+    const uint64_t fsize = (uint64_t)ftell(fp);
     const uint64_t n = L.vertex_count;
     if (n >= (1ull << 31)) return fail(GS_ERR_INVALID_ARGUMENT, "%s: too many gaussians", who);
     if (fsize < L.data_off + n * (uint64_t)L.stride) return fail(GS_ERR_INVALID_ARGUMENT, "%s: vertex data truncated", who);
+    if (L.stride > 0xFFFFu) return fail(GS_ERR_INVALID_ARGUMENT, "%s: vertex stride %u too large", who, L.stride); // (GsPlyTable: u16 offsets)
     return GS_OK;
 }
 
-// The two-buffer stream: vertex v of the file becomes splat first + v of `dst` (a scene that has room for them), converted on the
-// device while the next chunk is being read.  Returns when the stream is done.
-int32_t ply_stream(const char* who, gs_ctx* c, PlySource& src, const GsScene& dst, uint64_t first) {
-    const PlyLayout& L = src.L;
-    FILE* const fp = src.fp;
+int32_t PlySource::stream(const char* who, gs_ctx* c, const GsScene& dst, uint64_t first) {
     const uint64_t n = L.vertex_count;
     if (L.degree < 3 && n) { // coefficients the file does not have stay 0 (the shader hard-codes 16: process_gaussians.wgsl:6)
         hipError_t e0 = hipMemsetAsync((char*)dst.sh + (size_t)first * 192, 0, (size_t)n * 192, c->stream);
         if (e0 != hipSuccess) return fail(GS_ERR_HIP, "hipMemsetAsync: %s", hipGetErrorString(e0));
     }
-    const uint64_t CH = 65536;
-    const size_t chunk_bytes = (size_t)CH * L.stride;
-    PinnedBuf<unsigned char> h_stage[2]; // (an early exit frees them under copies still in flight: both frees wait for the device)
-    DevBuf<unsigned char> d_stage[2];
-    Event done[2];
-    for (int k = 0; k < 2; ++k) {
-        HIP_TRY(hipHostMalloc(h_stage[k].out(), std::max<size_t>(chunk_bytes, 256), hipHostMallocDefault));
-        HIP_TRY(hipMalloc(d_stage[k].out(), std::max<size_t>(chunk_bytes, 256)));
-        HIP_TRY(hipEventCreateWithFlags(done[k].out(), hipEventDisableTiming));
-    }
+    TripRing ring;
+    int32_t rc = ring.init(std::max<size_t>((size_t)kStreamTrip * L.stride, 256), true);
+    if (rc != GS_OK) return rc;
     GsPlyTable tab;
     tab.stride = L.stride; tab.nsrc = (uint32_t)L.nsrc; tab.all_float = L.all_float ? 1u : 0u;
     for (int k = 0; k < L.nsrc; ++k) { tab.soff[k] = (uint16_t)L.soff[k]; tab.stype[k] = (uint8_t)L.stype[k]; tab.slot[k] = (uint8_t)L.slot[k]; }
-    if (L.stride > 0xFFFFu) return fail(GS_ERR_INVALID_ARGUMENT, "%s: vertex stride %u too large", who, L.stride);
     fseek(fp, (long)L.data_off, SEEK_SET);
-    uint32_t it = 0;
-    for (uint64_t v0 = 0; v0 < n; v0 += CH, ++it) {
-        const int k = (int)(it & 1u);
-        const uint64_t m = std::min<uint64_t>(CH, n - v0);
-        if (it >= 2) HIP_TRY(hipEventSynchronize(done[k])); // the copy out of this staging buffer two chunks ago has finished
-        if (fread(h_stage[k], 1, (size_t)(m * L.stride), fp) != (size_t)(m * L.stride)) return fail(GS_ERR_INVALID_ARGUMENT, "%s: short read", who);
-        HIP_TRY(hipMemcpyAsync(d_stage[k], h_stage[k], (size_t)(m * L.stride), hipMemcpyHostToDevice, c->stream));
-        gs_launch_ply_chunk(d_stage[k], (uint32_t)m, (uint32_t)(first + v0), tab, dst, c->stream);
-        HIP_TRY(hipEventRecord(done[k], c->stream));
-    }
+    rc = ring.feed((n + kStreamTrip - 1) / kStreamTrip, c->stream, [&](uint64_t it, unsigned char* h, unsigned char* d) {
+        const uint64_t v0 = it * kStreamTrip, m = std::min(kStreamTrip, n - v0);
+        if (fread(h, 1, (size_t)(m * L.stride), fp) != (size_t)(m * L.stride)) return fail(GS_ERR_INVALID_ARGUMENT, "%s: short read", who);
+        HIP_TRY(hipMemcpyAsync(d, h, (size_t)(m * L.stride), hipMemcpyHostToDevice, c->stream));
+        gs_launch_ply_chunk(d, (uint32_t)m, (uint32_t)(first + v0), tab, dst, c->stream);
+        return (int32_t)GS_OK;
+    });
+    if (rc != GS_OK) return rc;
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
     return GS_OK;
 }
 
 GS_EXPORT int32_t gs_upload_ply(gs_ctx* c, const char* path, uint64_t* n_out) {
-    if (!c || !path) return fail(GS_ERR_INVALID_ARGUMENT, "gs_upload_ply: null argument");
-    PlySource src;
-    int32_t rc = ply_open("gs_upload_ply", path, &src);
-    if (rc != GS_OK) return rc;
-    const uint64_t n = src.L.vertex_count;
-    hipError_t he = hipSetDevice(c->cfg.device);
-    if (he != hipSuccess) return fail(GS_ERR_HIP, "hipSetDevice: %s", hipGetErrorString(he));
-    drop_shadows(c);
-    rc = scene_alloc(c, n);
-    if (rc != GS_OK) return rc;
-    rc = ply_stream("gs_upload_ply", c, src, c->scene, 0);
-    if (rc != GS_OK) return rc;
-    if (n_out) *n_out = n;
-    return GS_OK;
+    return upload_source<PlySource>("gs_upload_ply", c, path, n_out);
 }

@@ -1,4 +1,4 @@
-// gs_runtime.h -- private to the runtime sources (gs_context / gs_frame / gs_readback / gs_state / gs_export / gs_insert / gs_snapshot / gs_xform / gs_coverage / gs_attr / gs_neigh / gs_cluster / gs_ply / gs_stages .hip):
+// gs_runtime.h -- private to the runtime sources (gs_context / gs_frame / gs_readback / gs_state / gs_export / gs_insert / gs_snapshot / gs_xform / gs_coverage / gs_attr / gs_neigh / gs_cluster / gs_pack / gs_ply / gs_stages .hip):
 //   the error channel (fail, HIP_TRY);
 //   the owners of HIP resources (Owned: DevBuf, PinnedBuf, Event, Stream, File) and Scratch, a device buffer that grows on demand;
 //   the context (gs_ctx, GsOptions, FrameNotes, GraphKey), the lists of its last frame (frame_lists) and sums over its ring (over_ring);
@@ -6,9 +6,11 @@
 //   resident_drain, resident_begin), the last frame waited for (last_frame), the staging of a canvas mask (stage_mask), the
 //   coverage planes (cover_planes), the neighbour count plane (neigh_plane), the cell grid a count and a labelling build
 //   (neigh_build, neigh_budget, neigh_slices), the cluster planes (cluster_planes), the splat edits' selection (edit_select), the
+//   bounds kernel's round trip (neigh_bounds), the pair sort behind a private control block (private_sort and its helpers), the
 //   check of a gs_attr (attr_check), the layout of a scene allocation (scene_layout, scene_install), the serial that tells one
-//   numbering of the resident splats from the next (gs_ctx::scene_serial, scene_new_serial: what a gs_snapshot is valid for) and a
-//   .ply being streamed (PlySource, ply_open, ply_stream) and a packed file being streamed (PackSource, pack_open, pack_stream).
+//   numbering of the resident splats from the next (gs_ctx::scene_serial, scene_new_serial: what a gs_snapshot is valid for), a file
+//   being streamed into the scene (PlySource, PackSource) and the two-buffer trip ring of every streamed call (TripRing).
+//   (The file an export writes, FileWriter, is in gs_file_writer.h: it needs no HIP.)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -328,6 +330,48 @@ void neigh_slices(const std::vector<unsigned long long>& sums, Launch launch) {
         b0 = b1;
     }
 }
+// gs_neigh.hip: the bounds kernel under a source and a query filter (state: the plane, or null when both are (0, 0)): seeds the 16
+// words, launches, reads them back into hb and synchronises.  hb[0..2] / [3..5]: pk_okey of the finite sources' lowest / highest
+// coordinates; hb[6..9]: sources, finite sources, queried, finite queried.
+int32_t neigh_bounds(gs_ctx* c, const uint8_t* state, uint32_t smask, uint32_t svalue, uint32_t qmask, uint32_t qvalue, uint32_t hb[16]);
+// The pair sort behind a private control block -- the frame path's instance sort outside a frame: 8-bit digits of the key itself,
+// counted by the sort.  private_sort_bytes: the control block and the status words of `passes` passes over n pairs that follow it.
+// private_sort_plan: the plan over four arrays.  gs_sort_pairs_u32 has no context and drives these two itself; a call on a context
+// uses private_sort, which on c->stream reserves c->ng's four arrays and ctl for n pairs (private_sort_reserve: a caller that must
+// not fail later reserves for its largest `passes` up front), zeroes the block, sets the count, calls keys() -- it enqueues what
+// writes ng.keysA / valsA -- and launches the sort; *sorted: the pair that holds the result.  private_sort_fault enqueues the read of
+// the block's fault word (set when a look-back exceeded its spin bound); it must be waited for before the next private_sort.
+static constexpr size_t kCtlBytes = (sizeof(GsControl) + 255) & ~(size_t)255;
+inline size_t private_sort_bytes(uint64_t n, uint32_t passes) { return kCtlBytes + (size_t)passes * gs_sort_tiles(n) * 256 * 4; }
+inline GsSort private_sort_plan(uint32_t* keysA, uint32_t* valsA, uint32_t* keysB, uint32_t* valsB, uint32_t passes) {
+    return GsSort{{keysA, valsA}, {keysB, valsB}, passes, 8, 0, false, false};
+}
+inline int32_t private_sort_reserve(gs_ctx* c, uint32_t n, uint32_t passes) {
+    gs_ctx::Neigh& s = c->ng;
+    int32_t rc;
+    if ((rc = s.keysA.reserve(n)) != GS_OK || (rc = s.valsA.reserve(n)) != GS_OK || (rc = s.keysB.reserve(n)) != GS_OK ||
+        (rc = s.valsB.reserve(n)) != GS_OK)
+        return rc;
+    return s.ctl.reserve(private_sort_bytes(n, passes));
+}
+template <class Keys>
+int32_t private_sort(gs_ctx* c, uint32_t n, uint32_t passes, Keys keys, GsSortPair* sorted) {
+    gs_ctx::Neigh& s = c->ng;
+    const int32_t rc = private_sort_reserve(c, n, passes);
+    if (rc != GS_OK) return rc;
+    HIP_TRY(hipMemsetAsync(s.ctl, 0, private_sort_bytes(n, passes), c->stream));
+    GsControl* ctl = (GsControl*)s.ctl.get(); // view; the sort's status words follow it
+    s.n32 = n;
+    HIP_TRY(hipMemcpyAsync(&ctl->num_intersections, &s.n32, 4, hipMemcpyHostToDevice, c->stream));
+    keys();
+    *sorted = gs_launch_sort(private_sort_plan(s.keysA, s.valsA, s.keysB, s.valsB, passes), ctl, (uint32_t*)(s.ctl.get() + kCtlBytes), n,
+                             std::max(c->opt.grid_persist, 1u), c->stream);
+    return GS_OK;
+}
+inline int32_t private_sort_fault(gs_ctx* c, uint32_t* fault) {
+    HIP_TRY(hipMemcpyAsync(fault, &((const GsControl*)c->ng.ctl.get())->fault, 4, hipMemcpyDeviceToHost, c->stream));
+    return GS_OK;
+}
 // gs_cluster.hip: the label and size planes of `c`, allocated and set to their initial reading (on `st`) by the first call that needs them
 int32_t cluster_planes(gs_ctx* c, hipStream_t st);
 // gs_export.hip: the splat edits' selection: counts the splats with (s & mask) == value and, with want_ids, leaves their indices,
@@ -345,20 +389,92 @@ struct PlyLayout {
     uint32_t soff[11 + 48], stype[11 + 48], slot[11 + 48];
     bool all_float = true;
 };
-// A file being streamed (gs_upload_ply, gs_append_ply).  ply_open: opens it, reads the header, refuses 2^31 vertices or more and
-// a file shorter than data_off + count * stride; allocates nothing on the device.  ply_stream: vertex v becomes splat first + v of
-// `dst` (the SH of those splats zeroed first when the file's degree is below 3), through two pinned and two device staging buffers
-// of 64 Ki vertices; returns when the stream is done.  `who` names the caller in the messages.
-struct PlySource { File fp; PlyLayout L; };
-int32_t ply_open(const char* who, const char* path, PlySource* src);
-int32_t ply_stream(const char* who, gs_ctx* c, PlySource& src, const GsScene& dst, uint64_t first);
-// gs_pack.hip: a packed file being streamed (gs_upload_packed, gs_append_packed), the two halves as for a .ply.  pack_open: opens it,
-// checks its header against its size (gs_pack_host.h) and allocates nothing on the device.  pack_stream: vertex v becomes splat
-// first + v of `dst`, in trips of 256 whole chunks through two pinned and two device staging buffers, decoded on the device; returns
-// when the stream is done.
-struct PackSource { File fp; GsPackLayout L; };
-int32_t pack_open(const char* who, const char* path, PackSource* src);
-int32_t pack_stream(const char* who, gs_ctx* c, PackSource& src, const GsScene& dst, uint64_t first);
+// A file being streamed into the scene, in two forms with the same three members (upload_source below and append_source, gs_insert.hip,
+// are written once over them).  open: opens the file, reads its header and refuses what cannot be streamed; allocates nothing on the
+// device.  count: its vertices.  stream: vertex v becomes splat first + v of `dst` (a scene that has room for them) in trips of
+// kStreamTrip vertices through a TripRing with device staging, converted on the device while the next trip is being read; returns
+// when the stream is done.  `who` names the caller in the messages.
+static constexpr uint64_t kStreamTrip = 65536; // vertices per trip: 256 whole chunks of a packed file
+// gs_ply.hip: a .ply.  Refused: 2^31 vertices or more, a vertex stride above 0xFFFF, a file shorter than data_off + count * stride.
+// stream zeroes the SH of the new splats first when the file's degree is below 3.
+struct PlySource {
+    File fp;
+    PlyLayout L;
+    int32_t open(const char* who, const char* path);
+    uint64_t count() const { return L.vertex_count; }
+    int32_t stream(const char* who, gs_ctx* c, const GsScene& dst, uint64_t first);
+};
+// gs_pack.hip: a packed file.  Refused: a header that is not exactly the format's, a size other than the header implies (gs_pack_host.h).
+struct PackSource {
+    File fp;
+    GsPackLayout L;
+    int32_t open(const char* who, const char* path);
+    uint64_t count() const { return L.n; }
+    int32_t stream(const char* who, gs_ctx* c, const GsScene& dst, uint64_t first);
+};
+// gs_upload_ply / gs_upload_packed: the file becomes the scene (the file is opened before anything of the context is dropped)
+template <class Source>
+int32_t upload_source(const char* who, gs_ctx* c, const char* path, uint64_t* n_out) {
+    if (!c || !path) return fail(GS_ERR_INVALID_ARGUMENT, "%s: null argument", who);
+    Source src;
+    int32_t rc = src.open(who, path);
+    if (rc != GS_OK) return rc;
+    hipError_t he = hipSetDevice(c->cfg.device);
+    if (he != hipSuccess) return fail(GS_ERR_HIP, "hipSetDevice: %s", hipGetErrorString(he));
+    drop_shadows(c);
+    rc = scene_alloc(c, src.count());
+    if (rc != GS_OK) return rc;
+    rc = src.stream(who, c, c->scene, 0);
+    if (rc != GS_OK) return rc;
+    if (n_out) *n_out = src.count();
+    return GS_OK;
+}
+// The two-buffer trip ring of every streamed call: two pinned host buffers and two events (with `device`, two device staging buffers
+// beside them), so that the host works on one trip while the device copies the other.  Peak host memory is the two buffers, whatever
+// the size of the scene.  An early exit of a caller frees the pinned buffers under a copy still in flight: the free waits for the device.
+struct TripRing {
+    PinnedBuf<unsigned char> h[2];
+    DevBuf<unsigned char> d[2];
+    Event done[2];
+    int32_t init(size_t bytes, bool device) {
+        for (int k = 0; k < 2; ++k) {
+            HIP_TRY(hipHostMalloc(h[k].out(), bytes, hipHostMallocDefault));
+            if (device) HIP_TRY(hipMalloc(d[k].out(), bytes));
+            HIP_TRY(hipEventCreateWithFlags(done[k].out(), hipEventDisableTiming));
+        }
+        return GS_OK;
+    }
+    // file -> device: trip(it, pinned, staging) fills the pinned buffer from the file and enqueues the copy and the kernel on `st`
+    template <class Trip>
+    int32_t feed(uint64_t trips, hipStream_t st, Trip trip) {
+        for (uint64_t it = 0; it < trips; ++it) {
+            const int k = (int)(it & 1u);
+            if (it >= 2) HIP_TRY(hipEventSynchronize(done[k])); // the copy out of this pinned buffer two trips ago has finished
+            const int32_t rc = trip(it, h[k].get(), d[k].get());
+            if (rc != GS_OK) return rc;
+            HIP_TRY(hipEventRecord(done[k], st));
+        }
+        return GS_OK;
+    }
+    // device -> file: enqueue(it, pinned) enqueues the kernel and the copy into the pinned buffer on `st`; consume(it, pinned) writes
+    // trip it - 1 while that copy runs (its pinned buffer is not written again before trip it + 1 is enqueued).  The last trip is
+    // consumed before the call returns.
+    template <class Enqueue, class Consume>
+    int32_t drain(uint64_t trips, hipStream_t st, Enqueue enqueue, Consume consume) {
+        for (uint64_t it = 0; it <= trips && trips; ++it) {
+            int32_t rc;
+            if (it < trips) {
+                if ((rc = enqueue(it, h[it & 1u].get())) != GS_OK) return rc;
+                HIP_TRY(hipEventRecord(done[it & 1u], st));
+            }
+            if (it >= 1) {
+                HIP_TRY(hipEventSynchronize(done[(it - 1) & 1u]));
+                if ((rc = consume(it - 1, h[(it - 1) & 1u].get())) != GS_OK) return rc;
+            }
+        }
+        return GS_OK;
+    }
+};
 // gs_attr.hip: the refusals of a gs_attr (null, struct_size, kind, a non-finite p of the kinds that read it) in `who`'s name; *dev:
 // its parameters as the kernels take them.  attr_needs_cover: the kind reads the coverage planes (cover_planes first)
 int32_t attr_check(const char* who, const gs_attr* a, GsAttrDev* dev);

@@ -12,24 +12,22 @@ GS_EXPORT int32_t gs_sort_pairs_u32(int32_t device, uint32_t* keys, uint32_t* va
     if (n == 0) return GS_OK;
     HIP_TRY(hipSetDevice(device));
     const uint32_t passes = (key_bits + 7) / 8;
-    const size_t kb = (size_t)n * 4;
-    const size_t ctl_sz = (sizeof(GsControl) + 255) & ~(size_t)255;
-    const size_t st_sz = (size_t)passes * gs_sort_tiles(n) * 256 * 4;
+    const size_t kb = (size_t)n * 4, ctl_bytes = private_sort_bytes(n, passes);
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, device));
     DevBuf<uint32_t> kA, vA, kB, vB;
     DevBuf<> ctl_mem;
     HIP_TRY(hipMalloc(kA.out(), kb)); HIP_TRY(hipMalloc(vA.out(), kb)); HIP_TRY(hipMalloc(kB.out(), kb)); HIP_TRY(hipMalloc(vB.out(), kb));
-    HIP_TRY(hipMalloc(ctl_mem.out(), ctl_sz + st_sz));
-    HIP_TRY(hipMemset(ctl_mem, 0, ctl_sz + st_sz));
+    HIP_TRY(hipMalloc(ctl_mem.out(), ctl_bytes));
+    HIP_TRY(hipMemset(ctl_mem, 0, ctl_bytes));
     HIP_TRY(hipMemcpy(kA, keys, kb, hipMemcpyHostToDevice));
     if (values) HIP_TRY(hipMemcpy(vA, values, kb, hipMemcpyHostToDevice));
     else HIP_TRY(hipMemset(vA, 0, kb));
     GsControl* ctl = (GsControl*)ctl_mem.get(); // view into ctl_mem; the sort's status words follow it
     const uint32_t n32 = (uint32_t)n;
     HIP_TRY(hipMemcpy(&ctl->num_intersections, &n32, 4, hipMemcpyHostToDevice));
-    const GsSort plan{{kA, vA}, {kB, vB}, passes, 8, 0, false, false}; // 8-bit digits of the key itself, counted by the sort
-    const GsSortPair sorted = gs_launch_sort(plan, ctl, (uint32_t*)((char*)ctl_mem.get() + ctl_sz), n32, (uint32_t)prop.multiProcessorCount * 4, nullptr);
+    const GsSortPair sorted = gs_launch_sort(private_sort_plan(kA, vA, kB, vB, passes), ctl, (uint32_t*)((char*)ctl_mem.get() + kCtlBytes), n32,
+                                             (uint32_t)prop.multiProcessorCount * 4, nullptr);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     uint32_t fault = 0;
@@ -47,8 +45,7 @@ GS_EXPORT int32_t gs_exclusive_scan_u32(int32_t device, uint32_t* data, uint64_t
     if (n == 0) return GS_OK;
     HIP_TRY(hipSetDevice(device));
     const size_t kb = (size_t)n * 4;
-    const size_t ctl_sz = (sizeof(GsControl) + 255) & ~(size_t)255;
-    const size_t st_sz = ((size_t)gs_scan_blocks((uint32_t)n) + 1) * 8;
+    const size_t ctl_sz = kCtlBytes, st_sz = ((size_t)gs_scan_blocks((uint32_t)n) + 1) * 8;
     DevBuf<uint32_t> in, out;
     DevBuf<> ctl_mem;
     HIP_TRY(hipMalloc(in.out(), kb)); HIP_TRY(hipMalloc(out.out(), kb)); HIP_TRY(hipMalloc(ctl_mem.out(), ctl_sz + st_sz));

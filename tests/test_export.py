@@ -9,6 +9,7 @@ bytes) -- every tap and the image, bit for bit.
 import ctypes
 import functools
 import os
+import subprocess
 
 import numpy as np
 import pytest
@@ -16,7 +17,7 @@ import pytest
 from conftest import scene
 import export_restate as er
 import state_restate as sr
-from support import (F, FRAME_CASES, NODE, TAPS, code_of, frame_taps, guarded, hidden_plane, host_sources, in_region, is_fill, mk, raw_export, run_node,
+from support import (F, FRAME_CASES, NODE, ROOT, TAPS, code_of, frame_taps, guarded, hidden_plane, host_sources, in_region, is_fill, mk, raw_export, run_node,
                      special, special_records, state_ref, state_scene)
 
 _mk = functools.partial(mk, exact=True, state=True)
@@ -113,6 +114,26 @@ def test_ply_save_errors(tmp_path):
     assert not os.path.exists(missing) and not os.path.exists(os.path.dirname(missing))
     assert L.gs_ply_save(good, None, 0, 3) == 0  # no records: a header alone
     assert er.parse_ply_header(open(good.decode(), "rb").read())[0] == 0
+
+
+def test_sanitized_file_writer(tmp_path):
+    """tools/file_check: the writer every export shares (csrc/gs_file_writer.h) compiled alone with -fsanitize=address,undefined: a
+    finished file is the header and the bytes written, an unfinished one is removed, a path that cannot be created is refused with
+    `cannot create` and leaves nothing, a second writer replaces the first file.  Skipped where the sanitizer runtime is not installed."""
+    probe = tmp_path / "probe.cpp"
+    probe.write_text("int main() { return 0; }\n")
+    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
+    if subprocess.run(["g++"] + san + [str(probe), "-o", str(tmp_path / "probe")], capture_output=True).returncode != 0:
+        pytest.skip("the sanitizer runtime is not installed")
+    exe = str(tmp_path / "file_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall"] + san +
+                          ["-I", os.path.join(ROOT, "gaussian-splatting-wgpu_amd", "csrc"), os.path.join(ROOT, "tools", "file_check", "main.cpp"), "-o", exe])
+    work = tmp_path / "work"
+    work.mkdir()
+    out = subprocess.run([exe, str(work)], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    assert "file_check ok" in out.stdout
+    assert os.listdir(work) == []
 
 
 # ---- GPU --------------------------------------------------------------------------------------------------------------------------
@@ -494,6 +515,23 @@ def test_export_ply(tmp_path):
     pb = str(tmp_path / "big.ply")
     assert b.save_ply(pb) == n
     np.testing.assert_array_equal(er.bits(_abi.load_ply(pb)[0]), er.bits(er.zero_padding(big)))
+    b.destroy()
+
+
+@pytest.mark.gpu
+def test_export_ply_three_trips(tmp_path):
+    """131 329 = 2 x 65 536 + 257 distinct records exported whole: three trips of the export's ring, so the first pinned buffer is
+    used again, and a last trip of one whole chunk of 256 and one splat.  Read back, the file equals the zero-padded records bit for bit."""
+    from gsplat import _abi
+    n = 2 * 65536 + 257
+    big = np.tile(special_records(10000), (14, 1))[:n].copy()
+    big[:, 17] = np.arange(n, dtype=F)  # every record distinct: a record in the wrong place, or from the wrong trip, shows
+    b = _mk(big, 64, 64, 8, state=False)
+    pb = str(tmp_path / "three.ply")
+    assert b.save_ply(pb) == n
+    back, deg = _abi.load_ply(pb)
+    assert deg == 3 and back.shape == (n, 80)
+    np.testing.assert_array_equal(er.bits(back), er.bits(er.zero_padding(big)))
     b.destroy()
 
 

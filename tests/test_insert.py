@@ -430,6 +430,28 @@ def test_append_ply(tmp_path):
     r.destroy()
 
 
+@pytest.mark.gpu
+def test_append_ply_three_trips(tmp_path):
+    """A .ply of 131 329 = 2 x 65 536 + 257 vertices behind 300 resident splats: three trips of the stream, so its first staging
+    buffers are used again after the wait for the trip two before, and a last trip of 257.  The context equals one built by
+    insert.append of the records (the same ones tests/test_packed.py appends packed): records, ids, first, state bytes, splat count."""
+    from gsplat import _abi, insert, synth
+    n = 2 * 65536 + 257
+    big = cached(("packed_plain", n), lambda: synth.bicycle_like(n))
+    old, plane = np.ascontiguousarray(scene(10000)[:300]), old_plane(300)
+    path = str(tmp_path / "three.ply")
+    _abi.save_ply(path, big, 3)
+    r, fresh = _mk(old, 64, 64, 8), _mk(old, 64, 64, 8)
+    for x in (r, fresh):
+        x.write_state(plane)
+    assert insert.append_ply(r, path, NEW) == (300, n) == insert.append(fresh, big, NEW)
+    want_rec, want_state, _, _ = ir.appended(old, plane, big, NEW)
+    held(r, want_rec, want_state)
+    held(fresh, want_rec, want_state)
+    fresh.destroy()
+    r.destroy()
+
+
 # ---- rules -----------------------------------------------------------------------------------------------------------------------
 def _header_only_ply(path, n, names):
     with open(path, "wb") as f:

@@ -476,6 +476,66 @@ def test_more_than_one_trip(tmp_path):
     r.destroy()
 
 
+THREE = 2 * 65536 + 257  # three trips of every 65 536-vertex stream: the first buffer is used again; the last is a whole chunk and one splat
+
+
+def _three_trips():
+    from gsplat import synth
+    return cached(("packed_plain", THREE), lambda: synth.bicycle_like(THREE))
+
+
+@pytest.mark.gpu
+def test_three_trips(tmp_path):
+    """131 329 splats: the vertex section is three trips of the export's 1 MiB ring and the SH section at degree 3 six, so both pinned
+    buffers are written again after the host has consumed them; the loader's staging makes three trips, the last of one whole chunk
+    and one splat.  Both files equal the restatement's byte for byte, ids included; the uploaded scene equals the restated decode."""
+    from gsplat import _abi, packed
+    n = THREE
+    rec = _three_trips()
+    assert (n * 16 + (1 << 20) - 1) >> 20 == 3 and (n * 45 + (1 << 20) - 1) >> 20 == 6 and n % 65536 == 257
+    r = _mk(rec, 64, 64, 8, state=False)
+    path = tmp_path / "three.packed.ply"
+    want = er.zero_padding(rec)
+    info, ids, raw = _export(r, path, (0, 0), 3, _abi.GS_PACK_ORDER_INDEX)
+    np.testing.assert_array_equal(ids, np.arange(n, dtype=U))
+    _same_file(raw, want, 3, info, False)
+    order = pr.morton_order(want[:, 0:3])
+    info, ids, raw = _export(r, path, (0, 0), 1, _abi.GS_PACK_ORDER_MORTON)
+    np.testing.assert_array_equal(ids, order.astype(U))
+    _same_file(raw, want[order], 1, info, False)
+    m, d, chunks, verts, sh = pr.split_file(raw)
+    assert packed.upload(r, path) == n
+    np.testing.assert_array_equal(pr.bits(raw_export(r, 0, 0, False)[0]), pr.bits(pr.decode(chunks, verts, sh, 1, table())))
+    r.destroy()
+
+
+@pytest.mark.gpu
+def test_append_packed_three_trips(tmp_path):
+    """A packed file of 131 329 splats (degree 3: the largest trips) behind 300 resident ones: the context equals one built by
+    insert.append of the decoded records -- records, ids, first, state bytes and splat count."""
+    from gsplat import insert, packed
+    n = THREE
+    head = np.ascontiguousarray(_plain(300))
+    path = tmp_path / "tail.packed.ply"
+    packed.save_records(path, _three_trips(), 3)
+    m, d, chunks, verts, sh = pr.split_file(path.read_bytes())
+    decoded = pr.decode(chunks, verts, sh, 3, table())
+    r, fresh = _mk(head, 64, 64, 8), _mk(head, 64, 64, 8)
+    for x in (r, fresh):
+        x.write_state(plane_of(300))
+    assert packed.append(r, path, NEW) == (300, n) == insert.append(fresh, decoded, NEW)
+    assert r.numGaussians == 300 + n == r.stats()["num_gaussians"] == fresh.stats()["num_gaussians"]
+    (a, ai), (b, bi) = raw_export(r, 0, 0, True), raw_export(fresh, 0, 0, True)
+    np.testing.assert_array_equal(pr.bits(a), pr.bits(b))
+    np.testing.assert_array_equal(pr.bits(a[300:]), pr.bits(decoded))
+    np.testing.assert_array_equal(ai, bi)
+    np.testing.assert_array_equal(ai, np.arange(300 + n, dtype=U))
+    np.testing.assert_array_equal(r.read_state(), np.concatenate([plane_of(300), np.full(n, NEW, np.uint8)]))
+    np.testing.assert_array_equal(r.read_state(), fresh.read_state())
+    fresh.destroy()
+    r.destroy()
+
+
 @pytest.mark.gpu
 def test_append_packed(tmp_path):
     """257 packed splats behind 300 resident ones: the context equals one built by insert.append of the decoded records (records,
