@@ -18,8 +18,8 @@ ARCH = "gfx950"
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC", "-fvisibility=hidden",
          "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result"]
 FILE_FLAGS = {}  # per-file flags (none at present)
-SOURCES = ["k_preprocess.hip", "k_binning.hip", "k_gsort.hip", "k_rows.hip", "k_sort.hip", "k_blend.hip", "k_pick.hip", "k_state.hip", "k_export.hip", "k_insert.hip", "k_snapshot.hip", "k_xform.hip", "k_grade.hip", "k_coverage.hip", "k_attr.hip", "k_neigh.hip", "k_cluster.hip", "k_pack.hip",
-           "gs_context.hip", "gs_frame.hip", "gs_readback.hip", "gs_state.hip", "gs_export.hip", "gs_insert.hip", "gs_snapshot.hip", "gs_xform.hip", "gs_xform_math.hip", "gs_grade.hip", "gs_grade_math.hip", "gs_coverage.hip", "gs_attr.hip", "gs_neigh.hip", "gs_cluster.hip", "gs_pack.hip", "gs_pack_host.hip", "gs_ply.hip", "gs_stages.hip"]
+SOURCES = ["k_preprocess.hip", "k_binning.hip", "k_gsort.hip", "k_rows.hip", "k_sort.hip", "k_blend.hip", "k_pick.hip", "k_state.hip", "k_export.hip", "k_insert.hip", "k_snapshot.hip", "k_xform.hip", "k_grade.hip", "k_coverage.hip", "k_attr.hip", "k_neigh.hip", "k_cluster.hip", "k_knn.hip", "k_pack.hip",
+           "gs_context.hip", "gs_frame.hip", "gs_readback.hip", "gs_state.hip", "gs_export.hip", "gs_insert.hip", "gs_snapshot.hip", "gs_xform.hip", "gs_xform_math.hip", "gs_grade.hip", "gs_grade_math.hip", "gs_coverage.hip", "gs_attr.hip", "gs_neigh.hip", "gs_cluster.hip", "gs_knn.hip", "gs_pack.hip", "gs_pack_host.hip", "gs_ply.hip", "gs_stages.hip"]
 
 
 def _stale(target, deps):

@@ -129,11 +129,13 @@ void gs_launch_attr_values(uint32_t kind, const GsScene& s, const void* cov, uin
 // last.  The {start, end} table has `blocks` = none >> shift entries, one per 2^shift consecutive keys (shift 0: one per cell).
 struct GsNeighGrid { float lo[3]; float inv_h; uint32_t g[3]; uint32_t bx, bxy, shift, blocks, none; };
 // out: 16 words the caller initialises ([0..2] all ones, the rest 0): min / max order-preserving keys of x, y, z over the finite
-// sources, then sources, finite sources, queries, finite queries.  state null: every splat passes both filters.
+// sources, then sources, finite sources, queries, finite queries.  state null: every splat passes both filters.  gate (u32[n], or
+// null: no gate): a splat is a query -- in keys: a member -- only if its word there is +inf's (a refining gs_knn_search; null for
+// every other caller).
 void gs_launch_neigh_bounds(const uint8_t* state, const GsScene& s, uint32_t n, uint32_t smask, uint32_t svalue, uint32_t qmask, uint32_t qvalue,
-                            uint32_t* out, hipStream_t st);
-void gs_launch_neigh_keys(const uint8_t* state, const GsScene& s, uint32_t n, uint32_t mask, uint32_t value, const GsNeighGrid& g, uint32_t* keys,
-                          uint32_t* vals, hipStream_t st);
+                            const uint32_t* gate, uint32_t* out, hipStream_t st);
+void gs_launch_neigh_keys(const uint8_t* state, const GsScene& s, uint32_t n, uint32_t mask, uint32_t value, const uint32_t* gate, const GsNeighGrid& g,
+                          uint32_t* keys, uint32_t* vals, hipStream_t st);
 // the sorted pairs -> {x, y, z, id} records (16 B, n of them allocated) and, with `table` (blocks x {start, end}, zeroed), the
 // members' keys in sorted order (skeys, n allocated) and each block's run
 void gs_launch_neigh_records(const uint32_t* keys, const uint32_t* vals, uint32_t n, const GsNeighGrid& g, const GsScene& s, void* rec, uint32_t* skeys,
@@ -168,6 +170,19 @@ void gs_launch_cluster_commit(const uint32_t* parent, const uint32_t* count, uin
 void gs_launch_cluster_seeds(const uint8_t* state, const uint32_t* labels, uint32_t n, uint32_t mask, uint32_t value, uint32_t* flag, hipStream_t st);
 void gs_launch_state_cluster_linked(uint8_t* state, const uint32_t* labels, uint32_t n, const uint32_t* flag, uint32_t op, uint32_t bits, uint32_t where_mask,
                                     uint32_t where_value, unsigned long long* matched, hipStream_t st);
+// k_knn.hip: nearest neighbours (gs_knn.hip) over the neighbourhoods' grid, records and slices.
+// a whole search's start: dist2[i] = +inf for a splat that passes (mask, value) (state null: every splat), NaN 0x7FC00000 for the
+// others; nearest[i] = GS_KNN_NONE
+void gs_launch_knn_init(const uint8_t* state, uint32_t n, uint32_t mask, uint32_t value, uint32_t* dist2, uint32_t* nearest, hipStream_t st);
+// the query pass over workgroups [first_block, first_block + blocks) of 256 sorted queries: dist2[id] = the k-th smallest accepted d2
+// or +inf, nearest[id] = the smallest id at the smallest accepted d2 or GS_KNN_NONE; *unresolved += the queries that end +inf.
+// k: 1 .. GS_KNN_MAX_K (k KB of dynamic LDS)
+void gs_launch_knn_query(const void* qrec, uint32_t nq, uint32_t first_block, uint32_t blocks, const void* srec, const uint32_t* skeys, const void* table,
+                         uint32_t nrec, const GsNeighGrid& g, float r2, uint32_t k, uint32_t n, uint32_t* dist2, uint32_t* nearest, uint32_t* unresolved,
+                         hipStream_t st);
+// gs_state_knn: the state pass with the float-range membership (v >= lo && v <= hi) == inside over the dist2 plane read as words
+void gs_launch_state_knn(uint8_t* state, const uint32_t* dist2, uint32_t n, float lo, float hi, uint32_t inside, uint32_t op, uint32_t bits,
+                         uint32_t where_mask, uint32_t where_value, unsigned long long* matched, hipStream_t st);
 // k_export.hip: the splat edits (gs_export.hip).  Selection = splats with (s & mask) == value in ascending order: `counts` holds
 // gs_select_blocks(n) + 1 words (one per 1024 splats; after the launch their exclusive prefix, the total last), `ids` the total.
 uint32_t gs_select_blocks(uint32_t n);

@@ -50,13 +50,13 @@ static void choose_grid(const float lo[3], const float hi[3], float radius, GsNe
     *edge = h;
 }
 
-int32_t neigh_bounds(gs_ctx* c, const uint8_t* state, uint32_t smask, uint32_t svalue, uint32_t qmask, uint32_t qvalue, uint32_t hb[16]) {
+int32_t neigh_bounds(gs_ctx* c, const uint8_t* state, uint32_t smask, uint32_t svalue, uint32_t qmask, uint32_t qvalue, uint32_t hb[16], const uint32_t* gate) {
     gs_ctx::Neigh& s = c->ng;
     const int32_t rc = s.bounds.reserve(16);
     if (rc != GS_OK) return rc;
     for (int k = 0; k < 16; ++k) hb[k] = k < 3 ? 0xFFFFFFFFu : 0u; // (the three minima start at the largest key)
     HIP_TRY(hipMemcpyAsync(s.bounds, hb, 16 * 4, hipMemcpyHostToDevice, c->stream));
-    gs_launch_neigh_bounds(state, c->scene, c->n, smask, svalue, qmask, qvalue, s.bounds, c->stream);
+    gs_launch_neigh_bounds(state, c->scene, c->n, smask, svalue, qmask, qvalue, gate, s.bounds, c->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(hb, s.bounds, 16 * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -64,11 +64,11 @@ int32_t neigh_bounds(gs_ctx* c, const uint8_t* state, uint32_t smask, uint32_t s
 }
 
 // One filter's members in cell order: keys, the pair sort, the records (and the cell table when `table`).
-static int32_t sorted_records(gs_ctx* c, const uint8_t* state, uint32_t mask, uint32_t value, const GsNeighGrid& g, void* rec, void* table) {
+static int32_t sorted_records(gs_ctx* c, const uint8_t* state, uint32_t mask, uint32_t value, const uint32_t* gate, const GsNeighGrid& g, void* rec, void* table) {
     gs_ctx::Neigh& s = c->ng;
     const uint32_t passes = (bits_of(g.none) + 7) / 8; // the keys reach `none` itself (no member)
     GsSortPair sorted;
-    const int32_t rc = private_sort(c, c->n, passes, [&] { gs_launch_neigh_keys(state, c->scene, c->n, mask, value, g, s.keysA, s.valsA, c->stream); }, &sorted);
+    const int32_t rc = private_sort(c, c->n, passes, [&] { gs_launch_neigh_keys(state, c->scene, c->n, mask, value, gate, g, s.keysA, s.valsA, c->stream); }, &sorted);
     if (rc != GS_OK) return rc;
     gs_launch_neigh_records(sorted.keys, sorted.vals, c->n, g, c->scene, rec, s.skeys, table, c->stream);
     HIP_TRY(hipGetLastError());
@@ -78,11 +78,14 @@ static int32_t sorted_records(gs_ctx* c, const uint8_t* state, uint32_t mask, ui
 // Steps 1 to 3 of a count, which a labelling (gs_cluster.hip) shares: the bounds of the finite sources, the grid, the sources and
 // -- when their filter differs -- the queries in cell order, the candidates per workgroup of 256 sorted queries.  The caller has
 // drained the ring and c->n is 1 .. 2^30 - 1.  b->grid stays false when there is no finite source or no finite query (nothing to
-// find; only the two counts are set).
-int32_t neigh_build(gs_ctx* c, const char* who, float radius, uint32_t smask, uint32_t svalue, uint32_t qmask, uint32_t qvalue, NeighBuilt* b) {
+// find; only the two counts are set).  gate (u32[n], null for a count and a labelling): the queries are further restricted to the
+// splats whose word there is +inf's -- where the query set is formed: the bounds' counts and the queries' keys, and so their sort,
+// their records and the candidates.
+int32_t neigh_build(gs_ctx* c, const char* who, float radius, uint32_t smask, uint32_t svalue, uint32_t qmask, uint32_t qvalue, NeighBuilt* b,
+                    const uint32_t* gate) {
     gs_ctx::Neigh& s = c->ng;
     const uint32_t n = c->n;
-    const bool same = smask == qmask && svalue == qvalue;
+    const bool same = smask == qmask && svalue == qvalue && !gate;
     b->state = (smask | svalue | qmask | qvalue) ? c->scene.state : nullptr;
     int32_t rc;
 
@@ -94,7 +97,7 @@ int32_t neigh_build(gs_ctx* c, const char* who, float radius, uint32_t smask, ui
 
     // 1. the bounds of the finite sources and the four counts (the bounds words are reserved there, before the launch)
     uint32_t hb[16];
-    if ((rc = neigh_bounds(c, b->state, smask, svalue, qmask, qvalue, hb)) != GS_OK) return rc;
+    if ((rc = neigh_bounds(c, b->state, smask, svalue, qmask, qvalue, hb, gate)) != GS_OK) return rc;
     b->sources = hb[6];
     b->queried = hb[8];
     b->nsrc = hb[7]; // with finite coordinates: the others have no neighbours
@@ -109,14 +112,14 @@ int32_t neigh_build(gs_ctx* c, const char* who, float radius, uint32_t smask, ui
     rc = s.table.reserve((uint64_t)g.blocks * 8);
     if (rc != GS_OK) return rc;
     HIP_TRY(hipMemsetAsync(s.table, 0, (size_t)g.blocks * 8, c->stream));
-    rc = sorted_records(c, b->state, smask, svalue, g, s.src, s.table);
+    rc = sorted_records(c, b->state, smask, svalue, nullptr, g, s.src, s.table);
     if (rc != GS_OK) return rc;
     uint32_t fault[2] = {0u, 0u};
     if ((rc = private_sort_fault(c, &fault[0])) != GS_OK) return rc;
     b->qrec = s.src;
     if (!same) {
         HIP_TRY(hipStreamSynchronize(c->stream)); // fault[0] is read before the control block is zeroed again
-        rc = sorted_records(c, b->state, qmask, qvalue, g, s.qry, nullptr);
+        rc = sorted_records(c, b->state, qmask, qvalue, gate, g, s.qry, nullptr);
         if (rc != GS_OK) return rc;
         if ((rc = private_sort_fault(c, &fault[1])) != GS_OK) return rc;
         b->qrec = s.qry;

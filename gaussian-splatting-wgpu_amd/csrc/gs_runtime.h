@@ -1,4 +1,4 @@
-// gs_runtime.h -- private to the runtime sources (gs_context / gs_frame / gs_readback / gs_state / gs_export / gs_insert / gs_snapshot / gs_xform / gs_coverage / gs_attr / gs_neigh / gs_cluster / gs_pack / gs_ply / gs_stages .hip):
+// gs_runtime.h -- private to the runtime sources (gs_context / gs_frame / gs_readback / gs_state / gs_export / gs_insert / gs_snapshot / gs_xform / gs_coverage / gs_attr / gs_neigh / gs_cluster / gs_knn / gs_pack / gs_ply / gs_stages .hip):
 //   the error channel (fail, HIP_TRY);
 //   the owners of HIP resources (Owned: DevBuf, PinnedBuf, Event, Stream, File) and Scratch, a device buffer that grows on demand;
 //   the context (gs_ctx, GsOptions, FrameNotes, GraphKey), the lists of its last frame (frame_lists) and sums over its ring (over_ring);
@@ -219,6 +219,10 @@ struct gs_ctx {
     // clusters (gs_cluster.hip): the label and size planes u32[N], allocated (label = GS_CLUSTER_NONE, size = 0) on first use and
     // dropped with the scene like the count plane; a labelling works in ng's scratch and commits into them at its end
     struct Cluster { DevBuf<uint32_t> label, size; } cl;
+    // nearest neighbours (gs_knn.hip): the k-th nearest squared distance f32[N] (held as words) and the nearest source's id u32[N],
+    // allocated (NaN 0x7FC00000 / GS_KNN_NONE) on first use and dropped with the scene like the count plane; k: that of the last
+    // search without GS_KNN_REFINE (0: none yet), which a refinement must repeat.  A search works in ng's scratch.
+    struct Knn { DevBuf<uint32_t> dist2, nearest; uint32_t k = 0; } kn;
     Event ev[GS_EV_RING][GS_STAGE_COUNT + 1]; // ring of per-frame stage brackets (GS_FLAG_TIMING)
     bool have_events = false;
     uint64_t timed_from = 0; // first frame index included in the stage means
@@ -317,7 +321,8 @@ struct NeighBuilt {
     uint64_t candidates = 0;
 };
 int32_t neigh_check_radius(const char* who, float radius, float* r2);
-int32_t neigh_build(gs_ctx* c, const char* who, float radius, uint32_t smask, uint32_t svalue, uint32_t qmask, uint32_t qvalue, NeighBuilt* b);
+int32_t neigh_build(gs_ctx* c, const char* who, float radius, uint32_t smask, uint32_t svalue, uint32_t qmask, uint32_t qvalue, NeighBuilt* b,
+                    const uint32_t* gate = nullptr);
 int32_t neigh_budget(const char* who, uint64_t candidates, uint64_t max_candidates, float radius);
 template <class Launch>
 void neigh_slices(const std::vector<unsigned long long>& sums, Launch launch) {
@@ -333,7 +338,8 @@ void neigh_slices(const std::vector<unsigned long long>& sums, Launch launch) {
 // gs_neigh.hip: the bounds kernel under a source and a query filter (state: the plane, or null when both are (0, 0)): seeds the 16
 // words, launches, reads them back into hb and synchronises.  hb[0..2] / [3..5]: pk_okey of the finite sources' lowest / highest
 // coordinates; hb[6..9]: sources, finite sources, queried, finite queried.
-int32_t neigh_bounds(gs_ctx* c, const uint8_t* state, uint32_t smask, uint32_t svalue, uint32_t qmask, uint32_t qvalue, uint32_t hb[16]);
+int32_t neigh_bounds(gs_ctx* c, const uint8_t* state, uint32_t smask, uint32_t svalue, uint32_t qmask, uint32_t qvalue, uint32_t hb[16],
+                     const uint32_t* gate = nullptr);
 // The pair sort behind a private control block -- the frame path's instance sort outside a frame: 8-bit digits of the key itself,
 // counted by the sort.  private_sort_bytes: the control block and the status words of `passes` passes over n pairs that follow it.
 // private_sort_plan: the plan over four arrays.  gs_sort_pairs_u32 has no context and drives these two itself; a call on a context
@@ -374,6 +380,8 @@ inline int32_t private_sort_fault(gs_ctx* c, uint32_t* fault) {
 }
 // gs_cluster.hip: the label and size planes of `c`, allocated and set to their initial reading (on `st`) by the first call that needs them
 int32_t cluster_planes(gs_ctx* c, hipStream_t st);
+// gs_knn.hip: the nearest-neighbour planes of `c`, allocated and set to their initial reading (on `st`) by the first call that needs them
+int32_t knn_planes(gs_ctx* c, hipStream_t st);
 // gs_export.hip: the splat edits' selection: counts the splats with (s & mask) == value and, with want_ids, leaves their indices,
 // ascending, in c->ex.ids
 int32_t edit_select(gs_ctx* c, uint32_t mask, uint32_t value, bool want_ids, uint64_t* total);

@@ -1,5 +1,5 @@
 // gs_state.hip -- the state plane's entry points: region, id, coverage and attribute selections, counting, restore.  Part of the C ABI
-// (include/gsplat/gs_abi.h "splat state"; gs_state_coverage under "coverage", gs_state_attr under "splat attributes", gs_state_neigh under "neighbourhoods", gs_state_cluster and gs_state_cluster_linked under "clusters"); the kernels are in k_state.hip, the projection that
+// (include/gsplat/gs_abi.h "splat state"; gs_state_coverage under "coverage", gs_state_attr under "splat attributes", gs_state_neigh under "neighbourhoods", gs_state_knn under "nearest neighbours", gs_state_cluster and gs_state_cluster_linked under "clusters"); the kernels are in k_state.hip, the projection that
 // honours the plane in k_preprocess.hip (STATE).  Also what every call on the resident splats does first (gs_runtime.h).
 //
 // The reference has no counterpart: it is a viewer.  An editor on it would edit its own 320-byte records and upload them again
@@ -177,6 +177,24 @@ GS_EXPORT int32_t gs_state_neigh(gs_ctx* c, uint32_t min_count, uint32_t max_cou
     if (rc != GS_OK) return rc;
     return state_counted(c, [&](unsigned long long* slots) {
         gs_launch_state_neigh(plane(c), c->ng.plane, c->n, min_count, max_count, inside, op, bits, where_mask, where_value, slots, c->stream);
+    }, matched);
+}
+
+// Select by the k-th nearest distance: the pass over the dist2 plane (gs_knn.hip) read as words, with gs_state_attr's float range.
+GS_EXPORT int32_t gs_state_knn(gs_ctx* c, float lo, float hi, uint32_t inside, uint32_t where_mask, uint32_t where_value, uint32_t op, uint32_t bits,
+                               uint64_t* matched) {
+    int32_t rc = resident_check(c, "gs_state_knn", Plane::always);
+    if (rc != GS_OK) return rc;
+    rc = state_check_op("gs_state_knn", op, bits);
+    if (rc != GS_OK) return rc;
+    if (lo != lo || hi != hi) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_knn: range [%g, %g] has a bound that is not a number", (double)lo, (double)hi);
+    if (where_mask > 0xFFu) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_knn: where_mask 0x%x does not fit the state byte", where_mask);
+    rc = resident_drain(c, true);
+    if (rc != GS_OK) return rc;
+    rc = knn_planes(c, c->stream);
+    if (rc != GS_OK) return rc;
+    return state_counted(c, [&](unsigned long long* slots) {
+        gs_launch_state_knn(plane(c), c->kn.dist2, c->n, lo, hi, inside, op, bits, where_mask, where_value, slots, c->stream);
     }, matched);
 }
 

@@ -45,17 +45,18 @@ __device__ __forceinline__ uint32_t neigh_order_key(float v) { // order-preservi
     return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
 }
 // out[16]: [0..2] min keys of x, y, z over the finite sources, [3..5] max keys, [6] sources, [7] finite sources, [8] queries,
-// [9] finite queries.  The caller initialises it (min keys all ones, the rest 0).
+// [9] finite queries.  The caller initialises it (min keys all ones, the rest 0).  gate (null for everyone but a refining nearest-
+// neighbour search, gs_knn.hip): a query must also read +inf there.
 __global__ __launch_bounds__(256) void gs_neigh_bounds_kernel(const uint8_t* __restrict__ state, const float* __restrict__ px, const float* __restrict__ py,
                                                                const float* __restrict__ pz, uint32_t n, uint32_t smask, uint32_t svalue, uint32_t qmask,
-                                                               uint32_t qvalue, uint32_t* __restrict__ out) {
+                                                               uint32_t qvalue, const uint32_t* __restrict__ gate, uint32_t* __restrict__ out) {
     __shared__ uint32_t s_o[10];
     if (threadIdx.x < 10u) s_o[threadIdx.x] = threadIdx.x < 3u ? 0xFFFFFFFFu : 0u;
     __syncthreads();
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i < n) {
         const uint32_t sv = state ? state[i] : 0u;
-        const bool src = (sv & smask) == svalue, qry = (sv & qmask) == qvalue;
+        const bool src = (sv & smask) == svalue, qry = (sv & qmask) == qvalue && (!gate || gate[i] == 0x7F800000u);
         if (src || qry) {
             const float x = px[i], y = py[i], z = pz[i];
             const bool fin = neigh_finite(x, y, z);
@@ -82,9 +83,9 @@ __global__ __launch_bounds__(256) void gs_neigh_bounds_kernel(const uint8_t* __r
     }
 }
 void gs_launch_neigh_bounds(const uint8_t* state, const GsScene& s, uint32_t n, uint32_t smask, uint32_t svalue, uint32_t qmask, uint32_t qvalue,
-                            uint32_t* out, hipStream_t st) {
+                            const uint32_t* gate, uint32_t* out, hipStream_t st) {
     if (!n) return;
-    hipLaunchKernelGGL(gs_neigh_bounds_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, state, s.px, s.py, s.pz, n, smask, svalue, qmask, qvalue, out);
+    hipLaunchKernelGGL(gs_neigh_bounds_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, state, s.px, s.py, s.pz, n, smask, svalue, qmask, qvalue, gate, out);
 }
 
 __device__ __forceinline__ uint32_t neigh_key(const GsNeighGrid& g, float x, float y, float z) {
@@ -94,23 +95,24 @@ __device__ __forceinline__ uint32_t neigh_key(const GsNeighGrid& g, float x, flo
 }
 
 __global__ __launch_bounds__(256) void gs_neigh_keys_kernel(const uint8_t* __restrict__ state, const float* __restrict__ px, const float* __restrict__ py,
-                                                             const float* __restrict__ pz, uint32_t n, uint32_t mask, uint32_t value, GsNeighGrid g,
-                                                             uint32_t* __restrict__ keys, uint32_t* __restrict__ vals) {
+                                                             const float* __restrict__ pz, uint32_t n, uint32_t mask, uint32_t value,
+                                                             const uint32_t* __restrict__ gate, GsNeighGrid g, uint32_t* __restrict__ keys,
+                                                             uint32_t* __restrict__ vals) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
     const uint32_t sv = state ? state[i] : 0u;
     uint32_t key = g.none;
-    if ((sv & mask) == value) {
+    if ((sv & mask) == value && (!gate || gate[i] == 0x7F800000u)) {
         const float x = px[i], y = py[i], z = pz[i];
         if (neigh_finite(x, y, z)) key = neigh_key(g, x, y, z);
     }
     keys[i] = key;
     vals[i] = i;
 }
-void gs_launch_neigh_keys(const uint8_t* state, const GsScene& s, uint32_t n, uint32_t mask, uint32_t value, const GsNeighGrid& g, uint32_t* keys,
-                          uint32_t* vals, hipStream_t st) {
+void gs_launch_neigh_keys(const uint8_t* state, const GsScene& s, uint32_t n, uint32_t mask, uint32_t value, const uint32_t* gate, const GsNeighGrid& g,
+                          uint32_t* keys, uint32_t* vals, hipStream_t st) {
     if (!n) return;
-    hipLaunchKernelGGL(gs_neigh_keys_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, state, s.px, s.py, s.pz, n, mask, value, g, keys, vals);
+    hipLaunchKernelGGL(gs_neigh_keys_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, state, s.px, s.py, s.pz, n, mask, value, gate, g, keys, vals);
 }
 
 // Sorted position t (0 .. n): a key below `none` is a member; its record and, with `table`, its key and the ends of its block's run.

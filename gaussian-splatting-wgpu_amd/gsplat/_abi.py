@@ -81,6 +81,11 @@ GS_NEIGH_LIMIT_NONE = 0xFFFFFFFF  # gs_neigh.limit: count every neighbour
 GS_CLUSTER_NONE = 0xFFFFFFFF  # the label of a splat that is no member
 GS_CLUSTER_MAX_ROUNDS = 64
 
+# nearest neighbours
+GS_KNN_MAX_K = 32
+GS_KNN_NONE = 0xFFFFFFFF  # nearest of a splat without an accepted source (and of a splat that was no query)
+GS_KNN_REFINE = 0x1       # gs_knn.flags: only the splats whose dist2 reads +inf now are queried and written
+
 # packed scenes (gs_export_packed's order)
 GS_PACK_ORDER_INDEX, GS_PACK_ORDER_MORTON = 0, 1
 
@@ -99,6 +104,7 @@ ABI_SYMBOLS = ("gs_last_error", "gs_abi_version", "gs_create", "gs_destroy", "gs
                "gs_attr_summary", "gs_attr_histogram", "gs_attr_read", "gs_state_attr",
                "gs_neigh_count", "gs_neigh_read", "gs_state_neigh",
                "gs_cluster_label", "gs_cluster_read", "gs_state_cluster", "gs_state_cluster_linked",
+               "gs_knn_search", "gs_knn_read", "gs_state_knn",
                "gs_pack_encode", "gs_pack_decode", "gs_pack_save", "gs_pack_load", "gs_pack_logit_table", "gs_export_packed", "gs_upload_packed",
                "gs_append_packed", "gs_set_option", "gs_slab_width", "gs_assemble_slabs", "gs_sort_pairs_u32",
                "gs_exclusive_scan_u32")
@@ -194,6 +200,17 @@ class GsCluster(ctypes.Structure):
 class GsClusterInfo(ctypes.Structure):
     _fields_ = [("members", ctypes.c_uint64), ("clusters", ctypes.c_uint64), ("largest", ctypes.c_uint64), ("candidates", ctypes.c_uint64),
                 ("rounds", ctypes.c_uint32), ("cells", ctypes.c_uint32 * 3), ("cell_edge", ctypes.c_float), ("reserved", ctypes.c_uint32)]
+
+
+class GsKnn(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("radius", ctypes.c_float), ("k", ctypes.c_uint32), ("flags", ctypes.c_uint32),
+                ("src_mask", ctypes.c_uint32), ("src_value", ctypes.c_uint32), ("qry_mask", ctypes.c_uint32), ("qry_value", ctypes.c_uint32),
+                ("max_candidates", ctypes.c_uint64), ("reserved", ctypes.c_uint64)]
+
+
+class GsKnnInfo(ctypes.Structure):
+    _fields_ = [("queried", ctypes.c_uint64), ("sources", ctypes.c_uint64), ("candidates", ctypes.c_uint64), ("unresolved", ctypes.c_uint64),
+                ("cells", ctypes.c_uint32 * 3), ("cell_edge", ctypes.c_float)]
 
 
 class GsPackInfo(ctypes.Structure):
@@ -292,6 +309,9 @@ def load():
     L.gs_cluster_read.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64)]
     L.gs_state_cluster.argtypes = [vp, u32, u32, u32, u32, u32, u32, u32, ctypes.POINTER(u64)]
     L.gs_state_cluster_linked.argtypes = [vp, u32, u32, u32, u32, u32, u32, ctypes.POINTER(u64)]
+    L.gs_knn_search.argtypes = [vp, ctypes.POINTER(GsKnn), ctypes.POINTER(GsKnnInfo)]
+    L.gs_knn_read.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64)]
+    L.gs_state_knn.argtypes = [vp, f32, f32, u32, u32, u32, u32, u32, ctypes.POINTER(u64)]
     L.gs_pack_encode.argtypes = [vp, u64, i32, vp, vp, vp, ctypes.POINTER(u64)]
     L.gs_pack_decode.argtypes = [vp, vp, vp, u64, i32, vp]
     L.gs_pack_save.argtypes = [ctypes.c_char_p, vp, u64, i32]

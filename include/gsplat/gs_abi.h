@@ -871,6 +871,89 @@ int32_t gs_state_cluster(gs_ctx* ctx, uint32_t min_size, uint32_t max_size, uint
 int32_t gs_state_cluster_linked(gs_ctx* ctx, uint32_t seed_mask, uint32_t seed_value, uint32_t where_mask, uint32_t where_value,
                                 uint32_t op, uint32_t bits, uint64_t* matched);
 
+/* ---- nearest neighbours: the k-th nearest distance and the nearest id per splat ------------------------------
+ * A count and a labelling make the caller know a radius first, and a radius is a property of one capture's scale and density.
+ * Statistical outlier removal ("my k-th nearest neighbour is further away than most splats' k-th nearest neighbour"), the local
+ * spacing an editor shows, the initial scale of inserted points and, with the nearest splat's id, de-duplication after a merge
+ * need the DISTANCE instead -- without the gs_export_splats / host k-d tree / gs_state_ids round trip.  The reference has no
+ * counterpart (a viewer).
+ * THE DEFINITION.  Sources are the splats j with (s_j & src_mask) == src_value, queries the splats i with (s_i & qry_mask) ==
+ * qry_value.  With the neighbourhoods' expression unchanged
+ *     d = p_j - p_i per component;  d2 = (dx dx + dy dy) + dz dz;  r2 = radius * radius
+ * -- one f32 rounding per written operation, no contraction, r2 ONE f32 product, the comparison <= INCLUSIVE -- let, for a query i,
+ *     D_i = the multiset { d2(i, j) : j a source, j != i, d2(i, j) <= r2 }.
+ * Self is excluded by index, not by distance.  A NaN or infinite coordinate fails every comparison: such a splat has no neighbours
+ * and is nobody's.  Then
+ *     dist2[i]   = the k-th smallest element of D_i, or +inf (0x7F800000) when D_i has fewer than k elements: UNRESOLVED;
+ *     nearest[i] = the smallest index j among the sources that attain min D_i (the TIE RULE: d2 first, then the smaller id), or
+ *                  GS_KNN_NONE (0xFFFFFFFF) when D_i is empty;
+ *     a splat that is not a query reads dist2 = NaN with exactly the bits 0x7FC00000 and nearest = GS_KNN_NONE.
+ * Both numbers are functions of a multiset and of a total order (d2, then id): nothing depends on the order in which the device
+ * visits anything, and a square is never -0, so the planes compare by bit pattern: two runs, a slab ctx, a borrower of
+ * gs_share_splats, a fresh ctx and a brute-force host restatement agree bit for bit.  Exact duplicates have dist2 = +0.0.
+ * RADIUS-INDEPENDENCE, the property the design rests on: a RESOLVED dist2[i] (finite) and, for k = 1, its nearest[i] DO NOT DEPEND
+ * ON THE RADIUS.  D_i holds every source within r and nothing beyond, so when it has k elements its k-th smallest is the k-th
+ * smallest over ALL sources (any source outside r is further than all of them), and its minimum with the tie rule is the nearest
+ * source among all.  Only WHETHER a query is resolved depends on the radius.  (For k > 1 the nearest of an unresolved query with a
+ * non-empty D_i is already the true nearest source, for the same reason.)  This is also why one grid pass suffices: everything
+ * within r is in the 27 cells around the query, and nothing beyond r is accepted.
+ * REFINE.  With GS_KNN_REFINE the queries are further restricted to the splats whose dist2 reads +inf NOW, only their two entries
+ * are written and every other entry keeps its value; queried and unresolved count this call's queries only.  A host that doubles
+ * the radius while unresolved > 0 therefore ends with the planes of a single search at the last radius, for the price of the
+ * sparse remainder.  Refused (GS_ERR_INVALID_ARGUMENT) when k differs from the k of the last search without the flag on this ctx,
+ * or when there has been none since the planes were last dropped.
+ * THE PLANES are f32[N] (dist2) and u32[N] (nearest) and belong to the ctx the call is made on (the root of a ring; a borrower
+ * keeps its own), like the count plane.  They are allocated by the first call that needs them and read NaN / GS_KNN_NONE before
+ * the first search; gs_knn_search without GS_KNN_REFINE overwrites both as a whole; they are DROPPED -- they read as before the
+ * first search again -- by every gs_upload_*, gs_share_splats and gs_compact, whatever drops the count plane and nothing else.
+ * State calls and transforms leave them untouched: they describe the positions and states at the time of the search, and a host
+ * that moves or re-filters splats searches again.  A call that fails for any reason -- budget, allocation, a refused argument --
+ * leaves both planes as they were.
+ * WORK.  A search builds the neighbourhoods' grid over the sources at the radius given, computes `candidates` exactly and, above
+ * max_candidates (0: GS_NEIGH_DEFAULT_CANDIDATES), returns GS_ERR_CAPACITY with both numbers in the message; the query pass is
+ * issued in the count's slices (GS_NEIGH_SLICE_CANDIDATES).  Per query the device keeps the k smallest accepted d2 (k <=
+ * GS_KNN_MAX_K) and the (d2, id) minimum.  Measured rates: profiles/nearest.txt.
+ * Prologue, ordering and refusals are the neighbourhoods': each (mask, value) as gs_state_count, above 0xFF refused, (0, 0)
+ * matches every splat and is accepted on a ctx without GS_FLAG_SPLAT_STATE, any other filter on such a ctx is refused.  Every call
+ * first completes all frames enqueued on the ctx's ring, runs on the ctx's stream and returns when done; none is a frame or an
+ * upload (taps, statistics, gs_pick, the shadows and a captured graph stay).  GS_ERR_NO_SCENE before any upload; N == 0: zero
+ * results, GS_OK.  gs_knn_search and gs_knn_read work on a borrower; gs_state_knn has gs_state_region's rules.  A wrong
+ * struct_size, a radius that is negative or not finite, a radius * radius that is not finite in f32, k outside 1 .. GS_KNN_MAX_K,
+ * unknown flag bits or reserved != 0: GS_ERR_INVALID_ARGUMENT and a message that names the number. */
+#define GS_KNN_MAX_K 32u
+#define GS_KNN_NONE 0xFFFFFFFFu
+#define GS_KNN_REFINE 0x1u         /* gs_knn.flags: only the splats whose dist2 reads +inf now are queried and written */
+typedef struct gs_knn {            /* 48 bytes */
+    uint32_t struct_size;          /* = sizeof(gs_knn) */
+    float    radius;               /* finite, >= 0; r2 = radius * radius, ONE f32 product, must be finite */
+    uint32_t k;                    /* 1 .. GS_KNN_MAX_K */
+    uint32_t flags;                /* GS_KNN_REFINE or 0 */
+    uint32_t src_mask, src_value;  /* SOURCES: splats j with (s_j & src_mask) == src_value */
+    uint32_t qry_mask, qry_value;  /* QUERIES: splats i with (s_i & qry_mask) == qry_value */
+    uint64_t max_candidates;       /* work budget, 0 = GS_NEIGH_DEFAULT_CANDIDATES */
+    uint64_t reserved;             /* 0 */
+} gs_knn;
+typedef struct gs_knn_info {       /* 48 bytes */
+    uint64_t queried, sources;     /* splats that pass the two filters (queried: and, refining, read +inf) */
+    uint64_t candidates;           /* sum over the queries of the sources in the 27 cells around them, self included */
+    uint64_t unresolved;           /* queries that end with dist2 = +inf, those with a non-finite coordinate included */
+    uint32_t cells[3]; float cell_edge; /* the grid that was used (diagnostic; no result depends on it) */
+} gs_knn_info;
+/* Searches into the two planes.  info (may be NULL) is written whenever the grid was built, also when the budget refuses the call
+ * (queried, sources, candidates and the grid; unresolved is that of a completed search). */
+int32_t gs_knn_search(gs_ctx* ctx, const gs_knn* q, gs_knn_info* info);
+/* The planes in HOST memory, N values each in splat order, with gs_cluster_read's conventions: dist2 and nearest may each be NULL,
+ * both NULL: only *n (= N) is written (query); cap < N: GS_ERR_INVALID_ARGUMENT, the message names the count needed, nothing is
+ * written. */
+int32_t gs_knn_read(gs_ctx* ctx, float* dist2, uint32_t* nearest, uint64_t cap, uint64_t* n);
+/* Applies `op` with `bits` exactly as gs_state_region does, to the splats that pass (s & where_mask) == where_value and for which
+ *     (v >= lo && v <= hi) == (inside != 0),   v = dist2
+ * -- gs_state_attr's rule.  A NaN is in no range, so a splat that was no query is never selected with inside = 1; hi = +inf
+ * includes the unresolved.  A NaN lo or hi is refused, infinite bounds are allowed, lo > hi is a valid empty range.  Needs
+ * GS_FLAG_SPLAT_STATE; *matched (may be NULL) as for gs_state_region.  One streaming pass over 5 bytes per splat. */
+int32_t gs_state_knn(gs_ctx* ctx, float lo, float hi, uint32_t inside, uint32_t where_mask, uint32_t where_value, uint32_t op, uint32_t bits,
+                     uint64_t* matched);
+
 /* Tuning / profiling knobs. */
 #define GS_OPT_BLEND_ABLATION 1  /* bit 3 (8): the workgroup-per-tile blend kernel at tiles 16 and 32 (identical results; default = one
                                     wave per 8x8 pixel block); bit 2 (4): every blend kernel without its two parking culls (live box,
