@@ -57,8 +57,8 @@ int32_t alloc_kv(gs_ctx* c, uint64_t capacity, uint64_t row_cap) {
     HIP_TRY(hipMalloc(c->chunk_table.out(), (size_t)gs_emit_chunks(std::max(capacity, row_cap)) * 4));
     if (c->tight_ok) {
         HIP_TRY(hipMalloc(c->arena.out(), (size_t)row_cap * 12));
-        HIP_TRY(hipMalloc(c->rows_sorted.out(), (size_t)row_cap * 12));
-        HIP_TRY(hipMalloc(c->M3.out(), (size_t)gs_rows_chunks(row_cap) * 256 * 4));
+        HIP_TRY(hipMalloc(c->rows_sorted.out(), gs_rows_sorted_bytes(row_cap)));
+        HIP_TRY(hipMalloc(c->M3.out(), (size_t)gs_rows_chunks(row_cap) * 256 * 4)); // (rows of the widest canvas: a frame uses 64 * ceil(ntx / 64) columns)
     }
     const size_t ctl_sz = (sizeof(GsControl) + 255) & ~(size_t)255;
     const size_t scan_sz = (((size_t)gs_scan_blocks(c->n ? c->n : 1) + 1) * 8 + 255) & ~(size_t)255;

@@ -73,6 +73,7 @@ void gs_launch_gsort(const uint32_t* words, const uint32_t* aux_in, const unsign
 // k_rows.hip: the tight row pipeline (row sort, per-chunk counts, scan, expansion into the final per-tile lists + ranges)
 uint32_t gs_rows_sort_tiles(uint64_t row_cap);
 uint32_t gs_rows_chunks(uint64_t row_cap);
+size_t gs_rows_sorted_bytes(uint64_t row_cap); // rows_sorted: an 8-byte payload plane and a 2-byte span plane for row_cap items (k_rows.hip)
 void gs_launch_rows(const uint32_t* arena, const void* grec, const uint32_t* chunk_table, uint32_t* rows_sorted, GsControl* ctl, uint32_t* sort_status, uint32_t row_cap,
                     uint32_t* M3, uint32_t* tileoff, uint32_t* rowtot, const GsFrame& f, uint32_t* values, uint32_t* ranges, uint32_t cus,
                     uint32_t* sticky, GsReport* rep, hipStream_t st, void (*mark)(void*, int), void* mark_arg);

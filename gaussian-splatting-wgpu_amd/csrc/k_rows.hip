@@ -22,12 +22,26 @@
 //                          tile start + earlier chunks' count: the FINAL lists, written once, 4 bytes per instance; no key
 //                          is ever materialised, and `ranges` falls out of the scan.
 // Order inside a tile = item order inside the tile row = depth order of the gaussians = (bucket, index): the reference's.
-// Every kernel is integer work on 12-byte items and 4-byte values; algorithmic bytes per frame (R items, I instances):
-// 12 R read + 12 R written by the row sort, 12 R read twice by count / expand, 4 I written.
+// Every kernel is integer work on row items and 4-byte values.  The arena holds 12-byte items (the row sort needs the row digit on its
+// input side); behind the sort the row is implied by position, so the sorted items are two planes (below): {w0, w2} and the 16
+// bits of w1 that are left.  Algorithmic bytes per frame (R items, I instances): 12 R read + 10 R written by the row sort, 2 R read
+// by count, 10 R read by expand, 4 I written.
 #include "gs_binning.h"
 #include "gs_tight.h"
 
 typedef uint32_t gs_item3 __attribute__((ext_vector_type(3), aligned(4)));
+
+// The row-sorted items, two planes inside one allocation of gs_rows_sorted_bytes(row_cap): item i of the sorted order is
+//   pay[i]   {w0, w2}: record slot, sub-block intervals
+//   span[i]  bits 8..23 of w1: first tile column | (tiles - 1) << 8 (the tile row is the row of the chunk that holds i)
+// The span plane follows the payload plane on a 256-byte boundary.  The count reads the span plane alone.
+__host__ __device__ inline size_t rows_span_offset(uint64_t row_cap) { return ((size_t)row_cap * 8u + 255u) & ~(size_t)255u; }
+// Columns of one row of the column-count table M3[chunk][column]: the canvas's tile columns, rounded up to whole waves (128 at 1080p,
+// 256 at 4K).  A column >= ntx holds no instance (the aliased column is column 0 of the next row), so nothing past them is kept.
+__host__ __device__ inline uint32_t rows_table_stride(uint32_t ntx) { return 64u * ((ntx + 63u) / 64u); }
+__device__ __forceinline__ const unsigned short* rows_span_plane(const uint32_t* rows, uint32_t row_cap) {
+    return reinterpret_cast<const unsigned short*>(reinterpret_cast<const char*>(rows) + rows_span_offset(row_cap));
+}
 
 #ifndef RA_ITEMS
 #define RA_ITEMS 8 // measured (config B): 6: 101-105 us, 8: 98, 10: 96 (two workgroups per CU), 12: 111
@@ -84,6 +98,8 @@ __global__ __launch_bounds__(RA_THREADS) void gs_rows_sort_kernel(const uint32_t
     if (n > row_cap) n = row_cap;
     const uint32_t ntiles = (n + RA_TILE - 1) / RA_TILE;
     const uint32_t nvis = ctl->num_visible;
+    uint2* const pay_out = reinterpret_cast<uint2*>(rows_out);
+    unsigned short* const span_out = reinterpret_cast<unsigned short*>(reinterpret_cast<char*>(rows_out) + rows_span_offset(row_cap));
     {   // first slot of every tile row's run: exclusive scan of the digit histogram (every workgroup for itself)
         const uint32_t c = tid < 256u ? gs_rowhist(ctl, tid) : 0u;
         const uint32_t incl = wave_scan_publish(c, lane, w, sh.wsum);
@@ -232,10 +248,12 @@ __global__ __launch_bounds__(RA_THREADS) void gs_rows_sort_kernel(const uint32_t
         for (int j = 0; j < RA_ITEMS; ++j) {
             const uint32_t pos = j * RA_THREADS + tid;
             if (pos < nvalid) {
-                gs_item3 v;
-                v.x = sh.u.it[pos * 3 + 0]; v.y = sh.u.it[pos * 3 + 1]; v.z = sh.u.it[pos * 3 + 2];
-                const uint32_t g = sh.gbase[v.y & 0xFFu] + pos;
-                if (g < row_cap) *reinterpret_cast<gs_item3*>(rows_out + (uint64_t)g * 3u) = v;
+                const uint32_t vx = sh.u.it[pos * 3 + 0], vy = sh.u.it[pos * 3 + 1], vz = sh.u.it[pos * 3 + 2];
+                const uint32_t g = sh.gbase[vy & 0xFFu] + pos;
+                if (g < row_cap) { // (the row digit stays behind: position g lies in its tile row's run)
+                    pay_out[g] = make_uint2(vx, vz);
+                    span_out[g] = (unsigned short)(vy >> 8);
+                }
             }
         }
         __syncthreads(); // LDS is reused by the next tile
@@ -303,17 +321,24 @@ __device__ __forceinline__ uint2 chunk_items(const RowTables& T, uint32_t r, uin
 }
 
 __global__ __launch_bounds__(256) void gs_rows_count_kernel(const uint32_t* __restrict__ rows, const GsControl* ctl, uint32_t* __restrict__ M3,
-                                                            uint32_t chunk_cap, uint32_t row_cap) {
+                                                            uint32_t chunk_cap, uint32_t row_cap, uint32_t cs) {
     __shared__ RowTables T;
     __shared__ int s_diff[257];
     __shared__ uint32_t s_w[4];
     const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const unsigned short* const span = rows_span_plane(rows, row_cap);
     row_tables(T, ctl, row_cap, tid);
     uint32_t nch = T.cbase[256];
     if (nch > chunk_cap) nch = chunk_cap;
     for (uint32_t c = blockIdx.x; c < nch; c += gridDim.x) {
         const uint2 ext = chunk_items(T, row_of_chunk(T, c), c);
         const uint32_t i0 = ext.x, i1 = ext.y;
+        uint32_t sp[RB_CH / 256u]; // (every load issued before the first is used: unconditional, from a clamped index)
+#pragma unroll
+        for (int k = 0; k < (int)(RB_CH / 256u); ++k) {
+            const uint32_t i = i0 + k * 256u + tid;
+            sp[k] = span[i < i1 ? i : i0];
+        }
         s_diff[tid] = 0;
         if (tid == 0) s_diff[256] = 0;
         __syncthreads();
@@ -321,8 +346,7 @@ __global__ __launch_bounds__(256) void gs_rows_count_kernel(const uint32_t* __re
         for (int k = 0; k < (int)(RB_CH / 256u); ++k) {
             const uint32_t i = i0 + k * 256u + tid;
             if (i < i1) {
-                const uint32_t w1 = rows[(uint64_t)i * 3u + 1u];
-                const uint32_t tlo = (w1 >> 8) & 0xFFu, len = ((w1 >> 16) & 0xFFu) + 1u;
+                const uint32_t tlo = sp[k] & 0xFFu, len = (sp[k] >> 8) + 1u;
                 atomicAdd(&s_diff[tlo], 1);
                 atomicAdd(&s_diff[tlo + len > 256u ? 256u : tlo + len], -1);
             }
@@ -333,15 +357,16 @@ __global__ __launch_bounds__(256) void gs_rows_count_kernel(const uint32_t* __re
         const uint32_t incl = wave_incl_scan(v, lane); // (wave_scan_publish, written out: one instruction more as a call)
         if (lane == 63) s_w[w] = incl;
         __syncthreads();
-        M3[(uint64_t)c * 256u + tid] = waves_before<uint32_t>(s_w, w) + incl;
+        if (tid < cs) M3[(uint64_t)c * cs + tid] = waves_before<uint32_t>(s_w, w) + incl;
         __syncthreads();
     }
 }
 
-// One workgroup of 1024 threads per tile row: thread (column c, part p) takes a quarter of the row's chunks.
+// One workgroup of 1024 threads per tile row: thread (column c, part p) takes a quarter of the row's chunks (M3's rows are cs columns
+// wide: a thread of a column >= cs takes none).
 // tileoff[r * 256 + c] = instances of row r in columns < c; rowtot[r] = instances of the row (both saturate at 2^32 - 1).
 __global__ __launch_bounds__(1024) void gs_rows_scan_kernel(const GsControl* ctl, uint32_t* __restrict__ M3, uint32_t* __restrict__ tileoff,
-                                                            uint32_t* __restrict__ rowtot, uint32_t chunk_cap, uint32_t row_cap) {
+                                                            uint32_t* __restrict__ rowtot, uint32_t chunk_cap, uint32_t row_cap, uint32_t cs) {
     __shared__ RowTables T;
     __shared__ unsigned long long s_part[4][256];
     __shared__ unsigned long long s_ex[256];
@@ -352,12 +377,13 @@ __global__ __launch_bounds__(1024) void gs_rows_scan_kernel(const GsControl* ctl
     if (c0 > chunk_cap) c0 = chunk_cap;
     if (c1 > chunk_cap) c1 = chunk_cap;
     const uint32_t nch = c1 - c0, per = (nch + 3u) / 4u;
-    const uint32_t j0 = c0 + (p * per < nch ? p * per : nch), j1 = c0 + ((p + 1u) * per < nch ? (p + 1u) * per : nch);
+    const uint32_t j0 = c0 + (p * per < nch ? p * per : nch);
+    const uint32_t j1 = c < cs ? c0 + ((p + 1u) * per < nch ? (p + 1u) * per : nch) : j0; // (a column the table does not hold counts nothing)
     unsigned long long sum = 0;
     for (uint32_t j = j0; j < j1; j += 8u) { // eight independent loads in flight
         uint32_t v[8];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] = (j + k < j1) ? M3[(uint64_t)(j + k) * 256u + c] : 0u;
+        for (int k = 0; k < 8; ++k) v[k] = (j + k < j1) ? M3[(uint64_t)(j + k) * cs + c] : 0u;
 #pragma unroll
         for (int k = 0; k < 8; ++k) sum += v[k];
     }
@@ -369,10 +395,10 @@ __global__ __launch_bounds__(1024) void gs_rows_scan_kernel(const GsControl* ctl
     for (uint32_t j = j0; j < j1; j += 8u) {
         uint32_t v[8];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] = (j + k < j1) ? M3[(uint64_t)(j + k) * 256u + c] : 0u;
+        for (int k = 0; k < 8; ++k) v[k] = (j + k < j1) ? M3[(uint64_t)(j + k) * cs + c] : 0u;
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-            if (j + k < j1) M3[(uint64_t)(j + k) * 256u + c] = sat32(run);
+            if (j + k < j1) M3[(uint64_t)(j + k) * cs + c] = sat32(run);
             run += v[k];
         }
     }
@@ -401,7 +427,7 @@ __global__ __launch_bounds__(1024) void gs_rows_scan_kernel(const GsControl* ctl
 struct ExpandShared {
     RowTables T;
     uint32_t rbase[257];      // first instance of every tile row in the lists (exclusive scan of rowtot, saturating)
-    uint32_t w0[RB_CH], w1[RB_CH], w2[RB_CH];
+    uint32_t w0[RB_CH], sp[RB_CH], w2[RB_CH]; // the chunk's items: payload words and span (first column | (tiles - 1) << 8)
     uint32_t hist[4][256];
     uint32_t gbase[256];
     uint32_t wsum[8];
@@ -423,6 +449,7 @@ __global__ __launch_bounds__(256) void gs_rows_expand_kernel(const uint32_t* __r
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
     const uint32_t ns = f.tile_size >= 16u ? 2u : 1u;
     const GsDigits dg = gs_digits(f.ntx); // dg.hole: the digit of the slots past a sub-batch's end
+    const uint32_t cs = rows_table_stride(f.ntx);
     row_tables(S.T, ctl, row_cap, tid);
     {   // first instance of every tile row
         const uint32_t v = tid < f.nty ? rowtot[tid] : 0u;
@@ -454,8 +481,12 @@ __global__ __launch_bounds__(256) void gs_rows_expand_kernel(const uint32_t* __r
     if (nch > chunk_cap) nch = chunk_cap;
     // The global loads of a chunk (its items, the column's start and earlier-chunk count) are issued one chunk AHEAD: a chunk is
     // a dozen short barrier-separated phases, and with the loads at its head every one of them waited for HBM first.
-    gs_item3 nit[RB_IT];
-    uint32_t n_r = 0, n_ni = 0, n_tstart = 0, n_done = 0;
+    // (a row's first item index is arbitrary: the two spans of a thread are loaded one by one, not as an aligned pair)
+    const uint2* const pay = reinterpret_cast<const uint2*>(rows);
+    const unsigned short* const span = rows_span_plane(rows, row_cap);
+    uint2 npay[RB_IT];
+    uint32_t nsp[RB_IT];
+    uint32_t n_r = 0, n_ni = 0, n_rbase = 0, n_toff = 0, n_done = 0;
     auto prefetch = [&](uint32_t c) {
         n_r = row_of_chunk(S.T, c);
         const uint2 ext = chunk_items(S.T, n_r, c);
@@ -464,10 +495,13 @@ __global__ __launch_bounds__(256) void gs_rows_expand_kernel(const uint32_t* __r
 #pragma unroll
         for (int k = 0; k < (int)RB_IT; ++k) {
             const uint32_t e = tid * RB_IT + k;
-            nit[k] = *reinterpret_cast<const gs_item3*>(rows + (uint64_t)(i0 + (e < n_ni ? e : 0u)) * 3u);
+            const uint32_t i = i0 + (e < n_ni ? e : 0u);
+            npay[k] = pay[i];
+            nsp[k] = span[i];
         }
-        n_tstart = S.rbase[n_r] + tileoff[n_r * 256u + tid];
-        n_done = M3[(uint64_t)c * 256u + tid];
+        n_rbase = S.rbase[n_r];
+        n_toff = tileoff[n_r * 256u + tid]; // (added to the row's base by the consuming trip: a sum right here waits for every load above)
+        n_done = M3[(uint64_t)c * cs + (tid < cs ? tid : 0u)];
     };
     if (blockIdx.x < nch) prefetch(blockIdx.x);
     for (uint32_t c = blockIdx.x; c < nch; c += gridDim.x) {
@@ -479,13 +513,13 @@ __global__ __launch_bounds__(256) void gs_rows_expand_kernel(const uint32_t* __r
             const uint32_t e = tid * RB_IT + k;
             len[k] = 0u;
             if (e < ni) {
-                S.w0[e] = nit[k].x; S.w1[e] = nit[k].y; S.w2[e] = nit[k].z;
-                len[k] = ((nit[k].y >> 16) & 0xFFu) + 1u;
+                S.w0[e] = npay[k].x; S.sp[e] = nsp[k]; S.w2[e] = npay[k].y;
+                len[k] = (nsp[k] >> 8) + 1u;
             }
             lsum += len[k];
         }
-        const uint32_t tstart = n_tstart; // first list slot of column `tid` for this chunk: tile start ...
-        uint32_t done = n_done;           // ... + what the row's earlier chunks put there
+        const uint32_t tstart = n_rbase + n_toff; // first list slot of column `tid` for this chunk: tile start ...
+        uint32_t done = tid < cs ? n_done : 0u; // ... + what the row's earlier chunks put there (nothing in a column past the table's)
         if (c + gridDim.x < nch) prefetch(c + gridDim.x);
         {
             const uint32_t incl = wave_incl_scan(lsum, lane); // (wave_scan_publish / waves_before_total in place, here and twice below:
@@ -507,7 +541,7 @@ __global__ __launch_bounds__(256) void gs_rows_expand_kernel(const uint32_t* __r
                 __syncthreads(); // the previous sub-batch's stores have read x.vals: P / mark are rebuilt (P from the items kept in LDS)
                 uint32_t l2[RB_IT], ls = 0;
 #pragma unroll
-                for (int k = 0; k < (int)RB_IT; ++k) { const uint32_t e = tid * RB_IT + k; l2[k] = e < ni ? ((S.w1[e] >> 16) & 0xFFu) + 1u : 0u; ls += l2[k]; }
+                for (int k = 0; k < (int)RB_IT; ++k) { const uint32_t e = tid * RB_IT + k; l2[k] = e < ni ? (S.sp[e] >> 8) + 1u : 0u; ls += l2[k]; }
                 const uint32_t incl = wave_incl_scan(ls, lane);
                 if (lane == 63) S.wsum[w] = incl;
                 __syncthreads();
@@ -565,8 +599,8 @@ __global__ __launch_bounds__(256) void gs_rows_expand_kernel(const uint32_t* __r
                 val[j] = 0u;
                 if (x < ninst) {
                     const uint32_t e = m - 1u;
-                    const uint32_t q = x - S.x.e.P[e], i1w = S.w1[e];
-                    d = ((i1w >> 8) & 0xFFu) + q;
+                    const uint32_t q = x - S.x.e.P[e];
+                    d = (S.sp[e] & 0xFFu) + q;
                     val[j] = (S.w0[e] & GS_ID_MASK) | (tight_item_mask(S.w2[e], q, ns) << GS_ID_BITS);
                 }
                 col4[j >> 2] |= d << (8 * (j & 3));
@@ -695,6 +729,7 @@ __global__ __launch_bounds__(256) void gs_rows_rebuild_taps_kernel(const uint32_
 // ---- host launchers --------------------------------------------------------------------------------
 uint32_t gs_rows_sort_tiles(uint64_t row_cap) { return (uint32_t)((row_cap + RA_TILE - 1) / RA_TILE); }
 uint32_t gs_rows_chunks(uint64_t row_cap) { return (uint32_t)(row_cap / RB_CH + 256u); }
+size_t gs_rows_sorted_bytes(uint64_t row_cap) { return rows_span_offset(row_cap) + (((size_t)row_cap * 2u + 255u) & ~(size_t)255u); } // payload plane, span plane
 // cus: compute units (grids are sized by residency: three 8-wave workgroups of the sort, five of the expansion, eight of the count fit a CU)
 void gs_launch_rows(const uint32_t* arena, const void* grec, const uint32_t* chunk_table, uint32_t* rows_sorted, GsControl* ctl, uint32_t* sort_status, uint32_t row_cap,
                     uint32_t* M3, uint32_t* tileoff, uint32_t* rowtot, const GsFrame& f, uint32_t* values, uint32_t* ranges, uint32_t cus,
@@ -704,8 +739,10 @@ void gs_launch_rows(const uint32_t* arena, const void* grec, const uint32_t* chu
     hipLaunchKernelGGL(gs_rows_sort_kernel, dim3(cus * 3u), dim3(RA_THREADS), 0, st, arena, (const uint4*)grec, chunk_table, rows_sorted, ctl, sort_status,
                        row_cap, f.nty);
     if (mark) mark(mark_arg, 3);
-    hipLaunchKernelGGL(gs_rows_count_kernel, dim3(cus * RB_CNT_WG), dim3(256), 0, st, (const uint32_t*)rows_sorted, (const GsControl*)ctl, M3, chunk_cap, row_cap);
-    hipLaunchKernelGGL(gs_rows_scan_kernel, dim3(f.nty), dim3(1024), 0, st, (const GsControl*)ctl, M3, tileoff, rowtot, chunk_cap, row_cap);
+    hipLaunchKernelGGL(gs_rows_count_kernel, dim3(cus * RB_CNT_WG), dim3(256), 0, st, (const uint32_t*)rows_sorted, (const GsControl*)ctl, M3, chunk_cap, row_cap,
+                       rows_table_stride(f.ntx));
+    hipLaunchKernelGGL(gs_rows_scan_kernel, dim3(f.nty), dim3(1024), 0, st, (const GsControl*)ctl, M3, tileoff, rowtot, chunk_cap, row_cap,
+                       rows_table_stride(f.ntx));
     hipLaunchKernelGGL(gs_rows_expand_kernel, dim3(cus * RB_EXP_WG), dim3(256), 0, st, (const uint32_t*)rows_sorted, ctl, (const uint32_t*)M3,
                        (const uint32_t*)tileoff, (const uint32_t*)rowtot, f, values, ranges, chunk_cap, row_cap, sticky, rep);
 }
