@@ -124,6 +124,15 @@ void gs_launch_attr_histogram(uint32_t kind, const uint8_t* state, const GsScene
 // out[g] = v of splat ids[first + g], or of splat first + g when ids is null, g = 0 .. m
 void gs_launch_attr_values(uint32_t kind, const GsScene& s, const void* cov, uint32_t n, const GsAttrDev& a, const uint32_t* ids, uint32_t first,
                            uint32_t m, float* out, hipStream_t st);
+// k_moments.hip: moments (gs_moments.hip).  Exact sums and sums of products (j <= l, gs_abi.h's order) of `planes` f32 planes, 1 .. 3 (the
+// same plane may be given twice), over the splats that pass the filter and whose values are all finite.  slots: GS_MOMENTS_SLOTS copies
+// GS_MOMENTS_SLOT_WORDS words apart, zeroed by the caller; a workgroup adds to copy (workgroup % GS_MOMENTS_SLOTS).  A copy is
+// Q = planes + planes (planes + 1) / 2 tables of GS_EX_LIMBS signed 64-bit limbs (gs_exact_sum.h), the sums first, then matched,
+// counted.  The caller adds the copies.  grid: workgroups of the grid-stride loop (clamped to the work).
+#define GS_MOMENTS_SLOTS 8
+#define GS_MOMENTS_SLOT_WORDS 192 // >= 9 * 20 + 2, a multiple of 32 words
+void gs_launch_moments(uint32_t planes, const uint8_t* state, const float* p0, const float* p1, const float* p2, uint32_t n, uint32_t mask,
+                       uint32_t value, unsigned long long* slots, uint32_t grid, hipStream_t st);
 // k_neigh.hip: neighbourhoods (gs_neigh.hip).  The cell grid over the finite sources: cell coordinate of x on axis k =
 // clamp((int)floorf((x - lo[k]) * inv_h), 0, g[k] - 1), key = cz << bxy | cy << bx | cx (bx, bxy - bx: the bits of g[0] - 1,
 // g[1] - 1).  `none` = g[2] << bxy is above every key and marks a splat that is no member (filter, non-finite coordinate): it sorts

@@ -204,6 +204,9 @@ struct gs_ctx {
     struct { Scratch<uint32_t> counts, ids; } ex;
     // splat attributes (gs_attr.hip): the summary's slot records, the histogram's bins + 3 words, one trip of values; grown on demand
     struct { DevBuf<unsigned long long> slots; Scratch<unsigned long long> hist; Scratch<float> vals; } at;
+    // moments (gs_moments.hip): the slot copies of the limb tables, and one dense plane of N values per attribute that is not a
+    // position plane; grown on demand
+    struct { DevBuf<unsigned long long> slots; Scratch<float> vals[3]; } mo;
     // gs_coverage_* (gs_coverage.hip; root ctx): N x 16 B gs_coverage_rec, allocated and zeroed on first use, dropped with the scene
     DevBuf<> cov;
     // neighbourhoods (gs_neigh.hip): the count plane u32[N], allocated and zeroed on first use, dropped with the scene like cov; the

@@ -101,7 +101,7 @@ ABI_SYMBOLS = ("gs_last_error", "gs_abi_version", "gs_create", "gs_destroy", "gs
                "gs_write_splats", "gs_write_splats_device", "gs_snapshot_take", "gs_snapshot_restore", "gs_snapshot_swap",
                "gs_snapshot_get_info", "gs_snapshot_free",
                "gs_coverage_accumulate", "gs_coverage_reset", "gs_coverage_read", "gs_state_coverage",
-               "gs_attr_summary", "gs_attr_histogram", "gs_attr_read", "gs_state_attr",
+               "gs_attr_summary", "gs_attr_histogram", "gs_attr_read", "gs_state_attr", "gs_attr_moments", "gs_moments_host",
                "gs_neigh_count", "gs_neigh_read", "gs_state_neigh",
                "gs_cluster_label", "gs_cluster_read", "gs_state_cluster", "gs_state_cluster_linked",
                "gs_knn_search", "gs_knn_read", "gs_state_knn",
@@ -179,6 +179,17 @@ class GsAttr(ctypes.Structure):
 
 class GsAttrSummary(ctypes.Structure):
     _fields_ = [("matched", ctypes.c_uint64), ("nan", ctypes.c_uint64), ("min", ctypes.c_float), ("max", ctypes.c_float)]
+
+
+GS_MOMENTS_MAX_ATTRS = 3
+
+
+class GsExact(ctypes.Structure):  # hi = RN(sum), lo = RN(sum - hi)
+    _fields_ = [("hi", ctypes.c_double), ("lo", ctypes.c_double)]
+
+
+class GsAttrMoments(ctypes.Structure):  # prod: 00, 01, 02, 11, 12, 22
+    _fields_ = [("matched", ctypes.c_uint64), ("counted", ctypes.c_uint64), ("sum", GsExact * 3), ("prod", GsExact * 6)]
 
 
 class GsNeigh(ctypes.Structure):
@@ -299,6 +310,8 @@ def load():
     L.gs_state_coverage.argtypes = [vp, u32, ctypes.c_float, u32, u32, u32, u32, u32, ctypes.POINTER(u64)]
     f32 = ctypes.c_float
     L.gs_attr_summary.argtypes = [vp, ctypes.POINTER(GsAttr), u32, u32, ctypes.POINTER(GsAttrSummary)]
+    L.gs_attr_moments.argtypes = [vp, ctypes.POINTER(GsAttr), u32, u32, u32, ctypes.POINTER(GsAttrMoments)]
+    L.gs_moments_host.argtypes = [ctypes.POINTER(vp), u32, u64, vp, u32, u32, ctypes.POINTER(GsAttrMoments)]
     L.gs_attr_histogram.argtypes = [vp, ctypes.POINTER(GsAttr), u32, u32, f32, f32, u32, vp]
     L.gs_attr_read.argtypes = [vp, ctypes.POINTER(GsAttr), u32, u32, vp, u64, ctypes.POINTER(u64), vp]
     L.gs_state_attr.argtypes = [vp, ctypes.POINTER(GsAttr), f32, f32, u32, u32, u32, u32, u32, ctypes.POINTER(u64)]

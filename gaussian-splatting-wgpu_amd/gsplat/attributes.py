@@ -50,7 +50,7 @@ def depth_attr(uniforms):
 def summary(r, a, where=(0, 0)):
     """gs_attr_summary: {"matched", "nan", "min", "max"} over the splats with (s & where[0]) == where[1]; min / max (np.float32) over
     the values that are not NaN, in the total order that puts -0 below +0; (+inf, -inf) when there is none.  There is no mean: a
-    float sum depends on the order of the adds."""
+    float sum depends on the order of the adds (an exact one, which does not, is moments.mean)."""
     o = _owner(r)
     out = _abi.GsAttrSummary()
     check(o._L.gs_attr_summary(o._ctx, ctypes.byref(a), int(where[0]), int(where[1]), ctypes.byref(out)))

@@ -723,7 +723,7 @@ struct gs_attr_summary { uint64_t matched, nan; float min, max; };  /* 24 bytes 
  * total order of the order-preserving map of the bit pattern, k = b ^ (b >> 31 ? 0xFFFFFFFF : 0x80000000) -- so -0 < +0 and the
  * result does not depend on the order in which the device reduces.  No non-NaN value: min = +inf, max = -inf.  There is no mean:
  * a float sum depends on the order of the adds, and a host can restate every number this layer returns; the pivot an editor
- * wants is the centre of the bounds. */
+ * wants is the centre of the bounds.  (An EXACT mean, which does not depend on the order, is gs_attr_moments' below.) */
 int32_t gs_attr_summary(gs_ctx* ctx, const gs_attr* attr, uint32_t mask, uint32_t value, struct gs_attr_summary* out);
 /* counts: HOST u64[bins + 3]: [0, bins) the bins, [bins] below, [bins + 1] above, [bins + 2] NaN; they add up to matched.
  * scale = (float)bins / (hi - lo), once, in f32.  Per matching splat: a NaN v goes to the NaN slot, v < lo below, v >= hi above,
@@ -742,6 +742,44 @@ int32_t gs_attr_read(gs_ctx* ctx, const gs_attr* attr, uint32_t mask, uint32_t v
  * gs_state_region.  One streaming pass: the state byte and the kind's bytes per splat. */
 int32_t gs_state_attr(gs_ctx* ctx, const gs_attr* attr, float lo, float hi, uint32_t inside, uint32_t where_mask, uint32_t where_value,
                       uint32_t op, uint32_t bits, uint64_t* matched);
+
+/* ---- moments: the exact mean and covariance of resident splats by value ---------------------------------------
+ * The selections above answer "which splats"; this answers "where is the selection and how does it lie": the centroid as a pivot,
+ * the principal axes, an oriented box, the plane to level a capture by.  A float sum depends on the order of the adds and could
+ * not be restated, so this is not a float sum: the device accumulates integers and the host rounds ONCE.  The result does not
+ * depend on the order, the grid, slabs or borrowers, and a host restates it with rational arithmetic (tests/moments_restate.py).
+ * The reference has no counterpart (a viewer).
+ * attrs[0 .. n_attrs) are gs_attr values as every attribute call takes them, n_attrs in 1 .. GS_MOMENTS_MAX_ATTRS; the same kind
+ * may appear twice.  v_j(i) is attribute j's f32 value of splat i, exactly as gs_attr_read returns it.
+ *     matched   the splats that pass (s & mask) == value
+ *     counted   the matched splats whose n_attrs values are ALL finite.  A splat with a NaN or an infinity in any of them is left
+ *               out of every sum; matched - counted is the number left out
+ *     sum[j]    S_j  = sum over the counted splats of v_j
+ *     prod[]    P_jl = sum over the counted splats of v_j v_l for j <= l, in the order 00, 01, 02, 11, 12, 22
+ * These are sums of REAL numbers: a product of two f32 is exact (at most 48 significant bits), nothing is rounded before the end.
+ * A gs_exact holds one of them: hi is the double nearest to the sum, ties to even; lo is the double nearest to (sum - hi).  An
+ * exact zero is {+0.0, +0.0}; an entry with j or l >= n_attrs is {+0.0, +0.0} as well.  Nothing overflows: |sum| < 2^31 2^256, and
+ * every non-zero term is a multiple of 2^-298, so no subnormal double is involved.
+ * How: a finite f32 is m 2^e with an integer |m| < 2^24, a product m 2^e with |m| < 2^48 and e >= -298.  A term is added, with its
+ * sign, as three 32-bit chunks into signed 64-bit limbs at bit position e + 298 (twenty limbs per sum); the host propagates the
+ * carries into one big integer and rounds that to hi, subtracts hi exactly and rounds the rest to lo -- integer code, no long
+ * double, no float add (csrc/gs_exact_sum.h, compiled into the kernel and the host alike).  One streaming pass: 4 B per attribute
+ * and splat, 1 B of state with a filter; POS_X / Y / Z are read in place, any other kind is first written densely (4 B more each
+ * way).
+ * Filter, refusals, drain and ordering are gs_attr_summary's: (0, 0) matches every splat and works on a ctx without
+ * GS_FLAG_SPLAT_STATE; the COVER_* kinds read the ctx's own coverage planes; the call works on a borrower of gs_share_splats and is
+ * neither a frame nor an upload.  GS_ERR_NO_SCENE before any upload; N == 0: all zeros, GS_OK.  n_attrs outside 1 .. 3, a null
+ * pointer, a wrong struct_size, kind >= GS_ATTR_COUNT or a non-finite p of DIST2 / PLANE: GS_ERR_INVALID_ARGUMENT, a message that
+ * names the call, and *out untouched.  N >= 2^31 is refused too (a limb could overflow there; no device holds that many splats).
+ * gs_moments_host computes the same record from n values per HOST plane, planes[0 .. n_planes): no ctx, no GPU, the same code.
+ * state: u8[n], may be NULL when the filter is (0, 0).  For hosts that hold records, and for checking the shared code anywhere. */
+#define GS_MOMENTS_MAX_ATTRS 3u
+typedef struct gs_exact { double hi, lo; } gs_exact;   /* 16 bytes */
+/* (A struct tag only, like gs_attr_summary: the record shares its name with the call that fills it.) */
+struct gs_attr_moments { uint64_t matched, counted; gs_exact sum[3]; gs_exact prod[6]; };   /* 160 bytes */
+int32_t gs_attr_moments(gs_ctx* ctx, const gs_attr* attrs, uint32_t n_attrs, uint32_t mask, uint32_t value, struct gs_attr_moments* out);
+int32_t gs_moments_host(const float* const* planes, uint32_t n_planes, uint64_t n, const uint8_t* state, uint32_t mask, uint32_t value,
+                        struct gs_attr_moments* out);
 
 /* ---- neighbourhoods: count the splats within a radius, select by that count ---------------------------------
  * Every selection above asks about one splat at a time; these ask about a splat in relation to the others, which is what a splat
