@@ -7,8 +7,8 @@
 // limb L = p / 32, shift = p % 32, and |m| << shift (at most 80 bits) is three 32-bit chunks that are added, with the term's sign,
 // to the signed 64-bit limbs L, L + 1, L + 2.  p <= 506, so L + 2 <= 17: GS_EX_LIMBS = 20 limbs cover every case.  One term adds at
 // most one chunk (< 2^32) to any one limb, so with fewer than 2^31 terms no limb leaves i64 -- in any order, on any grid: integer
-// adds commute.  (The kernel first adds a lane's terms, shifted against a base limb, into a 128-bit integer in registers and adds
-// that integer's four 32-bit words to the limbs: the same sum, the same bound.)
+// adds commute.  (The kernels first add a lane's terms, shifted against a base limb, into a 128-bit integer in registers and add
+// that integer's four 32-bit words to the limbs: the same sum, the same bound -- gs_exact_dev.h, shared by k_moments.hip and k_pairs.hip.)
 // THE FINISH (host only).  Carries are propagated over the limbs into one sign-magnitude integer, which is rounded ONCE to the
 // nearest double, ties to even (hi); hi is subtracted exactly and the rest rounded once more (lo).  Integer code throughout: no
 // long double, no float add.  Every non-zero term is a multiple of 2^-298 and |sum| < 2^31 2^256, so neither result is subnormal

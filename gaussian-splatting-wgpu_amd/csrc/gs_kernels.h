@@ -133,6 +133,14 @@ void gs_launch_attr_values(uint32_t kind, const GsScene& s, const void* cov, uin
 #define GS_MOMENTS_SLOT_WORDS 192 // >= 9 * 20 + 2, a multiple of 32 words
 void gs_launch_moments(uint32_t planes, const uint8_t* state, const float* p0, const float* p1, const float* p2, uint32_t n, uint32_t mask,
                        uint32_t value, unsigned long long* slots, uint32_t grid, hipStream_t st);
+// k_pairs.hip: pair moments (gs_pairs.hip).  The exact sums over the pairs (p_i, p_partner[i]) of the splats that pass the filter: 21
+// tables of GS_EX_LIMBS limbs in gs_pair_host.h's order, then matched, paired.  partner: u32[n] on the device, read as a uint4 per
+// whole quad; an id >= n is never an index.  slots: GS_PAIRS_SLOTS copies GS_PAIRS_SLOT_WORDS words apart, zeroed by the caller, who
+// also adds them; a workgroup adds to copy (workgroup % GS_PAIRS_SLOTS).  grid: workgroups of the grid-stride loop (clamped to the work).
+#define GS_PAIRS_SLOTS 8
+#define GS_PAIRS_SLOT_WORDS 448 // >= 21 * 20 + 2, a multiple of 32 words
+void gs_launch_pairs(const uint8_t* state, const float* px, const float* py, const float* pz, const uint32_t* partner, uint32_t n, uint32_t mask,
+                     uint32_t value, float max_d2, unsigned long long* slots, uint32_t grid, hipStream_t st);
 // k_neigh.hip: neighbourhoods (gs_neigh.hip).  The cell grid over the finite sources: cell coordinate of x on axis k =
 // clamp((int)floorf((x - lo[k]) * inv_h), 0, g[k] - 1), key = cz << bxy | cy << bx | cx (bx, bxy - bx: the bits of g[0] - 1,
 // g[1] - 1).  `none` = g[2] << bxy is above every key and marks a splat that is no member (filter, non-finite coordinate): it sorts

@@ -207,6 +207,8 @@ struct gs_ctx {
     // moments (gs_moments.hip): the slot copies of the limb tables, and one dense plane of N values per attribute that is not a
     // position plane; grown on demand
     struct { DevBuf<unsigned long long> slots; Scratch<float> vals[3]; } mo;
+    // pair moments (gs_pairs.hip): the slot copies of the 21 limb tables, and the device copy of a host partner array; grown on demand
+    struct { DevBuf<unsigned long long> slots; Scratch<uint32_t> partner; } pr;
     // gs_coverage_* (gs_coverage.hip; root ctx): N x 16 B gs_coverage_rec, allocated and zeroed on first use, dropped with the scene
     DevBuf<> cov;
     // neighbourhoods (gs_neigh.hip): the count plane u32[N], allocated and zeroed on first use, dropped with the scene like cov; the

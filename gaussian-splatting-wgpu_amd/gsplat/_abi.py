@@ -105,6 +105,7 @@ ABI_SYMBOLS = ("gs_last_error", "gs_abi_version", "gs_create", "gs_destroy", "gs
                "gs_neigh_count", "gs_neigh_read", "gs_state_neigh",
                "gs_cluster_label", "gs_cluster_read", "gs_state_cluster", "gs_state_cluster_linked",
                "gs_knn_search", "gs_knn_read", "gs_state_knn",
+               "gs_pair_moments", "gs_pair_moments_host",
                "gs_pack_encode", "gs_pack_decode", "gs_pack_save", "gs_pack_load", "gs_pack_logit_table", "gs_export_packed", "gs_upload_packed",
                "gs_append_packed", "gs_set_option", "gs_slab_width", "gs_assemble_slabs", "gs_sort_pairs_u32",
                "gs_exclusive_scan_u32")
@@ -224,6 +225,11 @@ class GsKnnInfo(ctypes.Structure):
                 ("cells", ctypes.c_uint32 * 3), ("cell_edge", ctypes.c_float)]
 
 
+class GsPairMoments(ctypes.Structure):  # pq: row-major (a, b)
+    _fields_ = [("matched", ctypes.c_uint64), ("paired", ctypes.c_uint64), ("sum_p", GsExact * 3), ("sum_q", GsExact * 3), ("pq", GsExact * 9),
+                ("pp", GsExact * 3), ("qq", GsExact * 3)]
+
+
 class GsPackInfo(ctypes.Structure):
     _fields_ = [("count", ctypes.c_uint64), ("chunks", ctypes.c_uint64), ("file_bytes", ctypes.c_uint64), ("nonfinite", ctypes.c_uint64)]
 
@@ -325,6 +331,8 @@ def load():
     L.gs_knn_search.argtypes = [vp, ctypes.POINTER(GsKnn), ctypes.POINTER(GsKnnInfo)]
     L.gs_knn_read.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64)]
     L.gs_state_knn.argtypes = [vp, f32, f32, u32, u32, u32, u32, u32, ctypes.POINTER(u64)]
+    L.gs_pair_moments.argtypes = [vp, u32, u32, vp, f32, ctypes.POINTER(GsPairMoments)]
+    L.gs_pair_moments_host.argtypes = [vp, vp, vp, u64, vp, vp, u32, u32, f32, ctypes.POINTER(GsPairMoments)]
     L.gs_pack_encode.argtypes = [vp, u64, i32, vp, vp, vp, ctypes.POINTER(u64)]
     L.gs_pack_decode.argtypes = [vp, vp, vp, u64, i32, vp]
     L.gs_pack_save.argtypes = [ctypes.c_char_p, vp, u64, i32]

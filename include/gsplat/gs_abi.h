@@ -992,6 +992,47 @@ int32_t gs_knn_read(gs_ctx* ctx, float* dist2, uint32_t* nearest, uint64_t cap, 
 int32_t gs_state_knn(gs_ctx* ctx, float lo, float hi, uint32_t inside, uint32_t where_mask, uint32_t where_value, uint32_t op, uint32_t bits,
                      uint64_t* matched);
 
+/* ---- registration: the exact sums over matched pairs that a rigid or similarity fit needs --------------------
+ * A splat insertion puts a second capture behind the resident one; bringing it ONTO the first needs, per step of a point-to-point
+ * ICP, sums over PAIRS (p_i, q_i = p_j), j the partner of i: the two centroids, the 3x3 cross-covariance and the two spreads.
+ * gs_attr_moments cannot give them (it never gathers a second splat); this call does, with the moments' arithmetic: the device
+ * adds integers, the host rounds ONCE, nothing depends on the grid, the order, slabs or borrowers, and a host restates every sum
+ * with rational arithmetic (tests/pairs_restate.py).  The reference has no counterpart (a viewer).
+ *     matched   the splats i that pass (s_i & mask) == value
+ *     j         partner[i]; with partner == NULL, the ctx's own `nearest` plane as gs_knn_read would return it now (a plane that
+ *               was never searched or has been dropped reads GS_KNN_NONE everywhere: all zeros, GS_OK)
+ *     paired    the matched i for which ALL of these hold:
+ *                 j < N (GS_KNN_NONE and any other id >= N count as unpaired: never read, never an error);
+ *                 all six coordinates of p = p_i and q = p_j are finite;
+ *                 d2 <= max_dist2 with the neighbourhoods' expression on the positions as they are NOW: d = q - p per component,
+ *                 d2 = (dx dx + dy dy) + dz dz, one f32 rounding per operation, no contraction, the comparison INCLUSIVE.  A d2
+ *                 that overflows to +inf passes only max_dist2 = +inf.
+ *               j == i is allowed; the partner's state byte is not looked at.
+ *     sum_p[a], sum_q[a]   the sums over the paired splats of p_a and of q_a
+ *     pq[3 a + b]          ... of p_a q_b (row-major)
+ *     pp[a], qq[a]         ... of p_a^2 and of q_a^2
+ * Sums of REAL numbers, each finished once into a gs_exact exactly as in the moments section; an exact zero is {+0.0, +0.0}.
+ * One streaming pass: 16 B per splat (12 of position, 4 of partner id), 1 B of state with a filter, and a gather of 12 scattered
+ * bytes for every matched splat whose partner is below N.  A HOST partner array is first copied to the device (4 B per splat).
+ * Filter, refusals, drain and ordering are gs_attr_moments': the filter as gs_state_count, (0, 0) works on a ctx without
+ * GS_FLAG_SPLAT_STATE; the call completes the ring's frames first, runs on the ctx's stream and is neither a frame nor an upload;
+ * it works on a borrower of gs_share_splats and then reads THAT ctx's nearest plane.  GS_ERR_NO_SCENE before any upload; N == 0:
+ * all zeros, GS_OK.  N >= 2^31, a NaN or negative max_dist2 or a null out: GS_ERR_INVALID_ARGUMENT, a message that names the call,
+ * and *out untouched.
+ * gs_pair_moments_host runs the same loop (csrc/gs_pair_host.h) on n values per HOST plane: no ctx, no GPU, the same code.
+ * partner: u32[n], required when n > 0; state: u8[n], may be NULL when the filter is (0, 0). */
+/* (A struct tag only, like gs_attr_moments: the record shares its name with the call that fills it.) */
+struct gs_pair_moments {            /* 352 bytes */
+    uint64_t matched, paired;
+    gs_exact sum_p[3], sum_q[3];    /* sum of p_a, of q_a */
+    gs_exact pq[9];                 /* sum of p_a q_b, row-major (a, b) */
+    gs_exact pp[3], qq[3];          /* sum of p_a^2, of q_a^2 */
+};
+int32_t gs_pair_moments(gs_ctx* ctx, uint32_t mask, uint32_t value, const uint32_t* partner /* HOST u32[N] or NULL */, float max_dist2,
+                        struct gs_pair_moments* out);
+int32_t gs_pair_moments_host(const float* px, const float* py, const float* pz, uint64_t n, const uint32_t* partner, const uint8_t* state,
+                             uint32_t mask, uint32_t value, float max_dist2, struct gs_pair_moments* out);
+
 /* Tuning / profiling knobs. */
 #define GS_OPT_BLEND_ABLATION 1  /* bit 3 (8): the workgroup-per-tile blend kernel at tiles 16 and 32 (identical results; default = one
                                     wave per 8x8 pixel block); bit 2 (4): every blend kernel without its two parking culls (live box,
