@@ -1,6 +1,7 @@
 // gs_kernels.h -- host-side launchers of the gfx950 kernels (definitions next to each kernel).
 #pragma once
 #include "gs_device.h"
+#include "gs_consensus_host.h" // GsAttrDev
 
 void gs_launch_repack(const void* d_aos, uint32_t n, uint32_t first, const GsScene& s, hipStream_t st); // record r -> splat first + r
 void gs_launch_ply_chunk(const void* d_raw, uint32_t m, uint32_t first, const GsPlyTable& t, const GsScene& s, hipStream_t st);
@@ -108,7 +109,7 @@ void gs_launch_state_coverage(uint8_t* state, const void* planes, uint32_t n, ui
                               uint32_t bits, uint32_t where_mask, uint32_t where_value, unsigned long long* matched, hipStream_t st);
 // k_attr.hip: the splat attributes (gs_attr.hip; gs_state_attr in gs_state.hip).  kind: GS_ATTR_* (checked by the caller); cov: the
 // coverage planes, read by the COVER_* kinds only; state: null = every splat passes (the (0, 0) filter: the plane is not read).
-struct GsAttrDev { float p[4]; }; // a gs_attr's parameters as the kernels read them
+// (GsAttrDev, a gs_attr's parameters as the kernels read them, is gs_consensus_host.h's: the host loop of the consensus calls reads it too)
 // the state pass of gs_launch_state_region around (v >= lo && v <= hi) == inside
 void gs_launch_attr_state(uint32_t kind, uint8_t* state, const GsScene& s, const void* cov, uint32_t n, const GsAttrDev& a, float lo, float hi,
                           uint32_t inside, uint32_t op, uint32_t bits, uint32_t where_mask, uint32_t where_value, unsigned long long* matched,
@@ -124,6 +125,14 @@ void gs_launch_attr_histogram(uint32_t kind, const uint8_t* state, const GsScene
 // out[g] = v of splat ids[first + g], or of splat first + g when ids is null, g = 0 .. m
 void gs_launch_attr_values(uint32_t kind, const GsScene& s, const void* cov, uint32_t n, const GsAttrDev& a, const uint32_t* ids, uint32_t first,
                            uint32_t m, float* out, hipStream_t st);
+// k_consensus.hip: consensus (gs_consensus.hip).  kind: GS_ATTR_DIST2 or GS_ATTR_PLANE (checked by the caller).  params: f32[hp][4] on the
+// device, hp = h rounded up to GS_CONSENSUS_PAD hypotheses, the padding filled with NaNs (a NaN parameter counts nothing).  counts: hp
+// u64 words, zeroed by the caller: counts[j] += splats that pass the filter with lo <= v_j <= hi.  slots: the GS_STATE_SLOTS partial
+// sums of `matched`, zeroed by the caller, who also adds them.  grid: workgroups of the grid-stride loop (clamped to the work).
+#define GS_CONSENSUS_PAD 8u
+void gs_launch_consensus(uint32_t kind, const uint8_t* state, const float* px, const float* py, const float* pz, uint32_t n, const float* params,
+                         uint32_t hp, float lo, float hi, uint32_t mask, uint32_t value, unsigned long long* counts, unsigned long long* slots,
+                         uint32_t grid, hipStream_t st);
 // k_moments.hip: moments (gs_moments.hip).  Exact sums and sums of products (j <= l, gs_abi.h's order) of `planes` f32 planes, 1 .. 3 (the
 // same plane may be given twice), over the splats that pass the filter and whose values are all finite.  slots: GS_MOMENTS_SLOTS copies
 // GS_MOMENTS_SLOT_WORDS words apart, zeroed by the caller; a workgroup adds to copy (workgroup % GS_MOMENTS_SLOTS).  A copy is

@@ -204,6 +204,9 @@ struct gs_ctx {
     struct { Scratch<uint32_t> counts, ids; } ex;
     // splat attributes (gs_attr.hip): the summary's slot records, the histogram's bins + 3 words, one trip of values; grown on demand
     struct { DevBuf<unsigned long long> slots; Scratch<unsigned long long> hist; Scratch<float> vals; } at;
+    // consensus (gs_consensus.hip): GS_CONSENSUS_MAX count words and the matched slots behind them, the device copy of the hypothesis
+    // table (both of fixed size, allocated on first use), and the device copy of one trip of a gather's ids; grown on demand
+    struct { DevBuf<unsigned long long> counts; DevBuf<float> params; Scratch<uint32_t> ids; } cs;
     // moments (gs_moments.hip): the slot copies of the limb tables, and one dense plane of N values per attribute that is not a
     // position plane; grown on demand
     struct { DevBuf<unsigned long long> slots; Scratch<float> vals[3]; } mo;

@@ -2,7 +2,8 @@
 // (gs_attr.hip, gs_state.hip gs_state_attr; gs_abi.h "splat attributes").  The reference has no counterpart: it is a viewer, and an
 // editor built on it would scan the 320-byte records its host kept.
 //
-// The value is defined ONCE, in attr_value<KIND> and the three expression helpers under it; the four kernels are instantiated per
+// The value is defined ONCE, in attr_value<KIND> and the three expression helpers under it (the one of the centre, attr_of_pos, is in
+// gs_consensus_host.h, where the consensus kernel and its host loop read it too); the four kernels are instantiated per
 // kind and the launchers dispatch with a switch, so no kernel branches on the kind.  Bytes read per splat for the value:
 //   POS_X / Y / Z, LOG_SCALE_MAX             4 B   (its own f32 plane; a float4 per quad.  LOG_SCALE_MAX: + 16 B where the plane holds a NaN)
 //   DIST2, PLANE                            12 B   (the three position planes; three float4 per quad)
@@ -35,15 +36,7 @@ template <int KIND> constexpr bool attr_is_plane() {
 }
 template <int KIND> constexpr bool attr_is_pos() { return KIND == GS_ATTR_DIST2 || KIND == GS_ATTR_PLANE; }
 template <int KIND> constexpr bool attr_is_cover() { return KIND >= GS_ATTR_COVER_HITS; }
-// ... are an expression of the centre (one rounding per operation; DIST2 is state_member's sphere expression, PLANE the projection's pv.z)
-template <int KIND>
-__device__ __forceinline__ float attr_of_pos(const GsAttrDev& a, float x, float y, float z) {
-    if (KIND == GS_ATTR_DIST2) {
-        const float dx = x - a.p[0], dy = y - a.p[1], dz = z - a.p[2];
-        return (dx * dx + dy * dy) + dz * dz;
-    }
-    return ((a.p[0] * x + a.p[1] * y) + a.p[2] * z) + a.p[3];
-}
+// ... are an expression of the centre: attr_of_pos<KIND>, gs_consensus_host.h's one copy (the consensus kernel and its host loop use it too)
 // fmaxf / fminf as gs_abi.h means them: a NaN operand, quiet OR signalling, is missing data, and the result is a NaN only when both
 // are.  (v_max_f32 / v_min_f32 alone, which __builtin_fmaxf compiles to, turn a signalling NaN into a quiet one instead of dropping it.)
 __device__ __forceinline__ float attr_fmax(float a, float b) { return a != a ? b : b != b ? a : __builtin_fmaxf(a, b); }

@@ -72,6 +72,7 @@ GS_PART_RECORD = 0x7
 GS_ATTR_NAMES = ("POS_X", "POS_Y", "POS_Z", "OPACITY_LOGIT", "LOG_SCALE_MIN", "LOG_SCALE_MAX", "LOG_SCALE_SUM", "ANISOTROPY", "DC_R", "DC_G",
                  "DC_B", "DIST2", "PLANE", "COVER_HITS", "COVER_MAX_WEIGHT", "COVER_SUM")
 GS_ATTR_MAX_BINS = 1024
+GS_CONSENSUS_MAX = 4096
 
 # neighbourhoods
 GS_ERR_CAPACITY = -8
@@ -106,6 +107,7 @@ ABI_SYMBOLS = ("gs_last_error", "gs_abi_version", "gs_create", "gs_destroy", "gs
                "gs_cluster_label", "gs_cluster_read", "gs_state_cluster", "gs_state_cluster_linked",
                "gs_knn_search", "gs_knn_read", "gs_state_knn",
                "gs_pair_moments", "gs_pair_moments_host",
+               "gs_attr_consensus", "gs_consensus_host", "gs_attr_gather", "gs_planes_through",
                "gs_pack_encode", "gs_pack_decode", "gs_pack_save", "gs_pack_load", "gs_pack_logit_table", "gs_export_packed", "gs_upload_packed",
                "gs_append_packed", "gs_set_option", "gs_slab_width", "gs_assemble_slabs", "gs_sort_pairs_u32",
                "gs_exclusive_scan_u32")
@@ -333,6 +335,10 @@ def load():
     L.gs_state_knn.argtypes = [vp, f32, f32, u32, u32, u32, u32, u32, ctypes.POINTER(u64)]
     L.gs_pair_moments.argtypes = [vp, u32, u32, vp, f32, ctypes.POINTER(GsPairMoments)]
     L.gs_pair_moments_host.argtypes = [vp, vp, vp, u64, vp, vp, u32, u32, f32, ctypes.POINTER(GsPairMoments)]
+    L.gs_attr_consensus.argtypes = [vp, u32, vp, u32, f32, f32, u32, u32, vp, ctypes.POINTER(u64)]
+    L.gs_consensus_host.argtypes = [vp, vp, vp, u64, vp, u32, u32, u32, vp, u32, f32, f32, vp, ctypes.POINTER(u64)]
+    L.gs_attr_gather.argtypes = [vp, ctypes.POINTER(GsAttr), vp, u64, vp]
+    L.gs_planes_through.argtypes = [vp, u32, vp]
     L.gs_pack_encode.argtypes = [vp, u64, i32, vp, vp, vp, ctypes.POINTER(u64)]
     L.gs_pack_decode.argtypes = [vp, vp, vp, u64, i32, vp]
     L.gs_pack_save.argtypes = [ctypes.c_char_p, vp, u64, i32]

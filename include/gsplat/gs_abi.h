@@ -1033,6 +1033,51 @@ int32_t gs_pair_moments(gs_ctx* ctx, uint32_t mask, uint32_t value, const uint32
 int32_t gs_pair_moments_host(const float* px, const float* py, const float* pz, uint64_t n, const uint32_t* partner, const uint8_t* state,
                              uint32_t mask, uint32_t value, float max_dist2, struct gs_pair_moments* out);
 
+/* ---- consensus: score many plane or ball hypotheses in one pass; the plane through three points --------------
+ * gsplat.moments fits the least-squares plane through a selection that exists; FINDING the floor, a wall or a table top in an
+ * unselected, cluttered capture is a robust fit (RANSAC): many candidate planes, each scored by how many splats lie within a distance
+ * of it, the best kept.  One gs_attr_histogram or gs_state_attr pass per candidate streams the scene once per candidate; this call
+ * streams it ONCE for up to GS_CONSENSUS_MAX candidates.  With GS_ATTR_DIST2 the same call answers "where is the densest ball of
+ * radius r?" (the main object; a coarse seed for the registration).  The reference has no counterpart (a viewer).
+ *     counts[j]  the number of splats i with (s_i & mask) == value and lo <= v_j(i) && v_j(i) <= hi, both ends INCLUSIVE
+ *     v_j(i)     the GS_ATTR_PLANE or GS_ATTR_DIST2 value of splat i (splat attributes, above) with p = params[4 j .. 4 j + 3]:
+ *                PLANE ((p[0] x + p[1] y) + p[2] z) + p[3];  DIST2 d = position - p[0..2], (dx dx + dy dy) + dz dz, p[3] ignored --
+ *                one f32 rounding per operation, no contraction, so a host restates every count (tests/consensus_restate.py)
+ *     *matched   (may be NULL) the splats that pass the filter
+ * The expression is the whole rule.  Unlike a gs_attr, the parameters need NOT be finite: a NaN parameter or coordinate makes v a NaN,
+ * a NaN is in no range, the splat is not counted for that hypothesis.  lo > hi is a valid empty range (every count 0); infinite lo and
+ * hi are allowed.  Counts are integers: they do not depend on the grid, the order, slabs or borrowers, and two runs agree bit for bit.
+ * params, counts and matched are HOST pointers: f32[h][4], u64[h], u64.
+ * Filter, drain, ordering, borrowers and slabs are gs_attr_summary's: (mask, value) as gs_state_count, above 0xFF refused, (0, 0)
+ * matches every splat and works on a ctx without GS_FLAG_SPLAT_STATE; the call completes the ring's frames first, runs on the ctx's
+ * stream, returns when done and is neither a frame nor an upload.  GS_ERR_NO_SCENE before any upload; N == 0: all zeros, GS_OK.  A NaN
+ * lo or hi, h outside 1 .. GS_CONSENSUS_MAX, a kind other than GS_ATTR_PLANE / GS_ATTR_DIST2, null params or counts:
+ * GS_ERR_INVALID_ARGUMENT, a message that names the call, nothing written.
+ * gs_consensus_host runs the same loop (csrc/gs_consensus_host.h) over n values per HOST plane: no ctx, no GPU, the same code.  state:
+ * u8[n], may be NULL when the filter is (0, 0).  Its refusals are the same; n == 0 gives zeros. */
+#define GS_CONSENSUS_MAX 4096u
+int32_t gs_attr_consensus(gs_ctx* ctx, uint32_t kind, const float* params, uint32_t h, float lo, float hi, uint32_t mask, uint32_t value,
+                          uint64_t* counts, uint64_t* matched);
+int32_t gs_consensus_host(const float* px, const float* py, const float* pz, uint64_t n, const uint8_t* state, uint32_t mask, uint32_t value,
+                          uint32_t kind, const float* params, uint32_t h, float lo, float hi, uint64_t* counts, uint64_t* matched);
+/* The values of m GIVEN splats, in any order, repeats allowed: dst[g] = the value of splat ids[g] exactly as gs_attr_read returns it
+ * (every kind; the COVER_* kinds read the ctx's planes as the other attribute calls do).  ids and dst are HOST pointers.  The ids are
+ * checked before anything is launched: an id >= N is GS_ERR_INVALID_ARGUMENT, the message names the index, nothing is written.  m == 0:
+ * GS_OK.  4 B up and 4 B down per id, in trips through the ctx's scratch.  Drain and ordering as gs_attr_read. */
+int32_t gs_attr_gather(gs_ctx* ctx, const gs_attr* attr, const uint32_t* ids, uint64_t m, float* dst);
+/* Host only (no ctx, no GPU): the plane through each of h point triples, points f32[h][9] = (a, b, c) in the order given, as
+ * GS_ATTR_PLANE parameters, params f32[h][4].  Everything in DOUBLE, one rounding per operation as written, no contraction:
+ *     u = b - a,  w = c - a
+ *     n = (u1 w2 - u2 w1,  u2 w0 - u0 w2,  u0 w1 - u1 w0)
+ *     len = sqrt((n0 n0 + n1 n1) + n2 n2)
+ *     m = n / len                                       (three divisions)
+ *     d = -((m0 a0 + m1 a1) + m2 a2)
+ * Sign: if the component of m with the largest magnitude -- the FIRST such component on a tie -- is negative, m and d are negated.
+ * params = (m0, m1, m2, d), each rounded to f32.  If len is not finite or not greater than 0 (a repeated point, collinear points, a
+ * non-finite coordinate) all four are NaN: such a hypothesis counts nothing in gs_attr_consensus, so a sampler needs no special case.
+ * h == 0: GS_OK; null points or params with h > 0: GS_ERR_INVALID_ARGUMENT. */
+int32_t gs_planes_through(const float* points, uint32_t h, float* params);
+
 /* Tuning / profiling knobs. */
 #define GS_OPT_BLEND_ABLATION 1  /* bit 3 (8): the workgroup-per-tile blend kernel at tiles 16 and 32 (identical results; default = one
                                     wave per 8x8 pixel block); bit 2 (4): every blend kernel without its two parking culls (live box,
