@@ -2,6 +2,7 @@
 #pragma once
 #include "gs_device.h"
 #include "gs_consensus_host.h" // GsAttrDev
+#include "gs_grid_math.h"      // GsNeighGrid
 
 void gs_launch_repack(const void* d_aos, uint32_t n, uint32_t first, const GsScene& s, hipStream_t st); // record r -> splat first + r
 void gs_launch_ply_chunk(const void* d_raw, uint32_t m, uint32_t first, const GsPlyTable& t, const GsScene& s, hipStream_t st);
@@ -150,11 +151,7 @@ void gs_launch_moments(uint32_t planes, const uint8_t* state, const float* p0, c
 #define GS_PAIRS_SLOT_WORDS 448 // >= 21 * 20 + 2, a multiple of 32 words
 void gs_launch_pairs(const uint8_t* state, const float* px, const float* py, const float* pz, const uint32_t* partner, uint32_t n, uint32_t mask,
                      uint32_t value, float max_d2, unsigned long long* slots, uint32_t grid, hipStream_t st);
-// k_neigh.hip: neighbourhoods (gs_neigh.hip).  The cell grid over the finite sources: cell coordinate of x on axis k =
-// clamp((int)floorf((x - lo[k]) * inv_h), 0, g[k] - 1), key = cz << bxy | cy << bx | cx (bx, bxy - bx: the bits of g[0] - 1,
-// g[1] - 1).  `none` = g[2] << bxy is above every key and marks a splat that is no member (filter, non-finite coordinate): it sorts
-// last.  The {start, end} table has `blocks` = none >> shift entries, one per 2^shift consecutive keys (shift 0: one per cell).
-struct GsNeighGrid { float lo[3]; float inv_h; uint32_t g[3]; uint32_t bx, bxy, shift, blocks, none; };
+// k_neigh.hip: neighbourhoods (gs_neigh.hip) over the cell grid of the finite sources (GsNeighGrid, gs_grid_math.h).
 // out: 16 words the caller initialises ([0..2] all ones, the rest 0): min / max order-preserving keys of x, y, z over the finite
 // sources, then sources, finite sources, queries, finite queries.  state null: every splat passes both filters.  gate (u32[n], or
 // null: no gate): a splat is a query -- in keys: a member -- only if its word there is +inf's (a refining gs_knn_search; null for
@@ -280,3 +277,17 @@ struct GsCoverDev { // a gs_cover_region as the kernel reads it
     const uint8_t* mask;     // device u8[height][width] of the canvas, or null
 };
 void gs_launch_coverage(const GsLists& L, uint32_t bx0, uint32_t by0, uint32_t nbx, uint32_t nby, const GsCoverDev& r, void* planes, hipStream_t st);
+// k_merge.hip: the cell merge (gs_merge.hip; every expression is gs_merge_math.h's).  keys: (cell key, id) per splat, `none` for a splat
+// that is not eligible.  heads: flag[t] = 1 where a run of equal sorted keys begins (a byte plane for gs_launch_select_*).  runs: run r
+// spans heads[r] .. heads[r + 1] (n behind the last); flag[r] = 1 when it is merged (key < none, at least min_members long); stats
+// (three words, zeroed by the caller): eligible, largest run, members of merged runs.  sums: groups first .. first + count, group g =
+// merged run mruns[g], one wave each, into sums[(g - first) * 64]; group_of (u32[n]) and member (u8[n]) may be null.  finish: count
+// groups' sums -> 320-byte records.
+void gs_launch_merge_keys(const uint8_t* state, const GsScene& s, uint32_t n, uint32_t mask, uint32_t value, const GsNeighGrid& g, uint32_t* keys,
+                          uint32_t* vals, hipStream_t st);
+void gs_launch_merge_heads(const uint32_t* keys, uint32_t n, uint8_t* flag, hipStream_t st);
+void gs_launch_merge_runs(const uint32_t* keys, const uint32_t* heads, uint32_t runs, uint32_t n, uint32_t none, uint32_t min_members, uint8_t* flag,
+                          uint32_t* stats, hipStream_t st);
+void gs_launch_merge_sums(const uint32_t* vals, const uint32_t* heads, uint32_t runs, const uint32_t* mruns, uint32_t first, uint32_t count,
+                          uint32_t nsorted, const GsScene& s, uint32_t n, double* sums, uint32_t* group_of, uint8_t* member, hipStream_t st);
+void gs_launch_merge_finish(const double* sums, uint32_t count, void* d_aos, hipStream_t st);

@@ -26,30 +26,6 @@ int32_t neigh_plane(gs_ctx* c, hipStream_t st) {
     return GS_OK;
 }
 
-static uint32_t bits_of(uint32_t v) { uint32_t b = 0; while (b < 32 && (v >> b)) ++b; return b; }
-// The grid for sources with the finite bounds lo .. hi and a radius r: the smallest cell edge h >= 1.0011 r (k_neigh.hip: the
-// margin the cell expression's rounding needs) that leaves at most 1024 cells per axis; the key layout and the table's blocks.
-static void choose_grid(const float lo[3], const float hi[3], float radius, GsNeighGrid* g, float* edge) {
-    double ext[3], widest = 0.0;
-    for (int k = 0; k < 3; ++k) { ext[k] = (double)hi[k] - (double)lo[k]; widest = std::max(widest, ext[k]); }
-    float h = radius * 1.0011f;
-    h = std::max(h, (float)(widest / 1024.0 * 1.000001));
-    if (!(h >= 1e-30f)) h = widest > 0.0 ? 1e-30f : 1.0f; // (all sources in one point and radius 0: any edge does)
-    if (!std::isfinite(h)) h = 3.0e38f;
-    for (int k = 0; k < 3; ++k) {
-        g->g[k] = (uint32_t)std::min(std::floor(ext[k] / (double)h) + 1.0, 1024.0);
-        g->lo[k] = lo[k];
-    }
-    g->inv_h = 1.0f / h;
-    g->bx = bits_of(g->g[0] - 1u);
-    g->bxy = g->bx + bits_of(g->g[1] - 1u);
-    g->none = g->g[2] << g->bxy; // <= 2^30
-    const uint32_t kb = bits_of(g->none - 1u);
-    g->shift = kb > 24u ? kb - 24u : 0u; // < bxy, so `none` is a multiple of 2^shift
-    g->blocks = g->none >> g->shift;     // <= 2^24
-    *edge = h;
-}
-
 int32_t neigh_bounds(gs_ctx* c, const uint8_t* state, uint32_t smask, uint32_t svalue, uint32_t qmask, uint32_t qvalue, uint32_t hb[16], const uint32_t* gate) {
     gs_ctx::Neigh& s = c->ng;
     const int32_t rc = s.bounds.reserve(16);
@@ -66,7 +42,7 @@ int32_t neigh_bounds(gs_ctx* c, const uint8_t* state, uint32_t smask, uint32_t s
 // One filter's members in cell order: keys, the pair sort, the records (and the cell table when `table`).
 static int32_t sorted_records(gs_ctx* c, const uint8_t* state, uint32_t mask, uint32_t value, const uint32_t* gate, const GsNeighGrid& g, void* rec, void* table) {
     gs_ctx::Neigh& s = c->ng;
-    const uint32_t passes = (bits_of(g.none) + 7) / 8; // the keys reach `none` itself (no member)
+    const uint32_t passes = (neigh_bits_of(g.none) + 7) / 8; // the keys reach `none` itself (no member)
     GsSortPair sorted;
     const int32_t rc = private_sort(c, c->n, passes, [&] { gs_launch_neigh_keys(state, c->scene, c->n, mask, value, gate, g, s.keysA, s.valsA, c->stream); }, &sorted);
     if (rc != GS_OK) return rc;
@@ -106,7 +82,7 @@ int32_t neigh_build(gs_ctx* c, const char* who, float radius, uint32_t smask, ui
     float lo[3], hi[3];
     for (int k = 0; k < 3; ++k) { lo[k] = pk_okey_value(hb[k]); hi[k] = pk_okey_value(hb[3 + k]); }
     GsNeighGrid& g = b->g;
-    choose_grid(lo, hi, radius, &g, &b->cell_edge);
+    neigh_choose_grid(lo, hi, radius * 1.0011f, &g, &b->cell_edge); // h >= 1.0011 r: the margin the cell expression's rounding needs (k_neigh.hip)
 
     // 2. sources, then queries, in cell order
     rc = s.table.reserve((uint64_t)g.blocks * 8);

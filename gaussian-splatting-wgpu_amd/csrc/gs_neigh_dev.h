@@ -6,12 +6,7 @@
 #include "gs_kernels.h"
 #include "gs_state_sum.h"
 
-__device__ __forceinline__ bool neigh_finite(float x, float y, float z) {
-    return fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(z) < INFINITY; // (a NaN fails)
-}
-__device__ __forceinline__ int neigh_cell(float x, float lo, float inv_h, uint32_t g) {
-    return (int)fminf(fmaxf(floorf((x - lo) * inv_h), 0.0f), (float)(g - 1u)); // (fmaxf: a NaN product -- 0 * inf -- is cell 0)
-}
+// (neigh_finite, neigh_cell and neigh_key are gs_grid_math.h's, which gs_kernels.h includes: the cell merge's host twin compiles them too)
 
 // What the candidates kernel, the query pass and the clusters' edge pass read of the sources.  nrec bounds what a table entry may
 // name (it never names more: gs_neigh_records_kernel).

@@ -231,6 +231,10 @@ struct gs_ctx {
     // allocated (NaN 0x7FC00000 / GS_KNN_NONE) on first use and dropped with the scene like the count plane; k: that of the last
     // search without GS_KNN_REFINE (0: none yet), which a refinement must repeat.  A search works in ng's scratch.
     struct Knn { DevBuf<uint32_t> dist2, nearest; uint32_t k = 0; } kn;
+    // cell merge (gs_merge.hip): the byte planes of the run heads, the merged runs and the members; the compaction's counts; the run
+    // begins, the merged runs, the members' ids, the group numbers and the statistics words; one trip of sums and of records.  Grown
+    // on demand; the sort works in ng's scratch.
+    struct { Scratch<uint8_t> flags, member, rec; Scratch<uint32_t> counts, heads, mruns, ids, group_of, stats; Scratch<double> sums; } mg;
     Event ev[GS_EV_RING][GS_STAGE_COUNT + 1]; // ring of per-frame stage brackets (GS_FLAG_TIMING)
     bool have_events = false;
     uint64_t timed_from = 0; // first frame index included in the stage means

@@ -88,12 +88,6 @@ void gs_launch_neigh_bounds(const uint8_t* state, const GsScene& s, uint32_t n, 
     hipLaunchKernelGGL(gs_neigh_bounds_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, state, s.px, s.py, s.pz, n, smask, svalue, qmask, qvalue, gate, out);
 }
 
-__device__ __forceinline__ uint32_t neigh_key(const GsNeighGrid& g, float x, float y, float z) {
-    const uint32_t cx = (uint32_t)neigh_cell(x, g.lo[0], g.inv_h, g.g[0]), cy = (uint32_t)neigh_cell(y, g.lo[1], g.inv_h, g.g[1]),
-                   cz = (uint32_t)neigh_cell(z, g.lo[2], g.inv_h, g.g[2]);
-    return (cz << g.bxy) | (cy << g.bx) | cx;
-}
-
 __global__ __launch_bounds__(256) void gs_neigh_keys_kernel(const uint8_t* __restrict__ state, const float* __restrict__ px, const float* __restrict__ py,
                                                              const float* __restrict__ pz, uint32_t n, uint32_t mask, uint32_t value,
                                                              const uint32_t* __restrict__ gate, GsNeighGrid g, uint32_t* __restrict__ keys,

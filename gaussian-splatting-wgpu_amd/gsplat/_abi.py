@@ -74,6 +74,11 @@ GS_ATTR_NAMES = ("POS_X", "POS_Y", "POS_Z", "OPACITY_LOGIT", "LOG_SCALE_MIN", "L
 GS_ATTR_MAX_BINS = 1024
 GS_CONSENSUS_MAX = 4096
 
+# cell merge
+GS_MERGE_SUM_DOUBLES = 64
+GS_MERGE_NONE = 0xFFFFFFFF  # group_of of a splat that is in no merged group
+GS_MERGE_DEFAULT_MAX_MEMBERS = 65536
+
 # neighbourhoods
 GS_ERR_CAPACITY = -8
 GS_NEIGH_LIMIT_NONE = 0xFFFFFFFF  # gs_neigh.limit: count every neighbour
@@ -108,6 +113,7 @@ ABI_SYMBOLS = ("gs_last_error", "gs_abi_version", "gs_create", "gs_destroy", "gs
                "gs_knn_search", "gs_knn_read", "gs_state_knn",
                "gs_pair_moments", "gs_pair_moments_host",
                "gs_attr_consensus", "gs_consensus_host", "gs_attr_gather", "gs_planes_through",
+               "gs_cell_merge", "gs_cell_merge_device", "gs_cell_merge_host",
                "gs_pack_encode", "gs_pack_decode", "gs_pack_save", "gs_pack_load", "gs_pack_logit_table", "gs_export_packed", "gs_upload_packed",
                "gs_append_packed", "gs_set_option", "gs_slab_width", "gs_assemble_slabs", "gs_sort_pairs_u32",
                "gs_exclusive_scan_u32")
@@ -232,6 +238,16 @@ class GsPairMoments(ctypes.Structure):  # pq: row-major (a, b)
                 ("pp", GsExact * 3), ("qq", GsExact * 3)]
 
 
+class GsMerge(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("mask", ctypes.c_uint32), ("value", ctypes.c_uint32), ("cell", ctypes.c_float),
+                ("min_members", ctypes.c_uint32), ("max_members", ctypes.c_uint32), ("op", ctypes.c_uint32), ("bits", ctypes.c_uint32)]
+
+
+class GsMergeInfo(ctypes.Structure):
+    _fields_ = [("eligible", ctypes.c_uint64), ("groups", ctypes.c_uint64), ("members", ctypes.c_uint64), ("largest", ctypes.c_uint64),
+                ("cells", ctypes.c_uint32 * 3), ("cell_edge", ctypes.c_float)]
+
+
 class GsPackInfo(ctypes.Structure):
     _fields_ = [("count", ctypes.c_uint64), ("chunks", ctypes.c_uint64), ("file_bytes", ctypes.c_uint64), ("nonfinite", ctypes.c_uint64)]
 
@@ -339,6 +355,9 @@ def load():
     L.gs_consensus_host.argtypes = [vp, vp, vp, u64, vp, u32, u32, u32, vp, u32, f32, f32, vp, ctypes.POINTER(u64)]
     L.gs_attr_gather.argtypes = [vp, ctypes.POINTER(GsAttr), vp, u64, vp]
     L.gs_planes_through.argtypes = [vp, u32, vp]
+    L.gs_cell_merge.argtypes = [vp, ctypes.POINTER(GsMerge), vp, u64, vp, vp, ctypes.POINTER(GsMergeInfo)]
+    L.gs_cell_merge_device.argtypes = [vp, ctypes.POINTER(GsMerge), vp, u64, vp, vp, ctypes.POINTER(GsMergeInfo)]
+    L.gs_cell_merge_host.argtypes = [vp, vp, u64, ctypes.POINTER(GsMerge), vp, u64, vp, vp, ctypes.POINTER(GsMergeInfo)]
     L.gs_pack_encode.argtypes = [vp, u64, i32, vp, vp, vp, ctypes.POINTER(u64)]
     L.gs_pack_decode.argtypes = [vp, vp, vp, u64, i32, vp]
     L.gs_pack_save.argtypes = [ctypes.c_char_p, vp, u64, i32]

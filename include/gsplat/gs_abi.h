@@ -1078,6 +1078,78 @@ int32_t gs_attr_gather(gs_ctx* ctx, const gs_attr* attr, const uint32_t* ids, ui
  * h == 0: GS_OK; null points or params with h > 0: GS_ERR_INVALID_ARGUMENT. */
 int32_t gs_planes_through(const float* points, uint32_t h, float* params);
 
+/* ---- cell merge: one moment-matched splat per grid cell ---------------------------------------------------------
+ * Every edit above keeps or drops splats; this one makes FEWER of them without punching holes: the splats of one cell of a uniform
+ * grid become one splat with their weighted mean, covariance and colour (decimation by merging; gsplat.simplify builds "simplify the
+ * scene to a tenth" on it with gs_append_splats_device and gs_compact).  The reference has no counterpart (a viewer).
+ * All f32 operations take one rounding per written operation, no contraction; all f64 operations are plain + - *, only the finishing
+ * uses /, sqrt and log.  The whole definition is compiled from one header, csrc/gs_merge_math.h, by the kernels and the host twin.
+ * PER SPLAT i (f32; record floats: position 0..2, log-scales 4..6, rot 8..11, opacity logit 12, SH 16..63):
+ *     a_i      the projection's sigmoid of the logit (process_gaussians.wgsl:282-294, both branches, gs_exp)
+ *     sigma_k  gs_exp(s_k)
+ *     Sig_i    the six entries xx xy xz yy yz zz of the projection's 3D covariance with scale modifier 1 (:127-162: normalised
+ *              quaternion, M = S R, transpose(M) M), the same expression tree
+ *     A_i      max(sigma0 sigma1, max(sigma0 sigma2, sigma1 sigma2)), max(a, b) = a < b ? b : a: the cross-section of the two largest
+ *              axes, so a flat surfel weighs by its area
+ *     w_i      a_i * A_i
+ * ELIGIBLE: (s_i & mask) == value, a finite position, w_i finite and > 0, six finite Sig_i entries.  Everything else is never grouped,
+ * marked or changed.
+ * GRID: the bounds are those of the splats that pass the filter with a finite position (the neighbourhoods' bounds pass); the cell
+ * coordinate and key are the neighbourhoods' (clamp((int)floorf((x - lo) * inv_h), 0, g - 1), x lowest); the edge is `cell` itself,
+ * raised to widest / 1024 * 1.000001 (double, rounded to f32) when an axis would hold more than 1024 cells; info.cell_edge reports it.
+ * GROUPS: the eligible splats of one cell in ascending index.  A cell with at least min_members (>= 2) is MERGED; merged groups are
+ * numbered 0 .. G-1 in ascending cell key.  If the fullest cell holds more than max_members (0: GS_MERGE_DEFAULT_MAX_MEMBERS) the call
+ * returns GS_ERR_CAPACITY with the edge in the message before anything is written: the loop over a group's members is sequential.
+ * SUMS: GS_MERGE_SUM_DOUBLES doubles per merged group, from 0.0 over the members in ascending index; c = the position of the member
+ * with the smallest index, as double; d = (double)p - c; w as double:
+ *     [0] W += w   [1..3] S_k += w * d_k   [4..9] M_kl: t = d_k * d_l; t = (double)Sig_kl + t; t = w * t; M_kl += t  (xx xy xz yy yz zz)
+ *     [10..57] H_j += w * (double)sh_j, j = 3 * coefficient + channel (record float 16 + 4 * coefficient + channel)
+ *     [58] members   [59] first index   [60..62] c   [63] 0
+ * FINISHING (f64): mu = S / W; position = (float)(c + mu); C_kl = M_kl / W - mu_k * mu_l; eigenvalues l1 >= l2 >= l3 of C by a fixed
+ * number of cyclic Jacobi sweeps, each floored to 1e-30; log-scales (float)(0.5 * ln l_k), largest first; the eigenvectors are the
+ * columns of a rotation (the third flipped when the determinant is negative), the quaternion (r, x, y, z) has unit norm and r >= 0;
+ * A' = sqrt(l1 * l2), alpha' = min(0.99, W / A'), logit = (float)ln(alpha' / (1 - alpha')): opacity x area is conserved, k coincident
+ * copies of a splat merge into that splat with opacity min(0.99, k a); SH'_j = (float)(H_j / W) (world frame: no rotation); the
+ * padding floats are 0.  The sums are pinned bit for bit; the records up to the last places of /, sqrt and log.
+ * THE CALLS.  gs_cell_merge writes G records of GS_SPLAT_RECORD_BYTES in group order to HOST memory, gs_cell_merge_device to DEVICE
+ * memory; sums (double[G][64]) and group_of (u32[N]: the group's number or GS_MERGE_NONE) are HOST pointers and may be NULL; info may
+ * be NULL.  After the outputs are complete, op (0: none, else GS_STATE_*) with bits is applied to the members of merged groups.  A NULL
+ * record pointer with cap_records 0 is the COUNT-ONLY mode: only info is filled, nothing is marked.  cap_records < G:
+ * GS_ERR_INVALID_ARGUMENT, info filled, nothing written or marked.  With op == 0 the calls work on a borrower of gs_share_splats as
+ * gs_neigh_count does; with an op they have gs_state_region's rules: the borrower carries the owner's plane, the members are marked in
+ * THAT plane (owner and every borrower see it), and contexts the host drives itself are the host's to drain first.
+ * Prologue, drain, ordering and slabs are gs_neigh_count's;
+ * the calls use the neighbourhoods' scratch and leave every plane alone.  GS_ERR_NO_SCENE before any upload; N == 0: zeros, GS_OK.
+ * Refused with GS_ERR_INVALID_ARGUMENT and a message that names the call: a wrong struct_size, a cell that is not finite or <= 0,
+ * min_members < 2, an op above GS_STATE_ASSIGN, bits above 0xFF or without an op, a filter above 0xFF, and an op or a filter other
+ * than (0, 0) on a ctx without GS_FLAG_SPLAT_STATE.
+ * gs_cell_merge_host runs the same computation over n HOST records (80 floats each) without a ctx or a GPU; state (u8[n]) may be NULL
+ * when the filter is (0, 0) and op is 0, and is marked in place otherwise. */
+#define GS_MERGE_SUM_DOUBLES 64u
+#define GS_MERGE_NONE 0xFFFFFFFFu
+#define GS_MERGE_DEFAULT_MAX_MEMBERS 65536u
+typedef struct gs_merge {          /* 32 bytes */
+    uint32_t struct_size;          /* = sizeof(gs_merge) */
+    uint32_t mask, value;          /* the filter: (s & mask) == value */
+    float    cell;                 /* the requested cell edge: finite, > 0 */
+    uint32_t min_members;          /* >= 2: cells with fewer eligible splats are left alone */
+    uint32_t max_members;          /* 0 = GS_MERGE_DEFAULT_MAX_MEMBERS */
+    uint32_t op, bits;             /* 0, or GS_STATE_* applied to the merged members */
+} gs_merge;
+typedef struct gs_merge_info {     /* 48 bytes */
+    uint64_t eligible;             /* splats that take part in the grouping */
+    uint64_t groups;               /* G: merged groups = records */
+    uint64_t members;              /* splats in merged groups */
+    uint64_t largest;              /* eligible splats of the fullest cell */
+    uint32_t cells[3]; float cell_edge; /* the grid and the edge that were used */
+} gs_merge_info;
+int32_t gs_cell_merge(gs_ctx* ctx, const gs_merge* params, void* aos320, uint64_t cap_records, double* sums, uint32_t* group_of,
+                      gs_merge_info* info);
+int32_t gs_cell_merge_device(gs_ctx* ctx, const gs_merge* params, void* d_aos320, uint64_t cap_records, double* sums, uint32_t* group_of,
+                             gs_merge_info* info);
+int32_t gs_cell_merge_host(const void* records, uint8_t* state, uint64_t n, const gs_merge* params, void* aos320, uint64_t cap_records,
+                           double* sums, uint32_t* group_of, gs_merge_info* info);
+
 /* Tuning / profiling knobs. */
 #define GS_OPT_BLEND_ABLATION 1  /* bit 3 (8): the workgroup-per-tile blend kernel at tiles 16 and 32 (identical results; default = one
                                     wave per 8x8 pixel block); bit 2 (4): every blend kernel without its two parking culls (live box,
