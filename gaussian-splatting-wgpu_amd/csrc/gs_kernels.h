@@ -207,6 +207,26 @@ void gs_launch_knn_query(const void* qrec, uint32_t nq, uint32_t first_block, ui
 // gs_state_knn: the state pass with the float-range membership (v >= lo && v <= hi) == inside over the dist2 plane read as words
 void gs_launch_state_knn(uint8_t* state, const uint32_t* dist2, uint32_t n, float lo, float hi, uint32_t inside, uint32_t op, uint32_t bits,
                          uint32_t where_mask, uint32_t where_value, unsigned long long* matched, hipStream_t st);
+// k_surface.hip: surface (gs_surface.hip) over the neighbourhoods' grid, records and slices.  The two planes are 16-byte records per
+// splat: nrm = {nx, ny, nz, count as a word}, eig = {l0, l1, l2, 0}.
+// a whole estimate's start: NaN 0x7FC00000 in the six floats, count 0
+void gs_launch_surface_init(uint32_t n, void* nrm, void* eig, hipStream_t st);
+// the query pass over workgroups [first_block, first_block + blocks) of 256 sorted queries: the ten words count, S[3], M[6] of sorted
+// query t, word k at out[id * 10 + k] (by_id: the kept plane) or at out[k * word_stride + t - 256 first_block] (the slice's scratch,
+// word_stride >= 256 blocks); scale: 2^(16 - E); *unresolved += the queries that end with count < 3
+void gs_launch_surface_query(const void* qrec, uint32_t nq, uint32_t first_block, uint32_t blocks, const void* srec, const uint32_t* skeys, const void* table,
+                             uint32_t nrec, const GsNeighGrid& g, float r2, float scale, uint32_t n, int64_t* out, bool by_id, uint64_t word_stride,
+                             uint32_t* unresolved, hipStream_t st);
+// sorted queries first .. first + count: their ten words, addressed as the query pass wrote them (first = 256 first_block), -> the
+// two records of their splats; unscale: 2^(2 (E - 16)); orient: towards toward[3]
+void gs_launch_surface_finish(const void* qrec, uint32_t first, uint32_t count, uint32_t n, const int64_t* in, bool by_id, uint64_t word_stride,
+                              double unscale, bool orient, const float toward[3], void* nrm, void* eig, hipStream_t st);
+// xyz[3 i ..] = the first three floats of record i, w[i] = its fourth word (each may be null)
+void gs_launch_surface_unpack(const void* rec, uint32_t n, float* xyz, uint32_t* w, hipStream_t st);
+// gs_state_surface: the state pass with the float-range membership over a feature of ONE plane's record (the eig plane for kinds below
+// GS_SURFACE_FACING, the nrm plane for the others)
+void gs_launch_state_surface(uint8_t* state, const void* plane, uint32_t n, uint32_t kind, float lo, float hi, uint32_t inside, const float axis[3], uint32_t op,
+                             uint32_t bits, uint32_t where_mask, uint32_t where_value, unsigned long long* matched, hipStream_t st);
 // k_export.hip: the splat edits (gs_export.hip).  Selection = splats with (s & mask) == value in ascending order: `counts` holds
 // gs_select_blocks(n) + 1 words (one per 1024 splats; after the launch their exclusive prefix, the total last), `ids` the total.
 uint32_t gs_select_blocks(uint32_t n);

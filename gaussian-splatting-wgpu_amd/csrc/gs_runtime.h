@@ -231,6 +231,17 @@ struct gs_ctx {
     // allocated (NaN 0x7FC00000 / GS_KNN_NONE) on first use and dropped with the scene like the count plane; k: that of the last
     // search without GS_KNN_REFINE (0: none yet), which a refinement must repeat.  A search works in ng's scratch.
     struct Knn { DevBuf<uint32_t> dist2, nearest; uint32_t k = 0; } kn;
+    // surface (gs_surface.hip): two 16-byte records per splat, {nx, ny, nz, count} and {l0, l1, l2, 0}, allocated (NaN 0x7FC00000 /
+    // count 0) on first use and dropped with the scene like the nearest-neighbour planes; sums: the ten i64 per splat of the last
+    // estimate with GS_SURFACE_KEEP_SUMS (have_sums: they are that estimate's), dropped with the planes; the slice's sums of an
+    // estimate without the flag and the staging of a read, grown on demand.  An estimate works in ng's scratch.
+    struct Surface {
+        DevBuf<> nrm, eig;
+        DevBuf<int64_t> sums;
+        bool have_sums = false;
+        Scratch<int64_t> slice;
+        Scratch<uint32_t> out;
+    } sf;
     // cell merge (gs_merge.hip): the byte planes of the run heads, the merged runs and the members; the compaction's counts; the run
     // begins, the merged runs, the members' ids, the group numbers and the statistics words; one trip of sums and of records.  Grown
     // on demand; the sort works in ng's scratch.
@@ -394,6 +405,8 @@ inline int32_t private_sort_fault(gs_ctx* c, uint32_t* fault) {
 int32_t cluster_planes(gs_ctx* c, hipStream_t st);
 // gs_knn.hip: the nearest-neighbour planes of `c`, allocated and set to their initial reading (on `st`) by the first call that needs them
 int32_t knn_planes(gs_ctx* c, hipStream_t st);
+// gs_surface.hip: the surface planes of `c`, allocated and set to their initial reading (on `st`) by the first call that needs them
+int32_t surface_planes(gs_ctx* c, hipStream_t st);
 // gs_export.hip: the splat edits' selection: counts the splats with (s & mask) == value and, with want_ids, leaves their indices,
 // ascending, in c->ex.ids
 int32_t edit_select(gs_ctx* c, uint32_t mask, uint32_t value, bool want_ids, uint64_t* total);

@@ -198,6 +198,31 @@ GS_EXPORT int32_t gs_state_knn(gs_ctx* c, float lo, float hi, uint32_t inside, u
     }, matched);
 }
 
+// Select by a surface feature: the pass over one of the two surface planes (gs_surface.hip) -- the eigenvalues for the four shape
+// kinds, the normal and count for the others --, with gs_state_knn's float range on the feature (gs_surface_math.h: sf_feature).
+GS_EXPORT int32_t gs_state_surface(gs_ctx* c, const gs_surface_range* r, uint32_t where_mask, uint32_t where_value, uint32_t op, uint32_t bits,
+                                   uint64_t* matched) {
+    int32_t rc = resident_check(c, "gs_state_surface", Plane::always);
+    if (rc != GS_OK) return rc;
+    if (!r) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_surface: null range");
+    if (r->struct_size != sizeof(gs_surface_range))
+        return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_surface: struct_size %u != %zu", r->struct_size, sizeof(gs_surface_range));
+    if (r->kind > GS_SURFACE_COUNT) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_surface: unknown kind %u (0 .. %u)", r->kind, GS_SURFACE_COUNT);
+    rc = state_check_op("gs_state_surface", op, bits);
+    if (rc != GS_OK) return rc;
+    if (r->lo != r->lo || r->hi != r->hi)
+        return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_surface: range [%g, %g] has a bound that is not a number", (double)r->lo, (double)r->hi);
+    if (where_mask > 0xFFu) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_surface: where_mask 0x%x does not fit the state byte", where_mask);
+    rc = resident_drain(c, true);
+    if (rc != GS_OK) return rc;
+    rc = surface_planes(c, c->stream);
+    if (rc != GS_OK) return rc;
+    const void* rec = r->kind < GS_SURFACE_FACING ? c->sf.eig.get() : c->sf.nrm.get();
+    return state_counted(c, [&](unsigned long long* slots) {
+        gs_launch_state_surface(plane(c), rec, c->n, r->kind, r->lo, r->hi, r->inside, r->axis, op, bits, where_mask, where_value, slots, c->stream);
+    }, matched);
+}
+
 // Select by cluster size: gs_state_neigh's pass over the size plane (gs_cluster.hip), which the first call that needs it allocates.
 GS_EXPORT int32_t gs_state_cluster(gs_ctx* c, uint32_t min_size, uint32_t max_size, uint32_t inside, uint32_t where_mask, uint32_t where_value, uint32_t op,
                                    uint32_t bits, uint64_t* matched) {

@@ -92,6 +92,12 @@ GS_KNN_MAX_K = 32
 GS_KNN_NONE = 0xFFFFFFFF  # nearest of a splat without an accepted source (and of a splat that was no query)
 GS_KNN_REFINE = 0x1       # gs_knn.flags: only the splats whose dist2 reads +inf now are queried and written
 
+# surface
+GS_SURFACE_ORIENT, GS_SURFACE_KEEP_SUMS = 0x1, 0x2  # gs_surface.flags
+GS_SURFACE_SUM_WORDS = 10  # count, S x y z, M xx xy xz yy yz zz
+(GS_SURFACE_VARIATION, GS_SURFACE_PLANARITY, GS_SURFACE_LINEARITY, GS_SURFACE_SPHERICITY, GS_SURFACE_FACING, GS_SURFACE_FACING_SIGNED,
+ GS_SURFACE_COUNT) = range(7)  # gs_surface_range.kind
+
 # packed scenes (gs_export_packed's order)
 GS_PACK_ORDER_INDEX, GS_PACK_ORDER_MORTON = 0, 1
 
@@ -114,6 +120,7 @@ ABI_SYMBOLS = ("gs_last_error", "gs_abi_version", "gs_create", "gs_destroy", "gs
                "gs_pair_moments", "gs_pair_moments_host",
                "gs_attr_consensus", "gs_consensus_host", "gs_attr_gather", "gs_planes_through",
                "gs_cell_merge", "gs_cell_merge_device", "gs_cell_merge_host",
+               "gs_surface_estimate", "gs_surface_read", "gs_surface_read_sums", "gs_state_surface", "gs_surface_host",
                "gs_pack_encode", "gs_pack_decode", "gs_pack_save", "gs_pack_load", "gs_pack_logit_table", "gs_export_packed", "gs_upload_packed",
                "gs_append_packed", "gs_set_option", "gs_slab_width", "gs_assemble_slabs", "gs_sort_pairs_u32",
                "gs_exclusive_scan_u32")
@@ -248,6 +255,22 @@ class GsMergeInfo(ctypes.Structure):
                 ("cells", ctypes.c_uint32 * 3), ("cell_edge", ctypes.c_float)]
 
 
+class GsSurface(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("radius", ctypes.c_float), ("flags", ctypes.c_uint32), ("src_mask", ctypes.c_uint32),
+                ("src_value", ctypes.c_uint32), ("qry_mask", ctypes.c_uint32), ("qry_value", ctypes.c_uint32), ("toward", ctypes.c_float * 3),
+                ("max_candidates", ctypes.c_uint64), ("reserved", ctypes.c_uint64)]
+
+
+class GsSurfaceInfo(ctypes.Structure):
+    _fields_ = [("queried", ctypes.c_uint64), ("sources", ctypes.c_uint64), ("candidates", ctypes.c_uint64), ("unresolved", ctypes.c_uint64),
+                ("cells", ctypes.c_uint32 * 3), ("cell_edge", ctypes.c_float)]
+
+
+class GsSurfaceRange(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("kind", ctypes.c_uint32), ("lo", ctypes.c_float), ("hi", ctypes.c_float),
+                ("inside", ctypes.c_uint32), ("axis", ctypes.c_float * 3)]
+
+
 class GsPackInfo(ctypes.Structure):
     _fields_ = [("count", ctypes.c_uint64), ("chunks", ctypes.c_uint64), ("file_bytes", ctypes.c_uint64), ("nonfinite", ctypes.c_uint64)]
 
@@ -358,6 +381,11 @@ def load():
     L.gs_cell_merge.argtypes = [vp, ctypes.POINTER(GsMerge), vp, u64, vp, vp, ctypes.POINTER(GsMergeInfo)]
     L.gs_cell_merge_device.argtypes = [vp, ctypes.POINTER(GsMerge), vp, u64, vp, vp, ctypes.POINTER(GsMergeInfo)]
     L.gs_cell_merge_host.argtypes = [vp, vp, u64, ctypes.POINTER(GsMerge), vp, u64, vp, vp, ctypes.POINTER(GsMergeInfo)]
+    L.gs_surface_estimate.argtypes = [vp, ctypes.POINTER(GsSurface), ctypes.POINTER(GsSurfaceInfo)]
+    L.gs_surface_read.argtypes = [vp, vp, vp, vp, u64, ctypes.POINTER(u64)]
+    L.gs_surface_read_sums.argtypes = [vp, vp, u64, ctypes.POINTER(u64)]
+    L.gs_state_surface.argtypes = [vp, ctypes.POINTER(GsSurfaceRange), u32, u32, u32, u32, ctypes.POINTER(u64)]
+    L.gs_surface_host.argtypes = [vp, vp, u64, ctypes.POINTER(GsSurface), vp, vp, vp, vp, ctypes.POINTER(GsSurfaceInfo)]
     L.gs_pack_encode.argtypes = [vp, u64, i32, vp, vp, vp, ctypes.POINTER(u64)]
     L.gs_pack_decode.argtypes = [vp, vp, vp, u64, i32, vp]
     L.gs_pack_save.argtypes = [ctypes.c_char_p, vp, u64, i32]

@@ -1150,6 +1150,122 @@ int32_t gs_cell_merge_device(gs_ctx* ctx, const gs_merge* params, void* d_aos320
 int32_t gs_cell_merge_host(const void* records, uint8_t* state, uint64_t n, const gs_merge* params, void* aos320, uint64_t cap_records,
                            double* sums, uint32_t* group_of, gs_merge_info* info);
 
+/* ---- surface: per-splat normals and shape from neighbourhood covariance --------------------------------------
+ * A count, a label and a k-th distance are one scalar per splat; a plane fit and a consensus are one global answer.  "Select what
+ * lies on a surface", "select the horizontal surfaces" (floor, table tops and steps at once), "find the floaters that are dense but
+ * have no surface", oriented normals for export and the point-to-plane variant of a registration need the LOCAL geometry: the
+ * covariance of every splat's neighbourhood, its three eigenvalues and the eigenvector of the smallest.  The reference has no
+ * counterpart (a viewer).
+ * THE DEFINITION.  Sources are the splats j with (s_j & src_mask) == src_value, queries the splats i with (s_i & qry_mask) ==
+ * qry_value.  With the neighbourhoods' expression unchanged
+ *     d = p_j - p_i per component;  d2 = (dx dx + dy dy) + dz dz;  r2 = radius * radius
+ * -- one f32 rounding per written operation, no contraction, r2 ONE f32 product, the comparison <= INCLUSIVE -- let, for a query i,
+ *     D_i = the set of sources j != i with d2(i, j) <= r2.
+ * Self is excluded by index, not by distance.  A NaN or infinite coordinate fails every comparison: such a splat has no neighbours
+ * and is nobody's.
+ * THE SUMS ARE INTEGERS, so nothing depends on the order in which the device visits anything.  Let E be frexpf(radius)'s exponent,
+ * 2^(E-1) <= radius < 2^E, and s = 2^(16 - E) as an f32.  For an accepted j
+ *     q_a = (int32) rintf(d_a * s),   a = x, y, z
+ * -- the product by a power of two is exact, rintf rounds half to even: this is the ONE quantisation, its step between 2^-16 and
+ * 2^-15 of the radius.  Per query
+ *     count = |D_i| (u32);   S_a = the sum of q_a (3 x i64);   M_ab = the sum of q_a q_b for xx xy xz yy yz zz (6 x i64).
+ * THE BOUND: |d_a| <= radius (1 + 2^-22) <= 2^E, so |q_a| <= 2^16 + 1 and |q_a q_b| <= 2^32 + 2^18 + 1; with fewer than 2^30 sources
+ * (the cell sort's limit) no sum reaches 2^63: there is no wrap and no saturation rule.
+ * THE FINISHING is f64, one header (csrc/gs_surface_math.h) compiled by the device and the host, in the cell merge's order of
+ * operations with n = count:
+ *     mu_a = (double)S_a / n;   C_ab = (double)M_ab / n - mu_a * mu_b        (i64 -> double rounds to nearest even)
+ * then the cell merge's fixed number of cyclic Jacobi sweeps (the same two functions, no second copy).  The eigenvalues are ordered
+ * l0 >= l1 >= l2, each clamped with l >= 0 ? l : 0, scaled to world units by the exact power of two 2^(2 (E - 16)) and rounded ONCE
+ * to f32.  The normal is the eigenvector column of l2, flipped in f64 so that its component of largest magnitude is positive (a tie:
+ * the lowest axis), then each component rounded once to f32.  With GS_SURFACE_ORIENT, in f32 on the rounded normal,
+ *     e = toward - p_i;   t = (nx ex + ny ey) + nz ez;   the normal is negated when t < 0 and kept when t is 0 or NaN.
+ * WHAT THE PLANES READ.  A query with count < 3 reads NaN with exactly the bits 0x7FC00000 in all six floats and keeps its count:
+ * UNRESOLVED.  A splat that is not a query, or a query with a non-finite coordinate, reads NaN and count 0.  Sums, count and info
+ * compare bit for bit between two runs, a slab ctx, a borrower of gs_share_splats, gs_surface_host and a brute-force host
+ * restatement (tests/surface_restate.py); normal and eig bit for bit between the device and gs_surface_host.
+ * THE PLANES are normal f32[N][3], eig f32[N][3] and count u32[N] (held as two 16-byte records per splat) and belong to the ctx the
+ * call is made on (the root of a ring; a borrower keeps its own), like the nearest-neighbour planes.  They are allocated by the first
+ * call that needs them and read NaN / count 0 before the first estimate; gs_surface_estimate overwrites them as a whole; they are
+ * DROPPED -- they read as before the first estimate again -- by every gs_upload_*, gs_share_splats and gs_compact, whatever drops the
+ * count plane and nothing else.  State calls and transforms leave them untouched: they describe the positions and states at the time
+ * of the estimate, and a host that moves or re-filters splats estimates again.  A call that fails for any reason -- budget,
+ * allocation, a refused argument -- leaves the planes and the kept sums as they were.
+ * WORK.  An estimate builds the neighbourhoods' grid over the sources at the radius given, computes `candidates` exactly and, above
+ * max_candidates (0: GS_NEIGH_DEFAULT_CANDIDATES), returns GS_ERR_CAPACITY with both numbers in the message; the query pass is issued
+ * in the count's slices (GS_NEIGH_SLICE_CANDIDATES), each followed by its finishing pass.  Measured rates: profiles/surface.txt.
+ * Prologue, ordering and refusals are gs_knn_search's: each (mask, value) as gs_state_count, above 0xFF refused, (0, 0) matches every
+ * splat and is accepted on a ctx without GS_FLAG_SPLAT_STATE, any other filter on such a ctx is refused.  Every call first completes
+ * all frames enqueued on the ctx's ring, runs on the ctx's stream and returns when done; none is a frame or an upload.
+ * GS_ERR_NO_SCENE before any upload; N == 0: zero results, GS_OK.  gs_surface_estimate and the two reads work on a borrower;
+ * gs_state_surface has gs_state_region's rules.  GS_ERR_INVALID_ARGUMENT and a message that names the number: a wrong struct_size, a
+ * radius that is not above 0, negative or not finite, a radius * radius that is not finite in f32, 16 - E > 127 (s must be a finite
+ * normal f32), unknown flag bits, reserved != 0. */
+#define GS_SURFACE_ORIENT 0x1u     /* gs_surface.flags: the normals point towards `toward` */
+#define GS_SURFACE_KEEP_SUMS 0x2u  /* gs_surface.flags: keep the ten integers per splat for gs_surface_read_sums */
+#define GS_SURFACE_SUM_WORDS 10u   /* count, S x y z, M xx xy xz yy yz zz */
+typedef struct gs_surface {        /* 56 bytes */
+    uint32_t struct_size;          /* = sizeof(gs_surface) */
+    float    radius;               /* finite, > 0; r2 = radius * radius, ONE f32 product, must be finite */
+    uint32_t flags;                /* GS_SURFACE_ORIENT | GS_SURFACE_KEEP_SUMS */
+    uint32_t src_mask, src_value;  /* SOURCES: splats j with (s_j & src_mask) == src_value */
+    uint32_t qry_mask, qry_value;  /* QUERIES: splats i with (s_i & qry_mask) == qry_value */
+    float    toward[3];            /* GS_SURFACE_ORIENT: the point the normals face (a viewpoint); ignored otherwise */
+    uint64_t max_candidates;       /* work budget, 0 = GS_NEIGH_DEFAULT_CANDIDATES */
+    uint64_t reserved;             /* 0 */
+} gs_surface;
+typedef struct gs_surface_info {   /* 48 bytes */
+    uint64_t queried, sources;     /* splats that pass the two filters */
+    uint64_t candidates;           /* sum over the queries of the sources in the 27 cells around them, self included */
+    uint64_t unresolved;           /* queries that end with count < 3, those with a non-finite coordinate included */
+    uint32_t cells[3]; float cell_edge; /* the grid that was used (diagnostic; no result depends on it) */
+} gs_surface_info;
+/* Estimates into the planes.  info (may be NULL) is written whenever the grid was built, also when the budget refuses the call
+ * (queried, sources, candidates and the grid; unresolved is that of a completed estimate). */
+int32_t gs_surface_estimate(gs_ctx* ctx, const gs_surface* q, gs_surface_info* info);
+/* The planes in HOST memory in splat order, with gs_knn_read's conventions: normal (3 N floats), eig (3 N floats) and count (N words)
+ * may each be NULL, all NULL: only *n (= N) is written (query); cap < N: GS_ERR_INVALID_ARGUMENT, the message names the count needed,
+ * nothing is written. */
+int32_t gs_surface_read(gs_ctx* ctx, float* normal, float* eig, uint32_t* count, uint64_t cap, uint64_t* n);
+/* GS_SURFACE_SUM_WORDS x i64 per splat in splat order: count, S[3], M[6]; zeros for a splat that was no query.  Valid only after an
+ * estimate with GS_SURFACE_KEEP_SUMS: the sums are dropped with the planes and by the next estimate without the flag, and the call is
+ * then refused (GS_ERR_INVALID_ARGUMENT).  sums NULL: only *n is written; cap < N (in splats): refused as above. */
+int32_t gs_surface_read_sums(gs_ctx* ctx, int64_t* sums, uint64_t cap, uint64_t* n);
+/* Applies `op` with `bits` exactly as gs_state_region does, to the splats that pass (s & where_mask) == where_value and for which
+ *     (v >= lo && v <= hi) == (inside != 0)
+ * -- gs_state_knn's rule --, v computed from the stored f32 planes with one rounding per written operation:
+ *     GS_SURFACE_VARIATION      l2 / ((l0 + l1) + l2)         surface variation: 0 on a plane, 1/3 for an isotropic blob
+ *     GS_SURFACE_PLANARITY      (l1 - l2) / l0
+ *     GS_SURFACE_LINEARITY      (l0 - l1) / l0
+ *     GS_SURFACE_SPHERICITY     l2 / l0
+ *     GS_SURFACE_FACING         fabsf((nx ax + ny ay) + nz az), axis used as given (not normalised)
+ *     GS_SURFACE_FACING_SIGNED  the same without the fabsf
+ *     GS_SURFACE_COUNT          the count as f32
+ * A NaN (also 0 / 0) is in no range.  A NaN lo or hi, an unknown kind and a wrong struct_size are refused; infinite bounds are
+ * allowed, lo > hi is a valid empty range.  Needs GS_FLAG_SPLAT_STATE; *matched (may be NULL) as for gs_state_region.  One streaming
+ * pass over 17 bytes per splat. */
+#define GS_SURFACE_VARIATION 0u
+#define GS_SURFACE_PLANARITY 1u
+#define GS_SURFACE_LINEARITY 2u
+#define GS_SURFACE_SPHERICITY 3u
+#define GS_SURFACE_FACING 4u
+#define GS_SURFACE_FACING_SIGNED 5u
+#define GS_SURFACE_COUNT 6u
+typedef struct gs_surface_range {  /* 32 bytes */
+    uint32_t struct_size;          /* = sizeof(gs_surface_range) */
+    uint32_t kind;                 /* GS_SURFACE_VARIATION .. GS_SURFACE_COUNT */
+    float    lo, hi;               /* neither a NaN */
+    uint32_t inside;               /* 0: select what is outside the range */
+    float    axis[3];              /* the two FACING kinds; ignored otherwise */
+} gs_surface_range;
+int32_t gs_state_surface(gs_ctx* ctx, const gs_surface_range* r, uint32_t where_mask, uint32_t where_value, uint32_t op, uint32_t bits,
+                         uint64_t* matched);
+/* The same computation without a ctx or a GPU, compiled from the same header: pos f32[n][3] (x y z interleaved), state u8[n] (may be
+ * NULL when both filters are (0, 0)), normal f32[n][3], eig f32[n][3], count u32[n], sums i64[n][10] (may be NULL; GS_SURFACE_KEEP_SUMS
+ * is not needed), info (may be NULL).  It tests all pairs: info.candidates = finite queries x finite sources, cells = 1 1 1,
+ * cell_edge = 0.  The refusals are gs_surface_estimate's, a filter above 0xFF and a null array with n > 0 included. */
+int32_t gs_surface_host(const float* pos, const uint8_t* state, uint64_t n, const gs_surface* q, float* normal, float* eig, uint32_t* count,
+                        int64_t* sums, gs_surface_info* info);
+
 /* Tuning / profiling knobs. */
 #define GS_OPT_BLEND_ABLATION 1  /* bit 3 (8): the workgroup-per-tile blend kernel at tiles 16 and 32 (identical results; default = one
                                     wave per 8x8 pixel block); bit 2 (4): every blend kernel without its two parking culls (live box,
