@@ -249,6 +249,7 @@ int32_t wait_one(gs_ctx* c) {
     if (!c) return fail(GS_ERR_INVALID_ARGUMENT, "gs_wait: null ctx");
     HIP_TRY(hipSetDevice(c->cfg.device));
     uint32_t dropped = 0; // frames enqueued before the last one that overflowed: their output was truncated and is gone
+    const bool fresh = c->pending; // a frame was enqueued since the last wait: what this one finds has not been reported yet
     for (int attempt = 0; attempt < 8; ++attempt) {
         HIP_TRY(hipStreamSynchronize(c->stream));
         c->pending = false;
@@ -269,7 +270,9 @@ int32_t wait_one(gs_ctx* c) {
         const uint64_t need = std::max<uint64_t>(I, max_I), need_rows = std::max<uint64_t>(rows_last, max_rows);
         if (!last_over && need <= c->capacity && need_rows <= c->row_cap) break;
         // a frame overflowed the (key,value) capacity or the row-item arena: grow geometrically; re-render the last frame if it was one of them
-        if (need >= (1ull << 30)) return fail(GS_ERR_CAPACITY, "%llu intersections exceed the 2^30 limit", (unsigned long long)need);
+        // (a refused frame stays the member's last one -- its report still says I > capacity -- until the member renders again: the
+        // refusal is reported by the wait that follows the frame, not by every later one)
+        if (need >= (1ull << 30)) return fresh ? fail(GS_ERR_CAPACITY, "%llu intersections exceed the 2^30 limit", (unsigned long long)need) : GS_OK;
         uint64_t want = c->capacity, want_rows = c->row_cap;
         if (need > c->capacity) want = std::min<uint64_t>(std::max<uint64_t>(need + need / 4, c->capacity * 2), (1ull << 30) - 1);
         if (need_rows > c->row_cap) want_rows = std::max<uint64_t>(need_rows + need_rows / 4, c->row_cap * 2);

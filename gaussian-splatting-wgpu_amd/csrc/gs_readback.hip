@@ -248,7 +248,7 @@ GS_EXPORT int32_t gs_get_stats(gs_ctx* root, gs_stats* out) {
         out->num_visible = c->h_rep->num_visible;
         out->num_intersections = c->h_rep->num_intersections;
         out->capacity = c->capacity;
-        out->max_intersections_seen = std::max<uint64_t>(c->max_I_seen, c->h_rep->num_intersections);
+        out->max_intersections_seen = std::max<uint64_t>(over_ring(root, [](const gs_ctx* m) { return m->max_I_seen; }, true), c->h_rep->num_intersections);
         out->truncated_frames = over_ring(root, [](const gs_ctx* m) { return m->truncated_frames; });
         out->frames_in_flight = (uint32_t)root->shadows.size() + 1u;
         out->graph_frames = over_ring(root, [](const gs_ctx* m) { return m->gr.frames; });

@@ -228,7 +228,9 @@ __global__ __launch_bounds__(256) void gs_emit_kernel(const uint4* __restrict__ 
         const uint32_t x = (xx < wmain) ? xa + xx : f.ntx;
         const uint32_t y = (y_b & 0xFFFFu) + yy;
         const uint32_t key = (y * f.ntx + x) * 1000u + (y_b >> 16);
-        const uint32_t dst = first_off + e;
+        // 64 bits: past 2^32 intersections first_off is the scan's saturated 0xFFFFFFFF (or close below 2^32), and a 32-bit sum
+        // wraps to a slot that passes the clamp and overwrites the head of the list
+        const unsigned long long dst = (unsigned long long)first_off + e;
         if (dst < f.capacity) {
             keys[dst] = key;
             values[dst] = s_gid[w][lo];

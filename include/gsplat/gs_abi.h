@@ -13,7 +13,8 @@
  * Frames in flight: a whole-canvas ctx on its own stream keeps up to GS_OPT_FRAMES_IN_FLIGHT (default 3) frames in flight -- a
  * frame enqueued while the previous one is still on the device is rendered by a SHADOW of the ctx (own stream and per-frame
  * arrays, the same resident splats), gs_render taking turns over that ring.  With K frames enqueued: gs_wait waits for ALL of
- * them (and reports a capacity overflow of an earlier one as GS_ERR_TRUNCATED: only the last frame can be re-rendered);
+ * them (and reports a capacity overflow of an earlier one as GS_ERR_TRUNCATED: only the last frame can be re-rendered; a frame of
+ * the batch over the 2^30 limit makes it GS_ERR_CAPACITY instead, see there);
  * gs_read_rgba8, gs_read_buffer, gs_device_ptr and gs_get_stats describe the LAST frame enqueued (its ring member);
  * gs_render_host / gs_wait_ticket address a frame of their own.  A host that calls gs_wait after every gs_render (as
  * Renderer.animate does) never has more than one frame in flight and sees none of this.  Device work of one ring member is
@@ -41,7 +42,21 @@ extern "C" {
 #define GS_ERR_NO_SCENE (-5)         /* gs_render before gs_upload_splats                           */
 #define GS_ERR_NO_FRAME (-6)         /* read-back before any gs_render                              */
 #define GS_ERR_DEVICE_FAULT (-7)     /* an in-kernel bounded spin gave up (decoupled look-back)     */
-#define GS_ERR_CAPACITY (-8)         /* intersections exceed the hard limit (2^30, radix_sort.wgsl:220-221) */
+#define GS_ERR_CAPACITY (-8)         /* intersections exceed the hard limit (2^30, radix_sort.wgsl:220-221).  gs_wait: a frame enqueued
+                                        since the last gs_wait -- the last one or an earlier one, on any ring member -- has I >= 2^30.
+                                        The device sums instance counts in saturating 32-bit arithmetic: such a frame reports
+                                        min(I, 2^32 - 1), never a wrapped count.  It is not re-rendered and nothing is grown for it
+                                        (a last frame that ALSO overflowed the row-item arena is first rendered again with the arena, and
+                                        the lists for the instances that had fitted, grown: only then is its I known) and no frame of the
+                                        batch is counted in truncated_frames; its lists and image are truncated at the capacity and not
+                                        to be used.  After the refusal gs_get_stats reads, for a frame that was the last one enqueued,
+                                        num_intersections = min(I, 2^32 - 1), and max_intersections_seen >= that wherever in the batch or
+                                        the ring the frame was; capacity and row_capacity are what they were.  The refusal is reported
+                                        ONCE, by the gs_wait that follows the frame: later frames render normally, and a gs_wait that
+                                        finds no new over-limit frame returns GS_OK.  A batch that holds an over-limit frame returns
+                                        GS_ERR_CAPACITY whichever frame it was, also where an earlier frame of the batch merely overflowed
+                                        the capacity (GS_ERR_TRUNCATED is not reported then); the batch's last frame is complete unless
+                                        it is the refused one                                                                    */
 #define GS_ERR_TRUNCATED (-9)        /* gs_wait: a frame enqueued BEFORE the last one overflowed the (key,value) capacity; its
                                         output came from truncated lists and cannot be re-rendered (the last frame is complete and
                                         the capacity has been grown)                                                          */
@@ -114,9 +129,11 @@ typedef struct gs_stats {
     uint32_t depth_ordered;       /* 1 if the last frame used the depth-ordered pipeline (GS_OPT_EMIT_ORDER)   */
     uint64_t num_evaluated;       /* blend: (8x8 pixel block, entry) pairs evaluated after the block cull */
     uint64_t capacity;            /* entries the (key,value) arrays hold now                                  */
-    uint64_t max_intersections_seen; /* largest I of any frame since GS_OPT_RESET_TIMING (as of the last gs_wait) */
+    uint64_t max_intersections_seen; /* largest I of any frame of any ring member since GS_OPT_RESET_TIMING (as of the last gs_wait);
+                                        an I beyond 32 bits reads 2^32 - 1                                                  */
     uint64_t truncated_frames;    /* frames since GS_OPT_RESET_TIMING that overflowed the capacity and could not be re-rendered
-                                     (only possible when several frames are enqueued per gs_wait)                 */
+                                     (only possible when several frames are enqueued per gs_wait); a gs_wait that returns
+                                     GS_ERR_CAPACITY counts none                                                  */
     uint32_t tight_binning;       /* 1 if the last frame used the opacity-aware (tight) binning of the product path: its
                                      instance lists are then a subset of the reference's (GS_OPT_TILE_CULL)             */
     uint32_t frames_in_flight;    /* contexts of the ring gs_render alternates between now (GS_OPT_FRAMES_IN_FLIGHT)      */
@@ -193,7 +210,9 @@ int32_t gs_render_to(gs_ctx* ctx, const void* uniforms160, void* d_rgba8);
 /* Blocks until the frame is complete (the reference awaits onSubmittedWorkDone 8x per frame).
  * Reports device-side faults; grows the (key,value) capacity and re-renders if the frame overflowed.  When several
  * frames were enqueued since the last gs_wait and an EARLIER one overflowed, that frame cannot be re-rendered: the
- * capacity is grown for the following frames and GS_ERR_TRUNCATED is returned (the last frame is complete). */
+ * capacity is grown for the following frames and GS_ERR_TRUNCATED is returned (the last frame is complete).  A frame with 2^30
+ * or more intersections, wherever in the batch, is refused with GS_ERR_CAPACITY (see there for what the context holds afterwards);
+ * that takes precedence over GS_ERR_TRUNCATED, and the next gs_wait is clean. */
 int32_t gs_wait(gs_ctx* ctx);
 
 /* Pipelined presentation (a host that does not await every frame, unlike renderer.ts:394-587): as gs_render, plus an asynchronous
