@@ -151,6 +151,16 @@ void gs_launch_moments(uint32_t planes, const uint8_t* state, const float* p0, c
 #define GS_PAIRS_SLOT_WORDS 448 // >= 21 * 20 + 2, a multiple of 32 words
 void gs_launch_pairs(const uint8_t* state, const float* px, const float* py, const float* pz, const uint32_t* partner, uint32_t n, uint32_t mask,
                      uint32_t value, float max_d2, unsigned long long* slots, uint32_t grid, hipStream_t st);
+// k_plane_pairs.hip: plane pair moments (gs_plane_pairs.hip).  The exact sums of the point-to-plane normal equations over the pairs
+// (p_i, p_partner[i], normal[partner[i]]) of the splats that pass the filter: 29 tables of GS_EX_LIMBS limbs in gs_plane_pair_host.h's
+// order, then matched, paired.  partner as for gs_launch_pairs; normal: n 16-byte records {nx, ny, nz, any} on the device (the surface
+// plane, or a staged host array), gathered by partner id only.  pivot: three floats by value.  slots: GS_PLANE_PAIRS_SLOTS copies
+// GS_PLANE_PAIRS_SLOT_WORDS words apart, zeroed by the caller, who also adds them.  grid as for gs_launch_pairs.
+#define GS_PLANE_PAIRS_SLOTS 8
+#define GS_PLANE_PAIRS_SLOT_WORDS 608 // >= 29 * 20 + 2, a multiple of 32 words
+void gs_launch_plane_pairs(const uint8_t* state, const float* px, const float* py, const float* pz, const uint32_t* partner, const void* normal,
+                           uint32_t n, uint32_t mask, uint32_t value, float pvx, float pvy, float pvz, float max_d2, unsigned long long* slots,
+                           uint32_t grid, hipStream_t st);
 // k_neigh.hip: neighbourhoods (gs_neigh.hip) over the cell grid of the finite sources (GsNeighGrid, gs_grid_math.h).
 // out: 16 words the caller initialises ([0..2] all ones, the rest 0): min / max order-preserving keys of x, y, z over the finite
 // sources, then sources, finite sources, queries, finite queries.  state null: every splat passes both filters.  gate (u32[n], or

@@ -212,6 +212,9 @@ struct gs_ctx {
     struct { DevBuf<unsigned long long> slots; Scratch<float> vals[3]; } mo;
     // pair moments (gs_pairs.hip): the slot copies of the 21 limb tables, and the device copy of a host partner array; grown on demand
     struct { DevBuf<unsigned long long> slots; Scratch<uint32_t> partner; } pr;
+    // plane pair moments (gs_plane_pairs.hip): the slot copies of the 29 limb tables, and the device copy of a host normal array as
+    // 16-byte records {nx, ny, nz, 0} (the surface plane's layout); grown on demand.  A host partner array goes to pr.partner.
+    struct { DevBuf<unsigned long long> slots; Scratch<float> normal; } pp;
     // gs_coverage_* (gs_coverage.hip; root ctx): N x 16 B gs_coverage_rec, allocated and zeroed on first use, dropped with the scene
     DevBuf<> cov;
     // neighbourhoods (gs_neigh.hip): the count plane u32[N], allocated and zeroed on first use, dropped with the scene like cov; the

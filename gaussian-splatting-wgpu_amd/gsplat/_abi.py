@@ -117,7 +117,7 @@ ABI_SYMBOLS = ("gs_last_error", "gs_abi_version", "gs_create", "gs_destroy", "gs
                "gs_neigh_count", "gs_neigh_read", "gs_state_neigh",
                "gs_cluster_label", "gs_cluster_read", "gs_state_cluster", "gs_state_cluster_linked",
                "gs_knn_search", "gs_knn_read", "gs_state_knn",
-               "gs_pair_moments", "gs_pair_moments_host",
+               "gs_pair_moments", "gs_pair_moments_host", "gs_pair_plane_moments", "gs_pair_plane_moments_host",
                "gs_attr_consensus", "gs_consensus_host", "gs_attr_gather", "gs_planes_through",
                "gs_cell_merge", "gs_cell_merge_device", "gs_cell_merge_host",
                "gs_surface_estimate", "gs_surface_read", "gs_surface_read_sums", "gs_state_surface", "gs_surface_host",
@@ -243,6 +243,10 @@ class GsKnnInfo(ctypes.Structure):
 class GsPairMoments(ctypes.Structure):  # pq: row-major (a, b)
     _fields_ = [("matched", ctypes.c_uint64), ("paired", ctypes.c_uint64), ("sum_p", GsExact * 3), ("sum_q", GsExact * 3), ("pq", GsExact * 9),
                 ("pp", GsExact * 3), ("qq", GsExact * 3)]
+
+
+class GsPairPlaneMoments(ctypes.Structure):  # G: the upper triangle of sum g g^T, row-major; h: sum g_k r
+    _fields_ = [("matched", ctypes.c_uint64), ("paired", ctypes.c_uint64), ("G", GsExact * 21), ("h", GsExact * 6), ("rr", GsExact), ("d2", GsExact)]
 
 
 class GsMerge(ctypes.Structure):
@@ -374,6 +378,8 @@ def load():
     L.gs_state_knn.argtypes = [vp, f32, f32, u32, u32, u32, u32, u32, ctypes.POINTER(u64)]
     L.gs_pair_moments.argtypes = [vp, u32, u32, vp, f32, ctypes.POINTER(GsPairMoments)]
     L.gs_pair_moments_host.argtypes = [vp, vp, vp, u64, vp, vp, u32, u32, f32, ctypes.POINTER(GsPairMoments)]
+    L.gs_pair_plane_moments.argtypes = [vp, u32, u32, vp, vp, vp, f32, ctypes.POINTER(GsPairPlaneMoments)]
+    L.gs_pair_plane_moments_host.argtypes = [vp, vp, vp, u64, vp, vp, vp, u32, u32, vp, f32, ctypes.POINTER(GsPairPlaneMoments)]
     L.gs_attr_consensus.argtypes = [vp, u32, vp, u32, f32, f32, u32, u32, vp, ctypes.POINTER(u64)]
     L.gs_consensus_host.argtypes = [vp, vp, vp, u64, vp, u32, u32, u32, vp, u32, f32, f32, vp, ctypes.POINTER(u64)]
     L.gs_attr_gather.argtypes = [vp, ctypes.POINTER(GsAttr), vp, u64, vp]

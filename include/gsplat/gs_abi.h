@@ -1052,6 +1052,47 @@ int32_t gs_pair_moments(gs_ctx* ctx, uint32_t mask, uint32_t value, const uint32
 int32_t gs_pair_moments_host(const float* px, const float* py, const float* pz, uint64_t n, const uint32_t* partner, const uint8_t* state,
                              uint32_t mask, uint32_t value, float max_dist2, struct gs_pair_moments* out);
 
+/* Point-to-plane.  The point metric pulls every moving splat towards ONE fixed splat; on walls and floors sampled at different places
+ * the tangential part of each pair is sampling noise.  The plane metric penalises only the distance of p to the tangent plane of its
+ * partner, r = n . (q - p); its linearised normal equations over (omega, t) are sum g g^T x = sum g r with g = ((p - pivot) x n, n).
+ * gs_pair_plane_moments gives those sums exactly, with the arithmetic above; gsplat.register.fit_plane solves them in rational
+ * arithmetic.  n is the partner's normal: gs_surface_estimate over the FIXED splats, once -- they do not move during an alignment.
+ * A matched splat i (filter as above) with p = p_i, j = partner[i], q = p_j, n = normal[j] forms in f32, one rounding per written
+ * operation, no contraction:
+ *     u_a = p_a - pivot_a                       a = x, y, z
+ *     d_a = q_a - p_a,  d2 = (dx dx + dy dy) + dz dz          (gs_pair_moments' d and d2)
+ *     r   = (nx dx + ny dy) + nz dz             the signed distance of p to q's tangent plane
+ *     cx  = uy nz - uz ny;  cy = uz nx - ux nz;  cz = ux ny - uy nx
+ *     g   = (cx, cy, cz, nx, ny, nz)
+ * It is PAIRED when j < N, gs_pair_moments' acceptance holds (six finite coordinates, d2 <= max_dist2 inclusive, an overflowed d2
+ * passing only +inf), nx, ny, nz are finite (an unresolved or never-estimated normal is NaN 0x7FC00000) and cx, cy, cz, r are
+ * finite.  Only paired splats enter the 29 sums, each a gs_exact finished once:
+ *     G[21]   the upper triangle of sum g g^T, row-major (00, 01, .., 05, 11, .., 55)
+ *     h[6]    sum g_k r
+ *     rr      sum r r
+ *     d2      sum of the f32 value d2 (a d2 of +inf, possible only with max_dist2 = +inf, counts as what its bit pattern splits
+ *             into, 2^128)
+ * Every term but d2's is the exact product of two f32.  The 480 bytes do not depend on the grid, the order, slabs or borrowers; a
+ * host restates them with rational arithmetic (tests/plane_pairs_restate.py).
+ * partner: HOST u32[N], or NULL for the ctx's nearest plane.  normal: HOST f32[N][3], or NULL for the ctx's surface normal plane in
+ * place (never estimated or dropped: it reads NaN, nothing pairs, GS_OK).  Host arrays are first copied to the device (4 and 16 B per
+ * splat).  One streaming pass of 16 B per splat and a gather of 12 + 16 scattered bytes per matched splat with j < N.  Filter,
+ * drain, stream and refusals are gs_pair_moments'; also refused: a null pivot, a pivot component that is not finite.  A failed call
+ * leaves *out untouched.  gs_pair_plane_moments_host runs the same loop (csrc/gs_plane_pair_host.h) on host planes; partner and
+ * normal are required when n > 0. */
+struct gs_pair_plane_moments {      /* 480 bytes */
+    uint64_t matched, paired;
+    gs_exact G[21];                 /* upper triangle of sum g g^T, row-major */
+    gs_exact h[6];                  /* sum g_k r */
+    gs_exact rr, d2;                /* sum r^2, sum d2 */
+};
+int32_t gs_pair_plane_moments(gs_ctx* ctx, uint32_t mask, uint32_t value, const uint32_t* partner /* HOST u32[N] or NULL */,
+                              const float* normal /* HOST f32[N][3] or NULL */, const float pivot[3], float max_dist2,
+                              struct gs_pair_plane_moments* out);
+int32_t gs_pair_plane_moments_host(const float* px, const float* py, const float* pz, uint64_t n, const uint32_t* partner,
+                                   const float* normal /* f32[n][3] */, const uint8_t* state, uint32_t mask, uint32_t value,
+                                   const float pivot[3], float max_dist2, struct gs_pair_plane_moments* out);
+
 /* ---- consensus: score many plane or ball hypotheses in one pass; the plane through three points --------------
  * gsplat.moments fits the least-squares plane through a selection that exists; FINDING the floor, a wall or a table top in an
  * unselected, cluttered capture is a robust fit (RANSAC): many candidate planes, each scored by how many splats lie within a distance
