@@ -36,7 +36,7 @@ def build(force=False, verbose=False, profiling=False):
     os.makedirs(OUT, exist_ok=True)
     objdir = os.path.join(OUT, "obj_prof" if profiling else "obj")
     os.makedirs(objdir, exist_ok=True)
-    headers = [os.path.join(HERE, h) for h in ("gs_device.h", "gs_binning.h", "gs_kernels.h", "gs_tight.h", "gs_runtime.h", "gs_xform_math.h", "gs_grade_math.h", "gs_state_sum.h", "gs_neigh_dev.h", "gs_pack_math.h", "gs_exact_sum.h", "gs_exact_dev.h", "gs_pair_host.h", "gs_plane_pair_host.h", "gs_pack_host.h", "gs_file_writer.h", "gs_consensus_host.h", "gs_merge_math.h", "gs_grid_math.h", "gs_surface_math.h")] + [
+    headers = [os.path.join(HERE, h) for h in ("gs_device.h", "gs_binning.h", "gs_kernels.h", "gs_tight.h", "gs_runtime.h", "gs_xform_math.h", "gs_grade_math.h", "gs_state_sum.h", "gs_neigh_dev.h", "gs_pack_math.h", "gs_exact_sum.h", "gs_exact_dev.h", "gs_pair_host.h", "gs_plane_pair_host.h", "gs_pack_host.h", "gs_file_writer.h", "gs_consensus_host.h", "gs_merge_math.h", "gs_grid_math.h", "gs_surface_math.h", "gs_neigh_host.h")] + [
         os.path.join(HERE, "..", "..", "include", "gsplat", "gs_abi.h")]
 
     def compile_one(src):

@@ -14,7 +14,7 @@
 // anything in a frame: a context that never calls them launches exactly what it did before.
 #include <cstdlib>
 
-#include "gs_runtime.h"
+#include "gs_neigh_host.h"
 
 static_assert(sizeof(gs_cluster) == 32 && offsetof(gs_cluster, max_candidates) == 24, "gs_cluster layout");
 static_assert(sizeof(gs_cluster_info) == 56 && offsetof(gs_cluster_info, rounds) == 32 && offsetof(gs_cluster_info, cell_edge) == 48, "gs_cluster_info layout");
@@ -30,13 +30,10 @@ int32_t cluster_planes(gs_ctx* c, hipStream_t st) {
 
 GS_EXPORT int32_t gs_cluster_label(gs_ctx* c, const gs_cluster* q, gs_cluster_info* info) {
     const char* who = "gs_cluster_label";
-    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, "%s: null ctx", who);
-    if (!q) return fail(GS_ERR_INVALID_ARGUMENT, "%s: null query", who);
-    if (q->struct_size != sizeof(gs_cluster)) return fail(GS_ERR_INVALID_ARGUMENT, "%s: struct_size %u != %zu", who, q->struct_size, sizeof(gs_cluster));
-    int32_t rc = resident_check(c, who, Plane::filtered, q->mask, q->value);
-    if (rc != GS_OK) return rc;
     float r2;
-    rc = neigh_check_radius(who, q->radius, &r2);
+    int32_t rc = neigh_check_query(c, who, q);
+    if (rc != GS_OK) return rc;
+    rc = neigh_check_filters(c, who, q->mask, q->value, q->mask, q->value, q->radius, &r2); // (the one filter on both sides)
     if (rc != GS_OK) return rc;
     for (int k = 0; k < 2; ++k)
         if (q->reserved[k] != 0u) return fail(GS_ERR_INVALID_ARGUMENT, "%s: reserved[%d] = %u is not 0", who, k, q->reserved[k]);
@@ -48,37 +45,31 @@ GS_EXPORT int32_t gs_cluster_label(gs_ctx* c, const gs_cluster* q, gs_cluster_in
     if (info) *info = out;
     const uint32_t n = c->n;
     if (!n) { HIP_TRY(hipStreamSynchronize(c->stream)); return GS_OK; }
-    if (n >= (1u << 30)) return fail(GS_ERR_CAPACITY, "%s: %u splats, the cell sort takes fewer than 2^30", who, n); // (gs_sort_pairs_u32's limit)
     gs_ctx::Neigh& s = c->ng;
     NeighBuilt b;
-    rc = neigh_build(c, who, q->radius, q->mask, q->value, q->mask, q->value, &b);
+    rc = neigh_grid(c, who, q->radius, q->mask, q->value, q->mask, q->value, q->max_candidates, &b, [&](const NeighBuilt& b) {
+        out.members = b.sources;
+        out.candidates = b.candidates;
+        out.cell_edge = b.cell_edge;
+        for (int k = 0; k < 3; ++k) out.cells[k] = b.g.g[k];
+        if (info) *info = out;
+    });
     if (rc != GS_OK) return rc;
-    out.members = b.sources;
-    out.candidates = b.candidates;
-    out.cell_edge = b.cell_edge;
-    for (int k = 0; k < 3; ++k) out.cells[k] = b.g.g[k];
-    if (info) *info = out;
-    if (b.grid) {
-        rc = neigh_budget(who, b.candidates, q->max_candidates, q->radius);
-        if (rc != GS_OK) return rc;
-    }
 
     // the records are written: the sort's arrays are free.  Without a grid (no member with finite coordinates) init alone labels.
-    uint32_t *parent = s.keysA, *count = s.valsA, *words = s.bounds; // words[0]: the round's changed
+    uint32_t *parent = s.keysA, *count = s.valsA;
     gs_launch_cluster_init(b.state, c->scene, n, q->mask, q->value, parent, count, c->stream);
     HIP_TRY(hipGetLastError());
-    const uint32_t nrec = b.grid ? b.nsrc : 0u;
+    const uint32_t nrec = b.grid ? b.src.nrec : 0u;
     for (bool changed = nrec != 0u; changed;) {
         if (out.rounds >= GS_CLUSTER_MAX_ROUNDS)
             return fail(GS_ERR_DEVICE_FAULT, "%s: the edge pass still hooked after %u rounds (GS_CLUSTER_MAX_ROUNDS)", who, out.rounds);
-        HIP_TRY(hipMemsetAsync(words, 0, 4, c->stream));
-        neigh_slices(b.sums, [&](uint32_t b0, uint32_t blocks) {
-            gs_launch_cluster_edges(s.src, nrec, b0, blocks, s.skeys, s.table, b.g, r2, n, parent, words, c->stream);
-        });
-        gs_launch_cluster_flatten(s.src, nrec, n, parent, c->stream);
-        HIP_TRY(hipGetLastError());
-        uint32_t hooked = 0;
-        HIP_TRY(hipMemcpyAsync(&hooked, words, 4, hipMemcpyDeviceToHost, c->stream));
+        uint32_t hooked = 0; // the round's changed word
+        rc = neigh_open_word(c, [&](uint32_t* word) {
+            neigh_slices(b.sums, [&](uint32_t b0, uint32_t blocks) { gs_launch_cluster_edges(b, b0, blocks, r2, n, parent, word, c->stream); });
+            gs_launch_cluster_flatten(s.src, nrec, n, parent, c->stream);
+        }, &hooked);
+        if (rc != GS_OK) return rc;
         HIP_TRY(hipStreamSynchronize(c->stream));
         ++out.rounds;
         changed = hooked != 0u;
@@ -104,17 +95,7 @@ GS_EXPORT int32_t gs_cluster_label(gs_ctx* c, const gs_cluster* q, gs_cluster_in
 }
 
 GS_EXPORT int32_t gs_cluster_read(gs_ctx* c, uint32_t* labels, uint32_t* sizes, uint64_t cap, uint64_t* n) {
-    int32_t rc = resident_begin(c, "gs_cluster_read", Plane::none);
-    if (rc != GS_OK) return rc;
-    rc = cluster_planes(c, c->stream);
-    if (rc != GS_OK) return rc;
-    if (!n) return fail(GS_ERR_INVALID_ARGUMENT, "gs_cluster_read: null n");
-    *n = c->n;
-    if (!labels && !sizes) { HIP_TRY(hipStreamSynchronize(c->stream)); return GS_OK; }
-    if (cap < c->n)
-        return fail(GS_ERR_INVALID_ARGUMENT, "gs_cluster_read: %llu words per plane needed, the buffers hold %llu", (unsigned long long)c->n, (unsigned long long)cap);
-    if (c->n && labels) HIP_TRY(hipMemcpyAsync(labels, c->cl.label, (size_t)c->n * 4, hipMemcpyDeviceToHost, c->stream));
-    if (c->n && sizes) HIP_TRY(hipMemcpyAsync(sizes, c->cl.size, (size_t)c->n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return GS_OK;
+    void* const out[2] = {labels, sizes};
+    const auto planes = [](gs_ctx* c, const uint32_t* p[2]) { const int32_t rc = cluster_planes(c, c->stream); p[0] = c->cl.label; p[1] = c->cl.size; return rc; };
+    return plane_read(c, "gs_cluster_read", planes, "words per plane needed, the buffers hold", out, cap, n);
 }

@@ -174,12 +174,21 @@ void gs_launch_neigh_keys(const uint8_t* state, const GsScene& s, uint32_t n, ui
 // members' keys in sorted order (skeys, n allocated) and each block's run
 void gs_launch_neigh_records(const uint32_t* keys, const uint32_t* vals, uint32_t n, const GsNeighGrid& g, const GsScene& s, void* rec, uint32_t* skeys,
                              void* table, hipStream_t st);
-// sums[b]: candidates of sorted queries 256 b .. 256 b + 255; nrec: source records
-void gs_launch_neigh_cands(const void* qrec, uint32_t nq, const void* srec, const uint32_t* skeys, const void* table, uint32_t nrec, const GsNeighGrid& g,
-                           unsigned long long* sums, hipStream_t st);
+// What the candidates kernel, the query passes and the clusters' edge pass read of the sources: the records and their keys in cell
+// order, the {start, end} table.  nrec bounds what a table entry may name (it never names more: gs_neigh_records_kernel).
+struct NeighSources {
+    const float4* __restrict__ rec;
+    const uint32_t* __restrict__ keys;
+    const uint2* __restrict__ table;
+    uint32_t nrec;
+};
+// The built grid as a launch takes it (neigh_build fills it: NeighBuilt, gs_neigh_host.h): the sources, the nqry query records in
+// cell order (the sources' own when both filters are the same) and the grid.
+struct NeighView { NeighSources src{}; const float4* qrec = nullptr; uint32_t nqry = 0; GsNeighGrid g{}; };
+// sums[b]: candidates of sorted queries 256 b .. 256 b + 255
+void gs_launch_neigh_cands(const NeighView& v, unsigned long long* sums, hipStream_t st);
 // the query pass over workgroups [first_block, first_block + blocks) of 256 sorted queries: plane[id] = min(limit, count)
-void gs_launch_neigh_query(const void* qrec, uint32_t nq, uint32_t first_block, uint32_t blocks, const void* srec, const uint32_t* skeys, const void* table,
-                           uint32_t nrec, const GsNeighGrid& g, float r2, uint32_t limit, uint32_t n, uint32_t* plane, hipStream_t st);
+void gs_launch_neigh_query(const NeighView& v, uint32_t first_block, uint32_t blocks, float r2, uint32_t limit, uint32_t n, uint32_t* plane, hipStream_t st);
 // gs_state_neigh: the state pass with a membership read from the count plane (u32[n], 16-byte aligned)
 void gs_launch_state_neigh(uint8_t* state, const uint32_t* plane, uint32_t n, uint32_t min_count, uint32_t max_count, uint32_t inside, uint32_t op,
                            uint32_t bits, uint32_t where_mask, uint32_t where_value, unsigned long long* matched, hipStream_t st);
@@ -188,10 +197,10 @@ void gs_launch_state_neigh(uint8_t* state, const uint32_t* plane, uint32_t n, ui
 // parent / count of every splat: count = 1 for a member with a non-finite coordinate (it has no record), else 0
 void gs_launch_cluster_init(const uint8_t* state, const GsScene& s, uint32_t n, uint32_t mask, uint32_t value, uint32_t* parent, uint32_t* count,
                             hipStream_t st);
-// the edge pass over workgroups [first_block, first_block + blocks) of 256 sorted members (rec: nrec records, queries and sources
-// alike); *changed |= 1 when a root was hooked
-void gs_launch_cluster_edges(const void* rec, uint32_t nrec, uint32_t first_block, uint32_t blocks, const uint32_t* skeys, const void* table,
-                             const GsNeighGrid& g, float r2, uint32_t n, uint32_t* parent, uint32_t* changed, hipStream_t st);
+// the edge pass over workgroups [first_block, first_block + blocks) of 256 sorted members (v.src's records are queries and sources
+// alike: v.qrec is not read); *changed |= 1 when a root was hooked
+void gs_launch_cluster_edges(const NeighView& v, uint32_t first_block, uint32_t blocks, float r2, uint32_t n, uint32_t* parent, uint32_t* changed,
+                             hipStream_t st);
 void gs_launch_cluster_flatten(const void* rec, uint32_t nrec, uint32_t n, uint32_t* parent, hipStream_t st); // parent[id] = its root
 // count[root] += the records under it (flat trees); fold: one add per wave and distinct root
 void gs_launch_cluster_sizes(const void* rec, uint32_t nrec, uint32_t n, const uint32_t* parent, uint32_t* count, bool fold, hipStream_t st);
@@ -211,9 +220,8 @@ void gs_launch_knn_init(const uint8_t* state, uint32_t n, uint32_t mask, uint32_
 // the query pass over workgroups [first_block, first_block + blocks) of 256 sorted queries: dist2[id] = the k-th smallest accepted d2
 // or +inf, nearest[id] = the smallest id at the smallest accepted d2 or GS_KNN_NONE; *unresolved += the queries that end +inf.
 // k: 1 .. GS_KNN_MAX_K (k KB of dynamic LDS)
-void gs_launch_knn_query(const void* qrec, uint32_t nq, uint32_t first_block, uint32_t blocks, const void* srec, const uint32_t* skeys, const void* table,
-                         uint32_t nrec, const GsNeighGrid& g, float r2, uint32_t k, uint32_t n, uint32_t* dist2, uint32_t* nearest, uint32_t* unresolved,
-                         hipStream_t st);
+void gs_launch_knn_query(const NeighView& v, uint32_t first_block, uint32_t blocks, float r2, uint32_t k, uint32_t n, uint32_t* dist2, uint32_t* nearest,
+                         uint32_t* unresolved, hipStream_t st);
 // gs_state_knn: the state pass with the float-range membership (v >= lo && v <= hi) == inside over the dist2 plane read as words
 void gs_launch_state_knn(uint8_t* state, const uint32_t* dist2, uint32_t n, float lo, float hi, uint32_t inside, uint32_t op, uint32_t bits,
                          uint32_t where_mask, uint32_t where_value, unsigned long long* matched, hipStream_t st);
@@ -224,9 +232,8 @@ void gs_launch_surface_init(uint32_t n, void* nrm, void* eig, hipStream_t st);
 // the query pass over workgroups [first_block, first_block + blocks) of 256 sorted queries: the ten words count, S[3], M[6] of sorted
 // query t, word k at out[id * 10 + k] (by_id: the kept plane) or at out[k * word_stride + t - 256 first_block] (the slice's scratch,
 // word_stride >= 256 blocks); scale: 2^(16 - E); *unresolved += the queries that end with count < 3
-void gs_launch_surface_query(const void* qrec, uint32_t nq, uint32_t first_block, uint32_t blocks, const void* srec, const uint32_t* skeys, const void* table,
-                             uint32_t nrec, const GsNeighGrid& g, float r2, float scale, uint32_t n, int64_t* out, bool by_id, uint64_t word_stride,
-                             uint32_t* unresolved, hipStream_t st);
+void gs_launch_surface_query(const NeighView& v, uint32_t first_block, uint32_t blocks, float r2, float scale, uint32_t n, int64_t* out, bool by_id,
+                             uint64_t word_stride, uint32_t* unresolved, hipStream_t st);
 // sorted queries first .. first + count: their ten words, addressed as the query pass wrote them (first = 256 first_block), -> the
 // two records of their splats; unscale: 2^(2 (E - 16)); orient: towards toward[3]
 void gs_launch_surface_finish(const void* qrec, uint32_t first, uint32_t count, uint32_t n, const int64_t* in, bool by_id, uint64_t word_stride,

@@ -11,7 +11,7 @@
 // search: +inf for the queries, NaN for the others, NONE), the query pass in the count's slices, one word read back (the queries
 // the pass left +inf).  Every call drains the context's ring first (gs_wait), runs on the context's stream and returns when done.
 // None of them launches anything in a frame: a context that never calls them launches exactly what it did before.
-#include "gs_runtime.h"
+#include "gs_neigh_host.h"
 
 static_assert(sizeof(gs_knn) == 48 && offsetof(gs_knn, max_candidates) == 32 && offsetof(gs_knn, reserved) == 40, "gs_knn layout");
 static_assert(sizeof(gs_knn_info) == 48 && offsetof(gs_knn_info, unresolved) == 24 && offsetof(gs_knn_info, cells) == 32 && offsetof(gs_knn_info, cell_edge) == 44,
@@ -29,15 +29,10 @@ int32_t knn_planes(gs_ctx* c, hipStream_t st) {
 
 GS_EXPORT int32_t gs_knn_search(gs_ctx* c, const gs_knn* q, gs_knn_info* info) {
     const char* who = "gs_knn_search";
-    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, "%s: null ctx", who);
-    if (!q) return fail(GS_ERR_INVALID_ARGUMENT, "%s: null query", who);
-    if (q->struct_size != sizeof(gs_knn)) return fail(GS_ERR_INVALID_ARGUMENT, "%s: struct_size %u != %zu", who, q->struct_size, sizeof(gs_knn));
-    int32_t rc = resident_check(c, who, Plane::filtered, q->src_mask, q->src_value);
-    if (rc != GS_OK) return rc;
-    rc = resident_check(c, who, Plane::filtered, q->qry_mask, q->qry_value);
-    if (rc != GS_OK) return rc;
     float r2;
-    rc = neigh_check_radius(who, q->radius, &r2);
+    int32_t rc = neigh_check_query(c, who, q);
+    if (rc != GS_OK) return rc;
+    rc = neigh_check_filters(c, who, q->src_mask, q->src_value, q->qry_mask, q->qry_value, q->radius, &r2);
     if (rc != GS_OK) return rc;
     if (q->k == 0u || q->k > GS_KNN_MAX_K) return fail(GS_ERR_INVALID_ARGUMENT, "%s: k %u is not 1 .. %u", who, q->k, GS_KNN_MAX_K);
     if (q->flags & ~GS_KNN_REFINE) return fail(GS_ERR_INVALID_ARGUMENT, "%s: unknown flags 0x%x", who, q->flags & ~GS_KNN_REFINE);
@@ -57,21 +52,12 @@ GS_EXPORT int32_t gs_knn_search(gs_ctx* c, const gs_knn* q, gs_knn_info* info) {
         if (!refine) c->kn.k = q->k;
         return GS_OK;
     }
-    if (n >= (1u << 30)) return fail(GS_ERR_CAPACITY, "%s: %u splats, the cell sort takes fewer than 2^30", who, n); // (gs_sort_pairs_u32's limit)
-    gs_ctx::Neigh& s = c->ng;
     NeighBuilt b;
-    rc = neigh_build(c, who, q->radius, q->src_mask, q->src_value, q->qry_mask, q->qry_value, &b, refine ? c->kn.dist2.get() : nullptr);
+    rc = neigh_grid(c, who, q->radius, q->src_mask, q->src_value, q->qry_mask, q->qry_value, q->max_candidates, &b, [&](const NeighBuilt& b) {
+        neigh_report(&out, b);
+        if (info) *info = out;
+    }, refine ? c->kn.dist2.get() : nullptr);
     if (rc != GS_OK) return rc;
-    out.sources = b.sources;
-    out.queried = b.queried;
-    out.candidates = b.candidates;
-    out.cell_edge = b.cell_edge;
-    for (int k = 0; k < 3; ++k) out.cells[k] = b.g.g[k];
-    if (info) *info = out;
-    if (b.grid) {
-        rc = neigh_budget(who, b.candidates, q->max_candidates, q->radius);
-        if (rc != GS_OK) return rc;
-    }
 
     // from here on the planes are written.  A query without a record (a non-finite coordinate; every query when there is no grid:
     // nothing to find) keeps the +inf it is given here -- or, refining, the +inf that made it a query.
@@ -81,13 +67,10 @@ GS_EXPORT int32_t gs_knn_search(gs_ctx* c, const gs_knn* q, gs_knn_info* info) {
     }
     uint32_t open = 0; // finite queries the pass leaves +inf
     if (b.grid) {
-        uint32_t* word = s.bounds; // (neigh_build is done with its 16 words)
-        HIP_TRY(hipMemsetAsync(word, 0, 4, c->stream));
-        neigh_slices(b.sums, [&](uint32_t b0, uint32_t blocks) {
-            gs_launch_knn_query(b.qrec, b.nqry, b0, blocks, s.src, s.skeys, s.table, b.nsrc, b.g, r2, q->k, n, c->kn.dist2, c->kn.nearest, word, c->stream);
-        });
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(&open, word, 4, hipMemcpyDeviceToHost, c->stream));
+        rc = neigh_open_word(c, [&](uint32_t* word) {
+            neigh_slices(b.sums, [&](uint32_t b0, uint32_t blocks) { gs_launch_knn_query(b, b0, blocks, r2, q->k, n, c->kn.dist2, c->kn.nearest, word, c->stream); });
+        }, &open);
+        if (rc != GS_OK) return rc;
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
     out.unresolved = b.grid ? (b.queried - b.nqry) + open : b.queried;
@@ -97,17 +80,7 @@ GS_EXPORT int32_t gs_knn_search(gs_ctx* c, const gs_knn* q, gs_knn_info* info) {
 }
 
 GS_EXPORT int32_t gs_knn_read(gs_ctx* c, float* dist2, uint32_t* nearest, uint64_t cap, uint64_t* n) {
-    int32_t rc = resident_begin(c, "gs_knn_read", Plane::none);
-    if (rc != GS_OK) return rc;
-    rc = knn_planes(c, c->stream);
-    if (rc != GS_OK) return rc;
-    if (!n) return fail(GS_ERR_INVALID_ARGUMENT, "gs_knn_read: null n");
-    *n = c->n;
-    if (!dist2 && !nearest) { HIP_TRY(hipStreamSynchronize(c->stream)); return GS_OK; }
-    if (cap < c->n)
-        return fail(GS_ERR_INVALID_ARGUMENT, "gs_knn_read: %llu values per plane needed, the buffers hold %llu", (unsigned long long)c->n, (unsigned long long)cap);
-    if (c->n && dist2) HIP_TRY(hipMemcpyAsync(dist2, c->kn.dist2, (size_t)c->n * 4, hipMemcpyDeviceToHost, c->stream));
-    if (c->n && nearest) HIP_TRY(hipMemcpyAsync(nearest, c->kn.nearest, (size_t)c->n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return GS_OK;
+    void* const out[2] = {dist2, nearest};
+    const auto planes = [](gs_ctx* c, const uint32_t* p[2]) { const int32_t rc = knn_planes(c, c->stream); p[0] = c->kn.dist2; p[1] = c->kn.nearest; return rc; };
+    return plane_read(c, "gs_knn_read", planes, "values per plane needed, the buffers hold", out, cap, n);
 }

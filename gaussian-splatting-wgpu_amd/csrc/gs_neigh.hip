@@ -12,8 +12,8 @@
 // anything in a frame: a context that never calls them launches exactly what it did before.
 #include <cmath>
 
+#include "gs_neigh_host.h"
 #include "gs_pack_math.h"
-#include "gs_runtime.h"
 
 static_assert(sizeof(gs_neigh) == 40 && offsetof(gs_neigh, max_candidates) == 32, "gs_neigh layout");
 static_assert(sizeof(gs_neigh_info) == 40 && offsetof(gs_neigh_info, cells) == 24 && offsetof(gs_neigh_info, cell_edge) == 36, "gs_neigh_info layout");
@@ -51,10 +51,10 @@ static int32_t sorted_records(gs_ctx* c, const uint8_t* state, uint32_t mask, ui
     return GS_OK;
 }
 
-// Steps 1 to 3 of a count, which a labelling (gs_cluster.hip) shares: the bounds of the finite sources, the grid, the sources and
-// -- when their filter differs -- the queries in cell order, the candidates per workgroup of 256 sorted queries.  The caller has
-// drained the ring and c->n is 1 .. 2^30 - 1.  b->grid stays false when there is no finite source or no finite query (nothing to
-// find; only the two counts are set).  gate (u32[n], null for a count and a labelling): the queries are further restricted to the
+// Steps 1 to 3 of a count, which a labelling, a search and an estimate share (gs_neigh_host.h): the bounds of the finite sources,
+// the grid, the sources and -- when their filter differs -- the queries in cell order, the candidates per workgroup of 256 sorted
+// queries.  The caller has drained the ring and c->n is 1 .. 2^30 - 1.  b->grid stays false when there is no finite source or no
+// finite query (nothing to find; only the two counts are set).  gate (u32[n], null for a count and a labelling): the queries are further restricted to the
 // splats whose word there is +inf's -- where the query set is formed: the bounds' counts and the queries' keys, and so their sort,
 // their records and the candidates.
 int32_t neigh_build(gs_ctx* c, const char* who, float radius, uint32_t smask, uint32_t svalue, uint32_t qmask, uint32_t qvalue, NeighBuilt* b,
@@ -76,9 +76,9 @@ int32_t neigh_build(gs_ctx* c, const char* who, float radius, uint32_t smask, ui
     if ((rc = neigh_bounds(c, b->state, smask, svalue, qmask, qvalue, hb, gate)) != GS_OK) return rc;
     b->sources = hb[6];
     b->queried = hb[8];
-    b->nsrc = hb[7]; // with finite coordinates: the others have no neighbours
+    b->src.nrec = hb[7]; // with finite coordinates: the others have no neighbours
     b->nqry = hb[9];
-    if (!b->nsrc || !b->nqry) return GS_OK;
+    if (!b->src.nrec || !b->nqry) return GS_OK;
     float lo[3], hi[3];
     for (int k = 0; k < 3; ++k) { lo[k] = pk_okey_value(hb[k]); hi[k] = pk_okey_value(hb[3 + k]); }
     GsNeighGrid& g = b->g;
@@ -92,18 +92,19 @@ int32_t neigh_build(gs_ctx* c, const char* who, float radius, uint32_t smask, ui
     if (rc != GS_OK) return rc;
     uint32_t fault[2] = {0u, 0u};
     if ((rc = private_sort_fault(c, &fault[0])) != GS_OK) return rc;
-    b->qrec = s.src;
+    b->src = NeighSources{(const float4*)s.src.get(), s.skeys, (const uint2*)s.table.get(), b->src.nrec};
+    b->qrec = b->src.rec;
     if (!same) {
         HIP_TRY(hipStreamSynchronize(c->stream)); // fault[0] is read before the control block is zeroed again
         rc = sorted_records(c, b->state, qmask, qvalue, gate, g, s.qry, nullptr);
         if (rc != GS_OK) return rc;
         if ((rc = private_sort_fault(c, &fault[1])) != GS_OK) return rc;
-        b->qrec = s.qry;
+        b->qrec = (const float4*)s.qry.get();
     }
 
     // 3. the candidates, exactly, per workgroup of 256 sorted queries: the caller checks the budget and cuts the slices
     const uint32_t nblocks = (b->nqry + 255u) / 256u;
-    gs_launch_neigh_cands(b->qrec, b->nqry, s.src, s.skeys, s.table, b->nsrc, g, s.sums, c->stream);
+    gs_launch_neigh_cands(*b, s.sums, c->stream);
     HIP_TRY(hipGetLastError());
     b->sums.resize(nblocks);
     HIP_TRY(hipMemcpyAsync(b->sums.data(), s.sums, (size_t)nblocks * 8, hipMemcpyDeviceToHost, c->stream));
@@ -127,17 +128,19 @@ int32_t neigh_check_radius(const char* who, float radius, float* r2) {
     return GS_OK;
 }
 
+int32_t neigh_check_filters(gs_ctx* c, const char* who, uint32_t smask, uint32_t svalue, uint32_t qmask, uint32_t qvalue, float radius, float* r2) {
+    int32_t rc = resident_check(c, who, Plane::filtered, smask, svalue);
+    if (rc != GS_OK) return rc;
+    rc = resident_check(c, who, Plane::filtered, qmask, qvalue);
+    return rc != GS_OK ? rc : neigh_check_radius(who, radius, r2);
+}
+
 GS_EXPORT int32_t gs_neigh_count(gs_ctx* c, const gs_neigh* q, gs_neigh_info* info) {
     const char* who = "gs_neigh_count";
-    if (!c) return fail(GS_ERR_INVALID_ARGUMENT, "%s: null ctx", who);
-    if (!q) return fail(GS_ERR_INVALID_ARGUMENT, "%s: null query", who);
-    if (q->struct_size != sizeof(gs_neigh)) return fail(GS_ERR_INVALID_ARGUMENT, "%s: struct_size %u != %zu", who, q->struct_size, sizeof(gs_neigh));
-    int32_t rc = resident_check(c, who, Plane::filtered, q->src_mask, q->src_value);
-    if (rc != GS_OK) return rc;
-    rc = resident_check(c, who, Plane::filtered, q->qry_mask, q->qry_value);
-    if (rc != GS_OK) return rc;
     float r2;
-    rc = neigh_check_radius(who, q->radius, &r2);
+    int32_t rc = neigh_check_query(c, who, q);
+    if (rc != GS_OK) return rc;
+    rc = neigh_check_filters(c, who, q->src_mask, q->src_value, q->qry_mask, q->qry_value, q->radius, &r2);
     if (rc != GS_OK) return rc;
     if (q->limit == 0u) return fail(GS_ERR_INVALID_ARGUMENT, "%s: limit %u is not 1 .. 2^32-1", who, q->limit);
     if (q->reserved != 0u) return fail(GS_ERR_INVALID_ARGUMENT, "%s: reserved %u is not 0", who, q->reserved);
@@ -149,45 +152,40 @@ GS_EXPORT int32_t gs_neigh_count(gs_ctx* c, const gs_neigh* q, gs_neigh_info* in
     if (info) *info = out;
     const uint32_t n = c->n;
     if (!n) { HIP_TRY(hipStreamSynchronize(c->stream)); return GS_OK; }
-    if (n >= (1u << 30)) return fail(GS_ERR_CAPACITY, "%s: %u splats, the cell sort takes fewer than 2^30", who, n); // (gs_sort_pairs_u32's limit)
-    gs_ctx::Neigh& s = c->ng;
     NeighBuilt b;
-    rc = neigh_build(c, who, q->radius, q->src_mask, q->src_value, q->qry_mask, q->qry_value, &b);
-    if (rc != GS_OK) return rc;
-    out.sources = b.sources;
-    out.queried = b.queried;
-    out.candidates = b.candidates;
-    out.cell_edge = b.cell_edge;
-    for (int k = 0; k < 3; ++k) out.cells[k] = b.g.g[k];
-    if (info) *info = out;
-    if (!b.grid) { // nothing to find: every count is 0
-        HIP_TRY(hipMemsetAsync(s.plane, 0, plane_bytes(c), c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        return GS_OK;
-    }
-    rc = neigh_budget(who, b.candidates, q->max_candidates, q->radius);
+    rc = neigh_grid(c, who, q->radius, q->src_mask, q->src_value, q->qry_mask, q->qry_value, q->max_candidates, &b, [&](const NeighBuilt& b) {
+        neigh_report(&out, b);
+        if (info) *info = out;
+    });
     if (rc != GS_OK) return rc;
 
-    // 4. the query pass, in slices of whole workgroups
-    HIP_TRY(hipMemsetAsync(s.plane, 0, plane_bytes(c), c->stream));
-    neigh_slices(b.sums, [&](uint32_t b0, uint32_t blocks) {
-        gs_launch_neigh_query(b.qrec, b.nqry, b0, blocks, s.src, s.skeys, s.table, b.nsrc, b.g, r2, q->limit, n, s.plane, c->stream);
-    });
-    HIP_TRY(hipGetLastError());
+    // 4. the query pass, in slices of whole workgroups (without a grid there is nothing to find: every count is 0)
+    HIP_TRY(hipMemsetAsync(c->ng.plane, 0, plane_bytes(c), c->stream));
+    if (b.grid) {
+        neigh_slices(b.sums, [&](uint32_t b0, uint32_t blocks) { gs_launch_neigh_query(b, b0, blocks, r2, q->limit, n, c->ng.plane, c->stream); });
+        HIP_TRY(hipGetLastError());
+    }
     HIP_TRY(hipStreamSynchronize(c->stream));
     return GS_OK;
 }
 
-GS_EXPORT int32_t gs_neigh_read(gs_ctx* c, uint32_t* dst, uint64_t cap, uint64_t* n) {
-    int32_t rc = resident_begin(c, "gs_neigh_read", Plane::none);
+int32_t plane_read(gs_ctx* c, const char* who, int32_t (*planes)(gs_ctx*, const uint32_t* [2]), const char* what, void* const dst[2], uint64_t cap, uint64_t* n) {
+    int32_t rc = resident_begin(c, who, Plane::none);
     if (rc != GS_OK) return rc;
-    rc = neigh_plane(c, c->stream);
+    const uint32_t* plane[2] = {nullptr, nullptr};
+    rc = planes(c, plane);
     if (rc != GS_OK) return rc;
-    if (!n) return fail(GS_ERR_INVALID_ARGUMENT, "gs_neigh_read: null n");
+    if (!n) return fail(GS_ERR_INVALID_ARGUMENT, "%s: null n", who);
     *n = c->n;
-    if (!dst) { HIP_TRY(hipStreamSynchronize(c->stream)); return GS_OK; }
-    if (cap < c->n) return fail(GS_ERR_INVALID_ARGUMENT, "gs_neigh_read: %llu counts needed, the buffer holds %llu", (unsigned long long)c->n, (unsigned long long)cap);
-    if (c->n) HIP_TRY(hipMemcpyAsync(dst, c->ng.plane, (size_t)c->n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (!dst[0] && !dst[1]) { HIP_TRY(hipStreamSynchronize(c->stream)); return GS_OK; }
+    if (cap < c->n) return fail(GS_ERR_INVALID_ARGUMENT, "%s: %llu %s %llu", who, (unsigned long long)c->n, what, (unsigned long long)cap);
+    for (int k = 0; k < 2; ++k)
+        if (c->n && dst[k]) HIP_TRY(hipMemcpyAsync(dst[k], plane[k], (size_t)c->n * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return GS_OK;
+}
+GS_EXPORT int32_t gs_neigh_read(gs_ctx* c, uint32_t* dst, uint64_t cap, uint64_t* n) {
+    void* const out[2] = {dst, nullptr};
+    const auto planes = [](gs_ctx* c, const uint32_t* p[2]) { const int32_t rc = neigh_plane(c, c->stream); p[0] = c->ng.plane; return rc; };
+    return plane_read(c, "gs_neigh_read", planes, "counts needed, the buffer holds", out, cap, n);
 }

@@ -1,21 +1,15 @@
-// gs_neigh_dev.h -- device code that k_neigh.hip (neighbourhoods) and k_cluster.hip (clusters) share: the cell expression, the walk
-// over the source records of the 27 cells around a cell (the geometry is argued in k_neigh.hip), and the state pass around a
-// membership read from a resident u32 plane.
+// gs_neigh_dev.h -- device code that every consumer of the cell grid shares (k_neigh.hip, k_cluster.hip, k_knn.hip, k_surface.hip):
+// the walk over the source records of the 27 cells around a cell -- neigh_run, one x-run's spans, and neigh_visit, the wave's walk
+// over the nine runs (the geometry is argued in k_neigh.hip) --, and the state pass around a membership read from a resident plane.
 #pragma once
+#include <type_traits>
+
 #include "gs_device.h"
-#include "gs_kernels.h"
+#include "gs_kernels.h" // NeighSources
 #include "gs_state_sum.h"
 
 // (neigh_finite, neigh_cell and neigh_key are gs_grid_math.h's, which gs_kernels.h includes: the cell merge's host twin compiles them too)
 
-// What the candidates kernel, the query pass and the clusters' edge pass read of the sources.  nrec bounds what a table entry may
-// name (it never names more: gs_neigh_records_kernel).
-struct NeighSources {
-    const float4* __restrict__ rec;
-    const uint32_t* __restrict__ keys;
-    const uint2* __restrict__ table;
-    uint32_t nrec;
-};
 // The spans of source records of the x-run around cell x of row (y, z): cells max(x - 1, 0) .. min(x + 1, Gx - 1), consecutive
 // keys k0 .. k1, in every block they touch (one or two; three when a block is a cell).  f(lo, hi) takes each non-empty span.
 template <class F>
@@ -37,6 +31,39 @@ __device__ __forceinline__ void neigh_run(const NeighSources& S, const GsNeighGr
             hi = a;
         }
         if (lo < hi) f(lo, hi);
+    }
+}
+
+// THE WALK SKELETON of a query kernel (k_neigh.hip, "query", argues the geometry and the two paths).  A wave holds 64 consecutive
+// cell-sorted queries; q is the lane's record (zeros without one).  in: the lane has a record; live: it takes part (in, and whatever
+// else the kernel asks of its record: the clusters' id bound).  When every record of the wave is in one cell the nine x-runs' spans
+// are wave-uniform: walk(std::true_type, lo, hi) with lo / hi out of SGPRs, called in EVERY lane -- the span walk masks by live
+// itself.  Otherwise each live lane walks its own spans: walk(std::false_type, lo, hi).  The tag is a type, so that a kernel selects
+// its span walk at compile time.
+// GUARD: a wave without a record (the last workgroup's tail) walks nothing.  Its dead lanes sit in the cell of the origin, which
+// may be the scene's densest, and they pass the uniform test; a kernel whose uniform span walk does not end by itself (nearest
+// neighbours) asks for the guard.  The count's walk ends at its first ballot, and the clusters' edge pass never had the guard: both
+// are compiled without it, instruction for instruction as before there was one skeleton (with it both streams change and would have
+// to be timed on both paths).  The surface kernel alone keeps this skeleton written out, guard included: through this function its
+// uniform path misses the timing rule.  profiles/grid_walks_refactor.txt has the streams, the spellings tried and the timings.
+template <bool GUARD, class Walk>
+__device__ __forceinline__ void neigh_visit(const NeighSources& S, const GsNeighGrid& g, const float4& q, bool in, bool live, Walk&& walk) {
+    const int cx = neigh_cell(q.x, g.lo[0], g.inv_h, g.g[0]), cy = neigh_cell(q.y, g.lo[1], g.inv_h, g.g[1]), cz = neigh_cell(q.z, g.lo[2], g.inv_h, g.g[2]);
+    const uint32_t key = ((uint32_t)cz << g.bxy) | ((uint32_t)cy << g.bx) | (uint32_t)cx;
+    // the first lane's cell (lane 0 has a record whenever any lane has: the queries of a wave are consecutive)
+    const uint32_t key0 = __builtin_amdgcn_readfirstlane(key);
+    const bool uniform = __builtin_amdgcn_ballot_w64(in && key != key0) == 0ull;
+    const bool any = !GUARD || __builtin_amdgcn_ballot_w64(in) != 0ull;
+    if (any && uniform) {
+        const int ux = __builtin_amdgcn_readfirstlane(cx), uy = __builtin_amdgcn_readfirstlane(cy), uz = __builtin_amdgcn_readfirstlane(cz);
+        for (int dz = -1; dz <= 1; ++dz)
+            for (int dy = -1; dy <= 1; ++dy)
+                neigh_run(S, g, ux, uy + dy, uz + dz, [&](uint32_t lo, uint32_t hi) {
+                    walk(std::true_type{}, __builtin_amdgcn_readfirstlane(lo), __builtin_amdgcn_readfirstlane(hi));
+                });
+    } else if (live) {
+        for (int dz = -1; dz <= 1; ++dz)
+            for (int dy = -1; dy <= 1; ++dy) neigh_run(S, g, cx, cy + dy, cz + dz, [&](uint32_t lo, uint32_t hi) { walk(std::false_type{}, lo, hi); });
     }
 }
 

@@ -4,9 +4,9 @@
 //   the context (gs_ctx, GsOptions, FrameNotes, GraphKey), the lists of its last frame (frame_lists) and sums over its ring (over_ring);
 //   what the calls on the resident splats share: the prologue of a call that drains the ring (Plane, resident_check,
 //   resident_drain, resident_begin), the last frame waited for (last_frame), the staging of a canvas mask (stage_mask), the
-//   coverage planes (cover_planes), the neighbour count plane (neigh_plane), the cell grid a count and a labelling build
-//   (neigh_build, neigh_budget, neigh_slices), the cluster planes (cluster_planes), the splat edits' selection (edit_select), the
-//   bounds kernel's round trip (neigh_bounds), the pair sort behind a private control block (private_sort and its helpers), the
+//   coverage planes (cover_planes), the neighbour count plane (neigh_plane), the cluster planes (cluster_planes), the splat edits'
+//   selection (edit_select), the bounds kernel's round trip (neigh_bounds; what else the calls over the cell grid share is in
+//   gs_neigh_host.h), the pair sort behind a private control block (private_sort and its helpers), the
 //   check of a gs_attr (attr_check), the layout of a scene allocation (scene_layout, scene_install), the serial that tells one
 //   numbering of the resident splats from the next (gs_ctx::scene_serial, scene_new_serial: what a gs_snapshot is valid for), a file
 //   being streamed into the scene (PlySource, PackSource) and the two-buffer trip ring of every streamed call (TripRing).
@@ -329,38 +329,6 @@ int32_t cover_planes(gs_ctx* root, hipStream_t st);
 // gs_neigh.hip: the neighbour count plane of `c`, allocated and zeroed (on `st`) by the first call that needs it
 int32_t neigh_plane(gs_ctx* c, hipStream_t st);
 size_t plane_bytes(const gs_ctx* c); // of a u32[N] plane: whole 16-byte groups (the state pass reads a uint4 per thread)
-// What a count and a labelling share (gs_neigh.hip).  neigh_check_radius: the refusals of a radius; *r2 = radius * radius, once,
-// in f32.  neigh_build: the cell grid over the finite sources, the sources (c->ng.src, skeys, table) and the queries (qrec: the
-// sources' records when both filters are the same) in cell order, and the candidates of every workgroup of 256 sorted queries.
-// neigh_budget: GS_ERR_CAPACITY when the candidates exceed max_candidates (0: GS_NEIGH_DEFAULT_CANDIDATES).  neigh_slices: cuts the
-// workgroups into runs of at most GS_NEIGH_SLICE_CANDIDATES (one workgroup where a single one exceeds that) and calls
-// launch(first workgroup, workgroups) for each.
-struct NeighBuilt {
-    GsNeighGrid g{};
-    const uint8_t* state = nullptr;    // the state plane, or null when both filters are (0, 0)
-    uint64_t sources = 0, queried = 0; // splats that pass the two filters ...
-    uint32_t nsrc = 0, nqry = 0;       // ... and those of them with finite coordinates: the records
-    bool grid = false;                 // what follows is set: there was something to find
-    float cell_edge = 0.0f;
-    const void* qrec = nullptr;
-    std::vector<unsigned long long> sums;
-    uint64_t candidates = 0;
-};
-int32_t neigh_check_radius(const char* who, float radius, float* r2);
-int32_t neigh_build(gs_ctx* c, const char* who, float radius, uint32_t smask, uint32_t svalue, uint32_t qmask, uint32_t qvalue, NeighBuilt* b,
-                    const uint32_t* gate = nullptr);
-int32_t neigh_budget(const char* who, uint64_t candidates, uint64_t max_candidates, float radius);
-template <class Launch>
-void neigh_slices(const std::vector<unsigned long long>& sums, Launch launch) {
-    const uint32_t nblocks = (uint32_t)sums.size();
-    for (uint32_t b0 = 0; b0 < nblocks;) {
-        uint64_t sum = sums[b0];
-        uint32_t b1 = b0 + 1u;
-        while (b1 < nblocks && sum + sums[b1] <= GS_NEIGH_SLICE_CANDIDATES) sum += sums[b1++];
-        launch(b0, b1 - b0);
-        b0 = b1;
-    }
-}
 // gs_neigh.hip: the bounds kernel under a source and a query filter (state: the plane, or null when both are (0, 0)): seeds the 16
 // words, launches, reads them back into hb and synchronises.  hb[0..2] / [3..5]: pk_okey of the finite sources' lowest / highest
 // coordinates; hb[6..9]: sources, finite sources, queried, finite queried.

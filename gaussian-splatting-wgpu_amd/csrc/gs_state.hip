@@ -163,17 +163,30 @@ GS_EXPORT int32_t gs_state_attr(gs_ctx* c, const gs_attr* a, float lo, float hi,
     }, matched);
 }
 
-// Select by neighbour count: the pass over the count plane (gs_neigh.hip), which the first call that needs it allocates.
+// The prologue of a selection by a resident plane (the five calls below), the refusals in their order: resident_check, before() --
+// the call's own refusals that come ahead of the op's --, the op, after() -- those that follow it --, the where_mask; then the drain
+// with the counter and planes(c, stream), which the first call that needs them allocates.
+static int32_t no_refusal() { return GS_OK; }
+static int32_t state_check_range(const char* who, float lo, float hi) {
+    if (lo != lo || hi != hi) return fail(GS_ERR_INVALID_ARGUMENT, "%s: range [%g, %g] has a bound that is not a number", who, (double)lo, (double)hi);
+    return GS_OK;
+}
+template <class Before = int32_t (*)(), class After = int32_t (*)()>
+static int32_t plane_select_begin(gs_ctx* c, const char* who, uint32_t op, uint32_t bits, uint32_t where_mask, int32_t (*planes)(gs_ctx*, hipStream_t),
+                                  Before before = no_refusal, After after = no_refusal) {
+    int32_t rc;
+    if ((rc = resident_check(c, who, Plane::always)) != GS_OK || (rc = before()) != GS_OK || (rc = state_check_op(who, op, bits)) != GS_OK ||
+        (rc = after()) != GS_OK)
+        return rc;
+    if (where_mask > 0xFFu) return fail(GS_ERR_INVALID_ARGUMENT, "%s: where_mask 0x%x does not fit the state byte", who, where_mask);
+    if ((rc = resident_drain(c, true)) != GS_OK) return rc;
+    return planes(c, c->stream);
+}
+
+// Select by neighbour count: the pass over the count plane (gs_neigh.hip).
 GS_EXPORT int32_t gs_state_neigh(gs_ctx* c, uint32_t min_count, uint32_t max_count, uint32_t inside, uint32_t where_mask, uint32_t where_value, uint32_t op,
                                  uint32_t bits, uint64_t* matched) {
-    int32_t rc = resident_check(c, "gs_state_neigh", Plane::always);
-    if (rc != GS_OK) return rc;
-    rc = state_check_op("gs_state_neigh", op, bits);
-    if (rc != GS_OK) return rc;
-    if (where_mask > 0xFFu) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_neigh: where_mask 0x%x does not fit the state byte", where_mask);
-    rc = resident_drain(c, true);
-    if (rc != GS_OK) return rc;
-    rc = neigh_plane(c, c->stream);
+    const int32_t rc = plane_select_begin(c, "gs_state_neigh", op, bits, where_mask, neigh_plane);
     if (rc != GS_OK) return rc;
     return state_counted(c, [&](unsigned long long* slots) {
         gs_launch_state_neigh(plane(c), c->ng.plane, c->n, min_count, max_count, inside, op, bits, where_mask, where_value, slots, c->stream);
@@ -183,15 +196,7 @@ GS_EXPORT int32_t gs_state_neigh(gs_ctx* c, uint32_t min_count, uint32_t max_cou
 // Select by the k-th nearest distance: the pass over the dist2 plane (gs_knn.hip) read as words, with gs_state_attr's float range.
 GS_EXPORT int32_t gs_state_knn(gs_ctx* c, float lo, float hi, uint32_t inside, uint32_t where_mask, uint32_t where_value, uint32_t op, uint32_t bits,
                                uint64_t* matched) {
-    int32_t rc = resident_check(c, "gs_state_knn", Plane::always);
-    if (rc != GS_OK) return rc;
-    rc = state_check_op("gs_state_knn", op, bits);
-    if (rc != GS_OK) return rc;
-    if (lo != lo || hi != hi) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_knn: range [%g, %g] has a bound that is not a number", (double)lo, (double)hi);
-    if (where_mask > 0xFFu) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_knn: where_mask 0x%x does not fit the state byte", where_mask);
-    rc = resident_drain(c, true);
-    if (rc != GS_OK) return rc;
-    rc = knn_planes(c, c->stream);
+    const int32_t rc = plane_select_begin(c, "gs_state_knn", op, bits, where_mask, knn_planes, no_refusal, [&] { return state_check_range("gs_state_knn", lo, hi); });
     if (rc != GS_OK) return rc;
     return state_counted(c, [&](unsigned long long* slots) {
         gs_launch_state_knn(plane(c), c->kn.dist2, c->n, lo, hi, inside, op, bits, where_mask, where_value, slots, c->stream);
@@ -202,20 +207,16 @@ GS_EXPORT int32_t gs_state_knn(gs_ctx* c, float lo, float hi, uint32_t inside, u
 // kinds, the normal and count for the others --, with gs_state_knn's float range on the feature (gs_surface_math.h: sf_feature).
 GS_EXPORT int32_t gs_state_surface(gs_ctx* c, const gs_surface_range* r, uint32_t where_mask, uint32_t where_value, uint32_t op, uint32_t bits,
                                    uint64_t* matched) {
-    int32_t rc = resident_check(c, "gs_state_surface", Plane::always);
-    if (rc != GS_OK) return rc;
-    if (!r) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_surface: null range");
-    if (r->struct_size != sizeof(gs_surface_range))
-        return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_surface: struct_size %u != %zu", r->struct_size, sizeof(gs_surface_range));
-    if (r->kind > GS_SURFACE_COUNT) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_surface: unknown kind %u (0 .. %u)", r->kind, GS_SURFACE_COUNT);
-    rc = state_check_op("gs_state_surface", op, bits);
-    if (rc != GS_OK) return rc;
-    if (r->lo != r->lo || r->hi != r->hi)
-        return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_surface: range [%g, %g] has a bound that is not a number", (double)r->lo, (double)r->hi);
-    if (where_mask > 0xFFu) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_surface: where_mask 0x%x does not fit the state byte", where_mask);
-    rc = resident_drain(c, true);
-    if (rc != GS_OK) return rc;
-    rc = surface_planes(c, c->stream);
+    const char* who = "gs_state_surface";
+    const int32_t rc = plane_select_begin(
+        c, who, op, bits, where_mask, surface_planes,
+        [&]() -> int32_t {
+            if (!r) return fail(GS_ERR_INVALID_ARGUMENT, "%s: null range", who);
+            if (r->struct_size != sizeof(gs_surface_range)) return fail(GS_ERR_INVALID_ARGUMENT, "%s: struct_size %u != %zu", who, r->struct_size, sizeof(gs_surface_range));
+            if (r->kind > GS_SURFACE_COUNT) return fail(GS_ERR_INVALID_ARGUMENT, "%s: unknown kind %u (0 .. %u)", who, r->kind, GS_SURFACE_COUNT);
+            return GS_OK;
+        },
+        [&] { return state_check_range(who, r->lo, r->hi); });
     if (rc != GS_OK) return rc;
     const void* rec = r->kind < GS_SURFACE_FACING ? c->sf.eig.get() : c->sf.nrm.get();
     return state_counted(c, [&](unsigned long long* slots) {
@@ -223,17 +224,10 @@ GS_EXPORT int32_t gs_state_surface(gs_ctx* c, const gs_surface_range* r, uint32_
     }, matched);
 }
 
-// Select by cluster size: gs_state_neigh's pass over the size plane (gs_cluster.hip), which the first call that needs it allocates.
+// Select by cluster size: gs_state_neigh's pass over the size plane (gs_cluster.hip).
 GS_EXPORT int32_t gs_state_cluster(gs_ctx* c, uint32_t min_size, uint32_t max_size, uint32_t inside, uint32_t where_mask, uint32_t where_value, uint32_t op,
                                    uint32_t bits, uint64_t* matched) {
-    int32_t rc = resident_check(c, "gs_state_cluster", Plane::always);
-    if (rc != GS_OK) return rc;
-    rc = state_check_op("gs_state_cluster", op, bits);
-    if (rc != GS_OK) return rc;
-    if (where_mask > 0xFFu) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_cluster: where_mask 0x%x does not fit the state byte", where_mask);
-    rc = resident_drain(c, true);
-    if (rc != GS_OK) return rc;
-    rc = cluster_planes(c, c->stream);
+    const int32_t rc = plane_select_begin(c, "gs_state_cluster", op, bits, where_mask, cluster_planes);
     if (rc != GS_OK) return rc;
     return state_counted(c, [&](unsigned long long* slots) {
         gs_launch_state_neigh(plane(c), c->cl.size, c->n, min_size, max_size, inside, op, bits, where_mask, where_value, slots, c->stream);
@@ -244,15 +238,10 @@ GS_EXPORT int32_t gs_state_cluster(gs_ctx* c, uint32_t min_size, uint32_t max_si
 // then the state pass over the label plane reads the flag of every splat's label.
 GS_EXPORT int32_t gs_state_cluster_linked(gs_ctx* c, uint32_t seed_mask, uint32_t seed_value, uint32_t where_mask, uint32_t where_value, uint32_t op,
                                           uint32_t bits, uint64_t* matched) {
-    int32_t rc = resident_check(c, "gs_state_cluster_linked", Plane::always);
-    if (rc != GS_OK) return rc;
-    rc = state_check_op("gs_state_cluster_linked", op, bits);
-    if (rc != GS_OK) return rc;
-    if (seed_mask > 0xFFu) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_cluster_linked: seed_mask 0x%x does not fit the state byte", seed_mask);
-    if (where_mask > 0xFFu) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_cluster_linked: where_mask 0x%x does not fit the state byte", where_mask);
-    rc = resident_drain(c, true);
-    if (rc != GS_OK) return rc;
-    rc = cluster_planes(c, c->stream);
+    int32_t rc = plane_select_begin(c, "gs_state_cluster_linked", op, bits, where_mask, cluster_planes, no_refusal, [&]() -> int32_t {
+        if (seed_mask > 0xFFu) return fail(GS_ERR_INVALID_ARGUMENT, "gs_state_cluster_linked: seed_mask 0x%x does not fit the state byte", seed_mask);
+        return GS_OK;
+    });
     if (rc != GS_OK) return rc;
     if (!c->n) { if (matched) *matched = 0; return GS_OK; }
     rc = c->ng.keysA.reserve(c->n);

@@ -12,8 +12,8 @@
 // in the count's slices, each cut into runs of at most kSliceBlocks workgroups and followed by its finishing pass, one word read
 // back (the queries that end with count < 3).  Every call drains the context's ring first (gs_wait), runs on the context's stream
 // and returns when done.  None of them launches anything in a frame.
+#include "gs_neigh_host.h"
 #include "gs_surface_math.h"
-#include "gs_runtime.h"
 
 static_assert(sizeof(gs_surface) == 56 && offsetof(gs_surface, toward) == 28 && offsetof(gs_surface, max_candidates) == 40 && offsetof(gs_surface, reserved) == 48,
               "gs_surface layout");
@@ -47,12 +47,8 @@ GS_EXPORT int32_t gs_surface_estimate(gs_ctx* c, const gs_surface* q, gs_surface
     SfScale sc;
     char why[160];
     if (!sf_check(q, &sc, why, sizeof why)) return fail(GS_ERR_INVALID_ARGUMENT, "%s: %s", who, why);
-    int32_t rc = resident_check(c, who, Plane::filtered, q->src_mask, q->src_value);
-    if (rc != GS_OK) return rc;
-    rc = resident_check(c, who, Plane::filtered, q->qry_mask, q->qry_value);
-    if (rc != GS_OK) return rc;
-    float r2;
-    rc = neigh_check_radius(who, q->radius, &r2); // (sf_check has refused everything this refuses; r2 is sc.r2)
+    float r2; // (sf_check has refused every radius this refuses; r2 is sc.r2)
+    int32_t rc = neigh_check_filters(c, who, q->src_mask, q->src_value, q->qry_mask, q->qry_value, q->radius, &r2);
     if (rc != GS_OK) return rc;
     rc = resident_drain(c);
     if (rc != GS_OK) return rc;
@@ -67,30 +63,19 @@ GS_EXPORT int32_t gs_surface_estimate(gs_ctx* c, const gs_surface* q, gs_surface
         c->sf.have_sums = keep; // (zero splats, zero sums)
         return GS_OK;
     }
-    if (n >= (1u << 30)) return fail(GS_ERR_CAPACITY, "%s: %u splats, the cell sort takes fewer than 2^30", who, n); // (gs_sort_pairs_u32's limit)
-    gs_ctx::Neigh& s = c->ng;
     NeighBuilt b;
-    rc = neigh_build(c, who, q->radius, q->src_mask, q->src_value, q->qry_mask, q->qry_value, &b);
+    rc = neigh_grid(c, who, q->radius, q->src_mask, q->src_value, q->qry_mask, q->qry_value, q->max_candidates, &b, [&](const NeighBuilt& b) {
+        neigh_report(&out, b);
+        if (info) *info = out;
+    });
     if (rc != GS_OK) return rc;
-    out.sources = b.sources;
-    out.queried = b.queried;
-    out.candidates = b.candidates;
-    out.cell_edge = b.cell_edge;
-    for (int k = 0; k < 3; ++k) out.cells[k] = b.g.g[k];
-    if (info) *info = out;
     const uint32_t nblocks = b.grid ? (b.nqry + 255u) / 256u : 0u;
-    if (b.grid) {
-        rc = neigh_budget(who, b.candidates, q->max_candidates, q->radius);
-        if (rc != GS_OK) return rc;
-        // the last allocations: the kept plane, or the scratch of one run
-        if (keep && !c->sf.sums) {
-            HIP_TRY(hipMalloc(c->sf.sums.out(), std::max<size_t>((size_t)n * SF_SUM_WORDS * 8, 256)));
-        } else if (!keep) {
-            rc = c->sf.slice.reserve((uint64_t)std::min(nblocks, kSliceBlocks) * 256u * SF_SUM_WORDS);
-            if (rc != GS_OK) return rc;
-        }
-    } else if (keep && !c->sf.sums) {
+    // the last allocations: the kept plane, or -- with a grid -- the scratch of one run
+    if (keep && !c->sf.sums) {
         HIP_TRY(hipMalloc(c->sf.sums.out(), std::max<size_t>((size_t)n * SF_SUM_WORDS * 8, 256)));
+    } else if (!keep && b.grid) {
+        rc = c->sf.slice.reserve((uint64_t)std::min(nblocks, kSliceBlocks) * 256u * SF_SUM_WORDS);
+        if (rc != GS_OK) return rc;
     }
 
     // from here on the planes are written.  A query without a record (a non-finite coordinate; every query when there is no grid:
@@ -101,22 +86,21 @@ GS_EXPORT int32_t gs_surface_estimate(gs_ctx* c, const gs_surface* q, gs_surface
     if (keep) HIP_TRY(hipMemsetAsync(c->sf.sums, 0, (size_t)n * SF_SUM_WORDS * 8, c->stream));
     uint32_t open = 0; // finite queries the pass leaves with count < 3
     if (b.grid) {
-        uint32_t* word = s.bounds; // (neigh_build is done with its 16 words)
-        HIP_TRY(hipMemsetAsync(word, 0, 4, c->stream));
         const uint64_t stride = keep ? 1u : (uint64_t)std::min(nblocks, kSliceBlocks) * 256u;
         int64_t* sums = keep ? c->sf.sums.get() : c->sf.slice.get();
         const bool orient = (q->flags & GS_SURFACE_ORIENT) != 0u;
-        neigh_slices(b.sums, [&](uint32_t b0, uint32_t blocks) {
-            for (uint32_t done = 0; done < blocks; done += kSliceBlocks) { // (the finishing pass has read a run's scratch before the next writes it: one stream)
-                const uint32_t first = b0 + done, m = std::min(blocks - done, kSliceBlocks);
-                gs_launch_surface_query(b.qrec, b.nqry, first, m, s.src, s.skeys, s.table, b.nsrc, b.g, sc.r2, sc.s, n, sums, keep, stride, word, c->stream);
-                const uint32_t t0 = first * 256u;
-                gs_launch_surface_finish(b.qrec, t0, std::min(m * 256u, b.nqry - t0), n, sums, keep, stride, sc.unscale, orient, q->toward, c->sf.nrm,
-                                         c->sf.eig, c->stream);
-            }
-        });
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(&open, word, 4, hipMemcpyDeviceToHost, c->stream));
+        rc = neigh_open_word(c, [&](uint32_t* word) {
+            neigh_slices(b.sums, [&](uint32_t b0, uint32_t blocks) {
+                for (uint32_t done = 0; done < blocks; done += kSliceBlocks) { // (the finishing pass has read a run's scratch before the next writes it: one stream)
+                    const uint32_t first = b0 + done, m = std::min(blocks - done, kSliceBlocks);
+                    gs_launch_surface_query(b, first, m, sc.r2, sc.s, n, sums, keep, stride, word, c->stream);
+                    const uint32_t t0 = first * 256u;
+                    gs_launch_surface_finish(b.qrec, t0, std::min(m * 256u, b.nqry - t0), n, sums, keep, stride, sc.unscale, orient, q->toward, c->sf.nrm,
+                                             c->sf.eig, c->stream);
+                }
+            });
+        }, &open);
+        if (rc != GS_OK) return rc;
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->sf.have_sums = keep;

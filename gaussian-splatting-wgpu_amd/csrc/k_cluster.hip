@@ -113,32 +113,20 @@ __global__ __launch_bounds__(256) void gs_cluster_edges_kernel(const float4* __r
     const float4 q = t64 < nq ? qrec[(uint32_t)t64] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     const uint32_t qid = __float_as_uint(q.w);
     const bool live = t64 < nq && qid < n; // (qid < n always: gs_neigh_records_kernel; keeps every index inside parent[] whatever the records hold)
-    const int cx = neigh_cell(q.x, g.lo[0], g.inv_h, g.g[0]), cy = neigh_cell(q.y, g.lo[1], g.inv_h, g.g[1]), cz = neigh_cell(q.z, g.lo[2], g.inv_h, g.g[2]);
-    const uint32_t key = ((uint32_t)cz << g.bxy) | ((uint32_t)cy << g.bx) | (uint32_t)cx;
-    const uint32_t key0 = __builtin_amdgcn_readfirstlane(key);
-    const bool uniform = __builtin_amdgcn_ballot_w64(t64 < nq && key != key0) == 0ull;
     uint32_t cur = live ? qid : 0u;
     bool hooked = false;
-    if (uniform) {
-        const int ux = __builtin_amdgcn_readfirstlane(cx), uy = __builtin_amdgcn_readfirstlane(cy), uz = __builtin_amdgcn_readfirstlane(cz);
-        for (int dz = -1; dz <= 1; ++dz)
-            for (int dy = -1; dy <= 1; ++dy)
-                neigh_run(S, g, ux, uy + dy, uz + dz, [&](uint32_t lo, uint32_t hi) {
-                    cluster_walk<true>(S.rec, __builtin_amdgcn_readfirstlane(lo), __builtin_amdgcn_readfirstlane(hi), q, qid, r2, live, parent, cur, hooked);
-                });
-    } else if (live) {
-        for (int dz = -1; dz <= 1; ++dz)
-            for (int dy = -1; dy <= 1; ++dy)
-                neigh_run(S, g, cx, cy + dy, cz + dz, [&](uint32_t lo, uint32_t hi) { cluster_walk<false>(S.rec, lo, hi, q, qid, r2, true, parent, cur, hooked); });
-    }
+    // unguarded, as it always was (gs_neigh_dev.h: neigh_visit): a tail wave without a member walks the origin's cell, every union masked
+    neigh_visit<false>(S, g, q, t64 < nq, live, [&](auto uniform, uint32_t lo, uint32_t hi) {
+        constexpr bool U = decltype(uniform)::value;
+        cluster_walk<U>(S.rec, lo, hi, q, qid, r2, !U || live, parent, cur, hooked);
+    });
     if (live && cur < qid) atomicMin(parent + qid, cur);
     if (__builtin_amdgcn_ballot_w64(hooked) != 0ull && lane_id() == 0u) atomicOr(changed, 1u);
 }
-void gs_launch_cluster_edges(const void* rec, uint32_t nrec, uint32_t first_block, uint32_t blocks, const uint32_t* skeys, const void* table,
-                             const GsNeighGrid& g, float r2, uint32_t n, uint32_t* parent, uint32_t* changed, hipStream_t st) {
+void gs_launch_cluster_edges(const NeighView& v, uint32_t first_block, uint32_t blocks, float r2, uint32_t n, uint32_t* parent, uint32_t* changed,
+                             hipStream_t st) {
     if (!blocks) return;
-    const NeighSources S{(const float4*)rec, skeys, (const uint2*)table, nrec};
-    hipLaunchKernelGGL(gs_cluster_edges_kernel, dim3(blocks), dim3(256), 0, st, (const float4*)rec, nrec, first_block, S, g, r2, n, parent, changed);
+    hipLaunchKernelGGL(gs_cluster_edges_kernel, dim3(blocks), dim3(256), 0, st, v.src.rec, v.src.nrec, first_block, v.src, v.g, r2, n, parent, changed);
 }
 
 __global__ __launch_bounds__(256) void gs_cluster_flatten_kernel(const float4* __restrict__ rec, uint32_t nrec, uint32_t n, uint32_t* parent) {

@@ -102,27 +102,12 @@ __global__ __launch_bounds__(256) void gs_knn_query_kernel(const float4* __restr
     const bool live = t64 < nq;
     const float4 q = live ? qrec[(uint32_t)t64] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     const uint32_t qid = __float_as_uint(q.w);
-    const int cx = neigh_cell(q.x, g.lo[0], g.inv_h, g.g[0]), cy = neigh_cell(q.y, g.lo[1], g.inv_h, g.g[1]), cz = neigh_cell(q.z, g.lo[2], g.inv_h, g.g[2]);
-    const uint32_t key = ((uint32_t)cz << g.bxy) | ((uint32_t)cy << g.bx) | (uint32_t)cx;
-    // the first live lane's cell (lane 0 is live whenever any lane is: the queries of a wave are consecutive)
-    const uint32_t key0 = __builtin_amdgcn_readfirstlane(key);
-    const bool uniform = __builtin_amdgcn_ballot_w64(live && key != key0) == 0ull;
-    // a wave without a query (the last workgroup's tail) walks nothing: its dead lanes sit in the cell of the origin, which may be the
-    // scene's densest, and nothing would stop a uniform walk there (the count's stops at its first ballot)
-    const bool any = __builtin_amdgcn_ballot_w64(live) != 0ull;
     KnnLane L{0u, 0u, 0.0f, __uint_as_float(KNN_INF), KNN_NONE};
-    if (any && uniform) {
-        const int ux = __builtin_amdgcn_readfirstlane(cx), uy = __builtin_amdgcn_readfirstlane(cy), uz = __builtin_amdgcn_readfirstlane(cz);
-        for (int dz = -1; dz <= 1; ++dz)
-            for (int dy = -1; dy <= 1; ++dy)
-                neigh_run(S, g, ux, uy + dy, uz + dz, [&](uint32_t lo, uint32_t hi) {
-                    knn_walk<true>(S.rec, __builtin_amdgcn_readfirstlane(lo), __builtin_amdgcn_readfirstlane(hi), q, qid, r2, live, slots, k, L);
-                });
-    } else if (live) {
-        for (int dz = -1; dz <= 1; ++dz)
-            for (int dy = -1; dy <= 1; ++dy)
-                neigh_run(S, g, cx, cy + dy, cz + dz, [&](uint32_t lo, uint32_t hi) { knn_walk<false>(S.rec, lo, hi, q, qid, r2, true, slots, k, L); });
-    }
+    // guarded: nothing would stop a uniform walk of a wave without a query (gs_neigh_dev.h: neigh_visit)
+    neigh_visit<true>(S, g, q, live, live, [&](auto uniform, uint32_t lo, uint32_t hi) {
+        constexpr bool U = decltype(uniform)::value;
+        knn_walk<U>(S.rec, lo, hi, q, qid, r2, !U || live, slots, k, L);
+    });
     const bool resolved = L.fill >= k;
     if (live && qid < n) {
         dist2[qid] = resolved ? __float_as_uint(L.worst) : KNN_INF;
@@ -131,12 +116,10 @@ __global__ __launch_bounds__(256) void gs_knn_query_kernel(const float4* __restr
     const unsigned long long open = __builtin_amdgcn_ballot_w64(live && !resolved);
     if (open && (threadIdx.x & 63u) == 0u) atomicAdd(unresolved, (uint32_t)__popcll(open));
 }
-void gs_launch_knn_query(const void* qrec, uint32_t nq, uint32_t first_block, uint32_t blocks, const void* srec, const uint32_t* skeys, const void* table,
-                         uint32_t nrec, const GsNeighGrid& g, float r2, uint32_t k, uint32_t n, uint32_t* dist2, uint32_t* nearest, uint32_t* unresolved,
-                         hipStream_t st) {
+void gs_launch_knn_query(const NeighView& v, uint32_t first_block, uint32_t blocks, float r2, uint32_t k, uint32_t n, uint32_t* dist2, uint32_t* nearest,
+                         uint32_t* unresolved, hipStream_t st) {
     if (!blocks || !k || k > 32u) return; // (GS_KNN_MAX_K: gs_knn_search has refused anything else)
-    const NeighSources S{(const float4*)srec, skeys, (const uint2*)table, nrec};
-    hipLaunchKernelGGL(gs_knn_query_kernel, dim3(blocks), dim3(256), (size_t)k * 1024u, st, (const float4*)qrec, nq, first_block, S, g, r2, k, n, dist2, nearest,
+    hipLaunchKernelGGL(gs_knn_query_kernel, dim3(blocks), dim3(256), (size_t)k * 1024u, st, v.qrec, v.nqry, first_block, v.src, v.g, r2, k, n, dist2, nearest,
                        unresolved);
 }
 

@@ -38,7 +38,7 @@
 //             construction, a search halves its interval); no spin, no hand-off between workgroups, no float atomics, no scratch,
 //             no LDS.  Bound: VALU issue (uniform path) / L1 gather rate (per-lane path).  VGPRs and occupancy: gs_neigh_query_kernel.
 //   state   : gs_state_coverage's quad mapping around the u32 plane: 5 B read per splat, at most 1 B written.
-#include "gs_neigh_dev.h" // the cell expression, NeighSources, neigh_run and the state pass around a plane: shared with k_cluster.hip
+#include "gs_neigh_dev.h" // neigh_run, the walk skeleton neigh_visit and the state pass around a plane: shared with the other grid consumers
 
 __device__ __forceinline__ uint32_t neigh_order_key(float v) { // order-preserving map of the bit pattern (gs_abi.h, splat attributes)
     const uint32_t b = __float_as_uint(v);
@@ -153,11 +153,9 @@ __global__ __launch_bounds__(256) void gs_neigh_cands_kernel(const float4* __res
     __syncthreads();
     if (threadIdx.x == 0) sums[blockIdx.x] = s_sum;
 }
-void gs_launch_neigh_cands(const void* qrec, uint32_t nq, const void* srec, const uint32_t* skeys, const void* table, uint32_t nrec, const GsNeighGrid& g,
-                           unsigned long long* sums, hipStream_t st) {
-    if (!nq) return;
-    const NeighSources S{(const float4*)srec, skeys, (const uint2*)table, nrec};
-    hipLaunchKernelGGL(gs_neigh_cands_kernel, dim3((nq + 255u) / 256u), dim3(256), 0, st, (const float4*)qrec, nq, S, g, sums);
+void gs_launch_neigh_cands(const NeighView& v, unsigned long long* sums, hipStream_t st) {
+    if (!v.nqry) return;
+    hipLaunchKernelGGL(gs_neigh_cands_kernel, dim3((v.nqry + 255u) / 256u), dim3(256), 0, st, v.qrec, v.nqry, v.src, v.g, sums);
 }
 
 // One span against the lane's query.  UNIFORM: lo / hi are the same in every lane (scalar loads of the records, one ballot per record
@@ -190,31 +188,16 @@ __global__ __launch_bounds__(256) void gs_neigh_query_kernel(const float4* __res
     const bool live = t64 < nq;
     const float4 q = live ? qrec[(uint32_t)t64] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     const uint32_t qid = __float_as_uint(q.w);
-    const int cx = neigh_cell(q.x, g.lo[0], g.inv_h, g.g[0]), cy = neigh_cell(q.y, g.lo[1], g.inv_h, g.g[1]), cz = neigh_cell(q.z, g.lo[2], g.inv_h, g.g[2]);
-    const uint32_t key = ((uint32_t)cz << g.bxy) | ((uint32_t)cy << g.bx) | (uint32_t)cx;
-    // the first live lane's cell (lane 0 is live whenever any lane is: the queries of a wave are consecutive)
-    const uint32_t key0 = __builtin_amdgcn_readfirstlane(key);
-    const bool uniform = __builtin_amdgcn_ballot_w64(live && key != key0) == 0ull;
     uint32_t cnt = 0u;
-    if (uniform) {
-        const int ux = __builtin_amdgcn_readfirstlane(cx), uy = __builtin_amdgcn_readfirstlane(cy), uz = __builtin_amdgcn_readfirstlane(cz);
-        for (int dz = -1; dz <= 1; ++dz)
-            for (int dy = -1; dy <= 1; ++dy)
-                neigh_run(S, g, ux, uy + dy, uz + dz, [&](uint32_t lo, uint32_t hi) {
-                    neigh_walk<true>(S.rec, __builtin_amdgcn_readfirstlane(lo), __builtin_amdgcn_readfirstlane(hi), q, qid, r2, limit, live, cnt);
-                });
-    } else if (live) {
-        for (int dz = -1; dz <= 1; ++dz)
-            for (int dy = -1; dy <= 1; ++dy)
-                neigh_run(S, g, cx, cy + dy, cz + dz, [&](uint32_t lo, uint32_t hi) { neigh_walk<false>(S.rec, lo, hi, q, qid, r2, limit, true, cnt); });
-    }
+    neigh_visit<false>(S, g, q, live, live, [&](auto uniform, uint32_t lo, uint32_t hi) { // unguarded: the uniform walk ends at its first ballot
+        constexpr bool U = decltype(uniform)::value;
+        neigh_walk<U>(S.rec, lo, hi, q, qid, r2, limit, !U || live, cnt);
+    });
     if (live && qid < n) plane[qid] = cnt < limit ? cnt : limit;
 }
-void gs_launch_neigh_query(const void* qrec, uint32_t nq, uint32_t first_block, uint32_t blocks, const void* srec, const uint32_t* skeys, const void* table,
-                           uint32_t nrec, const GsNeighGrid& g, float r2, uint32_t limit, uint32_t n, uint32_t* plane, hipStream_t st) {
+void gs_launch_neigh_query(const NeighView& v, uint32_t first_block, uint32_t blocks, float r2, uint32_t limit, uint32_t n, uint32_t* plane, hipStream_t st) {
     if (!blocks) return;
-    const NeighSources S{(const float4*)srec, skeys, (const uint2*)table, nrec};
-    hipLaunchKernelGGL(gs_neigh_query_kernel, dim3(blocks), dim3(256), 0, st, (const float4*)qrec, nq, first_block, S, g, r2, limit, n, plane);
+    hipLaunchKernelGGL(gs_neigh_query_kernel, dim3(blocks), dim3(256), 0, st, v.qrec, v.nqry, first_block, v.src, v.g, r2, limit, n, plane);
 }
 
 // gs_state_neigh (and gs_state_cluster over the size plane): the state pass around a u32 plane (gs_neigh_dev.h) with the range

@@ -84,6 +84,7 @@ __device__ __forceinline__ void surface_walk(const float4* __restrict__ srec, ui
 // slot = the splat id (the kept plane: strides 10, 1) or t - 256 first_block (the slice's scratch: strides 1, cap); *unresolved += the
 // queries that end with count < 3.
 // 56 VGPRs, 66 SGPRs, no scratch (private segment 0), no LDS: 8 waves per SIMD (the launch bound's limit).
+// WRITTEN OUT, not neigh_visit<true> (gs_neigh_dev.h): through it 8 lines of the stream move and the uniform path misses the timing rule (profiles/grid_walks_refactor.txt).
 __global__ __launch_bounds__(256) void gs_surface_query_kernel(const float4* __restrict__ qrec, uint32_t nq, uint32_t first_block, NeighSources S, GsNeighGrid g,
                                                                 float r2, float sc, uint32_t n, long long* __restrict__ out, uint32_t by_id,
                                                                 unsigned long long word_stride, uint32_t* __restrict__ unresolved) {
@@ -96,7 +97,7 @@ __global__ __launch_bounds__(256) void gs_surface_query_kernel(const float4* __r
     // the first live lane's cell (lane 0 is live whenever any lane is: the queries of a wave are consecutive)
     const uint32_t key0 = __builtin_amdgcn_readfirstlane(key);
     const bool uniform = __builtin_amdgcn_ballot_w64(live && key != key0) == 0ull;
-    // a wave without a query (the last workgroup's tail) walks nothing (k_knn.hip)
+    // a wave without a query (the last workgroup's tail) walks nothing (gs_neigh_dev.h: neigh_visit's GUARD)
     const bool any = __builtin_amdgcn_ballot_w64(live) != 0ull;
     SfSums L{};
     if (any && uniform) {
@@ -121,12 +122,10 @@ __global__ __launch_bounds__(256) void gs_surface_query_kernel(const float4* __r
     const unsigned long long open = __builtin_amdgcn_ballot_w64(live && L.n < 3u);
     if (open && (threadIdx.x & 63u) == 0u) atomicAdd(unresolved, (uint32_t)__popcll(open));
 }
-void gs_launch_surface_query(const void* qrec, uint32_t nq, uint32_t first_block, uint32_t blocks, const void* srec, const uint32_t* skeys, const void* table,
-                             uint32_t nrec, const GsNeighGrid& g, float r2, float scale, uint32_t n, int64_t* out, bool by_id, uint64_t word_stride,
-                             uint32_t* unresolved, hipStream_t st) {
+void gs_launch_surface_query(const NeighView& v, uint32_t first_block, uint32_t blocks, float r2, float scale, uint32_t n, int64_t* out, bool by_id,
+                             uint64_t word_stride, uint32_t* unresolved, hipStream_t st) {
     if (!blocks) return;
-    const NeighSources S{(const float4*)srec, skeys, (const uint2*)table, nrec};
-    hipLaunchKernelGGL(gs_surface_query_kernel, dim3(blocks), dim3(256), 0, st, (const float4*)qrec, nq, first_block, S, g, r2, scale, n, (long long*)out,
+    hipLaunchKernelGGL(gs_surface_query_kernel, dim3(blocks), dim3(256), 0, st, v.qrec, v.nqry, first_block, v.src, v.g, r2, scale, n, (long long*)out,
                        by_id ? 1u : 0u, (unsigned long long)word_stride, unresolved);
 }
 
@@ -181,7 +180,8 @@ void gs_launch_surface_unpack(const void* rec, uint32_t n, float* xyz, uint32_t*
 
 // gs_state_surface: state_plane_pass's shape (gs_neigh_dev.h) around a 16-byte plane: a thread takes splats 4q .. 4q+3, one whole word
 // of the state plane and four records.  The record is the eigenvalues' for the four shape kinds and the normal's (count in its fourth
-// word) for the others: sf_feature reads the triple it needs.
+// word) for the others: sf_feature reads the triple it needs.  WRITTEN OUT: state_plane_pass over the plane's element type leaves the
+// u32 kernels' streams alone but reassociates this one's new state word and hit sum (profiles/grid_walks_refactor.txt).
 struct SurfaceRange {
     uint32_t kind;
     float lo, hi;

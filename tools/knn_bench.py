@@ -2,7 +2,7 @@
 """GPU box: what a nearest-neighbour search costs at config B size (6.1 M synthetic splats, a state plane), beside the neighbour count
 over the same candidates and beside the host route it replaces.
 
-  python tools/knn_bench.py [--out profiles/nearest.txt] [--n N] [--reps 7] [--mean 10] [--k 8] [--no-host]
+  python tools/knn_bench.py [--out profiles/nearest.txt] [--n N] [--reps 7] [--mean 10] [--k 8] [--no-host] [--radius R] [--search-only]
 
 A radius with a mean count of about `--mean` is found by bisection, as tools/neigh_bench.py does.  At that radius, in ONE run:
 
@@ -16,6 +16,10 @@ of `reps` calls.  The BUILD (bounds, keys, sort, records, cell table, candidates
 refused by max_candidates = 1, which does all of that and stops before the query pass; the QUERY PASS is the difference; the
 candidate rate is candidates / query pass.  distances() is timed over 3 calls after one, the host route once (it takes seconds).
 The search's resolved distances are compared with the tree's (float64) as a check of the comparison itself.
+
+--radius R skips the bisection; --search-only stops after the count's and the search's lines (an A/B of the query kernel).  The
+query kernel's uniform path alone -- every splat in one cell -- is --n 131072 --radius 1000 --search-only, as for
+tools/surface_bench.py (profiles/surface.txt); the default scene at 6.1 M splats is its per-lane path.
 """
 import argparse
 import math
@@ -38,6 +42,8 @@ def main():
     ap.add_argument("--mean", type=float, default=10.0)
     ap.add_argument("--k", type=int, default=8)
     ap.add_argument("--no-host", action="store_true", help="skip the host route (export + k-d tree + state_ids)")
+    ap.add_argument("--radius", type=float, default=0.0, help="skip the bisection and take this radius")
+    ap.add_argument("--search-only", action="store_true", help="the count and the search at the radius, nothing else")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -78,7 +84,10 @@ def main():
 
     # the radius: bisection on the mean count (a radius beyond the default budget counts as too large)
     lo, hi, radius, mean = 1e-3, 2.0, None, None
-    for _ in range(16):
+    if a.radius > 0.0:
+        neighbours.count(r, a.radius)
+        radius, mean = a.radius, float(neighbours.read(r).mean(dtype=np.float64))
+    for _ in range(0 if radius else 16):
         mid = math.sqrt(lo * hi)
         try:
             neighbours.count(r, mid)
@@ -120,6 +129,9 @@ def main():
             full = timed(lambda: nearest.search(r, kk, radius), reps=3, warm=1)
             say("  gs_knn_search, k = %-2d            " % kk + fmt % full + "   query pass = %.1f us: %.3g candidates / s   (3 calls)"
                 % (full[0] - kbuild[0], kinfo["candidates"] / ((full[0] - kbuild[0]) * 1e-6)))
+    if a.search_only:
+        r.destroy()
+        return
     if krate < 0.25 * crate:
         say("  BELOW a quarter of the count's rate.  What bounds it: k = 1 keeps one slot and hardly inserts, so a k = 1 rate near the count's")
         say("  puts the loss on the LDS insertions and rescans; a k = 1 rate as low puts it on the gather of the per-lane walk")
