@@ -20,7 +20,7 @@ FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-ffp-contract=off", "-f
 FILE_FLAGS = {}  # per-file flags (none at present)
 SOURCES = ["k_preprocess.hip", "k_binning.hip", "k_gsort.hip", "k_rows.hip", "k_sort.hip", "k_blend.hip", "k_pick.hip", "k_state.hip", "k_export.hip", "k_insert.hip", "k_snapshot.hip", "k_xform.hip", "k_grade.hip", "k_coverage.hip", "k_attr.hip", "k_neigh.hip", "k_cluster.hip", "k_knn.hip", "k_pack.hip",
            "gs_context.hip", "gs_frame.hip", "gs_readback.hip", "gs_state.hip", "gs_export.hip", "gs_insert.hip", "gs_snapshot.hip", "gs_xform.hip", "gs_xform_math.hip", "gs_grade.hip", "gs_grade_math.hip", "gs_coverage.hip", "gs_attr.hip", "gs_neigh.hip", "gs_cluster.hip", "gs_knn.hip", "gs_pack.hip", "gs_pack_host.hip", "gs_ply.hip", "gs_stages.hip",
-           "k_moments.hip", "gs_moments.hip", "k_pairs.hip", "gs_pairs.hip", "k_consensus.hip", "gs_consensus.hip", "k_merge.hip", "gs_merge.hip", "k_surface.hip", "gs_surface.hip", "k_plane_pairs.hip", "gs_plane_pairs.hip"]  # (new sources go last: the code objects before them load where they did)
+           "k_moments.hip", "gs_moments.hip", "k_pairs.hip", "gs_pairs.hip", "k_consensus.hip", "gs_consensus.hip", "k_merge.hip", "gs_merge.hip", "k_surface.hip", "gs_surface.hip", "k_plane_pairs.hip", "gs_plane_pairs.hip", "k_thin.hip", "gs_thin.hip"]  # (new sources go last: the code objects before them load where they did)
 
 
 def _stale(target, deps):
@@ -36,7 +36,7 @@ def build(force=False, verbose=False, profiling=False):
     os.makedirs(OUT, exist_ok=True)
     objdir = os.path.join(OUT, "obj_prof" if profiling else "obj")
     os.makedirs(objdir, exist_ok=True)
-    headers = [os.path.join(HERE, h) for h in ("gs_device.h", "gs_binning.h", "gs_kernels.h", "gs_tight.h", "gs_runtime.h", "gs_xform_math.h", "gs_grade_math.h", "gs_state_sum.h", "gs_neigh_dev.h", "gs_pack_math.h", "gs_exact_sum.h", "gs_exact_dev.h", "gs_pair_host.h", "gs_plane_pair_host.h", "gs_pack_host.h", "gs_file_writer.h", "gs_consensus_host.h", "gs_merge_math.h", "gs_grid_math.h", "gs_surface_math.h", "gs_neigh_host.h")] + [
+    headers = [os.path.join(HERE, h) for h in ("gs_device.h", "gs_binning.h", "gs_kernels.h", "gs_tight.h", "gs_runtime.h", "gs_xform_math.h", "gs_grade_math.h", "gs_state_sum.h", "gs_neigh_dev.h", "gs_pack_math.h", "gs_exact_sum.h", "gs_exact_dev.h", "gs_pair_host.h", "gs_plane_pair_host.h", "gs_pack_host.h", "gs_file_writer.h", "gs_consensus_host.h", "gs_merge_math.h", "gs_grid_math.h", "gs_surface_math.h", "gs_neigh_host.h", "gs_thin_math.h")] + [
         os.path.join(HERE, "..", "..", "include", "gsplat", "gs_abi.h")]
 
     def compile_one(src):

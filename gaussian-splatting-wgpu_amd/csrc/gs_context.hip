@@ -185,6 +185,7 @@ static int32_t alloc_per_gaussian(gs_ctx* c, uint64_t n, uint64_t min_capacity =
     c->cl = gs_ctx::Cluster{}; // ... and the cluster planes: they read "no label, size 0" again
     c->kn = gs_ctx::Knn{}; // ... and the nearest-neighbour planes: NaN / GS_KNN_NONE again, and no k to refine
     c->sf = gs_ctx::Surface{}; // ... and the surface planes and kept sums: NaN / count 0 again, no sums to read
+    c->th = gs_ctx::Thin{}; // ... and the thinning planes: GS_THIN_NONE / 0 again
     c->counts.reset(); c->offsets.reset(); c->grec.reset(); c->rowptr.reset(); c->gsort_scratch.reset(); c->gdata.reset(); c->gdataG.reset();
     c->unit_off.reset(); c->unit_n.reset();
     const size_t np = ((size_t)n + 63) & ~(size_t)63;

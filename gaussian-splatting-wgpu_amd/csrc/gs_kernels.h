@@ -213,6 +213,25 @@ void gs_launch_cluster_commit(const uint32_t* parent, const uint32_t* count, uin
 void gs_launch_cluster_seeds(const uint8_t* state, const uint32_t* labels, uint32_t n, uint32_t mask, uint32_t value, uint32_t* flag, hipStream_t st);
 void gs_launch_state_cluster_linked(uint8_t* state, const uint32_t* labels, uint32_t n, const uint32_t* flag, uint32_t op, uint32_t bits, uint32_t where_mask,
                                     uint32_t where_value, unsigned long long* matched, hipStream_t st);
+// k_thin.hip: thinning (gs_thin.hip) over the neighbourhoods' grid, records and slices.  rank (u64) and status (u32) are indexed by SORTED
+// POSITION, beside the record; the work planes keeper / covers by splat index.
+// keeper / covers of every splat: {i, 1} for a member with a non-finite coordinate (it has no record), else {GS_THIN_NONE, 0}
+void gs_launch_thin_init(const uint8_t* state, const GsScene& s, uint32_t n, uint32_t mask, uint32_t value, uint32_t* keeper, uint32_t* covers,
+                         hipStream_t st);
+// rank[t] of the member at sorted position t (prio: the priority values f32[n] by splat index, or null), status[t] = 0 (undecided)
+void gs_launch_thin_rank(const void* rec, uint32_t nrec, uint32_t n, const float* prio, uint32_t flags, uint32_t seed, unsigned long long* rank,
+                         uint32_t* status, hipStream_t st);
+// one round over workgroups [first_block, first_block + blocks) of 256 sorted members (v.src's records are queries and sources alike:
+// v.qrec is not read); round: 1, 2, ... (the stamp of its decisions); *undecided += the members it leaves undecided
+void gs_launch_thin_round(const NeighView& v, uint32_t first_block, uint32_t blocks, float r2, uint32_t round, const unsigned long long* rank, uint32_t* status,
+                          uint32_t* undecided, hipStream_t st);
+// after the last round: keeper[id] of every sorted member, covers[keeper] += 1
+void gs_launch_thin_assign(const NeighView& v, uint32_t first_block, uint32_t blocks, float r2, uint32_t n, const unsigned long long* rank,
+                           const uint32_t* status, uint32_t* keeper, uint32_t* covers, hipStream_t st);
+// the two planes from the work planes; slots: the GS_STATE_SLOTS partial records (zeroed by the caller), word 0 += kept, word 1 =
+// max(word 1, largest covers)
+void gs_launch_thin_commit(const uint32_t* wkeeper, const uint32_t* wcovers, uint32_t n, uint32_t* keeper, uint32_t* covers, unsigned long long* slots,
+                           hipStream_t st);
 // k_knn.hip: nearest neighbours (gs_knn.hip) over the neighbourhoods' grid, records and slices.
 // a whole search's start: dist2[i] = +inf for a splat that passes (mask, value) (state null: every splat), NaN 0x7FC00000 for the
 // others; nearest[i] = GS_KNN_NONE

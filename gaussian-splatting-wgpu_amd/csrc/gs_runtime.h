@@ -234,6 +234,10 @@ struct gs_ctx {
     // allocated (NaN 0x7FC00000 / GS_KNN_NONE) on first use and dropped with the scene like the count plane; k: that of the last
     // search without GS_KNN_REFINE (0: none yet), which a refinement must repeat.  A search works in ng's scratch.
     struct Knn { DevBuf<uint32_t> dist2, nearest; uint32_t k = 0; } kn;
+    // thinning (gs_thin.hip): the keeper and covers planes u32[N], allocated (keeper = GS_THIN_NONE, covers = 0) on first use and
+    // dropped with the scene like the count plane; rank: the u64 per sorted member of a sample, grown on demand and dropped with them.
+    // A sample works in ng's scratch beside it and commits into the planes at its end.
+    struct Thin { DevBuf<uint32_t> keeper, covers; Scratch<unsigned long long> rank; } th;
     // surface (gs_surface.hip): two 16-byte records per splat, {nx, ny, nz, count} and {l0, l1, l2, 0}, allocated (NaN 0x7FC00000 /
     // count 0) on first use and dropped with the scene like the nearest-neighbour planes; sums: the ten i64 per splat of the last
     // estimate with GS_SURFACE_KEEP_SUMS (have_sums: they are that estimate's), dropped with the planes; the slice's sums of an
@@ -376,6 +380,8 @@ inline int32_t private_sort_fault(gs_ctx* c, uint32_t* fault) {
 int32_t cluster_planes(gs_ctx* c, hipStream_t st);
 // gs_knn.hip: the nearest-neighbour planes of `c`, allocated and set to their initial reading (on `st`) by the first call that needs them
 int32_t knn_planes(gs_ctx* c, hipStream_t st);
+// gs_thin.hip: the keeper and covers planes of `c`, allocated and set to their initial reading (on `st`) by the first call that needs them
+int32_t thin_planes(gs_ctx* c, hipStream_t st);
 // gs_surface.hip: the surface planes of `c`, allocated and set to their initial reading (on `st`) by the first call that needs them
 int32_t surface_planes(gs_ctx* c, hipStream_t st);
 // gs_export.hip: the splat edits' selection: counts the splats with (s & mask) == value and, with want_ids, leaves their indices,

@@ -234,6 +234,16 @@ GS_EXPORT int32_t gs_state_cluster(gs_ctx* c, uint32_t min_size, uint32_t max_si
     }, matched);
 }
 
+// Select by covers: gs_state_neigh's pass over the covers plane (gs_thin.hip).  Kept: [1, 2^32 - 1]; dropped: [0, 0] under the member filter.
+GS_EXPORT int32_t gs_state_thin(gs_ctx* c, uint32_t min_covers, uint32_t max_covers, uint32_t inside, uint32_t where_mask, uint32_t where_value, uint32_t op,
+                                uint32_t bits, uint64_t* matched) {
+    const int32_t rc = plane_select_begin(c, "gs_state_thin", op, bits, where_mask, thin_planes);
+    if (rc != GS_OK) return rc;
+    return state_counted(c, [&](unsigned long long* slots) {
+        gs_launch_state_neigh(plane(c), c->th.covers, c->n, min_covers, max_covers, inside, op, bits, where_mask, where_value, slots, c->stream);
+    }, matched);
+}
+
 // Select the clusters that hold a seed: every seed sets the flag word of its label (n zeroed words of the neighbourhoods' scratch),
 // then the state pass over the label plane reads the flag of every splat's label.
 GS_EXPORT int32_t gs_state_cluster_linked(gs_ctx* c, uint32_t seed_mask, uint32_t seed_value, uint32_t where_mask, uint32_t where_value, uint32_t op,

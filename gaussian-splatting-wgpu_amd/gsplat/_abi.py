@@ -87,6 +87,12 @@ GS_NEIGH_LIMIT_NONE = 0xFFFFFFFF  # gs_neigh.limit: count every neighbour
 GS_CLUSTER_NONE = 0xFFFFFFFF  # the label of a splat that is no member
 GS_CLUSTER_MAX_ROUNDS = 64
 
+# thinning
+GS_THIN_NONE = 0xFFFFFFFF         # the keeper of a splat that is no member
+GS_THIN_NO_PRIORITY = 0xFFFFFFFF  # gs_thin.priority.kind: no priority attribute
+GS_THIN_ORDER_INDEX, GS_THIN_ASCENDING = 0x1, 0x2  # gs_thin.flags
+GS_THIN_DEFAULT_ROUNDS = 64
+
 # nearest neighbours
 GS_KNN_MAX_K = 32
 GS_KNN_NONE = 0xFFFFFFFF  # nearest of a splat without an accepted source (and of a splat that was no query)
@@ -117,6 +123,7 @@ ABI_SYMBOLS = ("gs_last_error", "gs_abi_version", "gs_create", "gs_destroy", "gs
                "gs_neigh_count", "gs_neigh_read", "gs_state_neigh",
                "gs_cluster_label", "gs_cluster_read", "gs_state_cluster", "gs_state_cluster_linked",
                "gs_knn_search", "gs_knn_read", "gs_state_knn",
+               "gs_thin_sample", "gs_thin_read", "gs_state_thin", "gs_thin_host",
                "gs_pair_moments", "gs_pair_moments_host", "gs_pair_plane_moments", "gs_pair_plane_moments_host",
                "gs_attr_consensus", "gs_consensus_host", "gs_attr_gather", "gs_planes_through",
                "gs_cell_merge", "gs_cell_merge_device", "gs_cell_merge_host",
@@ -227,6 +234,18 @@ class GsCluster(ctypes.Structure):
 class GsClusterInfo(ctypes.Structure):
     _fields_ = [("members", ctypes.c_uint64), ("clusters", ctypes.c_uint64), ("largest", ctypes.c_uint64), ("candidates", ctypes.c_uint64),
                 ("rounds", ctypes.c_uint32), ("cells", ctypes.c_uint32 * 3), ("cell_edge", ctypes.c_float), ("reserved", ctypes.c_uint32)]
+
+
+class GsThin(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("radius", ctypes.c_float), ("mask", ctypes.c_uint32), ("value", ctypes.c_uint32),
+                ("flags", ctypes.c_uint32), ("seed", ctypes.c_uint32), ("max_rounds", ctypes.c_uint32), ("reserved0", ctypes.c_uint32),
+                ("max_candidates", ctypes.c_uint64), ("priority", GsAttr), ("reserved", ctypes.c_uint32 * 2)]
+
+
+class GsThinInfo(ctypes.Structure):
+    _fields_ = [("members", ctypes.c_uint64), ("kept", ctypes.c_uint64), ("dropped", ctypes.c_uint64), ("largest", ctypes.c_uint64),
+                ("candidates", ctypes.c_uint64), ("rounds", ctypes.c_uint32), ("cells", ctypes.c_uint32 * 3), ("cell_edge", ctypes.c_float),
+                ("reserved", ctypes.c_uint32)]
 
 
 class GsKnn(ctypes.Structure):
@@ -373,6 +392,10 @@ def load():
     L.gs_cluster_read.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64)]
     L.gs_state_cluster.argtypes = [vp, u32, u32, u32, u32, u32, u32, u32, ctypes.POINTER(u64)]
     L.gs_state_cluster_linked.argtypes = [vp, u32, u32, u32, u32, u32, u32, ctypes.POINTER(u64)]
+    L.gs_thin_sample.argtypes = [vp, ctypes.POINTER(GsThin), ctypes.POINTER(GsThinInfo)]
+    L.gs_thin_read.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64)]
+    L.gs_state_thin.argtypes = [vp, u32, u32, u32, u32, u32, u32, u32, ctypes.POINTER(u64)]
+    L.gs_thin_host.argtypes = [vp, vp, vp, u64, vp, vp, ctypes.POINTER(GsThin), vp, vp, ctypes.POINTER(GsThinInfo)]
     L.gs_knn_search.argtypes = [vp, ctypes.POINTER(GsKnn), ctypes.POINTER(GsKnnInfo)]
     L.gs_knn_read.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64)]
     L.gs_state_knn.argtypes = [vp, f32, f32, u32, u32, u32, u32, u32, ctypes.POINTER(u64)]

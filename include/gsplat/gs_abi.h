@@ -1326,6 +1326,110 @@ int32_t gs_state_surface(gs_ctx* ctx, const gs_surface_range* r, uint32_t where_
 int32_t gs_surface_host(const float* pos, const uint8_t* state, uint64_t n, const gs_surface* q, float* normal, float* eig, uint32_t* count,
                         int64_t* sums, gs_surface_info* info);
 
+/* ---- thinning: a blue-noise subsample of resident splats by rank and radius ----------------------------------
+ * A count, a labelling and a cell merge cannot say "keep a subset such that no two kept splats are within a radius of each other,
+ * every dropped splat has a kept one within that radius, and where two compete the more important one survives": a Poisson-disk
+ * sample, the maximal independent set of the "within r" graph visited in priority order.  It decimates with REAL splats (the cell
+ * merge blurs), spaces query sets for a registration evenly, collapses near-duplicates with a rule about who survives, and hands
+ * out a partition for free: every dropped splat names the kept one that stands for it.  On the device, with the neighbourhoods'
+ * grid, distance expression, work budget and slices.
+ * MEMBERS, LINKS AND RANK.  MEMBERS are the splats i with (s_i & mask) == value (gs_state_count's filter).  Two members i != j are
+ * LINKED when
+ *     d2(i, j) <= r2;   d = p_j - p_i per component;  d2 = (dx dx + dy dy) + dz dz;  r2 = radius * radius
+ * -- the neighbourhoods' expression with nothing changed: one f32 rounding per written operation, no contraction, r2 ONE f32
+ * product, the comparison <= INCLUSIVE.  A member with a NaN or infinite coordinate is linked to nobody.  RANK is a 64-bit integer
+ *     R_i = (P_i << 32) | H_i;   member j OUTRANKS member i when R_j > R_i, or when R_j == R_i and j < i.
+ * P_i is 0 without a priority attribute.  With one -- a gs_attr evaluated exactly as gs_attr_read would -- P_i is the splat
+ * attributes' order-preserving key of the value's bit pattern b, k = b ^ (b >> 31 ? 0xFFFFFFFF : 0x80000000); with GS_THIN_ASCENDING
+ * P_i = ~k instead, so smaller values win.  A NaN value has P_i = 0 in both directions: missing data never wins.  H_i by default is
+ * this hash of the index, all arithmetic mod 2^32:
+ *     h = i + seed * 0x9E3779B9;  h ^= h >> 16;  h *= 0x7FEB352D;  h ^= h >> 15;  h *= 0x846CA68B;  h ^= h >> 16;  H_i = h
+ * -- every step invertible, so a bijection of i for a fixed seed, and R a total order by itself.  With GS_THIN_ORDER_INDEX
+ * H_i = ~i: the lower index wins among equal priorities.
+ * KEPT, KEEPER AND COVERS.  KEPT is the unique set obtained by visiting the members from the highest rank down: a member is kept
+ * iff no member kept before it is linked to it (the lexicographically first maximal independent set).  Equivalently the unique
+ * fixpoint of: a member is kept iff every linked member that outranks it is dropped; a member is dropped iff some linked member
+ * that outranks it is kept.  For every resident splat i, two u32 planes:
+ *     kept member:                          keeper[i] = i,   covers[i] = the members m with keeper[m] == i, itself included (>= 1)
+ *     dropped member:                       keeper[i] = of the kept members linked to it the one that outranks all the others
+ *                                           (there is one, by maximality),   covers[i] = 0
+ *     member with a non-finite coordinate:  keeper[i] = i (linked to nobody, hence kept),   covers[i] = 1
+ *     non-member:                           keeper[i] = GS_THIN_NONE,   covers[i] = 0
+ * The sum of covers is the number of members.  Both planes are integers and functions of the positions, the state bytes, the
+ * radius, the priority values, the flags and the seed only: two runs, a slab ctx, a borrower of gs_share_splats, a fresh ctx, the
+ * host twin and a brute-force restatement agree bit for bit.  radius = 0 (or one whose square is 0) collapses exact duplicates.
+ * THE PLANES belong to the ctx the call is made on, are allocated by the first call that needs them, read GS_THIN_NONE / 0 before
+ * the first sample and are DROPPED -- they read so again -- by exactly what drops the count plane: every gs_upload_*,
+ * gs_share_splats and gs_compact.  Nothing else drops them: they describe the positions, states and priorities at the time of the
+ * sample.  A call that fails for any reason -- budget, allocation, the round cap, a refused argument -- leaves both as they were.
+ * WORK.  A sample builds the neighbourhoods' grid over the members, writes R once, then runs ROUNDS of one query pass over the
+ * candidates: an undecided member that finds a linked, outranking member KEPT in an earlier round becomes DROPPED; one that finds no
+ * linked, outranking member still undecided becomes KEPT; the others wait.  Every round decides at least the highest-ranked
+ * undecided member, so the rounds end; `rounds` is a function of the inputs too (a round reads the decisions of earlier rounds only).
+ * One more query pass over the dropped members names their keepers and counts the covers.  max_candidates (0:
+ * GS_NEIGH_DEFAULT_CANDIDATES) is the budget of ONE round, as for clusters; every pass is issued in the count's slices.  THE ROUND
+ * CAP: more rounds than max_rounds (0: GS_THIN_DEFAULT_ROUNDS) is GS_ERR_CAPACITY with the rounds run and the members still
+ * undecided in the message.  It can be hit by legitimate input: the rounds needed are the longest chain of linked members in
+ * descending rank.  With the hash order that is O(log N) with high probability (15 rounds at 6.1 M splats and about 10 links per
+ * splat); with GS_THIN_ORDER_INDEX, or a priority that is constant along a spatially sorted index order, it is as long as the
+ * geometry makes it (a line of 2000 points in index order: 2000 rounds).  The default is what the hash order was seen to need at
+ * 6.1 M splats times a margin (profiles/thin.txt); the cap keeps a chain-like input from costing thousands of passes unasked, and a
+ * caller who wants such an order raises it.
+ * Prologue, ordering, borrowers, slabs, N == 0 and refusals are the clusters': the filter as gs_state_count, above 0xFF refused,
+ * (0, 0) accepted on a ctx without GS_FLAG_SPLAT_STATE, any other filter on such a ctx refused; every call first completes all
+ * frames enqueued on the ctx's ring, runs on the ctx's stream and returns when done; none is a frame or an upload.
+ * GS_ERR_NO_SCENE before any upload; N == 0: zero results, GS_OK.  gs_thin_sample and gs_thin_read work on a borrower; gs_state_thin needs
+ * GS_FLAG_SPLAT_STATE and has gs_state_region's rules.  GS_ERR_INVALID_ARGUMENT and a message that names the number: a wrong
+ * struct_size, a radius that is negative or not finite or whose square is not finite in f32, unknown flag bits, GS_THIN_ASCENDING
+ * without a priority, a priority that gs_attr_read would refuse, a reserved word that is not 0. */
+#define GS_THIN_NONE 0xFFFFFFFFu
+#define GS_THIN_NO_PRIORITY 0xFFFFFFFFu /* gs_thin.priority.kind: no priority attribute, P_i = 0 */
+#define GS_THIN_ORDER_INDEX 0x1u        /* gs_thin.flags: H_i = ~i */
+#define GS_THIN_ASCENDING 0x2u          /* gs_thin.flags: P_i = ~k, smaller priority values win; needs a priority */
+#define GS_THIN_DEFAULT_ROUNDS 64u      /* the hash order at 6.1 M splats, 15 rounds, times 4 (profiles/thin.txt) */
+typedef struct gs_thin {           /* 72 bytes */
+    uint32_t struct_size;          /* = sizeof(gs_thin) */
+    float    radius;               /* finite, >= 0; r2 = radius * radius must be finite in f32 */
+    uint32_t mask, value;          /* MEMBERS: splats i with (s_i & mask) == value */
+    uint32_t flags;                /* GS_THIN_ORDER_INDEX | GS_THIN_ASCENDING */
+    uint32_t seed;                 /* of the hash order */
+    uint32_t max_rounds;           /* 0 = GS_THIN_DEFAULT_ROUNDS */
+    uint32_t reserved0;            /* 0 */
+    uint64_t max_candidates;       /* work budget PER ROUND, 0 = GS_NEIGH_DEFAULT_CANDIDATES */
+    gs_attr  priority;             /* kind == GS_THIN_NO_PRIORITY: none (the rest of it is not read) */
+    uint32_t reserved[2];          /* 0 */
+} gs_thin;
+typedef struct gs_thin_info {      /* 64 bytes */
+    uint64_t members;              /* splats that pass the filter */
+    uint64_t kept;                 /* members with keeper[i] == i */
+    uint64_t dropped;              /* members - kept */
+    uint64_t largest;              /* the maximum of covers */
+    uint64_t candidates;           /* distance tests of a whole pass: the members in the 27 cells around every member, self included */
+    uint32_t rounds;               /* round passes that were run */
+    uint32_t cells[3]; float cell_edge; /* the grid that was used (diagnostic; no result depends on it) */
+    uint32_t reserved;
+} gs_thin_info;
+/* Samples into the two planes.  info (may be NULL) is written whenever the grid was built, also when the budget refuses the call
+ * (members, candidates and the grid; kept, dropped, largest and rounds are those of a completed sample). */
+int32_t gs_thin_sample(gs_ctx* ctx, const gs_thin* q, gs_thin_info* info);
+/* The planes in HOST memory, N words each in splat order, with gs_cluster_read's conventions: keeper and covers may each be NULL,
+ * both NULL: only *n (= N) is written (query); cap < N: GS_ERR_INVALID_ARGUMENT, the message names the count needed, nothing is
+ * written. */
+int32_t gs_thin_read(gs_ctx* ctx, uint32_t* keeper, uint32_t* covers, uint64_t cap, uint64_t* n);
+/* Applies `op` with `bits` exactly as gs_state_region does, to the splats that pass (s & where_mask) == where_value and for which
+ *     (covers >= min_covers && covers <= max_covers) == (inside != 0)
+ * -- the plain expression on the plane value: gs_state_cluster's pass over the covers plane.  "Kept" is [1, 2^32 - 1]; "dropped" is
+ * [0, 0] under where = the member filter (a non-member reads 0 too).  *matched (may be NULL) as for gs_state_region. */
+int32_t gs_state_thin(gs_ctx* ctx, uint32_t min_covers, uint32_t max_covers, uint32_t inside, uint32_t where_mask, uint32_t where_value,
+                      uint32_t op, uint32_t bits, uint64_t* matched);
+/* The same sample without a ctx or a GPU, by another algorithm (the members sorted by rank, a sequential greedy over a hashed grid
+ * of the kept ones -- not the rounds): px, py, pz f32[n], state u8[n] (NULL: every state byte is 0), priority f32[n] the priority
+ * VALUES (NULL: none; q->priority is not read), keeper and covers u32[n], info (may be NULL; rounds = 0, candidates = the distance
+ * tests made, cells = 1 1 1, cell_edge = 0).  The refusals are gs_thin_sample's, with GS_THIN_ASCENDING refused when priority is NULL, a
+ * filter above 0xFF and a null array with n > 0 included; n >= 2^32 is refused. */
+int32_t gs_thin_host(const float* px, const float* py, const float* pz, uint64_t n, const uint8_t* state, const float* priority,
+                     const gs_thin* q, uint32_t* keeper, uint32_t* covers, gs_thin_info* info);
+
 /* Tuning / profiling knobs. */
 #define GS_OPT_BLEND_ABLATION 1  /* bit 3 (8): the workgroup-per-tile blend kernel at tiles 16 and 32 (identical results; default = one
                                     wave per 8x8 pixel block); bit 2 (4): every blend kernel without its two parking culls (live box,
